@@ -3,6 +3,8 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on rank 0.
 For N > 1 the driver launches it with torch.distributed.run (one rank per GPU, RCCL).
+``--dump-outputs DIR`` also writes the volume the timed steps built as .npy files (dump_outputs), so that two builds can be
+compared output for output: with the same arguments the input frames are the same on every run.
 
 Workload (BASELINE.json configs[1]): synthetic 640x480 RGB-D stream (30 Hz camera on a 600-pose loop), 5 mm
 voxels, sdf_trunc 0.04 m, depth_trunc 4 m, Open3D ScalableTSDFVolume semantics.  A *step* fuses one batch of
@@ -74,13 +76,23 @@ PROFILE_ROUND = "r06"
 PMC_SUMMARY = os.path.join(ROOT, "profiles", PROFILE_ROUND, "pmc_summary.json")
 
 
+def frame_cache_path(name):
+    """/tmp/pyslam_amd_bench_<digest>_<name>.npz: the digest is that of the frame generator's source, so a cache written by
+    another version of pyslam_amd/synthetic.py (another checkout, another user of the box) is never read as this one's input."""
+    import hashlib
+
+    with open(os.path.join(ROOT, "pyslam_amd", "synthetic.py"), "rb") as f:
+        digest = hashlib.sha256(f.read()).hexdigest()[:16]
+    return f"/tmp/pyslam_amd_bench_{digest}_{name}.npz"
+
+
 def load_frames(config, n_frames, start=0, rank=0, barrier=None):
     """Synthetic frames, cached under /tmp (generation is host-side numpy ray casting, spread over the host cores).
     With several ranks on the node rank 0 renders, the others wait and read the cache."""
     from pyslam_amd.synthetic import SyntheticRGBD
 
     s = SyntheticRGBD(config)
-    cache = f"/tmp/pyslam_amd_bench_{config}_{start}_{n_frames}.npz"
+    cache = frame_cache_path(f"{config}_{start}_{n_frames}")
     if not os.path.exists(cache) and rank == 0:
         depth, rgb, T = s.batch(start, n_frames)
         try:
@@ -93,8 +105,48 @@ def load_frames(config, n_frames, start=0, rank=0, barrier=None):
             raise
     if barrier is not None:
         barrier()
-    z = np.load(cache)
-    return s, z["depth"], z["rgb"], z["T"]
+    try:
+        z = np.load(cache)
+        return s, z["depth"], z["rgb"], z["T"]
+    except Exception:  # unreadable (another user's file) or damaged: render the same frames here
+        return (s,) + tuple(s.batch(start, n_frames))
+
+
+DUMP_SAMPLE_UNITS = 512  # units whose voxels --dump-outputs writes: 512 x 4096 voxels x 20 B = 40 MB
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20260
+
+
+def dump_outputs(vol, out_dir):
+    """--dump-outputs: the state the timed steps left in the volume, which is what a caller of integrate_batch reads back.
+      unit_keys.npy             [U, 3] float64  every allocated unit, sorted lexicographically
+      sample_keys.npy           [K, 3] float64  a fixed sample of them: the K units with the smallest seeded hash of the key
+                                                (K = min(U, DUMP_SAMPLE_UNITS); chosen by key, not by position, so one extra
+                                                unit in one build leaves the rest of the sample unchanged), sorted
+      sample_tsdf_x_weight.npy  [K, 4096] float32 \\
+      sample_weight.npy         [K, 4096] float32  > export_numerators() of the sampled units (voxel order z*R^2 + x*R + y)
+      sample_color_sum.npy      [K, 4096, 3] float32 /
+    -> total bytes written."""
+    import torch
+
+    keys = vol.unit_keys()
+    keys = keys[np.lexsort(keys.T[::-1])]
+    salt = np.random.default_rng(DUMP_SEED).integers(1, 1 << 31, size=3)
+    h = (keys.astype(np.int64) * salt).sum(axis=1) % 2147483647
+    sample = np.ascontiguousarray(keys[np.sort(np.argsort(h, kind="stable")[:DUMP_SAMPLE_UNITS])])
+    payload = torch.empty((len(sample), vol.res ** 3, 5), dtype=torch.float32, device="cuda")
+    torch.cuda.current_stream().synchronize()
+    vol.export_numerators(sample, out=payload)
+    p = payload.cpu().numpy()
+    arrays = {"unit_keys": keys.astype(np.float64), "sample_keys": sample.astype(np.float64), "sample_tsdf_x_weight": p[..., 0],
+              "sample_weight": p[..., 1], "sample_color_sum": p[..., 2:5]}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte budget")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    return total
 
 
 def d2d_copy_gbs(n_bytes=1 << 30, reps=6):
@@ -553,7 +605,12 @@ def main():
                          "tile = image tiles + RCCL merge of the shared units at the end")
     ap.add_argument("--mode", choices=["batch", "online"], default="batch",
                     help="batch: one multi-frame sweep per step (replay/rebuild path); online: one integrate() per frame")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the volume they built (unit keys + a fixed sample of units' voxels, see "
+                         "dump_outputs) as DIR/<name>.npy; N > 1: every rank its own units under DIR/rank<r>")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -667,6 +724,9 @@ def main():
     launch_ms = vol.profile_launches()
     vol.profile_read()
     vol.profile_enable(False)
+    dumped = None
+    if args.dump_outputs:
+        dumped = {"dir": args.dump_outputs, "bytes": dump_outputs(vol, args.dump_outputs if world == 1 else os.path.join(args.dump_outputs, f"rank{rank}"))}
     per_rank = None
     if dist is not None:
         # every rank's own clock, its mean sweep launch (HIP events) and the units it holds: how to read the first real N-GPU run
@@ -1007,6 +1067,8 @@ def main():
                                          f"untimed clock-ramp steps: a fresh process on idle clocks (value above: after the ramp)"}
         if per_rank is not None:
             out["per_rank"] = per_rank
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if cpu is not None and world == 1:
             out["speedup_vs_cpu"] = round(fps / cpu["fps"], 1)
         if merge is not None:

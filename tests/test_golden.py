@@ -1,6 +1,6 @@
 """CPU: the C restatement (oracle/voxel_oracle.c) against the committed golden vectors that
 tools/make_golden.py generated from the *compiled reference* (oracle/_ref).  These fixtures travel
-to the GPU box, where /root/reference does not exist; the GPU tests use the same oracle."""
+to the GPU box, where the reference sources do not exist; the GPU tests use the same oracle."""
 import os
 
 import numpy as np
@@ -125,20 +125,16 @@ def test_host_prep_matches_reference_depth_fixture():
     assert (z["shadow_mad"] == -1).sum() > 0 and (z["shadow_fixed"] != z["depth"]).sum() > 0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/pyslam/utilities/depth.py"), reason="reference tree not present (GPU box)")
 def test_host_prep_matches_imported_reference():
-    """Dev container: the reference file itself as the oracle (it needs nothing but numpy), on fresh random inputs."""
-    from tools.make_golden_prep import load_reference_depth
+    """The reference file itself as the oracle (it needs nothing but numpy) on seeded random inputs: its outputs were recorded
+    by tools/make_golden_prep.py in tests/golden/prep_depth_random.npz."""
+    from tools.make_golden_prep import SHADOW_KWARGS
 
-    ref = load_reference_depth()
-    rng = np.random.default_rng(11)
-    for _ in range(3):
-        depth = (0.3 + 3.0 * rng.random((37, 53))).astype(np.float32)
-        depth[rng.random(depth.shape) < 0.1] = 0.0
-        rgb = rng.integers(0, 255, (37, 53, 3)).astype(np.uint8)
-        pc = ref.depth2pointcloud(depth, rgb, 60.0, 61.0, 26.0, 18.0, max_depth=3.0, min_depth=0.4)
+    z = load("prep_depth_random.npz")
+    for i in range(3):
+        depth, rgb = z[f"depth{i}"], z[f"rgb{i}"]
         pts, cols, _ = hp.depth2pointcloud(depth, rgb, 60.0, 61.0, 26.0, 18.0, 3.0, 0.4)
-        np.testing.assert_array_equal(pts, pc.points)
-        np.testing.assert_array_equal(cols, pc.colors)
-        for kw in ({}, {"delta_depth": 0.1, "delta_x": 1, "delta_y": 3, "fill_value": 0.0}):
-            np.testing.assert_array_equal(hp.filter_shadow_points(depth, **kw), ref.filter_shadow_points(depth, **kw))
+        np.testing.assert_array_equal(pts, z[f"points{i}"])
+        np.testing.assert_array_equal(cols, z[f"colors{i}"])
+        for j, kw in enumerate(SHADOW_KWARGS):
+            np.testing.assert_array_equal(hp.filter_shadow_points(depth, **kw), z[f"shadow{i}_{j}"])

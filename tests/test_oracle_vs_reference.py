@@ -1,5 +1,5 @@
-"""CPU, dev container only: the C restatement against the live compiled reference (oracle/_ref,
-built from /root/reference by oracle/Makefile) on larger seeded inputs than the golden fixtures."""
+"""CPU: the C restatement against the live compiled reference (oracle/_ref, built from the reference
+sources by oracle/Makefile) on larger seeded inputs than the golden fixtures."""
 import os
 
 import numpy as np
@@ -92,91 +92,35 @@ def test_reference_double_overload_keys_in_double():
     assert g32.dump()[0].shape != keys.shape or not np.array_equal(g32.dump()[2], counts)  # and NOT the float overload's result
 
 
-def _cpu_has_avx2():
-    try:
-        return "avx2" in open("/proc/cpuinfo").read()
-    except OSError:
-        return False
-
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/cpp/volumetric"), reason="needs the reference sources")
 def test_optimised_reference_build_against_the_portable_oracle_build():
     """The oracle is the reference compiled WITHOUT -march=native and with -ffp-contract=off (it has to give the same bits
-    on any host).  The reference's own CMake flags are -O3 -march=native with GCC's default contraction.  This test builds
-    that variant for THIS host (oracle/Makefile ref_native; never shipped, never the oracle) and measures the gap:
+    on any host).  The reference's own CMake flags are -O3 -march=native with GCC's default contraction.  That variant's outputs
+    (oracle/Makefile ref_native, built and recorded on the dev host by tools/make_golden_ref_native.py; never shipped, never the
+    oracle) are in tests/golden/ref_native_tiny.npz, stored as a patch on the portable build's outputs (decode() first checks that the
+    live portable build still gives exactly the bits they were recorded against); this test measures the gap to the portable build:
       * VoxelBlockGrid (pySLAM's default grid): keys and counts identical, position / colour sums within 1e-5 relative
         (bit-identical on the AVX2 + FMA host this was written on);
       * volumetric::VoxelGrid (direct hash, V16): with AVX2 the reference switches to a SIMD branch that sums four points per
         step (voxel_grid.h:42-46, voxel_grid_simd.hpp) - same voxels, positions within 2e-6 m, colours within 1e-6, under
         2 % of the values differ at all: two orders of magnitude inside the north star's 1e-4.
     The GPU path is bit-identical to the portable build (tests/test_gpu_voxel_grid.py)."""
-    import ctypes as C
-    import subprocess
+    from tools.make_golden_ref_native import clouds, decode, reference_outputs
 
-    from pyslam_amd.synthetic import SyntheticRGBD
-
-    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
-    lib_native = os.path.join(here, "_ref", "libref_volumetric_native.so")
-    if not os.path.exists(lib_native):
-        subprocess.check_call(["make", "-s", "-C", here, "-f", os.path.join(here, "Makefile"), "ref_native"])
     oracle.ref_lib()  # builds the portable variant if needed
-    vp, i64, i32, f32, f64 = C.c_void_p, C.c_int64, C.c_int32, C.c_float, C.c_double
-    s = SyntheticRGBD("tiny_160x120_2cm")
-    clouds = []
-    for i in range(6):
-        d, c, T = s[i]
-        pts, cols, _ = hp.frame_to_world_f32(d, c, *s.intrinsics, T, 4.0)
-        pts, cols = np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(cols, np.float32)
-        clouds.append((pts, cols, np.ascontiguousarray(np.clip(np.rint(cols * (255.0 if cols.max() <= 1.0 else 1.0)), 0, 255).astype(np.uint8))))
-    block, direct = [], []
-    for lib in (os.path.join(here, "_ref", "libref_volumetric.so"), lib_native):
-        L = C.CDLL(lib)
-        # default block grid, float32 and uint8 colours
-        L.ref_grid_create.restype = vp
-        L.ref_grid_create.argtypes = [f32, i32]
-        L.ref_grid_destroy.argtypes = [vp]
-        L.ref_grid_integrate.argtypes = [vp, vp, i64, vp, i32]
-        L.ref_grid_num_blocks.restype = i64
-        L.ref_grid_num_blocks.argtypes = [vp]
-        L.ref_grid_dump.restype = i64
-        L.ref_grid_dump.argtypes = [vp, vp, vp, vp, vp]
-        dumps = []
-        for kind in (2, 1):
-            h = L.ref_grid_create(0.02, 8)
-            for pts, cols, cols8 in clouds:
-                cc = cols if kind == 2 else cols8
-                L.ref_grid_integrate(h, pts.ctypes.data_as(vp), len(pts), cc.ctypes.data_as(vp), kind)
-            nb = L.ref_grid_num_blocks(h)
-            keys, hs = np.zeros((nb, 3), np.int32), np.zeros(nb, np.uint64)
-            cnt, sums = np.zeros((nb, 512), np.int32), np.zeros((nb, 512, 6), np.float32)
-            L.ref_grid_dump(h, keys.ctypes.data_as(vp), hs.ctypes.data_as(vp), cnt.ctypes.data_as(vp), sums.ctypes.data_as(vp))
-            L.ref_grid_destroy(h)
-            dumps.append((keys, cnt, sums))
-        block.append(dumps)
-        # direct voxel hash
-        L.ref_vgrid_create.restype = vp
-        L.ref_vgrid_create.argtypes = [f64]
-        L.ref_vgrid_destroy.argtypes = [vp]
-        L.ref_vgrid_integrate.argtypes = [vp, vp, i64, vp, i32]
-        L.ref_vgrid_get_voxels.restype = i64
-        L.ref_vgrid_get_voxels.argtypes = [vp, i32, f32, vp, vp, i64]
-        h = L.ref_vgrid_create(0.02)
-        for pts, cols, _ in clouds:
-            L.ref_vgrid_integrate(h, pts.ctypes.data_as(vp), len(pts), cols.ctypes.data_as(vp), 2)
-        n = L.ref_vgrid_get_voxels(h, 1, 0.0, None, None, 0)
-        P, Cc = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
-        L.ref_vgrid_get_voxels(h, 1, 0.0, P.ctypes.data_as(vp), Cc.ctypes.data_as(vp), n)
-        L.ref_vgrid_destroy(h)
-        order = np.lexsort(np.floor(P / 0.02).astype(np.int64).T[::-1])
-        direct.append((P[order], Cc[order]))
-    for (ka, ca, sa), (kb, cb, sb) in zip(*block):
+    here = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle")
+    port = reference_outputs(os.path.join(here, "_ref", "libref_volumetric.so"), clouds())
+    z = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_native_tiny.npz"))
+    native = decode(z, port)
+    for kind in (2, 1):
+        ka, ca, sa = (port[f"block{kind}_{x}"] for x in ("keys", "counts", "sums"))
+        kb, cb, sb = (native[f"block{kind}_{x}"] for x in ("keys", "counts", "sums"))
         np.testing.assert_array_equal(ka, kb)
         np.testing.assert_array_equal(ca, cb)
         np.testing.assert_allclose(sa, sb, rtol=1e-5, atol=1e-6)
-    (pa, ca), (pb, cb) = direct
+    (pa, ca), (pb, cb) = (port["direct_points"], port["direct_colors"]), (native["direct_points"], native["direct_colors"])
     assert pa.shape == pb.shape and len(pa) > 10_000
     assert float(np.abs(pa - pb).max()) <= 2e-6 and float(np.abs(ca - cb).max()) <= 1e-6
-    if _cpu_has_avx2():
+    if bool(z["avx2"]):
         assert float((pa.view(np.uint32) != pb.view(np.uint32)).mean()) < 0.02
 
 

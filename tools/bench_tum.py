@@ -25,15 +25,23 @@ def tum_frames(n_frames, start=0):
     """(stream, depth u16 [n,H,W], rgb u8 [n,H,W,3], T_cw [n,4,4]) rendered through the lens model, cached under /tmp."""
     from pyslam_amd.synthetic import SyntheticRGBD
 
+    from bench import frame_cache_path
+
     s = SyntheticRGBD(CONFIG, distorted=True, depth_dtype="uint16", depth_map_factor=DEPTH_FACTOR)
-    cache = f"/tmp/pyslam_amd_bench_{CONFIG}_distorted_u16_{start}_{n_frames}.npz"
+    cache = frame_cache_path(f"{CONFIG}_distorted_u16_{start}_{n_frames}")
     if not os.path.exists(cache):
         depth, rgb, T = s.batch(start, n_frames)
-        tmp = f"{cache}.{os.getpid()}.tmp.npz"
-        np.savez(tmp, depth=depth, rgb=rgb, T=T)
-        os.replace(tmp, cache)
-    z = np.load(cache)
-    return s, z["depth"], z["rgb"], z["T"]
+        try:
+            tmp = f"{cache}.{os.getpid()}.tmp.npz"
+            np.savez(tmp, depth=depth, rgb=rgb, T=T)
+            os.replace(tmp, cache)
+        except OSError:
+            return s, depth, rgb, T
+    try:
+        z = np.load(cache)
+        return s, z["depth"], z["rgb"], z["T"]
+    except Exception:  # unreadable (another user's file) or damaged: render the same frames here
+        return (s,) + tuple(s.batch(start, n_frames))
 
 
 def rectification(s):
