@@ -405,6 +405,39 @@ int hv_tsdf_extract_points_f32(hv_volume *v, float *points, float *colors, int64
  * (volumetric_integrator_tsdf.py:246-247).  normals f64 [N,3] in the order of hv_tsdf_extract_points; NULL to query *n. */
 int hv_tsdf_extract_point_normals(hv_volume *v, double *normals, int64_t cap, int64_t *n);
 
+/* Ray casting (KinectFusion's second TSDF operation; Open3D's tensor VoxelBlockGrid.ray_cast has one, the legacy
+ * ScalableTSDFVolume does not): what depth, world vertex, normal and colour the fused map predicts at pixel (u, v) of a pinhole
+ * camera intr = {fx, fy, cx, cy} at pose T_cw (row-major 4x4 double, as integrate).  This project's own contract, not Open3D-pinned:
+ *   ray       d_c = ((u - cx) / fx, (v - cy) / fy, 1) for integer u, v, so the ray parameter z IS camera z; in the world
+ *             o = T_wc * 0, d = R_wc * d_c (T_wc = inverse(T_cw)).  Everything below runs in float32 except the normal.
+ *   observed  a voxel with weight > weight_threshold.  Colour = sum / weight / 255.
+ *   nearest   the voxel floor(p / voxel_length), unit floor(voxel / 16); a missing unit is empty.
+ *   trilinear the 8 voxels around p - 0.5 voxel_length (hv_tsdf_at's cell), across units; valid only if all 8 are observed.
+ *   march     z from depth_min while z < depth_max, at most ceil(4 (depth_max - depth_min) / voxel_length) steps:
+ *               unit missing    z := max(exit of the unit's box, z) + HV_RAYCAST_UNIT_EPS * voxel_length; forget the previous sample
+ *               not observed    z += voxel_length; forget the previous sample
+ *               else            nearest f; previous observed sample f_prev > 0 and f <= 0: hit, bracket [z_prev, z] (front faces only)
+ *                               otherwise z += max(voxel_length, HV_RAYCAST_STEP_FRAC * f * sdf_trunc) for f > 0, voxel_length else
+ *   refine    HV_RAYCAST_REFINE_ITERS steps of regula falsi (Illinois) on the trilinear field.  The bracket [z_prev, z] of the
+ *             nearest field may miss the trilinear root by up to about a voxel, so each end first moves one voxel outwards
+ *             (max(z_prev - voxel_length, depth_min), min(z + voxel_length, depth_max)) where the trilinear sample there is valid and
+ *             of its sign (> 0 before, <= 0 behind); otherwise it stays, with its trilinear value if valid and of its sign, else
+ *             its nearest value.  A step whose trilinear sample is invalid ends the refinement.  z* = the last estimate.
+ *   hit       depth = z* * depth_scale; vertex = o + z* d (world); normal = GetNormalAt there (hv_tsdf_extract_point_normals' central
+ *             differences of the trilinear tsdf at +/- 0.99 voxel, double, normalised; world frame); colour in [0, 1] = trilinear
+ *             mean colour if valid, else the nearest voxel's (0 if it has no weight); mask = 1.
+ *   miss      every output 0, mask = 0.
+ * Outputs: depth [H,W] f32, vertex / normal / color [H,W,3] f32, mask [H,W] u8; any may be NULL (not computed).  loc = HV_DEVICE:
+ * device pointers, written asynchronously on the volume's stream; HV_HOST: staged by the library and copied back before returning.
+ * Reads only: no growth, reset or stamp; the extraction caches stay valid.  HV_ERR_MODE for a non-TSDF or owner-sharded volume
+ * (hv_tsdf_set_owner with world_size > 1: ray casting needs the whole volume), HV_ERR_INVALID for bad sizes or depth range. */
+#define HV_RAYCAST_STEP_FRAC 0.8f
+#define HV_RAYCAST_REFINE_ITERS 4
+#define HV_RAYCAST_UNIT_EPS 0.01f
+int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_min,
+                     double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
+                     float *color, uint8_t *mask, int32_t loc);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

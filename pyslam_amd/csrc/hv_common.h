@@ -457,6 +457,8 @@ struct hv_volume {
     void *out_b = nullptr;
     void *out_c = nullptr;
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
+    void *raycast_buf = nullptr; // HV_HOST outputs of hv_tsdf_ray_cast (apart from out_*: a cast leaves the extraction caches valid)
+    size_t raycast_buf_bytes = 0;
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)
     void *shadow_ring = nullptr;
     int shadow_ring_next = 0;

@@ -1079,6 +1079,43 @@ class ScalableTSDFVolume(_Volume):
                 L.check(self._lib.hv_tsdf_extract_point_normals(self._h, L.ptr(nrm), n.value, ctypes.byref(n)))
         return PointCloud(pts, cols, nrm)
 
+    RAY_CAST_ATTRIBUTES = ("depth", "vertex", "normal", "color", "mask")
+
+    def ray_cast(self, intrinsic, extrinsic, depth_min=0.1, depth_max=3.0, weight_threshold=3.0, depth_scale=1.0,
+                 render_attributes=RAY_CAST_ATTRIBUTES, device=False):
+        """What the fused map looks like from a pinhole camera at extrinsic = T_cw: a dict with the requested attributes,
+        depth [H,W] float32 (camera z * depth_scale, metres by default), vertex [H,W,3] float32 (world), normal [H,W,3] float32
+        (world, unit length), color [H,W,3] float32 in [0, 1], mask [H,W] bool (the ray hit a surface); 0 where it did not.
+        H, W = intrinsic.height, intrinsic.width.  Names and defaults follow Open3D's tensor VoxelBlockGrid.ray_cast; the
+        contract (include/hipvol.h, hv_tsdf_ray_cast) is this project's own.  Only the requested attributes are computed.
+        device=True: torch CUDA tensors on the volume's GPU, ordered before later work on torch's current stream."""
+        attrs = tuple(render_attributes)
+        bad = [a for a in attrs if a not in self.RAY_CAST_ATTRIBUTES]
+        if bad:
+            raise ValueError(f"ray_cast: unknown render attribute(s) {bad}; choose from {self.RAY_CAST_ATTRIBUTES}")
+        H, W = int(intrinsic.height), int(intrinsic.width)
+        shapes = {"depth": (H, W), "vertex": (H, W, 3), "normal": (H, W, 3), "color": (H, W, 3), "mask": (H, W)}
+        intr = intrinsic.as_array()
+        T = _as_f64_4x4(extrinsic)
+        out = {}
+        if device:
+            import torch
+
+            dev = torch.device("cuda", int(self._cfg.device))
+            for a in attrs:
+                out[a] = torch.empty(shapes[a], dtype=torch.bool if a == "mask" else torch.float32, device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
+        else:
+            for a in attrs:
+                out[a] = _result_array(shapes[a], np.bool_ if a == "mask" else np.float32)
+        p = {a: (L.ptr(out[a]) if a in out else None) for a in self.RAY_CAST_ATTRIBUTES}
+        L.check(self._lib.hv_tsdf_ray_cast(self._h, H, W, L.ptr(intr), L.ptr(T), float(depth_min), float(depth_max),
+                                           float(weight_threshold), float(depth_scale), p["depth"], p["vertex"], p["normal"],
+                                           p["color"], p["mask"], L.HV_DEVICE if device else L.HV_HOST))
+        if device:
+            self._torch_out(self._torch_stream(dev), dev)
+        return out
+
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
         """-> keys [U,3], tsdf [U,R^3] f32, weight [U,R^3] f32, color [U,R^3,3] f64 (0..255), key-sorted,
