@@ -44,6 +44,65 @@ def _as_f64_4x4(T):
     return T
 
 
+_UNSUPPORTED_IMAGE = "[ScalableTSDFVolume::Integrate] Unsupported image format."
+
+
+def _tsdf_operands(depth, color, intrinsic, frames=None):
+    """The depth / colour operands of ScalableTSDFVolume.integrate* in the layout the library reads from a bare pointer, as
+    Open3D's Image would hold them: depth uint16 as it is, any other real dtype as float32; colour uint8 [..., H, W, 3]; both
+    contiguous.  numpy arrays and torch tensors on either device alike; a conversion runs on the operand's own device, and an
+    operand that already has the layout is returned as it is (no copy).  frames=None: one [H, W] frame, else [frames, H, W].
+    -> (depth, color, depth kind, converted) - converted: a new CUDA tensor was made (torch's stream produces it).
+    Anything else - colour that is not uint8 of the depth's shape + (3,), an intrinsic of another size, depth and colour on
+    different devices - raises before any library call."""
+
+    def is_torch(a):
+        return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+    if is_torch(depth) != is_torch(color):
+        # one host array and one torch tensor: only together when the tensor lives on the host
+        if L.location(depth) != L.HV_HOST or L.location(color) != L.HV_HOST:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+    converted = False
+    if is_torch(depth):
+        import torch
+
+        if L.location(depth) != L.location(color) or (depth.is_cuda and depth.device != color.device):
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        if depth.dtype == torch.bool or depth.dtype.is_complex:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        d = depth if depth.dtype == torch.uint16 else depth.to(torch.float32)
+        d = d.contiguous()
+        dkind = L.HV_DEPTH_U16 if d.dtype == torch.uint16 else L.HV_DEPTH_F32
+        converted = d is not depth and d.is_cuda
+    else:
+        d = np.asarray(depth)
+        if not (np.issubdtype(d.dtype, np.integer) or np.issubdtype(d.dtype, np.floating)):
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        d = np.ascontiguousarray(d, dtype=np.uint16 if d.dtype == np.uint16 else np.float32)
+        dkind = L.HV_DEPTH_U16 if d.dtype == np.uint16 else L.HV_DEPTH_F32
+    if is_torch(color):
+        import torch
+
+        if color.dtype != torch.uint8:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        c = color.contiguous()
+        converted = converted or (c is not color and c.is_cuda)
+    else:
+        c = np.asarray(color)
+        if c.dtype != np.uint8:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        c = np.ascontiguousarray(c)
+    shape = tuple(int(s) for s in d.shape)
+    if len(shape) != (2 if frames is None else 3) or (frames is not None and shape[0] != frames):
+        raise RuntimeError(_UNSUPPORTED_IMAGE)
+    if tuple(int(s) for s in c.shape) != shape + (3,):
+        raise RuntimeError(_UNSUPPORTED_IMAGE)
+    if int(intrinsic.width) != shape[-1] or int(intrinsic.height) != shape[-2]:
+        raise RuntimeError(_UNSUPPORTED_IMAGE)
+    return d, c, dkind, converted
+
+
 class _Volume:
     """Owns one hv_volume handle."""
 
@@ -931,62 +990,65 @@ class ScalableTSDFVolume(_Volume):
         L.check(self._lib.hv_reset(self._h))
 
     def integrate(self, image, intrinsic, extrinsic):
-        """image: RGBDImage (color HxWx3 uint8 RGB, depth HxW float32|uint16); extrinsic = T_cw."""
-        depth, color = image.depth, image.color
-        dkind = L.HV_DEPTH_U16 if str(depth.dtype) in ("uint16", "torch.uint16") else L.HV_DEPTH_F32
-        if not hasattr(depth, "data_ptr"):
-            depth = np.ascontiguousarray(depth, dtype=np.uint16 if dkind == L.HV_DEPTH_U16 else np.float32)
-            color = np.ascontiguousarray(color, dtype=np.uint8)
+        """image: RGBDImage (color HxWx3 uint8 RGB, depth HxW uint16 or any real dtype, read as float32); extrinsic = T_cw."""
+        depth, color, dkind, converted = _tsdf_operands(image.depth, image.color, intrinsic)
         H, W = int(depth.shape[0]), int(depth.shape[1])
-        if tuple(color.shape) != (H, W, 3) or intrinsic.width != W or intrinsic.height != H:
-            raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
-        if L.location(depth) != L.location(color):
-            raise RuntimeError("depth and color must live on the same device")
         intr = intrinsic.as_array()
         T = _as_f64_4x4(extrinsic)
-        # the kernels gather from the caller's planes asynchronously on the volume's stream: keep device inputs
-        # alive until the next call (by then the stream has consumed them or they are still referenced here)
-        self._inflight = (getattr(self, "_inflight_prev", None), depth, color)
-        self._inflight_prev = (depth, color)
-        L.check(
-            self._lib.hv_tsdf_integrate(
-                self._h, L.ptr(depth), dkind, L.ptr(color), H, W, L.ptr(intr), L.ptr(T), image.depth_scale,
-                image.depth_trunc, L.location(depth)
-            )
-        )
+        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_integrate(
+            self._h, L.ptr(depth), dkind, L.ptr(color), H, W, L.ptr(intr), L.ptr(T), image.depth_scale, image.depth_trunc,
+            L.location(depth)))
 
     def integrate_batch(self, depth, color, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """Replay F posed frames ([F,H,W] depth, [F,H,W,3] colour, [F,4,4] T_cw); same result as F
         integrate() calls (the rebuild() use case, volumetric_integrator_base.py:1242-1318)."""
-        dkind = L.HV_DEPTH_U16 if str(depth.dtype) in ("uint16", "torch.uint16") else L.HV_DEPTH_F32
-        F, H, W = (int(s) for s in depth.shape)
-        T = np.ascontiguousarray(np.asarray(extrinsics, dtype=np.float64).reshape(F, 16))
+        F = int(depth.shape[0]) if len(depth.shape) == 3 else -1
+        depth, color, dkind, converted = _tsdf_operands(depth, color, intrinsic, frames=F)
+        T = np.asarray(extrinsics, dtype=np.float64)
+        if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        if F == 0:
+            return
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        T = np.ascontiguousarray(T.reshape(F, 16))
         intr = intrinsic.as_array()
+        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_integrate_batch(
+            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(T), float(depth_scale), float(depth_trunc),
+            L.location(depth)))
+
+    def _launch_tsdf(self, depth, color, converted, call):
+        """The kernels gather from the operands asynchronously on the volume's stream: keep them alive until the next call (by
+        then the stream has consumed them or they are still referenced here).  Operands converted on the device come from
+        torch's current stream: the volume's stream waits for it, and torch's waits for the launch before it may reuse them."""
         self._inflight = (getattr(self, "_inflight_prev", None), depth, color)
         self._inflight_prev = (depth, color)
-        L.check(
-            self._lib.hv_tsdf_integrate_batch(
-                self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(T), float(depth_scale),
-                float(depth_trunc), L.location(depth)
-            )
-        )
+        ts = self._torch_in(depth) if converted else None
+        try:
+            L.check(call())
+        finally:
+            if ts is not None:
+                self._torch_out(ts, depth.device)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
         its queue): no np.stack - the library copies every frame straight into page-locked staging slots and sends them
         over PCIe on a copy stream while the previous batch is swept.  Same result as len(depths) integrate() calls."""
         F = len(depths)
+        if len(colors) != F:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        T = np.asarray(extrinsics, dtype=np.float64)
+        if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
+            raise RuntimeError(_UNSUPPORTED_IMAGE)
         if F == 0:
             return
-        dkind = L.HV_DEPTH_U16 if str(depths[0].dtype) == "uint16" else L.HV_DEPTH_F32
-        dtype = np.uint16 if dkind == L.HV_DEPTH_U16 else np.float32
-        depths = [np.ascontiguousarray(d, dtype=dtype) for d in depths]
-        colors = [np.ascontiguousarray(c, dtype=np.uint8) for c in colors]
+        ops = [_tsdf_operands(d, c, intrinsic) for d, c in zip(depths, colors)]
+        if any(L.location(o[0]) != L.HV_HOST for o in ops) or len({o[2] for o in ops}) != 1:
+            raise RuntimeError(_UNSUPPORTED_IMAGE)  # host frames of one depth type
+        dkind = ops[0][2]
+        depths = [np.asarray(o[0]) for o in ops]  # (host torch tensors: numpy views of the same memory)
+        colors = [np.asarray(o[1]) for o in ops]
         H, W = (int(x) for x in depths[0].shape)
-        for d, c in zip(depths, colors):
-            if d.shape != (H, W) or c.shape != (H, W, 3):
-                raise RuntimeError("[ScalableTSDFVolume::Integrate] Unsupported image format.")
-        T = np.ascontiguousarray(np.asarray(extrinsics, dtype=np.float64).reshape(F, 16))
+        T = np.ascontiguousarray(T.reshape(F, 16))
         intr = intrinsic.as_array()
         dp = (ctypes.c_void_p * F)(*[d.ctypes.data for d in depths])
         cp = (ctypes.c_void_p * F)(*[c.ctypes.data for c in colors])

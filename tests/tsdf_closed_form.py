@@ -50,8 +50,15 @@ def pose(eye, target, up=(0.05, -1.0, 0.1)):
 POSES = (pose((0.25, -0.15, -0.35), (0.1, 0.0, 1.3)), pose((-0.35, 0.2, -0.2), (0.05, -0.05, 1.2)), pose((0.0, 0.35, -0.1), (0.1, -0.1, 1.25)))
 
 
-def render(T_cw):
+def camera(W=W, H=H, K=K, stride=STRIDE):
+    """(W, H, K, stride): the image size, pinhole intrinsics (fx, fy, cx, cy) and depth sampling stride every function below
+    takes as its optional `cam` argument.  Default: the module's constants."""
+    return int(W), int(H), np.asarray(K, np.float64), int(stride)
+
+
+def render(T_cw, cam=None):
     """z-depth (float32 metres, 0 = invalid) and colour (uint8 RGB) of the analytic scene: nearest of plane and sphere per pixel."""
+    W, H, K, _ = cam or camera()
     fx, fy, cx, cy = K
     T_wc = np.linalg.inv(T_cw)
     v, u = np.mgrid[0:H, 0:W].astype(np.float64)
@@ -76,13 +83,14 @@ def render(T_cw):
     return depth, rgb
 
 
-def frames():
-    return [(*render(T), T) for T in POSES]
+def frames(cam=None):
+    return [(*render(T, cam), T) for T in POSES]
 
 
-def touched_units(depth, T_cw):
+def touched_units(depth, T_cw, cam=None):
     """-> sorted [U, 3] int64: the units a frame opens (vectorised over the strided samples; sdf_trunc < unit_length, so a
     sample's range has one or two units per axis)."""
+    W, H, K, STRIDE = cam or camera()
     fx, fy, cx, cy = K
     T_wc = np.linalg.inv(T_cw)
     ii, jj = np.mgrid[0:H:STRIDE, 0:W:STRIDE]
@@ -100,11 +108,12 @@ def touched_units(depth, T_cw):
     return np.unique(np.concatenate(out), axis=0)
 
 
-def evaluate(frame_list, chunk=256):
+def evaluate(frame_list, chunk=256, cam=None):
     """-> keys [U,3] (sorted like the dumps), weight [U,4096] int, tsdf [U,4096] f64 (mean of the accepted frames' values),
     colour [U,4096,3] f64, fragile [U,4096] bool.  Voxel order inside a unit: x * 256 + y * 16 + z (the dumps')."""
+    W, H, K, _ = cam or camera()
     fx, fy, cx, cy = K
-    per_frame = [touched_units(d, T) for d, _, T in frame_list]
+    per_frame = [touched_units(d, T, cam) for d, _, T in frame_list]
     keys = np.unique(np.concatenate(per_frame), axis=0)
     order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
     keys = keys[order]
@@ -117,7 +126,7 @@ def evaluate(frame_list, chunk=256):
     local = (np.stack([lx, ly, lz], axis=-1).reshape(-1, 3) + 0.5) * VOXEL
     key_id = {tuple(k): i for i, k in enumerate(keys.tolist())}
     for depth, rgb, T_cw in frame_list:
-        rows = np.array(sorted(key_id[tuple(k)] for k in touched_units(depth, T_cw).tolist()))
+        rows = np.array(sorted(key_id[tuple(k)] for k in touched_units(depth, T_cw, cam).tolist()))
         R, t = T_cw[:3, :3], T_cw[:3, 3]
         for lo in range(0, len(rows), chunk):
             sel = rows[lo:lo + chunk]
