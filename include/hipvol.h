@@ -438,6 +438,66 @@ int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, const double *
                      double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
                      float *color, uint8_t *mask, int32_t loc);
 
+/* Frame-to-model tracking (KinectFusion's other half; names and defaults follow Open3D's tensor odometry, point-to-plane): where
+ * was a depth frame taken, aligned against the fused map rendered at an initial pose, and how well does it fit.  This project's
+ * own contract, not Open3D-pinned:
+ *   source    depth [H,W] (depth_dtype, at loc) -> float32 metres d = depth / (float)depth_scale (both dtypes, as integrate).
+ *             Level 0 valid: finite and depth_min < d <= depth_max (compared in double).  Level l+1 [H >> (l+1), W >> (l+1)]:
+ *             the valid ones of the 2x2 children (2u, 2v), (2u+1, 2v), (2u, 2v+1), (2u+1, 2v+1), summed in that order in float32
+ *             and divided by their count; valid iff >= 1 child is valid and max - min of the valid children <= depth_outlier_trunc.
+ *             Invalid is stored as 0.
+ *   levels    l = 0 .. n_levels - 1 (0 = full resolution), run from n_levels - 1 down to 0; intrinsics fx / 2^l, fy / 2^l,
+ *             (cx + 0.5) / 2^l - 0.5, (cy + 0.5) / 2^l - 0.5.
+ *   model     per level one hv_tsdf_ray_cast at T_cw_init with that level's intrinsics (depth_min, depth_max, weight_threshold,
+ *             depth_scale 1; depth, normal and mask only).  Everything below is double, in the ANCHOR frame = the T_cw_init
+ *             camera: model vertex q(u, v) = z* ((u - cx) / fx, (v - cy) / fy, 1) from the cast depth z*, normal
+ *             n = R_cw_init n_world (the world vertex is not used: the precision does not depend on where the world origin is).
+ *   state     A = T_cw_init T_wc (current camera -> anchor), identity at the start, kept on the device.
+ *   linearise every valid source pixel (u, v): p_c = d ((u - cx) / fx, (v - cy) / fy, 1), p = R_A p_c + t_A,
+ *             (u', v') = (floor(fx p_x / p_z + cx + 0.5), floor(fy p_y / p_z + cy + 0.5)); an INLIER iff p_z > 0, (u', v') lies
+ *             in the level's image, the model mask is set there and |p - q| <= depth_outlier_trunc.  For an inlier
+ *             r = n . (p - q), J = [p x n, n] (omega, t), Huber weight w = 1 if |r| <= depth_huber_delta else delta / |r|;
+ *             H = sum w J^T J, g = sum w J^T r, e = sum r^2 (unweighted), counts of inliers and of valid source pixels.
+ *   solve     H xi = -g by Cholesky; DEGENERATE if fewer than HV_TRACK_MIN_INLIERS inliers or a pivot <= HV_TRACK_PIVOT_REL
+ *             trace(H): A stays, the level ends and is marked degenerate.  Otherwise A := exp(xi) A with
+ *             exp(xi) = [Rodrigues(omega), t] (the translation as it is), and the level ends when |omega| + |t| <
+ *             HV_TRACK_CONVERGED or after its iterations[l] linearisations.
+ *   result    T_cw = inverse(A) T_cw_init; of the LAST level-0 linearisation: fitness = inliers / valid (0 if none), inlier_rmse
+ *             = sqrt(e / inliers) (0 if none), information = H (6x6, row-major, anchor frame, order (omega, t)); iterations =
+ *             linearisations run per level; degenerate = bit l set when level l ended on a degenerate step; success = level 0 did
+ *             not and had >= HV_TRACK_MIN_INLIERS inliers.  An empty map is not an error: success = 0, T_cw = T_cw_init.
+ * trace (may be NULL): one row of HV_TRACK_TRACE_STRIDE doubles per linearisation run, in order: {level, iteration, status
+ * (0 stepped, 1 converged, 2 degenerate), inliers, valid, e, A [16] (the state it linearised at), H [21] (upper triangle, row by
+ * row), g [6], xi [6]}; *trace_rows = rows written (at most trace_cap).
+ * All steps are queued at once on the volume's stream; a step of a finished level returns at once (a device flag), and the host
+ * waits once, for the result.  No float atomics: the reduction order is fixed, results are bitwise reproducible.  Reads only (as
+ * hv_tsdf_ray_cast).  HV_ERR_MODE for a non-TSDF or owner-sharded volume, HV_ERR_INVALID for bad sizes, depth range, intrinsics,
+ * thresholds or iterations (1 <= n_levels <= HV_TRACK_MAX_LEVELS, every entry >= 0, level 0's >= 1, H >> (n_levels - 1) >= 1). */
+#define HV_TRACK_MAX_LEVELS 8
+#define HV_TRACK_MIN_INLIERS 6
+#define HV_TRACK_PIVOT_REL 1e-10
+#define HV_TRACK_CONVERGED 1e-6
+#define HV_TRACK_TRACE_STRIDE 56
+typedef struct hv_track_params {
+    double depth_scale, depth_min, depth_max, weight_threshold;
+    double depth_outlier_trunc; /* Open3D default 0.07 m */
+    double depth_huber_delta;   /* Open3D default 0.05 m */
+    int32_t n_levels;
+    int32_t iterations[HV_TRACK_MAX_LEVELS]; /* per level, level 0 first (Open3D default {10, 5, 4}) */
+} hv_track_params;
+typedef struct hv_track_result {
+    double T_cw[16];
+    double information[36];
+    double fitness, inlier_rmse;
+    int64_t inliers, valid;
+    int32_t iterations[HV_TRACK_MAX_LEVELS];
+    int32_t degenerate;
+    int32_t success;
+} hv_track_result;
+int hv_tsdf_track(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t height, int32_t width, const double *intr,
+                  const double *T_cw_init, const hv_track_params *params, hv_track_result *result, double *trace, int64_t trace_cap,
+                  int64_t *trace_rows, int32_t loc);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

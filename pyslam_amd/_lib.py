@@ -40,6 +40,37 @@ class HvConfig(_c.Structure):
     ]
 
 
+HV_TRACK_MAX_LEVELS = 8
+HV_TRACK_TRACE_STRIDE = 56
+
+
+class HvTrackParams(_c.Structure):
+    _fields_ = [
+        ("depth_scale", _f64),
+        ("depth_min", _f64),
+        ("depth_max", _f64),
+        ("weight_threshold", _f64),
+        ("depth_outlier_trunc", _f64),
+        ("depth_huber_delta", _f64),
+        ("n_levels", _i32),
+        ("iterations", _i32 * HV_TRACK_MAX_LEVELS),
+    ]
+
+
+class HvTrackResult(_c.Structure):
+    _fields_ = [
+        ("T_cw", _f64 * 16),
+        ("information", _f64 * 36),
+        ("fitness", _f64),
+        ("inlier_rmse", _f64),
+        ("inliers", _i64),
+        ("valid", _i64),
+        ("iterations", _i32 * HV_TRACK_MAX_LEVELS),
+        ("degenerate", _i32),
+        ("success", _i32),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -121,6 +152,7 @@ SIGNATURES = {
     "hv_tsdf_extract_points_f32": (_i32, [_vp, _vp, _vp, _i64, _pi64]),
     "hv_tsdf_extract_point_normals": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_ray_cast": (_i32, [_vp, _i32, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),

@@ -459,6 +459,8 @@ struct hv_volume {
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
     void *raycast_buf = nullptr; // HV_HOST outputs of hv_tsdf_ray_cast (apart from out_*: a cast leaves the extraction caches valid)
     size_t raycast_buf_bytes = 0;
+    void *track_buf = nullptr;   // hv_tsdf_track: source pyramid, model casts, reduction slab, state and trace (device)
+    size_t track_buf_bytes = 0;
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)
     void *shadow_ring = nullptr;
     int shadow_ring_next = 0;
@@ -511,4 +513,8 @@ int hv_stage_frames_consumed(hv_volume *v, int set, hipStream_t consumer);
 void hv_profile_begin(hv_volume *v);
 void hv_profile_end(hv_volume *v, int64_t units);
 void hv_invert4x4(const double *m, double *out);
+// hv_raycast.hip: one cast queued on the volume's stream into device arrays (arguments checked by the caller)
+int hv_ray_cast_launch(hv_volume *v, int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_min,
+                       double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
+                       float *color, uint8_t *mask);
 void hv_segments_cache_free(void *cache); // hv_semantic_ops.hip

@@ -253,21 +253,11 @@ __global__ __launch_bounds__(256) void k_tsdf_ray_cast(HvTable table, const char
 
 } // namespace
 
-extern "C" int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_min,
-                                double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex,
-                                float *normal, float *color, uint8_t *mask, int32_t loc) {
-    HV_REQUIRE(v != nullptr && intr != nullptr && T_cw != nullptr, HV_ERR_INVALID, "hv_tsdf_ray_cast: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_ray_cast: volume is not in TSDF mode");
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "hv_tsdf_ray_cast: ray_cast needs the whole volume (owner-sharded: merge or gather first)");
-    HV_REQUIRE(height > 0 && width > 0 && height <= 65535 && width <= 65535, HV_ERR_INVALID, "hv_tsdf_ray_cast: bad image size %d x %d",
-               (int)height, (int)width);
-    HV_REQUIRE(std::isfinite(depth_min) && std::isfinite(depth_max) && depth_min >= 0.0 && depth_min < depth_max, HV_ERR_INVALID,
-               "hv_tsdf_ray_cast: bad depth range [%g, %g)", depth_min, depth_max);
-    HV_REQUIRE(intr[0] != 0.0 && intr[1] != 0.0 && std::isfinite(weight_threshold) && std::isfinite(depth_scale), HV_ERR_INVALID,
-               "hv_tsdf_ray_cast: bad intrinsics / threshold / scale");
-    HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "hv_tsdf_ray_cast: bad loc %d", (int)loc);
-    HV_HIP(hipSetDevice(v->device));
-
+// Queue one cast on the volume's stream into device arrays (any may be NULL); bracketed for hv_profile_read.  The caller has checked
+// the arguments and set pipe_armed = false.  (hv_tsdf_track renders its model with it.)
+int hv_ray_cast_launch(hv_volume *v, int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_min,
+                       double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
+                       float *color, uint8_t *mask) {
     HvRayParams P{};
     double T_wc[16];
     hv_invert4x4(T_cw, T_wc);
@@ -292,6 +282,29 @@ extern "C" int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, con
     P.max_steps = (int32_t)std::min(steps, 1.0e8);
     P.voxel_length_d = v->cfg.voxel_size;
     P.unit_length_d = v->cfg.voxel_size * (double)HV_TSDF_R;
+    HvRayOut O{depth, vertex, normal, color, mask};
+    hv_profile_begin(v);
+    hipLaunchKernelGGL(k_tsdf_ray_cast, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, v->stream, v->table,
+                       (const char *)v->pool, P, O);
+    hv_profile_end(v, 0);
+    HV_HIP(hipGetLastError());
+    return HV_OK;
+}
+
+extern "C" int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_min,
+                                double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex,
+                                float *normal, float *color, uint8_t *mask, int32_t loc) {
+    HV_REQUIRE(v != nullptr && intr != nullptr && T_cw != nullptr, HV_ERR_INVALID, "hv_tsdf_ray_cast: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_ray_cast: volume is not in TSDF mode");
+    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "hv_tsdf_ray_cast: ray_cast needs the whole volume (owner-sharded: merge or gather first)");
+    HV_REQUIRE(height > 0 && width > 0 && height <= 65535 && width <= 65535, HV_ERR_INVALID, "hv_tsdf_ray_cast: bad image size %d x %d",
+               (int)height, (int)width);
+    HV_REQUIRE(std::isfinite(depth_min) && std::isfinite(depth_max) && depth_min >= 0.0 && depth_min < depth_max, HV_ERR_INVALID,
+               "hv_tsdf_ray_cast: bad depth range [%g, %g)", depth_min, depth_max);
+    HV_REQUIRE(intr[0] != 0.0 && intr[1] != 0.0 && std::isfinite(weight_threshold) && std::isfinite(depth_scale), HV_ERR_INVALID,
+               "hv_tsdf_ray_cast: bad intrinsics / threshold / scale");
+    HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "hv_tsdf_ray_cast: bad loc %d", (int)loc);
+    HV_HIP(hipSetDevice(v->device));
 
     // outputs: in place (HV_DEVICE) or in one staging buffer of the volume, copied back before returning (HV_HOST)
     const size_t npx = (size_t)height * (size_t)width;
@@ -310,15 +323,12 @@ extern "C" int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, con
         }
         for (int i = 0; i < 5; ++i) dev[i] = sizes[i] ? (char *)v->raycast_buf + off[i] : nullptr;
     }
-    HvRayOut O{(float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (uint8_t *)dev[4]};
     // a batch issued after this call must not start claiming units (its touch + pack launch on the auxiliary stream) while the
     // cast still reads the table: the next hv_tsdf_integrate_batch starts a fresh chain behind it
     v->pipe_armed = false;
-    hv_profile_begin(v);
-    hipLaunchKernelGGL(k_tsdf_ray_cast, dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256), 0, v->stream, v->table,
-                       (const char *)v->pool, P, O);
-    hv_profile_end(v, 0);
-    HV_HIP(hipGetLastError());
+    const int rc = hv_ray_cast_launch(v, height, width, intr, T_cw, depth_min, depth_max, weight_threshold, depth_scale, (float *)dev[0],
+                                      (float *)dev[1], (float *)dev[2], (float *)dev[3], (uint8_t *)dev[4]);
+    if (rc != HV_OK) return rc;
     if (loc == HV_HOST) {
         for (int i = 0; i < 5; ++i)
             if (sizes[i]) HV_HIP(hipMemcpyAsync(user[i], dev[i], sizes[i], hipMemcpyDeviceToHost, v->stream));

@@ -1,0 +1,444 @@
+// libpyslam_hipvol.so — frame-to-model point-to-plane tracking against the fused TSDF map on gfx950 (hv_tsdf_track).  The contract
+// (pyramid, model, association, linearisation, solve, stopping, outputs) is written once in include/hipvol.h; tests/track_reference.py
+// restates it in numpy.
+//
+// Per call, all on the volume's stream and queued up front: one launch per source pyramid level, one ray cast per level (the
+// model, k_tsdf_ray_cast through hv_ray_cast_launch), then for every iteration of every level a linearise launch (one thread per
+// source pixel, grid-stride; wave butterfly + LDS reduction of the 30 sums in double into one slab row per workgroup) and a
+// one-workgroup solve launch (the slab summed in a fixed order, Cholesky, A update, trace row, level flag).  A step of a level that
+// has converged or gone degenerate reads the flag and returns.  No float atomics anywhere: results are bitwise reproducible.
+#include <cmath>
+
+#include "hv_common.h"
+
+namespace {
+
+constexpr int TK_NACC = 30;          // H upper triangle [21], g [6], e, inliers, valid
+constexpr int TK_BLOCK = 256;        // linearise workgroup (4 waves)
+constexpr int TK_MAX_BLOCKS = 1024;  // linearise grid cap = slab rows
+constexpr int TK_SUM_PARTS = 32;     // solve workgroup: 32 parts x 32 components
+constexpr int TK_SUM_THREADS = TK_SUM_PARTS * 32;
+
+struct TkState {
+    double A[16];                          // current camera -> anchor, row-major
+    double last[TK_NACC];                  // sums of the last level-0 linearisation
+    int32_t done[HV_TRACK_MAX_LEVELS];     // 0 running, 1 converged, 2 degenerate
+    int32_t iters[HV_TRACK_MAX_LEVELS];    // linearisations run
+    int32_t rows;                          // trace rows written
+    int32_t pad;
+};
+
+struct TkLevel {
+    const float *src;        // source depth of the level, metres, 0 = invalid
+    const float *mdepth;     // model (cast) depth
+    const float *mnormal;    // model normal, world frame [H,W,3]
+    const uint8_t *mmask;    // model hit mask
+    int32_t height, width;
+    double fx, fy, cx, cy;
+};
+
+struct TkParams {
+    double R0[9];  // R_cw_init: world normal -> anchor frame
+    double trunc, delta;
+};
+
+__global__ __launch_bounds__(64) void k_track_init(TkState *st) {
+    const int t = threadIdx.x;
+    if (t < 16) st->A[t] = (t % 5 == 0) ? 1.0 : 0.0;
+    if (t < TK_NACC) st->last[t] = 0.0;
+    if (t < HV_TRACK_MAX_LEVELS) {
+        st->done[t] = 0;
+        st->iters[t] = 0;
+    }
+    if (t == 0) st->rows = 0;
+}
+
+// level 0: depth / depth_scale in float32; valid iff finite and in (depth_min, depth_max] (double compares), else 0
+__global__ __launch_bounds__(256) void k_track_source(const void *__restrict__ raw, int is_u16, int64_t npx, float scale, double dmin,
+                                                      double dmax, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npx) return;
+    float d = is_u16 ? (float)((const uint16_t *)raw)[i] : ((const float *)raw)[i];
+    d = d / scale;
+    out[i] = (isfinite(d) && (double)d > dmin && (double)d <= dmax) ? d : 0.0f;
+}
+
+// level l -> l + 1: float32 mean of the valid 2x2 children (fixed order), valid iff max - min <= trunc
+__global__ __launch_bounds__(256) void k_track_down(const float *__restrict__ in, int32_t w_in, float *__restrict__ out, int32_t h_out,
+                                                    int32_t w_out, double trunc) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)h_out * w_out) return;
+    const int u = (int)(i % w_out), v = (int)(i / w_out);
+    const float *r0 = in + (int64_t)(2 * v) * w_in + 2 * u, *r1 = r0 + w_in;
+    const float c[4] = {r0[0], r0[1], r1[0], r1[1]};
+    float sum = 0.0f, mx = -INFINITY, mn = INFINITY;
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (c[k] > 0.0f) {
+            sum = sum + c[k];
+            mx = fmaxf(mx, c[k]);
+            mn = fminf(mn, c[k]);
+            ++n;
+        }
+    }
+    out[i] = (n > 0 && (double)(mx - mn) <= trunc) ? sum / (float)n : 0.0f;
+}
+
+__device__ __forceinline__ double tk_wave_sum(double x) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64); // butterfly: every lane ends with the same value
+    return x;
+}
+
+// one step's linearisation: per workgroup the 30 sums of its pixels -> slab[blockIdx.x]
+__global__ __launch_bounds__(TK_BLOCK) void k_track_linearise(TkLevel L, TkParams P, const TkState *__restrict__ st, int level,
+                                                              double *__restrict__ slab) {
+    if (st->done[level] != 0) return; // (uniform: every thread reads the same flag)
+    double A[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) A[k] = st->A[k];
+    double acc[TK_NACC];
+#pragma unroll
+    for (int k = 0; k < TK_NACC; ++k) acc[k] = 0.0;
+
+    const int64_t npx = (int64_t)L.height * L.width;
+    for (int64_t pix = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x; pix < npx; pix += (int64_t)gridDim.x * TK_BLOCK) {
+        const float ds = L.src[pix];
+        if (!(ds > 0.0f)) continue;
+        acc[29] += 1.0;
+        const int u = (int)(pix % L.width), v = (int)(pix / L.width);
+        const double d = (double)ds;
+        const double pc0 = d * (((double)u - L.cx) / L.fx), pc1 = d * (((double)v - L.cy) / L.fy), pc2 = d;
+        const double p0 = A[0] * pc0 + A[1] * pc1 + A[2] * pc2 + A[3];
+        const double p1 = A[4] * pc0 + A[5] * pc1 + A[6] * pc2 + A[7];
+        const double p2 = A[8] * pc0 + A[9] * pc1 + A[10] * pc2 + A[11];
+        if (!(p2 > 0.0)) continue;
+        const double uf = floor(L.fx * p0 / p2 + L.cx + 0.5), vf = floor(L.fy * p1 / p2 + L.cy + 0.5);
+        if (!(uf >= 0.0 && uf < (double)L.width && vf >= 0.0 && vf < (double)L.height)) continue;
+        const int64_t m = (int64_t)vf * L.width + (int64_t)uf;
+        if (!L.mmask[m]) continue;
+        const double z = (double)L.mdepth[m];
+        const double q0 = z * ((uf - L.cx) / L.fx), q1 = z * ((vf - L.cy) / L.fy), q2 = z;
+        const double nw0 = (double)L.mnormal[3 * m], nw1 = (double)L.mnormal[3 * m + 1], nw2 = (double)L.mnormal[3 * m + 2];
+        const double n0 = P.R0[0] * nw0 + P.R0[1] * nw1 + P.R0[2] * nw2;
+        const double n1 = P.R0[3] * nw0 + P.R0[4] * nw1 + P.R0[5] * nw2;
+        const double n2 = P.R0[6] * nw0 + P.R0[7] * nw1 + P.R0[8] * nw2;
+        const double e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
+        if (!(sqrt(e0 * e0 + e1 * e1 + e2 * e2) <= P.trunc)) continue;
+        const double r = n0 * e0 + n1 * e1 + n2 * e2;
+        const double J[6] = {p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, n0, n1, n2};
+        const double w = fabs(r) <= P.delta ? 1.0 : P.delta / fabs(r);
+        int k = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            const double wa = w * J[a];
+#pragma unroll
+            for (int b = a; b < 6; ++b) acc[k++] += wa * J[b];
+            acc[21 + a] += wa * r;
+        }
+        acc[27] += r * r;
+        acc[28] += 1.0;
+    }
+
+    __shared__ double red[TK_BLOCK / 64][TK_NACC];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < TK_NACC; ++k) {
+        const double s = tk_wave_sum(acc[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < TK_NACC) {
+        double s = red[0][threadIdx.x];
+#pragma unroll
+        for (int w = 1; w < TK_BLOCK / 64; ++w) s += red[w][threadIdx.x];
+        slab[(int64_t)blockIdx.x * TK_NACC + threadIdx.x] = s;
+    }
+}
+
+// one step's solve: the slab summed in a fixed order, then (thread 0) Cholesky, exp, A update, trace row, flag
+__global__ __launch_bounds__(TK_SUM_THREADS) void k_track_solve(TkState *__restrict__ st, const double *__restrict__ slab, int rows,
+                                                                int level, int iteration, double *__restrict__ trace, int trace_cap) {
+    if (st->done[level] != 0) return;
+    __shared__ double part[TK_SUM_PARTS][32];
+    __shared__ double tot[TK_NACC];
+    const int c = threadIdx.x & 31, k = threadIdx.x >> 5;
+    double s = 0.0;
+    if (c < TK_NACC)
+        for (int r = k; r < rows; r += TK_SUM_PARTS) s += slab[(int64_t)r * TK_NACC + c];
+    part[k][c] = s;
+    __syncthreads();
+    if (threadIdx.x < TK_NACC) {
+        double t = part[0][threadIdx.x];
+        for (int q = 1; q < TK_SUM_PARTS; ++q) t += part[q][threadIdx.x];
+        tot[threadIdx.x] = t;
+        if (level == 0) st->last[threadIdx.x] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+
+    // (every loop below has constant bounds and is unrolled: the 6 x 6 arrays stay in registers)
+    double H[6][6], g[6];
+    {
+        int q = 0;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) H[a][b] = H[b][a] = tot[q++];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) g[a] = tot[21 + a];
+    }
+    const double inliers = tot[28];
+    double trH = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) trH += H[a][a];
+    // Cholesky H = L L^T, then L y = -g, L^T xi = y (the values of a degenerate factorisation are not used)
+    bool degenerate = inliers < (double)HV_TRACK_MIN_INLIERS;
+    double Lm[6][6], xi[6];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        double d = H[j][j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) d -= Lm[j][q] * Lm[j][q];
+        if (!(d > HV_TRACK_PIVOT_REL * trH)) degenerate = true;
+        Lm[j][j] = sqrt(d);
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            double e = H[i][j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) e -= Lm[i][q] * Lm[j][q];
+            Lm[i][j] = e / Lm[j][j];
+        }
+    }
+    double A0[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) A0[i] = st->A[i];
+    int status = degenerate ? 2 : 0;
+    {
+        double y[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double e = -g[i];
+#pragma unroll
+            for (int q = 0; q < i; ++q) e -= Lm[i][q] * y[q];
+            y[i] = e / Lm[i][i];
+        }
+#pragma unroll
+        for (int i = 5; i >= 0; --i) {
+            double e = y[i];
+#pragma unroll
+            for (int q = i + 1; q < 6; ++q) e -= Lm[q][i] * xi[q];
+            xi[i] = e / Lm[i][i];
+        }
+    }
+    if (degenerate) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) xi[i] = 0.0;
+    } else {
+        // exp(xi) = [Rodrigues(omega), t]; A := exp(xi) A
+        const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
+        const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
+        const double sa = th < 1e-8 ? 1.0 : sin(th) / th, sb = th < 1e-8 ? 0.5 : (1.0 - cos(th)) / (th * th);
+        const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
+        double E[12];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double kk = K[i * 3] * K[j] + K[i * 3 + 1] * K[3 + j] + K[i * 3 + 2] * K[6 + j];
+                E[i * 4 + j] = (i == j ? 1.0 : 0.0) + sa * K[i * 3 + j] + sb * kk;
+            }
+            E[i * 4 + 3] = xi[3 + i];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                st->A[i * 4 + j] = E[i * 4] * A0[j] + E[i * 4 + 1] * A0[4 + j] + E[i * 4 + 2] * A0[8 + j] + E[i * 4 + 3] * A0[12 + j];
+        const double tn = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
+        if (th + tn < HV_TRACK_CONVERGED) status = 1;
+    }
+    const int row = st->rows;
+    if (trace != nullptr && row < trace_cap) {
+        double *o = trace + (int64_t)row * HV_TRACK_TRACE_STRIDE;
+        o[0] = level;
+        o[1] = iteration;
+        o[2] = status;
+        o[3] = inliers;
+        o[4] = tot[29];
+        o[5] = tot[27];
+        for (int i = 0; i < 16; ++i) o[6 + i] = A0[i];
+        for (int i = 0; i < 21; ++i) o[22 + i] = tot[i];
+        for (int i = 0; i < 6; ++i) o[43 + i] = g[i];
+        for (int i = 0; i < 6; ++i) o[49 + i] = xi[i];
+        o[55] = 0.0;
+    }
+    st->rows = row + 1;
+    st->iters[level] += 1;
+    if (status != 0) st->done[level] = status;
+}
+
+inline size_t tk_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+} // namespace
+
+extern "C" int hv_tsdf_track(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t height, int32_t width, const double *intr,
+                             const double *T_cw_init, const hv_track_params *prm, hv_track_result *res, double *trace, int64_t trace_cap,
+                             int64_t *trace_rows, int32_t loc) {
+    HV_REQUIRE(v != nullptr && depth != nullptr && intr != nullptr && T_cw_init != nullptr && prm != nullptr && res != nullptr,
+               HV_ERR_INVALID, "hv_tsdf_track: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_track: volume is not in TSDF mode");
+    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "hv_tsdf_track: tracking needs the whole volume (owner-sharded: merge or gather first)");
+    HV_REQUIRE(depth_dtype == HV_DEPTH_F32 || depth_dtype == HV_DEPTH_U16, HV_ERR_INVALID, "hv_tsdf_track: bad depth dtype %d",
+               (int)depth_dtype);
+    HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "hv_tsdf_track: bad loc %d", (int)loc);
+    const int nl = prm->n_levels;
+    HV_REQUIRE(nl >= 1 && nl <= HV_TRACK_MAX_LEVELS, HV_ERR_INVALID, "hv_tsdf_track: need 1 to %d pyramid levels, got %d",
+               HV_TRACK_MAX_LEVELS, nl);
+    HV_REQUIRE(height > 0 && width > 0 && height <= 65535 && width <= 65535 && (height >> (nl - 1)) >= 1 && (width >> (nl - 1)) >= 1,
+               HV_ERR_INVALID, "hv_tsdf_track: bad image size %d x %d for %d levels", (int)height, (int)width, nl);
+    HV_REQUIRE(std::isfinite(prm->depth_min) && std::isfinite(prm->depth_max) && prm->depth_min >= 0.0 && prm->depth_min < prm->depth_max,
+               HV_ERR_INVALID, "hv_tsdf_track: bad depth range [%g, %g)", prm->depth_min, prm->depth_max);
+    HV_REQUIRE(std::isfinite(intr[0]) && std::isfinite(intr[1]) && std::isfinite(intr[2]) && std::isfinite(intr[3]) && intr[0] != 0.0 &&
+                   intr[1] != 0.0 && std::isfinite(prm->weight_threshold) && std::isfinite(prm->depth_scale) && prm->depth_scale != 0.0,
+               HV_ERR_INVALID, "hv_tsdf_track: bad intrinsics / threshold / scale");
+    HV_REQUIRE(std::isfinite(prm->depth_outlier_trunc) && prm->depth_outlier_trunc > 0.0 && std::isfinite(prm->depth_huber_delta) &&
+                   prm->depth_huber_delta > 0.0,
+               HV_ERR_INVALID, "hv_tsdf_track: depth_outlier_trunc and depth_huber_delta must be positive");
+    int64_t steps = 0;
+    for (int l = 0; l < nl; ++l) {
+        HV_REQUIRE(prm->iterations[l] >= 0 && prm->iterations[l] <= 10000, HV_ERR_INVALID, "hv_tsdf_track: bad iteration count %d at level %d",
+                   (int)prm->iterations[l], l);
+        steps += prm->iterations[l];
+    }
+    HV_REQUIRE(prm->iterations[0] >= 1, HV_ERR_INVALID, "hv_tsdf_track: level 0 needs at least one iteration");
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            HV_REQUIRE(std::isfinite(T_cw_init[r * 4 + c]), HV_ERR_INVALID, "hv_tsdf_track: T_cw_init is not finite");
+    HV_HIP(hipSetDevice(v->device));
+
+    // scratch: [state][slab][trace][per level: source, model depth, model normal, model mask]
+    size_t off = 0;
+    const size_t o_state = off;
+    off += tk_align(sizeof(TkState));
+    const size_t o_slab = off;
+    off += tk_align(sizeof(double) * TK_NACC * TK_MAX_BLOCKS);
+    const size_t o_trace = off;
+    off += tk_align(sizeof(double) * HV_TRACK_TRACE_STRIDE * (size_t)steps);
+    size_t o_src[HV_TRACK_MAX_LEVELS], o_md[HV_TRACK_MAX_LEVELS], o_mn[HV_TRACK_MAX_LEVELS], o_mm[HV_TRACK_MAX_LEVELS];
+    for (int l = 0; l < nl; ++l) {
+        const size_t n = (size_t)(height >> l) * (size_t)(width >> l);
+        o_src[l] = off;
+        off += tk_align(4 * n);
+        o_md[l] = off;
+        off += tk_align(4 * n);
+        o_mn[l] = off;
+        off += tk_align(12 * n);
+        o_mm[l] = off;
+        off += tk_align(n);
+    }
+    int rc = hv_ensure_buffer(v, &v->track_buf, &v->track_buf_bytes, off);
+    if (rc != HV_OK) return rc;
+    char *base = (char *)v->track_buf;
+    TkState *st = (TkState *)(base + o_state);
+    double *slab = (double *)(base + o_slab);
+    double *d_trace = (double *)(base + o_trace);
+
+    const void *d_depth = nullptr;
+    const size_t npx0 = (size_t)height * (size_t)width;
+    rc = hv_stage_in(v, depth, npx0 * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
+    if (rc != HV_OK) return rc;
+    // reads only, as hv_tsdf_ray_cast: the next batch starts a fresh touch + pack chain behind this call
+    v->pipe_armed = false;
+
+    hipLaunchKernelGGL(k_track_init, dim3(1), dim3(64), 0, v->stream, st);
+    hv_profile_begin(v);
+    hipLaunchKernelGGL(k_track_source, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
+                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, (int64_t)npx0, (float)prm->depth_scale, prm->depth_min, prm->depth_max,
+                       (float *)(base + o_src[0]));
+    hv_profile_end(v, 0);
+    for (int l = 1; l < nl; ++l) {
+        const int ho = height >> l, wo = width >> l;
+        hv_profile_begin(v);
+        hipLaunchKernelGGL(k_track_down, dim3((unsigned)(((size_t)ho * wo + 255) / 256)), dim3(256), 0, v->stream,
+                           (const float *)(base + o_src[l - 1]), width >> (l - 1), (float *)(base + o_src[l]), ho, wo,
+                           prm->depth_outlier_trunc);
+        hv_profile_end(v, 0);
+    }
+    HV_HIP(hipGetLastError());
+
+    TkLevel lv[HV_TRACK_MAX_LEVELS];
+    for (int l = 0; l < nl; ++l) {
+        const double s = (double)(1 << l);
+        const double li[4] = {intr[0] / s, intr[1] / s, (intr[2] + 0.5) / s - 0.5, (intr[3] + 0.5) / s - 0.5};
+        lv[l] = TkLevel{(const float *)(base + o_src[l]), (const float *)(base + o_md[l]), (const float *)(base + o_mn[l]),
+                        (const uint8_t *)(base + o_mm[l]), height >> l, width >> l, li[0], li[1], li[2], li[3]};
+        if (prm->iterations[l] == 0) continue;
+        rc = hv_ray_cast_launch(v, height >> l, width >> l, li, T_cw_init, prm->depth_min, prm->depth_max, prm->weight_threshold, 1.0,
+                                (float *)(base + o_md[l]), nullptr, (float *)(base + o_mn[l]), nullptr, (uint8_t *)(base + o_mm[l]));
+        if (rc != HV_OK) return rc;
+    }
+
+    TkParams P{};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) P.R0[r * 3 + c] = T_cw_init[r * 4 + c];
+    P.trunc = prm->depth_outlier_trunc;
+    P.delta = prm->depth_huber_delta;
+    for (int l = nl - 1; l >= 0; --l) {
+        const int64_t npx = (int64_t)lv[l].height * lv[l].width;
+        const int blocks = (int)std::min<int64_t>((npx + TK_BLOCK - 1) / TK_BLOCK, TK_MAX_BLOCKS);
+        for (int it = 0; it < prm->iterations[l]; ++it) {
+            hv_profile_begin(v);
+            hipLaunchKernelGGL(k_track_linearise, dim3((unsigned)blocks), dim3(TK_BLOCK), 0, v->stream, lv[l], P, (const TkState *)st, l, slab);
+            hv_profile_end(v, 0);
+            hv_profile_begin(v);
+            hipLaunchKernelGGL(k_track_solve, dim3(1), dim3(TK_SUM_THREADS), 0, v->stream, st, (const double *)slab, blocks, l, it,
+                               trace ? d_trace : (double *)nullptr, (int)steps);
+            hv_profile_end(v, 0);
+        }
+    }
+    HV_HIP(hipGetLastError());
+
+    TkState h{};
+    HV_HIP(hipMemcpyAsync(&h, st, sizeof(TkState), hipMemcpyDeviceToHost, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    if (trace != nullptr) {
+        const int64_t n = std::min<int64_t>(h.rows, trace_cap);
+        if (n > 0) HV_HIP(hipMemcpy(trace, d_trace, sizeof(double) * HV_TRACK_TRACE_STRIDE * (size_t)n, hipMemcpyDeviceToHost));
+        if (trace_rows) *trace_rows = n;
+    } else if (trace_rows) {
+        *trace_rows = 0;
+    }
+
+    // T_cw = inverse(A) T_cw_init, A rigid: inverse(A) = [R^T, -R^T t]
+    double Ai[16] = {};
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) Ai[r * 4 + c] = h.A[c * 4 + r];
+        Ai[r * 4 + 3] = -(h.A[r] * h.A[3] + h.A[4 + r] * h.A[7] + h.A[8 + r] * h.A[11]);
+    }
+    Ai[15] = 1.0;
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c)
+            res->T_cw[r * 4 + c] = Ai[r * 4] * T_cw_init[c] + Ai[r * 4 + 1] * T_cw_init[4 + c] + Ai[r * 4 + 2] * T_cw_init[8 + c] +
+                                   Ai[r * 4 + 3] * T_cw_init[12 + c];
+    {
+        int q = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = a; b < 6; ++b) {
+                res->information[a * 6 + b] = res->information[b * 6 + a] = h.last[q++];
+            }
+    }
+    const double e = h.last[27], inl = h.last[28], val = h.last[29];
+    res->inliers = (int64_t)inl;
+    res->valid = (int64_t)val;
+    res->fitness = val > 0.0 ? inl / val : 0.0;
+    res->inlier_rmse = inl > 0.0 ? std::sqrt(e / inl) : 0.0;
+    res->degenerate = 0;
+    for (int l = 0; l < HV_TRACK_MAX_LEVELS; ++l) {
+        res->iterations[l] = l < nl ? h.iters[l] : 0;
+        if (l < nl && h.done[l] == 2) res->degenerate |= 1 << l;
+    }
+    res->success = (h.done[0] != 2 && inl >= (double)HV_TRACK_MIN_INLIERS) ? 1 : 0;
+    return HV_OK;
+}

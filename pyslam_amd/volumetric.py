@@ -47,19 +47,20 @@ def _as_f64_4x4(T):
 _UNSUPPORTED_IMAGE = "[ScalableTSDFVolume::Integrate] Unsupported image format."
 
 
-def _tsdf_operands(depth, color, intrinsic, frames=None):
+def _tsdf_operands(depth, color, intrinsic, frames=None, depth_only=False):
     """The depth / colour operands of ScalableTSDFVolume.integrate* in the layout the library reads from a bare pointer, as
     Open3D's Image would hold them: depth uint16 as it is, any other real dtype as float32; colour uint8 [..., H, W, 3]; both
     contiguous.  numpy arrays and torch tensors on either device alike; a conversion runs on the operand's own device, and an
     operand that already has the layout is returned as it is (no copy).  frames=None: one [H, W] frame, else [frames, H, W].
     -> (depth, color, depth kind, converted) - converted: a new CUDA tensor was made (torch's stream produces it).
     Anything else - colour that is not uint8 of the depth's shape + (3,), an intrinsic of another size, depth and colour on
-    different devices - raises before any library call."""
+    different devices - raises before any library call.  depth_only=True: the depth operand alone, color is ignored (and
+    returned as None)."""
 
     def is_torch(a):
         return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
 
-    if is_torch(depth) != is_torch(color):
+    if not depth_only and is_torch(depth) != is_torch(color):
         # one host array and one torch tensor: only together when the tensor lives on the host
         if L.location(depth) != L.HV_HOST or L.location(color) != L.HV_HOST:
             raise RuntimeError(_UNSUPPORTED_IMAGE)
@@ -67,7 +68,7 @@ def _tsdf_operands(depth, color, intrinsic, frames=None):
     if is_torch(depth):
         import torch
 
-        if L.location(depth) != L.location(color) or (depth.is_cuda and depth.device != color.device):
+        if not depth_only and (L.location(depth) != L.location(color) or (depth.is_cuda and depth.device != color.device)):
             raise RuntimeError(_UNSUPPORTED_IMAGE)
         if depth.dtype == torch.bool or depth.dtype.is_complex:
             raise RuntimeError(_UNSUPPORTED_IMAGE)
@@ -81,7 +82,9 @@ def _tsdf_operands(depth, color, intrinsic, frames=None):
             raise RuntimeError(_UNSUPPORTED_IMAGE)
         d = np.ascontiguousarray(d, dtype=np.uint16 if d.dtype == np.uint16 else np.float32)
         dkind = L.HV_DEPTH_U16 if d.dtype == np.uint16 else L.HV_DEPTH_F32
-    if is_torch(color):
+    if depth_only:
+        c = None
+    elif is_torch(color):
         import torch
 
         if color.dtype != torch.uint8:
@@ -96,11 +99,49 @@ def _tsdf_operands(depth, color, intrinsic, frames=None):
     shape = tuple(int(s) for s in d.shape)
     if len(shape) != (2 if frames is None else 3) or (frames is not None and shape[0] != frames):
         raise RuntimeError(_UNSUPPORTED_IMAGE)
-    if tuple(int(s) for s in c.shape) != shape + (3,):
+    if not depth_only and tuple(int(s) for s in c.shape) != shape + (3,):
         raise RuntimeError(_UNSUPPORTED_IMAGE)
     if int(intrinsic.width) != shape[-1] or int(intrinsic.height) != shape[-2]:
         raise RuntimeError(_UNSUPPORTED_IMAGE)
     return d, c, dkind, converted
+
+
+class OdometryResult:
+    """What ScalableTSDFVolume.track_frame_to_model returns (the fields of Open3D's tensor odometry result, plus the rest of
+    hv_track_result):  transformation 4x4 float64 T_cw; fitness = inliers / valid source pixels and inlier_rmse (metres) of the
+    last full-resolution linearisation; information 6x6 float64 (its Gauss-Newton matrix H, anchor frame, order (omega, t));
+    success; iterations run per pyramid level (level 0 first); degenerate = bit l set when level l ended on a degenerate step;
+    inliers / valid counts; trace = None, or one dict per linearisation (level, iteration, status, inliers, valid, sq_error,
+    A 4x4, H 6x6, g 6, xi 6) when asked for."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, information, success, iterations, degenerate, inliers, valid,
+                 trace=None):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.information = information
+        self.success = success
+        self.iterations = iterations
+        self.degenerate = degenerate
+        self.inliers = inliers
+        self.valid = valid
+        self.trace = trace
+
+    def __repr__(self):
+        return (f"OdometryResult(success={self.success}, fitness={self.fitness:.4f}, inlier_rmse={self.inlier_rmse:.6f}, "
+                f"iterations={self.iterations})")
+
+
+def _trace_rows(rows):
+    out = []
+    iu = np.triu_indices(6)
+    for r in rows:
+        H = np.zeros((6, 6))
+        H[iu] = r[22:43]
+        H = H + np.triu(H, 1).T
+        out.append({"level": int(r[0]), "iteration": int(r[1]), "status": int(r[2]), "inliers": int(r[3]), "valid": int(r[4]),
+                    "sq_error": float(r[5]), "A": r[6:22].reshape(4, 4).copy(), "H": H, "g": r[43:49].copy(), "xi": r[49:55].copy()})
+    return out
 
 
 class _Volume:
@@ -1177,6 +1218,44 @@ class ScalableTSDFVolume(_Volume):
         if device:
             self._torch_out(self._torch_stream(dev), dev)
         return out
+
+    def track_frame_to_model(self, depth, intrinsic, extrinsic, depth_scale=1.0, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
+                             iterations=(10, 5, 4), depth_outlier_trunc=0.07, depth_huber_delta=0.05, trace=False):
+        """Point-to-plane alignment of one depth frame against the fused map rendered at extrinsic = T_cw_init: -> OdometryResult
+        whose transformation is the refined T_cw.  depth [H,W]: numpy or torch (either device), uint16 or any real dtype (as
+        float32), divided by depth_scale; H, W = intrinsic.height, intrinsic.width.  iterations: the cap per pyramid level, level 0
+        (full resolution) first; levels run coarse to fine.  Names and defaults follow Open3D's tensor odometry; the contract
+        (include/hipvol.h, hv_tsdf_track) is this project's own.  Reads the volume only.  A CUDA depth tensor is read after the
+        work queued on torch's current stream.  trace=True: the per-linearisation record (tests)."""
+        d, _, dkind, _ = _tsdf_operands(depth, None, intrinsic, depth_only=True)
+        H, W = int(d.shape[0]), int(d.shape[1])
+        iters = [int(i) for i in iterations]
+        prm = L.HvTrackParams()
+        prm.depth_scale, prm.depth_min, prm.depth_max = float(depth_scale), float(depth_min), float(depth_max)
+        prm.weight_threshold = float(weight_threshold)
+        prm.depth_outlier_trunc, prm.depth_huber_delta = float(depth_outlier_trunc), float(depth_huber_delta)
+        prm.n_levels = len(iters)
+        for i, n in enumerate(iters[:L.HV_TRACK_MAX_LEVELS]):
+            prm.iterations[i] = n
+        res = L.HvTrackResult()
+        intr = intrinsic.as_array()
+        T0 = _as_f64_4x4(extrinsic)
+        steps = max(sum(iters), 1)
+        rows = np.zeros((steps, L.HV_TRACK_TRACE_STRIDE), np.float64) if trace else None
+        n_rows = ctypes.c_int64()
+        loc = L.location(d)
+        ts = self._torch_in(d) if loc == L.HV_DEVICE else None
+        try:
+            L.check(self._lib.hv_tsdf_track(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T0), ctypes.byref(prm), ctypes.byref(res),
+                                            L.ptr(rows), steps if trace else 0, ctypes.byref(n_rows), loc))
+        finally:
+            if ts is not None:
+                self._torch_out(ts, d.device)
+        n_levels = min(len(iters), L.HV_TRACK_MAX_LEVELS)
+        return OdometryResult(np.array(res.T_cw, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
+                              np.array(res.information, np.float64).reshape(6, 6), bool(res.success),
+                              tuple(int(res.iterations[i]) for i in range(n_levels)), int(res.degenerate), int(res.inliers),
+                              int(res.valid), _trace_rows(rows[:n_rows.value]) if trace else None)
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):

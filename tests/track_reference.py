@@ -1,0 +1,216 @@
+"""A numpy restatement of hv_tsdf_track (the contract in include/hipvol.h) - test infrastructure, no GPU.
+
+The model is whatever the caller hands in per pyramid level (depth, world normal and hit mask at the initial pose: the GPU's own
+ray_cast maps in the GPU tests, an analytic scene in the CPU tests).  Everything else - source pyramid, association, linearisation,
+Cholesky solve, update, stopping and outputs - follows the kernels operation by operation (float32 pyramid, float64 geometry in the
+same order), so per pixel the two agree bit for bit and the sums differ only by their summation order.
+"""
+import numpy as np
+
+# the named constants of include/hipvol.h
+MAX_LEVELS = 8
+MIN_INLIERS = 6
+PIVOT_REL = 1e-10
+CONVERGED = 1e-6
+TRACE_STRIDE = 56
+
+_f32 = np.float32
+
+
+def source_level0(depth, depth_scale=1.0, depth_min=0.1, depth_max=3.0):
+    """depth / depth_scale in float32; 0 where not finite or outside (depth_min, depth_max] (compared in float64)."""
+    d = np.asarray(depth)
+    d = d.astype(_f32) / _f32(depth_scale)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(d) & (d.astype(np.float64) > depth_min) & (d.astype(np.float64) <= depth_max)
+    return np.where(ok, d, _f32(0)).astype(_f32)
+
+
+def downsample(d, trunc):
+    """level l -> l + 1: float32 mean of the valid 2x2 children in the order (2u,2v), (2u+1,2v), (2u,2v+1), (2u+1,2v+1); valid iff
+    max - min of the valid children <= trunc."""
+    h, w = d.shape[0] // 2, d.shape[1] // 2
+    kids = (d[0:2 * h:2, 0:2 * w:2], d[0:2 * h:2, 1:2 * w:2], d[1:2 * h:2, 0:2 * w:2], d[1:2 * h:2, 1:2 * w:2])
+    s = np.zeros((h, w), _f32)
+    n = np.zeros((h, w), np.int32)
+    mx = np.full((h, w), -np.inf, _f32)
+    mn = np.full((h, w), np.inf, _f32)
+    for c in kids:
+        v = c > 0
+        s = np.where(v, s + c, s).astype(_f32)
+        mx = np.where(v, np.maximum(mx, c), mx)
+        mn = np.where(v, np.minimum(mn, c), mn)
+        n += v
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ok = (n > 0) & ((mx - mn).astype(np.float64) <= trunc)
+        out = np.where(ok, s / n.astype(_f32), _f32(0))
+    return out.astype(_f32)
+
+
+def pyramid(depth, n_levels, depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07):
+    levels = [source_level0(depth, depth_scale, depth_min, depth_max)]
+    for _ in range(1, n_levels):
+        levels.append(downsample(levels[-1], trunc))
+    return levels
+
+
+def level_intrinsics(K, level):
+    s = float(1 << level)
+    fx, fy, cx, cy = (float(k) for k in K)
+    return np.array([fx / s, fy / s, (cx + 0.5) / s - 0.5, (cy + 0.5) / s - 0.5])
+
+
+def associate(src, model, K, A, R0, trunc):
+    """-> (valid count, inlier arrays: pc [N,3] source camera points, q [N,3] model vertices, n [N,3] model normals, all anchor /
+    source camera frame, float64).  model = (depth [h,w], world normal [h,w,3], mask [h,w])."""
+    mdepth, mnormal, mmask = model
+    h, w = src.shape
+    fx, fy, cx, cy = (float(k) for k in K)
+    v, u = np.nonzero(src > 0)
+    valid = len(u)
+    d = src[v, u].astype(np.float64)
+    pc0, pc1, pc2 = d * ((u - cx) / fx), d * ((v - cy) / fy), d
+    p = transform(A, pc0, pc1, pc2)
+    keep = p[2] > 0
+    pc0, pc1, pc2, p = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p]
+    uf = np.floor(fx * p[0] / p[2] + cx + 0.5)
+    vf = np.floor(fy * p[1] / p[2] + cy + 0.5)
+    keep = (uf >= 0) & (uf < w) & (vf >= 0) & (vf < h)
+    pc0, pc1, pc2, p, uf, vf = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p], uf[keep], vf[keep]
+    ui, vi = uf.astype(np.int64), vf.astype(np.int64)
+    keep = np.asarray(mmask, bool)[vi, ui]
+    pc0, pc1, pc2, p, uf, vf, ui, vi = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p], uf[keep], vf[keep], ui[keep], vi[keep]
+    z = np.asarray(mdepth)[vi, ui].astype(np.float64)
+    q = np.stack([z * ((uf - cx) / fx), z * ((vf - cy) / fy), z], axis=1)
+    nw = np.asarray(mnormal)[vi, ui].astype(np.float64)
+    n = np.stack([R0[r, 0] * nw[:, 0] + R0[r, 1] * nw[:, 1] + R0[r, 2] * nw[:, 2] for r in range(3)], axis=1)
+    e = np.stack(p, axis=1) - q
+    keep = np.sqrt(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1] + e[:, 2] * e[:, 2]) <= trunc
+    pc = np.stack([pc0, pc1, pc2], axis=1)[keep]
+    return valid, pc, q[keep], n[keep]
+
+
+def transform(A, x, y, z):
+    return [A[r, 0] * x + A[r, 1] * y + A[r, 2] * z + A[r, 3] for r in range(3)]
+
+
+def residuals(A, pc, q, n):
+    """r = n . (A pc - q) and J = [p x n, n] of fixed associations."""
+    p = np.stack(transform(A, pc[:, 0], pc[:, 1], pc[:, 2]), axis=1)
+    e = p - q
+    r = n[:, 0] * e[:, 0] + n[:, 1] * e[:, 1] + n[:, 2] * e[:, 2]
+    J = np.stack([p[:, 1] * n[:, 2] - p[:, 2] * n[:, 1], p[:, 2] * n[:, 0] - p[:, 0] * n[:, 2], p[:, 0] * n[:, 1] - p[:, 1] * n[:, 0],
+                  n[:, 0], n[:, 1], n[:, 2]], axis=1)
+    return r, J
+
+
+def huber(r, delta):
+    a = np.abs(r)
+    with np.errstate(divide="ignore"):
+        return np.where(a <= delta, 1.0, delta / a)
+
+
+def linearise(src, model, K, A, R0, trunc, delta):
+    """-> dict(H 6x6, g 6, sq_error, inliers, valid)."""
+    valid, pc, q, n = associate(src, model, K, A, R0, trunc)
+    r, J = residuals(A, pc, q, n)
+    wJ = huber(r, delta)[:, None] * J
+    return {"H": wJ.T @ J, "g": wJ.T @ r, "sq_error": float(r @ r), "inliers": len(r), "valid": valid}
+
+
+def solve(H, g, inliers):
+    """Cholesky as the kernel does it -> (xi, degenerate)."""
+    if inliers < MIN_INLIERS:
+        return np.zeros(6), True
+    tr = float(np.trace(H))
+    L = np.zeros((6, 6))
+    for j in range(6):
+        d = H[j, j]
+        for q in range(j):
+            d -= L[j, q] * L[j, q]
+        if not d > PIVOT_REL * tr:
+            return np.zeros(6), True
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 6):
+            e = H[i, j]
+            for q in range(j):
+                e -= L[i, q] * L[j, q]
+            L[i, j] = e / L[j, j]
+    y = np.zeros(6)
+    for i in range(6):
+        e = -g[i]
+        for q in range(i):
+            e -= L[i, q] * y[q]
+        y[i] = e / L[i, i]
+    xi = np.zeros(6)
+    for i in range(5, -1, -1):
+        e = y[i]
+        for q in range(i + 1, 6):
+            e -= L[q, i] * xi[q]
+        xi[i] = e / L[i, i]
+    return xi, False
+
+
+def exp_twist(xi):
+    """[Rodrigues(omega), t] as a 4x4."""
+    w = np.asarray(xi[:3], np.float64)
+    th = float(np.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]))
+    sa = 1.0 if th < 1e-8 else np.sin(th) / th
+    sb = 0.5 if th < 1e-8 else (1.0 - np.cos(th)) / (th * th)
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    E = np.eye(4)
+    E[:3, :3] = np.eye(3) + sa * K + sb * (K @ K)
+    E[:3, 3] = xi[3:]
+    return E
+
+
+def converged(xi):
+    return float(np.linalg.norm(xi[:3]) + np.linalg.norm(xi[3:])) < CONVERGED
+
+
+def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05):
+    """The whole call.  model(level, K_level, h, w) -> (depth, world normal, mask) of the map cast at T_init.
+    -> dict(T_cw, fitness, inlier_rmse, information, success, iterations, degenerate, trace)."""
+    nl = len(iterations)
+    srcs = pyramid(depth, nl, depth_scale, depth_min, depth_max, trunc)
+    R0 = np.asarray(T_init, np.float64)[:3, :3]
+    A = np.eye(4)
+    trace, iters, degenerate, last = [], [0] * nl, 0, None
+    for level in range(nl - 1, -1, -1):
+        if iterations[level] == 0:
+            continue
+        Kl = level_intrinsics(K, level)
+        h, w = srcs[level].shape
+        maps = model(level, Kl, h, w)
+        for it in range(iterations[level]):
+            lin = linearise(srcs[level], maps, Kl, A, R0, trunc, delta)
+            xi, deg = solve(lin["H"], lin["g"], lin["inliers"])
+            row = dict(lin, level=level, iteration=it, A=A.copy(), xi=xi)
+            iters[level] += 1
+            if level == 0:
+                last = lin
+            if deg:
+                row["status"] = 2
+                trace.append(row)
+                degenerate |= 1 << level
+                break
+            A = exp_twist(xi) @ A
+            row["status"] = 1 if converged(xi) else 0
+            trace.append(row)
+            if row["status"] == 1:
+                break
+    Ai = np.eye(4)
+    Ai[:3, :3] = A[:3, :3].T
+    Ai[:3, 3] = -A[:3, :3].T @ A[:3, 3]
+    inl, val = last["inliers"], last["valid"]
+    return {"T_cw": Ai @ np.asarray(T_init, np.float64), "fitness": inl / val if val else 0.0,
+            "inlier_rmse": float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0, "information": last["H"],
+            "success": not (degenerate & 1) and inl >= MIN_INLIERS, "iterations": tuple(iters), "degenerate": degenerate,
+            "trace": trace}
+
+
+def pose_error(T_a, T_b):
+    """-> (distance between the camera centres in m, rotation angle in deg) of two T_cw."""
+    D = np.asarray(T_a, np.float64) @ np.linalg.inv(np.asarray(T_b, np.float64))
+    c = np.clip((np.trace(D[:3, :3]) - 1.0) / 2.0, -1.0, 1.0)
+    return float(np.linalg.norm(D[:3, 3])), float(np.degrees(np.arccos(c)))
