@@ -50,39 +50,21 @@ def bench_map():
 
 
 def test_kernel_matches_reference_step_by_step(bench_map):
+    """Every traced step through track_reference.check_call: counts exact, sums within the float64 summation bound, solve,
+    schedule and outputs."""
     s, vol, K, depth, _, T = bench_map
     i = 40
     T0 = perturbed(T[i], (1, 1, 0), (0, 1, -1), 2.0, 0.04)
     out = vol.track_frame_to_model(depth[i], K, T0, iterations=ITERATIONS, trace=True)
     assert out.success and len(out.trace) == sum(out.iterations)
-    srcs = tr.pyramid(depth[i], len(ITERATIONS))
-    maps = {}
-    for lv in range(len(ITERATIONS)):
-        Kl = tr.level_intrinsics(s.intrinsics, lv)
-        m = vol.ray_cast(_K(s.width >> lv, s.height >> lv, Kl), T0, 0.1, 3.0, 3.0, render_attributes=("depth", "normal", "mask"))
-        maps[lv] = (Kl, (m["depth"], m["normal"], m["mask"]))
-    A_final = T0 @ np.linalg.inv(out.transformation)
-    R0 = T0[:3, :3]
-    for k, row in enumerate(out.trace):
-        Kl, model = maps[row["level"]]
-        ref = tr.linearise(srcs[row["level"]], model, Kl, row["A"], R0, 0.07, 0.05)
-        what = (k, row["level"], row["iteration"])
-        assert row["valid"] == ref["valid"], what
-        assert abs(row["inliers"] - ref["inliers"]) <= 1e-3 * ref["inliers"], (what, row["inliers"], ref["inliers"])
-        Hs = np.abs(ref["H"]).max()
-        assert np.abs(row["H"] - ref["H"]).max() <= 1e-4 * Hs, what
-        assert np.abs(row["g"] - ref["g"]).max() <= 1e-4 * max(np.abs(ref["g"]).max(), 1e-6 * Hs), what
-        assert abs(row["sq_error"] - ref["sq_error"]) <= 1e-4 * ref["sq_error"], what
-        # the GPU's own H, g solved in float64 give the next state
-        nxt = out.trace[k + 1]["A"] if k + 1 < len(out.trace) else A_final
-        if row["status"] == 2:
-            assert np.array_equal(nxt, row["A"])
-        else:
-            xi = np.linalg.solve(row["H"], -row["g"])
-            assert np.abs(tr.exp_twist(xi) @ row["A"] - nxt).max() <= 1e-9, what
-    last = out.trace[-1]
-    assert last["level"] == 0 and out.inliers == last["inliers"] and np.array_equal(out.information, last["H"])
-    assert out.fitness == last["inliers"] / last["valid"] and np.isclose(out.inlier_rmse, np.sqrt(last["sq_error"] / last["inliers"]))
+
+    def model(level, Kl, h, w):
+        m = vol.ray_cast(_K(w, h, Kl), T0, 0.1, 3.0, 3.0, render_attributes=("depth", "normal", "mask"))
+        return m["depth"], m["normal"], m["mask"]
+
+    rep = tr.check_call(out, depth[i], s.intrinsics, T0, model, ITERATIONS)
+    print("step by step: %d rows, max xi rel %.3g, pivots near the threshold at %s" % (rep["rows"], rep["xi_rel"], rep["near_pivot"]))
+    assert not rep["near_pivot"]
 
 
 def test_accuracy_against_ground_truth(bench_map):

@@ -147,3 +147,166 @@ def test_pyramid_rules():
     u16 = tr.source_level0(np.array([[5000, 65535]], np.uint16), depth_scale=5000.0, depth_max=20.0)
     assert u16[0, 0] == 1.0 and u16[0, 1] == np.float32(65535) / np.float32(5000)
     assert np.allclose(tr.level_intrinsics(K, 1), [262.5, 262.5, 159.5, 119.5])
+
+
+# -- the source pyramid against plain per-pixel loops -----------------------------------------------------------------------------
+
+_f32 = np.float32
+
+
+def scalar_source(depth, depth_scale=1.0, depth_min=0.1, depth_max=3.0):
+    """hv_tsdf_track's level 0, one pixel at a time: float32 divide, compares in float64."""
+    h, w = depth.shape
+    out = np.zeros((h, w), _f32)
+    s = _f32(depth_scale)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        for v in range(h):
+            for u in range(w):
+                d = _f32(_f32(depth[v, u]) / s)
+                if np.isfinite(d) and float(d) > depth_min and float(d) <= depth_max:
+                    out[v, u] = d
+    return out
+
+
+def scalar_downsample(d, trunc):
+    """One level down, one parent at a time: the valid children in the order (2u,2v), (2u+1,2v), (2u,2v+1), (2u+1,2v+1)."""
+    h, w = d.shape[0] // 2, d.shape[1] // 2
+    out = np.zeros((h, w), _f32)
+    for v in range(h):
+        for u in range(w):
+            s, n, mx, mn = _f32(0.0), 0, _f32(-np.inf), _f32(np.inf)
+            for c in (d[2 * v, 2 * u], d[2 * v, 2 * u + 1], d[2 * v + 1, 2 * u], d[2 * v + 1, 2 * u + 1]):
+                if c > 0:
+                    s = _f32(s + c)
+                    mx, mn = max(mx, c), min(mn, c)
+                    n += 1
+            if n > 0 and float(_f32(mx - mn)) <= trunc:
+                out[v, u] = _f32(s / _f32(n))
+    return out
+
+
+SUB = _f32(1e-40)
+PLANTED = [np.nan, np.inf, -np.inf, -1.0, -0.0, 0.0, SUB, np.nextafter(_f32(0), _f32(1)), 0.25, np.nextafter(_f32(0.25), _f32(1)),
+           _f32(0.1), np.nextafter(_f32(0.1), _f32(0)), 3.0, np.nextafter(_f32(3.0), _f32(np.inf)), 1.0, 1.0625,
+           np.nextafter(_f32(1.0625), _f32(np.inf))]
+
+
+def _closed_form_frame(W, H):
+    from tests import tsdf_closed_form as cf
+
+    K = np.array([cf.K[0] * W / cf.W, cf.K[1] * H / cf.H, cf.K[2] * W / cf.W, cf.K[3] * H / cf.H])
+    return cf.render(cf.POSES[0], cf.camera(W, H, K))[0]
+
+
+def _planted_frame(h, w, seed):
+    rng = np.random.default_rng(seed)
+    d = rng.uniform(0.05, 3.5, (h, w)).astype(_f32)
+    pick = rng.random((h, w)) < 0.4
+    d[pick] = np.asarray(PLANTED, _f32)[rng.integers(0, len(PLANTED), int(pick.sum()))]
+    return d
+
+
+def _pairs_frame(h, w, seed):
+    """2x2 blocks of 1.0 and 1.0625 / the next float above (the trunc = 0.0625 edge), some children invalid."""
+    rng = np.random.default_rng(seed)
+    choices = np.asarray([0.0, 1.0, 1.0625, np.nextafter(_f32(1.0625), _f32(np.inf)), 1.03125], _f32)
+    return choices[rng.integers(0, len(choices), (h, w))]
+
+
+SHAPES_CPU = [(1, 9), (1, 64), (9, 1), (64, 1), (5, 7), (7, 5), (2, 2), (3, 3), (33, 17)]
+
+
+@pytest.mark.parametrize("h,w", SHAPES_CPU)
+@pytest.mark.parametrize("dmin,dmax", [(0.1, 3.0), (0.25, 3.0), (0.0, 2.5), (1.0, 1.0625)])
+def test_source_level0_matches_scalar_loop(h, w, dmin, dmax):
+    d = _planted_frame(h, w, h * 100 + w)
+    assert np.array_equal(tr.source_level0(d, 1.0, dmin, dmax), scalar_source(d, 1.0, dmin, dmax), equal_nan=False)
+
+
+@pytest.mark.parametrize("scale", [1000.0, 5000.0, 5000.1])
+@pytest.mark.parametrize("h,w", [(1, 64), (64, 1), (7, 5), (33, 17)])
+def test_source_level0_u16_matches_scalar_loop(h, w, scale):
+    rng = np.random.default_rng(h * 7 + w)
+    d = rng.integers(0, 20000, (h, w)).astype(np.uint16)
+    d.flat[::5] = 0
+    d.flat[1::5] = 65535
+    ref = scalar_source(d, scale, 0.1, 3.0)
+    assert np.array_equal(tr.source_level0(d, scale, 0.1, 3.0), ref)
+    assert (ref > 0).any()
+
+
+@pytest.mark.parametrize("h,w", SHAPES_CPU)
+@pytest.mark.parametrize("trunc", [0.07, 0.0625, 0.01])
+def test_downsample_matches_scalar_loop(h, w, trunc):
+    for d in (tr.source_level0(_planted_frame(h, w, h + w), 1.0, 0.0, 3.5), _pairs_frame(h, w, h * w)):
+        assert np.array_equal(tr.downsample(d, trunc), scalar_downsample(d, trunc))
+
+
+def test_downsample_trunc_edge_and_subnormal_blocks():
+    nxt = np.nextafter(_f32(1.0625), _f32(np.inf))
+    d = np.array([[1.0, 1.0625, 1.0, nxt, SUB, SUB], [1.0, 1.0625, 1.0, nxt, SUB, np.nextafter(_f32(0), _f32(1))]], _f32)
+    for out in (tr.downsample(d, 0.0625), scalar_downsample(d, 0.0625)):
+        assert out[0, 0] == _f32(1.03125) and out[0, 1] == 0.0 and 0.0 < out[0, 2] < 1e-39
+
+
+@pytest.mark.parametrize("crop", [(0, 0, 479, 641), (1, 3, 478, 637), (0, 0, 1, 641), (0, 0, 479, 1), (200, 300, 7, 5)])
+def test_pyramid_of_a_closed_form_frame_matches_scalar_loops(crop):
+    """641x479 closed-form frames (and crops) with planted values, five levels, every level against the loops."""
+    full = _closed_form_frame(641, 479)
+    full = np.where(np.random.default_rng(1).random(full.shape) < 0.02, _planted_frame(479, 641, 2), full).astype(_f32)
+    y, x, h, w = crop
+    d = full[y:y + h, x:x + w]
+    lv = tr.pyramid(d, 5, depth_min=0.1, depth_max=3.0, trunc=0.07)
+    ref = scalar_source(d)
+    assert np.array_equal(lv[0], ref)
+    for level in range(1, 5):
+        ref = scalar_downsample(ref, 0.07)
+        assert np.array_equal(lv[level], ref), level
+
+
+# -- the step checker the GPU tests use, on the reference's own call ---------------------------------------------------------------
+
+class _Out:
+    """The reference's track() in the shape of an OdometryResult with a trace."""
+
+    def __init__(self, r):
+        self.transformation, self.fitness, self.inlier_rmse = r["T_cw"], r["fitness"], r["inlier_rmse"]
+        self.information, self.success, self.iterations, self.degenerate = r["information"], r["success"], r["iterations"], r["degenerate"]
+        last = r["trace"][-1]
+        self.inliers, self.valid = last["inliers"], last["valid"]
+        self.trace = [{k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in row.items()} for row in r["trace"]]
+
+
+def test_check_call_accepts_the_reference_and_rejects_one_pixel():
+    """check_call passes the reference's own call; one pixel's worth of change to H, a count off by one or a wrong status fails it."""
+    import copy
+
+    w2, h2 = W // 4, H // 4
+    K2 = tr.level_intrinsics(K, 2)
+    depth = render(T_TRUE, K2, h2, w2)[0]
+    T0 = perturbed(T_TRUE, (1, 0, 1), (0, 1, 0), 1.0, 0.02)
+    its = (6, 3)
+    r = tr.track(depth, K2, T0, model_of(T0), iterations=its)
+    out = _Out(r)
+    rep = tr.check_call(out, depth, K2, T0, model_of(T0), its)
+    assert rep["rows"] == len(r["trace"]) and rep["xi_rel"] == 0.0 and not rep["near_pivot"]
+    row = out.trace[-1]
+    n = row["inliers"]
+
+    def broken(edit):
+        o = copy.deepcopy(out)
+        edit(o)
+        with pytest.raises(AssertionError):
+            tr.check_call(o, depth, K2, T0, model_of(T0), its)
+
+    def one_pixel(o):
+        o.trace[-1]["H"] = o.trace[-1]["H"] * (1.0 + 1.0 / n)
+
+    broken(one_pixel)
+    broken(lambda o: o.trace[0].update(inliers=o.trace[0]["inliers"] + 1))
+    broken(lambda o: o.trace[1].update(valid=o.trace[1]["valid"] - 1))
+    broken(lambda o: o.trace[-1].update(sq_error=o.trace[-1]["sq_error"] * (1.0 + 1.0 / n)))
+    broken(lambda o: o.trace[0].update(status=1))
+    broken(lambda o: setattr(o, "degenerate", o.degenerate ^ 1))
+    broken(lambda o: setattr(o, "iterations", (o.iterations[0] + 1, o.iterations[1])))
+    broken(lambda o: setattr(o, "inlier_rmse", np.nextafter(o.inlier_rmse, 1.0)))

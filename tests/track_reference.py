@@ -111,11 +111,42 @@ def huber(r, delta):
 
 
 def linearise(src, model, K, A, R0, trunc, delta):
-    """-> dict(H 6x6, g 6, sq_error, inliers, valid)."""
+    """-> dict(H 6x6, g 6, sq_error, inliers, valid, H_abs, g_abs).  Every term is the kernel's float64 product ((w J_a) J_b,
+    (w J_a) r, r r); H_abs and g_abs are the sums of the terms' absolute values (sq_error is its own), the scale of a summation
+    error bound."""
     valid, pc, q, n = associate(src, model, K, A, R0, trunc)
     r, J = residuals(A, pc, q, n)
-    wJ = huber(r, delta)[:, None] * J
-    return {"H": wJ.T @ J, "g": wJ.T @ r, "sq_error": float(r @ r), "inliers": len(r), "valid": valid}
+    w = huber(r, delta)
+    H, H_abs, g, g_abs = np.zeros((6, 6)), np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+    for a in range(6):
+        wa = w * J[:, a]
+        for b in range(a, 6):
+            t = wa * J[:, b]
+            H[a, b] = H[b, a] = t.sum()
+            H_abs[a, b] = H_abs[b, a] = np.abs(t).sum()
+        t = wa * r
+        g[a], g_abs[a] = t.sum(), np.abs(t).sum()
+    return {"H": H, "g": g, "sq_error": float((r * r).sum()), "inliers": len(r), "valid": valid, "H_abs": H_abs, "g_abs": g_abs}
+
+
+def pivots(H):
+    """-> the Cholesky pivots d_j of H as the kernel computes them, up to and including the first that is not positive."""
+    L = np.zeros((6, 6))
+    out = []
+    for j in range(6):
+        d = H[j, j]
+        for q in range(j):
+            d -= L[j, q] * L[j, q]
+        out.append(float(d))
+        if not d > 0.0:
+            break
+        L[j, j] = np.sqrt(d)
+        for i in range(j + 1, 6):
+            e = H[i, j]
+            for q in range(j):
+                e -= L[i, q] * L[j, q]
+            L[i, j] = e / L[j, j]
+    return out
 
 
 def solve(H, g, inliers):
@@ -165,7 +196,9 @@ def exp_twist(xi):
 
 
 def converged(xi):
-    return float(np.linalg.norm(xi[:3]) + np.linalg.norm(xi[3:])) < CONVERGED
+    """|omega| + |t| < CONVERGED, both norms as the kernel forms them."""
+    x = [float(v) for v in xi]
+    return float(np.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) + np.sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5])) < CONVERGED
 
 
 def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05):
@@ -207,6 +240,127 @@ def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth
             "inlier_rmse": float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0, "information": last["H"],
             "success": not (degenerate & 1) and inl >= MIN_INLIERS, "iterations": tuple(iters), "degenerate": degenerate,
             "trace": trace}
+
+
+EPS = 2.0 ** -53  # unit roundoff of float64
+XI_REL = 1e-12     # the solve of the same H, g: the same correctly rounded operations in the same order on both sides
+A_REL = 1e-13      # exp(xi) A: sin / cos of two libms and the order of a 4-term product
+
+
+def rigid_inverse(A):
+    Ai = np.eye(4)
+    Ai[:3, :3] = A[:3, :3].T
+    Ai[:3, 3] = -A[:3, :3].T @ A[:3, 3]
+    return Ai
+
+
+def pivot_near_threshold(H):
+    """True when a Cholesky pivot that decides the degenerate flag lies within rounding of PIVOT_REL * trace(H)."""
+    thr = PIVOT_REL * float(np.trace(H))
+    tol = 64.0 * EPS * float(np.abs(np.diag(H)).sum())
+    for d in pivots(H):
+        if abs(d - thr) <= tol:
+            return True
+        if not d > thr:
+            return False
+    return False
+
+
+def check_call(out, depth, K, T_init, model, iterations, depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05):
+    """Hold one traced hv_tsdf_track result (an OdometryResult with trace) to this restatement, step by step.
+
+    model(level, K_level, h, w) -> (depth, world normal, mask) of the map cast at T_init with the call's depth_min, depth_max and
+    weight_threshold (in the GPU tests: the public ray_cast, i.e. the same kernel the call uses).  Every traced row is linearised
+    here at the row's own state A.  Per pixel both sides do the same IEEE operations, so:
+      - valid and inliers are equal;
+      - H, g and the squared error differ only by the order of their float64 sums: |gpu - ref| <= 2 (n + 2) 2^-53 S element by
+        element, n the inliers and S the sum of the terms' absolute values (each order errs by at most ~n 2^-53 S; one pixel
+        contributes ~S / n, so one lost, doubled or mis-weighted pixel fails it);
+      - the row's H, g solved here give its xi and its degenerate decision (a pivot within rounding of the threshold is
+        reported in the result instead), status 1 iff converged(xi), and the next row's A is exp(xi) A, or A after status 2.
+    Then the schedule (coarse to fine, levels with 0 iterations absent, iterations from 0, a level ends at its first non-zero
+    status or its cap) and the outputs (iterations, degenerate bits, success, information, fitness, inlier_rmse, T_cw).
+    -> dict(rows, near_pivot [(row, level, iteration)], xi_rel: the largest relative xi difference)."""
+    nl = len(iterations)
+    T_init = np.asarray(T_init, np.float64)
+    R0 = T_init[:3, :3]
+    srcs = pyramid(depth, nl, depth_scale, depth_min, depth_max, trunc)
+    rows = out.trace
+    assert rows is not None and len(rows) == sum(out.iterations), (len(rows), out.iterations)
+    assert len(out.iterations) == nl and out.degenerate >> nl == 0, (out.iterations, out.degenerate)
+
+    # schedule
+    k = 0
+    for level in range(nl - 1, -1, -1):
+        if iterations[level] == 0:
+            assert out.iterations[level] == 0 and not out.degenerate >> level & 1, level
+            continue
+        start = k
+        while k < len(rows) and rows[k]["level"] == level:
+            k += 1
+        grp = rows[start:k]
+        assert 1 <= len(grp) <= iterations[level], (level, len(grp), iterations)
+        assert [r["iteration"] for r in grp] == list(range(len(grp))), level
+        assert all(r["status"] == 0 for r in grp[:-1]), (level, [r["status"] for r in grp])
+        assert grp[-1]["status"] in (1, 2) or len(grp) == iterations[level], (level, grp[-1]["status"], len(grp))
+        assert out.iterations[level] == len(grp), (level, out.iterations)
+        assert bool(out.degenerate >> level & 1) == (grp[-1]["status"] == 2), (level, out.degenerate)
+    assert k == len(rows), "rows out of the coarse-to-fine order"
+
+    # every step
+    maps, near, xi_rel = {}, [], 0.0
+    A_next = np.eye(4)
+    for k, row in enumerate(rows):
+        level = row["level"]
+        what = (k, level, row["iteration"])
+        if k == 0:
+            assert np.array_equal(row["A"], np.eye(4)), what
+        else:
+            assert np.abs(row["A"] - A_next).max() <= A_REL * max(1.0, np.abs(A_next).max()), (what, row["A"], A_next)
+        if level not in maps:
+            Kl = level_intrinsics(K, level)
+            h, w = srcs[level].shape
+            maps[level] = (Kl, model(level, Kl, h, w))
+        Kl, m = maps[level]
+        ref = linearise(srcs[level], m, Kl, row["A"], R0, trunc, delta)
+        assert row["valid"] == ref["valid"], (what, "valid", row["valid"], ref["valid"])
+        assert row["inliers"] == ref["inliers"], (what, "inliers", row["inliers"], ref["inliers"])
+        bar = 2.0 * (ref["inliers"] + 2) * EPS
+        dH = np.abs(row["H"] - ref["H"])
+        assert (dH <= bar * ref["H_abs"]).all(), (what, "H", float((dH / np.maximum(ref["H_abs"], 1e-300)).max()), bar)
+        dg = np.abs(row["g"] - ref["g"])
+        assert (dg <= bar * ref["g_abs"]).all(), (what, "g", float((dg / np.maximum(ref["g_abs"], 1e-300)).max()), bar)
+        assert abs(row["sq_error"] - ref["sq_error"]) <= bar * ref["sq_error"], (what, "e", row["sq_error"], ref["sq_error"])
+
+        xi_ref, deg_ref = solve(row["H"], row["g"], row["inliers"])
+        if row["inliers"] >= MIN_INLIERS and pivot_near_threshold(row["H"]):
+            near.append(what)
+        else:
+            assert (row["status"] == 2) == deg_ref, (what, "degenerate decision", row["status"], pivots(row["H"]))
+        if row["status"] == 2:
+            assert not row["xi"].any(), what
+            A_next = row["A"]
+        else:
+            if not deg_ref:
+                scale = np.abs(xi_ref).max()
+                rel = float(np.abs(row["xi"] - xi_ref).max() / scale) if scale > 0 else float(np.abs(row["xi"]).max())
+                xi_rel = max(xi_rel, rel)
+                assert rel <= XI_REL, (what, "xi", row["xi"], xi_ref)
+            assert (row["status"] == 1) == converged(row["xi"]), (what, row["status"], row["xi"])
+            A_next = exp_twist(row["xi"]) @ row["A"]
+
+    # outputs
+    last = rows[-1]
+    assert last["level"] == 0
+    inl, val = last["inliers"], last["valid"]
+    assert out.success == (last["status"] != 2 and inl >= MIN_INLIERS), (out.success, last["status"], inl)
+    assert np.array_equal(out.information, last["H"])
+    assert out.inliers == inl and out.valid == val
+    assert out.fitness == (inl / val if val else 0.0), (out.fitness, inl, val)
+    assert out.inlier_rmse == (float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0), (out.inlier_rmse, last["sq_error"], inl)
+    T_exp = rigid_inverse(A_next) @ T_init
+    assert np.abs(out.transformation - T_exp).max() <= 1e-12 * (1.0 + np.abs(T_init).max()), (out.transformation, T_exp)
+    return {"rows": len(rows), "near_pivot": near, "xi_rel": xi_rel}
 
 
 def pose_error(T_a, T_b):
