@@ -340,6 +340,51 @@ int hv_tsdf_integrate_frames(hv_volume *v, const void *const *depth_frames, int3
                              int32_t n_frames, int32_t height, int32_t width, const double *intr, const double *T_cw,
                              double depth_scale, double depth_trunc);
 
+/* De-integration and re-integration (BundleFusion's map correction after a loop closure: take a frame out at the pose it was
+ * fused with, put it back at the corrected one; Open3D's legacy ScalableTSDFVolume has none).  This project's own contract, not
+ * Open3D-pinned:
+ *   prep       depth conversion (dtype, depth_scale, depth_trunc, NaN / inf / negative), the volume's rectify maps and colour order
+ *              exactly as in hv_tsdf_integrate*: a frame handed here is sampled exactly as integrate sampled it.
+ *   touch set  the units integrate's touch pass would claim for the frame and pose (the volume's stride, +/- sdf_trunc; owned units
+ *              only when owner-sharded).  They are only LOOKED UP: nothing is claimed or grown; absent units are skipped.
+ *   predicate  within the touch set a voxel is updated under integrate's predicate (projection, valid depth, sdf >= -trunc) with
+ *              integrate's per-frame sample t (float32) and colour c.
+ *   update     a call of F frames acts as consecutive chunks of at most HV_TSDF_DEINTEGRATE_MAX_FRAMES frames, in call order.  Per
+ *              voxel and chunk, n = the chunk's frames that sample it, w0 / tsdf0 / sums its state before the chunk:
+ *                w0 < n   unchanged in all five planes, counted once in voxels_underflow;
+ *                w0 == n  the state of a freshly claimed voxel: weight 0, colour sums 0, tsdf 0 (what hv_tsdf_dump shows for a voxel
+ *                         no frame has touched);
+ *                else     w = w0 - n, each colour sum loses the frames' colour bytes exactly, and
+ *                         tsdf = (float)(((double)tsdf0 * w0 - sum_f (double)t_f) / (double)(w0 - n)), the sum in frame order, in
+ *                         double, without contraction (one double and one float rounding).
+ *              Weights and colour sums come back bit for bit; the tsdf mean carries the ~half-ulp rounding of every stored mean,
+ *              scaled by about w0 / w by the removal (63 of 64 observations removed: ~64 x 3e-8).
+ *   stamping   every unit of the touch set that the volume holds is stamped with a new frame counter value (the incremental
+ *              extractions recompute it, hv_tsdf_dirty_keys reports it).
+ *   reintegrate  hv_tsdf_deintegrate_batch at T_cw_old, then hv_tsdf_integrate_batch at T_cw_new (both F*16), over frames
+ *              uploaded and rectified once: bitwise the result of the two calls, the integrate side's pool growth included.
+ *   stats      may be NULL: the call is then asynchronous on the volume's stream, like integrate.  Otherwise the call waits once
+ *              and fills them (of the de-integration side).
+ *   errors     HV_ERR_MODE for a non-TSDF or tile-sharded volume (hv_tsdf_set_tile: a rank holds partial sums of a voxel that halo
+ *              merges move between ranks); owner-sharded volumes are supported (each rank removes from its own units).
+ *              HV_ERR_INVALID for bad sizes or arguments, as integrate. */
+#define HV_TSDF_DEINTEGRATE_MAX_FRAMES 64
+typedef struct hv_deintegrate_stats {
+    int64_t units_listed;     /* sum over frames of the units the frame's touch set names (owned units only when owner-sharded) */
+    int64_t units_missing;    /* ... of those, absent from the volume: skipped */
+    int64_t voxels_removed;   /* voxel observations removed */
+    int64_t voxels_underflow; /* voxels left unchanged because they hold fewer observations than were to be removed */
+} hv_deintegrate_stats;
+int hv_tsdf_deintegrate(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int32_t height, int32_t width,
+                        const double *intr, const double *T_cw, double depth_scale, double depth_trunc, int32_t loc,
+                        hv_deintegrate_stats *stats);
+int hv_tsdf_deintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int32_t n_frames,
+                              int32_t height, int32_t width, const double *intr, const double *T_cw, double depth_scale,
+                              double depth_trunc, int32_t loc, hv_deintegrate_stats *stats);
+int hv_tsdf_reintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int32_t n_frames,
+                              int32_t height, int32_t width, const double *intr, const double *T_cw_old, const double *T_cw_new,
+                              double depth_scale, double depth_trunc, int32_t loc, hv_deintegrate_stats *stats);
+
 /* Undistort / rectify on the device.  The reference remaps every keyframe on the host before it is fused
  * (estimate_depth_if_needed_and_rectify, volumetric_integrator_base.py:1017-1043: cv2.remap colour INTER_LINEAR, depth INTER_NEAREST,
  * maps from cv2.initUndistortRectifyMap, :758-786).  With maps set (float32 [H,W], at `loc`; copied), every frame handed to

@@ -71,6 +71,18 @@ class HvTrackResult(_c.Structure):
     ]
 
 
+HV_TSDF_DEINTEGRATE_MAX_FRAMES = 64
+
+
+class HvDeintegrateStats(_c.Structure):
+    _fields_ = [
+        ("units_listed", _i64),
+        ("units_missing", _i64),
+        ("voxels_removed", _i64),
+        ("voxels_underflow", _i64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -152,6 +164,10 @@ SIGNATURES = {
     "hv_tsdf_extract_points_f32": (_i32, [_vp, _vp, _vp, _i64, _pi64]),
     "hv_tsdf_extract_point_normals": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_ray_cast": (_i32, [_vp, _i32, _i32, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "hv_tsdf_deintegrate": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _f64, _f64, _i32, _c.POINTER(HvDeintegrateStats)]),
+    "hv_tsdf_deintegrate_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f64, _f64, _i32, _c.POINTER(HvDeintegrateStats)]),
+    "hv_tsdf_reintegrate_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _i32,
+                                         _c.POINTER(HvDeintegrateStats)]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),

@@ -471,6 +471,11 @@ struct hv_volume {
     // hv_semantic_fuse_keyframe: the keyframe's filtered depth and object-id image ([npx f32][npx i32])
     void *kf_buf = nullptr;
     size_t kf_buf_bytes = 0;
+    // hv_tsdf_deintegrate*: [counters 256 B][missing-unit keys cap u64][their frame masks cap u64] - the set of units a call names
+    // that the volume does not hold, kept only to count each (frame, unit) once for the stats; cap = deint_miss_cap
+    void *deint_buf = nullptr;
+    size_t deint_buf_bytes = 0;
+    uint64_t deint_miss_cap = 0;
 
     // profiling
     bool profiling = false;

@@ -132,6 +132,30 @@ class OdometryResult:
                 f"iterations={self.iterations})")
 
 
+class DeintegrationStats:
+    """What ScalableTSDFVolume.deintegrate* / reintegrate_batch return (hv_deintegrate_stats): units_listed = units the frames'
+    touch sets name, summed over frames; units_missing = of those, absent from the volume (skipped); voxels_removed = voxel
+    observations taken out; voxels_underflow = voxels left unchanged because they held fewer observations than were to go."""
+
+    __slots__ = ("units_listed", "units_missing", "voxels_removed", "voxels_underflow")
+
+    def __init__(self, units_listed=0, units_missing=0, voxels_removed=0, voxels_underflow=0):
+        self.units_listed = int(units_listed)
+        self.units_missing = int(units_missing)
+        self.voxels_removed = int(voxels_removed)
+        self.voxels_underflow = int(voxels_underflow)
+
+    def as_tuple(self):
+        return (self.units_listed, self.units_missing, self.voxels_removed, self.voxels_underflow)
+
+    def __eq__(self, other):
+        return isinstance(other, DeintegrationStats) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return (f"DeintegrationStats(units_listed={self.units_listed}, units_missing={self.units_missing}, "
+                f"voxels_removed={self.voxels_removed}, voxels_underflow={self.voxels_underflow})")
+
+
 def _trace_rows(rows):
     out = []
     iu = np.triu_indices(6)
@@ -1069,6 +1093,60 @@ class ScalableTSDFVolume(_Volume):
         finally:
             if ts is not None:
                 self._torch_out(ts, depth.device)
+
+    def deintegrate(self, image, intrinsic, extrinsic):
+        """Take the observations integrate(image, intrinsic, extrinsic) added back out of the map (include/hipvol.h,
+        hv_tsdf_deintegrate): image and extrinsic must be what that frame was fused with.  Waits for the GPU and returns
+        DeintegrationStats."""
+        depth, color, dkind, converted = _tsdf_operands(image.depth, image.color, intrinsic)
+        H, W = int(depth.shape[0]), int(depth.shape[1])
+        intr = intrinsic.as_array()
+        T = _as_f64_4x4(extrinsic)
+        st = L.HvDeintegrateStats()
+        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_deintegrate(
+            self._h, L.ptr(depth), dkind, L.ptr(color), H, W, L.ptr(intr), L.ptr(T), image.depth_scale, image.depth_trunc,
+            L.location(depth), ctypes.byref(st)))
+        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
+
+    def _batch_operands(self, depth, color, intrinsic, *extrinsics):
+        F = int(depth.shape[0]) if len(depth.shape) == 3 else -1
+        depth, color, dkind, converted = _tsdf_operands(depth, color, intrinsic, frames=F)
+        Ts = []
+        for T in extrinsics:
+            T = np.asarray(T, dtype=np.float64)
+            if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
+                raise RuntimeError(_UNSUPPORTED_IMAGE)
+            Ts.append(np.ascontiguousarray(T.reshape(F, 16)))
+        return F, depth, color, dkind, converted, Ts
+
+    def deintegrate_batch(self, depth, color, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
+        """Take F frames ([F,H,W] depth, [F,H,W,3] colour, [F,4,4] T_cw they were fused with) back out of the map, in chunks of 64
+        frames in order.  Waits for the GPU and returns DeintegrationStats; zero frames is a no-op."""
+        F, depth, color, dkind, converted, (T,) = self._batch_operands(depth, color, intrinsic, extrinsics)
+        if F == 0:
+            return DeintegrationStats()
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        intr = intrinsic.as_array()
+        st = L.HvDeintegrateStats()
+        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_deintegrate_batch(
+            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(T), float(depth_scale), float(depth_trunc),
+            L.location(depth), ctypes.byref(st)))
+        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
+
+    def reintegrate_batch(self, depth, color, intrinsic, old_extrinsics, new_extrinsics, depth_scale=1.0, depth_trunc=4.0):
+        """Move F fused frames from the poses they were fused with (old_extrinsics) to corrected ones (new_extrinsics): the
+        result of deintegrate_batch(old) followed by integrate_batch(new), bit for bit, with the frames uploaded once.  Waits for
+        the GPU and returns the de-integration's DeintegrationStats; zero frames is a no-op."""
+        F, depth, color, dkind, converted, (To, Tn) = self._batch_operands(depth, color, intrinsic, old_extrinsics, new_extrinsics)
+        if F == 0:
+            return DeintegrationStats()
+        H, W = int(depth.shape[1]), int(depth.shape[2])
+        intr = intrinsic.as_array()
+        st = L.HvDeintegrateStats()
+        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_reintegrate_batch(
+            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(To), L.ptr(Tn), float(depth_scale),
+            float(depth_trunc), L.location(depth), ctypes.byref(st)))
+        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
