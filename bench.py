@@ -3,6 +3,12 @@
 
 Contract (driver): ``python bench.py --gpus N --steps K --warmup W`` prints ONE JSON line on rank 0.
 For N > 1 the driver launches it with torch.distributed.run (one rank per GPU, RCCL).
+A plain run does what the headline needs and nothing else: frames into HBM, cold pass, clock ramp and warm-up, the K timed steps,
+the outputs when ``--dump-outputs`` asks for them, the line (metric, value, ms_per_step, config, per-rank and merge figures of the
+timed region; ``cold_clock``: the W + K steps of the cold pass are what the device executes ahead of the ramp, so they stay where
+they are - 25 ms at the default command - and their figure is free).  ``--full`` adds everything else this file measures - every
+object listed below, each a run of its own after the timed region - to the same line; the timed region and the headline keys are
+the same with and without it.
 ``--dump-outputs DIR`` also writes the volume the timed steps built as .npy files (dump_outputs), so that two builds can be
 compared output for output: with the same arguments the input frames are the same on every run.
 
@@ -22,7 +28,7 @@ N > 1 ("strong" scaling: total work is fixed): every rank sees every frame; --sh
 fused and stored by GPU hash(unit index) % N (SURVEY §8e "zero reduce" form: bit-identical to one GPU, no
 collective while fusing); --sharding tile: north-star image tiles + RCCL merge of the shared units (timed).
 
-Objects on the JSON line (N = 1):
+Objects on the JSON line with ``--full`` (N = 1; ``--no-cpu-baseline`` / ``--no-secondary`` / ``--no-batch32`` drop some of them again):
   roofline      the dominant kernel of the timed region, the multi-frame sweep k_tsdf_sweep_column, against the bound
                 SURVEY 8d names for the path: HBM.  achieved = BATCH-level algorithmic bytes (oracle: distinct units
                 touched by the batch x 81 920 B read + distinct voxels updated x 20 B written - the sweep reads and
@@ -100,9 +106,10 @@ def load_frames(config, n_frames, start=0, rank=0, barrier=None):
             np.savez(tmp, depth=depth, rgb=rgb, T=T)
             os.replace(tmp, cache)
         except OSError:
-            if barrier is None:
-                return s, depth, rgb, T
-            raise
+            if barrier is not None:
+                raise
+        if barrier is None:
+            return s, depth, rgb, T  # just rendered: reading 1.3 GB back from the cache would only cost seconds
     if barrier is not None:
         barrier()
     try:
@@ -225,8 +232,7 @@ def live_pmc(args, B, kernel_substr="k_tsdf_sweep"):
     if os.environ.get("BENCH_LIVE_PMC", "1") == "0" or shutil.which("rocprofv3") is None:
         return None
     child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(args.steps), "--warmup", str(args.warmup), "--clock-ramp-steps",
-             str(args.clock_ramp_steps), "--frames-per-step", str(B), "--window", args.window, "--config", args.config, "--no-cpu-baseline",
-             "--no-secondary"]
+             str(args.clock_ramp_steps), "--frames-per-step", str(B), "--window", args.window, "--config", args.config]  # (a plain run: no --full)
     cold = (args.warmup + args.steps) if args.clock_ramp_steps > 0 else 0  # the cold-clock pass comes first
     lo = cold + args.clock_ramp_steps + args.warmup
     hi = lo + args.steps
@@ -589,11 +595,15 @@ def main():
     ap.add_argument("--clock-ramp-steps", type=int, default=60, help="untimed steps before the warm-up steps (device clock ramp, ~40 ms)")
     ap.add_argument("--config", default="synthetic_640x480_5mm")
     ap.add_argument("--window", choices=["sliding", "replay"], default="sliding")
-    ap.add_argument("--cpu-budget-s", type=float, default=25.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else this file measures (CPU baseline and oracle counts, roofline with live "
+                         "rocprofv3 passes, replay / online / 32-frame / extraction / host-fed / TUM / other-shape / voxel-grid / semantic legs, "
+                         "the sharded EuRoC leg at N > 1) and report it on the same line; off: the headline alone")
+    ap.add_argument("--cpu-budget-s", type=float, default=25.0, help="--full: seconds the timed CPU baseline may take")
     ap.add_argument("--cpu-threads", type=int, default=0, help="OpenMP threads of the CPU baseline; 0 = min(os.cpu_count(), 32) (the stated policy)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the replay / online / extraction / voxel-grid legs (profiling runs)")
-    ap.add_argument("--no-batch32", action="store_true", help="skip the 32-frames-per-call leg (profiling runs: every sweep launch of the command is then a --frames-per-step one)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline, the oracle counts and the rooflines that need them")
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the replay / online / extraction / voxel-grid legs (profiling runs)")
+    ap.add_argument("--no-batch32", action="store_true", help="--full without the 32-frames-per-call leg (profiling runs: every sweep launch of the command is then a --frames-per-step one)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--force-dist", action="store_true",
                     help="initialise the process group (and run every barrier / all-reduce / all-gather of the N > 1 line) with ONE rank: "
@@ -747,7 +757,7 @@ def main():
     fps = frames / elapsed
     units_allocated = int(vol.num_blocks())
     euroc_sharded = None
-    if dist is not None and args.sharding == "tile" and not args.no_secondary:
+    if args.full and dist is not None and args.sharding == "tile" and not args.no_secondary:
         try:  # (every rank takes part: collectives inside)
             euroc_sharded = euroc_sharded_leg(rank, world, local_rank, dist, args.backend, args.sharding)
         except Exception as e:  # a secondary leg must never cost the headline line
@@ -755,7 +765,7 @@ def main():
 
             traceback.print_exc()
             euroc_sharded = {"error": f"{type(e).__name__}: {e}"}
-    secondary = world == 1 and args.mode == "batch" and not args.no_secondary
+    secondary = args.full and world == 1 and args.mode == "batch" and not args.no_secondary
 
     # ---- secondary legs (single GPU): extraction of the volume just built, replay figure, online mode ----
     extraction = replay = online = batch32 = None
@@ -936,7 +946,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             # the timed CPU baseline belongs to the N=1 line; at N>1 a two-step oracle pass still provides the counts
             budget = args.cpu_budget_s if world == 1 else 0.0
             cpu = cpu_baseline_and_counts(s, depth_h, rgb_h, T_h, B, args.steps, budget, args.cpu_threads if world == 1 else min(32, os.cpu_count() or 1), args.window)
@@ -1048,6 +1058,7 @@ def main():
                 "units_allocated": units_allocated,
                 "parity_pinned": False,  # Open3D (the reference's TSDF arithmetic) is not in the image: the oracle is a restatement (README)
                 "clock_ramp_steps": args.clock_ramp_steps,
+                "full": args.full,
                 "build_digest": digest,
             },
             "roofline": roofline,

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round evidence in one GPU call: GPU test suite, rocprofv3 kernel stats + PMC passes of the default bench command
-# (tools/profile_round.sh), the VOXEL_GRID and semantic kernel tables + traffic passes, then the default bench line (which parses
-# the summaries), the two sweep forms, the N = 8 line on the one GPU, the ownership-sharding projection.  Every profiler run sits
+# (tools/profile_round.sh), the VOXEL_GRID and semantic kernel tables + traffic passes, then the full bench line (`bench.py --full`, which parses
+# the summaries; it and the N = 8 lines go straight to profiles/$ROUND), the two sweep forms, the N = 8 line on the one GPU, the ownership-sharding projection.  Every profiler run sits
 # under its own `timeout`.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 ROUND=${ROUND:-r06}
@@ -43,8 +43,8 @@ python tools/pmc_summary.py --json gpurun_out/pmc_semantic_scannet_2mm.json --co
 cp gpurun_out/pmc_semantic.json gpurun_out/pmc_semantic_scannet_2mm.json profiles/$ROUND/
 grep -E "sem|shadow" gpurun_out/sem2_pmc_summary.txt | cut -c1-200 | head -8
 timeout 200 python __graft_entry__.py --smoke > gpurun_out/smoke.log 2>&1; tail -1 gpurun_out/smoke.log
-timeout 900 python bench.py > gpurun_out/bench_n1.log 2>&1
-grep '^{"metric"' gpurun_out/bench_n1.log > gpurun_out/bench_n1.json; cut -c1-1500 gpurun_out/bench_n1.json
+timeout 900 python bench.py --full > profiles/$ROUND/bench_n1.log 2>&1
+grep '^{"metric"' profiles/$ROUND/bench_n1.log > profiles/$ROUND/bench_n1.json; cut -c1-1500 profiles/$ROUND/bench_n1.json
 timeout 250 python tools/sweep_variants.py --steps 9 --warmup 3 --repeat 3 "HV_TSDF_SWEEP=4" "HV_TSDF_SWEEP=4 HV_TSDF_SWEEP_ZS=2" "HV_TSDF_SWEEP=4 HV_TSDF_PIPELINE=0" "HV_TSDF_SWEEP=2" 2>/dev/null | tail -4 > gpurun_out/sweep_forms.jsonl; cut -c1-200 gpurun_out/sweep_forms.jsonl
 for SH in owner tile; do
   BENCH_LIVE_PMC=0 timeout 300 python bench.py --force-dist --sharding $SH --steps 6 --warmup 2 --clock-ramp-steps 4 --no-secondary --no-cpu-baseline > gpurun_out/bench_nccl1_$SH.log 2>&1
@@ -55,7 +55,7 @@ timeout 250 python tools/simulate_ranks.py --worlds 1,2,4,8 --steps 12 > gpurun_
 # the driver's own N = 8 command shape on this one GPU (eight ranks share device 0, gloo transport: rendezvous, per-rank load_frames,
 # eight pools in one HBM, the per_rank block; NOT a scaling number)
 for SH in owner tile; do
-  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29531 bench.py --gpus 8 --steps 6 --warmup 2 --clock-ramp-steps 4 --all-on-device0 --backend gloo --sharding $SH > gpurun_out/bench_n8_$SH.log 2>&1
-  grep '^{"metric"' gpurun_out/bench_n8_$SH.log > gpurun_out/bench_n8_$SH.json; python -c "
-import json; z=json.load(open('gpurun_out/bench_n8_$SH.json')); print('n8 $SH', z['value'], z['n_gpus'], z.get('per_rank',{}).get('units_held'), z.get('merge'))" 2>&1 | tail -1 | cut -c1-400
+  timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29531 bench.py --full --gpus 8 --steps 6 --warmup 2 --clock-ramp-steps 4 --all-on-device0 --backend gloo --sharding $SH > profiles/$ROUND/bench_n8_$SH.log 2>&1
+  grep '^{"metric"' profiles/$ROUND/bench_n8_$SH.log > profiles/$ROUND/bench_n8_$SH.json; python -c "
+import json; z=json.load(open('profiles/$ROUND/bench_n8_$SH.json')); print('n8 $SH', z['value'], z['n_gpus'], z.get('per_rank',{}).get('units_held'), z.get('merge'))" 2>&1 | tail -1 | cut -c1-400
 done

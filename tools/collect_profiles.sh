@@ -4,7 +4,7 @@ ROUND=${ROUND:-r06}
 cd "$(dirname "$0")/.."
 P=profiles/$ROUND
 mkdir -p $P
-for f in bench_n1.json bench_n8_owner.json bench_n8_tile.json bench_nccl1_owner.json bench_nccl1_tile.json pytest_gpu.log smoke.log sweep_forms.jsonl simulate_ranks.jsonl \
+for f in bench_nccl1_owner.json bench_nccl1_tile.json pytest_gpu.log smoke.log sweep_forms.jsonl simulate_ranks.jsonl \
          memset_split_semantic.json memset_split_semantic_scannet_2mm.json pmc_voxel_grid.json pmc_semantic.json pmc_semantic_scannet_2mm.json; do
   cp gpurun_out/$f $P/ 2>/dev/null
 done

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Produces the rocprofv3 evidence for one round under gpurun_out/prof_round/ (copy the summaries to profiles/rNN/):
-#   kernel-trace + stats (timing) of the DEFAULT bench command, then FETCH_SIZE and WRITE_SIZE in separate --pmc
+#   kernel-trace + stats (timing) of the default `bench.py --full` command without its CPU baseline, then FETCH_SIZE and WRITE_SIZE in separate --pmc
 #   passes, one SQ pass and one TCP pass (counters only: --pmc with --kernel-trace, no other trace domain), all on the
 #   same command so that per-launch means line up with the bench line (extraction: k_unit_masks / k_mc_classify = the incremental
 #   ticks of bench.py's extraction leg, "<name>@full" = its forced full pass); tools/pmc_summary.py merges the passes into
@@ -13,7 +13,7 @@ cd /tmp && export TMPDIR=/tmp
 STEPS=${STEPS:-20}; WARM=${WARM:-5}; RAMP=${RAMP:-60}   # bench.py runs RAMP clock-ramp steps, then WARM warm-up steps, then the timed STEPS
 FB=${FB:-64}   # frames per step (bench.py --frames-per-step)
 KEY="steps=$STEPS warmup=$WARM B=$FB window=sliding config=synthetic_640x480_5mm"
-BENCH="python $R/bench.py --steps $STEPS --warmup $WARM --frames-per-step $FB --clock-ramp-steps $RAMP --no-cpu-baseline --no-batch32"
+BENCH="python $R/bench.py --full --steps $STEPS --warmup $WARM --frames-per-step $FB --clock-ramp-steps $RAMP --no-cpu-baseline --no-batch32"
 LO=$((WARM+STEPS+RAMP+WARM)); HI=$((LO+STEPS))   # bench.py: cold pass (WARM + STEPS), ramp, warm-up, then the timed steps
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- $BENCH > $O/kt.log 2>&1
 cp $O/kt/bench_kernel_stats.csv $O/rocprofv3_kernel_stats.csv 2>/dev/null || find $O/kt -name "*kernel_stats.csv" -exec cp {} $O/rocprofv3_kernel_stats.csv \;
