@@ -543,6 +543,38 @@ int hv_tsdf_track(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t 
                   const double *T_cw_init, const hv_track_params *params, hv_track_result *result, double *trace, int64_t trace_cap,
                   int64_t *trace_rows, int32_t loc);
 
+/* Pruning: give units back to the pool.  Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
+ * sampled depth point, whether or not a voxel of it is then updated, and de-integration leaves the units it emptied allocated - so
+ * a long session holds units that carry nothing, and units far from where the camera now is.  This project's own contract (Open3D's
+ * ScalableTSDFVolume never frees a unit):
+ *   empty     release_empty != 0: a unit goes when all R^3 weights are 0.  (A voxel of weight 0 is in the fresh state in all five
+ *             planes - integrate's initial state and de-integration's w0 == n rule - so the weight plane alone decides.)
+ *   outside   unit_lo / unit_hi ([3] each, both or neither): a unit goes when its index lies outside the INCLUSIVE range
+ *             [unit_lo, unit_hi] on some axis, observed voxels and all.  The caller converts metres to unit indices
+ *             (floor(x / (voxel_size * 16)) per axis keeps every unit whose half-open box meets the closed box in metres).
+ *   stats     units_before = units held at the call; units_outside; units_empty (a unit that is both counts as outside only - it is
+ *             not read); units_after = units_before - units_outside - units_empty.  Neither criterion: a no-op, {n, 0, 0, n}.
+ *   after     hv_tsdf_dump = the dump before with the released units' rows removed, bit for bit; hv_num_blocks, hv_tsdf_unit_keys
+ *             and the dump agree on units_after; hv_max_blocks is unchanged (the allocation does not shrink: the released blocks can
+ *             be claimed again, and are all zero like every block never handed out).  Units in use are blocks [0, units_after) again
+ *             - survivors from the tail move into the holes, at most min(released, kept) of them - and the table holds exactly the
+ *             surviving keys: keys claimed without a block by an overflowed call are gone and the latched overflow is cleared, as
+ *             after hv_reserve_blocks.  The "dirty since the last merge" stamps follow their units (hv_tsdf_dirty_keys = before
+ *             minus the released keys); hv_tsdf_touched lists nothing until the next integrate; a stored device halo plan is
+ *             dropped; cached extraction results and the per-unit extraction caches are recomputed.  If NOTHING is released the
+ *             volume is left exactly as it was, caches included.
+ * The batch pipeline is drained first; the call waits for the GPU.  Device work: one wave per unit streams the weight plane (16 KiB,
+ * 16 bytes per lane, leaving at the first weight it sees; a unit outside the range is not read), a one-workgroup scan plans the moves,
+ * the host reads the four counts, then one launch moves the tail's survivors (sources and destinations are disjoint), the freed tail
+ * is zeroed and the table re-keyed in place.  Extra device memory: 13 bytes per unit plus 20 bytes per table slot, never a second
+ * pool.  HV_ERR_MODE for a non-TSDF volume and for a tile-sharded one (hv_tsdf_set_tile: its ranks must agree on the unit set; an
+ * owner-sharded volume prunes the units it owns), HV_ERR_INVALID for one of unit_lo / unit_hi alone or unit_lo > unit_hi. */
+typedef struct hv_prune_stats {
+    int64_t units_before, units_outside, units_empty, units_after;
+} hv_prune_stats;
+int hv_tsdf_prune(hv_volume *v, int32_t release_empty, const int32_t *unit_lo /* [3] or NULL */,
+                  const int32_t *unit_hi /* [3] or NULL */, hv_prune_stats *stats /* may be NULL */);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

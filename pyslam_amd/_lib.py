@@ -83,6 +83,15 @@ class HvDeintegrateStats(_c.Structure):
     ]
 
 
+class HvPruneStats(_c.Structure):
+    _fields_ = [
+        ("units_before", _i64),
+        ("units_outside", _i64),
+        ("units_empty", _i64),
+        ("units_after", _i64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -168,6 +177,7 @@ SIGNATURES = {
     "hv_tsdf_deintegrate_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _f64, _f64, _i32, _c.POINTER(HvDeintegrateStats)]),
     "hv_tsdf_reintegrate_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _i32,
                                          _c.POINTER(HvDeintegrateStats)]),
+    "hv_tsdf_prune": (_i32, [_vp, _i32, _pi32, _pi32, _c.POINTER(HvPruneStats)]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),

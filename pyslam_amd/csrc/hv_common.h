@@ -494,6 +494,8 @@ int hv_capacity_gate(hv_volume *v, bool *checked);
 // written to voxels yet, so nothing is lost.  HV_ERR_CAPACITY if the pool cannot grow.
 int hv_claims_fit(hv_volume *v);
 static constexpr int HV_RETRY_CLAIM = 1000;
+// Empty the table and re-fill it from block_keys[0, keep); stamps follow their keys, counters and occupancy become exact (hv_core.hip).
+int hv_rekey_in_place(hv_volume *v, int64_t keep);
 int32_t hv_next_status_seq(hv_volume *v); // sequence number for the call's publishing kernel
 void hv_launch_publish_status(hv_volume *v); // modes whose last kernel does not publish by itself
 int hv_read_counters(hv_volume *v); // D2H of the counter block (synchronises the stream)

@@ -915,11 +915,14 @@ static int hv_rebuild(hv_volume *v, int64_t new_max_blocks, int64_t keep) {
     return HV_OK;
 }
 
-// Undo a claim pass that did not fit, without touching the pool: the table is emptied and re-filled from the keys of the
-// first `keep` blocks (the keys claimed by the failed call - with or without a block - are gone), the TSDF mode's per-slot
-// stamps follow their keys, the counters are repaired.  Blocks beyond `keep` were handed out by the failed call and never
-// written (a claim pass writes no voxel), so they are still zero.  Temporary memory: a copy of the old table (20 B per slot).
-static int hv_rollback_claims(hv_volume *v, int64_t keep) {
+// Re-key the table in place, without touching the pool: the table is emptied and re-filled from block_keys[0, keep) (every other
+// key - with or without a block - is gone), the TSDF mode's per-slot stamps follow their keys, the touched masks and lists are
+// void, the counters and the host's view of the occupancy are exact again.  The caller guarantees that blocks [0, keep) hold the
+// units block_keys names and that every block beyond `keep` is zero.  Temporary memory: a copy of the old table (20 B per slot).
+// Synchronises the stream.  (hv_rollback_claims below; hv_tsdf_prune in hv_prune.hip after it has compacted the pool.)
+} // extern "C"
+
+int hv_rekey_in_place(hv_volume *v, int64_t keep) {
     HV_HIP(hipSetDevice(v->device));
     HV_HIP(hipStreamSynchronize(v->stream));
     v->extract_epoch += 1;
@@ -983,6 +986,12 @@ static int hv_rollback_claims(hv_volume *v, int64_t keep) {
     v->bins_clean = false; // grid modes: the per-slot bin arrays are keyed by slots that just moved - re-made / cleared by the next call
     return HV_OK;
 }
+
+// Undo a claim pass that did not fit: the keys claimed by the failed call leave the table.  Blocks beyond `keep` were handed out
+// by the failed call and never written (a claim pass writes no voxel), so they are still zero.
+static int hv_rollback_claims(hv_volume *v, int64_t keep) { return hv_rekey_in_place(v, keep); }
+
+extern "C" {
 
 // Every call that returns data to the host passes through here (one counter read-back): the natural place to grow
 // the pool before it runs out.  Policy: when more than half of the blocks are in use, double the capacity (while the

@@ -156,6 +156,59 @@ class DeintegrationStats:
                 f"voxels_removed={self.voxels_removed}, voxels_underflow={self.voxels_underflow})")
 
 
+class PruneStats:
+    """What ScalableTSDFVolume.prune returns (hv_prune_stats): units_before = units held at the call; units_outside = released
+    because their index lies outside the bounds; units_empty = released because all their weights are 0 (a unit that is both
+    counts as outside); units_after = units_before - units_outside - units_empty."""
+
+    __slots__ = ("units_before", "units_outside", "units_empty", "units_after")
+
+    def __init__(self, units_before=0, units_outside=0, units_empty=0, units_after=0):
+        self.units_before = int(units_before)
+        self.units_outside = int(units_outside)
+        self.units_empty = int(units_empty)
+        self.units_after = int(units_after)
+
+    def as_tuple(self):
+        return (self.units_before, self.units_outside, self.units_empty, self.units_after)
+
+    def __eq__(self, other):
+        return isinstance(other, PruneStats) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return (f"PruneStats(units_before={self.units_before}, units_outside={self.units_outside}, "
+                f"units_empty={self.units_empty}, units_after={self.units_after})")
+
+
+_UNIT_KEY_BIAS = 1 << 20  # the library packs a unit index into 21 bits per axis: [-2^20, 2^20)
+
+
+def unit_range_of_bounds(bounds, voxel_length, resolution=16):
+    """(min_xyz, max_xyz) in world metres -> (lo[3], hi[3]) int32, the inclusive range of unit indices ScalableTSDFVolume.prune
+    keeps: lo = floor(min / L), hi = floor(max / L) per axis with L = voxel_length * resolution, in float64.  Unit k covers the
+    half-open box [k L, (k + 1) L), so these are exactly the units that meet the closed box.  ValueError on min > max, non-finite
+    values or a range outside the library's unit keys."""
+    try:
+        lo_m, hi_m = bounds
+        lo_m = np.asarray(lo_m, dtype=np.float64).reshape(-1)
+        hi_m = np.asarray(hi_m, dtype=np.float64).reshape(-1)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"bounds must be (min_xyz, max_xyz): {e}") from None
+    if lo_m.shape != (3,) or hi_m.shape != (3,):
+        raise ValueError("bounds must be (min_xyz, max_xyz) with three coordinates each")
+    L_unit = np.float64(voxel_length) * np.float64(resolution)
+    if not (np.isfinite(L_unit) and L_unit > 0.0):
+        raise ValueError(f"bad unit length {L_unit}")
+    if not (np.all(np.isfinite(lo_m)) and np.all(np.isfinite(hi_m))):
+        raise ValueError("bounds must be finite")
+    if np.any(lo_m > hi_m):
+        raise ValueError(f"bounds: min {lo_m.tolist()} exceeds max {hi_m.tolist()}")
+    lo, hi = np.floor(lo_m / L_unit), np.floor(hi_m / L_unit)
+    if np.any(lo < -_UNIT_KEY_BIAS) or np.any(hi >= _UNIT_KEY_BIAS):
+        raise ValueError(f"bounds reach beyond the unit keys [-2^20, 2^20): units {lo.tolist()} .. {hi.tolist()}")
+    return lo.astype(np.int32), hi.astype(np.int32)
+
+
 def _trace_rows(rows):
     out = []
     iu = np.triu_indices(6)
@@ -1147,6 +1200,21 @@ class ScalableTSDFVolume(_Volume):
             self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(To), L.ptr(Tn), float(depth_scale),
             float(depth_trunc), L.location(depth), ctypes.byref(st)))
         return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
+
+    def prune(self, empty=True, bounds=None):
+        """Give units back to the pool (include/hipvol.h, hv_tsdf_prune).  empty: release every unit whose weights are all 0 -
+        what de-integration emptied and what the touch pass claimed without ever updating.  bounds = (min_xyz, max_xyz) in world
+        metres or None: release every unit outside unit_range_of_bounds(bounds, ...), observed voxels and all (a window that
+        follows the camera).  num_blocks() shrinks, max_blocks() does not: the released blocks are claimed again by later
+        frames.  Waits for the GPU and returns PruneStats; with neither criterion, or nothing to release, the volume is untouched."""
+        lo = hi = None
+        if bounds is not None:
+            lo, hi = unit_range_of_bounds(bounds, self.voxel_length, self.res)
+            lo, hi = np.ascontiguousarray(lo, dtype=np.int32), np.ascontiguousarray(hi, dtype=np.int32)
+        st = L.HvPruneStats()
+        L.check(self._lib.hv_tsdf_prune(self._h, 1 if empty else 0, None if lo is None else lo.ctypes.data_as(L._pi32),
+                                        None if hi is None else hi.ctypes.data_as(L._pi32), ctypes.byref(st)))
+        return PruneStats(st.units_before, st.units_outside, st.units_empty, st.units_after)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
