@@ -543,6 +543,52 @@ int hv_tsdf_track(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t 
                   const double *T_cw_init, const hv_track_params *params, hv_track_result *result, double *trace, int64_t trace_cap,
                   int64_t *trace_rows, int32_t loc);
 
+/* Hybrid frame-to-model tracking (Open3D's tensor odometry "Hybrid": point-to-plane plus intensity): hv_tsdf_track with a
+ * photometric term on the colour the map already holds, for scenes whose geometry leaves motions free (a wall, a floor, a table
+ * top).  This project's own contract.  EVERYTHING of hv_tsdf_track holds unchanged - source depth pyramid, level intrinsics, the
+ * model cast per level at T_cw_init, anchor frame, state A, association (u', v'), the inlier test, r, J, its Huber weight, the
+ * solve, the degenerate rule, the stopping rule, the outputs - with these additions:
+ *   source I  color [H,W,3] uint8 at loc, channel order as integrate takes it (hv_tsdf_set_color_order).  Level 0, float32:
+ *             I_s = ((0.299f R + 0.587f G) + 0.114f B) / 255f.  Level l+1: (((c0 + c1) + c2) + c3) * 0.25f over the four children in
+ *             the depth pyramid's child order, all four whatever their depth.
+ *   model I   the per-level cast also renders colour (r, g, b) in [0, 1] (no second cast).  Per model pixel, float32:
+ *             I_m = (0.299f r + 0.587f g) + 0.114f b; g_x = 0.5f (I_m(u+1, v) - I_m(u-1, v)), g_y = 0.5f (I_m(u, v+1) - I_m(u, v-1)).
+ *             The pixel HAS A GRADIENT iff 1 <= u <= W-2 and 1 <= v <= H-2, the mask is set at it and at its four neighbours, and
+ *             |z*(neighbour) - z*(u, v)| <= depth_outlier_trunc for each of them (the float32 cast depths subtracted and compared
+ *             in double: no gradient across a depth edge).  A level narrower or lower than 3 pixels has no photometric term.
+ *   photometric  double, for every inlier of hv_tsdf_track's test whose model pixel (u', v') has a gradient: with the unrounded
+ *             x' = fx p_x / p_z + cx, y' = fy p_y / p_z + cy (u' = floor(x' + 0.5), v' likewise),
+ *             r_I = ((I_m + g_x (x' - u')) + g_y (y' - v')) - I_s(u, v)   (I_m, g_x, g_y of (u', v'); I_s of the source pixel);
+ *             a = g_x fx / p_z, b = g_y fy / p_z, c = -(a p_x + b p_y) / p_z, g3 = (a, b, c), J_I = [p x g3, g3] (omega, t);
+ *             w_I = intensity_weight * (1 if |r_I| <= intensity_huber_delta else intensity_huber_delta / |r_I|).
+ *             The first-order expansion about the associated pixel stands in for a bilinear sample: one record per inlier.
+ *   sums      H = sum w J^T J + sum w_I J_I^T J_I and g = sum w J^T r + sum w_I J_I^T r_I: per pixel the products (w J_a) J_b, (w J_a) r,
+ *             then (w_I J_I,a) J_I,b, (w_I J_I,a) r_I, are added into the same float64 sums; e, inliers and valid as before; new: the
+ *             count of photometric inliers and e_I = sum r_I^2 (unweighted).  The degenerate test, information and the trace's H, g
+ *             are those of the combined system.  The sums are reduced in hv_tsdf_track's order, so intensity_weight = 0 (every
+ *             photometric product is then 0) gives, bit for bit, hv_tsdf_track's T_cw, information, fitness, inlier_rmse, counts,
+ *             iterations and flags on the same inputs.
+ *   result    base as hv_tsdf_track; of the LAST level-0 linearisation: photometric_inliers, intensity_rmse = sqrt(e_I /
+ *             photometric_inliers) (0 if none).
+ * trace: rows of HV_TRACK_COLOR_TRACE_STRIDE doubles: hv_tsdf_track's 56 fields in their order, then photometric inliers, e_I.
+ * Depth and colour are both at loc.  Errors as hv_tsdf_track, plus HV_ERR_INVALID for a NULL color, an intensity_weight that is
+ * negative or not finite, an intensity_huber_delta that is not positive and finite.  Reads only, all steps queued at once, one
+ * host wait, no float atomics, bitwise reproducible: as hv_tsdf_track. */
+#define HV_TRACK_COLOR_TRACE_STRIDE 58
+typedef struct hv_track_color_params {
+    hv_track_params base;         /* everything hv_tsdf_track takes, same meaning */
+    double intensity_weight;      /* lambda >= 0: factor on the photometric normal equations */
+    double intensity_huber_delta; /* > 0, in intensity units (image range [0, 1]) */
+} hv_track_color_params;
+typedef struct hv_track_color_result {
+    hv_track_result base;
+    int64_t photometric_inliers; /* of the last level-0 linearisation */
+    double intensity_rmse;       /* sqrt(sum r_I^2 / photometric_inliers), unweighted, 0 if none */
+} hv_track_color_result;
+int hv_tsdf_track_color(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height, int32_t width,
+                        const double *intr, const double *T_cw_init, const hv_track_color_params *params, hv_track_color_result *result,
+                        double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc);
+
 /* Pruning: give units back to the pool.  Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
  * sampled depth point, whether or not a voxel of it is then updated, and de-integration leaves the units it emptied allocated - so
  * a long session holds units that carry nothing, and units far from where the camera now is.  This project's own contract (Open3D's

@@ -71,6 +71,17 @@ class HvTrackResult(_c.Structure):
     ]
 
 
+HV_TRACK_COLOR_TRACE_STRIDE = 58
+
+
+class HvTrackColorParams(_c.Structure):
+    _fields_ = [("base", HvTrackParams), ("intensity_weight", _f64), ("intensity_huber_delta", _f64)]
+
+
+class HvTrackColorResult(_c.Structure):
+    _fields_ = [("base", HvTrackResult), ("photometric_inliers", _i64), ("intensity_rmse", _f64)]
+
+
 HV_TSDF_DEINTEGRATE_MAX_FRAMES = 64
 
 
@@ -179,6 +190,7 @@ SIGNATURES = {
                                          _c.POINTER(HvDeintegrateStats)]),
     "hv_tsdf_prune": (_i32, [_vp, _i32, _pi32, _pi32, _c.POINTER(HvPruneStats)]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),

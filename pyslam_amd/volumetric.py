@@ -112,10 +112,12 @@ class OdometryResult:
     last full-resolution linearisation; information 6x6 float64 (its Gauss-Newton matrix H, anchor frame, order (omega, t));
     success; iterations run per pyramid level (level 0 first); degenerate = bit l set when level l ended on a degenerate step;
     inliers / valid counts; trace = None, or one dict per linearisation (level, iteration, status, inliers, valid, sq_error,
-    A 4x4, H 6x6, g 6, xi 6) when asked for."""
+    A 4x4, H 6x6, g 6, xi 6) when asked for.  A call with colour (hv_track_color_result) also fills photometric_inliers and
+    intensity_rmse (image range [0, 1]) of that linearisation, and its trace rows carry photometric_inliers and sq_intensity_error;
+    both are None after a depth-only call."""
 
     def __init__(self, transformation, fitness, inlier_rmse, information, success, iterations, degenerate, inliers, valid,
-                 trace=None):
+                 trace=None, photometric_inliers=None, intensity_rmse=None):
         self.transformation = transformation
         self.fitness = fitness
         self.inlier_rmse = inlier_rmse
@@ -126,6 +128,8 @@ class OdometryResult:
         self.inliers = inliers
         self.valid = valid
         self.trace = trace
+        self.photometric_inliers = photometric_inliers
+        self.intensity_rmse = intensity_rmse
 
     def __repr__(self):
         return (f"OdometryResult(success={self.success}, fitness={self.fitness:.4f}, inlier_rmse={self.inlier_rmse:.6f}, "
@@ -218,6 +222,8 @@ def _trace_rows(rows):
         H = H + np.triu(H, 1).T
         out.append({"level": int(r[0]), "iteration": int(r[1]), "status": int(r[2]), "inliers": int(r[3]), "valid": int(r[4]),
                     "sq_error": float(r[5]), "A": r[6:22].reshape(4, 4).copy(), "H": H, "g": r[43:49].copy(), "xi": r[49:55].copy()})
+        if len(r) > L.HV_TRACK_TRACE_STRIDE:  # a hybrid call's row
+            out[-1].update(photometric_inliers=int(r[56]), sq_intensity_error=float(r[57]))
     return out
 
 
@@ -1366,34 +1372,51 @@ class ScalableTSDFVolume(_Volume):
         return out
 
     def track_frame_to_model(self, depth, intrinsic, extrinsic, depth_scale=1.0, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
-                             iterations=(10, 5, 4), depth_outlier_trunc=0.07, depth_huber_delta=0.05, trace=False):
+                             iterations=(10, 5, 4), depth_outlier_trunc=0.07, depth_huber_delta=0.05, trace=False, color=None,
+                             intensity_weight=0.01, intensity_huber_delta=0.1):
         """Point-to-plane alignment of one depth frame against the fused map rendered at extrinsic = T_cw_init: -> OdometryResult
         whose transformation is the refined T_cw.  depth [H,W]: numpy or torch (either device), uint16 or any real dtype (as
         float32), divided by depth_scale; H, W = intrinsic.height, intrinsic.width.  iterations: the cap per pyramid level, level 0
         (full resolution) first; levels run coarse to fine.  Names and defaults follow Open3D's tensor odometry; the contract
         (include/hipvol.h, hv_tsdf_track) is this project's own.  Reads the volume only.  A CUDA depth tensor is read after the
-        work queued on torch's current stream.  trace=True: the per-linearisation record (tests)."""
-        d, _, dkind, _ = _tsdf_operands(depth, None, intrinsic, depth_only=True)
+        work queued on torch's current stream.  trace=True: the per-linearisation record (tests).
+        color [H,W,3] uint8 (the frame's image, as integrate takes it, same place as depth): hybrid tracking (hv_tsdf_track_color) -
+        a photometric term on the map's colour, weighted by intensity_weight (>= 0; 0 is the depth-only result bit for bit) with
+        Huber threshold intensity_huber_delta (image range [0, 1]), constrains the motions that geometry leaves free (a wall, a
+        floor); the result then carries photometric_inliers and intensity_rmse.  color=None: depth only."""
+        if color is None:
+            d, c, dkind, _ = _tsdf_operands(depth, None, intrinsic, depth_only=True)
+        else:
+            d, c, dkind, _ = _tsdf_operands(depth, color, intrinsic)
         H, W = int(d.shape[0]), int(d.shape[1])
         iters = [int(i) for i in iterations]
-        prm = L.HvTrackParams()
+        cprm = L.HvTrackColorParams()
+        cprm.intensity_weight, cprm.intensity_huber_delta = float(intensity_weight), float(intensity_huber_delta)
+        prm = cprm.base
         prm.depth_scale, prm.depth_min, prm.depth_max = float(depth_scale), float(depth_min), float(depth_max)
         prm.weight_threshold = float(weight_threshold)
         prm.depth_outlier_trunc, prm.depth_huber_delta = float(depth_outlier_trunc), float(depth_huber_delta)
         prm.n_levels = len(iters)
         for i, n in enumerate(iters[:L.HV_TRACK_MAX_LEVELS]):
             prm.iterations[i] = n
-        res = L.HvTrackResult()
+        cres = L.HvTrackColorResult()
+        res = cres.base
         intr = intrinsic.as_array()
         T0 = _as_f64_4x4(extrinsic)
         steps = max(sum(iters), 1)
-        rows = np.zeros((steps, L.HV_TRACK_TRACE_STRIDE), np.float64) if trace else None
+        stride = L.HV_TRACK_TRACE_STRIDE if c is None else L.HV_TRACK_COLOR_TRACE_STRIDE
+        rows = np.zeros((steps, stride), np.float64) if trace else None
         n_rows = ctypes.c_int64()
         loc = L.location(d)
         ts = self._torch_in(d) if loc == L.HV_DEVICE else None
         try:
-            L.check(self._lib.hv_tsdf_track(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T0), ctypes.byref(prm), ctypes.byref(res),
-                                            L.ptr(rows), steps if trace else 0, ctypes.byref(n_rows), loc))
+            if c is None:
+                L.check(self._lib.hv_tsdf_track(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T0), ctypes.byref(prm),
+                                                ctypes.byref(res), L.ptr(rows), steps if trace else 0, ctypes.byref(n_rows), loc))
+            else:
+                L.check(self._lib.hv_tsdf_track_color(self._h, L.ptr(d), dkind, L.ptr(c), H, W, L.ptr(intr), L.ptr(T0),
+                                                      ctypes.byref(cprm), ctypes.byref(cres), L.ptr(rows), steps if trace else 0,
+                                                      ctypes.byref(n_rows), loc))
         finally:
             if ts is not None:
                 self._torch_out(ts, d.device)
@@ -1401,7 +1424,8 @@ class ScalableTSDFVolume(_Volume):
         return OdometryResult(np.array(res.T_cw, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
                               np.array(res.information, np.float64).reshape(6, 6), bool(res.success),
                               tuple(int(res.iterations[i]) for i in range(n_levels)), int(res.degenerate), int(res.inliers),
-                              int(res.valid), _trace_rows(rows[:n_rows.value]) if trace else None)
+                              int(res.valid), _trace_rows(rows[:n_rows.value]) if trace else None,
+                              None if c is None else int(cres.photometric_inliers), None if c is None else float(cres.intensity_rmse))
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
