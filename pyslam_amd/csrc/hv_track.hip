@@ -9,11 +9,12 @@
 // one-workgroup solve launch (the slab summed in a fixed order, Cholesky, A update, trace row, level flag).  A step of a level that
 // has converged or gone degenerate reads the flag and returns.  No float atomics anywhere: results are bitwise reproducible.
 //
-// The hybrid call runs the same schedule with kernels of its own beside the depth-only ones, which stay as they are: the pyramid
-// kernels also produce the source intensity of the level, the casts also render colour, one model-preparation launch per level packs
-// {I_m, g_x, g_y, has-gradient} into a 16-byte record per model pixel, and k_track_linearise_color adds the photometric rank-1
-// update and two more sums (32 instead of 30) with the depth-only kernel's workgroup size, grid rule and reduction order - so with
-// intensity_weight = 0 every float64 sum associates as in the depth-only call and the two agree bit for bit.
+// The hybrid call runs the same schedule with the same kernels, instantiated with the hybrid part that sits under `if constexpr`:
+// k_track_source<true> / k_track_down<true> also produce the source intensity of the level, the casts also render colour, one
+// model-preparation launch per level packs {I_m, g_x, g_y, has-gradient} into a 16-byte record per model pixel, and
+// k_track_linearise<32> adds the photometric rank-1 update and two more sums (32 instead of 30).  The geometric body, workgroup
+// size, grid rule and reduction are one text for both instantiations - so with intensity_weight = 0 every float64 sum associates
+// as in the depth-only call and the two agree bit for bit.
 #include <cmath>
 
 #include "hv_common.h"
@@ -71,56 +72,30 @@ __global__ __launch_bounds__(64) void k_track_init(TkStateT<NACC> *st) {
     if (t == 0) st->rows = 0;
 }
 
-// level 0: depth / depth_scale in float32; valid iff finite and in (depth_min, depth_max] (double compares), else 0
-__global__ __launch_bounds__(256) void k_track_source(const void *__restrict__ raw, int is_u16, int64_t npx, float scale, double dmin,
-                                                      double dmax, float *__restrict__ out) {
+// level 0: depth / depth_scale in float32; valid iff finite and in (depth_min, depth_max] (double compares), else 0.  HYBRID: also
+// the intensity ((0.299f R + 0.587f G) + 0.114f B) / 255f of every pixel (depth only: rgb and iout are null and not read)
+template <bool HYBRID>
+__global__ __launch_bounds__(256) void k_track_source(const void *__restrict__ raw, int is_u16, const uint8_t *__restrict__ rgb, int bgr,
+                                                      int64_t npx, float scale, double dmin, double dmax, float *__restrict__ out,
+                                                      float *__restrict__ iout) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npx) return;
     float d = is_u16 ? (float)((const uint16_t *)raw)[i] : ((const float *)raw)[i];
     d = d / scale;
     out[i] = (isfinite(d) && (double)d > dmin && (double)d <= dmax) ? d : 0.0f;
-}
-
-// level l -> l + 1: float32 mean of the valid 2x2 children (fixed order), valid iff max - min <= trunc
-__global__ __launch_bounds__(256) void k_track_down(const float *__restrict__ in, int32_t w_in, float *__restrict__ out, int32_t h_out,
-                                                    int32_t w_out, double trunc) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)h_out * w_out) return;
-    const int u = (int)(i % w_out), v = (int)(i / w_out);
-    const float *r0 = in + (int64_t)(2 * v) * w_in + 2 * u, *r1 = r0 + w_in;
-    const float c[4] = {r0[0], r0[1], r1[0], r1[1]};
-    float sum = 0.0f, mx = -INFINITY, mn = INFINITY;
-    int n = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (c[k] > 0.0f) {
-            sum = sum + c[k];
-            mx = fmaxf(mx, c[k]);
-            mn = fminf(mn, c[k]);
-            ++n;
-        }
+    if constexpr (HYBRID) {
+        const uint8_t *c = rgb + 3 * i;
+        const float r = (float)c[bgr ? 2 : 0], g = (float)c[1], b = (float)c[bgr ? 0 : 2];
+        iout[i] = ((0.299f * r + 0.587f * g) + 0.114f * b) / 255.0f;
     }
-    out[i] = (n > 0 && (double)(mx - mn) <= trunc) ? sum / (float)n : 0.0f;
 }
 
-// hybrid, level 0: k_track_source's depth, and the intensity ((0.299f R + 0.587f G) + 0.114f B) / 255f of every pixel
-__global__ __launch_bounds__(256) void k_track_source_color(const void *__restrict__ raw, int is_u16, const uint8_t *__restrict__ rgb,
-                                                            int bgr, int64_t npx, float scale, double dmin, double dmax,
-                                                            float *__restrict__ out, float *__restrict__ iout) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npx) return;
-    float d = is_u16 ? (float)((const uint16_t *)raw)[i] : ((const float *)raw)[i];
-    d = d / scale;
-    out[i] = (isfinite(d) && (double)d > dmin && (double)d <= dmax) ? d : 0.0f;
-    const uint8_t *c = rgb + 3 * i;
-    const float r = (float)c[bgr ? 2 : 0], g = (float)c[1], b = (float)c[bgr ? 0 : 2];
-    iout[i] = ((0.299f * r + 0.587f * g) + 0.114f * b) / 255.0f;
-}
-
-// hybrid, level l -> l + 1: k_track_down's depth, and the float32 mean of all four children's intensities (same child order)
-__global__ __launch_bounds__(256) void k_track_down_color(const float *__restrict__ in, const float *__restrict__ iin, int32_t w_in,
-                                                          float *__restrict__ out, float *__restrict__ iout, int32_t h_out, int32_t w_out,
-                                                          double trunc) {
+// level l -> l + 1: float32 mean of the valid 2x2 children (fixed order), valid iff max - min <= trunc.  HYBRID: also the float32
+// mean of all four children's intensities, same child order (depth only: iin and iout are null and not read)
+template <bool HYBRID>
+__global__ __launch_bounds__(256) void k_track_down(const float *__restrict__ in, const float *__restrict__ iin, int32_t w_in,
+                                                    float *__restrict__ out, float *__restrict__ iout, int32_t h_out, int32_t w_out,
+                                                    double trunc) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)h_out * w_out) return;
     const int u = (int)(i % w_out), v = (int)(i / w_out);
@@ -139,8 +114,10 @@ __global__ __launch_bounds__(256) void k_track_down_color(const float *__restric
         }
     }
     out[i] = (n > 0 && (double)(mx - mn) <= trunc) ? sum / (float)n : 0.0f;
-    const float *i0 = iin + o0, *i1 = i0 + w_in;
-    iout[i] = (((i0[0] + i0[1]) + i1[0]) + i1[1]) * 0.25f;
+    if constexpr (HYBRID) {
+        const float *i0 = iin + o0, *i1 = i0 + w_in;
+        iout[i] = (((i0[0] + i0[1]) + i1[0]) + i1[1]) * 0.25f;
+    }
 }
 
 __device__ __forceinline__ float tk_model_intensity(const float *__restrict__ color, int64_t m) {
@@ -178,83 +155,22 @@ __device__ __forceinline__ double tk_wave_sum(double x) {
     return x;
 }
 
-// one step's linearisation: per workgroup the 30 sums of its pixels -> slab[blockIdx.x]
-__global__ __launch_bounds__(TK_BLOCK) void k_track_linearise(TkLevel L, TkParams P, const TkState *__restrict__ st, int level,
-                                                              double *__restrict__ slab) {
+// one step's linearisation: per workgroup the NACC sums of its pixels -> slab[blockIdx.x].  NACC = 30 is the depth-only call (C is
+// not read); NACC = 32 the hybrid one: for an inlier whose model pixel has a gradient also the photometric products into the same
+// accumulators, and two more sums.  The geometric part and the reduction are this one text for both, which is what makes the
+// hybrid call with intensity_weight = 0 associate every float64 sum as the depth-only call does.
+template <int NACC>
+__global__ __launch_bounds__(TK_BLOCK) void k_track_linearise(TkLevel L, TkParams P, TkColor C, const TkStateT<NACC> *__restrict__ st,
+                                                              int level, double *__restrict__ slab) {
+    constexpr bool HYBRID = NACC == TK_NACC_COLOR;
+    static_assert(HYBRID || NACC == TK_NACC, "30 sums (depth only) or 32 (hybrid)");
     if (st->done[level] != 0) return; // (uniform: every thread reads the same flag)
     double A[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) A[k] = st->A[k];
-    double acc[TK_NACC];
+    double acc[NACC];
 #pragma unroll
-    for (int k = 0; k < TK_NACC; ++k) acc[k] = 0.0;
-
-    const int64_t npx = (int64_t)L.height * L.width;
-    for (int64_t pix = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x; pix < npx; pix += (int64_t)gridDim.x * TK_BLOCK) {
-        const float ds = L.src[pix];
-        if (!(ds > 0.0f)) continue;
-        acc[29] += 1.0;
-        const int u = (int)(pix % L.width), v = (int)(pix / L.width);
-        const double d = (double)ds;
-        const double pc0 = d * (((double)u - L.cx) / L.fx), pc1 = d * (((double)v - L.cy) / L.fy), pc2 = d;
-        const double p0 = A[0] * pc0 + A[1] * pc1 + A[2] * pc2 + A[3];
-        const double p1 = A[4] * pc0 + A[5] * pc1 + A[6] * pc2 + A[7];
-        const double p2 = A[8] * pc0 + A[9] * pc1 + A[10] * pc2 + A[11];
-        if (!(p2 > 0.0)) continue;
-        const double uf = floor(L.fx * p0 / p2 + L.cx + 0.5), vf = floor(L.fy * p1 / p2 + L.cy + 0.5);
-        if (!(uf >= 0.0 && uf < (double)L.width && vf >= 0.0 && vf < (double)L.height)) continue;
-        const int64_t m = (int64_t)vf * L.width + (int64_t)uf;
-        if (!L.mmask[m]) continue;
-        const double z = (double)L.mdepth[m];
-        const double q0 = z * ((uf - L.cx) / L.fx), q1 = z * ((vf - L.cy) / L.fy), q2 = z;
-        const double nw0 = (double)L.mnormal[3 * m], nw1 = (double)L.mnormal[3 * m + 1], nw2 = (double)L.mnormal[3 * m + 2];
-        const double n0 = P.R0[0] * nw0 + P.R0[1] * nw1 + P.R0[2] * nw2;
-        const double n1 = P.R0[3] * nw0 + P.R0[4] * nw1 + P.R0[5] * nw2;
-        const double n2 = P.R0[6] * nw0 + P.R0[7] * nw1 + P.R0[8] * nw2;
-        const double e0 = p0 - q0, e1 = p1 - q1, e2 = p2 - q2;
-        if (!(sqrt(e0 * e0 + e1 * e1 + e2 * e2) <= P.trunc)) continue;
-        const double r = n0 * e0 + n1 * e1 + n2 * e2;
-        const double J[6] = {p1 * n2 - p2 * n1, p2 * n0 - p0 * n2, p0 * n1 - p1 * n0, n0, n1, n2};
-        const double w = fabs(r) <= P.delta ? 1.0 : P.delta / fabs(r);
-        int k = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const double wa = w * J[a];
-#pragma unroll
-            for (int b = a; b < 6; ++b) acc[k++] += wa * J[b];
-            acc[21 + a] += wa * r;
-        }
-        acc[27] += r * r;
-        acc[28] += 1.0;
-    }
-
-    __shared__ double red[TK_BLOCK / 64][TK_NACC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < TK_NACC; ++k) {
-        const double s = tk_wave_sum(acc[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < TK_NACC) {
-        double s = red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < TK_BLOCK / 64; ++w) s += red[w][threadIdx.x];
-        slab[(int64_t)blockIdx.x * TK_NACC + threadIdx.x] = s;
-    }
-}
-
-// one hybrid step's linearisation: k_track_linearise's body, then for an inlier whose model pixel has a gradient the photometric
-// products into the same accumulators and two more sums -> slab[blockIdx.x] (32 per workgroup)
-__global__ __launch_bounds__(TK_BLOCK) void k_track_linearise_color(TkLevel L, TkParams P, TkColor C, const TkStateColor *__restrict__ st,
-                                                                    int level, double *__restrict__ slab) {
-    if (st->done[level] != 0) return; // (uniform: every thread reads the same flag)
-    double A[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) A[k] = st->A[k];
-    double acc[TK_NACC_COLOR];
-#pragma unroll
-    for (int k = 0; k < TK_NACC_COLOR; ++k) acc[k] = 0.0;
+    for (int k = 0; k < NACC; ++k) acc[k] = 0.0;
 
     const int64_t npx = (int64_t)L.height * L.width;
     for (int64_t pix = (int64_t)blockIdx.x * TK_BLOCK + threadIdx.x; pix < npx; pix += (int64_t)gridDim.x * TK_BLOCK) {
@@ -295,39 +211,41 @@ __global__ __launch_bounds__(TK_BLOCK) void k_track_linearise_color(TkLevel L, T
         acc[27] += r * r;
         acc[28] += 1.0;
 
-        const float4 rec = C.mrec[m];
-        if (rec.w == 0.0f) continue;
-        const double gx = (double)rec.y, gy = (double)rec.z;
-        const double ri = (((double)rec.x + gx * (xf - uf)) + gy * (yf - vf)) - (double)C.isrc[pix];
-        const double ga = gx * L.fx / p2, gb = gy * L.fy / p2;
-        const double gc = -(ga * p0 + gb * p1) / p2;
-        const double JI[6] = {p1 * gc - p2 * gb, p2 * ga - p0 * gc, p0 * gb - p1 * ga, ga, gb, gc};
-        const double wi = C.lambda * (fabs(ri) <= C.delta ? 1.0 : C.delta / fabs(ri));
-        k = 0;
+        if constexpr (HYBRID) {
+            const float4 rec = C.mrec[m];
+            if (rec.w == 0.0f) continue;
+            const double gx = (double)rec.y, gy = (double)rec.z;
+            const double ri = (((double)rec.x + gx * (xf - uf)) + gy * (yf - vf)) - (double)C.isrc[pix];
+            const double ga = gx * L.fx / p2, gb = gy * L.fy / p2;
+            const double gc = -(ga * p0 + gb * p1) / p2;
+            const double JI[6] = {p1 * gc - p2 * gb, p2 * ga - p0 * gc, p0 * gb - p1 * ga, ga, gb, gc};
+            const double wi = C.lambda * (fabs(ri) <= C.delta ? 1.0 : C.delta / fabs(ri));
+            k = 0;
 #pragma unroll
-        for (int a = 0; a < 6; ++a) {
-            const double wa = wi * JI[a];
+            for (int a = 0; a < 6; ++a) {
+                const double wa = wi * JI[a];
 #pragma unroll
-            for (int b = a; b < 6; ++b) acc[k++] += wa * JI[b];
-            acc[21 + a] += wa * ri;
+                for (int b = a; b < 6; ++b) acc[k++] += wa * JI[b];
+                acc[21 + a] += wa * ri;
+            }
+            acc[30] += 1.0;
+            acc[31] += ri * ri;
         }
-        acc[30] += 1.0;
-        acc[31] += ri * ri;
     }
 
-    __shared__ double red[TK_BLOCK / 64][TK_NACC_COLOR];
+    __shared__ double red[TK_BLOCK / 64][NACC];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
-    for (int k = 0; k < TK_NACC_COLOR; ++k) {
+    for (int k = 0; k < NACC; ++k) {
         const double s = tk_wave_sum(acc[k]);
         if (lane == 0) red[wave][k] = s;
     }
     __syncthreads();
-    if (threadIdx.x < TK_NACC_COLOR) {
+    if (threadIdx.x < NACC) {
         double s = red[0][threadIdx.x];
 #pragma unroll
         for (int w = 1; w < TK_BLOCK / 64; ++w) s += red[w][threadIdx.x];
-        slab[(int64_t)blockIdx.x * TK_NACC_COLOR + threadIdx.x] = s;
+        slab[(int64_t)blockIdx.x * NACC + threadIdx.x] = s;
     }
 }
 
@@ -457,14 +375,8 @@ __global__ __launch_bounds__(TK_SUM_THREADS) void k_track_solve(TkStateT<NACC> *
     if (status != 0) st->done[level] = status;
 }
 
-inline size_t tk_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-} // namespace
-
-namespace {
-
 // Both entry points: HYBRID = false is hv_tsdf_track (color, cprm and cres unused), true is hv_tsdf_track_color.  The depth-only
-// call queues exactly the launches it always did.
+// call queues exactly the launches it always did, with null colour / intensity operands.
 template <bool HYBRID>
 int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height, int32_t width,
            const double *intr, const double *T_cw_init, const hv_track_params *prm, const hv_track_color_params *cprm,
@@ -514,36 +426,33 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
     // scratch: [state][slab][trace][per level: source, model depth, model normal, model mask; hybrid: model colour, model
     // record, source intensity]
     size_t off = 0;
-    const size_t o_state = off;
-    off += tk_align(sizeof(State));
-    const size_t o_slab = off;
-    off += tk_align(sizeof(double) * NACC * TK_MAX_BLOCKS);
-    const size_t o_trace = off;
-    off += tk_align(sizeof(double) * STRIDE * (size_t)steps);
+    auto take = [&off](size_t bytes) { // -> the offset of the next bytes, every piece 256-byte aligned
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    const size_t o_state = take(sizeof(State));
+    const size_t o_slab = take(sizeof(double) * NACC * TK_MAX_BLOCKS);
+    const size_t o_trace = take(sizeof(double) * STRIDE * (size_t)steps);
     size_t o_src[HV_TRACK_MAX_LEVELS], o_md[HV_TRACK_MAX_LEVELS], o_mn[HV_TRACK_MAX_LEVELS], o_mm[HV_TRACK_MAX_LEVELS];
     size_t o_mc[HV_TRACK_MAX_LEVELS] = {}, o_rec[HV_TRACK_MAX_LEVELS] = {}, o_int[HV_TRACK_MAX_LEVELS] = {};
     for (int l = 0; l < nl; ++l) {
         const size_t n = (size_t)(height >> l) * (size_t)(width >> l);
-        o_src[l] = off;
-        off += tk_align(4 * n);
-        o_md[l] = off;
-        off += tk_align(4 * n);
-        o_mn[l] = off;
-        off += tk_align(12 * n);
-        o_mm[l] = off;
-        off += tk_align(n);
+        o_src[l] = take(4 * n);
+        o_md[l] = take(4 * n);
+        o_mn[l] = take(12 * n);
+        o_mm[l] = take(n);
         if (HYBRID) {
-            o_mc[l] = off;
-            off += tk_align(12 * n);
-            o_rec[l] = off;
-            off += tk_align(16 * n);
-            o_int[l] = off;
-            off += tk_align(4 * n);
+            o_mc[l] = take(12 * n);
+            o_rec[l] = take(16 * n);
+            o_int[l] = take(4 * n);
         }
     }
     int rc = hv_ensure_buffer(v, &v->track_buf, &v->track_buf_bytes, off);
     if (rc != HV_OK) return rc;
     char *base = (char *)v->track_buf;
+    // the source intensity of a level; null in the depth-only call, whose kernels do not read it
+    auto intensity = [&](int l) { return HYBRID ? (float *)(base + o_int[l]) : (float *)nullptr; };
     State *st = (State *)(base + o_state);
     double *slab = (double *)(base + o_slab);
     double *d_trace = (double *)(base + o_trace);
@@ -562,27 +471,16 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
 
     hipLaunchKernelGGL(k_track_init<NACC>, dim3(1), dim3(64), 0, v->stream, st);
     hv_profile_begin(v);
-    if (HYBRID)
-        hipLaunchKernelGGL(k_track_source_color, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
-                           depth_dtype == HV_DEPTH_U16 ? 1 : 0, (const uint8_t *)d_color, v->color_bgr, (int64_t)npx0,
-                           (float)prm->depth_scale, prm->depth_min, prm->depth_max, (float *)(base + o_src[0]),
-                           (float *)(base + o_int[0]));
-    else
-        hipLaunchKernelGGL(k_track_source, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
-                           depth_dtype == HV_DEPTH_U16 ? 1 : 0, (int64_t)npx0, (float)prm->depth_scale, prm->depth_min, prm->depth_max,
-                           (float *)(base + o_src[0]));
+    hipLaunchKernelGGL(k_track_source<HYBRID>, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
+                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, (const uint8_t *)d_color, v->color_bgr, (int64_t)npx0, (float)prm->depth_scale,
+                       prm->depth_min, prm->depth_max, (float *)(base + o_src[0]), intensity(0));
     hv_profile_end(v, 0);
     for (int l = 1; l < nl; ++l) {
         const int ho = height >> l, wo = width >> l;
         hv_profile_begin(v);
-        if (HYBRID)
-            hipLaunchKernelGGL(k_track_down_color, dim3((unsigned)(((size_t)ho * wo + 255) / 256)), dim3(256), 0, v->stream,
-                               (const float *)(base + o_src[l - 1]), (const float *)(base + o_int[l - 1]), width >> (l - 1),
-                               (float *)(base + o_src[l]), (float *)(base + o_int[l]), ho, wo, prm->depth_outlier_trunc);
-        else
-            hipLaunchKernelGGL(k_track_down, dim3((unsigned)(((size_t)ho * wo + 255) / 256)), dim3(256), 0, v->stream,
-                               (const float *)(base + o_src[l - 1]), width >> (l - 1), (float *)(base + o_src[l]), ho, wo,
-                               prm->depth_outlier_trunc);
+        hipLaunchKernelGGL(k_track_down<HYBRID>, dim3((unsigned)(((size_t)ho * wo + 255) / 256)), dim3(256), 0, v->stream,
+                           (const float *)(base + o_src[l - 1]), (const float *)intensity(l - 1), width >> (l - 1),
+                           (float *)(base + o_src[l]), intensity(l), ho, wo, prm->depth_outlier_trunc);
         hv_profile_end(v, 0);
     }
     HV_HIP(hipGetLastError());
@@ -616,17 +514,12 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
     for (int l = nl - 1; l >= 0; --l) {
         const int64_t npx = (int64_t)lv[l].height * lv[l].width;
         const int blocks = (int)std::min<int64_t>((npx + TK_BLOCK - 1) / TK_BLOCK, TK_MAX_BLOCKS);
+        TkColor C{}; // depth only: zero, and not read
+        if constexpr (HYBRID) C = TkColor{(const float4 *)(base + o_rec[l]), intensity(l), cprm->intensity_weight, cprm->intensity_huber_delta};
         for (int it = 0; it < prm->iterations[l]; ++it) {
             hv_profile_begin(v);
-            if constexpr (HYBRID) {
-                const TkColor C{(const float4 *)(base + o_rec[l]), (const float *)(base + o_int[l]), cprm->intensity_weight,
-                                cprm->intensity_huber_delta};
-                hipLaunchKernelGGL(k_track_linearise_color, dim3((unsigned)blocks), dim3(TK_BLOCK), 0, v->stream, lv[l], P, C,
-                                   (const State *)st, l, slab);
-            } else {
-                hipLaunchKernelGGL(k_track_linearise, dim3((unsigned)blocks), dim3(TK_BLOCK), 0, v->stream, lv[l], P, (const State *)st, l,
-                                   slab);
-            }
+            hipLaunchKernelGGL(k_track_linearise<NACC>, dim3((unsigned)blocks), dim3(TK_BLOCK), 0, v->stream, lv[l], P, C,
+                               (const State *)st, l, slab);
             hv_profile_end(v, 0);
             hv_profile_begin(v);
             hipLaunchKernelGGL((k_track_solve<NACC, STRIDE>), dim3(1), dim3(TK_SUM_THREADS), 0, v->stream, st, (const double *)slab, blocks, l, it,

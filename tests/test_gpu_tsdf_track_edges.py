@@ -175,9 +175,8 @@ def test_parameters(vol, kw):
         src = tr.pyramid(depth, 3)[2]
         m = vol.ray_cast(_K(src.shape[1], src.shape[0], tr.level_intrinsics(K, 2)), T_INIT, 0.1, 3.0, WT,
                          render_attributes=("depth", "normal", "mask"))
-        _, pc, q, n = tr.associate(src, (m["depth"], m["normal"], m["mask"]), tr.level_intrinsics(K, 2), row["A"], T_INIT[:3, :3],
-                                   0.07)
-        r, _ = tr.residuals(row["A"], pc, q, n)
+        _, a = tr.associate(src, (m["depth"], m["normal"], m["mask"]), tr.level_intrinsics(K, 2), row["A"], T_INIT[:3, :3], 0.07)
+        r, _ = tr.residuals(row["A"], a["pc"], a["q"], a["n"])
         assert (np.abs(r) > kw["depth_huber_delta"]).mean() > 0.5
     if kw.get("weight_threshold") == 5.0:  # no voxel of a 3-frame map reaches it: nothing to track against
         assert out.degenerate == 7 and not out.success and out.inliers == 0

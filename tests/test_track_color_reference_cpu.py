@@ -96,7 +96,7 @@ def test_photometric_jacobian_matches_finite_differences(scene_frame):
     x' - u' moves with the projection.  The step keeps every x' inside its pixel (pixels within 1e-3 of a boundary are left out)."""
     src, isrc, model, R0, A = _fixed_association(scene_frame)
     I, gx, gy, ok = tc.model_record(model[3], model[0], model[2], 0.07)
-    valid, a = tc.associate(src, model, K, A, R0, 0.07)
+    valid, a = tr.associate(src, model, K, A, R0, 0.07)
     pk = ok[a["vi"], a["ui"]] & (np.abs(a["dx"]) < 0.499) & (np.abs(a["dy"]) < 0.499)
     assert pk.sum() > 40000
     pc, us, vs = a["pc"][pk], a["ui"][pk], a["vi"][pk]

@@ -107,7 +107,8 @@ def test_hessian_matches_finite_differences():
     model = render(T0, K, H, W)
     R0 = T0[:3, :3]
     A = tr.exp_twist(np.array([0.004, -0.003, 0.002, 0.005, 0.004, -0.006]))
-    valid, pc, q, n = tr.associate(src, model, K, A, R0, 0.07)
+    valid, a = tr.associate(src, model, K, A, R0, 0.07)
+    pc, q, n = a["pc"], a["q"], a["n"]
     assert valid > 50000 and len(pc) > 40000
     r0, J = tr.residuals(A, pc, q, n)
     eps = 1e-6

@@ -1,4 +1,6 @@
-"""A numpy restatement of hv_tsdf_track (the contract in include/hipvol.h) - test infrastructure, no GPU.
+"""A numpy restatement of hv_tsdf_track (the contract in include/hipvol.h) - test infrastructure, no GPU - and the flow of
+hv_tsdf_track_color: association, linearisation, the call's loop and the step-by-step checker take an optional photometric term,
+which tests/track_color_reference.py supplies.
 
 The model is whatever the caller hands in per pyramid level (depth, world normal and hit mask at the initial pose: the GPU's own
 ray_cast maps in the GPU tests, an analytic scene in the CPU tests).  Everything else - source pyramid, association, linearisation,
@@ -61,33 +63,35 @@ def level_intrinsics(K, level):
 
 
 def associate(src, model, K, A, R0, trunc):
-    """-> (valid count, inlier arrays: pc [N,3] source camera points, q [N,3] model vertices, n [N,3] model normals, all anchor /
-    source camera frame, float64).  model = (depth [h,w], world normal [h,w,3], mask [h,w])."""
-    mdepth, mnormal, mmask = model
+    """-> (valid count, dict of inlier arrays: pc [N,3] source camera points, q [N,3] model vertices, n [N,3] model normals, all
+    anchor / source camera frame, float64; and what a photometric term needs: the source pixel (u, v), the model pixel (ui, vi) and
+    the projection's offsets from it (dx, dy) = (x' - u', y' - v')).  model = (depth [h,w], world normal [h,w,3], mask [h,w], ...)."""
+    mdepth, mnormal, mmask = model[:3]
     h, w = src.shape
     fx, fy, cx, cy = (float(k) for k in K)
     v, u = np.nonzero(src > 0)
     valid = len(u)
     d = src[v, u].astype(np.float64)
-    pc0, pc1, pc2 = d * ((u - cx) / fx), d * ((v - cy) / fy), d
-    p = transform(A, pc0, pc1, pc2)
-    keep = p[2] > 0
-    pc0, pc1, pc2, p = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p]
-    uf = np.floor(fx * p[0] / p[2] + cx + 0.5)
-    vf = np.floor(fy * p[1] / p[2] + cy + 0.5)
-    keep = (uf >= 0) & (uf < w) & (vf >= 0) & (vf < h)
-    pc0, pc1, pc2, p, uf, vf = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p], uf[keep], vf[keep]
+    pc = np.stack([d * ((u - cx) / fx), d * ((v - cy) / fy), d], axis=1)
+    p = np.stack(transform(A, pc[:, 0], pc[:, 1], pc[:, 2]), axis=1)
+    keep = p[:, 2] > 0
+    pc, p, u, v = pc[keep], p[keep], u[keep], v[keep]
+    with np.errstate(over="ignore", invalid="ignore"):
+        xf, yf = fx * p[:, 0] / p[:, 2] + cx, fy * p[:, 1] / p[:, 2] + cy
+        uf, vf = np.floor(xf + 0.5), np.floor(yf + 0.5)
+        keep = (uf >= 0) & (uf < w) & (vf >= 0) & (vf < h)
+    pc, p, u, v, xf, yf, uf, vf = (a[keep] for a in (pc, p, u, v, xf, yf, uf, vf))
     ui, vi = uf.astype(np.int64), vf.astype(np.int64)
     keep = np.asarray(mmask, bool)[vi, ui]
-    pc0, pc1, pc2, p, uf, vf, ui, vi = pc0[keep], pc1[keep], pc2[keep], [x[keep] for x in p], uf[keep], vf[keep], ui[keep], vi[keep]
+    pc, p, u, v, xf, yf, uf, vf, ui, vi = (a[keep] for a in (pc, p, u, v, xf, yf, uf, vf, ui, vi))
     z = np.asarray(mdepth)[vi, ui].astype(np.float64)
     q = np.stack([z * ((uf - cx) / fx), z * ((vf - cy) / fy), z], axis=1)
     nw = np.asarray(mnormal)[vi, ui].astype(np.float64)
     n = np.stack([R0[r, 0] * nw[:, 0] + R0[r, 1] * nw[:, 1] + R0[r, 2] * nw[:, 2] for r in range(3)], axis=1)
-    e = np.stack(p, axis=1) - q
+    e = p - q
     keep = np.sqrt(e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1] + e[:, 2] * e[:, 2]) <= trunc
-    pc = np.stack([pc0, pc1, pc2], axis=1)[keep]
-    return valid, pc, q[keep], n[keep]
+    return valid, {"pc": pc[keep], "q": q[keep], "n": n[keep], "u": u[keep], "v": v[keep], "ui": ui[keep], "vi": vi[keep],
+                   "dx": (xf - uf)[keep], "dy": (yf - vf)[keep]}
 
 
 def transform(A, x, y, z):
@@ -110,23 +114,38 @@ def huber(r, delta):
         return np.where(a <= delta, 1.0, delta / a)
 
 
-def linearise(src, model, K, A, R0, trunc, delta):
-    """-> dict(H 6x6, g 6, sq_error, inliers, valid, H_abs, g_abs).  Every term is the kernel's float64 product ((w J_a) J_b,
-    (w J_a) r, r r); H_abs and g_abs are the sums of the terms' absolute values (sq_error is its own), the scale of a summation
-    error bound."""
-    valid, pc, q, n = associate(src, model, K, A, R0, trunc)
-    r, J = residuals(A, pc, q, n)
-    w = huber(r, delta)
-    H, H_abs, g, g_abs = np.zeros((6, 6)), np.zeros((6, 6)), np.zeros(6), np.zeros(6)
+def _sums(w, J, r):
+    """One term's sums and the sums of their absolute values, each [6,7] upper triangular: [a,b] = sum (w J_a) J_b for a <= b < 6,
+    [a,6] = sum (w J_a) r - every element the kernel's float64 product."""
+    S, S_abs = np.zeros((6, 7)), np.zeros((6, 7))
     for a in range(6):
         wa = w * J[:, a]
-        for b in range(a, 6):
-            t = wa * J[:, b]
-            H[a, b] = H[b, a] = t.sum()
-            H_abs[a, b] = H_abs[b, a] = np.abs(t).sum()
-        t = wa * r
-        g[a], g_abs[a] = t.sum(), np.abs(t).sum()
-    return {"H": H, "g": g, "sq_error": float((r * r).sum()), "inliers": len(r), "valid": valid, "H_abs": H_abs, "g_abs": g_abs}
+        for b in range(a, 7):
+            t = wa * (J[:, b] if b < 6 else r)
+            S[a, b], S_abs[a, b] = t.sum(), np.abs(t).sum()
+    return S, S_abs
+
+
+def linearise(src, model, K, A, R0, trunc, delta, photometric=None):
+    """-> dict(H 6x6, g 6, sq_error, inliers, valid, H_abs, g_abs).  H_abs and g_abs are the sums of the terms' absolute values
+    (sq_error is its own), the scale of a summation error bound.  photometric(A, inliers of associate) -> (r_I, J_I, w_I) of the
+    inliers that have a photometric term: H, g and their _abs are then those of the combined system, each the geometric sum plus
+    the photometric sum, and the dict also holds photometric_inliers and sq_intensity_error."""
+    valid, a = associate(src, model, K, A, R0, trunc)
+    r, J = residuals(A, a["pc"], a["q"], a["n"])
+    S, S_abs = _sums(huber(r, delta), J, r)
+    lin = {"sq_error": float((r * r).sum()), "inliers": len(r), "valid": valid}
+    if photometric is not None:
+        rI, JI, wI = photometric(A, a)
+        SI, SI_abs = _sums(wI, JI, rI)
+        S, S_abs = S + SI, S_abs + SI_abs
+        lin.update(photometric_inliers=len(rI), sq_intensity_error=float((rI * rI).sum()))
+    low = np.tril_indices(6, -1)
+    for name, M in (("", S), ("_abs", S_abs)):
+        H = M[:, :6].copy()
+        H[low] = H.T[low]
+        lin.update({"H" + name: H, "g" + name: M[:, 6].copy()})
+    return lin
 
 
 def pivots(H):
@@ -201,12 +220,16 @@ def converged(xi):
     return float(np.sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]) + np.sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5])) < CONVERGED
 
 
-def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05):
-    """The whole call.  model(level, K_level, h, w) -> (depth, world normal, mask) of the map cast at T_init.
-    -> dict(T_cw, fitness, inlier_rmse, information, success, iterations, degenerate, trace)."""
+def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05,
+          photometric=None):
+    """The whole call.  model(level, K_level, h, w) -> (depth, world normal, mask, ...) of the map cast at T_init.  A hybrid call
+    gives photometric(level, K_level, maps) -> the level's term for linearise.
+    -> dict(T_cw, fitness, inlier_rmse, information, success, iterations, degenerate, inliers, valid, trace) and, hybrid,
+    photometric_inliers and intensity_rmse."""
     nl = len(iterations)
     srcs = pyramid(depth, nl, depth_scale, depth_min, depth_max, trunc)
-    R0 = np.asarray(T_init, np.float64)[:3, :3]
+    T_init = np.asarray(T_init, np.float64)
+    R0 = T_init[:3, :3]
     A = np.eye(4)
     trace, iters, degenerate, last = [], [0] * nl, 0, None
     for level in range(nl - 1, -1, -1):
@@ -215,8 +238,9 @@ def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth
         Kl = level_intrinsics(K, level)
         h, w = srcs[level].shape
         maps = model(level, Kl, h, w)
+        term = photometric(level, Kl, maps) if photometric else None
         for it in range(iterations[level]):
-            lin = linearise(srcs[level], maps, Kl, A, R0, trunc, delta)
+            lin = linearise(srcs[level], maps, Kl, A, R0, trunc, delta, term)
             xi, deg = solve(lin["H"], lin["g"], lin["inliers"])
             row = dict(lin, level=level, iteration=it, A=A.copy(), xi=xi)
             iters[level] += 1
@@ -232,14 +256,15 @@ def track(depth, K, T_init, model, iterations=(10, 5, 4), depth_scale=1.0, depth
             trace.append(row)
             if row["status"] == 1:
                 break
-    Ai = np.eye(4)
-    Ai[:3, :3] = A[:3, :3].T
-    Ai[:3, 3] = -A[:3, :3].T @ A[:3, 3]
     inl, val = last["inliers"], last["valid"]
-    return {"T_cw": Ai @ np.asarray(T_init, np.float64), "fitness": inl / val if val else 0.0,
-            "inlier_rmse": float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0, "information": last["H"],
-            "success": not (degenerate & 1) and inl >= MIN_INLIERS, "iterations": tuple(iters), "degenerate": degenerate,
-            "trace": trace}
+    out = {"T_cw": rigid_inverse(A) @ T_init, "fitness": inl / val if val else 0.0,
+           "inlier_rmse": float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0, "information": last["H"],
+           "success": not (degenerate & 1) and inl >= MIN_INLIERS, "iterations": tuple(iters), "degenerate": degenerate,
+           "inliers": inl, "valid": val, "trace": trace}
+    if photometric:
+        pin = last["photometric_inliers"]
+        out.update(photometric_inliers=pin, intensity_rmse=float(np.sqrt(last["sq_intensity_error"] / pin)) if pin else 0.0)
+    return out
 
 
 EPS = 2.0 ** -53  # unit roundoff of float64
@@ -266,20 +291,25 @@ def pivot_near_threshold(H):
     return False
 
 
-def check_call(out, depth, K, T_init, model, iterations, depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05):
-    """Hold one traced hv_tsdf_track result (an OdometryResult with trace) to this restatement, step by step.
+def check_call(out, depth, K, T_init, model, iterations, depth_scale=1.0, depth_min=0.1, depth_max=3.0, trunc=0.07, delta=0.05,
+               photometric=None):
+    """Hold one traced hv_tsdf_track or (photometric given, as for track) hv_tsdf_track_color result (an OdometryResult with trace)
+    to this restatement, step by step.
 
-    model(level, K_level, h, w) -> (depth, world normal, mask) of the map cast at T_init with the call's depth_min, depth_max and
-    weight_threshold (in the GPU tests: the public ray_cast, i.e. the same kernel the call uses).  Every traced row is linearised
-    here at the row's own state A.  Per pixel both sides do the same IEEE operations, so:
-      - valid and inliers are equal;
+    model(level, K_level, h, w) -> (depth, world normal, mask, ...) of the map cast at T_init with the call's depth_min, depth_max
+    and weight_threshold (in the GPU tests: the public ray_cast, i.e. the same kernel the call uses).  Every traced row is
+    linearised here at the row's own state A.  Per pixel both sides do the same IEEE operations, so:
+      - valid, inliers and (hybrid) photometric_inliers are equal;
       - H, g and the squared error differ only by the order of their float64 sums: |gpu - ref| <= 2 (n + 2) 2^-53 S element by
-        element, n the inliers and S the sum of the terms' absolute values (each order errs by at most ~n 2^-53 S; one pixel
-        contributes ~S / n, so one lost, doubled or mis-weighted pixel fails it);
+        element, n the number of terms in the sum and S the sum of the terms' absolute values (each order errs by at most
+        ~n 2^-53 S; one pixel contributes ~S / n, so one lost, doubled or mis-weighted pixel fails it).  n is the inliers for the
+        squared error and for a depth-only H and g, inliers + photometric inliers for the H and g of a hybrid call's combined
+        system, and the photometric inliers for the squared intensity error;
       - the row's H, g solved here give its xi and its degenerate decision (a pivot within rounding of the threshold is
         reported in the result instead), status 1 iff converged(xi), and the next row's A is exp(xi) A, or A after status 2.
     Then the schedule (coarse to fine, levels with 0 iterations absent, iterations from 0, a level ends at its first non-zero
-    status or its cap) and the outputs (iterations, degenerate bits, success, information, fitness, inlier_rmse, T_cw).
+    status or its cap) and the outputs (iterations, degenerate bits, success, information, fitness, inlier_rmse, T_cw; hybrid:
+    photometric_inliers and intensity_rmse from the last row).
     -> dict(rows, near_pivot [(row, level, iteration)], xi_rel: the largest relative xi difference)."""
     nl = len(iterations)
     T_init = np.asarray(T_init, np.float64)
@@ -320,17 +350,26 @@ def check_call(out, depth, K, T_init, model, iterations, depth_scale=1.0, depth_
         if level not in maps:
             Kl = level_intrinsics(K, level)
             h, w = srcs[level].shape
-            maps[level] = (Kl, model(level, Kl, h, w))
-        Kl, m = maps[level]
-        ref = linearise(srcs[level], m, Kl, row["A"], R0, trunc, delta)
+            m = model(level, Kl, h, w)
+            maps[level] = (Kl, m, photometric(level, Kl, m) if photometric else None)
+        Kl, m, term = maps[level]
+        ref = linearise(srcs[level], m, Kl, row["A"], R0, trunc, delta, term)
         assert row["valid"] == ref["valid"], (what, "valid", row["valid"], ref["valid"])
         assert row["inliers"] == ref["inliers"], (what, "inliers", row["inliers"], ref["inliers"])
-        bar = 2.0 * (ref["inliers"] + 2) * EPS
+        pin = 0
+        if photometric:
+            pin = ref["photometric_inliers"]
+            assert row["photometric_inliers"] == pin, (what, "photometric inliers", row["photometric_inliers"], pin)
+            bar_i = 2.0 * (pin + 2) * EPS
+            assert abs(row["sq_intensity_error"] - ref["sq_intensity_error"]) <= bar_i * ref["sq_intensity_error"], (
+                what, "e_I", row["sq_intensity_error"], ref["sq_intensity_error"])
+        bar = 2.0 * (ref["inliers"] + pin + 2) * EPS
         dH = np.abs(row["H"] - ref["H"])
         assert (dH <= bar * ref["H_abs"]).all(), (what, "H", float((dH / np.maximum(ref["H_abs"], 1e-300)).max()), bar)
         dg = np.abs(row["g"] - ref["g"])
         assert (dg <= bar * ref["g_abs"]).all(), (what, "g", float((dg / np.maximum(ref["g_abs"], 1e-300)).max()), bar)
-        assert abs(row["sq_error"] - ref["sq_error"]) <= bar * ref["sq_error"], (what, "e", row["sq_error"], ref["sq_error"])
+        bar_e = 2.0 * (ref["inliers"] + 2) * EPS
+        assert abs(row["sq_error"] - ref["sq_error"]) <= bar_e * ref["sq_error"], (what, "e", row["sq_error"], ref["sq_error"])
 
         xi_ref, deg_ref = solve(row["H"], row["g"], row["inliers"])
         if row["inliers"] >= MIN_INLIERS and pivot_near_threshold(row["H"]):
@@ -358,6 +397,11 @@ def check_call(out, depth, K, T_init, model, iterations, depth_scale=1.0, depth_
     assert out.inliers == inl and out.valid == val
     assert out.fitness == (inl / val if val else 0.0), (out.fitness, inl, val)
     assert out.inlier_rmse == (float(np.sqrt(last["sq_error"] / inl)) if inl else 0.0), (out.inlier_rmse, last["sq_error"], inl)
+    if photometric:
+        pin = last["photometric_inliers"]
+        assert out.photometric_inliers == pin, (out.photometric_inliers, pin)
+        assert out.intensity_rmse == (float(np.sqrt(last["sq_intensity_error"] / pin)) if pin else 0.0), (
+            out.intensity_rmse, last["sq_intensity_error"], pin)
     T_exp = rigid_inverse(A_next) @ T_init
     assert np.abs(out.transformation - T_exp).max() <= 1e-12 * (1.0 + np.abs(T_init).max()), (out.transformation, T_exp)
     return {"rows": len(rows), "near_pivot": near, "xi_rel": xi_rel}
