@@ -621,6 +621,50 @@ typedef struct hv_prune_stats {
 int hv_tsdf_prune(hv_volume *v, int32_t release_empty, const int32_t *unit_lo /* [3] or NULL */,
                   const int32_t *unit_hi /* [3] or NULL */, hv_prune_stats *stats /* may be NULL */);
 
+/* Volume-to-volume fusion: the observations of `src` enter `dst` through a rigid transform, p_dst = T_dst_src p_src (row-major 4x4
+ * double, R = its upper 3x3, t = its last column).  For joining submaps whose relative pose is known, for moving a map to another
+ * frame (one merge into an empty volume), for adding maps whose voxel lattices do not coincide.  This project's own contract
+ * (Open3D has no such call).  src is only read.  For EVERY voxel of the destination lattice, with global index i = 16 key + xyz per
+ * axis, all arithmetic float64, one IEEE operation per step in the order written, no contraction:
+ *   locate    d_a = ((double)i_a + 0.5) * voxel_length - t_a;   p_a = (R_0a d_0 + R_1a d_1) + R_2a d_2   (R^-1 is taken as R^T);
+ *             g_a = p_a / voxel_length - 0.5;  g0_a = floor(g_a);  r_a = g_a - g0_a.  The eight source voxels are g0 + {0,1}^3 in
+ *             hv_tsdf_at's corner order; the NEAREST is g0_a + (r_a >= 0.5 ? 1 : 0) per axis.  A source voxel is OBSERVED when its
+ *             unit exists and its weight is > 0.  A point with some |g_a| >= 1e9 (or not finite) has no observed voxel around it.
+ *   sample    nearest unobserved: the destination voxel is not touched.  All eight observed: tsdf_s = the trilinear interpolation
+ *             of the eight tsdf values (float32 widened), (1-r0)((1-r1)((1-r2) f0 + r2 f4) + r1((1-r2) f3 + r2 f7)) +
+ *             r0((1-r1)((1-r2) f1 + r2 f5) + r1((1-r2) f2 + r2 f6)), and mean_s per channel the same expression of the eight mean
+ *             colours (double)sum / (double)weight.  Otherwise tsdf_s and mean_s are the nearest voxel's.  In both cases w_s is the
+ *             nearest voxel's weight: weights stay integer observation counts.
+ *   update    with the destination voxel's tsdf0, w0 and sums:  weight = w0 + w_s;
+ *             tsdf = (float)(((double)tsdf0 * (double)w0 + tsdf_s * (double)w_s) / (double)(w0 + w_s));
+ *             each colour sum gains (uint32) floor(mean_s * (double)w_s + 0.5).
+ *   units     afterwards dst holds its former units plus exactly the units (inside the key range) in which at least one voxel was
+ *             updated - no all-zero unit is left behind.  The pool grows as for integrate (HV_ERR_CAPACITY, dst unchanged, if it
+ *             cannot).  Updated units get a new stamp: incremental extraction and hv_tsdf_dirty_keys see them; cached extraction
+ *             results are dropped.  If no voxel is updated (src holds no observed voxel) dst is left exactly as it was, caches
+ *             included.
+ *   stats     units_source = source units that hold a weight; units_claimed = units new in dst; voxels_trilinear / voxels_nearest
+ *             = voxels updated from an interpolated / a nearest sample; voxels_updated = their sum.
+ * No float atomics; every destination voxel is written by one lane from values only it computes: two calls on equal inputs give
+ * bitwise equal dumps.  Both volumes' batch pipelines are drained, src's pending work is waited for, the device work is queued on
+ * dst's stream and the call waits for it.  Device work: one wave per source unit (emptiness as hv_tsdf_prune) names candidate
+ * units through a scratch key set; one workgroup per candidate evaluates only the nearest-observed predicate and leaves at the first
+ * hit; the host reads the count; claim; one workgroup per kept unit resolves the 3 x 3 x 3 source units it can reach into LDS and
+ * sweeps its voxels.  Extra device memory, freed before the call returns: with c = 27 x (units src holds), 8 c bytes of candidate
+ * keys, 8 c of kept keys and a key set of 8 x (the power of two >= max(1024, 2 c)) bytes - under 108 keys per unit - plus 256 bytes.
+ * NOT given: frames fused into src cannot later be de-integrated from dst exactly (their contribution was resampled); every merge
+ * resamples once, so chained merges accumulate interpolation error - to move a map, merge it ONCE into an empty volume.
+ * HV_ERR_MODE when either volume is not TSDF or is tile- or owner-sharded; HV_ERR_INVALID for dst == src, volumes that differ in
+ * voxel_length, sdf_trunc, unit resolution or device, a non-finite T, |R^T R - I|_inf > 1e-6 (largest absolute row sum) or
+ * det R < 0, a bottom row other than (0, 0, 0, 1).  HV_ERR_CAPACITY, dst unchanged, when src's pool overflowed in an earlier call
+ * (hv_reserve_blocks or hv_reset it first), when the scratch key set overflows (it cannot, by the bound above), or when dst's pool
+ * cannot grow.  HV_ERR_DEVICE from the sweep itself (a device fault after the claim) is the one path on which dst may be left with
+ * claimed units that were not written, under a new content version: hv_tsdf_prune releases them. */
+typedef struct hv_merge_stats {
+    int64_t units_source, units_claimed, voxels_updated, voxels_trilinear, voxels_nearest;
+} hv_merge_stats;
+int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const double *T_dst_src /* [16] */, hv_merge_stats *stats /* may be NULL */);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

@@ -103,6 +103,16 @@ class HvPruneStats(_c.Structure):
     ]
 
 
+class HvMergeStats(_c.Structure):
+    _fields_ = [
+        ("units_source", _i64),
+        ("units_claimed", _i64),
+        ("voxels_updated", _i64),
+        ("voxels_trilinear", _i64),
+        ("voxels_nearest", _i64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -189,6 +199,7 @@ SIGNATURES = {
     "hv_tsdf_reintegrate_batch": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _f64, _f64, _i32,
                                          _c.POINTER(HvDeintegrateStats)]),
     "hv_tsdf_prune": (_i32, [_vp, _i32, _pi32, _pi32, _c.POINTER(HvPruneStats)]),
+    "hv_tsdf_integrate_volume": (_i32, [_vp, _vp, _vp, _c.POINTER(HvMergeStats)]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),

@@ -184,6 +184,31 @@ class PruneStats:
                 f"units_empty={self.units_empty}, units_after={self.units_after})")
 
 
+class MergeStats:
+    """What ScalableTSDFVolume.integrate_volume returns (hv_merge_stats): units_source = source units that hold a weight;
+    units_claimed = units new in the destination; voxels_trilinear / voxels_nearest = voxels updated from an interpolated / a
+    nearest sample; voxels_updated = their sum."""
+
+    __slots__ = ("units_source", "units_claimed", "voxels_updated", "voxels_trilinear", "voxels_nearest")
+
+    def __init__(self, units_source=0, units_claimed=0, voxels_updated=0, voxels_trilinear=0, voxels_nearest=0):
+        self.units_source = int(units_source)
+        self.units_claimed = int(units_claimed)
+        self.voxels_updated = int(voxels_updated)
+        self.voxels_trilinear = int(voxels_trilinear)
+        self.voxels_nearest = int(voxels_nearest)
+
+    def as_tuple(self):
+        return (self.units_source, self.units_claimed, self.voxels_updated, self.voxels_trilinear, self.voxels_nearest)
+
+    def __eq__(self, other):
+        return isinstance(other, MergeStats) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return (f"MergeStats(units_source={self.units_source}, units_claimed={self.units_claimed}, voxels_updated={self.voxels_updated}, "
+                f"voxels_trilinear={self.voxels_trilinear}, voxels_nearest={self.voxels_nearest})")
+
+
 _UNIT_KEY_BIAS = 1 << 20  # the library packs a unit index into 21 bits per axis: [-2^20, 2^20)
 
 
@@ -1221,6 +1246,23 @@ class ScalableTSDFVolume(_Volume):
         L.check(self._lib.hv_tsdf_prune(self._h, 1 if empty else 0, None if lo is None else lo.ctypes.data_as(L._pi32),
                                         None if hi is None else hi.ctypes.data_as(L._pi32), ctypes.byref(st)))
         return PruneStats(st.units_before, st.units_outside, st.units_empty, st.units_after)
+
+    def integrate_volume(self, source, transformation=None):
+        """Fuse another TSDF volume into this one (include/hipvol.h, hv_tsdf_integrate_volume): p_self = transformation @ p_source,
+        a rigid float64 [4,4] (default: identity).  Every voxel of this volume whose centre falls onto observed voxels of `source`
+        takes the source field sampled there (trilinear, or the nearest voxel at the edge of what was observed) as that many
+        observations; units are claimed exactly where a voxel is updated.  `source` is only read and must have the same
+        voxel_length, sdf_trunc and unit resolution.  To move a map to another frame, merge it ONCE into an empty volume: every merge
+        resamples.  Waits for the GPU and returns MergeStats; a source without observed voxels leaves this volume untouched."""
+        if getattr(source, "_h", None) is None:
+            raise TypeError("integrate_volume: source must be a volume")
+        T = np.eye(4) if transformation is None else np.asarray(transformation, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("integrate_volume: transformation must be a 4x4 matrix")
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        st = L.HvMergeStats()
+        L.check(self._lib.hv_tsdf_integrate_volume(self._h, source._h, L.ptr(T), ctypes.byref(st)))
+        return MergeStats(st.units_source, st.units_claimed, st.voxels_updated, st.voxels_trilinear, st.voxels_nearest)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
