@@ -654,6 +654,9 @@ int hv_tsdf_prune(hv_volume *v, int32_t release_empty, const int32_t *unit_lo /*
  * keys, 8 c of kept keys and a key set of 8 x (the power of two >= max(1024, 2 c)) bytes - under 108 keys per unit - plus 256 bytes.
  * NOT given: frames fused into src cannot later be de-integrated from dst exactly (their contribution was resampled); every merge
  * resamples once, so chained merges accumulate interpolation error - to move a map, merge it ONCE into an empty volume.
+ * NOT given either: weights of 2^24 and more.  Weights and colour sums are uint32 counters that the merge adds without a check:
+ * hv_tsdf_dump reports weights as float32 (exact below 2^24 only) and a colour sum wraps past 2^32, i.e. near 1.68e7
+ * observations of a voxel at full brightness.
  * HV_ERR_MODE when either volume is not TSDF or is tile- or owner-sharded; HV_ERR_INVALID for dst == src, volumes that differ in
  * voxel_length, sdf_trunc, unit resolution or device, a non-finite T, |R^T R - I|_inf > 1e-6 (largest absolute row sum) or
  * det R < 0, a bottom row other than (0, 0, 0, 1).  HV_ERR_CAPACITY, dst unchanged, when src's pool overflowed in an earlier call

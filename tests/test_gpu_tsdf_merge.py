@@ -72,8 +72,11 @@ def neighbour_weights(src_dump, T, keys, rows, words):
     return np.stack(out, axis=-1)
 
 
-def assert_matches_restatement(gpu, before, src_dump, T, name):
-    """-> True when the dumps are equal bit for bit."""
+def assert_matches_restatement(gpu, before, src_dump, T, name, on_a_boundary=None):
+    """-> (True when the dumps are equal bit for bit, the restatement's stats).  on_a_boundary: every voxel is fragile by
+    construction, so every voxel is compared and no share bound applies (default: `name` is one of ON_A_BOUNDARY)."""
+    if on_a_boundary is None:
+        on_a_boundary = name in ON_A_BOUNDARY
     ref, stats, detail = mr.merge_reference(before, src_dump, T, VOX, detail=True)
     np.testing.assert_array_equal(gpu[0], ref[0], err_msg=f"{name}: unit set")
     fragile = np.zeros(np.asarray(ref[2]).shape, bool)
@@ -82,8 +85,8 @@ def assert_matches_restatement(gpu, before, src_dump, T, name):
         if tuple(k) in index:
             fragile[index[tuple(k)]] = detail["fragile"][j]
     share = float(fragile.mean())
-    exclude = fragile if name not in ON_A_BOUNDARY else np.zeros_like(fragile)
-    if name not in ON_A_BOUNDARY:
+    exclude = fragile if not on_a_boundary else np.zeros_like(fragile)
+    if not on_a_boundary:
         assert share <= 1e-4, (name, "fragile share", share)
         rows, words = np.nonzero(fragile)
         if len(rows):
@@ -340,12 +343,11 @@ def test_errors():
 
 
 # 8 ---------------------------------------------------------------------------------------------------------------------------
-def test_empty_source_leaves_the_destination_untouched():
+def merges_that_leave_untouched(dst, merges):
+    """`dst`, a filled volume, through `merges` (callables -> MergeStats) that update no voxel: the mesh cached before them is
+    still served without an extraction kernel (launches == 0), the dump is bitwise the same and no unit is dirty.  -> their stats."""
     from pyslam_amd import _lib as L
 
-    s, frames = tiny_frames(0, 8)
-    dst = volume(VOX, TRUNC)
-    fuse(dst, s, frames)
     dst.mark_merged()
     before = dst.dump()
     mesh = dst.extract_triangle_mesh()
@@ -354,17 +356,9 @@ def test_empty_source_leaves_the_destination_untouched():
     L.check(dst._lib.hv_tsdf_extract_mesh(dst._h, None, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)))
     dst.profile_enable(True)
     dst.profile_read()
-    never = volume(VOX, TRUNC)  # never fused
-    hollow = volume(VOX, TRUNC)  # units, but no observed voxel: fused and de-integrated
-    d, c, T = stack(frames[:2])
-    hollow.integrate_batch(*cuda(d, c), intrinsic(s), T)
-    hollow.deintegrate_batch(*cuda(d, c), intrinsic(s), T)
-    assert hollow.num_blocks() > 0
-    for src in (never, hollow):
-        st = dst.integrate_volume(src, GENERIC)
-        assert st.as_tuple() == (0, 0, 0, 0, 0)
+    stats = [merge() for merge in merges]
     # ... and the fetch after the merges is served from it: no extraction kernel runs (the profile brackets those; the merge's own
-    # candidate pass, which does run for the hollow source, is not bracketed)
+    # candidate pass, which does run for a source that holds units, is not bracketed)
     verts, cols, tris = np.zeros((nv.value, 3)), np.zeros((nv.value, 3)), np.zeros((nt.value, 3), np.int32)
     L.check(dst._lib.hv_tsdf_extract_mesh(dst._h, L.ptr(verts), L.ptr(cols), nv.value, L.ptr(tris), nt.value, ctypes.byref(nv), ctypes.byref(nt)))
     launches = dst.profile_read()[1]
@@ -374,6 +368,21 @@ def test_empty_source_leaves_the_destination_untouched():
     np.testing.assert_array_equal(tris, mesh.triangles)
     assert_bitwise(dst.dump(), before)
     assert len(dst.dirty_keys()) == 0
+    return stats
+
+
+def test_empty_source_leaves_the_destination_untouched():
+    s, frames = tiny_frames(0, 8)
+    dst = volume(VOX, TRUNC)
+    fuse(dst, s, frames)
+    never = volume(VOX, TRUNC)  # never fused
+    hollow = volume(VOX, TRUNC)  # units, but no observed voxel: fused and de-integrated
+    d, c, T = stack(frames[:2])
+    hollow.integrate_batch(*cuda(d, c), intrinsic(s), T)
+    hollow.deintegrate_batch(*cuda(d, c), intrinsic(s), T)
+    assert hollow.num_blocks() > 0
+    for st in merges_that_leave_untouched(dst, [lambda src=src: dst.integrate_volume(src, GENERIC) for src in (never, hollow)]):
+        assert st.as_tuple() == (0, 0, 0, 0, 0)
     # the other way round: a map merged into a never-used volume
     st = never.integrate_volume(dst, np.eye(4))
     assert st.units_claimed == never.num_blocks() > 0

@@ -130,6 +130,39 @@ def assert_is_shifted_source(out_dump, src_dump, shift, what):
     return err
 
 
+def assert_is_permuted_source(out_dump, src_dump, T, voxel_length, what):
+    """assert_is_shifted_source for a signed-permutation rotation with a whole-voxel translation: every observed voxel of out_dump
+    is the source voxel whose centre T carries onto it and vice versa (centre (i + 0.5) voxel_length; exact in float64 for such T) -
+    weights and colour sums exactly, tsdf within 2^-23."""
+    T = np.asarray(T, np.float64)
+    gi, t, w, c = observed_voxels(out_dump)
+    sgi, st, sw, sc = observed_voxels(src_dump)
+    assert len(gi) == len(sgi) > 0, (what, len(gi), len(sgi))
+    moved = (sgi.astype(np.float64) + 0.5) @ T[:3, :3].T + T[:3, 3] / voxel_length - 0.5
+    assert np.abs(moved - np.rint(moved)).max() < 1e-6, (what, "not a whole-voxel permutation")
+    moved = np.rint(moved).astype(np.int64)
+    a = np.lexsort(gi.T[::-1])
+    b = np.lexsort(moved.T[::-1])
+    np.testing.assert_array_equal(gi[a], moved[b], err_msg=what)
+    np.testing.assert_array_equal(w[a], sw[b], err_msg=what)
+    np.testing.assert_array_equal(c[a], sc[b], err_msg=what)
+    err = float(np.abs(t[a].astype(np.float64) - st[b].astype(np.float64)).max())
+    assert err <= 2.0 ** -23, (what, err)
+    assert (np.asarray(out_dump[2]).reshape(len(out_dump[0]), -1).max(axis=1) > 0).all(), what  # no all-zero unit is left behind
+    return err
+
+
+def fragile_share(ref_dump, detail):
+    """Share of the voxels of a restated merge's result that sit on a boundary of the rules (the figure
+    tests/test_gpu_tsdf_merge.py::assert_matches_restatement caps)."""
+    fragile = np.zeros(np.asarray(ref_dump[2]).shape, bool)
+    index = {tuple(k): i for i, k in enumerate(np.asarray(ref_dump[0]).tolist())}
+    for j, k in enumerate(detail["keys"].tolist()):
+        if tuple(k) in index:
+            fragile[index[tuple(k)]] = detail["fragile"][j]
+    return float(fragile.mean()) if fragile.size else 0.0
+
+
 @pytest.mark.parametrize("shift", [(0, 0, 0), tuple(SHIFT)])
 def test_whole_voxel_shift_reproduces_the_source(shift):
     src = tiny_dump()
