@@ -224,6 +224,47 @@ __device__ inline int32_t hv_wave_append(int32_t *counter, bool pred) {
     const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
     return pred ? base + (int32_t)__popcll(m & lt) : -1;
 }
+
+// Wave reductions (xor butterfly: every lane ends with the result); T = int32_t, uint32_t, uint64_t, float or double.
+template <typename T>
+__device__ __forceinline__ T hv_wave_sum(T x) {
+#pragma unroll
+    for (int o = HV_WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, HV_WAVE);
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T hv_wave_min(T x) {
+#pragma unroll
+    for (int o = HV_WAVE / 2; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o, HV_WAVE));
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ T hv_wave_max(T x) {
+#pragma unroll
+    for (int o = HV_WAVE / 2; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o, HV_WAVE));
+    return x;
+}
+
+// Find-or-insert of a key in a scratch key set (open addressing over keys[mask + 1], HV_EMPTY_KEY = free; no pool behind it).
+// Returns the slot, or -1 when the set is full; *is_new = this call put the key in.
+__device__ inline int32_t hv_keyset_insert(unsigned long long *keys, uint32_t mask, unsigned long long key, bool *is_new) {
+    *is_new = false;
+    uint32_t s = hv_slot_hash(key) & mask;
+    for (uint32_t probe = 0; probe <= mask; ++probe) {
+        unsigned long long k = keys[s];
+        if (k == key) return (int32_t)s;
+        if (k == HV_EMPTY_KEY) {
+            k = atomicCAS(&keys[s], HV_EMPTY_KEY, key);
+            if (k == HV_EMPTY_KEY) {
+                *is_new = true;
+                return (int32_t)s;
+            }
+            if (k == key) return (int32_t)s;
+        }
+        s = (s + 1) & mask;
+    }
+    return -1;
+}
 #endif // __HIPCC__
 
 // ------------------------------------------------------------------------------------------------
@@ -235,6 +276,30 @@ __device__ inline int32_t hv_wave_append(int32_t *counter, bool pred) {
 // (mean = sum / weight reproduces Open3D's running mean to double rounding).
 // ------------------------------------------------------------------------------------------------
 static constexpr int HV_TSDF_PLANES = 5;
+static constexpr int HV_TSDF_R = 16;
+static constexpr int HV_TSDF_RR = HV_TSDF_R * HV_TSDF_R;
+static constexpr int HV_TSDF_RRR = HV_TSDF_RR * HV_TSDF_R;
+static constexpr int HV_TSDF_PLANE_BYTES = HV_TSDF_RRR * 4;
+static constexpr int HV_TSDF_UNIT_BYTES = HV_TSDF_PLANE_BYTES * HV_TSDF_PLANES;
+
+// word index of voxel (x, y, z) inside a plane of a unit
+__host__ __device__ __forceinline__ int hv_tsdf_word(int x, int y, int z) { return z * HV_TSDF_RR + x * HV_TSDF_R + y; }
+
+#ifdef __HIPCC__
+// Does pool unit `unit` hold an observed voxel?  The whole wave asks (lane = hv_lane_id()) and gets one answer.  Streams the weight
+// plane: a lane loads 16 bytes, so one instruction of the wave covers 1 KiB; four of them are in flight per step (one load at a time
+// would wait out the memory latency sixteen times per empty unit) and the wave leaves the unit at the first step that saw a weight.
+__device__ __forceinline__ bool hv_tsdf_unit_has_weight(const char *__restrict__ pool, int32_t unit, int lane) {
+    const uint4 *w = (const uint4 *)(pool + (size_t)unit * HV_TSDF_UNIT_BYTES + HV_TSDF_PLANE_BYTES);
+    bool seen = false;
+    for (int k = 0; k < HV_TSDF_PLANE_BYTES / 1024 && !seen; k += 4) {
+        const uint4 a = w[(k + 0) * 64 + lane], b = w[(k + 1) * 64 + lane], c = w[(k + 2) * 64 + lane], d = w[(k + 3) * 64 + lane];
+        const uint32_t any = a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w;
+        seen = __ballot(any != 0) != 0ull;
+    }
+    return seen;
+}
+#endif
 
 // VOXEL_GRID voxel record: the reference's 28-byte VoxelData padded to 32 B so that one voxel is
 // two aligned 16-byte accesses and never straddles a 64-B line.

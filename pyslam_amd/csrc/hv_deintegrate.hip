@@ -24,27 +24,6 @@
 enum { HV_DEINT_LISTED = 0, HV_DEINT_MISSING = 1, HV_DEINT_REMOVED = 2, HV_DEINT_UNDERFLOW = 3, HV_DEINT_MISS_FULL = 4 };
 static constexpr size_t HV_DEINT_HDR = 256; // counter block at the head of deint_buf
 
-__device__ __forceinline__ unsigned long long hv_wave_sum_u64(unsigned long long x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
-}
-
-// Find-or-insert in the scratch key set of missing units (no pool behind it).  -1: the set is full.
-__device__ inline int32_t hv_miss_slot(unsigned long long *keys, uint32_t mask, unsigned long long key) {
-    uint32_t s = hv_slot_hash(key) & mask;
-    for (uint32_t probe = 0; probe <= mask; ++probe) {
-        unsigned long long k = keys[s];
-        if (k == key) return (int32_t)s;
-        if (k == HV_EMPTY_KEY) {
-            k = atomicCAS(&keys[s], HV_EMPTY_KEY, key);
-            if (k == HV_EMPTY_KEY || k == key) return (int32_t)s;
-        }
-        s = (s + 1) & mask;
-    }
-    return -1;
-}
-
 __global__ __launch_bounds__(256) void k_tsdf_deint_touch(HvTable table, int32_t *__restrict__ stamp,
                                                            unsigned long long *__restrict__ frame_mask, int32_t *__restrict__ list,
                                                            int batch_stamp, const char *__restrict__ depth_raw, int64_t depth_stride,
@@ -88,7 +67,8 @@ __global__ __launch_bounds__(256) void k_tsdf_deint_touch(HvTable table, int32_t
                 if (at < table.max_blocks) list[at] = slot;
             }
         } else if (miss_keys != nullptr) {
-            const int32_t ms = hv_miss_slot(miss_keys, miss_cap_mask, key);
+            bool is_new; // (not needed: the frame bit below says whether this frame counted the unit)
+            const int32_t ms = hv_keyset_insert(miss_keys, miss_cap_mask, key, &is_new);
             if (ms < 0) {
                 full += 1;
             } else if (!(atomicOr(&miss_mask[ms], fbit) & fbit)) {
@@ -98,9 +78,9 @@ __global__ __launch_bounds__(256) void k_tsdf_deint_touch(HvTable table, int32_t
         }
     });
     // (hv_touch_patch returns with the whole wave: one atomic per counter and wave)
-    listed = hv_wave_sum_u64(listed);
-    missing = hv_wave_sum_u64(missing);
-    full = hv_wave_sum_u64(full);
+    listed = hv_wave_sum(listed);
+    missing = hv_wave_sum(missing);
+    full = hv_wave_sum(full);
     if (hv_lane_id() == 0) {
         if (listed) atomicAdd(&cnt[HV_DEINT_LISTED], listed);
         if (missing) atomicAdd(&cnt[HV_DEINT_MISSING], missing);
@@ -218,28 +198,28 @@ __global__ __launch_bounds__(256) void k_tsdf_deint_sweep(HvTable table, const i
             // (whole-image frames only: tile-sharded volumes are refused).
             hv_deint_frame(P, px, mf, pc, inc0, inc1, inc2, st, rg, bn);
         }
-        char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
+        char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
 #pragma unroll
         for (int zz = 0; zz < 4; ++zz) {
             if (((bn[zz][0] | bn[zz][1] | bn[zz][2] | bn[zz][3]) >> 16) == 0u) continue;
-            const int q = ((z0 + zz) * RR + x * R + y0) >> 2;
-            float4 vt = ((const float4 *)(unit + 0 * PLANE_BYTES))[q];
-            uint4 vw = ((const uint4 *)(unit + 1 * PLANE_BYTES))[q];
-            uint4 vr = ((const uint4 *)(unit + 2 * PLANE_BYTES))[q];
-            uint4 vg = ((const uint4 *)(unit + 3 * PLANE_BYTES))[q];
-            uint4 vb = ((const uint4 *)(unit + 4 * PLANE_BYTES))[q];
+            const int q = hv_tsdf_word(x, y0, z0 + zz) >> 2;
+            float4 vt = ((const float4 *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+            uint4 vw = ((const uint4 *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
+            uint4 vr = ((const uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q];
+            uint4 vg = ((const uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q];
+            uint4 vb = ((const uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q];
             hv_deint_apply(st[zz][0], rg[zz][0], bn[zz][0], vt.x, vw.x, vr.x, vg.x, vb.x, removed, underflow);
             hv_deint_apply(st[zz][1], rg[zz][1], bn[zz][1], vt.y, vw.y, vr.y, vg.y, vb.y, removed, underflow);
             hv_deint_apply(st[zz][2], rg[zz][2], bn[zz][2], vt.z, vw.z, vr.z, vg.z, vb.z, removed, underflow);
             hv_deint_apply(st[zz][3], rg[zz][3], bn[zz][3], vt.w, vw.w, vr.w, vg.w, vb.w, removed, underflow);
-            ((float4 *)(unit + 0 * PLANE_BYTES))[q] = vt;
-            ((uint4 *)(unit + 1 * PLANE_BYTES))[q] = vw;
-            ((uint4 *)(unit + 2 * PLANE_BYTES))[q] = vr;
-            ((uint4 *)(unit + 3 * PLANE_BYTES))[q] = vg;
-            ((uint4 *)(unit + 4 * PLANE_BYTES))[q] = vb;
+            ((float4 *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = vt;
+            ((uint4 *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = vw;
+            ((uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] = vr;
+            ((uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] = vg;
+            ((uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] = vb;
         }
     }
-    const unsigned long long rs = hv_wave_sum_u64(removed), us = hv_wave_sum_u64(underflow);
+    const unsigned long long rs = hv_wave_sum<unsigned long long>(removed), us = hv_wave_sum<unsigned long long>(underflow);
     if (lane == 0) {
         if (rs) atomicAdd(&cnt[HV_DEINT_REMOVED], rs);
         if (us) atomicAdd(&cnt[HV_DEINT_UNDERFLOW], us);
@@ -296,13 +276,13 @@ static int tsdf_deintegrate_device(hv_volume *v, const void *d_depth, int32_t de
         }
         rc = tsdf_multiplier_table(v, params[0]);
         if (rc != HV_OK) return rc;
-        const size_t px_bytes = 8 * npx * (size_t)B;
-        const size_t want = ((px_bytes + 255) & ~(size_t)255) + sizeof(HvFrameParams) * (size_t)B;
+        size_t params_off = 0;
+        const size_t want = tsdf_batch_scratch(8, npx, B, &params_off);
         if (v->batch_buf_bytes < want && v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
         rc = hv_ensure_buffer(v, &v->batch_buf, &v->batch_buf_bytes, want);
         if (rc != HV_OK) return rc;
         uint2 *d_px = (uint2 *)v->batch_buf;
-        HvFrameParams *d_params = (HvFrameParams *)((char *)v->batch_buf + ((px_bytes + 255) & ~(size_t)255));
+        HvFrameParams *d_params = (HvFrameParams *)((char *)v->batch_buf + params_off);
         rc = hv_h2d(v, d_params, params.data(), sizeof(HvFrameParams) * (size_t)B); // (pageable: read before it returns)
         if (rc != HV_OK) return rc;
         if (count_missing) {

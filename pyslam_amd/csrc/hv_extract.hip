@@ -31,19 +31,13 @@
 #include "mc_tables.h"
 #include <rocprim/device/device_scan.hpp>
 
-static constexpr int R = 16;
-static constexpr int RR = R * R;
-static constexpr int RRR = R * R * R;
-static constexpr int PLANE_BYTES = RRR * 4;
-static constexpr int UNIT_BYTES = PLANE_BYTES * HV_TSDF_PLANES;
-static constexpr int MASK_WORDS = 3 * RRR / 64; // 192
+static constexpr int MASK_WORDS = 3 * HV_TSDF_RRR / 64; // 192
 
 __constant__ unsigned short c_edge_table[256];
 __constant__ __attribute__((aligned(16))) signed char c_tri_table[256][16];
 __constant__ unsigned char c_tri_count[256];
 
-__device__ __forceinline__ int voxel_word(int x, int y, int z) { return z * RR + x * R + y; }
-// A unit's 192 edge-mask words in z-MAJOR order: word = z * 12 + axis * 4 + quarter (quarter = x >> 2; the word's bit = voxel_word & 63).
+// A unit's 192 edge-mask words in z-MAJOR order: word = z * 12 + axis * 4 + quarter (quarter = x >> 2; the word's bit = hv_tsdf_word & 63).
 // The vertex ranks of a unit follow the word order, and lane j of the vertex pass builds vertices j, j + 64, ...: with the three
 // axes of a z slice next to each other a wave walks the unit's planes ONCE (round 6).  Axis-major words (rounds 2-5) walked them
 // three times, microseconds apart - longer than a 4 MB L2 holds a line at this fetch rate: 1.35 GB fetched for 152 MB of values.
@@ -71,8 +65,8 @@ __device__ inline void load_neighbours(const HvTable &table, int idx, int *s_nbr
 __device__ __forceinline__ void edge_owner(int x, int y, int z, int i, int &n, int &axis, int &lin) {
     const int ox = x + hv_mc_edge_shift[i][0], oy = y + hv_mc_edge_shift[i][1], oz = z + hv_mc_edge_shift[i][2];
     axis = hv_mc_edge_shift[i][3];
-    n = (ox >= R ? 1 : 0) | (oy >= R ? 2 : 0) | (oz >= R ? 4 : 0);
-    lin = voxel_word(ox & (R - 1), oy & (R - 1), oz & (R - 1));
+    n = (ox >= HV_TSDF_R ? 1 : 0) | (oy >= HV_TSDF_R ? 2 : 0) | (oz >= HV_TSDF_R ? 4 : 0);
+    lin = hv_tsdf_word(ox & (HV_TSDF_R - 1), oy & (HV_TSDF_R - 1), oz & (HV_TSDF_R - 1));
 }
 
 // Column masks of one unit (thread <-> column x * 16 + y; a wave load is one 256-byte run of a plane):
@@ -104,17 +98,17 @@ __global__ __launch_bounds__(256) void k_unit_masks(HvTable table, const char *_
     }
     __syncthreads();
     if (s_skip) return;
-    const char *unit = pool + (int64_t)idx * UNIT_BYTES;
-    float t[R];
-    uint32_t w[R];
+    const char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+    float t[HV_TSDF_R];
+    uint32_t w[HV_TSDF_R];
 #pragma unroll
-    for (int z = 0; z < R; ++z) {
-        t[z] = ((const float *)unit)[z * RR + threadIdx.x];
-        w[z] = ((const uint32_t *)(unit + PLANE_BYTES))[z * RR + threadIdx.x];
+    for (int z = 0; z < HV_TSDF_R; ++z) {
+        t[z] = ((const float *)unit)[z * HV_TSDF_RR + threadIdx.x];
+        w[z] = ((const uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[z * HV_TSDF_RR + threadIdx.x];
     }
     uint32_t obs = 0u, neg = 0u, inr = 0u, pos = 0u;
 #pragma unroll
-    for (int z = 0; z < R; ++z) {
+    for (int z = 0; z < HV_TSDF_R; ++z) {
         const bool o = w[z] != 0u;
         const bool r = o && t[z] < 0.98f && t[z] >= -0.98f;
         obs |= (o ? 1u : 0u) << z;
@@ -122,8 +116,8 @@ __global__ __launch_bounds__(256) void k_unit_masks(HvTable table, const char *_
         inr |= (r ? 1u : 0u) << z;
         pos |= (r && t[z] > 0.0f ? 1u : 0u) << z;
     }
-    m_on[(int64_t)idx * RR + threadIdx.x] = obs | (neg << 16);
-    m_ip[(int64_t)idx * RR + threadIdx.x] = inr | (pos << 16);
+    m_on[(int64_t)idx * HV_TSDF_RR + threadIdx.x] = obs | (neg << 16);
+    m_ip[(int64_t)idx * HV_TSDF_RR + threadIdx.x] = inr | (pos << 16);
     const uint32_t wave_signs = (__any(neg != 0u) ? 1u : 0u) | (__any((obs & ~neg) != 0u) ? 2u : 0u);
     if (hv_lane_id() == 0 && wave_signs) atomicOr(&s_signs, wave_signs);
     __syncthreads();
@@ -214,13 +208,13 @@ __global__ __launch_bounds__(256) void k_mc_classify(HvTable table, const uint32
             else if (h < 52) { cx = h - 36; cy = -1; }
             else { cx = h - 52; cy = 16; }
         }
-        const int nxy = (cx < 0 ? 0 : cx >= R ? 2 : 1) + 3 * (cy < 0 ? 0 : cy >= R ? 2 : 1);
-        const int col = (cx & (R - 1)) * R + (cy & (R - 1));
+        const int nxy = (cx < 0 ? 0 : cx >= HV_TSDF_R ? 2 : 1) + 3 * (cy < 0 ? 0 : cy >= HV_TSDF_R ? 2 : 1);
+        const int col = (cx & (HV_TSDF_R - 1)) * HV_TSDF_R + (cy & (HV_TSDF_R - 1));
         // bit k <-> z = k - 1: bit 15 of the unit below, the 16 bits of the unit at this level, bit 0 of the unit above
         const int nl = s_nbr[nxy], nm = s_nbr[nxy + 9], nh = s_nbr[nxy + 18];
-        const uint32_t lo = nl >= 0 ? m_on[(int64_t)nl * RR + col] : 0u;
-        const uint32_t mid = nm >= 0 ? m_on[(int64_t)nm * RR + col] : 0u;
-        const uint32_t hi = nh >= 0 ? m_on[(int64_t)nh * RR + col] : 0u;
+        const uint32_t lo = nl >= 0 ? m_on[(int64_t)nl * HV_TSDF_RR + col] : 0u;
+        const uint32_t mid = nm >= 0 ? m_on[(int64_t)nm * HV_TSDF_RR + col] : 0u;
+        const uint32_t hi = nh >= 0 ? m_on[(int64_t)nh * HV_TSDF_RR + col] : 0u;
         const uint32_t obs = ((lo >> 15) & 1u) | ((mid & 0xffffu) << 1) | ((hi & 1u) << 17);
         const uint32_t neg = ((lo >> 31) & 1u) | ((mid >> 16) << 1) | (((hi >> 16) & 1u) << 17);
         s_obs[(cx + 1) * H2 + (cy + 1)] = obs;
@@ -252,11 +246,11 @@ __global__ __launch_bounds__(256) void k_mc_classify(HvTable table, const uint32
     const uint32_t Ex = (g[1][1] ^ g[2][1]) & o[1][1] & o[2][1] & (Wx | (Wx << 1));
     const uint32_t Ey = (g[1][1] ^ g[1][2]) & o[1][1] & o[1][2] & (Wy | (Wy << 1));
     const uint32_t Ez = (g[1][1] ^ (g[1][1] >> 1)) & pairz(o[1][1]) & (V11 | V01 | V10 | V00);
-    // this unit's mask words: mc_word = z * 12 + axis * 4 + wave, bit = lane (= voxel_word & 63)
+    // this unit's mask words: mc_word = z * 12 + axis * 4 + wave, bit = lane (= hv_tsdf_word & 63)
     const int lane = hv_lane_id(), wave = threadIdx.x >> 6;
     unsigned long long mine = 0ull; // lane k keeps ballot k (k = axis * 16 + z)
 #pragma unroll
-    for (int z = 0; z < R; ++z) {
+    for (int z = 0; z < HV_TSDF_R; ++z) {
         const unsigned long long bx = __ballot((Ex >> (z + 1)) & 1u), by = __ballot((Ey >> (z + 1)) & 1u), bz = __ballot((Ez >> (z + 1)) & 1u);
         if (lane == z) mine = bx;
         if (lane == 16 + z) mine = by;
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(256) void k_mc_classify(HvTable table, const uint32
     int tris = 0;
     uint32_t packed[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
-    for (int z = 0; z < R; ++z) {
+    for (int z = 0; z < HV_TSDF_R; ++z) {
         int cube = (int)(((c0 >> z) & 1u) | (((c1 >> z) & 1u) << 1) | (((c2 >> z) & 1u) << 2) | (((c3 >> z) & 1u) << 3) |
                          (((c0 >> (z + 1)) & 1u) << 4) | (((c1 >> (z + 1)) & 1u) << 5) | (((c2 >> (z + 1)) & 1u) << 6) |
                          (((c3 >> (z + 1)) & 1u) << 7));
@@ -280,7 +274,7 @@ __global__ __launch_bounds__(256) void k_mc_classify(HvTable table, const uint32
         packed[z >> 2] |= (uint32_t)cube << ((z & 3) * 8);
         tris += s_tcnt[cube];
     }
-    ((uint4 *)(cases + (int64_t)idx * RRR))[threadIdx.x] = make_uint4(packed[0], packed[1], packed[2], packed[3]);
+    ((uint4 *)(cases + (int64_t)idx * HV_TSDF_RRR))[threadIdx.x] = make_uint4(packed[0], packed[1], packed[2], packed[3]);
     if (tris) atomicAdd(&s_tris, tris);
     __syncthreads();
     if (wave == 0) { // exclusive popcount prefix over the 192 mask words: three words per lane + a wave scan
@@ -349,7 +343,7 @@ __global__ __launch_bounds__(64) void k_mc_vertices(HvTable table, const char *_
     __builtin_amdgcn_wave_barrier();
     int32_t ux, uy, uz;
     hv_unpack_key(table.block_keys[idx], ux, uy, uz);
-    const char *u0 = pool + (int64_t)idx * UNIT_BYTES;
+    const char *u0 = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
     for (int r = lane; r < total; r += HV_WAVE) {
         const int64_t vi = vbase + r;
         if (vi >= cap) return;
@@ -363,31 +357,31 @@ __global__ __launch_bounds__(64) void k_mc_vertices(HvTable table, const char *_
         const int axis = (word % 12) >> 2;
         const int lin = ((word / 12) * 4 + (word & 3)) * 64 + hv_nth_set_bit(s_mask[word], r - (int)s_prefix[word]);
         // owner voxel and its +axis neighbour
-        const int z = lin / RR, x = (lin / R) % R, y = lin % R;
+        const int z = lin / HV_TSDF_RR, x = (lin / HV_TSDF_R) % HV_TSDF_R, y = lin % HV_TSDF_R;
         int nx = x + (axis == 0), ny = y + (axis == 1), nz = z + (axis == 2);
         int nidx = idx;
-        if (nx >= R || ny >= R || nz >= R) {
-            const int32_t slot = hv_table_find(table, hv_pack_key(ux + (nx >= R), uy + (ny >= R), uz + (nz >= R)));
+        if (nx >= HV_TSDF_R || ny >= HV_TSDF_R || nz >= HV_TSDF_R) {
+            const int32_t slot = hv_table_find(table, hv_pack_key(ux + (nx >= HV_TSDF_R), uy + (ny >= HV_TSDF_R), uz + (nz >= HV_TSDF_R)));
             nidx = slot >= 0 ? table.vals[slot] : -1;
-            nx &= R - 1; ny &= R - 1; nz &= R - 1;
+            nx &= HV_TSDF_R - 1; ny &= HV_TSDF_R - 1; nz &= HV_TSDF_R - 1;
         }
         const double f0 = fabs((double)((const float *)u0)[lin]);
-        const double w0 = (double)((const uint32_t *)(u0 + PLANE_BYTES))[lin];
+        const double w0 = (double)((const uint32_t *)(u0 + HV_TSDF_PLANE_BYTES))[lin];
         double c0[3], c1[3] = {0, 0, 0};
 #pragma unroll
-        for (int k = 0; k < 3; ++k) c0[k] = ((double)((const uint32_t *)(u0 + (2 + k) * PLANE_BYTES))[lin] / w0) / 255.0;
+        for (int k = 0; k < 3; ++k) c0[k] = ((double)((const uint32_t *)(u0 + (2 + k) * HV_TSDF_PLANE_BYTES))[lin] / w0) / 255.0;
         double f1 = 0.0;
         if (nidx >= 0) {
-            const char *u1 = pool + (int64_t)nidx * UNIT_BYTES;
-            const int nl = voxel_word(nx, ny, nz);
+            const char *u1 = pool + (int64_t)nidx * HV_TSDF_UNIT_BYTES;
+            const int nl = hv_tsdf_word(nx, ny, nz);
             f1 = fabs((double)((const float *)u1)[nl]);
-            const double w1 = (double)((const uint32_t *)(u1 + PLANE_BYTES))[nl];
+            const double w1 = (double)((const uint32_t *)(u1 + HV_TSDF_PLANE_BYTES))[nl];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) c1[k] = ((double)((const uint32_t *)(u1 + (2 + k) * PLANE_BYTES))[nl] / w1) / 255.0;
+            for (int k = 0; k < 3; ++k) c1[k] = ((double)((const uint32_t *)(u1 + (2 + k) * HV_TSDF_PLANE_BYTES))[nl] / w1) / 255.0;
         }
-        double pt[3] = {M.half_voxel_length + M.voxel_length * (double)(ux * R + x),
-                        M.half_voxel_length + M.voxel_length * (double)(uy * R + y),
-                        M.half_voxel_length + M.voxel_length * (double)(uz * R + z)};
+        double pt[3] = {M.half_voxel_length + M.voxel_length * (double)(ux * HV_TSDF_R + x),
+                        M.half_voxel_length + M.voxel_length * (double)(uy * HV_TSDF_R + y),
+                        M.half_voxel_length + M.voxel_length * (double)(uz * HV_TSDF_R + z)};
         pt[axis] += f0 * M.voxel_length / (f0 + f1);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -428,7 +422,7 @@ __global__ __launch_bounds__(256) void k_mc_triangles(HvTable table, int n_units
         s_mask[threadIdx.x] = edge_mask[(int64_t)idx * MASK_WORDS + threadIdx.x];
         s_pref[threadIdx.x] = word_prefix[(int64_t)idx * MASK_WORDS + threadIdx.x];
     }
-    const uint4 pk = ((const uint4 *)(cases + (int64_t)idx * RRR))[threadIdx.x];
+    const uint4 pk = ((const uint4 *)(cases + (int64_t)idx * HV_TSDF_RRR))[threadIdx.x];
     s_cases[threadIdx.x] = pk;
     __syncthreads();
     if (threadIdx.x < 8) s_vbase[threadIdx.x] = s_nbr[threadIdx.x] >= 0 ? (int32_t)(uint32_t)bases[s_nbr[threadIdx.x]] : 0;
@@ -436,7 +430,7 @@ __global__ __launch_bounds__(256) void k_mc_triangles(HvTable table, int n_units
     int tris = 0;
     unsigned long long nib = 0ull; // nibble z: triangles of the column's cube z (at most 5)
 #pragma unroll
-    for (int z = 0; z < R; ++z) {
+    for (int z = 0; z < HV_TSDF_R; ++z) {
         const int c = s_tcnt[(packed[z >> 2] >> ((z & 3) * 8)) & 255u];
         tris += c;
         nib |= (unsigned long long)c << (4 * z);
@@ -469,7 +463,7 @@ __global__ __launch_bounds__(256) void k_mc_triangles(HvTable table, int n_units
         const int x = lo >> 4, y = lo & 15;
         unsigned long long cw = s_nib[lo];
         int j = r - s_pre[lo], z = 0;
-        for (; z < R - 1; ++z) {
+        for (; z < HV_TSDF_R - 1; ++z) {
             const int c = (int)(cw & 15ull);
             if (j < c) break;
             j -= c;
@@ -537,8 +531,8 @@ __global__ __launch_bounds__(256) void k_pc_extract(HvTable table, const char *_
         const int nb = s_nbr[n];
         uint32_t ip = 0u, on = 0u;
         if (nb >= 0) {
-            ip = m_ip[(int64_t)nb * RR + col];
-            on = m_on[(int64_t)nb * RR + col];
+            ip = m_ip[(int64_t)nb * HV_TSDF_RR + col];
+            on = m_on[(int64_t)nb * HV_TSDF_RR + col];
         }
         inr = ip & 0xffffu;
         pos = ip >> 16;
@@ -546,8 +540,8 @@ __global__ __launch_bounds__(256) void k_pc_extract(HvTable table, const char *_
     };
     uint32_t ia, na, pa, ib, nb_, pb, ic, nc, pc, id, nd, pd;
     column(0, (int)threadIdx.x, ia, na, pa);
-    column(x == R - 1 ? 1 : 0, ((x + 1) & (R - 1)) * R + y, ib, nb_, pb);
-    column(y == R - 1 ? 2 : 0, x * R + ((y + 1) & (R - 1)), ic, nc, pc);
+    column(x == HV_TSDF_R - 1 ? 1 : 0, ((x + 1) & (HV_TSDF_R - 1)) * HV_TSDF_R + y, ib, nb_, pb);
+    column(y == HV_TSDF_R - 1 ? 2 : 0, x * HV_TSDF_R + ((y + 1) & (HV_TSDF_R - 1)), ic, nc, pc);
     column(4, (int)threadIdx.x, id, nd, pd); // z = 16: bit 0 of the unit above
     const uint32_t hx = ia & ib & ((na & pb) | (pa & nb_));
     const uint32_t hy = ia & ic & ((na & pc) | (pa & nc));
@@ -585,7 +579,7 @@ __global__ __launch_bounds__(256) void k_pc_extract(HvTable table, const char *_
     if (total == 0) return;
     int32_t ux, uy, uz;
     hv_unpack_key(table.block_keys[idx], ux, uy, uz);
-    const char *u0 = pool + (int64_t)idx * UNIT_BYTES;
+    const char *u0 = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
     const int64_t vbase = base[idx];
     for (int r = threadIdx.x; r < total; r += 256) {
         const int64_t at = vbase + r;
@@ -598,21 +592,21 @@ __global__ __launch_bounds__(256) void k_pc_extract(HvTable table, const char *_
         const int x = lo >> 4, y = lo & 15;
         const int bit = hv_nth_set_bit(s_hits[lo], r - s_pre[lo]);
         const int i = bit >> 4, z = bit & 15;
-        const int lin = voxel_word(x, y, z);
+        const int lin = hv_tsdf_word(x, y, z);
         const float f0 = ((const float *)u0)[lin];
-        const uint32_t w0 = ((const uint32_t *)(u0 + PLANE_BYTES))[lin];
+        const uint32_t w0 = ((const uint32_t *)(u0 + HV_TSDF_PLANE_BYTES))[lin];
         int nx = x + (i == 0), ny = y + (i == 1), nz = z + (i == 2);
-        const int ni = s_nbr[(nx >= R ? 1 : 0) | (ny >= R ? 2 : 0) | (nz >= R ? 4 : 0)];
-        nx &= R - 1; ny &= R - 1; nz &= R - 1;
-        const char *u1 = pool + (int64_t)ni * UNIT_BYTES;
-        const int l1 = voxel_word(nx, ny, nz);
+        const int ni = s_nbr[(nx >= HV_TSDF_R ? 1 : 0) | (ny >= HV_TSDF_R ? 2 : 0) | (nz >= HV_TSDF_R ? 4 : 0)];
+        nx &= HV_TSDF_R - 1; ny &= HV_TSDF_R - 1; nz &= HV_TSDF_R - 1;
+        const char *u1 = pool + (int64_t)ni * HV_TSDF_UNIT_BYTES;
+        const int l1 = hv_tsdf_word(nx, ny, nz);
         const float f1 = ((const float *)u1)[l1];
-        const double w1 = (double)((const uint32_t *)(u1 + PLANE_BYTES))[l1];
+        const double w1 = (double)((const uint32_t *)(u1 + HV_TSDF_PLANE_BYTES))[l1];
         float c0[3], c1[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) { // color_.cast<float>() of the double running mean
-            c0[k] = (float)((double)((const uint32_t *)(u0 + (2 + k) * PLANE_BYTES))[lin] / (double)w0);
-            c1[k] = (float)((double)((const uint32_t *)(u1 + (2 + k) * PLANE_BYTES))[l1] / w1);
+            c0[k] = (float)((double)((const uint32_t *)(u0 + (2 + k) * HV_TSDF_PLANE_BYTES))[lin] / (double)w0);
+            c1[k] = (float)((double)((const uint32_t *)(u1 + (2 + k) * HV_TSDF_PLANE_BYTES))[l1] / w1);
         }
         const double p0[3] = {(M.half_voxel_length + M.voxel_length * (double)x) + (double)ux * unit_length,
                               (M.half_voxel_length + M.voxel_length * (double)y) + (double)uy * unit_length,
@@ -697,7 +691,7 @@ extern "C" {
 // cloud of the same contents computes them once)
 // The three per-unit caches (hv_common.h: incremental extraction) are laid out for unit_cache_cap units; a pool that outgrows the
 // layout gets new buffers and one full pass.
-static constexpr size_t MC_UNIT_BYTES = sizeof(uint64_t) * MASK_WORDS + sizeof(uint32_t) * MASK_WORDS + RRR;
+static constexpr size_t MC_UNIT_BYTES = sizeof(uint64_t) * MASK_WORDS + sizeof(uint32_t) * MASK_WORDS + HV_TSDF_RRR;
 static int unit_caches_ensure(hv_volume *v, int n) {
     if (n <= v->unit_cache_cap && v->unit_masks != nullptr) return HV_OK;
     int cap = 1024;
@@ -711,7 +705,7 @@ static int unit_caches_ensure(hv_volume *v, int n) {
     v->unit_masks_version = 0;
     v->unit_masks_epoch = v->mc_epoch = v->pc_epoch = 0; // (no epoch is 0: everything is computed in full)
     // masks: [m_on cap*256][m_ip cap*256][unit_signs cap][mask_stamp cap]
-    HV_HIP(hipMalloc(&v->unit_masks, sizeof(uint32_t) * (size_t)cap * (2 * RR + 2)));
+    HV_HIP(hipMalloc(&v->unit_masks, sizeof(uint32_t) * (size_t)cap * (2 * HV_TSDF_RR + 2)));
     HV_HIP(hipMalloc(&v->mc_cache, MC_UNIT_BYTES * (size_t)cap + sizeof(uint64_t) * ((size_t)cap + 1) + 256));
     HV_HIP(hipMalloc(&v->pc_cache, sizeof(int32_t) * ((size_t)cap + 1)));
     v->unit_cache_cap = cap;
@@ -727,7 +721,7 @@ static int unit_masks_compute(hv_volume *v, int n, HvUnitMasks *out) {
     int rc = unit_caches_ensure(v, n);
     if (rc != HV_OK) return rc;
     const size_t cap = (size_t)v->unit_cache_cap;
-    uint32_t *on = (uint32_t *)v->unit_masks, *ip = on + (size_t)RR * cap, *signs = ip + (size_t)RR * cap;
+    uint32_t *on = (uint32_t *)v->unit_masks, *ip = on + (size_t)HV_TSDF_RR * cap, *signs = ip + (size_t)HV_TSDF_RR * cap;
     int32_t *stamp = (int32_t *)(signs + cap);
     if (v->unit_masks_version != v->content_version || v->unit_masks_units != n) {
         const bool full = v->unit_masks_epoch != v->extract_epoch || v->touched_stamp == nullptr || n < v->unit_masks_units || hv_extract_full();
@@ -884,7 +878,7 @@ static int points_compute(hv_volume *v, bool f32) {
     const bool pc_full = v->pc_epoch != v->extract_epoch || nu < v->pc_units || hv_extract_full();
     HV_HIP(hipMemsetAsync(count + nu, 0, sizeof(int32_t), v->stream)); // the scan's extra element
     hipLaunchKernelGGL((k_pc_extract<false, double>), dim3(nu), dim3(256), 0, v->stream, v->table, (const char *)v->pool, m_on, m_ip, nu, M,
-                       v->cfg.voxel_size * (double)R, count, (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (int64_t)0,
+                       v->cfg.voxel_size * (double)HV_TSDF_R, count, (const int32_t *)nullptr, (double *)nullptr, (double *)nullptr, (int64_t)0,
                        UM.stamp, pc_full ? (int32_t)-1 : v->pc_stamp);
     HV_HIP(hipGetLastError());
     v->pc_epoch = v->extract_epoch;
@@ -904,11 +898,11 @@ static int points_compute(hv_volume *v, bool f32) {
         if (f32) {
             float *d_pts = (float *)v->out_a, *d_cols = d_pts + 3 * n;
             hipLaunchKernelGGL((k_pc_extract<true, float>), dim3(nu), dim3(256), 0, v->stream, v->table, (const char *)v->pool, m_on, m_ip, nu, M,
-                               v->cfg.voxel_size * (double)R, (int32_t *)nullptr, (const int32_t *)base, d_pts, d_cols, n, UM.stamp, (int32_t)-1);
+                               v->cfg.voxel_size * (double)HV_TSDF_R, (int32_t *)nullptr, (const int32_t *)base, d_pts, d_cols, n, UM.stamp, (int32_t)-1);
         } else {
             double *d_pts = (double *)v->out_a, *d_cols = d_pts + 3 * n;
             hipLaunchKernelGGL((k_pc_extract<true, double>), dim3(nu), dim3(256), 0, v->stream, v->table, (const char *)v->pool, m_on, m_ip, nu, M,
-                               v->cfg.voxel_size * (double)R, (int32_t *)nullptr, (const int32_t *)base, d_pts, d_cols, n, UM.stamp, (int32_t)-1);
+                               v->cfg.voxel_size * (double)HV_TSDF_R, (int32_t *)nullptr, (const int32_t *)base, d_pts, d_cols, n, UM.stamp, (int32_t)-1);
         }
         hv_profile_end(v, nb);
         HV_HIP(hipGetLastError());
@@ -966,7 +960,7 @@ int hv_tsdf_extract_point_normals(hv_volume *v, double *normals, int64_t cap, in
     if (rc != HV_OK) return rc;
     hv_profile_begin(v);
     hipLaunchKernelGGL(k_pc_normals, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, v->stream, v->table, (const char *)v->pool,
-                       v->cfg.voxel_size, v->cfg.voxel_size * (double)R, (const double *)v->out_a, m, (double *)v->out_b);
+                       v->cfg.voxel_size, v->cfg.voxel_size * (double)HV_TSDF_R, (const double *)v->out_a, m, (double *)v->out_b);
     hv_profile_end(v, 0);
     HV_HIP(hipGetLastError());
     HV_HIP(hipMemcpyAsync(normals, v->out_b, sizeof(double) * 3 * m, hipMemcpyDefault, v->stream));

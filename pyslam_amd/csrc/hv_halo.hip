@@ -1,15 +1,23 @@
-// libpyslam_hipvol.so - the halo merge's key lists and plan ON THE DEVICE (round 6).
+// libpyslam_hipvol.so - the exchange of TSDF units between GPUs: numerators export / import (a gather onto one rank) and the halo
+// merge of image-tile-sharded volumes (include/hipvol.h "halo merge", pyslam_amd/distributed.py::merge_halo).
 //
-// The halo merge of image-tile-sharded TSDF volumes (include/hipvol.h "halo merge", pyslam_amd/distributed.py::merge_halo) needs every
-// rank's list of units written since its last merge and its list of units held, and from the all-gathered lists the plan: the keys some
-// rank updated that two ranks or more hold, with this rank's action.  Rounds 3-5 downloaded the lists, gathered them through host
-// arrays (two .cpu() per merge) and planned on the host (hv_merge_halo_plan_held: a std::sort of (key, rank) pairs).  Here the lists
-// are written as packed 64-bit keys into DEVICE buffers of the caller (torch tensors: what RCCL's all_gather_into_tensor takes), the
-// plan is a device radix sort + two small kernels, and the shared keys / actions stay in the volume for hv_merge_halo_pack_planned /
-// _unpack_planned (hv_tsdf.hip).  What still crosses to the host is three integers per merge: the two list lengths (they size the
-// gather) and the number of shared units (it sizes the payload).  Same plan as the host function, in packed-key order instead of
-// (x, y, z) order - every rank of a group takes the same path, and tests/test_gpu_distributed.py holds the two to each other.
+// The library packs and unpacks on the device (k_tsdf_export / _import / _halo_unpack: a unit travels as five float numerators per
+// voxel, tsdf * w, w and the colour sums, so that an all-reduce adds observations); the caller runs the collectives with whatever
+// transport it has - torch.distributed over RCCL in pyslam_amd/distributed.py.
+//
+// The halo merge needs every rank's list of units written since its last merge and its list of units held, and from the
+// all-gathered lists the plan: the keys some rank updated that two ranks or more hold, with this rank's action.  Two forms:
+//   host    hv_tsdf_dirty_keys + hv_merge_halo_plan / _plan_held (a std::sort of (key, rank) pairs) + hv_merge_halo_pack / _unpack;
+//   device  (round 6) the lists are written as packed 64-bit keys into DEVICE buffers of the caller (torch
+//           tensors: what RCCL's all_gather_into_tensor takes), the plan is a device radix sort + two small kernels, and the shared
+//           keys / actions stay in the volume for hv_merge_halo_pack_planned / _unpack_planned.  What still crosses to the host is
+//           three integers per merge: the two list lengths (they size the gather) and the number of shared units (it sizes the
+//           payload).  Same plan as the host function, in packed-key order instead of (x, y, z) order - every rank of a group takes
+//           the same path, and tests/test_gpu_distributed.py holds the two to each other.
 #include <algorithm>
+#include <array>
+#include <cstring>
+#include <vector>
 
 #include "hv_common.h"
 #include <rocprim/device/device_radix_sort.hpp>
@@ -95,6 +103,120 @@ __global__ __launch_bounds__(256) void k_halo_emit(const unsigned long long *__r
     out_keys[at * 3 + 1] = y;
     out_keys[at * 3 + 2] = z;
     out_act[at] = act[i];
+}
+
+// ---- numerators export / import (multi-GPU merge) ----------------------------------------------
+__global__ void k_tsdf_export(HvTable table, const char *__restrict__ pool, const int32_t *__restrict__ keys,
+                              int64_t k, float *__restrict__ payload) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= k * HV_TSDF_RRR) return;
+    const int64_t ui = gid / HV_TSDF_RRR;
+    const int word = (int)(gid % HV_TSDF_RRR);
+    float out[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
+    if (hv_key_in_range(kx, ky, kz)) {
+        const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
+        const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
+        if (idx >= 0) {
+            const char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+            const float tsdf = ((const float *)(unit))[word];
+            const uint32_t w = ((const uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word];
+            out[0] = tsdf * (float)w;
+            out[1] = (float)w;
+            out[2] = (float)((const uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word];
+            out[3] = (float)((const uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word];
+            out[4] = (float)((const uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word];
+        }
+    }
+    float *dst = payload + gid * 5;
+#pragma unroll
+    for (int c = 0; c < 5; ++c) dst[c] = out[c];
+}
+
+__global__ void k_tsdf_import_claim(HvTable table, const int32_t *__restrict__ keys, int64_t k) {
+    const int64_t ui = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (ui >= k) return;
+    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
+    if (!hv_key_in_range(kx, ky, kz)) {
+        atomicAdd(&table.counters[HV_CNT_DROPPED], 1);
+        return;
+    }
+    hv_table_insert(table, hv_pack_key(kx, ky, kz));
+}
+
+__global__ void k_tsdf_import(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys,
+                              int64_t k, const float *__restrict__ payload) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= k * HV_TSDF_RRR) return;
+    const int64_t ui = gid / HV_TSDF_RRR;
+    const int word = (int)(gid % HV_TSDF_RRR);
+    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
+    if (!hv_key_in_range(kx, ky, kz)) return;
+    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
+    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
+    if (idx < 0) return;
+    const float *src = payload + gid * 5;
+    char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+    const float w = src[1];
+    ((float *)unit)[word] = w > 0.f ? src[0] / w : 0.f;
+    ((uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word] = (uint32_t)w;
+    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[2];
+    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[3];
+    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[4];
+}
+
+// ---- halo merge (image-tile sharding): units stamped since the last merge, and the unpack ------------
+__global__ void k_tsdf_collect_dirty(HvTable table, const int32_t *__restrict__ stamp, int32_t merge_stamp, int32_t n_blocks,
+                                     int32_t *__restrict__ keys, int32_t cap) {
+    const int32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    bool dirty = false;
+    int32_t kx = 0, ky = 0, kz = 0;
+    if (idx < n_blocks) {
+        const unsigned long long key = table.block_keys[idx];
+        const int32_t slot = hv_table_find(table, key);
+        dirty = slot >= 0 && stamp[slot] > merge_stamp;
+        hv_unpack_key(key, kx, ky, kz);
+    }
+    const int32_t at = hv_wave_append(&table.counters[HV_CNT_OUT], dirty);
+    if (dirty && at < cap) {
+        keys[at * 3 + 0] = kx;
+        keys[at * 3 + 1] = ky;
+        keys[at * 3 + 2] = kz;
+    }
+}
+
+// action[u]: 0 = leave the unit alone (this GPU does not hold it), 1 = replace its state by the reduced numerators (this GPU
+// keeps the unit), 2 = zero it (another GPU keeps it; this one goes on fusing deltas into an empty unit)
+__global__ void k_tsdf_halo_unpack(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys, int64_t k,
+                                   const float *__restrict__ payload, const uint8_t *__restrict__ action) {
+    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= k * HV_TSDF_RRR) return;
+    const int64_t ui = gid / HV_TSDF_RRR;
+    const int act = action[ui];
+    if (act == 0) return;
+    const int word = (int)(gid % HV_TSDF_RRR);
+    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
+    if (!hv_key_in_range(kx, ky, kz)) return;
+    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
+    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
+    if (idx < 0) return;
+    char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+    float tsdf = 0.f;
+    uint32_t w = 0u, r = 0u, g = 0u, b = 0u;
+    if (act == 1) {
+        const float *src = payload + gid * 5;
+        const float wf = src[1];
+        tsdf = wf > 0.f ? src[0] / wf : 0.f;
+        w = (uint32_t)wf;
+        r = (uint32_t)src[2];
+        g = (uint32_t)src[3];
+        b = (uint32_t)src[4];
+    }
+    ((float *)unit)[word] = tsdf;
+    ((uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word] = w;
+    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word] = r;
+    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word] = g;
+    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word] = b;
 }
 
 extern "C" {
@@ -193,6 +315,275 @@ int hv_merge_halo_plan_fetch(hv_volume *v, int32_t *shared_keys, uint8_t *action
     HV_HIP(hipMemcpyAsync(shared_keys, v->halo_plan, sizeof(int32_t) * 3 * (size_t)m, hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipMemcpyAsync(action, (const uint8_t *)v->halo_plan + (size_t)v->halo_plan_n * 12, (size_t)m, hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+int hv_tsdf_export_numerators(hv_volume *v, const int32_t *keys, int64_t k, float *payload, int32_t loc) {
+    HV_REQUIRE(v != nullptr && (k == 0 || (keys != nullptr && payload != nullptr)), HV_ERR_INVALID,
+               "hv_tsdf_export_numerators: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_export_numerators: not a TSDF volume");
+    if (k == 0) return HV_OK;
+    HV_HIP(hipSetDevice(v->device));
+    const void *d_keys = nullptr;
+    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
+    if (rc != HV_OK) return rc;
+    const size_t bytes = sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k;
+    float *d_payload = payload;
+    if (loc == HV_HOST) {
+        v->mesh_cache_version = v->points_cache_version = 0; // out_a is about to be overwritten
+        rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, bytes);
+        if (rc != HV_OK) return rc;
+        d_payload = (float *)v->out_a;
+    }
+    const int64_t total = k * HV_TSDF_RRR;
+    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                       (const char *)v->pool, (const int32_t *)d_keys, k, d_payload);
+    HV_HIP(hipGetLastError());
+    if (loc == HV_HOST) {
+        HV_HIP(hipMemcpyAsync(payload, d_payload, bytes, hipMemcpyDeviceToHost, v->stream));
+    }
+    HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, const float *payload, int32_t loc) {
+    HV_REQUIRE(v != nullptr && (k == 0 || (keys != nullptr && payload != nullptr)), HV_ERR_INVALID,
+               "hv_tsdf_import_numerators: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_import_numerators: not a TSDF volume");
+    if (k == 0) return HV_OK;
+    v->content_version += 1;
+    v->extract_epoch += 1; // (writes voxels without stamping their units)
+    HV_HIP(hipSetDevice(v->device));
+    const void *d_keys = nullptr, *d_payload = nullptr;
+    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
+    if (rc != HV_OK) return rc;
+    rc = hv_stage_in(v, payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k, loc, 1, &d_payload);
+    if (rc != HV_OK) return rc;
+    // the imported units are claimed first and the claims verified (this call synchronises anyway): a pool that is too small
+    // grows before anything is written, or the call fails with the volume unchanged (a gather onto a root whose
+    // pool was sized like every other rank's)
+    bool checked = false;
+    rc = hv_capacity_gate(v, &checked);
+    if (rc != HV_OK) return rc;
+    for (int attempt = 0;; ++attempt) {
+        hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                           (const int32_t *)d_keys, k);
+        rc = hv_claims_fit(v);
+        if (rc == HV_OK) break;
+        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
+    }
+    const int64_t total = k * HV_TSDF_RRR;
+    hipLaunchKernelGGL(k_tsdf_import, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                       (char *)v->pool, (const int32_t *)d_keys, k, (const float *)d_payload);
+    HV_HIP(hipGetLastError());
+    hv_launch_publish_status(v); // the imported units are part of the published occupancy (a later rollback keeps them)
+    HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+// ---- halo merge entry points (SURVEY 8b hv_merge_halo, 8e): the library packs / unpacks on the device, the caller runs
+// the two collectives (all-gather of key lists, all-reduce of the dense buffer) with whatever transport it has -
+// torch.distributed over RCCL in pyslam_amd/distributed.py ----
+int hv_tsdf_dirty_keys(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n) {
+    HV_REQUIRE(v != nullptr && n != nullptr, HV_ERR_INVALID, "hv_tsdf_dirty_keys: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_dirty_keys: not a TSDF volume");
+    HV_HIP(hipSetDevice(v->device));
+    int64_t nb = 0;
+    int rc = hv_num_blocks(v, &nb);
+    if (rc != HV_OK) return rc;
+    *n = 0;
+    if (nb == 0) return HV_OK;
+    v->mesh_cache_version = v->points_cache_version = 0; // out_a is reused below
+    rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, sizeof(int32_t) * 3 * (size_t)nb);
+    if (rc != HV_OK) return rc;
+    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
+    hipLaunchKernelGGL(k_tsdf_collect_dirty, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                       (const int32_t *)v->touched_stamp, v->merge_stamp, (int32_t)nb, (int32_t *)v->out_a, (int32_t)nb);
+    HV_HIP(hipGetLastError());
+    rc = hv_read_counters(v);
+    if (rc != HV_OK) return rc;
+    const int64_t nd = v->h_counters[HV_CNT_OUT];
+    *n = nd;
+    if (keys == nullptr || nd == 0) return HV_OK;
+    std::vector<std::array<int32_t, 3>> out((size_t)nd);
+    HV_HIP(hipMemcpy(out.data(), v->out_a, sizeof(int32_t) * 3 * (size_t)nd, hipMemcpyDeviceToHost));
+    std::sort(out.begin(), out.end());
+    const int64_t m = std::min(nd, cap);
+    for (int64_t i = 0; i < m; ++i) memcpy(keys + i * 3, out[i].data(), 12);
+    return HV_OK;
+}
+
+int hv_tsdf_mark_merged(hv_volume *v) {
+    HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "hv_tsdf_mark_merged: null volume");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_mark_merged: not a TSDF volume");
+    v->merge_stamp = v->frame_counter;
+    return HV_OK;
+}
+
+int hv_merge_halo_plan(const int32_t *gathered_keys, const int64_t *counts, int32_t world_size, int32_t rank,
+                       int32_t *shared_keys, uint8_t *action, int64_t cap, int64_t *n_shared) {
+    HV_REQUIRE(counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size, HV_ERR_INVALID,
+               "hv_merge_halo_plan: bad argument");
+    // (key, rank) pairs of every rank's dirty list, sorted by key then rank; a key listed by >= 2 ranks is shared
+    struct Entry { std::array<int32_t, 3> key; int32_t rank; };
+    int64_t total = 0;
+    for (int r = 0; r < world_size; ++r) total += counts[r];
+    HV_REQUIRE(total == 0 || gathered_keys != nullptr, HV_ERR_INVALID, "hv_merge_halo_plan: null key list");
+    std::vector<Entry> all((size_t)total);
+    int64_t at = 0;
+    for (int r = 0; r < world_size; ++r)
+        for (int64_t i = 0; i < counts[r]; ++i, ++at) {
+            memcpy(all[at].key.data(), gathered_keys + at * 3, 12);
+            all[at].rank = r;
+        }
+    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) { return a.key != b.key ? a.key < b.key : a.rank < b.rank; });
+    int64_t ns = 0;
+    for (int64_t i = 0; i < total;) {
+        int64_t j = i;
+        bool mine = false;
+        while (j < total && all[j].key == all[i].key) {
+            mine |= all[j].rank == rank;
+            ++j;
+        }
+        if (j - i >= 2) { // listed by two ranks or more (a rank lists a key once)
+            if (shared_keys != nullptr && action != nullptr && ns < cap) {
+                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
+                // the lowest listing rank keeps the unit; EVERY other rank zeroes its copy if it has one - also a rank that holds
+                // the unit from an earlier window without having listed it now: the pack step exports whatever a rank holds,
+                // so a holder that kept its copy would be counted twice (unpack is a no-op where the unit does not exist)
+                action[ns] = all[i].rank == rank ? 1 : 2;
+                (void)mine;
+            }
+            ++ns;
+        }
+        i = j;
+    }
+    *n_shared = ns;
+    return HV_OK;
+}
+
+int hv_merge_halo_plan_held(const int32_t *dirty_keys, const int64_t *dirty_counts, const int32_t *held_keys,
+                            const int64_t *held_counts, int32_t world_size, int32_t rank, int32_t *shared_keys, uint8_t *action,
+                            int64_t cap, int64_t *n_shared) {
+    HV_REQUIRE(dirty_counts != nullptr && held_counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size,
+               HV_ERR_INVALID, "hv_merge_halo_plan_held: bad argument");
+    // (key, rank, kind) of every rank's two lists; a key is merged when some rank updated it since its last merge AND two
+    // ranks or more hold it: afterwards the lowest HOLDING rank has the complete unit and every other holder zeros
+    struct Entry { std::array<int32_t, 3> key; int32_t rank; int32_t dirty; };
+    int64_t nd = 0, nh = 0;
+    for (int r = 0; r < world_size; ++r) {
+        nd += dirty_counts[r];
+        nh += held_counts[r];
+    }
+    HV_REQUIRE((nd == 0 || dirty_keys != nullptr) && (nh == 0 || held_keys != nullptr), HV_ERR_INVALID, "hv_merge_halo_plan_held: null key list");
+    std::vector<Entry> all((size_t)(nd + nh));
+    int64_t at = 0, src = 0;
+    for (int r = 0; r < world_size; ++r)
+        for (int64_t i = 0; i < dirty_counts[r]; ++i, ++at, ++src) {
+            memcpy(all[at].key.data(), dirty_keys + src * 3, 12);
+            all[at].rank = r;
+            all[at].dirty = 1;
+        }
+    src = 0;
+    for (int r = 0; r < world_size; ++r)
+        for (int64_t i = 0; i < held_counts[r]; ++i, ++at, ++src) {
+            memcpy(all[at].key.data(), held_keys + src * 3, 12);
+            all[at].rank = r;
+            all[at].dirty = 0;
+        }
+    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) {
+        if (a.key != b.key) return a.key < b.key;
+        if (a.rank != b.rank) return a.rank < b.rank;
+        return a.dirty < b.dirty;
+    });
+    int64_t ns = 0;
+    const int64_t total = nd + nh;
+    for (int64_t i = 0; i < total;) {
+        int64_t j = i;
+        int holders = 0, keeper = -1, last_holder = -1;
+        bool any_dirty = false;
+        while (j < total && all[j].key == all[i].key) {
+            if (all[j].dirty) {
+                any_dirty = true;
+            } else if (all[j].rank != last_holder) {
+                last_holder = all[j].rank;
+                if (keeper < 0) keeper = all[j].rank;
+                ++holders;
+            }
+            ++j;
+        }
+        if (any_dirty && holders >= 2) {
+            if (shared_keys != nullptr && action != nullptr && ns < cap) {
+                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
+                action[ns] = keeper == rank ? 1 : 2;
+            }
+            ++ns;
+        }
+        i = j;
+    }
+    *n_shared = ns;
+    return HV_OK;
+}
+
+int hv_merge_halo_pack(hv_volume *v, const int32_t *shared_keys, int64_t k, float *payload, int32_t loc) {
+    return hv_tsdf_export_numerators(v, shared_keys, k, payload, loc);
+}
+
+int hv_merge_halo_unpack(hv_volume *v, const int32_t *shared_keys, int64_t k, const float *payload, const uint8_t *action,
+                         int32_t loc) {
+    HV_REQUIRE(v != nullptr && (k == 0 || (shared_keys != nullptr && payload != nullptr && action != nullptr)), HV_ERR_INVALID,
+               "hv_merge_halo_unpack: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_unpack: not a TSDF volume");
+    if (k == 0) return HV_OK;
+    v->content_version += 1;
+    v->extract_epoch += 1; // (writes voxels without stamping their units)
+    HV_HIP(hipSetDevice(v->device));
+    // keys + actions in one staging buffer, payload in the other
+    std::vector<char> host((size_t)k * 13);
+    memcpy(host.data(), shared_keys, (size_t)k * 12);
+    memcpy(host.data() + (size_t)k * 12, action, (size_t)k);
+    const void *d_ka = nullptr, *d_payload = nullptr;
+    int rc = hv_stage_in(v, host.data(), host.size(), HV_HOST, 0, &d_ka);
+    if (rc != HV_OK) return rc;
+    rc = hv_stage_in(v, payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k, loc, 1, &d_payload);
+    if (rc != HV_OK) return rc;
+    const int64_t total = k * HV_TSDF_RRR;
+    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                       (char *)v->pool, (const int32_t *)d_ka, k, (const float *)d_payload,
+                       (const uint8_t *)d_ka + (size_t)k * 12);
+    HV_HIP(hipGetLastError());
+    HV_HIP(hipStreamSynchronize(v->stream)); // `host` goes out of scope
+    return HV_OK;
+}
+
+// ... with the plan hv_merge_halo_plan_device left in the volume: units [first, first + count) of it, device payload,
+// nothing staged, nothing waited for - the caller orders its collective against the volume's stream
+int hv_merge_halo_pack_planned(hv_volume *v, int64_t first, int64_t count, float *d_payload) {
+    HV_REQUIRE(v != nullptr && (count == 0 || d_payload != nullptr), HV_ERR_INVALID, "hv_merge_halo_pack_planned: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_pack_planned: not a TSDF volume");
+    HV_REQUIRE(first >= 0 && count >= 0 && first + count <= v->halo_plan_n, HV_ERR_INVALID, "hv_merge_halo_pack_planned: range outside the plan");
+    if (count == 0) return HV_OK;
+    HV_HIP(hipSetDevice(v->device));
+    const int64_t total = count * HV_TSDF_RRR;
+    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (const char *)v->pool,
+                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload);
+    HV_HIP(hipGetLastError());
+    return HV_OK;
+}
+
+int hv_merge_halo_unpack_planned(hv_volume *v, int64_t first, int64_t count, const float *d_payload) {
+    HV_REQUIRE(v != nullptr && (count == 0 || d_payload != nullptr), HV_ERR_INVALID, "hv_merge_halo_unpack_planned: null argument");
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_unpack_planned: not a TSDF volume");
+    HV_REQUIRE(first >= 0 && count >= 0 && first + count <= v->halo_plan_n, HV_ERR_INVALID, "hv_merge_halo_unpack_planned: range outside the plan");
+    if (count == 0) return HV_OK;
+    v->content_version += 1;
+    v->extract_epoch += 1; // (writes voxels without stamping their units)
+    HV_HIP(hipSetDevice(v->device));
+    const int64_t total = count * HV_TSDF_RRR;
+    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (char *)v->pool,
+                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload,
+                       (const uint8_t *)v->halo_plan + (size_t)v->halo_plan_n * 12 + first);
+    HV_HIP(hipGetLastError());
     return HV_OK;
 }
 

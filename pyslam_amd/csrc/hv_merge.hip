@@ -2,7 +2,7 @@
 //
 // Every destination voxel centre is carried into the source's frame and the source field is sampled there (trilinear where all
 // eight voxels around the point are observed, else the nearest voxel); the sample enters the destination as w_s observations.
-//   candidates  one wave per source unit: the emptiness test of k_prune_scan; a unit that holds a weight names the destination
+//   candidates  one wave per source unit: hv_tsdf_unit_has_weight; a unit that holds a weight names the destination
 //               units its transformed box can reach (at most 3 per axis) into a scratch key set                k_merge_candidates
 //   probe       one workgroup per candidate: does ANY of its voxels have an observed nearest source voxel?  Leaves at the first
 //               plane group that has one; such a unit goes onto the keep list                                  k_merge_probe
@@ -19,10 +19,6 @@
 #include "hv_tsdf_sample.h"
 
 namespace {
-
-constexpr int R = HV_TSDF_R;
-constexpr int PLANE_BYTES = HV_TSDF_PLANE_BYTES;
-constexpr int UNIT_BYTES = HV_TSDF_UNIT_BYTES;
 
 enum { HV_MERGE_N_SOURCE = 0, HV_MERGE_N_CAND = 1, HV_MERGE_N_KEEP = 2, HV_MERGE_TRILINEAR = 3, HV_MERGE_NEAREST = 4, HV_MERGE_SET_FULL = 5,
        HV_MERGE_WORDS = 8 };
@@ -74,11 +70,11 @@ __device__ __forceinline__ int32_t hv_merge_unit(const HvMergeSrc &S, int32_t ux
 // pool index and word of source voxel (vx, vy, vz); idx < 0: no such unit
 __device__ __forceinline__ void hv_merge_voxel(const HvMergeSrc &S, int32_t vx, int32_t vy, int32_t vz, int32_t &idx, int &word) {
     idx = hv_merge_unit(S, vx >> 4, vy >> 4, vz >> 4);
-    word = hv_tsdf_word(vx & (R - 1), vy & (R - 1), vz & (R - 1));
+    word = hv_tsdf_word(vx & (HV_TSDF_R - 1), vy & (HV_TSDF_R - 1), vz & (HV_TSDF_R - 1));
 }
 
 __device__ __forceinline__ uint32_t hv_merge_weight(const HvMergeSrc &S, int32_t idx, int word) {
-    return idx < 0 ? 0u : ((const uint32_t *)(S.pool + (int64_t)idx * UNIT_BYTES + PLANE_BYTES))[word];
+    return idx < 0 ? 0u : ((const uint32_t *)(S.pool + (int64_t)idx * HV_TSDF_UNIT_BYTES + HV_TSDF_PLANE_BYTES))[word];
 }
 
 // weight of the nearest source voxel (0: unobserved); its pool index and word
@@ -96,7 +92,7 @@ __device__ __forceinline__ void hv_merge_resolve(const HvMergeXf &X, const HvTab
     if (t < 8) { // the eight corner voxels: g is affine in the voxel index, its minimum is at a corner
         int32_t g0[3];
         double r[3];
-        const bool ok = hv_merge_locate(X, kx * R + ((t & 1) ? R - 1 : 0), ky * R + ((t & 2) ? R - 1 : 0), kz * R + ((t & 4) ? R - 1 : 0), g0, r);
+        const bool ok = hv_merge_locate(X, kx * HV_TSDF_R + ((t & 1) ? HV_TSDF_R - 1 : 0), ky * HV_TSDF_R + ((t & 2) ? HV_TSDF_R - 1 : 0), kz * HV_TSDF_R + ((t & 4) ? HV_TSDF_R - 1 : 0), g0, r);
         if (ok)
             for (int a = 0; a < 3; ++a) atomicMin(&s_base[a], g0[a] >> 4);
     }
@@ -114,13 +110,7 @@ __device__ __forceinline__ void hv_merge_resolve(const HvMergeXf &X, const HvTab
     __syncthreads();
 }
 
-__device__ __forceinline__ int hv_wave_sum_i32(int v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// One wave per source unit.  Emptiness as k_prune_scan (the weight plane in 1 KiB steps, four in flight, out at the first weight).
+// One wave per source unit.  Emptiness: hv_tsdf_unit_has_weight.
 // A unit with a weight: the eight corners of its box [k L, (k + 1) L) go to the destination frame; every destination unit with a
 // voxel centre inside their bounding box (padded by 1e-3 voxel against the rounding of the per-voxel arithmetic) is a candidate.
 // A destination voxel whose nearest source voxel lies in this unit has its centre's pre-image inside the box, so no unit is missed.
@@ -130,18 +120,11 @@ __global__ __launch_bounds__(256) void k_merge_candidates(const unsigned long lo
     const int32_t unit = (int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6); // wave-uniform
     if (unit >= used) return;
     const int lane = hv_lane_id();
-    const uint4 *w = (const uint4 *)(src_pool + (size_t)unit * UNIT_BYTES + PLANE_BYTES);
-    bool seen = false;
-    for (int k = 0; k < PLANE_BYTES / 1024 && !seen; k += 4) {
-        const uint4 a = w[(k + 0) * 64 + lane], b = w[(k + 1) * 64 + lane], c = w[(k + 2) * 64 + lane], d = w[(k + 3) * 64 + lane];
-        const uint32_t any = a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w;
-        seen = __ballot(any != 0) != 0ull;
-    }
-    if (!seen) return;
+    if (!hv_tsdf_unit_has_weight(src_pool, unit, lane)) return;
     if (lane == 0) atomicAdd(&cnt[HV_MERGE_N_SOURCE], 1);
     int32_t kx, ky, kz;
     hv_unpack_key(src_keys[unit], kx, ky, kz);
-    const double L = X.voxel_length * (double)R;
+    const double L = X.voxel_length * (double)HV_TSDF_R;
     double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -159,7 +142,7 @@ __global__ __launch_bounds__(256) void k_merge_candidates(const unsigned long lo
     for (int a = 0; a < 3; ++a) {
         const double glo = lo[a] / X.voxel_length - 0.5 - 1.0e-3, ghi = hi[a] / X.voxel_length - 0.5 + 1.0e-3;
         ok = ok && fabs(glo) < 1.0e9 && fabs(ghi) < 1.0e9;
-        const double a0 = floor(ceil(glo) / (double)R), a1 = floor(floor(ghi) / (double)R); // units of the first / last voxel centre inside
+        const double a0 = floor(ceil(glo) / (double)HV_TSDF_R), a1 = floor(floor(ghi) / (double)HV_TSDF_R); // units of the first / last voxel centre inside
         ulo[a] = ok ? (int32_t)a0 : 0;
         n[a] = ok ? (int32_t)(a1 - a0) + 1 : 0; // <= 3: the box spans 16 sqrt(3) + 0.002 < 32 voxels
     }
@@ -169,22 +152,13 @@ __global__ __launch_bounds__(256) void k_merge_candidates(const unsigned long lo
     const int32_t ux = ulo[0] + i, uy = ulo[1] + j, uz = ulo[2] + k;
     if (!hv_key_in_range(ux, uy, uz)) return;
     const unsigned long long key = hv_pack_key(ux, uy, uz);
-    uint32_t s = hv_slot_hash(key) & set_mask;
-    for (uint32_t probe = 0; probe <= set_mask; ++probe) {
-        unsigned long long cur = set[s];
-        if (cur == key) return;
-        if (cur == HV_EMPTY_KEY) {
-            cur = atomicCAS(&set[s], HV_EMPTY_KEY, key);
-            if (cur == HV_EMPTY_KEY) {
-                const int32_t at = atomicAdd(&cnt[HV_MERGE_N_CAND], 1);
-                if (at < cand_cap) cand[at] = key;
-                return;
-            }
-            if (cur == key) return;
-        }
-        s = (s + 1) & set_mask;
+    bool is_new;
+    if (hv_keyset_insert(set, set_mask, key, &is_new) < 0) {
+        atomicAdd(&cnt[HV_MERGE_SET_FULL], 1);
+    } else if (is_new) {
+        const int32_t at = atomicAdd(&cnt[HV_MERGE_N_CAND], 1);
+        if (at < cand_cap) cand[at] = key;
     }
-    atomicAdd(&cnt[HV_MERGE_SET_FULL], 1);
 }
 
 // One workgroup per candidate: a wave per z plane, lane -> (x, 4 y's); the workgroup leaves after the first group of four planes
@@ -200,7 +174,7 @@ __global__ __launch_bounds__(256) void k_merge_probe(const unsigned long long *_
     const HvMergeSrc S{s_tab, s_base[0], s_base[1], s_base[2], &src, src_pool};
     const int lane = hv_lane_id(), wave = (int)(threadIdx.x >> 6);
     const int x = lane >> 2, y0 = (lane & 3) * 4;
-    for (int zb = 0; zb < R; zb += 4) {
+    for (int zb = 0; zb < HV_TSDF_R; zb += 4) {
         const int z = zb + wave;
         int hit = 0;
 #pragma unroll
@@ -208,7 +182,7 @@ __global__ __launch_bounds__(256) void k_merge_probe(const unsigned long long *_
             int32_t g0[3], idx;
             double r[3];
             int word;
-            if (hv_merge_locate(X, kx * R + x, ky * R + y0 + q, kz * R + z, g0, r)) hit |= hv_merge_nearest(S, g0, r, idx, word) != 0u;
+            if (hv_merge_locate(X, kx * HV_TSDF_R + x, ky * HV_TSDF_R + y0 + q, kz * HV_TSDF_R + z, g0, r)) hit |= hv_merge_nearest(S, g0, r, idx, word) != 0u;
         }
         if (__syncthreads_or(hit)) {
             if (threadIdx.x == 0) keep[atomicAdd(&cnt[HV_MERGE_N_KEEP], 1)] = key;
@@ -248,12 +222,12 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
     }
     hv_merge_resolve(X, src, kx, ky, kz, s_tab, s_base); // (its barriers publish s_unit)
     if (s_unit < 0) return;                              // (claimed without a block: the host has refused the call already)
-    char *unit = dst_pool + (int64_t)s_unit * UNIT_BYTES;
+    char *unit = dst_pool + (int64_t)s_unit * HV_TSDF_UNIT_BYTES;
     const HvMergeSrc S{s_tab, s_base[0], s_base[1], s_base[2], &src, src_pool};
     const int lane = hv_lane_id(), wave = (int)(threadIdx.x >> 6);
     const int x = lane >> 2, y0 = (lane & 3) * 4;
     int n_tri = 0, n_near = 0;
-    for (int z = wave; z < R; z += 4) {
+    for (int z = wave; z < HV_TSDF_R; z += 4) {
         uint32_t ws[4];     // the sample's weight (0: the voxel is not touched)
         double ts[4];       // tsdf_s
         uint32_t gain[4][3];
@@ -265,7 +239,7 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
             int32_t g0[3], nidx;
             double r[3];
             int nword;
-            if (!hv_merge_locate(X, kx * R + x, ky * R + y0 + q, kz * R + z, g0, r)) continue;
+            if (!hv_merge_locate(X, kx * HV_TSDF_R + x, ky * HV_TSDF_R + y0 + q, kz * HV_TSDF_R + z, g0, r)) continue;
             const uint32_t wn = hv_merge_nearest(S, g0, r, nidx, nword);
             if (wn == 0u) continue;
             int32_t cidx[8];
@@ -283,21 +257,21 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
             if (all) {
                 double f[8];
 #pragma unroll
-                for (int i = 0; i < 8; ++i) f[i] = (double)((const float *)(src_pool + (int64_t)cidx[i] * UNIT_BYTES))[cword[i]];
+                for (int i = 0; i < 8; ++i) f[i] = (double)((const float *)(src_pool + (int64_t)cidx[i] * HV_TSDF_UNIT_BYTES))[cword[i]];
                 ts[q] = hv_merge_lerp(r, f);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
-                        f[i] = (double)((const uint32_t *)(src_pool + (int64_t)cidx[i] * UNIT_BYTES + (2 + c) * PLANE_BYTES))[cword[i]] / (double)cw[i];
+                        f[i] = (double)((const uint32_t *)(src_pool + (int64_t)cidx[i] * HV_TSDF_UNIT_BYTES + (2 + c) * HV_TSDF_PLANE_BYTES))[cword[i]] / (double)cw[i];
                     mean[c] = hv_merge_lerp(r, f);
                 }
                 n_tri += 1;
             } else {
-                const char *u = src_pool + (int64_t)nidx * UNIT_BYTES;
+                const char *u = src_pool + (int64_t)nidx * HV_TSDF_UNIT_BYTES;
                 ts[q] = (double)((const float *)u)[nword];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) mean[c] = (double)((const uint32_t *)(u + (2 + c) * PLANE_BYTES))[nword] / (double)wn;
+                for (int c = 0; c < 3; ++c) mean[c] = (double)((const uint32_t *)(u + (2 + c) * HV_TSDF_PLANE_BYTES))[nword] / (double)wn;
                 n_near += 1;
             }
             ws[q] = wn;
@@ -305,12 +279,12 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
             for (int c = 0; c < 3; ++c) gain[q][c] = (uint32_t)floor(mean[c] * (double)wn + 0.5);
         }
         if ((ws[0] | ws[1] | ws[2] | ws[3]) == 0u) continue;
-        const int v4 = (z * R * R + x * R + y0) >> 2;
+        const int v4 = hv_tsdf_word(x, y0, z) >> 2;
         float4 vt = ((const float4 *)unit)[v4];
-        uint4 vw = ((const uint4 *)(unit + PLANE_BYTES))[v4];
-        uint4 vr = ((const uint4 *)(unit + 2 * PLANE_BYTES))[v4];
-        uint4 vg = ((const uint4 *)(unit + 3 * PLANE_BYTES))[v4];
-        uint4 vb = ((const uint4 *)(unit + 4 * PLANE_BYTES))[v4];
+        uint4 vw = ((const uint4 *)(unit + HV_TSDF_PLANE_BYTES))[v4];
+        uint4 vr = ((const uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[v4];
+        uint4 vg = ((const uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[v4];
+        uint4 vb = ((const uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[v4];
 #define HV_MERGE_APPLY(q, m)                                                                                                         \
     if (ws[q] != 0u) {                                                                                                               \
         const uint32_t w1 = vw.m + ws[q];                                                                                            \
@@ -326,13 +300,13 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
         HV_MERGE_APPLY(3, w)
 #undef HV_MERGE_APPLY
         ((float4 *)unit)[v4] = vt;
-        ((uint4 *)(unit + PLANE_BYTES))[v4] = vw;
-        ((uint4 *)(unit + 2 * PLANE_BYTES))[v4] = vr;
-        ((uint4 *)(unit + 3 * PLANE_BYTES))[v4] = vg;
-        ((uint4 *)(unit + 4 * PLANE_BYTES))[v4] = vb;
+        ((uint4 *)(unit + HV_TSDF_PLANE_BYTES))[v4] = vw;
+        ((uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[v4] = vr;
+        ((uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[v4] = vg;
+        ((uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[v4] = vb;
     }
-    n_tri = hv_wave_sum_i32(n_tri);
-    n_near = hv_wave_sum_i32(n_near);
+    n_tri = hv_wave_sum(n_tri);
+    n_near = hv_wave_sum(n_near);
     if (lane == 0) {
         if (n_tri) atomicAdd(&cnt64[0], (unsigned long long)n_tri);
         if (n_near) atomicAdd(&cnt64[1], (unsigned long long)n_near);

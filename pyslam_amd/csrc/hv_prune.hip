@@ -16,10 +16,7 @@
 
 namespace {
 
-constexpr int R = 16;
-constexpr int PLANE_BYTES = R * R * R * 4;
-constexpr int UNIT_BYTES = PLANE_BYTES * HV_TSDF_PLANES;
-constexpr int UNIT_VEC = UNIT_BYTES / 16; // 16-byte words of a unit
+constexpr int UNIT_VEC = HV_TSDF_UNIT_BYTES / 16; // 16-byte words of a unit
 static_assert(UNIT_VEC % (256 * 5) == 0, "k_prune_move copies a unit in rounds of 5 x 256 16-byte words");
 
 enum : uint8_t { HV_PRUNE_KEEP = 0, HV_PRUNE_OUTSIDE = 1, HV_PRUNE_EMPTY = 2 };
@@ -31,10 +28,8 @@ struct HvPruneBox {
     int32_t release_empty;
 };
 
-// One wave per unit.  The box test is arithmetic on the key; a unit it releases is not read.  The emptiness test streams the weight
-// plane (plane 1, 16 KiB): a lane loads 16 bytes, so one instruction of the wave covers 1 KiB; four of them are in flight per step
-// (one load at a time would wait out the memory latency sixteen times per empty unit) and the wave leaves the unit at the first
-// step that saw a weight.
+// One wave per unit.  The box test is arithmetic on the key; a unit it releases is not read.  The emptiness test is
+// hv_tsdf_unit_has_weight.
 __global__ __launch_bounds__(256) void k_prune_scan(const unsigned long long *__restrict__ block_keys, const char *__restrict__ pool, int32_t used,
                                                     HvPruneBox box, uint8_t *__restrict__ flags) {
     const int32_t unit = (int32_t)blockIdx.x * 4 + (int32_t)(threadIdx.x >> 6); // wave-uniform
@@ -47,14 +42,7 @@ __global__ __launch_bounds__(256) void k_prune_scan(const unsigned long long *__
         if (x < box.lo[0] || x > box.hi[0] || y < box.lo[1] || y > box.hi[1] || z < box.lo[2] || z > box.hi[2]) f = HV_PRUNE_OUTSIDE;
     }
     if (f == HV_PRUNE_KEEP && box.release_empty) {
-        const uint4 *w = (const uint4 *)(pool + (size_t)unit * UNIT_BYTES + PLANE_BYTES);
-        bool seen = false;
-        for (int k = 0; k < PLANE_BYTES / 1024 && !seen; k += 4) {
-            const uint4 a = w[(k + 0) * 64 + lane], b = w[(k + 1) * 64 + lane], c = w[(k + 2) * 64 + lane], d = w[(k + 3) * 64 + lane];
-            const uint32_t any = a.x | a.y | a.z | a.w | b.x | b.y | b.z | b.w | c.x | c.y | c.z | c.w | d.x | d.y | d.z | d.w;
-            seen = __ballot(any != 0) != 0ull;
-        }
-        if (!seen) f = HV_PRUNE_EMPTY;
+        if (!hv_tsdf_unit_has_weight(pool, unit, lane)) f = HV_PRUNE_EMPTY;
     }
     if (lane == 0) flags[unit] = f;
 }
@@ -114,8 +102,8 @@ __global__ __launch_bounds__(1024) void k_prune_plan(const uint8_t *__restrict__
 __global__ __launch_bounds__(256) void k_prune_move(char *__restrict__ pool, unsigned long long *__restrict__ block_keys,
                                                     const int32_t *__restrict__ move_src, const int32_t *__restrict__ move_dst) {
     const int32_t from = move_src[blockIdx.x], to = move_dst[blockIdx.x];
-    const uint4 *s = (const uint4 *)(pool + (size_t)from * UNIT_BYTES);
-    uint4 *d = (uint4 *)(pool + (size_t)to * UNIT_BYTES);
+    const uint4 *s = (const uint4 *)(pool + (size_t)from * HV_TSDF_UNIT_BYTES);
+    uint4 *d = (uint4 *)(pool + (size_t)to * HV_TSDF_UNIT_BYTES);
     const int t = (int)threadIdx.x;
     for (int base = 0; base < UNIT_VEC; base += 256 * 5) {
         uint4 x[5];
@@ -203,7 +191,7 @@ extern "C" int hv_tsdf_prune(hv_volume *v, int32_t release_empty, const int32_t 
         e = hipGetLastError();
     }
     if (e == hipSuccess && released > 0)
-        e = hipMemsetAsync((char *)v->pool + (size_t)kept * UNIT_BYTES, 0, (size_t)released * UNIT_BYTES, v->stream);
+        e = hipMemsetAsync((char *)v->pool + (size_t)kept * HV_TSDF_UNIT_BYTES, 0, (size_t)released * HV_TSDF_UNIT_BYTES, v->stream);
     // pool slots moved: the per-unit extraction caches (hv_rekey_in_place bumps extract_epoch), cached extraction results and a stored
     // halo plan describe a volume that no longer exists
     v->content_version += 1;

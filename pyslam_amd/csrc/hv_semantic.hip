@@ -349,8 +349,7 @@ __device__ __forceinline__ void semb_sort_window(uint32_t *s_src, uint32_t *s_ds
         const uint32_t up = __shfl_up(incl, o);
         if (lane >= o) incl += up;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) longest = max(longest, (uint32_t)__shfl_xor((int)longest, o));
+    longest = hv_wave_max(longest);
     if (longest > 48u) { // long runs: the rank pass below is quadratic in the run length
         int m2 = HV_WAVE;
         while (m2 < m) m2 <<= 1;

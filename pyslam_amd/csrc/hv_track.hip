@@ -149,11 +149,6 @@ __global__ __launch_bounds__(256) void k_track_model_prep(const float *__restric
     rec[i] = o;
 }
 
-__device__ __forceinline__ double tk_wave_sum(double x) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64); // butterfly: every lane ends with the same value
-    return x;
-}
 
 // one step's linearisation: per workgroup the NACC sums of its pixels -> slab[blockIdx.x].  NACC = 30 is the depth-only call (C is
 // not read); NACC = 32 the hybrid one: for an inlier whose model pixel has a gradient also the photometric products into the same
@@ -237,7 +232,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_track_linearise(TkLevel L, TkParam
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NACC; ++k) {
-        const double s = tk_wave_sum(acc[k]);
+        const double s = hv_wave_sum(acc[k]);
         if (lane == 0) red[wave][k] = s;
     }
     __syncthreads();

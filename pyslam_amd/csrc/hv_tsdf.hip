@@ -18,9 +18,10 @@
 //   HBM-bound: algorithmic bytes per touched unit = 4096 voxels * 20 B read (+ 20 B per updated
 //   voxel written); no reuse of voxel data within a frame.  Frame gathers are served by L1/L2 (a
 //   640x480 frame = 2.4 MB packed, resident in every XCD's 4 MiB L2).
-// Multi-frame sweep (hv_tsdf_integrate_batch): k_tsdf_prep_touch_batch + k_tsdf_integrate_batch further
-// down — unit slabs are reused in registers across up to 64 frames.
-// Multi-GPU hooks: image-tile restriction (hv_tsdf_set_tile) and unit ownership (hv_tsdf_set_owner).
+// Multi-frame sweep (hv_tsdf_integrate_batch): k_tsdf_prep_touch_batch + k_tsdf_sweep_column (or k_tsdf_sweep, the bitwise form)
+// further down — a unit's voxels stay in registers across up to 64 frames.
+// Multi-GPU hooks: image-tile restriction (hv_tsdf_set_tile) and unit ownership (hv_tsdf_set_owner); the exchange of units between
+// GPUs (numerators export / import, halo merge) is hv_halo.hip.
 #include <algorithm>
 #include <array>
 #include <cmath>
@@ -181,12 +182,12 @@ __device__ __forceinline__ void hv_tsdf_slabs(const HvFrameParams &P, const uint
 #pragma unroll
     for (int zz = 0; zz < ZB; ++zz) {
         if ((mask >> (zz * 4)) & 15u) {
-            const int q = (wordb + zz * RR) >> 2;
-            vt[zz] = ((const float4 *)(unit + 0 * PLANE_BYTES))[q];
-            vw[zz] = ((const uint4 *)(unit + 1 * PLANE_BYTES))[q];
-            vr[zz] = ((const uint4 *)(unit + 2 * PLANE_BYTES))[q];
-            vg[zz] = ((const uint4 *)(unit + 3 * PLANE_BYTES))[q];
-            vb[zz] = ((const uint4 *)(unit + 4 * PLANE_BYTES))[q];
+            const int q = (wordb + zz * HV_TSDF_RR) >> 2;
+            vt[zz] = ((const float4 *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+            vw[zz] = ((const uint4 *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
+            vr[zz] = ((const uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q];
+            vg[zz] = ((const uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q];
+            vb[zz] = ((const uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q];
         }
     }
 #pragma unroll
@@ -197,12 +198,12 @@ __device__ __forceinline__ void hv_tsdf_slabs(const HvFrameParams &P, const uint
             hv_tsdf_apply(m & 2u, tv[zz][1], cv[zz][1], vt[zz].y, vw[zz].y, vr[zz].y, vg[zz].y, vb[zz].y);
             hv_tsdf_apply(m & 4u, tv[zz][2], cv[zz][2], vt[zz].z, vw[zz].z, vr[zz].z, vg[zz].z, vb[zz].z);
             hv_tsdf_apply(m & 8u, tv[zz][3], cv[zz][3], vt[zz].w, vw[zz].w, vr[zz].w, vg[zz].w, vb[zz].w);
-            const int q = (wordb + zz * RR) >> 2;
-            ((float4 *)(unit + 0 * PLANE_BYTES))[q] = vt[zz];
-            ((uint4 *)(unit + 1 * PLANE_BYTES))[q] = vw[zz];
-            ((uint4 *)(unit + 2 * PLANE_BYTES))[q] = vr[zz];
-            ((uint4 *)(unit + 3 * PLANE_BYTES))[q] = vg[zz];
-            ((uint4 *)(unit + 4 * PLANE_BYTES))[q] = vb[zz];
+            const int q = (wordb + zz * HV_TSDF_RR) >> 2;
+            ((float4 *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = vt[zz];
+            ((uint4 *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = vw[zz];
+            ((uint4 *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] = vr[zz];
+            ((uint4 *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] = vg[zz];
+            ((uint4 *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] = vb[zz];
         }
     }
 }
@@ -258,12 +259,12 @@ __global__ __launch_bounds__(256) void k_tsdf_integrate(HvTable table, const int
                 pc[c][2] += inc2;
             }
         }
-        char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
+        char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
         // 2 z-slabs evaluated per batch: (107 VGPRs, 4 waves/SIMD) measured 7269 frames/s vs 6342 for 4
         // (180 VGPRs, 2 waves/SIMD) on the headline config
         constexpr int ZB = 2;
 #pragma unroll
-        for (int zb = 0; zb < 4; zb += ZB) hv_tsdf_slabs<ZB>(P, frame_px, unit, (z0 + zb) * RR + x * R + y0, pc, inc0, inc1, inc2);
+        for (int zb = 0; zb < 4; zb += ZB) hv_tsdf_slabs<ZB>(P, frame_px, unit, hv_tsdf_word(x, y0, z0 + zb), pc, inc0, inc1, inc2);
     }
 }
 
@@ -385,21 +386,46 @@ __device__ __forceinline__ HvSweepFrameK hv_sweep_frame_k(const HvFrameParams *_
     return HvSweepFrameK{hv_f2{k[0], k[1]}, hv_f2{k[2], k[3]}, hv_f2{k[4], k[5]}, hv_f2{k[6], k[7]}, k[8], k[9], hv_f2{k[10], k[11]}, hv_f2{k[12], k[13]}, k[14]};
 }
 
-template <int ZH>
+// Work items -> workgroups, for both sweep kernels.  A unit is `parts` work items (one workgroup each).  Workgroup b runs on XCD
+// b % 8 and every XCD has its own L2; the union list is in touch order, i.e. roughly in image raster order of the first frames.  The
+// parts of a unit (which read the same depth pixels in every frame) and G consecutive list entries stay on one XCD: item i -> XCD
+// i & 7, and within that XCD entries (8 g + xcd) G .. + G - 1 of the list for g = 0, 1, ... - the XCD's L2 holds one band of the
+// frame records instead of every XCD pulling every frame whole (profiles/r02/baseline: 2.0x the algorithmic traffic).  G small
+// enough that a heavy stretch of the list is spread over all XCDs: G = 2 measured best, +2.5 %, FETCH_SIZE halves; one contiguous
+// eighth of the list per XCD halves the traffic too but is 28 % slower, the dispatcher waits for the heaviest XCD.
+// hv_sweep_items: the number of work items (the list is run in whole rounds of 8 G entries); hv_sweep_item: item -> list entry t
+// and part of it.  t >= n_units: a padding item of the last round, nothing to run.
+static constexpr unsigned HV_SWEEP_XCD_GROUP = 2; // G
+__device__ __forceinline__ int hv_sweep_items(const int n_units, const int parts) {
+    constexpr int G = HV_SWEEP_XCD_GROUP;
+    return (n_units + 8 * G - 1) / (8 * G) * 8 * G * parts;
+}
+__device__ __forceinline__ void hv_sweep_item(const unsigned item, const unsigned parts, int &t, int &part) {
+    constexpr unsigned G = HV_SWEEP_XCD_GROUP; // (unsigned throughout: G and parts are powers of two, the mapping is shifts and masks)
+    const unsigned xcd = item & 7u, j = item >> 3;
+    const unsigned g = j / (G * parts), within = j % (G * parts);
+    t = (int)((g * 8 + xcd) * G + within / parts);
+    part = (int)(within % parts);
+}
+
+// the bitwise form's shape: a lane owns ZH voxels along z, a wave 64 columns x ZH z = one of a unit's 64 / ZH tasks
+static constexpr int HV_SWEEP_ZH = 4;
+static constexpr int HV_SWEEP_SPLIT = 8; // workgroups per unit
+static constexpr int HV_SWEEP_WAVES = 64 / HV_SWEEP_ZH / HV_SWEEP_SPLIT; // waves per workgroup
+static constexpr int HV_SWEEP_WPE = 4;   // waves per SIMD the kernel is compiled for
+static_assert(HV_SWEEP_ZH % 2 == 0, "voxels are folded in pairs");
+
 struct HvSweepGather { // what a frame's evaluation leaves for its fold: the gathered records, multipliers, depths along z, tests
-    uint2 rec[ZH];
-    float mm[ZH], zk[ZH];
-    bool ok[ZH];
+    uint2 rec[HV_SWEEP_ZH];
+    float mm[HV_SWEEP_ZH], zk[HV_SWEEP_ZH];
+    bool ok[HV_SWEEP_ZH];
 };
 
-template <int ZH, int SPLIT, int WPE>
-__global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
+__global__ __launch_bounds__(64 * HV_SWEEP_WAVES, HV_SWEEP_WPE) void k_tsdf_sweep(
     HvTable table, const int32_t *__restrict__ list, const unsigned long long *__restrict__ frame_mask,
     char *__restrict__ pool, const uint2 *__restrict__ frame_px, const HvFrameParams *__restrict__ Ps, int n_frames,
-    int general, const float *__restrict__ mult, int xcd_aware, int parity) {
-    static_assert(ZH % 2 == 0, "voxels are folded in pairs");
-    constexpr int TASKS = 64 / ZH;          // wave tasks per unit
-    constexpr int WAVES = TASKS / SPLIT;    // waves per workgroup
+    int general, const float *__restrict__ mult, int parity) {
+    constexpr int ZH = HV_SWEEP_ZH, SPLIT = HV_SWEEP_SPLIT, WAVES = HV_SWEEP_WAVES;
     int n_units = table.counters[HV_CNT_TOUCH(parity)];
     if (n_units > table.max_blocks) n_units = table.max_blocks;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -416,30 +442,11 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
     const uint32_t W24 = (uint32_t)P0.W;
     const float ntrunc = -P0.sdf_trunc_f, tinv = P0.sdf_trunc_inv_f;
     const __amdgpu_buffer_rsrc_t rs_m = __builtin_amdgcn_make_buffer_rsrc((void *)mult, 0, npx * 4, 0x00020000);
-    // XCD-aware work distribution (workgroup b runs on XCD b % 8; each XCD has its own L2): the union list is in touch order,
-    // i.e. roughly in image raster order of the first frames, so XCD k takes the k-th CONTIGUOUS eighth of the list, all SPLIT
-    // parts of a unit included - its units project into one band of the images and its L2 only has to hold that band of the
-    // frame records, instead of every XCD pulling every frame whole (profiles/r02/baseline: 2.0x the algorithmic traffic).
-    // Work items -> workgroups.  Workgroup b runs on XCD b % 8 and every XCD has its own L2, so with xcd_group = G > 0 the
-    // SPLIT parts of a unit (which read the same depth pixels in every frame) and G consecutive list entries stay on one
-    // XCD: item i -> XCD i & 7, and within that XCD entries (8 g + xcd) G .. + G - 1 of the list for g = 0, 1, ...
-    // (G small enough that a heavy stretch of the list is spread over all XCDs: G = 2 measured best, +2.5 %, FETCH_SIZE halves;
-    // one contiguous eighth of the list per XCD halves the traffic too but is 28 % slower, the dispatcher waits for the heaviest XCD).
-    const int G = xcd_aware > 0 ? xcd_aware : 1;
-    const int rounds = (n_units + 8 * G - 1) / (8 * G);
-    const int n_items = xcd_aware > 0 ? rounds * 8 * G * SPLIT : n_units * SPLIT;
+    const int n_items = hv_sweep_items(n_units, SPLIT);
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         int t, part;
-        if (xcd_aware > 0) {
-            const int xcd = item & 7, j = item >> 3;
-            const int g = j / (G * SPLIT), within = j - g * (G * SPLIT);
-            t = (g * 8 + xcd) * G + within / SPLIT;
-            part = within % SPLIT;
-            if (t >= n_units) continue;
-        } else {
-            t = item / SPLIT;
-            part = item % SPLIT;
-        }
+        hv_sweep_item(item, SPLIT, t, part);
+        if (t >= n_units) continue;
         const int task = part * WAVES + wave;
         const int cg = task & 3;            // column group: x in [4 cg, 4 cg + 4)
         const int z0 = (task >> 2) * ZH;
@@ -465,15 +472,15 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
             near = !(zmin > 0.03f);
         }
         const bool near_any = __any(near);
-        char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
-        const int wordb = z0 * RR + cg * 64 + lane;
+        char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+        const int wordb = z0 * HV_TSDF_RR + cg * 64 + lane;
         float vt[ZH];
         uint32_t vw[ZH];
 #pragma unroll
         for (int zz = 0; zz < ZH; ++zz) {
-            const int q = wordb + zz * RR;
-            vt[zz] = ((const float *)(unit + 0 * PLANE_BYTES))[q];
-            vw[zz] = ((const uint32_t *)(unit + 1 * PLANE_BYTES))[q];
+            const int q = wordb + zz * HV_TSDF_RR;
+            vt[zz] = ((const float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+            vw[zz] = ((const uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
         }
         // the voxel centre of (x, y, z = 0) does not depend on the frame
         const float p0 = (float)((double)(hl + vl * (float)x) + o0);
@@ -488,10 +495,10 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
             uint32_t vr[ZH], vg[ZH], vb[ZH];
 #pragma unroll
             for (int zz = 0; zz < ZH; ++zz) {
-                const int q = wordb + zz * RR;
-                vr[zz] = ((const uint32_t *)(unit + 2 * PLANE_BYTES))[q];
-                vg[zz] = ((const uint32_t *)(unit + 3 * PLANE_BYTES))[q];
-                vb[zz] = ((const uint32_t *)(unit + 4 * PLANE_BYTES))[q];
+                const int q = wordb + zz * HV_TSDF_RR;
+                vr[zz] = ((const uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q];
+                vg[zz] = ((const uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q];
+                vb[zz] = ((const uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q];
             }
             while (mask) {
                 const int f = __ffsll((long long)mask) - 1;
@@ -522,12 +529,12 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
 #pragma unroll
             for (int zz = 0; zz < ZH; ++zz) {
                 if (dirty & (1u << zz)) {
-                    const int q = wordb + zz * RR;
-                    ((float *)(unit + 0 * PLANE_BYTES))[q] = vt[zz];
-                    ((uint32_t *)(unit + 1 * PLANE_BYTES))[q] = vw[zz];
-                    ((uint32_t *)(unit + 2 * PLANE_BYTES))[q] = vr[zz];
-                    ((uint32_t *)(unit + 3 * PLANE_BYTES))[q] = vg[zz];
-                    ((uint32_t *)(unit + 4 * PLANE_BYTES))[q] = vb[zz];
+                    const int q = wordb + zz * HV_TSDF_RR;
+                    ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = vt[zz];
+                    ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = vw[zz];
+                    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] = vr[zz];
+                    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] = vg[zz];
+                    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] = vb[zz];
                 }
             }
             continue;
@@ -542,7 +549,7 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
         }
         // One frame folded into the registers; K = the frame's 16 constant dwords, already in scalar registers.
         auto project_frame = [&](const HvSweepFrameK K, const int f, HvSweepFrameK &Knext, const unsigned long long rest,
-                                 HvSweepGather<ZH> &g) __attribute__((always_inline)) {
+                                 HvSweepGather &g) __attribute__((always_inline)) {
             const __amdgpu_buffer_rsrc_t rs_px = __builtin_amdgcn_make_buffer_rsrc((void *)(frame_px + (int64_t)f * npx), 0, npx * 8, 0x00020000);
             const hv_f2 INC = K.i01;
             const float inc2 = K.i2;
@@ -588,7 +595,7 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
             }
         };
         // ---- fold of an evaluated frame, two voxels at a time ----
-        auto apply_frame = [&](const HvSweepGather<ZH> &g) __attribute__((always_inline)) {
+        auto apply_frame = [&](const HvSweepGather &g) __attribute__((always_inline)) {
 #pragma unroll
             for (int zp = 0; zp < ZH / 2; ++zp) {
                 const int k0 = 2 * zp, k1 = 2 * zp + 1;
@@ -623,7 +630,7 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
         HvSweepFrameK ka = hv_sweep_frame_k(Ps, __ffsll((long long)mask) - 1), kb = ka;
         // (Measured dead end: issuing frame n+1's evaluation - projection + gathers - BEFORE folding frame n, two gather sets
         // in flight at 126 VGPRs: 32.0 k frames/s against 32.7 k.  The wave does not wait for its gathers.)
-        HvSweepGather<ZH> g;
+        HvSweepGather g;
         while (true) {
             const int fa = __ffsll((long long)mask) - 1;
             mask &= mask - 1;
@@ -641,12 +648,12 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
             const float wfz = (zz & 1) ? WF[zz / 2].y : WF[zz / 2].x;
             const uint32_t nw = (uint32_t)wfz;
             if (nw != vw[zz]) { // updated by at least one frame: fold the batch's colour into the planes
-                const int q = wordb + zz * RR;
-                ((float *)(unit + 0 * PLANE_BYTES))[q] = (zz & 1) ? VT[zz / 2].y : VT[zz / 2].x;
-                ((uint32_t *)(unit + 1 * PLANE_BYTES))[q] = nw;
-                ((uint32_t *)(unit + 2 * PLANE_BYTES))[q] += arb[zz] & 0xffffu;
-                ((uint32_t *)(unit + 3 * PLANE_BYTES))[q] += ag[zz] >> 8;
-                ((uint32_t *)(unit + 4 * PLANE_BYTES))[q] += arb[zz] >> 16;
+                const int q = wordb + zz * HV_TSDF_RR;
+                ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = (zz & 1) ? VT[zz / 2].y : VT[zz / 2].x;
+                ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = nw;
+                ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] += arb[zz] & 0xffffu;
+                ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] += ag[zz] >> 8;
+                ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] += arb[zz] >> 16;
             }
         }
     }
@@ -679,33 +686,29 @@ __global__ __launch_bounds__(64 * (64 / ZH) / SPLIT, WPE) void k_tsdf_sweep(
 // r | b << 16, g << 8 | n << 24) + two gather groups: AT the 128 registers of 4 waves per SIMD.
 // (Measured and dropped, rounds 3-5 - profiles/r03 .. r05: gather groups of 1 / 2 / 8 voxels, gathers pipelined across frames, the
 // select form of the accumulation, 1 / 2 workgroups per unit, register caps of 120 / 112 / 5-6 waves per SIMD, 16-byte records.)
-// Correction rounds of the projection's shared-reciprocal division.  hv_div2 (online path, bitwise form) runs two; with the reciprocal
-// refined by one Newton step the FIRST round already returns the correctly rounded quotient on every operand pair tried:
-// tools/divtest.hip, round 4 - 0 mismatches against IEEE division in 3.4e12 pairs each of the kernel's operand ranges, wide random
-// exponents and divisors whose mantissa ends in runs of ones / zeros.  Two packed FMAs less per voxel visit.
-// -DHV_SWEEP_DIV_ROUNDS=2 restores the second round.
-#ifndef HV_SWEEP_DIV_ROUNDS
-#define HV_SWEEP_DIV_ROUNDS 1
-#endif
-// hv_sweep_column_core: the sweep of ONE work item (unit slot, part) as the callable `run_item(slot, part)`, handed to `drive`, which
-// decides what items this workgroup runs (k_tsdf_sweep_column: the grid-stride loop over the batch's union list).  Everything inlines.
-template <int ZS, class Drive>
-__device__ __forceinline__ void hv_sweep_column_core(
-    const HvTable &table, const unsigned long long *__restrict__ frame_mask,
-    char *__restrict__ pool, const uint2 *__restrict__ frame_px, const HvFrameParams *__restrict__ Ps, const int n_frames,
-    const int general, const float *__restrict__ mult, Drive drive) {
-    constexpr int SPLIT = 4;       // workgroups per unit: one wave each
+// Correction rounds of the projection's shared-reciprocal division: hv_div2 (online path, bitwise form) runs two, this kernel ONE.
+// With the reciprocal refined by one Newton step the first round already returns the correctly rounded quotient on every operand
+// pair tried: tools/divtest.hip, round 4 - 0 mismatches against IEEE division in 3.4e12 pairs each of the kernel's operand ranges,
+// wide random exponents and divisors whose mantissa ends in runs of ones / zeros.  Two packed FMAs less per voxel visit.
+// The kernel is a grid-stride loop over the work items of the batch's union list (hv_sweep_item), one wave per workgroup.  ZS = 2 (z
+// halves, 8 one-wave tasks per unit) is the default for a GPU that shares the volume with 3 or more others.
+// ================================================================================================
+template <int ZS>
+__global__ __launch_bounds__(64, 4) void k_tsdf_sweep_column(
+    HvTable table, const int32_t *__restrict__ list, const unsigned long long *__restrict__ frame_mask,
+    char *__restrict__ pool, const uint2 *__restrict__ frame_px, const HvFrameParams *__restrict__ Ps, int n_frames,
+    int general, const float *__restrict__ mult, int parity) {
     constexpr int GV = 4;          // voxels per gather group
-    constexpr bool INTERIOR = true;
     // ZS = 2: a column is split into two z halves = 8 wave tasks per unit (a GPU that owns few units - multi-GPU sharding - has
     // ~3 000 column tasks of very different lengths for 4 096 wave slots: nothing evens them out; twice as many, half as long
     // tasks do).  The upper half replays the reference's 8 repeated float additions along z per frame.
     static_assert(ZS == 1 || ZS == 2, "whole columns or z halves");
     constexpr int ZH = 16 / ZS;
     constexpr int NG = ZH / GV;
-    constexpr int WAVES = 4 / SPLIT; // waves per workgroup
+    constexpr int PARTS = 4 * ZS;  // work items per unit: its 4 column groups x ZS z ranges
     typedef uint32_t hv_u3 __attribute__((ext_vector_type(3)));
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int n_units = table.counters[HV_CNT_TOUCH(parity)];
+    if (n_units > table.max_blocks) n_units = table.max_blocks;
     const int lane = threadIdx.x & 63;
     const HvFrameParams &P0 = Ps[0];
     const float vl = P0.voxel_length_f, hl = P0.half_voxel_length_f;
@@ -719,21 +722,25 @@ __device__ __forceinline__ void hv_sweep_column_core(
     const uint32_t W24 = (uint32_t)P0.W;
     const float ntrunc = -P0.sdf_trunc_f, tinv = P0.sdf_trunc_inv_f;
     const float near_z = fmaxf(0.03f, 1.25f * P0.sdf_trunc_f);
-    auto run_item = [&](const int32_t slot, int part) __attribute__((always_inline)) {
+    const int n_items = hv_sweep_items(n_units, PARTS);
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        int t, part;
+        hv_sweep_item(item, PARTS, t, part);
+        if (t >= n_units) continue;
         const int z0 = ZS == 1 ? 0 : (part >> 2) * ZH; // first z of this task
-        if (ZS == 2) part &= 3;
-        const int cg = part * WAVES + wave; // column group: x in [4 cg, 4 cg + 4)
+        const int32_t slot = list[t];
+        const int cg = part & 3; // column group: x in [4 cg, 4 cg + 4)
         const int x = cg * 4 + (lane >> 4);
         const int y = lane & 15;
         const int32_t idx = table.vals[slot];
         unsigned long long mask = frame_mask[slot];
-        if (idx < 0 || mask == 0ull) return;
+        if (idx < 0 || mask == 0ull) continue;
         int32_t ux, uy, uz;
         hv_unpack_key(table.keys[slot], ux, uy, uz);
         const double o0 = (double)ux * unit_length, o1 = (double)uy * unit_length, o2 = (double)uz * unit_length;
         // lane f <-> frame f: does the box of this wave's voxel centres come within near_z of frame f's camera plane?
         bool near = false;
-        // ... and (round 5, INTERIOR): does the box project at least 2 pixels inside the image (the GPU's tile) in frame f?  Then every voxel
+        // ... and: does the box project at least 2 pixels inside the image (the GPU's tile) in frame f?  Then every voxel
         // of the item does - a perspective projection maps the box into the hull of its projected corners - and the frame's visits skip the
         // image-range test: two v_sub + two v_cmp of ~30 instructions per visit, for ~70 % of the (item, frame) pairs of the bench's stream.
         bool interior = false;
@@ -744,7 +751,7 @@ __device__ __forceinline__ void hv_sweep_column_core(
             const float zmin = (Pl.ext[8] * bx + Pl.ext[9] * by + Pl.ext[10] * bz + Pl.ext[11]) + fminf(Pl.ext[8] * (3.0f * vl), 0.f) +
                                fminf(Pl.ext[9] * (15.0f * vl), 0.f) + fminf(Pl.ext[10] * ((float)(ZH - 1) * vl), 0.f);
             near = !(zmin > near_z);
-            if (INTERIOR && !near) {
+            if (!near) {
                 float umin = 3.0e38f, umax = -3.0e38f, vmin = 3.0e38f, vmax = -3.0e38f;
 #pragma unroll
                 for (int c = 0; c < 8; ++c) {
@@ -759,10 +766,10 @@ __device__ __forceinline__ void hv_sweep_column_core(
                 interior = umin >= lo_uf + 2.0f && umax <= hi_uf - 2.0f && vmin >= lo_vf + 2.0f && vmax <= hi_vf - 2.0f;
             }
         }
-        const unsigned long long interior_mask = INTERIOR ? __ballot(interior) : 0ull;
+        const unsigned long long interior_mask = __ballot(interior);
         const bool near_any = __any(near);
-        char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
-        const int wordb = z0 * RR + cg * 64 + lane;
+        char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+        const int wordb = z0 * HV_TSDF_RR + cg * 64 + lane;
         const float p0 = (float)((double)(hl + vl * (float)x) + o0);
         const float p1 = (float)((double)(hl + vl * (float)y) + o1);
         const float p2 = (float)((double)hl + o2);
@@ -770,12 +777,12 @@ __device__ __forceinline__ void hv_sweep_column_core(
             // rare regime: the reference's evaluation frame by frame with integer weights, one voxel at a time
 #pragma unroll 1
             for (int zz = 0; zz < ZH; ++zz) {
-                const int q = wordb + zz * RR;
-                float vt = ((const float *)(unit + 0 * PLANE_BYTES))[q];
-                uint32_t vw = ((const uint32_t *)(unit + 1 * PLANE_BYTES))[q];
-                uint32_t vr = ((const uint32_t *)(unit + 2 * PLANE_BYTES))[q];
-                uint32_t vg = ((const uint32_t *)(unit + 3 * PLANE_BYTES))[q];
-                uint32_t vb = ((const uint32_t *)(unit + 4 * PLANE_BYTES))[q];
+                const int q = wordb + zz * HV_TSDF_RR;
+                float vt = ((const float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+                uint32_t vw = ((const uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
+                uint32_t vr = ((const uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q];
+                uint32_t vg = ((const uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q];
+                uint32_t vb = ((const uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q];
                 bool dirty = false;
                 unsigned long long m = mask;
 #pragma unroll 1
@@ -801,14 +808,14 @@ __device__ __forceinline__ void hv_sweep_column_core(
                     dirty |= ok;
                 }
                 if (dirty) {
-                    ((float *)(unit + 0 * PLANE_BYTES))[q] = vt;
-                    ((uint32_t *)(unit + 1 * PLANE_BYTES))[q] = vw;
-                    ((uint32_t *)(unit + 2 * PLANE_BYTES))[q] = vr;
-                    ((uint32_t *)(unit + 3 * PLANE_BYTES))[q] = vg;
-                    ((uint32_t *)(unit + 4 * PLANE_BYTES))[q] = vb;
+                    ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = vt;
+                    ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = vw;
+                    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] = vr;
+                    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] = vg;
+                    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] = vb;
                 }
             }
-            return;
+            continue;
         }
         float S[ZH];               // sum of the accepted frames' t
         uint32_t arb[ZH], agn[ZH]; // r | b << 16 and g << 8 | n << 24 of the accepted frames
@@ -847,11 +854,11 @@ __device__ __forceinline__ void hv_sweep_column_core(
             Knext = hv_sweep_frame_k(Ps, rest ? __ffsll((long long)rest) - 1 : f);
             __builtin_amdgcn_sched_barrier(0);
         };
-        bool frame_checked = true; // (wave-uniform) false: the frame is INTERIOR for this item, no voxel can leave the image
+        bool frame_checked = true; // (wave-uniform) false: the frame is interior for this item, no voxel can leave the image
         auto project = [&](Group &g) __attribute__((always_inline)) {
 #pragma unroll
             for (int k = 0; k < GV; ++k) {
-                // (a0, a1) / pc2, correctly rounded, sharing one refined reciprocal (hv_div2's chain on a float2)
+                // (a0, a1) / pc2, correctly rounded, sharing one refined reciprocal (hv_div2's chain on a float2, ONE correction round)
                 float r = __builtin_amdgcn_rcpf(Z);
                 const float e = fmaf(-Z, r, 1.0f);
                 r = fmaf(e, r, r);
@@ -860,16 +867,12 @@ __device__ __forceinline__ void hv_sweep_column_core(
                 hv_f2 Q = A * R;
                 hv_f2 REM = hv_fma2(NZ, Q, A);
                 Q = hv_fma2(REM, R, Q);
-                if (HV_SWEEP_DIV_ROUNDS == 2) { // (hv_div2's second correction round: never needed, see HV_SWEEP_DIV_ROUNDS)
-                    REM = hv_fma2(NZ, Q, A);
-                    Q = hv_fma2(REM, R, Q);
-                }
                 const hv_f2 UV = (Q + C) + hv_splat(0.5f);
                 bool in = true;
                 // a scalar branch around four vector instructions, kept a branch by the empty asm.  (The same choice per gather group - two
                 // copies of this loop - costs two more spilled registers and 5 % of the sweep; per frame - two copies of the frame body - 171.)
-                if (!INTERIOR || frame_checked) {
-                    if (INTERIOR) asm volatile("" ::: "memory");
+                if (frame_checked) {
+                    asm volatile("" ::: "memory");
                     const bool in_u = (__float_as_uint(UV.x) - lo_u) < lim_u;
                     const bool in_v = (__float_as_uint(UV.y) - lo_v) < lim_v;
                     in = (int)in_u & (int)in_v;
@@ -900,7 +903,7 @@ __device__ __forceinline__ void hv_sweep_column_core(
         HvSweepFrameK ka = hv_sweep_frame_k(Ps, __ffsll((long long)mask) - 1), kb = ka;
         auto fold_frame = [&](const HvSweepFrameK K, const int f, HvSweepFrameK &Knext, const unsigned long long rest) __attribute__((always_inline)) {
             begin_frame(K, f, Knext, rest);
-            if (INTERIOR) frame_checked = !((interior_mask >> f) & 1ull);
+            frame_checked = !((interior_mask >> f) & 1ull);
             // the gathers of group g+1 are issued before group g is folded; the pipeline drains at the end of a frame
             Group ga, gb;
             project(ga);
@@ -934,9 +937,9 @@ __device__ __forceinline__ void hv_sweep_column_core(
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (agn[z4 + k] >> 24) {
-                    const int q = wordb + (z4 + k) * RR;
-                    vt[k] = ((const float *)(unit + 0 * PLANE_BYTES))[q];
-                    vw[k] = ((const uint32_t *)(unit + 1 * PLANE_BYTES))[q];
+                    const int q = wordb + (z4 + k) * HV_TSDF_RR;
+                    vt[k] = ((const float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+                    vw[k] = ((const uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
                 }
             }
 #pragma unroll
@@ -944,49 +947,17 @@ __device__ __forceinline__ void hv_sweep_column_core(
                 const int z = z4 + k;
                 const uint32_t n = agn[z] >> 24;
                 if (n) {
-                    const int q = wordb + z * RR;
+                    const int q = wordb + z * HV_TSDF_RR;
                     const uint32_t nw = vw[k] + n;
-                    ((float *)(unit + 0 * PLANE_BYTES))[q] = (vt[k] * (float)vw[k] + S[z]) / (float)nw;
-                    ((uint32_t *)(unit + 1 * PLANE_BYTES))[q] = nw;
-                    ((uint32_t *)(unit + 2 * PLANE_BYTES))[q] += arb[z] & 0xffffu;
-                    ((uint32_t *)(unit + 3 * PLANE_BYTES))[q] += (agn[z] >> 8) & 0xffffu;
-                    ((uint32_t *)(unit + 4 * PLANE_BYTES))[q] += arb[z] >> 16;
+                    ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = (vt[k] * (float)vw[k] + S[z]) / (float)nw;
+                    ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = nw;
+                    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] += arb[z] & 0xffffu;
+                    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] += (agn[z] >> 8) & 0xffffu;
+                    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] += arb[z] >> 16;
                 }
             }
         }
-    };
-    drive(run_item);
-}
-
-// The column sweep's kernel: a grid-stride loop over the batch's union list, XCD-aware (see k_tsdf_sweep).  4 waves per SIMD = 128
-// registers.  ZS = 2 (z halves, 8 one-wave tasks per unit) is the default for a GPU that shares the volume with 3 or more others.
-template <int ZS>
-__global__ __launch_bounds__(64, 4) void k_tsdf_sweep_column(
-    HvTable table, const int32_t *__restrict__ list, const unsigned long long *__restrict__ frame_mask,
-    char *__restrict__ pool, const uint2 *__restrict__ frame_px, const HvFrameParams *__restrict__ Ps, int n_frames,
-    int general, const float *__restrict__ mult, int xcd_aware, int parity) {
-    constexpr int PARTS = 4 * ZS; // work items per unit
-    int n_units = table.counters[HV_CNT_TOUCH(parity)];
-    if (n_units > table.max_blocks) n_units = table.max_blocks;
-    hv_sweep_column_core<ZS>(table, frame_mask, pool, frame_px, Ps, n_frames, general, mult, [&](auto &&run_item) __attribute__((always_inline)) {
-        const int G = xcd_aware > 0 ? xcd_aware : 1;
-        const int rounds = (n_units + 8 * G - 1) / (8 * G);
-        const int n_items = xcd_aware > 0 ? rounds * 8 * G * PARTS : n_units * PARTS;
-        for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
-            int t, part;
-            if (xcd_aware > 0) {
-                const int xcd = item & 7, j = item >> 3;
-                const int g = j / (G * PARTS), within = j - g * (G * PARTS);
-                t = (g * 8 + xcd) * G + within / PARTS;
-                part = within % PARTS;
-                if (t >= n_units) continue;
-            } else {
-                t = item / PARTS;
-                part = item % PARTS;
-            }
-            run_item(list[t], part);
-        }
-    });
+    }
 }
 
 // n16 16-byte words from device-visible host memory to device memory, one workgroup (see hv_tsdf_integrate_batch: frame constants).
@@ -1019,120 +990,6 @@ __global__ __launch_bounds__(1024) void k_tsdf_batch_finish(HvTable table, const
         table.counters[HV_CNT_TOUCH(parity)] = 0; // (the other set's counter may be filling: the next batch's touch pass)
         hv_publish_status(table, status, status_seq); // pool occupancy after this batch, for hv_capacity_gate
     }
-}
-
-// ---- numerators export / import (multi-GPU merge) ----------------------------------------------
-__global__ void k_tsdf_export(HvTable table, const char *__restrict__ pool, const int32_t *__restrict__ keys,
-                              int64_t k, float *__restrict__ payload) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= k * RRR) return;
-    const int64_t ui = gid / RRR;
-    const int word = (int)(gid % RRR);
-    float out[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (hv_key_in_range(kx, ky, kz)) {
-        const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-        const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-        if (idx >= 0) {
-            const char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
-            const float tsdf = ((const float *)(unit))[word];
-            const uint32_t w = ((const uint32_t *)(unit + PLANE_BYTES))[word];
-            out[0] = tsdf * (float)w;
-            out[1] = (float)w;
-            out[2] = (float)((const uint32_t *)(unit + 2 * PLANE_BYTES))[word];
-            out[3] = (float)((const uint32_t *)(unit + 3 * PLANE_BYTES))[word];
-            out[4] = (float)((const uint32_t *)(unit + 4 * PLANE_BYTES))[word];
-        }
-    }
-    float *dst = payload + gid * 5;
-#pragma unroll
-    for (int c = 0; c < 5; ++c) dst[c] = out[c];
-}
-
-__global__ void k_tsdf_import_claim(HvTable table, const int32_t *__restrict__ keys, int64_t k) {
-    const int64_t ui = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (ui >= k) return;
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (!hv_key_in_range(kx, ky, kz)) {
-        atomicAdd(&table.counters[HV_CNT_DROPPED], 1);
-        return;
-    }
-    hv_table_insert(table, hv_pack_key(kx, ky, kz));
-}
-
-__global__ void k_tsdf_import(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys,
-                              int64_t k, const float *__restrict__ payload) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= k * RRR) return;
-    const int64_t ui = gid / RRR;
-    const int word = (int)(gid % RRR);
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (!hv_key_in_range(kx, ky, kz)) return;
-    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-    if (idx < 0) return;
-    const float *src = payload + gid * 5;
-    char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
-    const float w = src[1];
-    ((float *)unit)[word] = w > 0.f ? src[0] / w : 0.f;
-    ((uint32_t *)(unit + PLANE_BYTES))[word] = (uint32_t)w;
-    ((uint32_t *)(unit + 2 * PLANE_BYTES))[word] = (uint32_t)src[2];
-    ((uint32_t *)(unit + 3 * PLANE_BYTES))[word] = (uint32_t)src[3];
-    ((uint32_t *)(unit + 4 * PLANE_BYTES))[word] = (uint32_t)src[4];
-}
-
-// ---- halo merge (image-tile sharding): units stamped since the last merge, and the unpack ------------
-__global__ void k_tsdf_collect_dirty(HvTable table, const int32_t *__restrict__ stamp, int32_t merge_stamp, int32_t n_blocks,
-                                     int32_t *__restrict__ keys, int32_t cap) {
-    const int32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    bool dirty = false;
-    int32_t kx = 0, ky = 0, kz = 0;
-    if (idx < n_blocks) {
-        const unsigned long long key = table.block_keys[idx];
-        const int32_t slot = hv_table_find(table, key);
-        dirty = slot >= 0 && stamp[slot] > merge_stamp;
-        hv_unpack_key(key, kx, ky, kz);
-    }
-    const int32_t at = hv_wave_append(&table.counters[HV_CNT_OUT], dirty);
-    if (dirty && at < cap) {
-        keys[at * 3 + 0] = kx;
-        keys[at * 3 + 1] = ky;
-        keys[at * 3 + 2] = kz;
-    }
-}
-
-// action[u]: 0 = leave the unit alone (this GPU does not hold it), 1 = replace its state by the reduced numerators (this GPU
-// keeps the unit), 2 = zero it (another GPU keeps it; this one goes on fusing deltas into an empty unit)
-__global__ void k_tsdf_halo_unpack(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys, int64_t k,
-                                   const float *__restrict__ payload, const uint8_t *__restrict__ action) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= k * RRR) return;
-    const int64_t ui = gid / RRR;
-    const int act = action[ui];
-    if (act == 0) return;
-    const int word = (int)(gid % RRR);
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (!hv_key_in_range(kx, ky, kz)) return;
-    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-    if (idx < 0) return;
-    char *unit = pool + (int64_t)idx * (PLANE_BYTES * HV_TSDF_PLANES);
-    float tsdf = 0.f;
-    uint32_t w = 0u, r = 0u, g = 0u, b = 0u;
-    if (act == 1) {
-        const float *src = payload + gid * 5;
-        const float wf = src[1];
-        tsdf = wf > 0.f ? src[0] / wf : 0.f;
-        w = (uint32_t)wf;
-        r = (uint32_t)src[2];
-        g = (uint32_t)src[3];
-        b = (uint32_t)src[4];
-    }
-    ((float *)unit)[word] = tsdf;
-    ((uint32_t *)(unit + PLANE_BYTES))[word] = w;
-    ((uint32_t *)(unit + 2 * PLANE_BYTES))[word] = r;
-    ((uint32_t *)(unit + 3 * PLANE_BYTES))[word] = g;
-    ((uint32_t *)(unit + 4 * PLANE_BYTES))[word] = b;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1193,13 +1050,6 @@ int make_frame_params(hv_volume *v, int H, int W, const double *intr, const doub
     return HV_OK;
 }
 
-// Per-frame scratch (single-buffered: the two halves of a frame run back to back on one stream).
-// Measured alternative, rejected: prep+touch of frame f+1 on a second stream overlapping the sweep of
-// frame f (double-buffered scratch, event hand-offs) ran 6955 vs 7280 frames/s - the cross-stream
-// waits and the contention on the sweep cost more than the 16 us they hide.
-static inline uint2 *frame_px_of(hv_volume *v, int) { return (uint2 *)v->frame_px; }
-static inline int32_t *touched_list_of(hv_volume *v, int) { return v->touched_list; }
-
 // First half of a frame: convert/pack the frame, claim and list the touched units.  (This parity's
 // touched counter was zeroed by the previous frame's sweep kernel.)
 static int tsdf_launch_touch(hv_volume *v, hipStream_t s, const HvFrameParams &P, int parity, const void *d_depth,
@@ -1208,9 +1058,12 @@ static int tsdf_launch_touch(hv_volume *v, hipStream_t s, const HvFrameParams &P
     const int n_prep_blocks = (int)((npx + 255) / 256);
     const int ns = ((P.W + P.stride - 1) / P.stride) * ((P.H + P.stride - 1) / P.stride);
     const int n_touch_blocks = (ns * HV_TOUCH_FAN + 255) / 256;
+    // Per-frame scratch (frame_px, touched_list) is single-buffered: the two halves of a frame run back to back on one stream.
+    // Measured alternative, rejected: prep+touch of frame f+1 on a second stream overlapping the sweep of frame f (double-buffered
+    // scratch, event hand-offs) ran 6955 vs 7280 frames/s - the cross-stream waits and the contention on the sweep cost more than
+    // the 16 us they hide.
     hipLaunchKernelGGL(k_tsdf_prep_touch, dim3(n_prep_blocks + n_touch_blocks), dim3(256), 0, s, v->table,
-                       v->touched_stamp, touched_list_of(v, parity), parity, d_depth, d_rgb, frame_px_of(v, parity), P,
-                       n_touch_blocks);
+                       v->touched_stamp, v->touched_list, parity, d_depth, d_rgb, (uint2 *)v->frame_px, P, n_touch_blocks);
     return HV_OK;
 }
 
@@ -1238,8 +1091,8 @@ int tsdf_multiplier_table(hv_volume *v, const HvFrameParams &P) {
 static int tsdf_launch_integrate(hv_volume *v, const HvFrameParams &P, int parity) {
     const dim3 grid(8192), block(256); // > touched units of a frame: no second pass per block
     hv_profile_begin(v);
-    hipLaunchKernelGGL(k_tsdf_integrate, grid, block, 0, v->stream, v->table, (const int32_t *)touched_list_of(v, parity), parity, (char *)v->pool,
-                       (const uint2 *)frame_px_of(v, parity), P, v->d_status, hv_next_status_seq(v));
+    hipLaunchKernelGGL(k_tsdf_integrate, grid, block, 0, v->stream, v->table, (const int32_t *)v->touched_list, parity, (char *)v->pool,
+                       (const uint2 *)v->frame_px, P, v->d_status, hv_next_status_seq(v));
     hv_profile_end(v, 0);
     HV_HIP(hipGetLastError());
     return HV_OK;
@@ -1334,6 +1187,14 @@ int hv_tsdf_integrate(hv_volume *v, const void *depth, int32_t depth_dtype, cons
 
 } // extern "C"
 
+// Scratch of a multi-frame call: [B frame records of rec_bytes each per pixel][pad to 256][B HvFrameParams].  Returns the bytes to
+// ask for; *params_offset = where the frame constants start.
+size_t tsdf_batch_scratch(size_t rec_bytes, size_t npx, int B, size_t *params_offset) {
+    const size_t px_bytes = rec_bytes * npx * (size_t)B;
+    *params_offset = (px_bytes + 255) & ~(size_t)255;
+    return px_bytes + 256 + sizeof(HvFrameParams) * (size_t)B;
+}
+
 // depth_ptrs / rgb_ptrs != nullptr: host-resident frames given one pointer per frame (hv_tsdf_integrate_frames); else `depth`
 // / `rgb` hold the frames contiguously at `loc`.
 int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const *depth_ptrs, int32_t depth_dtype,
@@ -1384,7 +1245,6 @@ int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const
     const int general = getenv("HV_TSDF_BATCH_GENERAL") ? atoi(getenv("HV_TSDF_BATCH_GENERAL")) : 0;
     // z halves (8 tasks per unit) when this GPU shares the volume with 3 or more others: DESIGN section 4
     const int zs = getenv("HV_TSDF_SWEEP_ZS") ? atoi(getenv("HV_TSDF_SWEEP_ZS")) : (v->owner_world >= 4 ? 2 : 1);
-    const int xcd_aware = 2;      // list entries per XCD group (k_tsdf_sweep: measured best, FETCH_SIZE halves)
     const int sweep_grid = 65536; // one work item each up to 16 384 units per batch, grid-stride beyond (measured: 29.6 k frames/s vs 28.2 k at 8192)
     bool chain_ok = v->pipe_armed && v->pipe_version == v->content_version; // nothing but batches since ev_presweep was recorded
     v->content_version += 1;
@@ -1450,15 +1310,15 @@ int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const
             }
         }
         const float *d_mult = v->mult_table;
-        // scratch: [B frame records of npx][B HvFrameParams]
-        const size_t px_bytes = rec_bytes * npx * (size_t)B;
+        size_t params_off = 0;
+        const size_t want = tsdf_batch_scratch(rec_bytes, npx, B, &params_off);
         void **bb = parity ? &v->batch_buf2 : &v->batch_buf;
         size_t *bb_bytes = parity ? &v->batch_buf2_bytes : &v->batch_buf_bytes;
-        if (*bb_bytes < px_bytes + sizeof(HvFrameParams) * (size_t)B + 256 && v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux)); // (a launch two batches back may still write the old buffer)
-        rc = hv_ensure_buffer(v, bb, bb_bytes, px_bytes + sizeof(HvFrameParams) * (size_t)B + 256); // (re-allocation drains the main stream, and with it every batch whose touch pass it waited for)
+        if (*bb_bytes < want && v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux)); // (a launch two batches back may still write the old buffer)
+        rc = hv_ensure_buffer(v, bb, bb_bytes, want); // (re-allocation drains the main stream, and with it every batch whose touch pass it waited for)
         if (rc != HV_OK) return rc;
         uint2 *d_px = (uint2 *)*bb;
-        HvFrameParams *d_params = (HvFrameParams *)((char *)*bb + ((px_bytes + 255) & ~(size_t)255));
+        HvFrameParams *d_params = (HvFrameParams *)((char *)*bb + params_off);
         // The 12 KB of frame constants go up with a ONE-WORKGROUP kernel that reads the page-locked ring slot in place (hipHostMalloc
         // memory is device-visible).  hipMemcpyAsync turns a small pinned copy into the runtime's blit kernel, whose workgroups wait
         // for wave slots behind the sweep that is running on the other queue: 100-420 us per batch in profiles/r03/
@@ -1510,14 +1370,14 @@ int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const
         hv_profile_begin(v);
         const unsigned long long *d_mask = d_mask_rw;
         if (sweep_form == 2)
-            hipLaunchKernelGGL((k_tsdf_sweep<4, 8, 4>), dim3(sweep_grid), dim3(64 * 16 / 8), 0, v->stream, v->table, (const int32_t *)d_list, d_mask,
-                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, xcd_aware, parity);
+            hipLaunchKernelGGL(k_tsdf_sweep, dim3(sweep_grid), dim3(64 * HV_SWEEP_WAVES), 0, v->stream, v->table, (const int32_t *)d_list, d_mask,
+                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, parity);
         else if (zs == 2)
             hipLaunchKernelGGL(k_tsdf_sweep_column<2>, dim3(sweep_grid), dim3(64), 0, v->stream, v->table, (const int32_t *)d_list, d_mask,
-                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, xcd_aware, parity);
+                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, parity);
         else
             hipLaunchKernelGGL(k_tsdf_sweep_column<1>, dim3(sweep_grid), dim3(64), 0, v->stream, v->table, (const int32_t *)d_list, d_mask,
-                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, xcd_aware, parity);
+                               (char *)v->pool, (const uint2 *)d_px, (const HvFrameParams *)d_params, B, general, d_mult, parity);
         hv_profile_end(v, B);
         hipLaunchKernelGGL(k_tsdf_batch_finish, dim3(1), dim3(1024), 0, v->stream, v->table, (const int32_t *)d_list, d_mask_rw, parity, v->d_status,
                            hv_next_status_seq(v));
@@ -1600,22 +1460,22 @@ int hv_tsdf_dump(hv_volume *v, int32_t *keys, float *tsdf, float *weight, double
             if (xyz[a * 3 + k] != xyz[b * 3 + k]) return xyz[a * 3 + k] < xyz[b * 3 + k];
         return false;
     });
-    std::vector<char> unit((size_t)PLANE_BYTES * HV_TSDF_PLANES);
+    std::vector<char> unit((size_t)HV_TSDF_UNIT_BYTES);
     for (int64_t o = 0; o < nb; ++o) {
         const int64_t i = order[o];
         if (keys) memcpy(keys + o * 3, &xyz[i * 3], 12);
         if (!(tsdf || weight || color)) continue;
         HV_HIP(hipMemcpy(unit.data(), (char *)v->pool + i * unit.size(), unit.size(), hipMemcpyDeviceToHost));
         const float *pt = (const float *)unit.data();
-        const uint32_t *pw = (const uint32_t *)(unit.data() + PLANE_BYTES);
-        const uint32_t *pr = (const uint32_t *)(unit.data() + 2 * PLANE_BYTES);
-        const uint32_t *pg = (const uint32_t *)(unit.data() + 3 * PLANE_BYTES);
-        const uint32_t *pb = (const uint32_t *)(unit.data() + 4 * PLANE_BYTES);
-        for (int x = 0; x < R; ++x)
-            for (int y = 0; y < R; ++y)
-                for (int z = 0; z < R; ++z) {
-                    const int src = z * RR + x * R + y;
-                    const int64_t dst = o * RRR + (x * R + y) * R + z;
+        const uint32_t *pw = (const uint32_t *)(unit.data() + HV_TSDF_PLANE_BYTES);
+        const uint32_t *pr = (const uint32_t *)(unit.data() + 2 * HV_TSDF_PLANE_BYTES);
+        const uint32_t *pg = (const uint32_t *)(unit.data() + 3 * HV_TSDF_PLANE_BYTES);
+        const uint32_t *pb = (const uint32_t *)(unit.data() + 4 * HV_TSDF_PLANE_BYTES);
+        for (int x = 0; x < HV_TSDF_R; ++x)
+            for (int y = 0; y < HV_TSDF_R; ++y)
+                for (int z = 0; z < HV_TSDF_R; ++z) {
+                    const int src = hv_tsdf_word(x, y, z);
+                    const int64_t dst = o * HV_TSDF_RRR + (x * HV_TSDF_R + y) * HV_TSDF_R + z;
                     if (tsdf) tsdf[dst] = pt[src];
                     if (weight) weight[dst] = (float)pw[src];
                     if (color) {
@@ -1639,7 +1499,7 @@ int hv_tsdf_touched(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n) {
     *n = nt;
     if (keys == nullptr || nt == 0) return HV_OK;
     std::vector<int32_t> slots((size_t)nt);
-    HV_HIP(hipMemcpy(slots.data(), touched_list_of(v, v->last_touch_parity), sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
+    HV_HIP(hipMemcpy(slots.data(), v->touched_list, sizeof(int32_t) * nt, hipMemcpyDeviceToHost));
     std::vector<uint64_t> tkeys((size_t)v->table_capacity);
     HV_HIP(hipMemcpy(tkeys.data(), v->table.keys, sizeof(uint64_t) * v->table_capacity, hipMemcpyDeviceToHost));
     std::vector<std::array<int32_t, 3>> out((size_t)nt);
@@ -1661,275 +1521,6 @@ int hv_tsdf_unit_keys(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n) {
     HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost));
     const int64_t m = std::min(nb, cap);
     for (int64_t i = 0; i < m; ++i) hv_unpack_key(bkeys[i], keys[i * 3], keys[i * 3 + 1], keys[i * 3 + 2]);
-    return HV_OK;
-}
-
-int hv_tsdf_export_numerators(hv_volume *v, const int32_t *keys, int64_t k, float *payload, int32_t loc) {
-    HV_REQUIRE(v != nullptr && (k == 0 || (keys != nullptr && payload != nullptr)), HV_ERR_INVALID,
-               "hv_tsdf_export_numerators: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_export_numerators: not a TSDF volume");
-    if (k == 0) return HV_OK;
-    HV_HIP(hipSetDevice(v->device));
-    const void *d_keys = nullptr;
-    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
-    if (rc != HV_OK) return rc;
-    const size_t bytes = sizeof(float) * 5 * RRR * (size_t)k;
-    float *d_payload = payload;
-    if (loc == HV_HOST) {
-        v->mesh_cache_version = v->points_cache_version = 0; // out_a is about to be overwritten
-        rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, bytes);
-        if (rc != HV_OK) return rc;
-        d_payload = (float *)v->out_a;
-    }
-    const int64_t total = k * RRR;
-    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const char *)v->pool, (const int32_t *)d_keys, k, d_payload);
-    HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(payload, d_payload, bytes, hipMemcpyDeviceToHost, v->stream));
-    }
-    HV_HIP(hipStreamSynchronize(v->stream));
-    return HV_OK;
-}
-
-int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, const float *payload, int32_t loc) {
-    HV_REQUIRE(v != nullptr && (k == 0 || (keys != nullptr && payload != nullptr)), HV_ERR_INVALID,
-               "hv_tsdf_import_numerators: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_import_numerators: not a TSDF volume");
-    if (k == 0) return HV_OK;
-    v->content_version += 1;
-    v->extract_epoch += 1; // (writes voxels without stamping their units)
-    HV_HIP(hipSetDevice(v->device));
-    const void *d_keys = nullptr, *d_payload = nullptr;
-    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, payload, sizeof(float) * 5 * RRR * (size_t)k, loc, 1, &d_payload);
-    if (rc != HV_OK) return rc;
-    // the imported units are claimed first and the claims verified (this call synchronises anyway): a pool that is too small
-    // grows before anything is written, or the call fails with the volume unchanged (a gather onto a root whose
-    // pool was sized like every other rank's)
-    bool checked = false;
-    rc = hv_capacity_gate(v, &checked);
-    if (rc != HV_OK) return rc;
-    for (int attempt = 0;; ++attempt) {
-        hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                           (const int32_t *)d_keys, k);
-        rc = hv_claims_fit(v);
-        if (rc == HV_OK) break;
-        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-    }
-    const int64_t total = k * RRR;
-    hipLaunchKernelGGL(k_tsdf_import, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (char *)v->pool, (const int32_t *)d_keys, k, (const float *)d_payload);
-    HV_HIP(hipGetLastError());
-    hv_launch_publish_status(v); // the imported units are part of the published occupancy (a later rollback keeps them)
-    HV_HIP(hipStreamSynchronize(v->stream));
-    return HV_OK;
-}
-
-// ---- halo merge entry points (SURVEY 8b hv_merge_halo, 8e): the library packs / unpacks on the device, the caller runs
-// the two collectives (all-gather of key lists, all-reduce of the dense buffer) with whatever transport it has -
-// torch.distributed over RCCL in pyslam_amd/distributed.py ----
-int hv_tsdf_dirty_keys(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n) {
-    HV_REQUIRE(v != nullptr && n != nullptr, HV_ERR_INVALID, "hv_tsdf_dirty_keys: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_dirty_keys: not a TSDF volume");
-    HV_HIP(hipSetDevice(v->device));
-    int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
-    *n = 0;
-    if (nb == 0) return HV_OK;
-    v->mesh_cache_version = v->points_cache_version = 0; // out_a is reused below
-    rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, sizeof(int32_t) * 3 * (size_t)nb);
-    if (rc != HV_OK) return rc;
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    hipLaunchKernelGGL(k_tsdf_collect_dirty, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const int32_t *)v->touched_stamp, v->merge_stamp, (int32_t)nb, (int32_t *)v->out_a, (int32_t)nb);
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v);
-    if (rc != HV_OK) return rc;
-    const int64_t nd = v->h_counters[HV_CNT_OUT];
-    *n = nd;
-    if (keys == nullptr || nd == 0) return HV_OK;
-    std::vector<std::array<int32_t, 3>> out((size_t)nd);
-    HV_HIP(hipMemcpy(out.data(), v->out_a, sizeof(int32_t) * 3 * (size_t)nd, hipMemcpyDeviceToHost));
-    std::sort(out.begin(), out.end());
-    const int64_t m = std::min(nd, cap);
-    for (int64_t i = 0; i < m; ++i) memcpy(keys + i * 3, out[i].data(), 12);
-    return HV_OK;
-}
-
-int hv_tsdf_mark_merged(hv_volume *v) {
-    HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "hv_tsdf_mark_merged: null volume");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_mark_merged: not a TSDF volume");
-    v->merge_stamp = v->frame_counter;
-    return HV_OK;
-}
-
-int hv_merge_halo_plan(const int32_t *gathered_keys, const int64_t *counts, int32_t world_size, int32_t rank,
-                       int32_t *shared_keys, uint8_t *action, int64_t cap, int64_t *n_shared) {
-    HV_REQUIRE(counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size, HV_ERR_INVALID,
-               "hv_merge_halo_plan: bad argument");
-    // (key, rank) pairs of every rank's dirty list, sorted by key then rank; a key listed by >= 2 ranks is shared
-    struct Entry { std::array<int32_t, 3> key; int32_t rank; };
-    int64_t total = 0;
-    for (int r = 0; r < world_size; ++r) total += counts[r];
-    HV_REQUIRE(total == 0 || gathered_keys != nullptr, HV_ERR_INVALID, "hv_merge_halo_plan: null key list");
-    std::vector<Entry> all((size_t)total);
-    int64_t at = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < counts[r]; ++i, ++at) {
-            memcpy(all[at].key.data(), gathered_keys + at * 3, 12);
-            all[at].rank = r;
-        }
-    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) { return a.key != b.key ? a.key < b.key : a.rank < b.rank; });
-    int64_t ns = 0;
-    for (int64_t i = 0; i < total;) {
-        int64_t j = i;
-        bool mine = false;
-        while (j < total && all[j].key == all[i].key) {
-            mine |= all[j].rank == rank;
-            ++j;
-        }
-        if (j - i >= 2) { // listed by two ranks or more (a rank lists a key once)
-            if (shared_keys != nullptr && action != nullptr && ns < cap) {
-                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
-                // the lowest listing rank keeps the unit; EVERY other rank zeroes its copy if it has one - also a rank that holds
-                // the unit from an earlier window without having listed it now: the pack step exports whatever a rank holds,
-                // so a holder that kept its copy would be counted twice (unpack is a no-op where the unit does not exist)
-                action[ns] = all[i].rank == rank ? 1 : 2;
-                (void)mine;
-            }
-            ++ns;
-        }
-        i = j;
-    }
-    *n_shared = ns;
-    return HV_OK;
-}
-
-int hv_merge_halo_plan_held(const int32_t *dirty_keys, const int64_t *dirty_counts, const int32_t *held_keys,
-                            const int64_t *held_counts, int32_t world_size, int32_t rank, int32_t *shared_keys, uint8_t *action,
-                            int64_t cap, int64_t *n_shared) {
-    HV_REQUIRE(dirty_counts != nullptr && held_counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size,
-               HV_ERR_INVALID, "hv_merge_halo_plan_held: bad argument");
-    // (key, rank, kind) of every rank's two lists; a key is merged when some rank updated it since its last merge AND two
-    // ranks or more hold it: afterwards the lowest HOLDING rank has the complete unit and every other holder zeros
-    struct Entry { std::array<int32_t, 3> key; int32_t rank; int32_t dirty; };
-    int64_t nd = 0, nh = 0;
-    for (int r = 0; r < world_size; ++r) {
-        nd += dirty_counts[r];
-        nh += held_counts[r];
-    }
-    HV_REQUIRE((nd == 0 || dirty_keys != nullptr) && (nh == 0 || held_keys != nullptr), HV_ERR_INVALID, "hv_merge_halo_plan_held: null key list");
-    std::vector<Entry> all((size_t)(nd + nh));
-    int64_t at = 0, src = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < dirty_counts[r]; ++i, ++at, ++src) {
-            memcpy(all[at].key.data(), dirty_keys + src * 3, 12);
-            all[at].rank = r;
-            all[at].dirty = 1;
-        }
-    src = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < held_counts[r]; ++i, ++at, ++src) {
-            memcpy(all[at].key.data(), held_keys + src * 3, 12);
-            all[at].rank = r;
-            all[at].dirty = 0;
-        }
-    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) {
-        if (a.key != b.key) return a.key < b.key;
-        if (a.rank != b.rank) return a.rank < b.rank;
-        return a.dirty < b.dirty;
-    });
-    int64_t ns = 0;
-    const int64_t total = nd + nh;
-    for (int64_t i = 0; i < total;) {
-        int64_t j = i;
-        int holders = 0, keeper = -1, last_holder = -1;
-        bool any_dirty = false;
-        while (j < total && all[j].key == all[i].key) {
-            if (all[j].dirty) {
-                any_dirty = true;
-            } else if (all[j].rank != last_holder) {
-                last_holder = all[j].rank;
-                if (keeper < 0) keeper = all[j].rank;
-                ++holders;
-            }
-            ++j;
-        }
-        if (any_dirty && holders >= 2) {
-            if (shared_keys != nullptr && action != nullptr && ns < cap) {
-                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
-                action[ns] = keeper == rank ? 1 : 2;
-            }
-            ++ns;
-        }
-        i = j;
-    }
-    *n_shared = ns;
-    return HV_OK;
-}
-
-int hv_merge_halo_pack(hv_volume *v, const int32_t *shared_keys, int64_t k, float *payload, int32_t loc) {
-    return hv_tsdf_export_numerators(v, shared_keys, k, payload, loc);
-}
-
-int hv_merge_halo_unpack(hv_volume *v, const int32_t *shared_keys, int64_t k, const float *payload, const uint8_t *action,
-                         int32_t loc) {
-    HV_REQUIRE(v != nullptr && (k == 0 || (shared_keys != nullptr && payload != nullptr && action != nullptr)), HV_ERR_INVALID,
-               "hv_merge_halo_unpack: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_unpack: not a TSDF volume");
-    if (k == 0) return HV_OK;
-    v->content_version += 1;
-    v->extract_epoch += 1; // (writes voxels without stamping their units)
-    HV_HIP(hipSetDevice(v->device));
-    // keys + actions in one staging buffer, payload in the other
-    std::vector<char> host((size_t)k * 13);
-    memcpy(host.data(), shared_keys, (size_t)k * 12);
-    memcpy(host.data() + (size_t)k * 12, action, (size_t)k);
-    const void *d_ka = nullptr, *d_payload = nullptr;
-    int rc = hv_stage_in(v, host.data(), host.size(), HV_HOST, 0, &d_ka);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, payload, sizeof(float) * 5 * RRR * (size_t)k, loc, 1, &d_payload);
-    if (rc != HV_OK) return rc;
-    const int64_t total = k * RRR;
-    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (char *)v->pool, (const int32_t *)d_ka, k, (const float *)d_payload,
-                       (const uint8_t *)d_ka + (size_t)k * 12);
-    HV_HIP(hipGetLastError());
-    HV_HIP(hipStreamSynchronize(v->stream)); // `host` goes out of scope
-    return HV_OK;
-}
-
-// ... with the plan hv_merge_halo_plan_device left in the volume (hv_halo.hip): units [first, first + count) of it, device payload,
-// nothing staged, nothing waited for - the caller orders its collective against the volume's stream
-int hv_merge_halo_pack_planned(hv_volume *v, int64_t first, int64_t count, float *d_payload) {
-    HV_REQUIRE(v != nullptr && (count == 0 || d_payload != nullptr), HV_ERR_INVALID, "hv_merge_halo_pack_planned: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_pack_planned: not a TSDF volume");
-    HV_REQUIRE(first >= 0 && count >= 0 && first + count <= v->halo_plan_n, HV_ERR_INVALID, "hv_merge_halo_pack_planned: range outside the plan");
-    if (count == 0) return HV_OK;
-    HV_HIP(hipSetDevice(v->device));
-    const int64_t total = count * RRR;
-    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (const char *)v->pool,
-                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload);
-    HV_HIP(hipGetLastError());
-    return HV_OK;
-}
-
-int hv_merge_halo_unpack_planned(hv_volume *v, int64_t first, int64_t count, const float *d_payload) {
-    HV_REQUIRE(v != nullptr && (count == 0 || d_payload != nullptr), HV_ERR_INVALID, "hv_merge_halo_unpack_planned: null argument");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_unpack_planned: not a TSDF volume");
-    HV_REQUIRE(first >= 0 && count >= 0 && first + count <= v->halo_plan_n, HV_ERR_INVALID, "hv_merge_halo_unpack_planned: range outside the plan");
-    if (count == 0) return HV_OK;
-    v->content_version += 1;
-    v->extract_epoch += 1; // (writes voxels without stamping their units)
-    HV_HIP(hipSetDevice(v->device));
-    const int64_t total = count * RRR;
-    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (char *)v->pool,
-                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload,
-                       (const uint8_t *)v->halo_plan + (size_t)v->halo_plan_n * 12 + first);
-    HV_HIP(hipGetLastError());
     return HV_OK;
 }
 

@@ -4,10 +4,6 @@
 #pragma once
 #include "hv_common.h"
 
-static constexpr int R = 16;
-static constexpr int RR = R * R;
-static constexpr int RRR = R * R * R;
-static constexpr int PLANE_BYTES = RRR * 4;
 static constexpr int HV_TOUCH_FAN = 8; // lanes per depth sample in the online touch pass
 static constexpr uint32_t HV_REC_ONE = 1u << 24; // observation count byte of a batch frame record's colour word
 
@@ -75,17 +71,6 @@ struct HvTouchScratch { // per wave
     uint16_t list[HV_TOUCH_BOX_BITS];
 };
 
-__device__ __forceinline__ int32_t hv_wave_min_i32(int32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = min(x, __shfl_xor(x, o));
-    return x;
-}
-__device__ __forceinline__ int32_t hv_wave_max_i32(int32_t x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x = max(x, __shfl_xor(x, o));
-    return x;
-}
-
 __host__ __device__ inline int hv_touch_patches_1d(int extent, int stride) {
     return ((extent + stride - 1) / stride + HV_TOUCH_PATCH - 1) / HV_TOUCH_PATCH;
 }
@@ -144,8 +129,8 @@ __device__ __forceinline__ void hv_touch_patch(const HvTable &table, const HvFra
     int32_t blo[3], bhi[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        blo[r] = hv_wave_min_i32(has ? lo[r] : INT32_MAX);
-        bhi[r] = hv_wave_max_i32(has ? hi[r] : INT32_MIN);
+        blo[r] = hv_wave_min(has ? lo[r] : INT32_MAX);
+        bhi[r] = hv_wave_max(has ? hi[r] : INT32_MIN);
     }
     const int64_t d0 = (int64_t)bhi[0] - blo[0] + 1, d1 = (int64_t)bhi[1] - blo[1] + 1, d2 = (int64_t)bhi[2] - blo[2] + 1;
     const bool boxed = d0 <= P.touch_box_bits && d1 <= P.touch_box_bits && d2 <= P.touch_box_bits &&
@@ -450,6 +435,7 @@ int tsdf_multiplier_table(hv_volume *v, const HvFrameParams &P); // v->mult_tabl
 int tsdf_rectify(hv_volume *v, hipStream_t s, const void **depth, int depth_dtype, const uint8_t **rgb, int B, int H, int W);
 int check_tsdf_args(hv_volume *v, const void *depth, const uint8_t *rgb, int H, int W, const double *intr, const double *T_cw,
                     int frames);
+size_t tsdf_batch_scratch(size_t rec_bytes, size_t npx, int B, size_t *params_offset); // bytes of a multi-frame call's scratch
 int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const *depth_ptrs, int32_t depth_dtype, const uint8_t *rgb,
                               const void *const *rgb_ptrs, int32_t n_frames, int32_t height, int32_t width, const double *intr,
                               const double *T_cw, double depth_scale, double depth_trunc, int32_t loc);

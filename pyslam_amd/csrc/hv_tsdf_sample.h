@@ -9,13 +9,6 @@
 #include "hv_common.h"
 
 #ifdef __HIPCC__
-static constexpr int HV_TSDF_R = 16;
-static constexpr int HV_TSDF_PLANE_BYTES = HV_TSDF_R * HV_TSDF_R * HV_TSDF_R * 4;
-static constexpr int HV_TSDF_UNIT_BYTES = HV_TSDF_PLANE_BYTES * HV_TSDF_PLANES;
-
-// word index of voxel (x, y, z) inside a plane of a unit (hv_common.h: z*R*R + x*R + y)
-__device__ __forceinline__ int hv_tsdf_word(int x, int y, int z) { return z * HV_TSDF_R * HV_TSDF_R + x * HV_TSDF_R + y; }
-
 // pool index of unit (ux, uy, uz), -1 if absent; the last key looked up and its index are cached in (cached_key, cached_idx)
 __device__ __forceinline__ int32_t hv_tsdf_unit(const HvTable &table, int32_t ux, int32_t uy, int32_t uz, unsigned long long &cached_key,
                                                 int32_t &cached_idx) {
@@ -38,7 +31,6 @@ __device__ __forceinline__ float hv_tsdf_voxel(const HvTable &table, const char 
 
 __device__ inline double hv_tsdf_at(const HvTable &table, const char *__restrict__ pool, double voxel_length, double unit_length,
                                     const double *p, unsigned long long &ck, int32_t &ci) {
-    constexpr int R = HV_TSDF_R;
     int32_t index0[3];
     int idx0[3];
     double r[3];
@@ -48,7 +40,7 @@ __device__ inline double hv_tsdf_at(const HvTable &table, const char *__restrict
         index0[i] = (int32_t)floor(p_locate / unit_length);
         const double p_grid = (p_locate - (double)index0[i] * unit_length) / voxel_length;
         int q = (int)floor(p_grid);
-        q = q < 0 ? 0 : (q >= R ? R - 1 : q);
+        q = q < 0 ? 0 : (q >= HV_TSDF_R ? HV_TSDF_R - 1 : q);
         idx0[i] = q;
         r[i] = p_grid - (double)q;
     }
@@ -65,8 +57,8 @@ __device__ inline double hv_tsdf_at(const HvTable &table, const char *__restrict
     for (int i = 0; i < 8; ++i) {
         const int sx = (i == 1 || i == 2 || i == 5 || i == 6), sy = (i == 2 || i == 3 || i == 6 || i == 7), sz = i >= 4;
         int x = idx0[0] + sx, y = idx0[1] + sy, z = idx0[2] + sz;
-        const int32_t ux = index0[0] + (x >= R), uy = index0[1] + (y >= R), uz = index0[2] + (z >= R);
-        f[i] = hv_tsdf_voxel(table, pool, ux, uy, uz, x & (R - 1), y & (R - 1), z & (R - 1), ck, ci);
+        const int32_t ux = index0[0] + (x >= HV_TSDF_R), uy = index0[1] + (y >= HV_TSDF_R), uz = index0[2] + (z >= HV_TSDF_R);
+        f[i] = hv_tsdf_voxel(table, pool, ux, uy, uz, x & (HV_TSDF_R - 1), y & (HV_TSDF_R - 1), z & (HV_TSDF_R - 1), ck, ci);
     }
     return (1 - r[0]) * ((1 - r[1]) * ((1 - r[2]) * f[0] + r[2] * f[4]) + r[1] * ((1 - r[2]) * f[3] + r[2] * f[7])) +
            r[0] * ((1 - r[1]) * ((1 - r[2]) * f[1] + r[2] * f[5]) + r[1] * ((1 - r[2]) * f[2] + r[2] * f[6]));

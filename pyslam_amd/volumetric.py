@@ -136,77 +136,55 @@ class OdometryResult:
                 f"iterations={self.iterations})")
 
 
-class DeintegrationStats:
+class _Stats:
+    """Base of the *Stats results below: integer fields, named (and ordered) by the subclass's __slots__, each defaulting to 0."""
+
+    __slots__ = ()
+
+    def __init__(self, *args, **kwargs):
+        names = self.__slots__
+        if len(args) > len(names):
+            raise TypeError(f"{type(self).__name__}() takes at most {len(names)} arguments ({len(args)} given)")
+        values = dict(zip(names, args))
+        for name, value in kwargs.items():
+            if name not in names or name in values:
+                raise TypeError(f"{type(self).__name__}() got an unexpected or repeated argument '{name}'")
+            values[name] = value
+        for name in names:
+            setattr(self, name, int(values.get(name, 0)))
+
+    def as_tuple(self):
+        return tuple(getattr(self, name) for name in self.__slots__)
+
+    def __eq__(self, other):
+        return isinstance(other, type(self)) and self.as_tuple() == other.as_tuple()
+
+    def __repr__(self):
+        return f"{type(self).__name__}({', '.join(f'{name}={getattr(self, name)}' for name in self.__slots__)})"
+
+
+class DeintegrationStats(_Stats):
     """What ScalableTSDFVolume.deintegrate* / reintegrate_batch return (hv_deintegrate_stats): units_listed = units the frames'
     touch sets name, summed over frames; units_missing = of those, absent from the volume (skipped); voxels_removed = voxel
     observations taken out; voxels_underflow = voxels left unchanged because they held fewer observations than were to go."""
 
     __slots__ = ("units_listed", "units_missing", "voxels_removed", "voxels_underflow")
 
-    def __init__(self, units_listed=0, units_missing=0, voxels_removed=0, voxels_underflow=0):
-        self.units_listed = int(units_listed)
-        self.units_missing = int(units_missing)
-        self.voxels_removed = int(voxels_removed)
-        self.voxels_underflow = int(voxels_underflow)
 
-    def as_tuple(self):
-        return (self.units_listed, self.units_missing, self.voxels_removed, self.voxels_underflow)
-
-    def __eq__(self, other):
-        return isinstance(other, DeintegrationStats) and self.as_tuple() == other.as_tuple()
-
-    def __repr__(self):
-        return (f"DeintegrationStats(units_listed={self.units_listed}, units_missing={self.units_missing}, "
-                f"voxels_removed={self.voxels_removed}, voxels_underflow={self.voxels_underflow})")
-
-
-class PruneStats:
+class PruneStats(_Stats):
     """What ScalableTSDFVolume.prune returns (hv_prune_stats): units_before = units held at the call; units_outside = released
     because their index lies outside the bounds; units_empty = released because all their weights are 0 (a unit that is both
     counts as outside); units_after = units_before - units_outside - units_empty."""
 
     __slots__ = ("units_before", "units_outside", "units_empty", "units_after")
 
-    def __init__(self, units_before=0, units_outside=0, units_empty=0, units_after=0):
-        self.units_before = int(units_before)
-        self.units_outside = int(units_outside)
-        self.units_empty = int(units_empty)
-        self.units_after = int(units_after)
 
-    def as_tuple(self):
-        return (self.units_before, self.units_outside, self.units_empty, self.units_after)
-
-    def __eq__(self, other):
-        return isinstance(other, PruneStats) and self.as_tuple() == other.as_tuple()
-
-    def __repr__(self):
-        return (f"PruneStats(units_before={self.units_before}, units_outside={self.units_outside}, "
-                f"units_empty={self.units_empty}, units_after={self.units_after})")
-
-
-class MergeStats:
+class MergeStats(_Stats):
     """What ScalableTSDFVolume.integrate_volume returns (hv_merge_stats): units_source = source units that hold a weight;
     units_claimed = units new in the destination; voxels_trilinear / voxels_nearest = voxels updated from an interpolated / a
     nearest sample; voxels_updated = their sum."""
 
     __slots__ = ("units_source", "units_claimed", "voxels_updated", "voxels_trilinear", "voxels_nearest")
-
-    def __init__(self, units_source=0, units_claimed=0, voxels_updated=0, voxels_trilinear=0, voxels_nearest=0):
-        self.units_source = int(units_source)
-        self.units_claimed = int(units_claimed)
-        self.voxels_updated = int(voxels_updated)
-        self.voxels_trilinear = int(voxels_trilinear)
-        self.voxels_nearest = int(voxels_nearest)
-
-    def as_tuple(self):
-        return (self.units_source, self.units_claimed, self.voxels_updated, self.voxels_trilinear, self.voxels_nearest)
-
-    def __eq__(self, other):
-        return isinstance(other, MergeStats) and self.as_tuple() == other.as_tuple()
-
-    def __repr__(self):
-        return (f"MergeStats(units_source={self.units_source}, units_claimed={self.units_claimed}, voxels_updated={self.voxels_updated}, "
-                f"voxels_trilinear={self.voxels_trilinear}, voxels_nearest={self.voxels_nearest})")
 
 
 _UNIT_KEY_BIAS = 1 << 20  # the library packs a unit index into 21 bits per axis: [-2^20, 2^20)
