@@ -354,11 +354,15 @@ int hv_tsdf_integrate_frames(hv_volume *v, const void *const *depth_frames, int3
  *                w0 < n   unchanged in all five planes, counted once in voxels_underflow;
  *                w0 == n  the state of a freshly claimed voxel: weight 0, colour sums 0, tsdf 0 (what hv_tsdf_dump shows for a voxel
  *                         no frame has touched);
- *                else     w = w0 - n, each colour sum loses the frames' colour bytes exactly, and
+ *                else     w = w0 - n, each colour sum becomes min(max(sum - bytes, 0), 255 * w) with `bytes` the frames' colour bytes
+ *                         (exact integers), and
  *                         tsdf = (float)(((double)tsdf0 * w0 - sum_f (double)t_f) / (double)(w0 - n)), the sum in frame order, in
  *                         double, without contraction (one double and one float rounding).
  *              Weights and colour sums come back bit for bit; the tsdf mean carries the ~half-ulp rounding of every stored mean,
- *              scaled by about w0 / w by the removal (63 of 64 observations removed: ~64 x 3e-8).
+ *              scaled by about w0 / w by the removal (63 of 64 observations removed: ~64 x 3e-8).  The clamp of the colour sums
+ *              never acts when the removed frames were fused into the voxel (the bytes that remain sum to at most 255 * w); it
+ *              keeps sum / w in [0, 255] when a frame that was never fused into the voxel is removed while w0 > n (a second
+ *              removal, a wrong pose, a merged map).  The tsdf is NOT clamped: after such a removal it can leave [-1, 1].
  *   stamping   every unit of the touch set that the volume holds is stamped with a new frame counter value (the incremental
  *              extractions recompute it, hv_tsdf_dirty_keys reports it).
  *   reintegrate  hv_tsdf_deintegrate_batch at T_cw_old, then hv_tsdf_integrate_batch at T_cw_new (both F*16), over frames

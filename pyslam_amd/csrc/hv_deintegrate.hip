@@ -107,9 +107,12 @@ __device__ __forceinline__ void hv_deint_apply(double s, uint32_t rg, uint32_t b
     const uint32_t w1 = w - n;
     tsdf = (float)(((double)tsdf * (double)w - s) / (double)w1);
     w = w1;
-    sr -= rg & 0xffffu;
-    sg -= rg >> 16;
-    sb -= bn & 0xffffu;
+    // each sum stays in [0, 255 * w]: the clamp acts only when a frame that was never fused into the voxel is removed from it
+    const uint32_t top = 255u * w1;
+    const uint32_t r = rg & 0xffffu, g = rg >> 16, b = bn & 0xffffu;
+    sr = sr > r ? std::min(sr - r, top) : 0u;
+    sg = sg > g ? std::min(sg - g, top) : 0u;
+    sb = sb > b ? std::min(sb - b, top) : 0u;
 }
 
 // One frame's samples of a lane's 4 x 4 voxels added to its accumulators: n and colour bytes packed (rg = r | g << 16, bn = b | n << 16:

@@ -618,7 +618,8 @@ __global__ __launch_bounds__(256) void k_pc_extract(HvTable table, const char *_
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             points[at * 3 + k] = (OUT)p[k];
-            colors[at * 3 + k] = (OUT)(double)((c0[k] * r1 + c1[k] * r0) / (r0 + r1) / 255.0f);
+            // (the float chain can round two means of 255 to 255.00002: the colour stays in [0, 1])
+            colors[at * 3 + k] = (OUT)(double)fminf((c0[k] * r1 + c1[k] * r0) / (r0 + r1) / 255.0f, 1.0f);
         }
     }
 }

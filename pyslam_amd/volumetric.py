@@ -1158,8 +1158,9 @@ class ScalableTSDFVolume(_Volume):
 
     def deintegrate(self, image, intrinsic, extrinsic):
         """Take the observations integrate(image, intrinsic, extrinsic) added back out of the map (include/hipvol.h,
-        hv_tsdf_deintegrate): image and extrinsic must be what that frame was fused with.  Waits for the GPU and returns
-        DeintegrationStats."""
+        hv_tsdf_deintegrate): image and extrinsic must be what that frame was fused with.  Where they are not, and the voxel holds
+        more observations than are removed, each colour sum is clamped to [0, 255 * weight] (colours stay in 0..255); the tsdf is
+        not clamped.  Waits for the GPU and returns DeintegrationStats."""
         depth, color, dkind, converted = _tsdf_operands(image.depth, image.color, intrinsic)
         H, W = int(depth.shape[0]), int(depth.shape[1])
         intr = intrinsic.as_array()
@@ -1183,7 +1184,8 @@ class ScalableTSDFVolume(_Volume):
 
     def deintegrate_batch(self, depth, color, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """Take F frames ([F,H,W] depth, [F,H,W,3] colour, [F,4,4] T_cw they were fused with) back out of the map, in chunks of 64
-        frames in order.  Waits for the GPU and returns DeintegrationStats; zero frames is a no-op."""
+        frames in order (colour sums clamped as in deintegrate).  Waits for the GPU and returns DeintegrationStats; zero frames is a
+        no-op."""
         F, depth, color, dkind, converted, (T,) = self._batch_operands(depth, color, intrinsic, extrinsics)
         if F == 0:
             return DeintegrationStats()

@@ -65,7 +65,8 @@ def deintegrate_reference(dump, samples, max_frames=MAX_FRAMES):
         tsdf[rest] = ((tsdf[rest].astype(np.float64) * w[rest].astype(np.float64) - s[rest]) /
                       (w[rest] - n[rest]).astype(np.float64)).astype(np.float32)
         w[rest] -= n[rest]
-        sums[rest] -= csum[rest]
+        # each sum stays in [0, 255 w]: acts only when a frame that was never fused into the voxel is removed from it
+        sums[rest] = np.minimum(np.maximum(sums[rest] - csum[rest], 0), 255 * w[rest][:, None])
     wf = w.astype(np.float64)
     with np.errstate(invalid="ignore", divide="ignore"):
         col = np.where(wf[..., None] > 0, sums / wf[..., None], 0.0)

@@ -1,16 +1,23 @@
 """Voxel states that no depth image produces, for the two kernels that read the map at arbitrary positions (hv_merge.hip,
-hv_raycast.hip) - test infrastructure, no GPU.
+hv_raycast.hip) and the two that rewrite it in place (hv_deintegrate.hip, hv_prune.hip) - test infrastructure, no GPU.
 
 A STATE is (keys [U,3] int32 sorted by (x, y, z), tsdf [U,4096] float32, weight [U,4096] float32, colour [U,4096,3] float64) in
-dump order (x * 256 + y * 16 + z).  Weights are integers <= 7 and colours integers 0..255, so every numerator of the float32
-payload of hv_tsdf_import_numerators (tsdf * weight aside) is exact; the tsdf goes through one float32 product and one float32
-quotient, which as_dump() repeats, so as_dump(states) IS the dump of a volume the states were planted into, bit for bit.  The GPU
-tests still run the restatements on the planted volume's own dump(), never on the arrays that were planted.
+dump order (x * 256 + y * 16 + z).  Weights are integers <= 7 (finish(max_weight=...) admits up to 65 000) and colours integers
+0..255, so every numerator of the float32 payload of hv_tsdf_import_numerators (tsdf * weight aside) is exact: colour * weight <=
+255 * 65 000 < 2^24 is an integer float32 holds.  The tsdf goes through one float32 product and one float32 quotient, which
+as_dump() repeats, so as_dump(states) IS the dump of a volume the states were planted into, bit for bit.  The GPU tests still run
+the restatements on the planted volume's own dump(), never on the arrays that were planted.
+
+The de-integration and prune builders (deintegration_target, chunk_boundary_target, one_voxel_units, empty_units) plant what a map
+fused from the frames that are then removed never holds: all three branches of the removal rule inside one 16-byte quad, weights
+between a voxel's count in the first 64-frame chunk and its count over the call, colours the removed frames never contributed,
+units with one observed voxel, all-zero units.
 
 Poses: EXACT-INVERSE camera poses (a signed-permutation rotation of determinant +1 and a translation in multiples of 2^-7 m) have
 an inverse that every method computes without rounding, so the ray-cast reference and the library start from the same float32
 rays.  Merge transforms that are signed permutations are written with literal 0 / +-1 entries.
 """
+import functools
 import itertools
 
 import numpy as np
@@ -28,12 +35,16 @@ def centres(keys, voxel=VOX):
     return (np.asarray(keys, np.int64).reshape(-1, 1, 3) * R + _IDX[None] + 0.5) * voxel
 
 
-def finish(keys, tsdf, weight, colour):
+MAX_WEIGHT = 65000  # 255 * 65 000 < 2^24: colour * weight stays an exact float32 integer
+
+
+def finish(keys, tsdf, weight, colour, max_weight=7):
     """Sort by key, cast, and put unobserved voxels into the fresh state (tsdf 0, colour 0)."""
+    assert max_weight <= MAX_WEIGHT
     keys = np.asarray(keys, np.int64).reshape(-1, 3)
     order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
     weight = np.asarray(weight, np.float32).reshape(len(keys), NV)[order]
-    assert (weight == np.rint(weight)).all() and weight.min() >= 0 and weight.max() <= 7
+    assert (weight == np.rint(weight)).all() and weight.min() >= 0 and weight.max() <= max_weight
     tsdf = np.where(weight > 0, np.asarray(tsdf, np.float32).reshape(len(keys), NV)[order], np.float32(0))
     colour = np.asarray(colour, np.float64).reshape(len(keys), NV, 3)[order]
     assert (colour == np.rint(colour)).all() and colour.min() >= 0 and colour.max() <= 255
@@ -319,3 +330,194 @@ def tilted_wall_at_a_missing_unit(seed=5, camera=CAMERA):
     tsdf = np.where(band, sdf / TRUNC, 0.0).astype(np.float32)
     weight = np.where(band, 4.0, 0.0).astype(np.float32)
     return finish(keys, tsdf, weight, rng.integers(0, 256, tsdf.shape + (3,)).astype(np.float64))
+
+
+# ---- de-integration targets ----------------------------------------------------------------------------------------------------
+SPECIAL_TSDF = (-1.0, -0.98, -0.5, -1e-3, -0.0, 0.0, 1e-3, 0.5, 0.98, 1.0)
+CHUNK = 64  # HV_TSDF_DEINTEGRATE_MAX_FRAMES
+
+
+def sample_counts(keys, samples):
+    """Per voxel of the units `keys` [U,3]: how many of the frames `samples` (FrameSamples) sample it, and the sum of their colour
+    bytes.  -> (n [U,4096] int64, bytes [U,4096,3] int64, units the frames list that `keys` does not hold)."""
+    index = {tuple(int(x) for x in k): i for i, k in enumerate(np.asarray(keys))}
+    n, csum, missing = np.zeros((len(index), NV), np.int64), np.zeros((len(index), NV, 3), np.int64), 0
+    for fs in samples:
+        for j, k in enumerate(fs.keys):
+            i = index.get(tuple(int(x) for x in k))
+            if i is None:
+                missing += 1
+                continue
+            n[i] += fs.sampled[j]
+            csum[i] += fs.colour[j] * fs.sampled[j][:, None]
+    return n, csum, missing
+
+
+def removal_classes(weight, n):
+    """The three branches of the removal rule for voxels of weight `weight` that n frames of one chunk sample.
+    -> (underflow, fresh, remaining) bool masks."""
+    w = np.asarray(weight).astype(np.int64)
+    return (n > 0) & (w < n), (n > 0) & (w == n), (n > 0) & (w > n)
+
+
+def quads_with_all_classes(under, fresh, rest):
+    """How many quads (four consecutive y at fixed x, z of one unit: one lane's 16-byte access) hold all three classes."""
+    q = lambda m: m.reshape(-1, R, R // 4, 4, R).any(axis=3)
+    return int((q(under) & q(fresh) & q(rest)).sum())
+
+
+def clamp_ends(dump, n, csum):
+    """Voxels of a single-chunk removal (n, csum = sample_counts of the dump's keys) at which the clamp of the colour sums acts:
+    (sum - bytes < 0 in some channel, sum - bytes > 255 (w - n) in some channel), counted over the remaining class."""
+    _, _, weight, colour = dump
+    rest = removal_classes(weight, n)[2]
+    w = np.asarray(weight).astype(np.int64)
+    left = np.rint(np.asarray(colour) * np.asarray(weight, np.float64)[..., None]).astype(np.int64) - csum
+    return int((rest & (left < 0).any(-1)).sum()), int((rest & (left > 255 * (w - n)[..., None]).any(-1)).sum())
+
+
+def _target_keys(samples, rng, drop):
+    keys = np.unique(np.concatenate([np.asarray(fs.keys, np.int64).reshape(-1, 3) for fs in samples]), axis=0)
+    gone = rng.random(len(keys)) < drop
+    gone[rng.integers(len(keys))] = True  # at least one unit of the touch sets is absent
+    return keys[~gone]
+
+
+def _arbitrary_tsdf(rng, shape):
+    tsdf = rng.uniform(-1.0, 1.0, shape).astype(np.float32)
+    m = rng.random(shape) < 0.08
+    tsdf[m] = rng.choice(np.array(SPECIAL_TSDF, np.float32), int(m.sum()))
+    return tsdf
+
+
+def _consistent_colour(rng, colour, weight, n, csum):
+    """Where weight > n: an integer mean c with bytes <= c * weight <= bytes + 255 (weight - n) - the sum holds the bytes that are
+    removed, and what is left is the sum of weight - n bytes.  (The range is 255 (weight - n) / weight >= 255 / 65 wide.)"""
+    rest = weight > n
+    w = np.maximum(weight, 1)[..., None]
+    lo = -((-csum) // w)
+    hi = (csum + 255 * (weight - n)[..., None]) // w
+    assert (lo <= hi)[rest].all() and (lo >= 0).all() and (hi[rest] <= 255).all()
+    c = lo + np.floor(rng.random(csum.shape) * (hi - lo + 1)).astype(np.int64)
+    return np.where(rest[..., None], np.minimum(c, hi), colour)
+
+
+def _foreign_colour(rng, shape):
+    colour = rng.integers(0, 256, shape + (3,))
+    u = rng.random(shape + (3,))
+    colour[u < 0.2] = 0
+    colour[u > 0.8] = 255
+    return colour
+
+
+def deintegration_target(samples, seed, colours="consistent", drop=0.15):
+    """A state for the removal of the frames `samples` (FrameSamples of ONE chunk: <= 64 frames).  Units: the union of the frames'
+    touch sets less a share `drop` (at least one unit; each absence counts once per frame that lists it in units_missing).  A
+    voxel that n >= 1 frames sample gets a weight drawn evenly from {0, n - 1, n, n + 1, n + k} (k in 2..6; n - 1 = 0 when n = 1):
+    underflow, underflow, fresh, one observation left, several left - placed at random, so all branches meet inside single quads.
+    Voxels no frame samples hold weights 0..7.  tsdf arbitrary in [-1, 1] with special values.  colours = "consistent": where
+    observations remain the planted sum holds the removed bytes and leaves at most 255 per remaining observation (the clamp never
+    acts); "foreign": random colours with 0 and 255 over-represented (both ends of the clamp are reached)."""
+    assert 1 <= len(samples) <= CHUNK and colours in ("consistent", "foreign")
+    rng = np.random.default_rng(seed)
+    keys = _target_keys(samples, rng, drop)
+    n, csum, _ = sample_counts(keys, samples)
+    pick = rng.integers(0, 5, n.shape)
+    weight = np.select([pick == 0, pick == 1, pick == 2, pick == 3], [0, n - 1, n, n + 1], n + rng.integers(2, 7, n.shape))
+    free = rng.integers(1, 8, n.shape)
+    free[rng.random(n.shape) < 0.3] = 0
+    weight = np.where(n > 0, weight, free)
+    assert quads_with_all_classes(*removal_classes(weight, n)) > 0  # random placement: the three branches share quads
+    colour = _foreign_colour(rng, n.shape)
+    if colours == "consistent":
+        colour = _consistent_colour(rng, colour, weight, n, csum)
+    return finish(keys, _arbitrary_tsdf(rng, n.shape), weight, colour, max_weight=CHUNK + 6)
+
+
+def chunk_boundary_target(samples, seed, drop=0.1):
+    """A state for the removal of more than 64 frames in one call.  n1 = a voxel's count in the first chunk, nt = over the whole
+    call.  Where n1 >= 1 and nt - n1 >= 2, half of the voxels get a weight strictly between n1 and nt: decided per chunk the first
+    chunk's observations leave and the second chunk underflows; decided per call nothing would be removed.  Every other voxel is
+    drawn as in deintegration_target with n = nt.  Colours are consistent where the weight exceeds the count."""
+    assert CHUNK < len(samples) <= 2 * CHUNK
+    rng = np.random.default_rng(seed)
+    keys = _target_keys(samples, rng, drop)
+    n1, csum1, _ = sample_counts(keys, samples[:CHUNK])
+    n2, csum2, _ = sample_counts(keys, samples[CHUNK:])
+    nt = n1 + n2
+    pick = rng.integers(0, 5, nt.shape)
+    weight = np.select([pick == 0, pick == 1, pick == 2, pick == 3], [0, nt - 1, nt, nt + 1], nt + rng.integers(2, 7, nt.shape))
+    free = rng.integers(1, 8, nt.shape)
+    free[rng.random(nt.shape) < 0.3] = 0
+    weight = np.where(nt > 0, weight, free)
+    between = (n1 >= 1) & (n2 >= 2) & (rng.random(nt.shape) < 0.5)
+    weight = np.where(between, n1 + 1 + np.floor(rng.random(nt.shape) * np.maximum(n2 - 1, 1)).astype(np.int64), weight)
+    assert ((weight > n1) & (weight < nt))[between].all()
+    colour = _consistent_colour(rng, _foreign_colour(rng, nt.shape), weight, nt, csum1 + csum2)
+    colour = np.where(between[..., None], _consistent_colour(rng, colour, weight, n1, csum1), colour)
+    return finish(keys, _arbitrary_tsdf(rng, nt.shape), weight, colour, max_weight=2 * CHUNK + 6)
+
+
+# the removals the de-integration tests plant for: name -> (camera, first frame, frames, colours, seed).  "tiny": 160 x 120, float32
+# depth, stride 4; "odd": 97 x 61, uint16 depth (scale 5000), stride 1.
+REMOVALS = {"single": ("tiny", 2, 1, "consistent", 5), "single odd": ("odd", 2, 1, "consistent", 6), "batch5": ("tiny", 10, 5, "consistent", 7),
+            "batch64": ("tiny", 0, 64, "consistent", 8), "foreign": ("tiny", 20, 5, "foreign", 9), "chunk70": ("tiny", 0, 70, "consistent", 10)}
+
+
+@functools.lru_cache(maxsize=None)
+def _removal_frames(camera, count):
+    from tests.deintegrate_reference import frame_samples
+    from tests.test_gpu_tsdf_edges import frames_of, intrinsic, odd_config
+
+    odd = camera == "odd"
+    s, frames = frames_of(odd_config(97, 61) if odd else "tiny_160x120_2cm", 0, count, depth_dtype="uint16" if odd else "float32")
+    scale, stride = (5000.0, 1) if odd else (1.0, 4)
+    K = intrinsic(s).as_array()
+    return s, frames, [frame_samples(VOX, TRUNC, d, c, K, T, scale, 4.0, stride) for d, c, T in frames], scale, stride
+
+
+@functools.lru_cache(maxsize=None)
+def removal_case(name):
+    """-> (camera, frames [(depth, colour, T_cw)], their FrameSamples, the planted states, depth_scale, stride) of REMOVALS[name].
+    Shared between the tests: nothing of it may be written to."""
+    camera, first, count, colours, seed = REMOVALS[name]
+    s, frames, samples, scale, stride = _removal_frames(camera, 70 if camera == "tiny" else first + count)
+    frames, samples = frames[first:first + count], samples[first:first + count]
+    # (foreign: a quarter of the units - the test extracts a mesh from arbitrary tsdf values)
+    states = (chunk_boundary_target(samples, seed) if count > CHUNK else
+              deintegration_target(samples, seed, colours, drop=0.75 if colours == "foreign" else 0.15))
+    return s, frames, samples, states, scale, stride
+
+
+# ---- prune targets -----------------------------------------------------------------------------------------------------------
+CORNER_WORDS = tuple((x * R + y) * R + z for x in (0, R - 1) for y in (0, R - 1) for z in (0, R - 1))
+ONE_VOXEL_WORDS = tuple(sorted(set(range(0, NV, 13)) | {0, NV - 1} | set(CORNER_WORDS)))  # 13 is coprime to 4096
+
+
+def library_word(i):
+    """Dump-order voxel index i = x * 256 + y * 16 + z -> the library's word z * 256 + x * 16 + y inside a plane of the unit."""
+    x, y, z = i >> 8, (i >> 4) & 15, i & 15
+    return z * 256 + x * 16 + y
+
+
+def one_voxel_keys(count, first=-150):
+    """`count` distinct unit keys on a line through negative and positive indices."""
+    j = np.arange(count, dtype=np.int64)
+    return np.stack([first + j, j % 5 - 2, 1 - j % 3], axis=1)
+
+
+def one_voxel_units(words=ONE_VOXEL_WORDS, keys=None):
+    """For each word index i (dump order) a unit whose only observed voxel is i.  -> (states, words in the states' key order)."""
+    keys = one_voxel_keys(len(words)) if keys is None else np.asarray(keys, np.int64).reshape(-1, 3)
+    assert len(keys) == len(words)
+    parts = [single_voxel(tuple(int(v) for v in key), (i >> 8, (i >> 4) & 15, i & 15), tsdf=((i % 9) - 4) / 4.0, weight=1 + i % 7,
+                          colour=(i % 256, (i * 7) % 256, (i * 31) % 256)) for key, i in zip(keys, words)]
+    states = finish(*(np.concatenate([p[k] for p in parts]) for k in range(4)))
+    order = np.lexsort((keys[:, 2], keys[:, 1], keys[:, 0]))
+    return states, np.asarray(words, np.int64)[order]
+
+
+def empty_units(keys):
+    """All-zero units: claimed, never updated."""
+    keys = np.asarray(keys, np.int64).reshape(-1, 3)
+    return finish(keys, np.zeros((len(keys), NV), np.float32), np.zeros((len(keys), NV), np.float32), np.zeros((len(keys), NV, 3)))

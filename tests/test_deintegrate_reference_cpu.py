@@ -1,5 +1,5 @@
 """CPU: the numpy restatement of TSDF de-integration (tests/deintegrate_reference.py) on hand-built volumes - the zero-weight
-reset, underflow, chunking at 64 frames and the tsdf error a removal leaves."""
+reset, underflow, the clamp of the colour sums, chunking at 64 frames and the tsdf error a removal leaves."""
 import numpy as np
 
 from tests.deintegrate_reference import MAX_FRAMES, FrameSamples, deintegrate_reference
@@ -52,6 +52,21 @@ def test_partial_removal_is_exact_on_weights_and_colour_sums():
     np.testing.assert_array_equal(c[0, 0], [150.0, 75.0, 37.5])  # (400 - 100) / 2, (200 - 50) / 2, (100 - 25) / 2
     assert t[0, 0] == np.float32((0.5 * 4.0 - (0.25 + -0.25)) / 2.0)
     assert stats == (2, 0, 2, 0)
+
+
+def test_colour_sums_are_clamped_when_a_frame_that_was_never_fused_is_removed():
+    # sums 30, 1500, 400 at weight 6; a foreign frame of colour (200, 0, 100) leaves weight 5 and
+    #   r: 30 - 200 < 0 -> 0 (the low end);  g: 1500 - 0 > 255 * 5 -> 1275 (the high end);  b: 400 - 100 = 300, inside
+    dump = one_unit(np.float32(0.5), 6, (5.0, 250.0, 400.0 / 6.0))
+    (_, t, w, c), stats = deintegrate_reference(dump, [sample(0.25, (200, 0, 100))])
+    assert w[0, 0] == 5.0 and stats == (1, 0, 1, 0)
+    np.testing.assert_array_equal(c[0, 0], [0.0, 255.0, 60.0])
+    assert t[0, 0] == np.float32((0.5 * 6.0 - 0.25) / 5.0)  # the tsdf rule is untouched by the clamp
+    # a removal of frames that WERE fused never reaches the clamp: the extreme bytes on both sides
+    dump = one_unit(np.float32(0.0), 3, (170.0, 85.0, 255.0))  # sums 510 = 255 + 255 + 0, 255 = 0 + 0 + 255, 765
+    (_, _, w, c), _ = deintegrate_reference(dump, [sample(0.0, (0, 255, 255))])
+    assert w[0, 0] == 2.0
+    np.testing.assert_array_equal(c[0, 0], [255.0, 0.0, 255.0])
 
 
 def test_underflow_leaves_the_voxel_unchanged_and_counts_it_once():

@@ -1,5 +1,6 @@
 """CPU: the planted voxel states of tests/planted_states.py and the conditions the GPU tests built on them rely on
-(tests/test_gpu_tsdf_merge_edges.py, tests/test_gpu_tsdf_raycast_edges.py).  No GPU.
+(tests/test_gpu_tsdf_merge_edges.py, tests/test_gpu_tsdf_raycast_edges.py, tests/test_gpu_tsdf_deintegrate_planted.py,
+tests/test_gpu_tsdf_prune_planted.py).  No GPU.
 
 The two restatements (tests/merge_reference.py, tests/raycast_reference.py) are run on every planted input and held to what can
 be known without them - exact permutations, the analytic depth and normal of the planted walls - before the GPU is held to them;
@@ -17,8 +18,10 @@ Measured when the file was written (voxel 0.02, sdf_trunc 0.08):
 import numpy as np
 import pytest
 
+from tests import deintegrate_reference as dr
 from tests import merge_reference as mr
 from tests import planted_states as ps
+from tests import prune_reference as pr
 from tests import raycast_reference as rr
 from tests.test_merge_reference_cpu import GENERIC, assert_is_permuted_source, fragile_share, observed_voxels, rigid, rigid_inverse
 
@@ -331,3 +334,90 @@ def test_generic_pose_sees_the_sparse_source():
     g = GENERIC_CAST
     out = rr.ray_cast(dump, ps.VOX, ps.TRUNC, g["intr"], look_at(g["eye"], g["target"]), g["height"], g["width"], 0.1, 3.0, g["threshold"])
     assert out["mask"].sum() == 1919
+
+
+# ---- de-integration and prune targets --------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(ps.REMOVALS))
+def test_deintegration_targets_hold_every_branch_inside_single_quads(name):
+    """The conditions tests/test_gpu_tsdf_deintegrate_planted.py relies on, from the builders and the restatement alone: >= 200
+    voxels in each branch of the removal rule, >= 50 quads (one lane's 16-byte access) that hold all three, >= 1 unit of the touch
+    sets absent; the restatement's stats follow from the class counts; voxels no frame samples come back untouched."""
+    s, frames, samples, states, scale, stride = ps.removal_case(name)
+    dump = ps.as_dump(states)
+    first = samples[:ps.CHUNK]
+    n, csum, missing = ps.sample_counts(dump[0], first)
+    under, fresh, rest = ps.removal_classes(dump[2], n)
+    quads = ps.quads_with_all_classes(under, fresh, rest)
+    print(f"{name}: {len(dump[0])} units, underflow {under.sum()}, fresh {fresh.sum()}, remaining {rest.sum()}, quads {quads}, missing {missing}")
+    assert min(under.sum(), fresh.sum(), rest.sum()) >= 200 and quads >= 50 and missing >= 1
+    assert dump[2].max() > 7 or len(samples) == 1
+    after, stats = dr.deintegrate_reference(dump, first)
+    assert stats == (sum(len(f.keys) for f in first), missing, int(n[fresh | rest].sum()), int(under.sum()))
+    same = (n == 0) | under
+    for a, b in zip(after[1:], dump[1:]):
+        assert np.array_equal(a[same], b[same])
+    assert np.all(after[2][fresh] == 0) and np.all(after[1][fresh] == 0) and np.all(after[3][fresh] == 0)
+    np.testing.assert_array_equal(after[2][rest], (dump[2].astype(np.int64) - n)[rest])
+    assert after[3].min() >= 0.0 and after[3].max() <= 255.0
+    low, high = ps.clamp_ends(dump, n, csum)
+    if ps.REMOVALS[name][3] == "foreign":
+        assert low >= 100 and high >= 100, (low, high)
+    elif len(samples) <= ps.CHUNK:
+        assert (low, high) == (0, 0)  # consistent colours: the clamp never acts, the sums are those of the frames that remain
+        left = np.rint(dump[3] * dump[2][..., None]).astype(np.int64) - csum
+        np.testing.assert_array_equal(np.rint(after[3] * after[2][..., None]).astype(np.int64)[rest], left[rest])
+
+
+def test_chunk_boundary_target_separates_the_per_chunk_decision_from_a_per_call_one():
+    s, frames, samples, states, scale, stride = ps.removal_case("chunk70")
+    assert len(samples) == 70
+    dump = ps.as_dump(states)
+    per_chunk, st_chunk = dr.deintegrate_reference(dump, samples)
+    per_call, st_call = dr.deintegrate_reference(dump, samples, max_frames=70)
+    differ = int((per_chunk[2] != per_call[2]).sum())
+    print(f"chunk70: {differ} voxels differ, stats per chunk {st_chunk}, per call {st_call}")
+    assert differ >= 200 and st_chunk[3] != st_call[3] and st_chunk[2] != st_call[2]
+    # where they differ the per-call decision left the voxel alone and the per-chunk one removed the first chunk's observations
+    n1 = ps.sample_counts(dump[0], samples[:ps.CHUNK])[0]
+    m = per_chunk[2] != per_call[2]
+    np.testing.assert_array_equal(per_call[2][m], dump[2][m])
+    np.testing.assert_array_equal(per_chunk[2][m], (dump[2].astype(np.int64) - n1)[m])
+
+
+def test_one_voxel_units_visit_every_lane_component_and_group_of_the_emptiness_reader():
+    """hv_tsdf_unit_has_weight reads the weight plane in 16 iterations of 64 lanes x 16 bytes, with an exit test per group of four
+    iterations: library word = ((iteration * 64 + lane) * 4 + component)."""
+    words = np.array(ps.ONE_VOXEL_WORDS)
+    assert 320 <= len(words) <= 340 and {0, ps.NV - 1} | set(ps.CORNER_WORDS) <= set(words.tolist())
+    lib = np.array([ps.library_word(int(i)) for i in words])
+    assert len(set(lib.tolist())) == len(words)
+    assert set(lib & 3) == set(range(4)) and set((lib >> 2) & 63) == set(range(64)) and set(lib >> 8) == set(range(16))
+    assert {(int(w) >> 10, int(w) & 3) for w in lib} == {(g, c) for g in range(4) for c in range(4)}
+    assert {(int(w) >> 10, (int(w) >> 2) & 63) for w in lib} == {(g, l) for g in range(4) for l in range(64)}
+    states, order = ps.one_voxel_units()
+    keys, tsdf, weight, colour = states
+    assert len(keys) == len(words) and sorted(order.tolist()) == sorted(words.tolist())
+    assert (np.diff(np.asarray(keys, np.int64) @ [1 << 40, 1 << 20, 1]) > 0).all() and keys[:, 0].min() < 0 < keys[:, 0].max()
+    assert ((weight > 0).sum(axis=1) == 1).all()
+    np.testing.assert_array_equal(np.argmax(weight, axis=1), order)
+    ref, stats = pr.prune_reference(ps.as_dump(states), True)
+    assert stats == (len(keys), 0, 0, len(keys))
+
+
+def test_empty_units_are_what_prune_releases():
+    keys = ps.one_voxel_keys(5, first=-2) + [0, 7, 0]
+    states = ps.empty_units(keys)
+    assert all(not np.any(x) for x in states[1:]) and len(states[0]) == 5
+    ref, stats = pr.prune_reference(ps.as_dump(states), True)
+    assert stats == (5, 0, 5, 0) and len(ref[0]) == 0
+    assert pr.prune_reference(ps.as_dump(states), False)[1] == (5, 0, 0, 5)
+
+
+def test_finish_admits_weights_up_to_the_exactness_limit():
+    w = np.float32(ps.MAX_WEIGHT)
+    c = np.arange(256, dtype=np.float32) * w
+    assert np.array_equal(c.astype(np.float64), np.arange(256) * float(w)) and float(c.max()) < 2.0 ** 24
+    keys, tsdf, weight, colour = ps.finish([(0, 0, 0)], np.full(ps.NV, 0.5), np.full(ps.NV, ps.MAX_WEIGHT), np.full((ps.NV, 3), 255), max_weight=ps.MAX_WEIGHT)
+    assert weight.max() == ps.MAX_WEIGHT
+    with pytest.raises(AssertionError):
+        ps.finish([(0, 0, 0)], np.zeros(ps.NV), np.full(ps.NV, 8), np.zeros((ps.NV, 3)))  # the default stays 7
