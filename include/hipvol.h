@@ -672,6 +672,86 @@ typedef struct hv_merge_stats {
 } hv_merge_stats;
 int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const double *T_dst_src /* [16] */, hv_merge_stats *stats /* may be NULL */);
 
+/* Map-to-map registration: refine the rigid transform p_dst = T p_src between two TSDF volumes on their signed distance fields
+ * (SDF-2-SDF, voxgraph's submap constraints), for maps whose frames are gone - the transform hv_tsdf_integrate_volume takes as
+ * given.  A REFINEMENT, not a global search: the field knows distances only inside the truncation band, so T_init must be good to
+ * roughly (1 - tsdf_band) * sdf_trunc.  This project's own contract.  Both volumes are only read.  All geometry float64, one IEEE
+ * operation per step in the order written, no contraction:
+ *   candidates  fixed for the call: every source voxel with (double)weight > weight_threshold and |(double)tsdf_s| <= tsdf_band (a
+ *             saturated voxel carries no distance), in pool order of the units and word order (z, x, y) inside a unit.  Its point
+ *             is the voxel centre x_a = ((double)i_a + 0.5) * voxel_length, i = 16 key + xyz.
+ *   anchor    cs_a = ((double)(kmin_a + kmax_a + 1) * 0.5) * (16.0 * voxel_length): the centre of the bounding box of the source's
+ *             unit keys (all units it holds), computed on the host; c_a = ((T_a0 cs_0 + T_a1 cs_1) + T_a2 cs_2) + T_a3 with T =
+ *             T_init.  State A (4x4) = identity at the start, kept on the device.  With R = T_init's rotation:
+ *             d_a = x_a - cs_a;  q_a = (R_a0 d_0 + R_a1 d_1) + R_a2 d_2   (= T_init x - c, taken as R (x - cs) so that two far-away
+ *             points are never subtracted);  y_a = ((A_a0 q_0 + A_a1 q_1) + A_a2 q_2) + A_a3;  p_a = c_a + y_a, the point in the
+ *             destination frame.  H and g are those of motions about c: they do not degrade far from the world origin.
+ *   sample    p is located in the destination lattice as hv_tsdf_integrate_volume locates a point in the source lattice:
+ *             g_a = p_a / voxel_length - 0.5, g0_a = floor(g_a), r_a = g_a - g0_a; some |g_a| >= 1e9 (or not finite): invalid.  The
+ *             eight voxels f0..f7 are g0 + {0,1}^3 in hv_tsdf_at's corner order ((0,0,0) (1,0,0) (1,1,0) (0,1,0) (0,0,1) (1,0,1)
+ *             (1,1,1) (0,1,1)).  VALID iff all eight exist (unit held, key in range) and have (double)weight > weight_threshold.
+ *             With u_a = 1 - r_a and the float32 values widened:
+ *               c00 = u2 f0 + r2 f4,  c01 = u2 f3 + r2 f7,  c10 = u2 f1 + r2 f5,  c11 = u2 f2 + r2 f6,
+ *               b0 = u1 c00 + r1 c01,  b1 = u1 c10 + r1 c11,  phi_d = u0 b0 + r0 b1      (the merge contract's trilinear expression)
+ *             and its analytic derivative (eight gathers per candidate, not hv_tsdf_extract_point_normals' 48):
+ *               dphi/dr0 = b1 - b0
+ *               dphi/dr1 = u0 (c01 - c00) + r0 (c11 - c10)
+ *               dphi/dr2 = u0 (u1 (f4 - f0) + r1 (f7 - f3)) + r0 (u1 (f5 - f1) + r1 (f6 - f2))
+ *             grad_a = (sdf_trunc / voxel_length) * dphi/dr_a, metres per metre.
+ *   residual  rho = sdf_trunc * (phi_d - (double)tsdf_s), metres.  INLIER iff the sample is valid and |rho| <= residual_trunc.
+ *             J = [y x grad, grad] (omega, t); Huber weight w = 1 if |rho| <= huber_delta else huber_delta / |rho|.
+ *             H = sum w J^T J (products (w J_a) J_b), g = sum w J^T rho ((w J_a) rho), e = sum rho^2 (unweighted), counts of
+ *             inliers and of candidates.
+ *   solve     as hv_tsdf_track: H xi = -g by Cholesky; DEGENERATE below HV_REGISTER_MIN_INLIERS inliers or at a pivot <=
+ *             HV_REGISTER_PIVOT_REL trace(H): A stays and the call ends with success = 0.  Otherwise A := exp(xi) A with exp(xi) =
+ *             [Rodrigues(omega), t]; the call ends when |omega| + |t| < HV_REGISTER_CONVERGED or after max_iterations
+ *             linearisations (1 .. 10000).
+ *   result    T_dst_src = Tr(c) A Tr(-c) T_init, evaluated as [R_A, (c + t_A) - R_A c] T_init (T_init itself, bit for bit, when A
+ *             never moved): pass it to hv_tsdf_integrate_volume.  Of the LAST linearisation: fitness = inliers / candidates,
+ *             inlier_rmse = sqrt(e / inliers) (0 if none), information = H (6x6, row-major, order (omega, t), motions about
+ *             anchor = c, which is returned: an edge of a submap pose graph).  success = the last step was not degenerate and had
+ *             >= HV_REGISTER_MIN_INLIERS inliers.  An empty src, an empty dst, no candidate or no overlap is not an error:
+ *             success = 0, T_dst_src = T_init.
+ * trace (may be NULL): one row of HV_REGISTER_TRACE_STRIDE doubles per linearisation run: {iteration, status (0 stepped, 1
+ * converged, 2 degenerate), inliers, candidates, e, A [16] (the state it linearised at), H [21] (upper triangle, row by row), g [6],
+ * xi [6]}; *trace_rows = rows written (at most trace_cap).
+ * No float atomics, a fixed reduction order (hv_tsdf_track's): two calls on the same two volumes are bitwise equal.  Both batch
+ * pipelines are drained and src's pending work is waited for, as hv_tsdf_integrate_volume does; the host reads the candidate count,
+ * then every iteration is queued at once on dst's stream - a step of a finished call returns on a device flag - and the host waits
+ * once for the result.  Device work: one workgroup per source unit counts, a scan, one workgroup per unit writes the 16-byte
+ * candidates {index, tsdf_s} in their fixed order (ballot prefix, no atomic append); per iteration one thread per candidate
+ * linearises (the iterations read the near-surface band only, not every allocated voxel) and one workgroup solves.  Extra device
+ * memory, freed before the call returns: 16 bytes per candidate, 8 bytes per source unit, 240 KiB of reduction slab, 432 bytes per
+ * iteration of trace and under 1 KiB of state.  Nothing of either volume is written, stamped, grown or claimed: dumps stay bit
+ * for bit, extraction caches stay valid.
+ * HV_ERR_MODE / HV_ERR_INVALID for the volumes and T_init exactly as hv_tsdf_integrate_volume (mode, sharding, dst == src, differing
+ * voxel_length / sdf_trunc / unit resolution / device, a T_init that is not finite, rigid or has a bad bottom row); HV_ERR_INVALID
+ * for max_iterations outside 1 .. 10000, a weight_threshold that is negative or not finite, tsdf_band outside (0, 1],
+ * residual_trunc or huber_delta not positive and finite; HV_ERR_CAPACITY when src's pool overflowed in an earlier call. */
+#define HV_REGISTER_MIN_INLIERS 6
+#define HV_REGISTER_PIVOT_REL 1e-10
+#define HV_REGISTER_CONVERGED 1e-6
+#define HV_REGISTER_TRACE_STRIDE 54
+typedef struct hv_register_params {
+    double weight_threshold; /* a voxel counts when its weight is > this (source candidates and destination samples) */
+    double tsdf_band;        /* candidates have |tsdf| <= this, in (0, 1] */
+    double residual_trunc;   /* metres; customary 0.5 sdf_trunc */
+    double huber_delta;      /* metres; customary 0.25 sdf_trunc */
+    int32_t max_iterations;
+    int32_t reserved;
+} hv_register_params;
+typedef struct hv_register_result {
+    double T_dst_src[16];
+    double information[36];
+    double anchor[3]; /* c: the point of the destination frame the motions (omega, t) of `information` turn about */
+    double fitness, inlier_rmse;
+    int64_t inliers, candidates;
+    int32_t iterations;
+    int32_t success;
+} hv_register_result;
+int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const double *T_init /* [16] */, const hv_register_params *params,
+                            hv_register_result *result, double *trace, int64_t trace_cap, int64_t *trace_rows);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

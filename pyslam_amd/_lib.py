@@ -113,6 +113,34 @@ class HvMergeStats(_c.Structure):
     ]
 
 
+HV_REGISTER_TRACE_STRIDE = 54
+
+
+class HvRegisterParams(_c.Structure):
+    _fields_ = [
+        ("weight_threshold", _f64),
+        ("tsdf_band", _f64),
+        ("residual_trunc", _f64),
+        ("huber_delta", _f64),
+        ("max_iterations", _i32),
+        ("reserved", _i32),
+    ]
+
+
+class HvRegisterResult(_c.Structure):
+    _fields_ = [
+        ("T_dst_src", _f64 * 16),
+        ("information", _f64 * 36),
+        ("anchor", _f64 * 3),
+        ("fitness", _f64),
+        ("inlier_rmse", _f64),
+        ("inliers", _i64),
+        ("candidates", _i64),
+        ("iterations", _i32),
+        ("success", _i32),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -200,6 +228,7 @@ SIGNATURES = {
                                          _c.POINTER(HvDeintegrateStats)]),
     "hv_tsdf_prune": (_i32, [_vp, _i32, _pi32, _pi32, _c.POINTER(HvPruneStats)]),
     "hv_tsdf_integrate_volume": (_i32, [_vp, _vp, _vp, _c.POINTER(HvMergeStats)]),
+    "hv_tsdf_register_volume": (_i32, [_vp, _vp, _vp, _c.POINTER(HvRegisterParams), _c.POINTER(HvRegisterResult), _vp, _i64, _pi64]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),

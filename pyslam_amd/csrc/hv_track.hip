@@ -7,7 +7,8 @@
 // model, k_tsdf_ray_cast through hv_ray_cast_launch), then for every iteration of every level a linearise launch (one thread per
 // source pixel, grid-stride; wave butterfly + LDS reduction of the 30 sums in double into one slab row per workgroup) and a
 // one-workgroup solve launch (the slab summed in a fixed order, Cholesky, A update, trace row, level flag).  A step of a level that
-// has converged or gone degenerate reads the flag and returns.  No float atomics anywhere: results are bitwise reproducible.
+// has converged or gone degenerate reads the flag and returns.  No float atomics anywhere: results are bitwise reproducible.  The
+// reduction, the slab sum and the 6 x 6 step are hv_gauss_newton.h's, shared with map-to-map registration (hv_register.hip).
 //
 // The hybrid call runs the same schedule with the same kernels, instantiated with the hybrid part that sits under `if constexpr`:
 // k_track_source<true> / k_track_down<true> also produce the source intensity of the level, the casts also render colour, one
@@ -18,6 +19,7 @@
 #include <cmath>
 
 #include "hv_common.h"
+#include "hv_gauss_newton.h"
 
 namespace {
 
@@ -25,8 +27,8 @@ constexpr int TK_NACC = 30;          // H upper triangle [21], g [6], e, inliers
 constexpr int TK_NACC_COLOR = 32;    // ... photometric inliers, sum r_I^2
 constexpr int TK_BLOCK = 256;        // linearise workgroup (4 waves)
 constexpr int TK_MAX_BLOCKS = 1024;  // linearise grid cap = slab rows
-constexpr int TK_SUM_PARTS = 32;     // solve workgroup: 32 parts x 32 components
-constexpr int TK_SUM_THREADS = TK_SUM_PARTS * 32;
+constexpr int TK_SUM_PARTS = HV_GN_SUM_PARTS;
+constexpr int TK_SUM_THREADS = HV_GN_SUM_THREADS;
 
 template <int NACC>
 struct TkStateT {
@@ -229,19 +231,7 @@ __global__ __launch_bounds__(TK_BLOCK) void k_track_linearise(TkLevel L, TkParam
     }
 
     __shared__ double red[TK_BLOCK / 64][NACC];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NACC; ++k) {
-        const double s = hv_wave_sum(acc[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        double s = red[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < TK_BLOCK / 64; ++w) s += red[w][threadIdx.x];
-        slab[(int64_t)blockIdx.x * NACC + threadIdx.x] = s;
-    }
+    hv_gn_block_reduce<NACC, TK_BLOCK>(acc, red, slab + (int64_t)blockIdx.x * NACC);
 }
 
 // one step's solve: the slab summed in a fixed order, then (thread 0) Cholesky, exp, A update, trace row, flag
@@ -253,102 +243,14 @@ __global__ __launch_bounds__(TK_SUM_THREADS) void k_track_solve(TkStateT<NACC> *
     if (st->done[level] != 0) return;
     __shared__ double part[TK_SUM_PARTS][32];
     __shared__ double tot[NACC];
-    const int c = threadIdx.x & 31, k = threadIdx.x >> 5;
-    double s = 0.0;
-    if (c < NACC)
-        for (int r = k; r < rows; r += TK_SUM_PARTS) s += slab[(int64_t)r * NACC + c];
-    part[k][c] = s;
-    __syncthreads();
-    if (threadIdx.x < NACC) {
-        double t = part[0][threadIdx.x];
-        for (int q = 1; q < TK_SUM_PARTS; ++q) t += part[q][threadIdx.x];
-        tot[threadIdx.x] = t;
-        if (level == 0) st->last[threadIdx.x] = t;
-    }
+    hv_gn_slab_sum<NACC>(slab, rows, part, tot);
+    if (threadIdx.x < NACC && level == 0) st->last[threadIdx.x] = tot[threadIdx.x];
     __syncthreads();
     if (threadIdx.x != 0) return;
 
-    // (every loop below has constant bounds and is unrolled: the 6 x 6 arrays stay in registers)
-    double H[6][6], g[6];
-    {
-        int q = 0;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) H[a][b] = H[b][a] = tot[q++];
-#pragma unroll
-        for (int a = 0; a < 6; ++a) g[a] = tot[21 + a];
-    }
+    double A0[16], g[6], xi[6];
+    const int status = hv_gn_step(tot, (double)HV_TRACK_MIN_INLIERS, HV_TRACK_PIVOT_REL, HV_TRACK_CONVERGED, st->A, A0, g, xi);
     const double inliers = tot[28];
-    double trH = 0.0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a) trH += H[a][a];
-    // Cholesky H = L L^T, then L y = -g, L^T xi = y (the values of a degenerate factorisation are not used)
-    bool degenerate = inliers < (double)HV_TRACK_MIN_INLIERS;
-    double Lm[6][6], xi[6];
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        double d = H[j][j];
-#pragma unroll
-        for (int q = 0; q < j; ++q) d -= Lm[j][q] * Lm[j][q];
-        if (!(d > HV_TRACK_PIVOT_REL * trH)) degenerate = true;
-        Lm[j][j] = sqrt(d);
-#pragma unroll
-        for (int i = j + 1; i < 6; ++i) {
-            double e = H[i][j];
-#pragma unroll
-            for (int q = 0; q < j; ++q) e -= Lm[i][q] * Lm[j][q];
-            Lm[i][j] = e / Lm[j][j];
-        }
-    }
-    double A0[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) A0[i] = st->A[i];
-    int status = degenerate ? 2 : 0;
-    {
-        double y[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            double e = -g[i];
-#pragma unroll
-            for (int q = 0; q < i; ++q) e -= Lm[i][q] * y[q];
-            y[i] = e / Lm[i][i];
-        }
-#pragma unroll
-        for (int i = 5; i >= 0; --i) {
-            double e = y[i];
-#pragma unroll
-            for (int q = i + 1; q < 6; ++q) e -= Lm[q][i] * xi[q];
-            xi[i] = e / Lm[i][i];
-        }
-    }
-    if (degenerate) {
-#pragma unroll
-        for (int i = 0; i < 6; ++i) xi[i] = 0.0;
-    } else {
-        // exp(xi) = [Rodrigues(omega), t]; A := exp(xi) A
-        const double w0 = xi[0], w1 = xi[1], w2 = xi[2];
-        const double th = sqrt(w0 * w0 + w1 * w1 + w2 * w2);
-        const double sa = th < 1e-8 ? 1.0 : sin(th) / th, sb = th < 1e-8 ? 0.5 : (1.0 - cos(th)) / (th * th);
-        const double K[9] = {0.0, -w2, w1, w2, 0.0, -w0, -w1, w0, 0.0};
-        double E[12];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                const double kk = K[i * 3] * K[j] + K[i * 3 + 1] * K[3 + j] + K[i * 3 + 2] * K[6 + j];
-                E[i * 4 + j] = (i == j ? 1.0 : 0.0) + sa * K[i * 3 + j] + sb * kk;
-            }
-            E[i * 4 + 3] = xi[3 + i];
-        }
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                st->A[i * 4 + j] = E[i * 4] * A0[j] + E[i * 4 + 1] * A0[4 + j] + E[i * 4 + 2] * A0[8 + j] + E[i * 4 + 3] * A0[12 + j];
-        const double tn = sqrt(xi[3] * xi[3] + xi[4] * xi[4] + xi[5] * xi[5]);
-        if (th + tn < HV_TRACK_CONVERGED) status = 1;
-    }
     const int row = st->rows;
     if (trace != nullptr && row < trace_cap) {
         double *o = trace + (int64_t)row * STRIDE;

@@ -136,6 +136,31 @@ class OdometryResult:
                 f"iterations={self.iterations})")
 
 
+class RegistrationResult:
+    """What ScalableTSDFVolume.register_volume returns (hv_register_result): transformation 4x4 float64, the refined T_dst_src
+    (p_dst = T p_src) - pass it straight to integrate_volume; of the last linearisation: fitness = inliers / candidates,
+    inlier_rmse (metres, unweighted SDF residual of the inliers), information 6x6 float64 (its Gauss-Newton matrix H, order
+    (omega, t), motions about `anchor`, a point [3] of the destination frame: an edge of a submap pose graph), inliers and
+    candidates; success; iterations = linearisations run; trace = None, or one dict per linearisation (iteration, status, inliers,
+    candidates, sq_error, A 4x4, H 6x6, g 6, xi 6) when asked for."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, information, success, iterations, inliers, candidates, anchor, trace=None):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.information = information
+        self.success = success
+        self.iterations = iterations
+        self.inliers = inliers
+        self.candidates = candidates
+        self.anchor = anchor
+        self.trace = trace
+
+    def __repr__(self):
+        return (f"RegistrationResult(success={self.success}, fitness={self.fitness:.4f}, inlier_rmse={self.inlier_rmse:.6f}, "
+                f"iterations={self.iterations})")
+
+
 class _Stats:
     """Base of the *Stats results below: integer fields, named (and ordered) by the subclass's __slots__, each defaulting to 0."""
 
@@ -227,6 +252,18 @@ def _trace_rows(rows):
                     "sq_error": float(r[5]), "A": r[6:22].reshape(4, 4).copy(), "H": H, "g": r[43:49].copy(), "xi": r[49:55].copy()})
         if len(r) > L.HV_TRACK_TRACE_STRIDE:  # a hybrid call's row
             out[-1].update(photometric_inliers=int(r[56]), sq_intensity_error=float(r[57]))
+    return out
+
+
+def _register_trace_rows(rows):
+    out = []
+    iu = np.triu_indices(6)
+    for r in rows:
+        H = np.zeros((6, 6))
+        H[iu] = r[21:42]
+        H = H + np.triu(H, 1).T
+        out.append({"iteration": int(r[0]), "status": int(r[1]), "inliers": int(r[2]), "candidates": int(r[3]), "sq_error": float(r[4]),
+                    "A": r[5:21].reshape(4, 4).copy(), "H": H, "g": r[42:48].copy(), "xi": r[48:54].copy()})
     return out
 
 
@@ -1243,6 +1280,40 @@ class ScalableTSDFVolume(_Volume):
         st = L.HvMergeStats()
         L.check(self._lib.hv_tsdf_integrate_volume(self._h, source._h, L.ptr(T), ctypes.byref(st)))
         return MergeStats(st.units_source, st.units_claimed, st.voxels_updated, st.voxels_trilinear, st.voxels_nearest)
+
+    def register_volume(self, source, init=None, max_iterations=30, weight_threshold=3.0, tsdf_band=0.5, residual_trunc=None,
+                        huber_delta=None, trace=False):
+        """Align another TSDF volume to this one on the two signed distance fields (include/hipvol.h, hv_tsdf_register_volume): ->
+        RegistrationResult whose transformation is the refined T_self_source (p_self = T p_source), ready for integrate_volume.
+        init: the guess, a rigid float64 [4,4] (default: identity), checked as integrate_volume checks its transform.  A REFINEMENT,
+        not a global search: the fields know distances only inside the truncation band, so init must be good to roughly
+        (1 - tsdf_band) * sdf_trunc.  Source voxels with weight > weight_threshold and |tsdf| <= tsdf_band are sampled in this volume
+        (all eight voxels around them observed above the same threshold); residuals beyond residual_trunc (default 0.5 sdf_trunc)
+        are outliers, beyond huber_delta (default 0.25 sdf_trunc) down-weighted.  Both volumes are only read and must agree in
+        voxel_length, sdf_trunc and unit resolution.  Empty maps or no overlap: success False, transformation == init.  Waits for
+        the GPU.  trace=True: the per-linearisation record (tests)."""
+        if getattr(source, "_h", None) is None:
+            raise TypeError("register_volume: source must be a volume")
+        T = np.eye(4) if init is None else np.asarray(init, dtype=np.float64)
+        if T.shape != (4, 4):
+            raise ValueError("register_volume: init must be a 4x4 matrix")
+        T = np.ascontiguousarray(T, dtype=np.float64)
+        prm = L.HvRegisterParams()
+        prm.weight_threshold, prm.tsdf_band = float(weight_threshold), float(tsdf_band)
+        sdf_trunc = float(getattr(self, "sdf_trunc", 0.0))  # (a volume without one is refused by the library for its mode)
+        prm.residual_trunc = 0.5 * sdf_trunc if residual_trunc is None else float(residual_trunc)
+        prm.huber_delta = 0.25 * sdf_trunc if huber_delta is None else float(huber_delta)
+        prm.max_iterations = int(max_iterations)
+        res = L.HvRegisterResult()
+        steps = max(int(max_iterations), 1)
+        rows = np.zeros((steps, L.HV_REGISTER_TRACE_STRIDE), np.float64) if trace else None
+        n_rows = ctypes.c_int64()
+        L.check(self._lib.hv_tsdf_register_volume(self._h, source._h, L.ptr(T), ctypes.byref(prm), ctypes.byref(res), L.ptr(rows),
+                                                  steps if trace else 0, ctypes.byref(n_rows)))
+        return RegistrationResult(np.array(res.T_dst_src, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
+                                  np.array(res.information, np.float64).reshape(6, 6), bool(res.success), int(res.iterations),
+                                  int(res.inliers), int(res.candidates), np.array(res.anchor, np.float64),
+                                  _register_trace_rows(rows[:n_rows.value]) if trace else None)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
