@@ -769,6 +769,77 @@ int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, cons
 /* All allocated unit keys (unsorted) for the key all-gather; keys may be NULL. */
 int hv_tsdf_unit_keys(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n);
 
+/* Packed maps: a compact, BIT-EXACT form of a TSDF map, made and consumed on the GPU - for keeping a map across sessions, handing it
+ * to another process or GPU, checkpointing it before a correction.  This project's own format; this comment is its contract.
+ * One flat little-endian byte buffer.  Every section starts on a 64-byte boundary, padding bytes are zero, and the buffer ends on
+ * one: total_bytes = the end of the last section rounded up to 64.
+ *   header, 128 bytes
+ *     off  type        field
+ *       0  8 bytes     magic "HVTSDFPK"
+ *       8  uint32      version = HV_PACK_VERSION (1)
+ *      12  uint32      header_bytes = 128
+ *      16  float64     voxel_length
+ *      24  float64     sdf_trunc
+ *      32  int32       resolution = 16
+ *      36  int32       reserved = 0
+ *      40  int64       units  U
+ *      48  int64       voxels N (stored voxel records)
+ *      56  int64       total_bytes
+ *      64  8 x uint64  byte offsets of the eight sections below, in this order
+ *   keys     int32  [U,3]    unit indices, strictly ascending by (x, then y, then z) - the order of hv_tsdf_dump: the same map gives
+ *                            the same bytes whatever its pool order
+ *   offsets  uint64 [U+1]    offsets[0] = 0, offsets[U] = N; unit u's records are [offsets[u], offsets[u+1])
+ *   masks    uint32 [U,128]  bit (k & 31) of word (k >> 5) is set when voxel word k of the unit is STORED; k = z * 256 + x * 16 + y,
+ *                            the library's voxel word (the order hv_tsdf_export_numerators exposes)
+ *   tsdf     float32 [N]     records, unit after unit, within a unit by ascending k
+ *   weight   uint32 [N]      same order
+ *   sum_r, sum_g, sum_b  uint32 [N] each, same order
+ * A voxel is STORED when any of its five 32-bit words is non-zero as a bit pattern (a tsdf of -0.0 counts, and so does a voxel of
+ * weight 0 that still carries a colour sum): the round trip is bit-exact without relying on "weight 0 implies the fresh state".
+ * EVERY allocated unit is stored, all-zero ones included (count 0, mask 0): hv_num_blocks and hv_tsdf_unit_keys survive the trip
+ * (hv_tsdf_prune first drops empty units).  NOT stored, NOT restored: rectify maps, colour order, tile and owner settings, pool
+ * size - settings of a volume, not content of a map.
+ *   hv_tsdf_packed_check  host only, no GPU.  Checks, in this order, and names the first rule that fails (HV_ERR_INVALID): at least
+ *              128 bytes; magic; version; header_bytes; resolution == 16; units, voxels >= 0 and no more than the buffer could hold;
+ *              total_bytes == bytes; every section offset 64-byte aligned; every section behind the header and inside the buffer
+ *              with the size U and N imply; no two sections overlap; keys in the library's range [-2^20, 2^20) and strictly
+ *              ascending; offsets[0] == 0, offsets non-decreasing, offsets[U] == N; offsets[u+1] - offsets[u] == popcount(masks[u]).
+ *              Fills *out (may be NULL) with the header fields once the header rules hold.
+ *   hv_tsdf_pack_size     waits; info = {U, N, exact buffer size}.
+ *   hv_tsdf_pack          dst (cap bytes) at loc = HV_HOST or HV_DEVICE (the volume's GPU).  cap too small: HV_ERR_CAPACITY, info
+ *              filled in, nothing written.  Only READS the volume: dumps, extraction caches, hv_tsdf_dirty_keys and hv_tsdf_touched
+ *              are what they were.  An empty volume packs to a valid buffer with U = N = 0.  Device work: one workgroup per unit
+ *              reads the five planes in word order and writes the unit's 128 mask words (a wave's ballot = two of them) and its
+ *              count; a scan of the counts; one workgroup per unit ranks each stored voxel by the popcount of the mask bits below it
+ *              and writes the five record streams.  The key order is a host sort of the unit keys, as hv_tsdf_dump's.
+ *   hv_tsdf_unpack        src (bytes) at loc.  Runs hv_tsdf_packed_check BEFORE it launches anything - on a host buffer itself; of a
+ *              device buffer it copies the header, then the keys / offsets / masks sections (about 532 bytes per unit, never the
+ *              records) to the host - so nothing a caller passes reaches a kernel unvalidated and the kernels cannot index outside
+ *              the buffer.  Requires a TSDF volume with hv_num_blocks == 0 whose voxel_length and sdf_trunc are BITWISE equal to the
+ *              header's (merging a packed map into a non-empty volume is hv_tsdf_integrate_volume's job, after unpacking into a
+ *              fresh volume).  Then: the keys are claimed and the claims verified (a pool that is too small grows before anything is
+ *              written, or the call fails with HV_ERR_CAPACITY); one workgroup per unit writes ALL 4096 voxels of all five planes,
+ *              the record where the bit is set and zero where it is not; every unpacked unit is stamped with one new frame id
+ *              (hv_tsdf_dirty_keys lists them, incremental extraction sees them; hv_tsdf_touched lists nothing); the content and
+ *              extraction versions are bumped and the occupancy is published, as hv_tsdf_import_numerators does.
+ *              On ANY error the volume is unchanged.
+ * Both hv_tsdf_pack and hv_tsdf_unpack drain the batch pipeline and wait for the GPU; HV_ERR_MODE for a non-TSDF volume and for a
+ * tile- or owner-sharded one (it holds partial sums, or a part of the map's units), as hv_tsdf_integrate_volume. */
+#define HV_PACK_VERSION 1
+#define HV_PACK_HEADER_BYTES 128
+typedef struct hv_pack_info {
+    int64_t units, voxels, bytes;
+} hv_pack_info;
+typedef struct hv_packed_header {
+    double voxel_length, sdf_trunc;
+    int32_t resolution, version;
+    int64_t units, voxels, bytes;
+} hv_packed_header;
+int hv_tsdf_pack_size(hv_volume *v, hv_pack_info *info);
+int hv_tsdf_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_pack_info *info);
+int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv_pack_info *info);
+int hv_tsdf_packed_check(const void *host_src, int64_t bytes, hv_packed_header *out);
+
 /* ---- halo merge of image-tile-sharded volumes (SURVEY 8b `hv_merge_halo`, 8e; north-star "RCCL all-reduce of
  * overlapping-block TSDF/weight").  pySLAM has no multi-GPU path (no NCCL/MPI/torch.distributed call anywhere in the
  * reference): these are new.  With hv_tsdf_set_tile each GPU fuses the voxels that project into its image tile, so units

@@ -141,6 +141,26 @@ class HvRegisterResult(_c.Structure):
     ]
 
 
+HV_PACK_VERSION = 1
+HV_PACK_HEADER_BYTES = 128
+
+
+class HvPackInfo(_c.Structure):
+    _fields_ = [("units", _i64), ("voxels", _i64), ("bytes", _i64)]
+
+
+class HvPackedHeader(_c.Structure):
+    _fields_ = [
+        ("voxel_length", _f64),
+        ("sdf_trunc", _f64),
+        ("resolution", _i32),
+        ("version", _i32),
+        ("units", _i64),
+        ("voxels", _i64),
+        ("bytes", _i64),
+    ]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -236,6 +256,10 @@ SIGNATURES = {
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),
     "hv_tsdf_import_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),
     "hv_tsdf_unit_keys": (_i32, [_vp, _vp, _i64, _pi64]),
+    "hv_tsdf_pack_size": (_i32, [_vp, _c.POINTER(HvPackInfo)]),
+    "hv_tsdf_pack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvPackInfo)]),
+    "hv_tsdf_unpack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvPackInfo)]),
+    "hv_tsdf_packed_check": (_i32, [_vp, _i64, _c.POINTER(HvPackedHeader)]),
     "hv_tsdf_dirty_keys": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_mark_merged": (_i32, [_vp]),
     "hv_set_owner": (_i32, [_vp, _i32, _i32]),

@@ -219,6 +219,11 @@ __global__ void k_tsdf_halo_unpack(HvTable table, char *__restrict__ pool, const
     ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word] = b;
 }
 
+// the claim pass of the calls that are handed unit keys (hv_tsdf_import_numerators here, hv_tsdf_unpack in hv_pack.hip)
+void hv_launch_tsdf_import_claim(hv_volume *v, const int32_t *d_keys, int64_t k) {
+    hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table, d_keys, k);
+}
+
 extern "C" {
 
 int hv_merge_halo_lists_device(hv_volume *v, int64_t *d_dirty_keys, int64_t dirty_cap, int64_t *d_held_keys, int64_t held_cap, int64_t *n_dirty,
@@ -366,8 +371,7 @@ int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, cons
     rc = hv_capacity_gate(v, &checked);
     if (rc != HV_OK) return rc;
     for (int attempt = 0;; ++attempt) {
-        hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                           (const int32_t *)d_keys, k);
+        hv_launch_tsdf_import_claim(v, (const int32_t *)d_keys, k);
         rc = hv_claims_fit(v);
         if (rc == HV_OK) break;
         if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;

@@ -212,6 +212,28 @@ class MergeStats(_Stats):
     __slots__ = ("units_source", "units_claimed", "voxels_updated", "voxels_trilinear", "voxels_nearest")
 
 
+class PackStats(_Stats):
+    """What ScalableTSDFVolume.unpack / save return (hv_pack_info): units = units of the packed map, all-zero ones included;
+    voxels = stored voxel records (a voxel is stored when any of its five words is non-zero); bytes = size of the packed buffer."""
+
+    __slots__ = ("units", "voxels", "bytes")
+
+
+def _packed_operand(buf):
+    """A packed map as the C ABI takes it: numpy array, bytes-like object or torch tensor (either device) -> contiguous 1-D uint8,
+    numpy for host memory, torch for a GPU."""
+    if hasattr(buf, "is_cuda"):
+        import torch
+
+        if buf.dtype != torch.uint8 or buf.dim() != 1:
+            raise ValueError(f"a packed map is a 1-D uint8 buffer, got {buf.dtype} with shape {tuple(buf.shape)}")
+        return buf.contiguous() if buf.is_cuda else buf.contiguous().numpy()
+    a = buf if isinstance(buf, np.ndarray) else np.frombuffer(buf, dtype=np.uint8)
+    if a.dtype != np.uint8 or a.ndim != 1:
+        raise ValueError(f"a packed map is a 1-D uint8 buffer, got {a.dtype} with shape {a.shape}")
+    return np.ascontiguousarray(a)
+
+
 _UNIT_KEY_BIAS = 1 << 20  # the library packs a unit index into 21 bits per axis: [-2^20, 2^20)
 
 
@@ -1613,3 +1635,103 @@ class ScalableTSDFVolume(_Volume):
     def import_numerators(self, keys, payload):
         keys = np.ascontiguousarray(keys, dtype=np.int32)
         L.check(self._lib.hv_tsdf_import_numerators(self._h, L.ptr(keys), keys.shape[0], L.ptr(payload), L.location(payload)))
+
+    # -- packed maps: keeping and moving a map (include/hipvol.h "Packed maps"; hv_pack.hip) ---------------------------------------
+    def _pack(self, device):
+        info = L.HvPackInfo()
+        L.check(self._lib.hv_tsdf_pack_size(self._h, ctypes.byref(info)))
+        if device:
+            import torch
+
+            out = torch.empty(info.bytes, dtype=torch.uint8, device=torch.device("cuda", int(self._cfg.device)))
+        else:
+            out = _result_array((info.bytes,), np.uint8)
+        ts = self._torch_in(out)
+        L.check(self._lib.hv_tsdf_pack(self._h, L.ptr(out), info.bytes, L.location(out), ctypes.byref(info)))
+        if device:
+            self._torch_out(ts, out.device)
+        return out, PackStats(info.units, info.voxels, info.bytes)
+
+    def pack(self, device=False):
+        """The map as one packed buffer, bit for bit (include/hipvol.h "Packed maps"): every allocated unit, and of each the voxels
+        that hold anything.  -> 1-D uint8, a numpy array (page-locked like the extraction results), or with device=True a torch CUDA
+        tensor on the volume's GPU (nothing crosses PCIe: for handing the map to another rank).  Only reads the volume; waits for
+        the GPU.  Settings of the volume (rectify maps, colour order, sharding, pool size) are not part of a map."""
+        return self._pack(device)[0]
+
+    def unpack(self, buf):
+        """Fill this EMPTY volume (num_blocks() == 0, same voxel_length and sdf_trunc as the packed map, bit for bit) from a packed
+        buffer: numpy, bytes-like or a torch uint8 tensor on either device.  The buffer is validated on the host before a kernel
+        sees it; a corrupt or foreign buffer, a non-empty or sharded volume raise HipVolError with the library's message and leave
+        the volume unchanged.  Afterwards the volume behaves, call for call, like the one that was packed; every unit counts as
+        dirty (dirty_keys()).  To merge a packed map into a map that already holds something, unpack it into a fresh volume and
+        integrate_volume that.  Waits for the GPU and returns PackStats."""
+        op = _packed_operand(buf)
+        info = L.HvPackInfo()
+        ts = self._torch_in(op)
+        L.check(self._lib.hv_tsdf_unpack(self._h, L.ptr(op), int(op.numel() if hasattr(op, "numel") else op.size), L.location(op),
+                                         ctypes.byref(info)))
+        if ts is not None:
+            self._torch_out(ts, op.device)
+        return PackStats(info.units, info.voxels, info.bytes)
+
+    def save(self, path):
+        """pack() into the file `path`: written to a temporary file in the same directory, then moved into place (os.replace), so
+        a reader never sees half a map.  -> PackStats."""
+        import os
+        import tempfile
+
+        buf, stats = self._pack(False)
+        path = os.fspath(path)
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                f.write(memoryview(buf))
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return stats
+
+    @staticmethod
+    def _read_packed(path):
+        import os
+
+        size = os.path.getsize(path)
+        buf = _result_array((size,), np.uint8)  # page-locked when large: the upload is one DMA
+        with open(path, "rb") as f:
+            got = f.readinto(memoryview(buf))
+        if got != size:
+            raise ValueError(f"{path}: read {got} of {size} bytes")
+        return buf
+
+    @classmethod
+    def load(cls, path, device=0, max_blocks=None):
+        """A new volume holding the map save() wrote to `path`: voxel_length and sdf_trunc from the file's header, the pool sized
+        max_blocks or max(1024, 2 * units) so that the first integrate() after a load does not have to grow it."""
+        buf = cls._read_packed(path)
+        hdr = cls.packed_info(buf)
+        vol = cls(hdr["voxel_length"], hdr["sdf_trunc"], device=device, max_blocks=max_blocks or max(1024, 2 * hdr["units"]))
+        vol.unpack(buf)
+        return vol
+
+    @staticmethod
+    def packed_info(path_or_buffer):
+        """The header of a packed map - {voxel_length, sdf_trunc, resolution, version, units, voxels, bytes} - after the library's
+        validator (hv_tsdf_packed_check) has passed the WHOLE buffer: a file path, or a buffer as unpack() takes it.  Needs no GPU.
+        ValueError with the validator's message, which names the first rule that failed."""
+        import os
+
+        if isinstance(path_or_buffer, (str, os.PathLike)):
+            op = np.fromfile(path_or_buffer, dtype=np.uint8)
+        else:
+            op = _packed_operand(path_or_buffer)
+            if hasattr(op, "is_cuda"):
+                op = op.cpu().numpy()
+        lib = L.load()
+        hdr = L.HvPackedHeader()
+        if lib.hv_tsdf_packed_check(L.ptr(op), int(op.size), ctypes.byref(hdr)) != L.HV_OK:
+            raise ValueError((lib.hv_last_error() or b"hv_tsdf_packed_check failed").decode())
+        return {"voxel_length": hdr.voxel_length, "sdf_trunc": hdr.sdf_trunc, "resolution": hdr.resolution, "version": hdr.version,
+                "units": hdr.units, "voxels": hdr.voxels, "bytes": hdr.bytes}
