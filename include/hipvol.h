@@ -752,6 +752,88 @@ typedef struct hv_register_result {
 int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const double *T_init /* [16] */, const hv_register_params *params,
                             hv_register_result *result, double *trace, int64_t trace_cap, int64_t *trace_rows);
 
+/* Point queries: what does the map hold at given points - signed distance, its gradient, colour and observation count - for
+ * collision and clearance checks, for external optimisers, and as the core of hv_tsdf_check_frame below.  This project's own
+ * contract, not Open3D-pinned.  The volume is only read.  points [n,3] of point_dtype (HV_F32 | HV_F64: the values
+ * hv_integrate_points_semantic's point_dtype takes; float32 points are widened first) at loc.  For every point p all geometry is
+ * float64, one IEEE operation per step in the order written, no contraction:
+ *   locate    as hv_tsdf_integrate_volume locates a point in the source lattice: g_a = p_a / voxel_length - 0.5, g0_a = floor(g_a),
+ *             r_a = g_a - g0_a.  The eight voxels are g0 + {0,1}^3 in hv_tsdf_at's corner order ((0,0,0) (1,0,0) (1,1,0) (0,1,0)
+ *             (0,0,1) (1,0,1) (1,1,1) (0,1,1)); the NEAREST is g0_a + (r_a >= 0.5 ? 1 : 0) per axis; the unit of a voxel is its
+ *             index >> 4.  A voxel is OBSERVED when its unit is held, its key is in range and (double)weight > weight_threshold.
+ *   status    HV_SAMPLE_OUTSIDE     the point is not finite, some |g_a| >= 1e9, or the nearest voxel's unit is not held (or its key is
+ *                                   out of range)
+ *             HV_SAMPLE_UNOBSERVED  the nearest voxel's unit is held, the nearest voxel is not observed
+ *             HV_SAMPLE_NEAREST     the nearest voxel is observed, not all eight are
+ *             HV_SAMPLE_TRILINEAR   all eight are observed
+ *   value     TRILINEAR: with u_a = 1 - r_a and the eight float32 tsdf values f0..f7 widened,
+ *               c00 = u2 f0 + r2 f4,  c01 = u2 f3 + r2 f7,  c10 = u2 f1 + r2 f5,  c11 = u2 f2 + r2 f6,
+ *               b0 = u1 c00 + r1 c01,  b1 = u1 c10 + r1 c11,  phi = u0 b0 + r0 b1     (the merge contract's trilinear expression)
+ *               dphi/dr0 = b1 - b0
+ *               dphi/dr1 = u0 (c01 - c00) + r0 (c11 - c10)
+ *               dphi/dr2 = u0 (u1 (f4 - f0) + r1 (f7 - f3)) + r0 (u1 (f5 - f1) + r1 (f6 - f2))   (the registration contract's derivative)
+ *             sdf = (float)(sdf_trunc * phi), metres; gradient_a = (float)((sdf_trunc / voxel_length) * dphi/dr_a), metres per metre,
+ *             not normalised; color_c = (float)(tri(mean_c) / 255.0), tri = the expression of phi on the eight mean colours
+ *             mean = (double)sum / (double)weight.
+ *             NEAREST: sdf = (float)(sdf_trunc * (double)tsdf) of the nearest voxel, gradient 0, color_c = (float)(mean_c / 255.0) of
+ *             the nearest voxel.  In both cases weight = (float) the nearest voxel's weight.
+ *             OUTSIDE and UNOBSERVED: every output 0.
+ * Outputs: sdf [n], gradient [n,3], color [n,3], weight [n] f32, status [n] u8; any may be NULL, and a NULL output is not computed - a
+ * call that asks for neither colour nor gradient reads the weight and tsdf planes only.  loc = HV_DEVICE: device pointers, the call is
+ * queued on the volume's stream and returns without waiting; HV_HOST: staged by the library and copied back before returning, as
+ * hv_tsdf_ray_cast.  Reads only: no growth, no stamp, no claim - dumps stay bit for bit, extraction caches stay valid; the batch
+ * pipeline is drained first, as hv_tsdf_ray_cast does.  Every point is written by one lane from values only that lane computes: two
+ * calls give bitwise equal outputs, whatever the pool order.
+ * HV_ERR_MODE for a volume that is not TSDF or is tile- or owner-sharded; HV_ERR_INVALID for n < 0 (or n > 2^36), NULL points with
+ * n > 0, a bad dtype, a weight_threshold that is negative or not finite.  n == 0 is a no-op. */
+typedef enum hv_point_dtype { HV_F32 = 0, HV_F64 = 1 } hv_point_dtype;
+#define HV_SAMPLE_OUTSIDE 0
+#define HV_SAMPLE_UNOBSERVED 1
+#define HV_SAMPLE_NEAREST 2
+#define HV_SAMPLE_TRILINEAR 3
+int hv_tsdf_sample_points(hv_volume *v, const void *points /* [n,3] */, int32_t point_dtype, int64_t n, double weight_threshold,
+                          float *sdf /* [n] */, float *gradient /* [n,3] */, float *color /* [n,3] */, float *weight /* [n] */,
+                          uint8_t *status /* [n] */, int32_t loc);
+
+/* Does a depth frame agree with the map?  Every pixel's back-projected point is sampled as above and classified: a point that floats
+ * where the map has SEEN free space belongs to something that was not there before (zero such pixels - depth 0 is invalid everywhere
+ * in this library - before hv_tsdf_integrate or hv_tsdf_track), and the five counts say whether keyframes still agree with a
+ * corrected or merged map.  This project's own contract.  The volume is only read.
+ *   depth     hv_tsdf_track's level 0: d = depth / (float)depth_scale in float32 (both dtypes); valid iff finite and
+ *             depth_min < d <= depth_max, compared in double.
+ *   point     float64 for integer u, v:  a = ((double)u - cx) / fx;  x = a * d;  b = ((double)v - cy) / fy;  y = b * d;  z = d;
+ *             P_r = ((Rwc_r0 x + Rwc_r1 y) + Rwc_r2 z) + twc_r with Rwc = R_cw^T, twc_r = -((Rwc_r0 t_0 + Rwc_r1 t_1) + Rwc_r2 t_2)
+ *             (t = T_cw's last column), computed on the host.  P is sampled by hv_tsdf_sample_points' rule with params->weight_threshold.
+ *   class     HV_CHECK_INVALID     no valid depth
+ *             HV_CHECK_UNKNOWN     sample status OUTSIDE or UNOBSERVED: the map knows nothing here
+ *             HV_CHECK_CONSISTENT  |sdf| <= tolerance
+ *             HV_CHECK_IN_FRONT    sdf > tolerance: the point floats in space the map saw as free
+ *             HV_CHECK_BEHIND      sdf < -tolerance: the point lies behind the map's surface
+ *             decided on the float32 sdf of the sample, widened and compared with tolerance in double.  sdf is 0 where the class is
+ *             INVALID or UNKNOWN.
+ *   stats     count[c] = pixels of class c, exact (integer atomics, at most one per wave and class).
+ * Outputs: sdf [H,W] f32, cls [H,W] u8, stats; any may be NULL.  depth and the two arrays live at loc; HV_HOST is staged and copied
+ * back.  With stats != NULL the call waits for the GPU; with stats == NULL and loc = HV_DEVICE it is queued on the volume's stream
+ * and returns without waiting.  Reads only, as hv_tsdf_sample_points.  One lane per pixel, a wave per 8 x 8 pixel tile.
+ * HV_ERR_MODE as hv_tsdf_sample_points; HV_ERR_INVALID for sizes, intrinsics, depth_scale and the depth range as hv_tsdf_track, a
+ * tolerance that is not positive and finite, a weight_threshold that is negative or not finite, a T_cw that is not finite, has a
+ * bottom row other than (0, 0, 0, 1) or is not rigid by hv_tsdf_integrate_volume's rule (T_cw is inverted as a rigid transform).  An
+ * empty map is not an error: every valid pixel is UNKNOWN. */
+#define HV_CHECK_INVALID 0
+#define HV_CHECK_UNKNOWN 1
+#define HV_CHECK_CONSISTENT 2
+#define HV_CHECK_IN_FRONT 3
+#define HV_CHECK_BEHIND 4
+typedef struct hv_check_params {
+    double depth_scale, depth_min, depth_max, weight_threshold, tolerance;
+} hv_check_params;
+typedef struct hv_check_stats {
+    int64_t count[5]; /* pixels per class, indexed by HV_CHECK_* */
+} hv_check_stats;
+int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t height, int32_t width, const double *intr,
+                        const double *T_cw, const hv_check_params *params, float *sdf /* [H,W] or NULL */,
+                        uint8_t *cls /* [H,W] or NULL */, hv_check_stats *stats /* or NULL */, int32_t loc);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

@@ -161,6 +161,25 @@ class HvPackedHeader(_c.Structure):
     ]
 
 
+HV_F32, HV_F64 = 0, 1
+HV_SAMPLE_OUTSIDE, HV_SAMPLE_UNOBSERVED, HV_SAMPLE_NEAREST, HV_SAMPLE_TRILINEAR = 0, 1, 2, 3
+HV_CHECK_INVALID, HV_CHECK_UNKNOWN, HV_CHECK_CONSISTENT, HV_CHECK_IN_FRONT, HV_CHECK_BEHIND = 0, 1, 2, 3, 4
+
+
+class HvCheckParams(_c.Structure):
+    _fields_ = [
+        ("depth_scale", _f64),
+        ("depth_min", _f64),
+        ("depth_max", _f64),
+        ("weight_threshold", _f64),
+        ("tolerance", _f64),
+    ]
+
+
+class HvCheckStats(_c.Structure):
+    _fields_ = [("count", _i64 * 5)]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -251,6 +270,8 @@ SIGNATURES = {
     "hv_tsdf_register_volume": (_i32, [_vp, _vp, _vp, _c.POINTER(HvRegisterParams), _c.POINTER(HvRegisterResult), _vp, _i64, _pi64]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),

@@ -524,6 +524,8 @@ struct hv_volume {
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
     void *raycast_buf = nullptr; // HV_HOST outputs of hv_tsdf_ray_cast (apart from out_*: a cast leaves the extraction caches valid)
     size_t raycast_buf_bytes = 0;
+    void *sample_buf = nullptr;  // hv_tsdf_sample_points / hv_tsdf_check_frame: class counters and HV_HOST outputs (hv_sample.hip)
+    size_t sample_buf_bytes = 0;
     void *track_buf = nullptr;   // hv_tsdf_track: source pyramid, model casts, reduction slab, state and trace (device)
     size_t track_buf_bytes = 0;
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)

@@ -219,6 +219,56 @@ class PackStats(_Stats):
     __slots__ = ("units", "voxels", "bytes")
 
 
+# hv_tsdf_sample_points' status and hv_tsdf_check_frame's class values (include/hipvol.h)
+SAMPLE_OUTSIDE, SAMPLE_UNOBSERVED, SAMPLE_NEAREST, SAMPLE_TRILINEAR = (L.HV_SAMPLE_OUTSIDE, L.HV_SAMPLE_UNOBSERVED, L.HV_SAMPLE_NEAREST,
+                                                                      L.HV_SAMPLE_TRILINEAR)
+CHECK_INVALID, CHECK_UNKNOWN, CHECK_CONSISTENT, CHECK_IN_FRONT, CHECK_BEHIND = (L.HV_CHECK_INVALID, L.HV_CHECK_UNKNOWN, L.HV_CHECK_CONSISTENT,
+                                                                                L.HV_CHECK_IN_FRONT, L.HV_CHECK_BEHIND)
+
+
+class SampleResult:
+    """What ScalableTSDFVolume.sample_points returns, one row per point: sdf [n] float32 (metres), gradient [n,3] float32 (metres
+    per metre, not normalised) or None, color [n,3] float32 in [0, 1] or None, weight [n] float32 (the nearest voxel's observation
+    count), status [n] uint8 (SAMPLE_OUTSIDE / SAMPLE_UNOBSERVED / SAMPLE_NEAREST / SAMPLE_TRILINEAR).  Every value is 0 where the
+    status is SAMPLE_OUTSIDE or SAMPLE_UNOBSERVED."""
+
+    def __init__(self, sdf, gradient, color, weight, status):
+        self.sdf = sdf
+        self.gradient = gradient
+        self.color = color
+        self.weight = weight
+        self.status = status
+
+    def __repr__(self):
+        return f"SampleResult(n={len(self.sdf)}, gradient={self.gradient is not None}, color={self.color is not None})"
+
+
+class FrameCheckStats(_Stats):
+    """Pixels per class of one ScalableTSDFVolume.check_frame (hv_check_stats, in the order of the CHECK_* values)."""
+
+    __slots__ = ("invalid", "unknown", "consistent", "in_front", "behind")
+
+
+class FrameCheck:
+    """What ScalableTSDFVolume.check_frame returns: sdf [H,W] float32 (the map's signed distance at the pixel's point, 0 where the
+    class is CHECK_INVALID or CHECK_UNKNOWN), cls [H,W] uint8 (CHECK_*), stats (FrameCheckStats) and its five counts as attributes:
+    invalid, unknown, consistent, in_front, behind."""
+
+    def __init__(self, sdf, cls, stats):
+        self.sdf = sdf
+        self.cls = cls
+        self.stats = stats
+
+    invalid = property(lambda self: self.stats.invalid)
+    unknown = property(lambda self: self.stats.unknown)
+    consistent = property(lambda self: self.stats.consistent)
+    in_front = property(lambda self: self.stats.in_front)
+    behind = property(lambda self: self.stats.behind)
+
+    def __repr__(self):
+        return f"FrameCheck({', '.join(f'{name}={getattr(self.stats, name)}' for name in self.stats.__slots__)})"
+
+
 def _packed_operand(buf):
     """A packed map as the C ABI takes it: numpy array, bytes-like object or torch tensor (either device) -> contiguous 1-D uint8,
     numpy for host memory, torch for a GPU."""
@@ -400,6 +450,22 @@ class _Volume:
 
         if ts is not None:
             torch.cuda.current_stream(device).wait_stream(ts)
+
+    def _query_place(self, a, device):
+        """Where a query runs: -> (operand at that place, torch device or None).  device=None: where the operand lives (a torch CUDA
+        tensor stays on its GPU, anything else is host memory); True / False: the volume's GPU / the host, the operand moved there."""
+        is_torch = hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+        on_gpu = L.location(a) == L.HV_DEVICE
+        if device is None:
+            device = on_gpu
+        if not device:
+            return (a.cpu().numpy() if is_torch else a), None
+        import torch
+
+        dev = torch.device("cuda", int(self._cfg.device))
+        if on_gpu and a.device != dev:
+            raise ValueError(f"the operand lives on {a.device}, the volume on {dev}")
+        return (a if on_gpu else torch.as_tensor(a).to(dev)), dev
 
     def _carve(self, camera_frustrum, depth_image, depth_threshold):
         """carve(camera_frustrum, depth f32 HxW, threshold) of every grid type (voxel_grid_carving.h:47-79).  Host array or
@@ -1541,6 +1607,86 @@ class ScalableTSDFVolume(_Volume):
                               tuple(int(res.iterations[i]) for i in range(n_levels)), int(res.degenerate), int(res.inliers),
                               int(res.valid), _trace_rows(rows[:n_rows.value]) if trace else None,
                               None if c is None else int(cres.photometric_inliers), None if c is None else float(cres.intensity_rmse))
+
+    def sample_points(self, points, weight_threshold=0.0, gradient=True, color=False, device=None):
+        """What the map holds at `points` [n,3] (float32 or float64; numpy or torch, either device): -> SampleResult with the signed
+        distance (metres), its gradient (metres per metre, not normalised; gradient=False: None), the colour in [0, 1] (color=True,
+        else None), the nearest voxel's observation count and a status per point.  Trilinear where all eight voxels around the point
+        have weight > weight_threshold, the nearest voxel where only it has, 0 elsewhere (include/hipvol.h, hv_tsdf_sample_points).
+        Reads the volume only.  device=None: results where the input lives - a torch CUDA tensor gives torch CUDA tensors, queued behind
+        torch's current stream and ordered before its later work, nothing crosses PCIe; anything else gives numpy arrays.
+        device=True / False: torch CUDA tensors on the volume's GPU / numpy arrays, wherever the input lives."""
+        if hasattr(points, "data_ptr") and not isinstance(points, np.ndarray):
+            import torch
+
+            if points.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"sample_points: points must be float32 or float64, got {points.dtype}")
+            p = points.contiguous()
+        else:
+            p = np.asarray(points)
+            if p.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise ValueError(f"sample_points: points must be float32 or float64, got {p.dtype}")
+            p = np.ascontiguousarray(p)
+        if len(p.shape) != 2 or int(p.shape[1]) != 3:
+            raise ValueError(f"sample_points: points must have shape [n, 3], got {tuple(p.shape)}")
+        p, dev = self._query_place(p, device)
+        n = int(p.shape[0])
+        f64 = str(p.dtype).endswith("float64")
+        shapes = {"sdf": (n,), "gradient": (n, 3) if gradient else None, "color": (n, 3) if color else None, "weight": (n,), "status": (n,)}
+        out = {}
+        for name, shape in shapes.items():
+            if shape is None:
+                out[name] = None
+            elif dev is not None:
+                import torch
+
+                out[name] = torch.empty(shape, dtype=torch.uint8 if name == "status" else torch.float32, device=dev)
+            else:
+                out[name] = np.empty(shape, np.uint8 if name == "status" else np.float32)
+        ts = self._torch_in(p) if dev is not None else None
+        try:
+            L.check(self._lib.hv_tsdf_sample_points(self._h, L.ptr(p), L.HV_F64 if f64 else L.HV_F32, n, float(weight_threshold),
+                                                    L.ptr(out["sdf"]), L.ptr(out["gradient"]), L.ptr(out["color"]), L.ptr(out["weight"]),
+                                                    L.ptr(out["status"]), L.HV_DEVICE if dev is not None else L.HV_HOST))
+        finally:
+            if ts is not None:
+                self._torch_out(ts, dev)
+        return SampleResult(out["sdf"], out["gradient"], out["color"], out["weight"], out["status"])
+
+    def check_frame(self, depth, intrinsic, extrinsic, depth_scale=1.0, depth_min=0.1, depth_max=3.0, weight_threshold=0.0,
+                    tolerance=None, device=None):
+        """Does a depth frame taken at extrinsic = T_cw agree with the map?  -> FrameCheck: per pixel the map's signed distance at the
+        back-projected point and a class - CHECK_INVALID (no valid depth), CHECK_UNKNOWN (the map knows nothing there),
+        CHECK_CONSISTENT (|sdf| <= tolerance), CHECK_IN_FRONT (sdf > tolerance: the point floats in space the map saw as free -
+        something that was not there before), CHECK_BEHIND (sdf < -tolerance) - and the five pixel counts (include/hipvol.h,
+        hv_tsdf_check_frame).  depth [H,W] as track_frame_to_model takes it: numpy or torch (either device), uint16 or any real dtype
+        (as float32), divided by depth_scale, valid in (depth_min, depth_max].  tolerance=None: 0.5 sdf_trunc (register_volume's
+        default residual_trunc).  Reads the volume only; waits for the GPU (the counts).  device as sample_points."""
+        d, _, dkind, _ = _tsdf_operands(depth, None, intrinsic, depth_only=True)
+        H, W = int(d.shape[0]), int(d.shape[1])
+        d, dev = self._query_place(d, device)
+        prm = L.HvCheckParams()
+        prm.depth_scale, prm.depth_min, prm.depth_max = float(depth_scale), float(depth_min), float(depth_max)
+        prm.weight_threshold = float(weight_threshold)
+        prm.tolerance = 0.5 * float(getattr(self, "sdf_trunc", 0.0)) if tolerance is None else float(tolerance)
+        intr = intrinsic.as_array()
+        T = _as_f64_4x4(extrinsic)
+        if dev is not None:
+            import torch
+
+            sdf = torch.empty((H, W), dtype=torch.float32, device=dev)
+            cls = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        else:
+            sdf, cls = np.empty((H, W), np.float32), np.empty((H, W), np.uint8)
+        st = L.HvCheckStats()
+        ts = self._torch_in(d) if dev is not None else None
+        try:
+            L.check(self._lib.hv_tsdf_check_frame(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T), ctypes.byref(prm), L.ptr(sdf),
+                                                  L.ptr(cls), ctypes.byref(st), L.HV_DEVICE if dev is not None else L.HV_HOST))
+        finally:
+            if ts is not None:
+                self._torch_out(ts, dev)
+        return FrameCheck(sdf, cls, FrameCheckStats(*st.count))
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
