@@ -834,6 +834,62 @@ int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t depth_dtype, in
                         const double *T_cw, const hv_check_params *params, float *sdf /* [H,W] or NULL */,
                         uint8_t *cls /* [H,W] or NULL */, hv_check_stats *stats /* or NULL */, int32_t loc);
 
+/* Distance field: how far is every cell of a box from the nearest surface of the map - beyond the truncation band, where the map
+ * itself holds no value and, in open space, no unit.  A dense signed Euclidean distance over a box of the map's OWN voxel lattice, out
+ * to a radius of R voxels, for planners, collision checks and camera-to-surface guards.  This project's own contract.  The volume is
+ * only read.  Everything up to the final square root is integer arithmetic on squared voxel distances: there are no fragile points.
+ *   cell      (i, j, k), 0 <= i < nx ..., is voxel q = origin + (i, j, k) of the map's lattice (centre (q + 0.5) * voxel_length); its
+ *             unit is q >> 4 per axis (arithmetic shift: negative indices work), its local index q & 15.
+ *   observed  hv_tsdf_sample_points' rule: the unit is held, its key is in range, (double)weight > weight_threshold.
+ *   state     HV_DIST_INSIDE  observed and tsdf <= 0;  HV_DIST_FREE  observed and tsdf > 0 (a NaN tsdf is FREE);  HV_DIST_UNKNOWN
+ *             otherwise.
+ *   site      an observed voxel with at least one of its six axis neighbours IN THE MAP (inside the box or not) observed and of the
+ *             other state (FREE against INSIDE): both voxels of every sign-changing lattice edge.  An UNKNOWN voxel is never a site
+ *             and never makes one.  cls = state, with HV_DIST_SITE OR-ed on at a site.
+ *   dist2     min(R * R, min over the sites s INSIDE THE BOX of |c - s|^2) in integer voxel units, evaluated as three separable
+ *             passes with a window of +-R per axis, along x, then y, then z:
+ *               g1(i, j, k) = min over |i' - i| <= R of (site(i', j, k) ? (i - i')^2 : INF)
+ *               g2(i, j, k) = min over |j' - j| <= R of g1(i, j', k) + (j - j')^2
+ *               g3(i, j, k) = min over |k' - k| <= R of g2(i, j, k') + (k - k')^2,     dist2 = min(g3, R * R)
+ *             (a site within Euclidean distance R has every axis offset <= R, so the windows lose nothing below the cap).  A cell is
+ *             FAR when dist2 == R * R: no site of the box lies nearer than R voxels.
+ *   distance  s * (sqrtf((float)dist2) * (float)voxel_length): one correctly rounded float32 square root, then one float32 product;
+ *             s = -1.0f for INSIDE cells (an inside site is -0.0f), +1.0f for FREE and UNKNOWN ones.  Metres.
+ *   stats     unknown + free + inside = cells; sites = cells with the SITE bit; far = FAR cells.  Exact (integer atomics, at most one
+ *             per wave and counter, after ballots).  They count the box of the call.
+ * What the number means: `distance` is the distance to the nearest site CENTRE.  Every site centre lies within one voxel length of
+ * a zero crossing on a lattice edge, so against the true surface it under-reports by at most one voxel length; for a planar surface
+ * it over-reports by at most sqrt(3) voxel lengths.  A surface just outside the box is not seen: grow the box by R cells per side (the
+ * Python front does, pad=True) where that matters.  Inside the truncation band hv_tsdf_sample_points remains the precise value.
+ * Unknown space is not an obstacle here: cls tells known free from unknown, the caller decides.
+ * Outputs: distance f32, dist2 u32, cls u8, each [nx,ny,nz] C-ordered (z fastest); any may be NULL, and a NULL output is neither
+ * computed nor staged (a call for cls alone stops after the classification).  loc = HV_DEVICE: device pointers, queued on the
+ * volume's stream; HV_HOST: staged by the library and copied back before returning, as hv_tsdf_sample_points.  With stats != NULL
+ * the call waits for the GPU.  Reads only: no growth, no stamp, no claim - dumps stay bit for bit, extraction caches,
+ * hv_tsdf_dirty_keys and hv_tsdf_touched are what they were; the batch pipeline is drained first, as hv_tsdf_ray_cast does.  Every
+ * cell is written from values that depend on the map's content alone: two calls give bitwise equal outputs, whatever the pool order.
+ * HV_ERR_MODE for a volume that is not TSDF or is tile- or owner-sharded; HV_ERR_INVALID for NULL params, a shape outside
+ * 1..HV_DIST_MAX_SHAPE or with more than 2^31 - 1 cells, an |origin| above 2^30 (origin + shape stays inside int32), a radius outside
+ * 1..HV_DIST_MAX_RADIUS, a weight_threshold that is negative or not finite, a bad loc.  An empty map is not an error: every cell is
+ * UNKNOWN and FAR. */
+#define HV_DIST_UNKNOWN 0
+#define HV_DIST_FREE 1
+#define HV_DIST_INSIDE 2
+#define HV_DIST_SITE 4 /* OR-ed onto FREE or INSIDE */
+#define HV_DIST_MAX_SHAPE 4096
+#define HV_DIST_MAX_RADIUS 1024
+typedef struct hv_distance_params {
+    int32_t origin[3];        /* voxel index of cell (0,0,0); voxel q has its centre at (q + 0.5) * voxel_length */
+    int32_t shape[3];         /* nx, ny, nz cells, each 1..4096; nx*ny*nz <= 2^31 - 1 */
+    int32_t radius;           /* R, in voxels, 1..1024 */
+    double weight_threshold;  /* >= 0, finite */
+} hv_distance_params;
+typedef struct hv_distance_stats {
+    int64_t unknown, free, inside, sites, far;
+} hv_distance_stats;
+int hv_tsdf_distance_field(hv_volume *v, const hv_distance_params *p, float *distance /* [nx,ny,nz] */, uint32_t *dist2 /* [nx,ny,nz] */,
+                           uint8_t *cls /* [nx,ny,nz] */, hv_distance_stats *stats, int32_t loc);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

@@ -180,6 +180,18 @@ class HvCheckStats(_c.Structure):
     _fields_ = [("count", _i64 * 5)]
 
 
+HV_DIST_UNKNOWN, HV_DIST_FREE, HV_DIST_INSIDE, HV_DIST_SITE = 0, 1, 2, 4
+HV_DIST_MAX_SHAPE, HV_DIST_MAX_RADIUS = 4096, 1024
+
+
+class HvDistanceParams(_c.Structure):
+    _fields_ = [("origin", _i32 * 3), ("shape", _i32 * 3), ("radius", _i32), ("weight_threshold", _f64)]
+
+
+class HvDistanceStats(_c.Structure):
+    _fields_ = [("unknown", _i64), ("free", _i64), ("inside", _i64), ("sites", _i64), ("far", _i64)]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -272,6 +284,7 @@ SIGNATURES = {
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
+    "hv_tsdf_distance_field": (_i32, [_vp, _c.POINTER(HvDistanceParams), _vp, _vp, _vp, _c.POINTER(HvDistanceStats), _i32]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),

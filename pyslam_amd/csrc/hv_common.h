@@ -526,6 +526,8 @@ struct hv_volume {
     size_t raycast_buf_bytes = 0;
     void *sample_buf = nullptr;  // hv_tsdf_sample_points / hv_tsdf_check_frame: class counters and HV_HOST outputs (hv_sample.hip)
     size_t sample_buf_bytes = 0;
+    void *dist_buf = nullptr;    // hv_tsdf_distance_field: counters, the intermediate grid, classes and HV_HOST outputs (hv_distance.hip)
+    size_t dist_buf_bytes = 0;
     void *track_buf = nullptr;   // hv_tsdf_track: source pyramid, model casts, reduction slab, state and trace (device)
     size_t track_buf_bytes = 0;
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)

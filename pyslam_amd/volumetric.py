@@ -269,6 +269,69 @@ class FrameCheck:
         return f"FrameCheck({', '.join(f'{name}={getattr(self.stats, name)}' for name in self.stats.__slots__)})"
 
 
+# hv_tsdf_distance_field's cell classes (include/hipvol.h): DIST_SITE is OR-ed onto DIST_FREE or DIST_INSIDE
+DIST_UNKNOWN, DIST_FREE, DIST_INSIDE, DIST_SITE = L.HV_DIST_UNKNOWN, L.HV_DIST_FREE, L.HV_DIST_INSIDE, L.HV_DIST_SITE
+
+
+class DistanceFieldStats(_Stats):
+    """Cells per kind of one ScalableTSDFVolume.distance_field (hv_distance_stats), over the box the call computed (the padded one
+    with pad=True): unknown + free + inside = cells; sites = cells at a sign change of the map; far = cells with no site of the box
+    nearer than max_distance."""
+
+    __slots__ = ("unknown", "free", "inside", "sites", "far")
+
+
+class DistanceField:
+    """What ScalableTSDFVolume.distance_field returns: a dense grid over a box of the map's voxel lattice, cell (i, j, k) being voxel
+    origin + (i, j, k), centred at (origin + (i, j, k) + 0.5) * voxel_length.  distance [nx,ny,nz] float32: metres to the nearest
+    surface site, negative inside a surface, capped at max_distance; dist2 [nx,ny,nz] uint32: the same in squared voxels, capped at
+    R^2; cls [nx,ny,nz] uint8: DIST_UNKNOWN / DIST_FREE / DIST_INSIDE, with DIST_SITE OR-ed on at a sign change.  An output that was
+    not asked for is None.  origin [3] int64, shape (nx, ny, nz), voxel_length, radius = R, max_distance = R * voxel_length, stats
+    (DistanceFieldStats of the computed box)."""
+
+    def __init__(self, distance, dist2, cls, origin, shape, voxel_length, radius, stats):
+        self.distance = distance
+        self.dist2 = dist2
+        self.cls = cls
+        self.origin = np.asarray(origin, np.int64).reshape(3)
+        self.shape = tuple(int(n) for n in shape)
+        self.voxel_length = float(voxel_length)
+        self.radius = int(radius)
+        self.max_distance = float(self.radius * np.float64(voxel_length))
+        self.stats = stats
+
+    def cell_of(self, points):
+        """points [n,3] world metres -> (idx [n,3] int64 = floor(p / voxel_length) - origin, inside [n] bool: the cell is in the box).
+        Not finite: outside."""
+        p = np.asarray(points, np.float64).reshape(-1, 3)
+        with np.errstate(invalid="ignore"):
+            q = np.floor(p / np.float64(self.voxel_length))
+            ok = np.isfinite(q).all(axis=1) & (np.abs(q) < 2.0 ** 62).all(axis=1)
+        idx = np.where(ok[:, None], q, 0.0).astype(np.int64) - self.origin
+        inside = ok & ((idx >= 0) & (idx < np.asarray(self.shape, np.int64))).all(axis=1)
+        return idx, inside
+
+    def lookup(self, points):
+        """distance at the cell that contains each of points [n,3] (float32 [n], numpy); max_distance where the point is outside
+        the box - as float32(R) * float32(voxel_length), the very value a far cell holds."""
+        if self.distance is None:
+            raise ValueError("DistanceField.lookup: the field was computed without 'distance'")
+        idx, inside = self.cell_of(points)
+        out = np.full(len(idx), np.float32(self.radius) * np.float32(self.voxel_length), np.float32)
+        i = idx[inside]
+        if hasattr(self.distance, "is_cuda"):
+            import torch
+
+            t = torch.from_numpy(i).to(self.distance.device)
+            out[inside] = self.distance[t[:, 0], t[:, 1], t[:, 2]].cpu().numpy()
+        else:
+            out[inside] = self.distance[i[:, 0], i[:, 1], i[:, 2]]
+        return out
+
+    def __repr__(self):
+        return f"DistanceField(origin={self.origin.tolist()}, shape={self.shape}, max_distance={self.max_distance:g})"
+
+
 def _packed_operand(buf):
     """A packed map as the C ABI takes it: numpy array, bytes-like object or torch tensor (either device) -> contiguous 1-D uint8,
     numpy for host memory, torch for a GPU."""
@@ -1687,6 +1750,75 @@ class ScalableTSDFVolume(_Volume):
             if ts is not None:
                 self._torch_out(ts, dev)
         return FrameCheck(sdf, cls, FrameCheckStats(*st.count))
+
+    DISTANCE_FIELD_OUTPUTS = ("distance", "dist2", "cls")
+
+    def distance_field(self, bounds, max_distance, weight_threshold=0.0, pad=True, outputs=("distance", "cls"), device=False):
+        """Signed Euclidean distance to the map's nearest surface at every voxel of a box, out to max_distance - beyond the
+        truncation band, in open space where the map holds no unit: -> DistanceField.  bounds = (lo, hi) in world metres; the box is
+        the voxels floor(lo / voxel_length) .. floor(hi / voxel_length) of the map's own lattice (float64), R = ceil(max_distance /
+        voxel_length) voxels.  A voxel is observed when weight > weight_threshold, INSIDE when its tsdf <= 0, else FREE; a SITE is an
+        observed voxel with an observed axis neighbour of the other sign; distance = +-sqrt(dist2) * voxel_length to the nearest site
+        of the computed box, capped at R * voxel_length (include/hipvol.h, hv_tsdf_distance_field).  pad=True computes the box grown by
+        R cells per side, so that surfaces just outside `bounds` are seen, and returns views cropped back to it; pad=False computes
+        `bounds` as given.  No axis of the computed box may exceed 4096 cells.  outputs: which of "distance", "dist2", "cls" to
+        compute.  Reads the volume only; waits for the GPU (the counts).  device=True: torch CUDA tensors on the volume's GPU, ordered
+        before later work on torch's current stream."""
+        names = tuple(outputs)
+        bad = [a for a in names if a not in self.DISTANCE_FIELD_OUTPUTS]
+        if bad:
+            raise ValueError(f"distance_field: unknown output(s) {bad}; choose from {self.DISTANCE_FIELD_OUTPUTS}")
+        try:
+            lo_m, hi_m = bounds
+            lo_m = np.asarray(lo_m, dtype=np.float64).reshape(-1)
+            hi_m = np.asarray(hi_m, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"distance_field: bounds must be (lo_xyz, hi_xyz): {e}") from None
+        if lo_m.shape != (3,) or hi_m.shape != (3,) or not (np.all(np.isfinite(lo_m)) and np.all(np.isfinite(hi_m))) or np.any(lo_m > hi_m):
+            raise ValueError("distance_field: bounds must be (lo_xyz, hi_xyz), finite, lo <= hi")
+        vl = np.float64(self.voxel_length)
+        if not (np.isfinite(max_distance) and max_distance > 0.0):
+            raise ValueError(f"distance_field: max_distance must be positive and finite, got {max_distance}")
+        R = int(np.ceil(np.float64(max_distance) / vl))
+        if not 1 <= R <= L.HV_DIST_MAX_RADIUS:
+            raise ValueError(f"distance_field: max_distance {max_distance} is {R} voxels; the radius is limited to {L.HV_DIST_MAX_RADIUS}")
+        first, last = np.floor(lo_m / vl), np.floor(hi_m / vl)
+        if np.any(np.abs(first) > 2.0 ** 30) or np.any(np.abs(last) > 2.0 ** 30):
+            raise ValueError("distance_field: bounds reach beyond voxel index +-2^30")
+        origin = first.astype(np.int64)
+        shape = last.astype(np.int64) - origin + 1
+        grow = R if pad else 0
+        full_origin, full_shape = origin - grow, shape + 2 * grow
+        if np.any(full_shape > L.HV_DIST_MAX_SHAPE):
+            raise ValueError(f"distance_field: the box is {shape.tolist()} cells" + (f", {full_shape.tolist()} with {R} cells of padding per side" if pad else "")
+                             + f"; the limit is {L.HV_DIST_MAX_SHAPE} per axis (a smaller box, a smaller max_distance or pad=False)")
+        prm = L.HvDistanceParams()
+        for a in range(3):
+            prm.origin[a], prm.shape[a] = int(full_origin[a]), int(full_shape[a])
+        prm.radius, prm.weight_threshold = R, float(weight_threshold)
+        dtypes = {"distance": np.float32, "dist2": np.uint32, "cls": np.uint8}
+        full = tuple(int(n) for n in full_shape)
+        out = {}
+        dev = None
+        if device:
+            import torch
+
+            dev = torch.device("cuda", int(self._cfg.device))
+            for a in names:  # (torch has no uint32 arithmetic: dist2 is an int32 tensor with the same bits, values <= 2^20)
+                out[a] = torch.empty(full, dtype={"distance": torch.float32, "dist2": torch.int32, "cls": torch.uint8}[a], device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
+        else:
+            for a in names:
+                out[a] = _result_array(full, dtypes[a])
+        st = L.HvDistanceStats()
+        L.check(self._lib.hv_tsdf_distance_field(self._h, ctypes.byref(prm), L.ptr(out.get("distance")), L.ptr(out.get("dist2")),
+                                                 L.ptr(out.get("cls")), ctypes.byref(st), L.HV_DEVICE if device else L.HV_HOST))
+        if device:
+            self._torch_out(self._torch_stream(dev), dev)
+        crop = tuple(slice(grow, grow + int(n)) for n in shape)
+        view = {a: (out[a][crop] if a in out else None) for a in self.DISTANCE_FIELD_OUTPUTS}
+        return DistanceField(view["distance"], view["dist2"], view["cls"], origin, shape, float(vl), R,
+                             DistanceFieldStats(st.unknown, st.free, st.inside, st.sites, st.far))
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
