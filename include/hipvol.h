@@ -890,6 +890,74 @@ typedef struct hv_distance_stats {
 int hv_tsdf_distance_field(hv_volume *v, const hv_distance_params *p, float *distance /* [nx,ny,nz] */, uint32_t *dist2 /* [nx,ny,nz] */,
                            uint8_t *cls /* [nx,ny,nz] */, hv_distance_stats *stats, int32_t loc);
 
+/* Surface components: the connected pieces of the map's surface, found in the sparse unit hash itself, and the removal of the small
+ * ones in place - the floaters that noisy depth, depth edges and moving objects leave in every real map, which show up in
+ * hv_tsdf_extract_mesh, become obstacles in hv_tsdf_distance_field and pull on hv_tsdf_register_volume.  This project's own
+ * contract (Open3D clusters the triangles of an extracted, welded mesh on the host and leaves the map dirty).  Every definition is
+ * integer: the whole contract is bit-exact, there is no fragile point.
+ *   observed, state, site   exactly hv_tsdf_distance_field's rules: a voxel is OBSERVED when its unit is held, its key is in range
+ *             and (double)weight > weight_threshold; its state is INSIDE when tsdf <= 0, else FREE (a NaN tsdf is FREE); a SITE is an
+ *             observed voxel with at least one of its six axis neighbours observed and of the other state.
+ *   adjacent  two sites whose global voxel indices (16 * key + local) differ by at most 1 on every axis: the 26-neighbourhood, across
+ *             unit borders, edges and corners.  Both ends of every sign-changing lattice edge are sites and adjacent; a one-voxel-
+ *             thick oblique sheet stays one piece (under the 6-neighbourhood it may not).
+ *   component a class of the transitive closure of "adjacent".  Its SEED is its smallest site in lexicographic (x, y, z) order of the
+ *             global voxel index; components are numbered 0 .. C-1 by increasing seed.  The numbering depends on the map's content
+ *             alone - not on pool order, table order or launch order.
+ * hv_tsdf_surface_components (reads only).  Per component, in its number's order: seed [C,3] i32, sites [C] i64 (how many), lo and
+ * hi [C,3] i32 (the inclusive bounding box in global voxel indices).  The site list: site_index [N,3] i32 (global voxel index) and
+ * site_label [N] i32 (component number), rows sorted by unit key (x, y, z), then by dump order x * 256 + y * 16 + z inside the unit.
+ * Count-then-fill, as hv_tsdf_extract_mesh: *n_components = C and *n_sites = N are always written; every buffer may be NULL and a
+ * NULL buffer is neither computed nor staged (with no table and no label the seeds are not computed nor sorted); a call with all
+ * six NULL returns the counts.  A table buffer needs component_cap >= C, a list buffer site_cap >= N.  Buffers live at loc: HV_DEVICE
+ * = device pointers, HV_HOST = staged by the library and copied back.  stats (may be NULL): units = units held, sites = N,
+ * components = C, largest = the most sites in one component.  The call waits for the GPU.  Nothing of the volume changes: dumps stay
+ * bit for bit, extraction caches, hv_tsdf_dirty_keys and hv_tsdf_touched are what they were; the batch pipeline is drained first.
+ * An empty map or a map without a site is not an error: C = N = 0.  The two calls of a count-then-fill pair each label the map.
+ * hv_tsdf_remove_components (rewrites the map).  With SMALL = the sites of components that have fewer than min_sites sites and KEPT =
+ * all other sites, a voxel v of a held unit with weight > 0 (as an integer: any observation, whatever weight_threshold) is RESET when
+ *   v is in SMALL, or some site of SMALL lies within Chebyshev distance `margin` of v and no site of KEPT does.
+ * Reset = the fresh state in all five planes: what a never-written voxel holds and what hv_tsdf_deintegrate leaves behind.
+ *   why this is safe   A voxel that is not a site has no observed axis neighbour of the other state, so making voxels unobserved
+ *             never creates a sign-changing edge: no new site, no new surface.  Every cube that marching cubes triangulates for a
+ *             kept component has a sign change, hence a KEPT site, among its corners, so all its corners lie within Chebyshev
+ *             distance 1 of a KEPT site: with margin >= 1 the kept mesh is untouched (margin 0 resets SMALL sites only - and with them
+ *             the triangles of kept cubes that have a SMALL corner).  After the call no SMALL site is observed any more and every KEPT
+ *             site still is a site (its other-state neighbour is a site of its own component, so KEPT, so not reset): a second
+ *             identical call finds exactly the KEPT components, none of them small, and resets nothing - the call is idempotent.
+ *   after     units in which a voxel changed get a new stamp, as after hv_tsdf_deintegrate: incremental extraction and
+ *             hv_tsdf_dirty_keys see them, cached extraction results are dropped; other units keep their stamp.  No unit is released
+ *             (hv_tsdf_prune does that; units_emptied says how many now hold no weight).  If NOTHING is reset the volume is left
+ *             exactly as it was, caches included.
+ *   stats     components, sites = as hv_tsdf_surface_components before the call; components_removed, sites_removed = those of SMALL;
+ *             voxels_reset; units_changed; units_emptied = changed units left without a weight.
+ * Device work (hv_components.hip): one workgroup per unit classifies as hv_tsdf_distance_field does and writes the unit's 4096-bit
+ * site mask; the host ranks the unit keys (hv_tsdf_dump's sort; 12 bytes per unit cross PCIe) and a scan gives every site its index in
+ * the site list's order; union-find with atomicMin towards the smaller index, inside a unit in LDS, across units through the 26
+ * neighbour units' masks - every link loop strictly lowers an index, no wave waits for another, nothing loops over rounds; a flatten
+ * pass; sizes, boxes and seeds by integer atomics (one per wave where a wave's rows share a component); the canonical order by three
+ * stable device radix sorts of the C seeds; the removal's two box dilations as shifts and ORs of 16-bit rows of the 3 x 3 x 3 units'
+ * masks in LDS, the reset as 16-byte stores.  The site list never visits the host (HV_HOST copies the finished rows).  Extra device
+ * memory, freed before the call returns, never a word per pool voxel: 1036 bytes per unit (site mask 512, row prefix 512, count,
+ * base, rank) - 1552 for the removal (+ the SMALL mask and its count) -, 8 bytes per site (parent, component slot), 36 bytes per
+ * component plus, where the table or the labels are asked for, 20 bytes per component and the radix sort's own scratch, 64 bytes of
+ * counters, and with HV_HOST the outputs.
+ * HV_ERR_MODE for a volume that is not TSDF or is tile- or owner-sharded (components cross ranks); HV_ERR_INVALID for a
+ * weight_threshold that is negative or not finite, a bad loc, a capacity that is too small (the counts are still written), more than
+ * 2^31 - 1 sites, min_sites < 1, a margin outside 0..HV_COMPONENTS_MAX_MARGIN (one unit: only the 26 neighbour units reach in). */
+#define HV_COMPONENTS_MAX_MARGIN 16
+typedef struct hv_components_stats {
+    int64_t units, sites, components, largest;
+} hv_components_stats;
+typedef struct hv_remove_components_stats {
+    int64_t components, components_removed, sites, sites_removed, voxels_reset, units_changed, units_emptied;
+} hv_remove_components_stats;
+int hv_tsdf_surface_components(hv_volume *v, double weight_threshold, int32_t *seed /* [C,3] */, int64_t *sites /* [C] */,
+                               int32_t *lo /* [C,3] */, int32_t *hi /* [C,3] */, int64_t component_cap, int32_t *site_index /* [N,3] */,
+                               int32_t *site_label /* [N] */, int64_t site_cap, int64_t *n_components, int64_t *n_sites,
+                               hv_components_stats *stats, int32_t loc);
+int hv_tsdf_remove_components(hv_volume *v, double weight_threshold, int64_t min_sites, int32_t margin, hv_remove_components_stats *stats);
+
 /* Parity/debug export, units sorted by (x,y,z) index: keys [U,3] i32; tsdf, weight [U,R^3] f32;
  * color [U,R^3,3] f64 = running-mean RGB on the 0..255 scale; voxel order = Open3D's IndexOf
  * x*R^2 + y*R + z.  Host pointers; any may be NULL. */

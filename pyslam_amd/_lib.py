@@ -192,6 +192,18 @@ class HvDistanceStats(_c.Structure):
     _fields_ = [("unknown", _i64), ("free", _i64), ("inside", _i64), ("sites", _i64), ("far", _i64)]
 
 
+HV_COMPONENTS_MAX_MARGIN = 16
+
+
+class HvComponentsStats(_c.Structure):
+    _fields_ = [("units", _i64), ("sites", _i64), ("components", _i64), ("largest", _i64)]
+
+
+class HvRemoveComponentsStats(_c.Structure):
+    _fields_ = [("components", _i64), ("components_removed", _i64), ("sites", _i64), ("sites_removed", _i64), ("voxels_reset", _i64),
+                ("units_changed", _i64), ("units_emptied", _i64)]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -285,6 +297,8 @@ SIGNATURES = {
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
     "hv_tsdf_distance_field": (_i32, [_vp, _c.POINTER(HvDistanceParams), _vp, _vp, _vp, _c.POINTER(HvDistanceStats), _i32]),
+    "hv_tsdf_surface_components": (_i32, [_vp, _f64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _pi64, _pi64, _c.POINTER(HvComponentsStats), _i32]),
+    "hv_tsdf_remove_components": (_i32, [_vp, _f64, _i64, _i32, _c.POINTER(HvRemoveComponentsStats)]),
     "hv_tsdf_dump": (_i32, [_vp, _vp, _vp, _vp, _vp, _pi64]),
     "hv_tsdf_touched": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_export_numerators": (_i32, [_vp, _vp, _i64, _vp, _i32]),

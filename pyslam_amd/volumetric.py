@@ -12,6 +12,7 @@ All compute happens in libpyslam_hipvol.so on the GPU; nothing here falls back t
 Arrays may be numpy (host) or torch CUDA tensors (zero-copy, already resident in HBM).
 """
 import ctypes
+import typing
 
 import numpy as np
 
@@ -330,6 +331,52 @@ class DistanceField:
 
     def __repr__(self):
         return f"DistanceField(origin={self.origin.tolist()}, shape={self.shape}, max_distance={self.max_distance:g})"
+
+
+class SurfaceComponentsStats(_Stats):
+    """Counts of one ScalableTSDFVolume.surface_components (hv_components_stats): units = units held; sites = surface sites;
+    components = connected components of the sites; largest = the most sites in one component."""
+
+    __slots__ = ("units", "sites", "components", "largest")
+
+
+class SurfaceComponents:
+    """What ScalableTSDFVolume.surface_components returns.  Per component, numbered 0 .. C-1 by increasing seed: seed [C,3] int32
+    (its smallest site in (x, y, z) order of the global voxel index), sites [C] int64 (how many), lo, hi [C,3] int32 (its inclusive
+    bounding box in global voxel indices; voxel q has its centre at (q + 0.5) * voxel_length).  With sites=True the site list:
+    site_index [N,3] int32 and site_label [N] int32 (the component number), rows sorted by unit key, then by x * 256 + y * 16 + z
+    inside the unit; else both None.  stats (SurfaceComponentsStats), voxel_length."""
+
+    def __init__(self, seed, sites, lo, hi, site_index, site_label, stats, voxel_length):
+        self.seed = seed
+        self.sites = sites
+        self.lo = lo
+        self.hi = hi
+        self.site_index = site_index
+        self.site_label = site_label
+        self.stats = stats
+        self.voxel_length = float(voxel_length)
+
+    def __len__(self):
+        return int(self.stats.components)
+
+    def __repr__(self):
+        return f"SurfaceComponents(components={self.stats.components}, sites={self.stats.sites}, largest={self.stats.largest})"
+
+
+class ComponentRemovalStats(typing.NamedTuple):
+    """What ScalableTSDFVolume.remove_small_components returns (hv_remove_components_stats): components, sites = what
+    surface_components counts before the call; components_removed, sites_removed = those with fewer than min_sites sites;
+    voxels_reset = voxels put back into the fresh state; units_changed = units holding one of them; units_emptied = changed units
+    left without a weight (prune(empty=True) releases them)."""
+
+    components: int
+    components_removed: int
+    sites: int
+    sites_removed: int
+    voxels_reset: int
+    units_changed: int
+    units_emptied: int
 
 
 def _packed_operand(buf):
@@ -1819,6 +1866,61 @@ class ScalableTSDFVolume(_Volume):
         view = {a: (out[a][crop] if a in out else None) for a in self.DISTANCE_FIELD_OUTPUTS}
         return DistanceField(view["distance"], view["dist2"], view["cls"], origin, shape, float(vl), R,
                              DistanceFieldStats(st.unknown, st.free, st.inside, st.sites, st.far))
+
+    def surface_components(self, weight_threshold=0.0, sites=False, device=False):
+        """The connected pieces of the map's surface, labelled in the sparse unit hash on the GPU: -> SurfaceComponents.  A voxel is
+        observed when weight > weight_threshold, INSIDE when its tsdf <= 0, else FREE; a SITE is an observed voxel with an observed
+        axis neighbour of the other sign (distance_field's rule); two sites are adjacent when their voxel indices differ by at most 1
+        on every axis, across unit borders, edges and corners; a component is a class of the closure of that.  Components are
+        numbered by their smallest site in (x, y, z) order, whatever the pool order (include/hipvol.h, hv_tsdf_surface_components).
+        Per component: seed, sites (the count), lo, hi.  sites=True adds the site list, site_index [N,3] and site_label [N] - to
+        colour a mesh by component, look its vertices' voxels up there.  Reads the volume only; waits for the GPU; labels the map
+        twice (once for the sizes of the results, once to fill them).  device=True: torch CUDA tensors on the volume's GPU, ordered
+        before later work on torch's current stream.  An empty map gives zero components."""
+        st = L.HvComponentsStats()
+        nc, ns = ctypes.c_int64(), ctypes.c_int64()
+        call = self._lib.hv_tsdf_surface_components
+        L.check(call(self._h, float(weight_threshold), None, None, None, None, 0, None, None, 0, ctypes.byref(nc), ctypes.byref(ns),
+                     ctypes.byref(st), L.HV_HOST))
+        C, N = int(nc.value), int(ns.value)
+        shapes = {"seed": ((C, 3), np.int32), "sites": ((C,), np.int64), "lo": ((C, 3), np.int32), "hi": ((C, 3), np.int32)}
+        if sites:
+            shapes.update({"site_index": ((N, 3), np.int32), "site_label": ((N,), np.int32)})
+        out = {}
+        dev = None
+        if device:
+            import torch
+
+            dev = torch.device("cuda", int(self._cfg.device))
+            for name, (shape, dtype) in shapes.items():
+                out[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
+            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
+        else:
+            for name, (shape, dtype) in shapes.items():
+                out[name] = _result_array(shape, dtype)
+        if C > 0:
+            L.check(call(self._h, float(weight_threshold), L.ptr(out["seed"]), L.ptr(out["sites"]), L.ptr(out["lo"]), L.ptr(out["hi"]), C,
+                         L.ptr(out.get("site_index")), L.ptr(out.get("site_label")), N, ctypes.byref(nc), ctypes.byref(ns), ctypes.byref(st),
+                         L.HV_DEVICE if device else L.HV_HOST))
+            if device:
+                self._torch_out(self._torch_stream(dev), dev)
+        return SurfaceComponents(out["seed"], out["sites"], out["lo"], out["hi"], out.get("site_index"), out.get("site_label"),
+                                 SurfaceComponentsStats(st.units, st.sites, st.components, st.largest), self.voxel_length)
+
+    def remove_small_components(self, min_sites, weight_threshold=0.0, margin=None):
+        """Clean the map: reset, in place, every surface component with fewer than min_sites sites - the floaters that noisy depth,
+        depth edges and moving objects leave behind - together with the observed voxels within `margin` voxels (Chebyshev) of them
+        that are not that close to a kept component (include/hipvol.h, hv_tsdf_remove_components).  margin=None: min(16,
+        ceil(sdf_trunc / voxel_length)), the truncation band's half width - a floater's band goes with it; margin >= 1 leaves the
+        kept surface's mesh untouched.  Reset voxels are in the fresh state, as after deintegrate; changed units are stamped
+        (incremental extraction and dirty_keys() see them); no unit is released - follow with prune(empty=True).  Waits for the GPU
+        and returns ComponentRemovalStats; with nothing to remove the volume is untouched, caches included."""
+        if margin is None:
+            margin = min(L.HV_COMPONENTS_MAX_MARGIN, int(np.ceil(np.float64(self.sdf_trunc) / np.float64(self.voxel_length))))
+        st = L.HvRemoveComponentsStats()
+        L.check(self._lib.hv_tsdf_remove_components(self._h, float(weight_threshold), int(min_sites), int(margin), ctypes.byref(st)))
+        return ComponentRemovalStats(st.components, st.components_removed, st.sites, st.sites_removed, st.voxels_reset, st.units_changed,
+                                     st.units_emptied)
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
