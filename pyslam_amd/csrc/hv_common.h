@@ -568,6 +568,34 @@ int hv_rekey_in_place(hv_volume *v, int64_t keep);
 int32_t hv_next_status_seq(hv_volume *v); // sequence number for the call's publishing kernel
 void hv_launch_publish_status(hv_volume *v); // modes whose last kernel does not publish by itself
 int hv_read_counters(hv_volume *v); // D2H of the counter block (synchronises the stream)
+// ---- the host prologue of the operations on a whole TSDF map (hv_core.hip) ----
+// HV_ERR_MODE unless v is a plain TSDF map: TSDF mode, not tile-sharded, not owner-sharded.  The message starts with fn and names v
+// as `subject` ("the volume", "the source", ...).
+int hv_tsdf_require_whole_map(const hv_volume *v, const char *fn, const char *subject);
+// Drain the batch pipeline and read the counters (waits for the GPU): *used = units held (used may be null).  refuse_overflow: HV_ERR_CAPACITY when an
+// earlier call ran out of pool.
+int hv_tsdf_drain(hv_volume *v, const char *fn, bool refuse_overflow, int64_t *used);
+// The units ranked by key: order[r] = pool index of the unit with the r-th smallest (x, y, z); xyz_in_order (may be null) = their
+// keys [used,3] in that order.  One D2H of block_keys, one sort on the host; waits for the stream.
+int hv_tsdf_key_order(hv_volume *v, int64_t used, std::vector<int32_t> &order, std::vector<int32_t> *xyz_in_order);
+// Device memory of one call, freed when it leaves scope (the caller has waited for whatever uses it).
+struct HvScratch {
+    std::vector<void *> held;
+    HvScratch() = default;
+    HvScratch(const HvScratch &) = delete;
+    HvScratch &operator=(const HvScratch &) = delete;
+    ~HvScratch() {
+        for (void *p : held) (void)hipFree(p);
+    }
+    template <typename T>
+    hipError_t get(T **p, size_t n) {
+        void *raw = nullptr;
+        const hipError_t e = hipMalloc(&raw, (n > 0 ? n : 1) * sizeof(T));
+        if (e == hipSuccess) held.push_back(raw);
+        *p = (T *)raw;
+        return e;
+    }
+};
 // hv_prep.hip: n_frames device-resident frames through the volume's rectify maps, queued on `s`
 int hv_rectify_frames_device(hv_volume *v, hipStream_t s, const void *d_depth, int32_t depth_dtype, const uint8_t *d_rgb, int n_frames,
                              int height, int width, void *d_depth_out, uint8_t *d_rgb_out);

@@ -4,10 +4,10 @@
 //
 // Nothing here holds a word per pool voxel.  Per unit: a 4096-bit site mask in dump bit order (bit x * 256 + y * 16 + z, i.e. 256
 // rows of 16 z bits), the exclusive popcount prefix of its rows, its count and its base.  The units are ranked by key on the host
-// (as hv_tsdf_dump and hv_tsdf_pack do), the bases are the prefix sum of the counts in that order, and
+// (hv_tsdf_key_order, the order of hv_tsdf_dump and hv_tsdf_pack), the bases are the prefix sum of the counts in that order, and
 //   index(site) = base[unit] + rowpre[row] + popcount(row bits below z)
 // numbers the sites in the order of the site list: the parent array and the list come from the same masks.
-//   k_cc_sites    one workgroup per unit: hv_tsdf_distance_field's classification (18^3 state halo in LDS, seven hash probes), the
+//   k_cc_sites    one workgroup per unit: the classification halo of hv_tsdf_sites.h (18^3 states in LDS, six hash probes), the
 //                 row masks, their prefix, the count
 //   k_cc_scan     one workgroup: bases in key order, the number of sites
 //   k_cc_local    one workgroup per unit: union-find over the unit's 4096 voxels in LDS (atomicMin towards the smaller index, 13
@@ -25,36 +25,23 @@
 // Every link loop strictly lowers the larger of its two indices, so it ends; no wave waits for another; there is no loop over
 // propagation rounds on the host at all.
 #include <algorithm>
-#include <array>
 #include <cmath>
 #include <vector>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "hv_common.h"
+#include "hv_tsdf_sites.h"
 
 namespace {
 
 constexpr int CC_ROWS = HV_TSDF_RR;   // 16-bit z rows of a unit, row = x * 16 + y
-constexpr int CC_H = HV_TSDF_R + 2;   // side of the state halo
 constexpr int CC_W = 3 * HV_TSDF_R;   // side of the 3 x 3 x 3 unit neighbourhood in voxels
 enum { CC_R_SITES = 0, CC_R_COMPONENTS = 1, CC_R_LARGEST = 2, CC_R_COMP_REMOVED = 3, CC_R_SITES_REMOVED = 4, CC_R_VOXELS_RESET = 5,
        CC_R_UNITS_CHANGED = 6, CC_R_UNITS_EMPTIED = 7, CC_R_WORDS = 8 };
 enum { CC_LO = 0, CC_HI = 3, CC_SY = 6, CC_SZ = 7, CC_BOX_ROWS = 8 }; // rows of the per-component int32 table [8][C]
 
-__device__ __forceinline__ uint32_t cc_state(uint32_t w, float f, double thr) {
-    return (double)w > thr ? (f <= 0.0f ? 2u : 1u) : 0u; // HV_DIST_INSIDE, HV_DIST_FREE, HV_DIST_UNKNOWN
-}
-__device__ __forceinline__ int cc_halo(int x, int y, int z) { return ((x + 1) * CC_H + (y + 1)) * CC_H + (z + 1); }
 __device__ __forceinline__ uint32_t cc_below(uint32_t row, int z) { return (uint32_t)__popc(row & ((1u << z) - 1u)); }
-
-// pool index of unit (kx, ky, kz), or -1 when the map does not hold it
-__device__ __forceinline__ int32_t cc_unit_of(const HvTable &table, int32_t used, int32_t kx, int32_t ky, int32_t kz) {
-    if (!hv_key_in_range(kx, ky, kz)) return -1;
-    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-    return idx >= 0 && idx < used ? idx : -1;
-}
 
 // exclusive prefix of v over the 256 threads of the workgroup; *total = the sum.  s_w: 4 ints of LDS, used once per kernel.
 __device__ __forceinline__ int cc_block_scan(int v, int *s_w, int *total) {
@@ -79,66 +66,21 @@ __device__ __forceinline__ int cc_block_scan(int v, int *s_w, int *total) {
 
 __global__ __launch_bounds__(256) void k_cc_sites(HvTable table, const char *__restrict__ pool, int32_t used, double thr,
                                                   uint16_t *__restrict__ mask, uint16_t *__restrict__ rowpre, uint32_t *__restrict__ count) {
-    __shared__ uint8_t st[CC_H * CC_H * CC_H];
+    __shared__ uint8_t st[HV_SITE_HALO_CELLS];
     __shared__ int32_t unit_idx[7]; // the unit, then its -x +x -y +y -z +z neighbours
     __shared__ int s_w[4];
     const int t = (int)threadIdx.x;
     const int32_t self = (int32_t)blockIdx.x;
     int32_t ux, uy, uz;
     hv_unpack_key(table.block_keys[self], ux, uy, uz);
-    if (t < 7) unit_idx[t] = t == 0 ? self : cc_unit_of(table, used, ux + (t == 2) - (t == 1), uy + (t == 4) - (t == 3), uz + (t == 6) - (t == 5));
+    hv_site_halo_units(table, ux, uy, uz, used, self, unit_idx);
     __syncthreads();
-    const char *unit = pool + (size_t)self * HV_TSDF_UNIT_BYTES;
-    uint4 w[4];
-    float4 f[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) w[q] = ((const uint4 *)(unit + HV_TSDF_PLANE_BYTES))[q * 256 + t];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) f[q] = ((const float4 *)unit)[q * 256 + t];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int word = (q * 256 + t) * 4; // z * 256 + x * 16 + y: four consecutive y
-        const int at = cc_halo((word >> 4) & 15, word & 15, word >> 8);
-        st[at] = (uint8_t)cc_state(w[q].x, f[q].x, thr);
-        st[at + CC_H] = (uint8_t)cc_state(w[q].y, f[q].y, thr);
-        st[at + 2 * CC_H] = (uint8_t)cc_state(w[q].z, f[q].z, thr);
-        st[at + 3 * CC_H] = (uint8_t)cc_state(w[q].w, f[q].w, thr);
-    }
-    { // the six faces: 256 voxels each, one per thread
-        const int a = t >> 4, b = t & 15;
-        const int word[6] = {hv_tsdf_word(15, b, a), hv_tsdf_word(0, b, a), hv_tsdf_word(b, 15, a),
-                             hv_tsdf_word(b, 0, a), hv_tsdf_word(a, b, 15), hv_tsdf_word(a, b, 0)};
-        uint32_t s[6];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const int32_t nb = unit_idx[1 + k];
-            uint32_t fw = 0u;
-            float ff = 0.0f;
-            if (nb >= 0) {
-                const char *nu = pool + (size_t)nb * HV_TSDF_UNIT_BYTES;
-                fw = ((const uint32_t *)(nu + HV_TSDF_PLANE_BYTES))[word[k]];
-                ff = ((const float *)nu)[word[k]];
-            }
-            s[k] = cc_state(fw, ff, thr);
-        }
-        st[cc_halo(-1, b, a)] = (uint8_t)s[0];
-        st[cc_halo(16, b, a)] = (uint8_t)s[1];
-        st[cc_halo(b, -1, a)] = (uint8_t)s[2];
-        st[cc_halo(b, 16, a)] = (uint8_t)s[3];
-        st[cc_halo(a, b, -1)] = (uint8_t)s[4];
-        st[cc_halo(a, b, 16)] = (uint8_t)s[5];
-    }
+    hv_site_halo_load(pool, unit_idx, thr, st);
     __syncthreads();
     const int x = t >> 4, y = t & 15;
     uint32_t row = 0u;
 #pragma unroll 4
-    for (int z = 0; z < HV_TSDF_R; ++z) {
-        const int at = cc_halo(x, y, z);
-        const uint32_t s = st[at], other = s ^ 3u; // FREE <-> INSIDE; UNKNOWN gives 3, which no voxel holds
-        const bool site = st[at - CC_H * CC_H] == other || st[at + CC_H * CC_H] == other || st[at - CC_H] == other ||
-                          st[at + CC_H] == other || st[at - 1] == other || st[at + 1] == other;
-        row |= site ? 1u << z : 0u;
-    }
+    for (int z = 0; z < HV_TSDF_R; ++z) row |= hv_site_is_site(st, hv_site_halo_at(x, y, z)) ? 1u << z : 0u;
     int total;
     const int pre = cc_block_scan(__popc(row), s_w, &total);
     mask[(size_t)self * CC_ROWS + t] = (uint16_t)row;
@@ -268,7 +210,7 @@ __global__ __launch_bounds__(256) void k_cc_cross(HvTable table, int32_t used, c
     if (t < 27) {
         int32_t ux, uy, uz;
         hv_unpack_key(table.block_keys[self], ux, uy, uz);
-        nb[t] = t == 13 ? self : cc_unit_of(table, used, ux + t / 9 - 1, uy + (t / 3) % 3 - 1, uz + t % 3 - 1);
+        nb[t] = t == 13 ? self : hv_tsdf_unit_index(table, ux + t / 9 - 1, uy + (t / 3) % 3 - 1, uz + t % 3 - 1, used);
     }
     __syncthreads();
     const uint32_t mine = mask[(size_t)self * CC_ROWS + t];
@@ -518,7 +460,7 @@ __global__ __launch_bounds__(256) void k_cc_reset(HvTable table, char *__restric
     if (t < 27) {
         int32_t ux, uy, uz;
         hv_unpack_key(key, ux, uy, uz);
-        int32_t idx = t == 13 ? self : cc_unit_of(table, used, ux + t / 9 - 1, uy + (t / 3) % 3 - 1, uz + t % 3 - 1);
+        int32_t idx = t == 13 ? self : hv_tsdf_unit_index(table, ux + t / 9 - 1, uy + (t / 3) % 3 - 1, uz + t % 3 - 1, used);
         if (idx >= 0 && t != 13 && margin == 0) idx = -1; // margin 0: the neighbours do not reach in
         nb[t] = idx;
     }
@@ -618,21 +560,6 @@ __global__ __launch_bounds__(256) void k_cc_reset(HvTable table, char *__restric
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------
-struct CcScratch { // device memory of one call, freed when it returns
-    std::vector<void *> held;
-    ~CcScratch() {
-        for (void *p : held) (void)hipFree(p);
-    }
-    template <typename T>
-    hipError_t get(T **p, size_t n) {
-        void *raw = nullptr;
-        const hipError_t e = hipMalloc(&raw, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) held.push_back(raw);
-        *p = (T *)raw;
-        return e;
-    }
-};
-
 struct CcLabels {
     int64_t units = 0, sites = 0, components = 0;
     uint16_t *mask = nullptr, *rowpre = nullptr;
@@ -643,10 +570,8 @@ struct CcLabels {
 
 int cc_check(hv_volume *v, double weight_threshold, const char *fn) {
     HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "%s: null volume", fn);
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", fn);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "%s: the volume is tile-sharded (it holds partial sums of a voxel)", fn);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: components cross ranks (owner-sharded: merge or gather first)", fn);
+    const int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
+    if (rc != HV_OK) return rc;
     HV_REQUIRE(std::isfinite(weight_threshold) && weight_threshold >= 0.0, HV_ERR_INVALID, "%s: weight_threshold must be finite and >= 0", fn);
     return HV_OK;
 }
@@ -661,29 +586,18 @@ void cc_launch_stats(hv_volume *v, const CcLabels &L) {
 }
 
 // Sites, union-find, component slots, sizes (and boxes and seeds when `seeds`).  Drains the pipeline and waits for the GPU.
-int cc_label(hv_volume *v, double thr, bool seeds, CcScratch &S, CcLabels &L, const char *fn) {
-    HV_HIP(hipSetDevice(v->device));
-    if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
-    v->pipe_armed = false;
-    int rc = hv_read_counters(v); // synchronises the stream
+int cc_label(hv_volume *v, double thr, bool seeds, HvScratch &S, CcLabels &L, const char *fn) {
+    int64_t used = 0;
+    int rc = hv_tsdf_drain(v, fn, false, &used);
     if (rc != HV_OK) return rc;
-    const int64_t used = std::min<int64_t>(std::max<int32_t>(v->h_counters[HV_CNT_BLOCKS], 0), v->cfg.max_blocks);
     L.units = used;
     HV_HIP(S.get(&L.result, CC_R_WORDS));
     HV_HIP(hipMemsetAsync(L.result, 0, CC_R_WORDS * sizeof(unsigned long long), v->stream));
     if (used == 0) return HV_OK;
-    // rank the units by key, as hv_tsdf_dump does: 8 bytes per unit to the host, 4 back
-    std::vector<unsigned long long> keys((size_t)used);
-    HV_HIP(hipMemcpyAsync(keys.data(), v->table.block_keys, 8 * (size_t)used, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipStreamSynchronize(v->stream));
-    std::vector<std::array<int32_t, 4>> ranked((size_t)used);
-    for (int64_t u = 0; u < used; ++u) {
-        hv_unpack_key(keys[(size_t)u], ranked[(size_t)u][0], ranked[(size_t)u][1], ranked[(size_t)u][2]);
-        ranked[(size_t)u][3] = (int32_t)u;
-    }
-    std::sort(ranked.begin(), ranked.end());
-    std::vector<int32_t> order((size_t)used);
-    for (int64_t r = 0; r < used; ++r) order[(size_t)r] = ranked[(size_t)r][3];
+    // rank the units by key: 8 bytes per unit to the host, 4 back
+    std::vector<int32_t> order;
+    rc = hv_tsdf_key_order(v, used, order, nullptr);
+    if (rc != HV_OK) return rc;
     HV_HIP(S.get(&L.mask, (size_t)used * CC_ROWS));
     HV_HIP(S.get(&L.rowpre, (size_t)used * CC_ROWS));
     HV_HIP(S.get(&L.count, (size_t)used));
@@ -756,7 +670,7 @@ extern "C" int hv_tsdf_surface_components(hv_volume *v, double weight_threshold,
     const bool want_table = seed != nullptr || sites != nullptr || lo != nullptr || hi != nullptr;
     const bool want_list = site_index != nullptr || site_label != nullptr;
     HV_REQUIRE((!want_table || component_cap >= 0) && (!want_list || site_cap >= 0), HV_ERR_INVALID, "%s: negative capacity", fn);
-    CcScratch S;
+    HvScratch S;
     CcLabels L;
     rc = cc_label(v, weight_threshold, want_table || site_label != nullptr, S, L, fn);
     if (rc != HV_OK) return rc;
@@ -843,7 +757,7 @@ extern "C" int hv_tsdf_remove_components(hv_volume *v, double weight_threshold, 
     HV_REQUIRE(min_sites >= 1, HV_ERR_INVALID, "%s: min_sites must be >= 1, got %lld", fn, (long long)min_sites);
     HV_REQUIRE(margin >= 0 && margin <= HV_COMPONENTS_MAX_MARGIN, HV_ERR_INVALID, "%s: margin %d is outside 0..%d", fn, (int)margin,
                HV_COMPONENTS_MAX_MARGIN);
-    CcScratch S;
+    HvScratch S;
     CcLabels L;
     rc = cc_label(v, weight_threshold, false, S, L, fn);
     if (rc != HV_OK) return rc;

@@ -5,6 +5,7 @@
 #include <immintrin.h>
 
 #include <algorithm>
+#include <array>
 #include <condition_variable>
 #include <functional>
 #include <mutex>
@@ -66,6 +67,47 @@ int hv_read_counters(hv_volume *v) {
     HV_HIP(hipMemcpyAsync(v->h_counters, v->table.counters, sizeof(int32_t) * HV_CNT_COUNT,
                           hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+int hv_tsdf_require_whole_map(const hv_volume *v, const char *fn, const char *subject) {
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: %s is not in TSDF mode", fn, subject);
+    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
+               "%s: %s is tile-sharded (it holds partial sums of a voxel)", fn, subject);
+    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: %s is owner-sharded (it holds a part of the map's units: merge or gather first)", fn,
+               subject);
+    return HV_OK;
+}
+
+int hv_tsdf_drain(hv_volume *v, const char *fn, bool refuse_overflow, int64_t *used) {
+    HV_HIP(hipSetDevice(v->device));
+    if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
+    v->pipe_armed = false;
+    const int rc = hv_read_counters(v); // synchronises the stream
+    if (rc != HV_OK) return rc;
+    if (used != nullptr) *used = std::min<int64_t>(std::max<int32_t>(v->h_counters[HV_CNT_BLOCKS], 0), v->cfg.max_blocks);
+    HV_REQUIRE(!refuse_overflow || (v->h_counters[HV_CNT_OVERFLOW] == 0 && !v->overflow_latched), HV_ERR_CAPACITY,
+               "%s: the volume's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)", fn);
+    return HV_OK;
+}
+
+int hv_tsdf_key_order(hv_volume *v, int64_t used, std::vector<int32_t> &order, std::vector<int32_t> *xyz_in_order) {
+    const size_t n = (size_t)used;
+    std::vector<unsigned long long> keys(n);
+    if (n > 0) HV_HIP(hipMemcpyAsync(keys.data(), v->table.block_keys, 8 * n, hipMemcpyDeviceToHost, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    std::vector<std::array<int32_t, 4>> ranked(n); // (x, y, z, pool index): sorted as records, the keys are distinct
+    for (size_t i = 0; i < n; ++i) {
+        hv_unpack_key(keys[i], ranked[i][0], ranked[i][1], ranked[i][2]);
+        ranked[i][3] = (int32_t)i;
+    }
+    std::sort(ranked.begin(), ranked.end());
+    order.resize(n);
+    if (xyz_in_order != nullptr) xyz_in_order->resize(n * 3);
+    for (size_t r = 0; r < n; ++r) {
+        order[r] = ranked[r][3];
+        if (xyz_in_order != nullptr) memcpy(&(*xyz_in_order)[r * 3], ranked[r].data(), 12);
+    }
     return HV_OK;
 }
 

@@ -3,10 +3,10 @@
 // windowed passes, cap, square root and sign) is written once in include/hipvol.h; tests/distance_reference.py restates it in numpy.
 //
 // Four launches over a grid of nx x ny x nz cells (z fastest), all integer until the last instruction:
-//   k_dist_classify   one workgroup per 16^3 brick of the box, aligned to the map's units: seven hash probes (the unit and its six face
-//                     neighbours), the unit's weight plane, then its tsdf plane, as 16-byte loads, the six neighbour faces, the states
-//                     in an 18^3 LDS halo; writes the class byte and the seed (0 at a site, DF_INF elsewhere).  A brick whose unit is
-//                     not held writes UNKNOWN / DF_INF and reads nothing of the pool.
+//   k_dist_classify   one workgroup per 16^3 brick of the box, aligned to the map's units: the classification halo of hv_tsdf_sites.h
+//                     (seven hash probes, the unit's planes, the six neighbour faces, the states in an 18^3 LDS halo); clips to the
+//                     box and writes the class byte and the seed (0 at a site, DF_INF elsewhere).  A brick whose unit is not held
+//                     writes UNKNOWN / DF_INF and reads nothing of the pool.
 //   k_dist_scan_x     one lane per (y, z) column: a forward and a backward scan along x (distance to the last site seen), no window
 //                     walk; for a fixed x the lanes of a wave read and write consecutive words.
 //   k_dist_pass_y     one workgroup per (x, group of ZT consecutive z): the whole ny x ZT slab staged in LDS (ZT * 4 bytes contiguous
@@ -19,11 +19,11 @@
 
 #include "hv_common.h"
 #include "hv_tsdf_device.h"
+#include "hv_tsdf_sites.h"
 
 namespace {
 
 constexpr uint32_t DF_INF = 0x3fffffffu; // "no site within the window": above every sum of three squares <= 3 * 1024^2, and + 1024^2 fits
-constexpr int DF_H = HV_TSDF_R + 2;      // side of the state halo
 constexpr int DF_LINE_WORDS = 8192;      // LDS words a pass aims to stage per workgroup (32 KiB: several workgroups per CU)
 constexpr int DF_LINE_WORDS_MAX = 16384; // ... and never exceeds (a 4096-cell line times the narrowest slab, 64 KiB)
 enum { DF_N_UNKNOWN = 0, DF_N_FREE = 1, DF_N_INSIDE = 2, DF_N_SITES = 3, DF_N_FAR = 4, DF_N_COUNT = 5 };
@@ -35,26 +35,13 @@ struct HvDistGrid {
     int32_t R;
 };
 
-__device__ __forceinline__ uint32_t df_state(uint32_t w, float f, double thr) {
-    return (double)w > thr ? (f <= 0.0f ? (uint32_t)HV_DIST_INSIDE : (uint32_t)HV_DIST_FREE) : (uint32_t)HV_DIST_UNKNOWN;
-}
-__device__ __forceinline__ int df_halo(int x, int y, int z) { return ((x + 1) * DF_H + (y + 1)) * DF_H + (z + 1); }
-
 __global__ __launch_bounds__(256) void k_dist_classify(HvTable table, const char *__restrict__ pool, HvDistGrid G, double thr,
                                                        uint8_t *__restrict__ cls, uint32_t *__restrict__ seed) {
-    __shared__ uint8_t st[DF_H * DF_H * DF_H];
+    __shared__ uint8_t st[HV_SITE_HALO_CELLS];
     __shared__ int32_t unit_idx[7]; // the brick's unit, then its -x +x -y +y -z +z neighbours
     const int t = (int)threadIdx.x;
     const int32_t ux = G.u[0] + (int32_t)blockIdx.x, uy = G.u[1] + (int32_t)blockIdx.y, uz = G.u[2] + (int32_t)blockIdx.z;
-    if (t < 7) {
-        const int32_t kx = ux + (t == 2) - (t == 1), ky = uy + (t == 4) - (t == 3), kz = uz + (t == 6) - (t == 5);
-        int32_t idx = -1;
-        if (hv_key_in_range(kx, ky, kz)) {
-            const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-            idx = slot >= 0 ? table.vals[slot] : -1;
-        }
-        unit_idx[t] = idx;
-    }
+    hv_site_halo_units(table, ux, uy, uz, INT32_MAX, -1, unit_idx);
     __syncthreads();
     const int32_t self = unit_idx[0];
     // cells of this thread: one (y, z) of the brick, all x - a wave writes runs of 16 consecutive z
@@ -62,51 +49,7 @@ __global__ __launch_bounds__(256) void k_dist_classify(HvTable table, const char
     const int32_t j = uy * HV_TSDF_R + ly - G.o[1], k = uz * HV_TSDF_R + lz - G.o[2];
     const bool in_yz = j >= 0 && j < G.n[1] && k >= 0 && k < G.n[2];
     const int32_t i0 = ux * HV_TSDF_R - G.o[0];
-    if (self >= 0) {
-        const char *unit = pool + (size_t)self * HV_TSDF_UNIT_BYTES;
-        uint4 w[4];
-        float4 f[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = ((const uint4 *)(unit + HV_TSDF_PLANE_BYTES))[q * 256 + t];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) f[q] = ((const float4 *)unit)[q * 256 + t];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int word = (q * 256 + t) * 4; // z * 256 + x * 16 + y: four consecutive y
-            const int at = df_halo((word >> 4) & 15, word & 15, word >> 8);
-            st[at] = (uint8_t)df_state(w[q].x, f[q].x, thr);
-            st[at + DF_H] = (uint8_t)df_state(w[q].y, f[q].y, thr);
-            st[at + 2 * DF_H] = (uint8_t)df_state(w[q].z, f[q].z, thr);
-            st[at + 3 * DF_H] = (uint8_t)df_state(w[q].w, f[q].w, thr);
-        }
-        // the six faces: 256 voxels each, one per thread (a = t >> 4, b = t & 15)
-        const int a = t >> 4, b = t & 15;
-        uint32_t fw[6];
-        float ff[6];
-        int word[6];
-        word[0] = hv_tsdf_word(15, b, a);
-        word[1] = hv_tsdf_word(0, b, a);
-        word[2] = hv_tsdf_word(b, 15, a);
-        word[3] = hv_tsdf_word(b, 0, a);
-        word[4] = hv_tsdf_word(a, b, 15);
-        word[5] = hv_tsdf_word(a, b, 0);
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            const int32_t nb = unit_idx[1 + s];
-            fw[s] = nb >= 0 ? ((const uint32_t *)(pool + (size_t)nb * HV_TSDF_UNIT_BYTES + HV_TSDF_PLANE_BYTES))[word[s]] : 0u;
-        }
-#pragma unroll
-        for (int s = 0; s < 6; ++s) {
-            const int32_t nb = unit_idx[1 + s];
-            ff[s] = nb >= 0 ? ((const float *)(pool + (size_t)nb * HV_TSDF_UNIT_BYTES))[word[s]] : 0.0f;
-        }
-        st[df_halo(-1, b, a)] = (uint8_t)df_state(fw[0], ff[0], thr);
-        st[df_halo(16, b, a)] = (uint8_t)df_state(fw[1], ff[1], thr);
-        st[df_halo(b, -1, a)] = (uint8_t)df_state(fw[2], ff[2], thr);
-        st[df_halo(b, 16, a)] = (uint8_t)df_state(fw[3], ff[3], thr);
-        st[df_halo(a, b, -1)] = (uint8_t)df_state(fw[4], ff[4], thr);
-        st[df_halo(a, b, 16)] = (uint8_t)df_state(fw[5], ff[5], thr);
-    }
+    if (self >= 0) hv_site_halo_load(pool, unit_idx, thr, st);
     __syncthreads();
     if (!in_yz) return;
 #pragma unroll 4
@@ -115,11 +58,8 @@ __global__ __launch_bounds__(256) void k_dist_classify(HvTable table, const char
         if (i < 0 || i >= G.n[0]) continue;
         uint32_t c = HV_DIST_UNKNOWN;
         if (self >= 0) {
-            const int at = df_halo(lx, ly, lz);
-            const uint32_t s = st[at], other = s ^ 3u; // FREE <-> INSIDE; UNKNOWN gives 3, which no voxel holds
-            const bool site = st[at - DF_H * DF_H] == other || st[at + DF_H * DF_H] == other || st[at - DF_H] == other ||
-                              st[at + DF_H] == other || st[at - 1] == other || st[at + 1] == other;
-            c = s | (site ? (uint32_t)HV_DIST_SITE : 0u);
+            const int at = hv_site_halo_at(lx, ly, lz);
+            c = st[at] | (hv_site_is_site(st, at) ? (uint32_t)HV_DIST_SITE : 0u);
         }
         const int64_t cell = ((int64_t)i * G.n[1] + j) * G.n[2] + k;
         cls[cell] = (uint8_t)c;
@@ -226,10 +166,10 @@ extern "C" int hv_tsdf_distance_field(hv_volume *v, const hv_distance_params *p,
                                       hv_distance_stats *stats, int32_t loc) {
     const char *fn = "hv_tsdf_distance_field";
     HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "%s: null argument", fn);
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", fn);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "%s: the volume is tile-sharded (it holds partial sums of a voxel)", fn);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: the query needs the whole volume (owner-sharded: merge or gather first)", fn);
+    {
+        const int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
+        if (rc != HV_OK) return rc;
+    }
     HV_REQUIRE(p != nullptr, HV_ERR_INVALID, "%s: null params", fn);
     for (int a = 0; a < 3; ++a) {
         HV_REQUIRE(p->shape[a] >= 1 && p->shape[a] <= HV_DIST_MAX_SHAPE, HV_ERR_INVALID, "%s: shape[%d] = %d is outside 1..%d", fn, a,

@@ -10,13 +10,14 @@
 //   claim       the kept keys enter the destination's table (hv_table_insert); the pool grows as for integrate  k_merge_claim
 //   sweep       one workgroup per kept unit, lane -> (x, 4 y's), a wave per z plane: sample, update, stamp     k_merge_sweep
 // Probe and sweep resolve the 3 x 3 x 3 source units a destination unit can reach into LDS once (27 hash probes); a voxel fetch is
-// then integer arithmetic and loads.  Probe and sweep evaluate the same predicate with the same instructions (hv_merge_locate /
-// hv_merge_nearest), so every kept unit gets at least one voxel and no other unit is claimed.
+// then integer arithmetic and loads; the cell rule, the corner order and the trilinear form are hv_tsdf_cell.h's.  Probe and sweep
+// evaluate the same predicate with the same instructions (hv_merge_locate / hv_merge_nearest), so every kept unit gets at least
+// one voxel and no other unit is claimed.
 #include <algorithm>
 #include <cmath>
 
 #include "hv_common.h"
-#include "hv_tsdf_sample.h"
+#include "hv_tsdf_cell.h"
 
 namespace {
 
@@ -31,23 +32,16 @@ struct HvMergeXf {
     double voxel_length;
 };
 
-// Destination voxel (global index gv) -> its cell in the source lattice.  false: the point lies outside every representable source
-// voxel (|g| >= 1e9 or not finite) - no source voxel there is observed.
+// Destination voxel (global index gv) -> its cell in the source lattice (hv_cell_locate).  false: the point lies outside every
+// representable source voxel - no source voxel there is observed.
 __device__ __forceinline__ bool hv_merge_locate(const HvMergeXf &X, int32_t gx, int32_t gy, int32_t gz, int32_t *g0, double *r) {
     const double d0 = ((double)gx + 0.5) * X.voxel_length - X.t[0];
     const double d1 = ((double)gy + 0.5) * X.voxel_length - X.t[1];
     const double d2 = ((double)gz + 0.5) * X.voxel_length - X.t[2];
-    bool ok = true;
+    double p[3];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double p = (X.rt[a * 3 + 0] * d0 + X.rt[a * 3 + 1] * d1) + X.rt[a * 3 + 2] * d2;
-        const double g = p / X.voxel_length - 0.5;
-        ok = ok && fabs(g) < 1.0e9;
-        const double f = floor(g);
-        g0[a] = ok ? (int32_t)f : 0;
-        r[a] = g - f;
-    }
-    return ok;
+    for (int a = 0; a < 3; ++a) p[a] = (X.rt[a * 3 + 0] * d0 + X.rt[a * 3 + 1] * d1) + X.rt[a * 3 + 2] * d2;
+    return hv_cell_locate(p, X.voxel_length, g0, r);
 }
 
 // The source units around a destination unit: pool indices of units base + {0,1,2}^3 (-1 = absent) in LDS.
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(256) void k_merge_candidates(const unsigned long lo
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const double glo = lo[a] / X.voxel_length - 0.5 - 1.0e-3, ghi = hi[a] / X.voxel_length - 0.5 + 1.0e-3;
-        ok = ok && fabs(glo) < 1.0e9 && fabs(ghi) < 1.0e9;
+        ok = ok && fabs(glo) < HV_CELL_LIMIT && fabs(ghi) < HV_CELL_LIMIT;
         const double a0 = floor(ceil(glo) / (double)HV_TSDF_R), a1 = floor(floor(ghi) / (double)HV_TSDF_R); // units of the first / last voxel centre inside
         ulo[a] = ok ? (int32_t)a0 : 0;
         n[a] = ok ? (int32_t)(a1 - a0) + 1 : 0; // <= 3: the box spans 16 sqrt(3) + 0.002 < 32 voxels
@@ -196,11 +190,6 @@ __global__ __launch_bounds__(256) void k_merge_claim(HvTable dst, const unsigned
     if (i < n) hv_table_insert(dst, keep[i]);
 }
 
-__device__ __forceinline__ double hv_merge_lerp(const double *r, const double *f) {
-    return (1 - r[0]) * ((1 - r[1]) * ((1 - r[2]) * f[0] + r[2] * f[4]) + r[1] * ((1 - r[2]) * f[3] + r[2] * f[7])) +
-           r[0] * ((1 - r[1]) * ((1 - r[2]) * f[1] + r[2] * f[5]) + r[1] * ((1 - r[2]) * f[2] + r[2] * f[6]));
-}
-
 // One workgroup per kept destination unit.  A wave owns the planes z = wave, wave + 4, ...; a lane owns (x, y0 .. y0 + 3), so the
 // destination's five planes are read and written in 1 KiB bursts of 16-byte accesses - and only where one of the lane's four voxels
 // is updated (most voxels of a unit lie off the observed band).  Source fetches are gathers: neighbours along the source's y are
@@ -248,7 +237,8 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
             bool all = true;
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const int sx = (i == 1 || i == 2 || i == 5 || i == 6), sy = (i == 2 || i == 3 || i == 6 || i == 7), sz = i >= 4;
+                int sx, sy, sz;
+                hv_cell_corner(i, sx, sy, sz);
                 hv_merge_voxel(S, g0[0] + sx, g0[1] + sy, g0[2] + sz, cidx[i], cword[i]);
                 cw[i] = hv_merge_weight(S, cidx[i], cword[i]);
                 all = all && cw[i] != 0u;
@@ -258,13 +248,13 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
                 double f[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) f[i] = (double)((const float *)(src_pool + (int64_t)cidx[i] * HV_TSDF_UNIT_BYTES))[cword[i]];
-                ts[q] = hv_merge_lerp(r, f);
+                ts[q] = hv_cell_lerp(r, f);
 #pragma unroll
                 for (int c = 0; c < 3; ++c) {
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
                         f[i] = (double)((const uint32_t *)(src_pool + (int64_t)cidx[i] * HV_TSDF_UNIT_BYTES + (2 + c) * HV_TSDF_PLANE_BYTES))[cword[i]] / (double)cw[i];
-                    mean[c] = hv_merge_lerp(r, f);
+                    mean[c] = hv_cell_lerp(r, f);
                 }
                 n_tri += 1;
             } else {
@@ -313,21 +303,14 @@ __global__ __launch_bounds__(256) void k_merge_sweep(const unsigned long long *_
     }
 }
 
-int merge_check_volume(const hv_volume *v, const char *which) {
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_integrate_volume: %s is not in TSDF mode", which);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "hv_tsdf_integrate_volume: %s is tile-sharded (it holds partial sums of a voxel)", which);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "hv_tsdf_integrate_volume: %s is owner-sharded (it holds a part of the map's units)", which);
-    return HV_OK;
-}
-
 } // namespace
 
 extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const double *T, hv_merge_stats *stats) {
     HV_REQUIRE(dst != nullptr && src != nullptr && T != nullptr, HV_ERR_INVALID, "hv_tsdf_integrate_volume: null argument");
-    int rc = merge_check_volume(dst, "the destination");
+    const char *fn = "hv_tsdf_integrate_volume";
+    int rc = hv_tsdf_require_whole_map(dst, fn, "the destination");
     if (rc != HV_OK) return rc;
-    rc = merge_check_volume(src, "the source");
+    rc = hv_tsdf_require_whole_map(src, fn, "the source");
     if (rc != HV_OK) return rc;
     HV_REQUIRE(dst != src, HV_ERR_INVALID, "hv_tsdf_integrate_volume: source and destination are the same volume");
     HV_REQUIRE(dst->cfg.voxel_size == src->cfg.voxel_size && dst->cfg.sdf_trunc == src->cfg.sdf_trunc && dst->cfg.block_size == src->cfg.block_size,
@@ -357,18 +340,13 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
                "hv_tsdf_integrate_volume: the transformation is not rigid (|R^T R - I|_inf = %.3g, det = %.3g)", ortho, det);
     X.voxel_length = dst->cfg.voxel_size;
 
-    HV_HIP(hipSetDevice(dst->device));
     // drain both batch pipelines; the source's pending work is done before the destination's stream reads it
-    for (hv_volume *v : {src, dst}) {
-        if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
-        v->pipe_armed = false;
-        rc = hv_read_counters(v); // synchronises the stream
-        if (rc != HV_OK) return rc;
-    }
+    int64_t src_used = 0, dst_before = 0;
+    rc = hv_tsdf_drain(src, fn, false, &src_used);
+    if (rc == HV_OK) rc = hv_tsdf_drain(dst, fn, false, &dst_before);
+    if (rc != HV_OK) return rc;
     HV_REQUIRE(src->h_counters[HV_CNT_OVERFLOW] == 0 && !src->overflow_latched, HV_ERR_CAPACITY,
-               "hv_tsdf_integrate_volume: the source's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)");
-    const int64_t src_used = std::min<int64_t>(std::max<int32_t>(src->h_counters[HV_CNT_BLOCKS], 0), src->cfg.max_blocks);
-    const int64_t dst_before = std::min<int64_t>(std::max<int32_t>(dst->h_counters[HV_CNT_BLOCKS], 0), dst->cfg.max_blocks);
+               "%s: the source's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)", fn);
     if (stats != nullptr) *stats = hv_merge_stats{0, 0, 0, 0, 0};
     if (src_used == 0) return HV_OK;
 
@@ -378,16 +356,16 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
     HV_REQUIRE(cap < (1ll << 30), HV_ERR_CAPACITY, "hv_tsdf_integrate_volume: %lld source units are too many", (long long)src_used);
     uint64_t set_cap = 1024;
     while (set_cap < 2 * (uint64_t)cap) set_cap <<= 1;
-    void *scratch = nullptr;
-    HV_HIP(hipMalloc(&scratch, HV_MERGE_HDR + 8 * (size_t)(2 * cap + (int64_t)set_cap)));
+    HvScratch S; // (every return below has waited for the stream, or follows a device error)
+    char *scratch = nullptr;
+    HV_HIP(S.get(&scratch, HV_MERGE_HDR + 8 * (size_t)(2 * cap + (int64_t)set_cap)));
     int32_t *d_cnt = (int32_t *)scratch;
-    unsigned long long *d_cnt64 = (unsigned long long *)((char *)scratch + 128);
-    unsigned long long *d_cand = (unsigned long long *)((char *)scratch + HV_MERGE_HDR);
+    unsigned long long *d_cnt64 = (unsigned long long *)(scratch + 128);
+    unsigned long long *d_cand = (unsigned long long *)(scratch + HV_MERGE_HDR);
     unsigned long long *d_keep = d_cand + cap;
     unsigned long long *d_set = d_keep + cap;
     int32_t h_cnt[HV_MERGE_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
     auto fail = [&](const char *what, hipError_t e) {
-        (void)hipFree(scratch);
         hv_set_error("hv_tsdf_integrate_volume: %s failed: %s", what, hipGetErrorString(e));
         return HV_ERR_DEVICE;
     };
@@ -405,11 +383,8 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
                        (const char *)src->pool, (int32_t)src_used, X, d_set, (uint32_t)(set_cap - 1), d_cand, (int32_t)cap, d_cnt);
     if ((e = read_counts()) != hipSuccess) return fail("the candidate pass", e);
     const int64_t n_cand = h_cnt[HV_MERGE_N_CAND];
-    if (h_cnt[HV_MERGE_SET_FULL] != 0 || n_cand > cap) {
-        (void)hipFree(scratch);
-        hv_set_error("hv_tsdf_integrate_volume: the candidate set overflowed (%lld candidates, room for %lld)", (long long)n_cand, (long long)cap);
-        return HV_ERR_CAPACITY;
-    }
+    HV_REQUIRE(h_cnt[HV_MERGE_SET_FULL] == 0 && n_cand <= cap, HV_ERR_CAPACITY,
+               "hv_tsdf_integrate_volume: the candidate set overflowed (%lld candidates, room for %lld)", (long long)n_cand, (long long)cap);
     if (stats != nullptr) stats->units_source = h_cnt[HV_MERGE_N_SOURCE];
     int64_t n_keep = 0;
     if (n_cand > 0) {
@@ -418,10 +393,7 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
         if ((e = read_counts()) != hipSuccess) return fail("the probe pass", e);
         n_keep = h_cnt[HV_MERGE_N_KEEP];
     }
-    if (n_keep == 0) { // no destination voxel has an observed source voxel nearest: the destination is left exactly as it was
-        (void)hipFree(scratch);
-        return HV_OK;
-    }
+    if (n_keep == 0) return HV_OK; // no destination voxel has an observed source voxel nearest: the destination is left exactly as it was
     // claim the kept units.  The gate refuses a latched overflow and grows a pool that is more than half full; whether it asks
     // for a checked claim does not matter here: the claim is ALWAYS verified (hv_claims_fit - this call waits for the GPU anyway),
     // so a pool that is too small grows before a voxel is written
@@ -435,10 +407,7 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
         if (rc == HV_RETRY_CLAIM && attempt < 8) rc = HV_OK;
         else if (rc == HV_RETRY_CLAIM) rc = HV_ERR_CAPACITY;
     }
-    if (rc != HV_OK) {
-        (void)hipFree(scratch);
-        return rc;
-    }
+    if (rc != HV_OK) return rc;
     const int64_t dst_after = std::min<int64_t>(dst->h_counters[HV_CNT_BLOCKS], dst->cfg.max_blocks);
     // voxels change from here on: cached extraction results are void, the written units carry a new stamp (the per-unit extraction
     // caches and hv_tsdf_dirty_keys see them)
@@ -455,7 +424,6 @@ extern "C" int hv_tsdf_integrate_volume(hv_volume *dst, hv_volume *src, const do
     if (e == hipSuccess) e = hipStreamSynchronize(dst->stream);
     if (e != hipSuccess) // (a device fault: the claimed units are in dst, written or not - the contract's error paragraph says so)
         return fail("the sweep (the destination holds the claimed units, possibly unwritten; hv_tsdf_prune releases the empty ones)", e);
-    (void)hipFree(scratch);
     if (stats != nullptr) {
         stats->units_claimed = dst_after - dst_before;
         stats->voxels_trilinear = (int64_t)h_cnt64[0];

@@ -11,7 +11,6 @@
 // unit's count = popcount(masks[u]) is what the validator established, so every index lies inside [0, N).
 #include <algorithm>
 #include <cstring>
-#include <numeric>
 #include <vector>
 
 #include "hv_common.h"
@@ -258,72 +257,40 @@ __global__ __launch_bounds__(256) void k_unpack_scatter(HvTable table, char *__r
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-int pack_check_volume(const hv_volume *v, const char *fn) {
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: the volume is not in TSDF mode", fn);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "%s: the volume is tile-sharded (it holds partial sums of a voxel)", fn);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: the volume is owner-sharded (it holds a part of the map's units)", fn);
-    return HV_OK;
-}
-
-// drain the batch pipeline and read the counters (waits for the GPU); *used = units held
-int pack_drain(hv_volume *v, const char *fn, int64_t *used) {
-    HV_HIP(hipSetDevice(v->device));
-    if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
-    v->pipe_armed = false;
-    const int rc = hv_read_counters(v);
-    if (rc != HV_OK) return rc;
-    HV_REQUIRE(v->h_counters[HV_CNT_OVERFLOW] == 0 && !v->overflow_latched, HV_ERR_CAPACITY,
-               "%s: the volume's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)", fn);
-    *used = std::min<int64_t>(std::max<int32_t>(v->h_counters[HV_CNT_BLOCKS], 0), v->cfg.max_blocks);
-    return HV_OK;
-}
-
 // device scratch of one pack call, released when it goes out of scope
 struct PackScratch {
-    void *mem = nullptr;
+    HvScratch device; // the masks / counts block, and the assembled map of a host destination
     int32_t *order = nullptr;
     uint32_t *masks = nullptr;
     unsigned long long *counts = nullptr, *offsets = nullptr;
     std::vector<int32_t> keys; // [U,3] in key order (host)
     int64_t U = 0, N = 0;
-    ~PackScratch() {
-        if (mem) (void)hipFree(mem);
-    }
 };
 
-// The first two steps of a pack: key order (host sort, as hv_tsdf_dump), masks + counts, scan.  Reads the volume only; touches
+// The first two steps of a pack: key order (hv_tsdf_key_order), masks + counts, scan.  Reads the volume only; touches
 // none of its output buffers (the cached extraction results live there).  Waits for the GPU.
 int pack_prepare(hv_volume *v, const char *fn, PackScratch &S) {
-    int rc = pack_check_volume(v, fn);
+    int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
     if (rc != HV_OK) return rc;
     int64_t U = 0;
-    rc = pack_drain(v, fn, &U);
+    rc = hv_tsdf_drain(v, fn, true, &U);
     if (rc != HV_OK) return rc;
     S.U = U;
     S.N = 0;
     if (U == 0) return HV_OK;
-    std::vector<uint64_t> bkeys((size_t)U);
-    HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * (size_t)U, hipMemcpyDeviceToHost));
-    std::vector<int32_t> xyz((size_t)U * 3), order((size_t)U);
-    for (int64_t i = 0; i < U; ++i) hv_unpack_key(bkeys[i], xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-        for (int k = 0; k < 3; ++k)
-            if (xyz[(size_t)a * 3 + k] != xyz[(size_t)b * 3 + k]) return xyz[(size_t)a * 3 + k] < xyz[(size_t)b * 3 + k];
-        return false;
-    });
-    S.keys.resize((size_t)U * 3);
-    for (int64_t o = 0; o < U; ++o) memcpy(&S.keys[(size_t)o * 3], &xyz[(size_t)order[o] * 3], 12);
+    std::vector<int32_t> order;
+    rc = hv_tsdf_key_order(v, U, order, &S.keys);
+    if (rc != HV_OK) return rc;
     // [order U i32][masks U*128 u32][counts U+1 u64][offsets U+1 u64], each part on a 256-byte boundary
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_order = up(sizeof(int32_t) * (size_t)U), b_masks = up(sizeof(uint32_t) * HV_PACK_MASK_WORDS * (size_t)U),
                  b_cnt = up(sizeof(uint64_t) * (size_t)(U + 1));
-    HV_HIP(hipMalloc(&S.mem, b_order + b_masks + 2 * b_cnt));
-    S.order = (int32_t *)S.mem;
-    S.masks = (uint32_t *)((char *)S.mem + b_order);
-    S.counts = (unsigned long long *)((char *)S.mem + b_order + b_masks);
-    S.offsets = (unsigned long long *)((char *)S.mem + b_order + b_masks + b_cnt);
+    char *mem = nullptr;
+    HV_HIP(S.device.get(&mem, b_order + b_masks + 2 * b_cnt));
+    S.order = (int32_t *)mem;
+    S.masks = (uint32_t *)(mem + b_order);
+    S.counts = (unsigned long long *)(mem + b_order + b_masks);
+    S.offsets = (unsigned long long *)(mem + b_order + b_masks + b_cnt);
     HV_HIP(hipMemcpyAsync(S.order, order.data(), sizeof(int32_t) * (size_t)U, hipMemcpyHostToDevice, v->stream));
     HV_HIP(hipMemsetAsync(S.counts + U, 0, sizeof(uint64_t), v->stream)); // the scan's extra element: its output there is N
     hipLaunchKernelGGL(k_pack_mask, dim3((unsigned)U), dim3(256), 0, v->stream, (const char *)v->pool, (const int32_t *)S.order, S.masks, S.counts);
@@ -390,9 +357,9 @@ int hv_tsdf_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_pack_info
     memcpy(header + 56, &L.total, 8);
     memcpy(header + 64, L.off, 8 * HV_PACK_SECTIONS);
 
-    void *tmp = nullptr; // a host destination is assembled in device memory and crosses PCIe once
-    if (loc == HV_HOST) HV_HIP(hipMalloc(&tmp, (size_t)L.total));
-    char *d = loc == HV_HOST ? (char *)tmp : (char *)dst;
+    char *tmp = nullptr; // a host destination is assembled in device memory and crosses PCIe once
+    if (loc == HV_HOST) HV_HIP(S.device.get(&tmp, (size_t)L.total));
+    char *d = loc == HV_HOST ? tmp : (char *)dst;
     hipStream_t s = v->stream;
     hipError_t e = hipMemcpyAsync(d, header, sizeof(header), hipMemcpyHostToDevice, s);
     if (e == hipSuccess && S.U > 0) e = hipMemcpyAsync(d + L.off[0], S.keys.data(), L.size[0], hipMemcpyHostToDevice, s);
@@ -411,7 +378,6 @@ int hv_tsdf_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_pack_info
     }
     if (e == hipSuccess && loc == HV_HOST) e = hipMemcpyAsync(dst, d, (size_t)L.total, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) {
         hv_set_error("hv_tsdf_pack: writing the packed map failed: %s", hipGetErrorString(e));
         return HV_ERR_DEVICE;
@@ -422,12 +388,12 @@ int hv_tsdf_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_pack_info
 int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv_pack_info *info) {
     HV_REQUIRE(v != nullptr && src != nullptr, HV_ERR_INVALID, "hv_tsdf_unpack: null argument");
     HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "hv_tsdf_unpack: loc must be HV_HOST or HV_DEVICE");
-    int rc = pack_check_volume(v, "hv_tsdf_unpack");
+    int rc = hv_tsdf_require_whole_map(v, "hv_tsdf_unpack", "the volume");
     if (rc != HV_OK) return rc;
     HV_REQUIRE(bytes >= HV_PACK_HEADER_BYTES, HV_ERR_INVALID, "hv_tsdf_packed_check: %lld bytes are fewer than the %d-byte header", (long long)bytes,
                HV_PACK_HEADER_BYTES);
     int64_t used = 0;
-    rc = pack_drain(v, "hv_tsdf_unpack", &used);
+    rc = hv_tsdf_drain(v, "hv_tsdf_unpack", true, &used);
     if (rc != HV_OK) return rc;
     // nothing reaches a kernel before the validator has passed it: a host buffer as it lies, of a device buffer the header and then
     // the three metadata sections (the records are only ever indexed through them)
@@ -465,14 +431,12 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
     if (info != nullptr) *info = hv_pack_info{H.U, H.N, H.total};
     if (H.U == 0) return HV_OK;
 
-    void *tmp = nullptr;
+    HvScratch S;
+    char *tmp = nullptr;
     if (loc == HV_HOST) {
-        HV_HIP(hipMalloc(&tmp, (size_t)bytes));
+        HV_HIP(S.get(&tmp, (size_t)bytes));
         rc = hv_h2d(v, tmp, src, (size_t)bytes);
-        if (rc != HV_OK) {
-            (void)hipFree(tmp);
-            return rc;
-        }
+        if (rc != HV_OK) return rc;
     }
     const char *d = loc == HV_HOST ? (const char *)tmp : (const char *)src;
     // claim first, and verify (this call waits for the GPU anyway): a pool that is too small grows before a voxel is written, or the
@@ -486,10 +450,7 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
         if (rc == HV_RETRY_CLAIM && attempt < 8) rc = HV_OK;
         else if (rc == HV_RETRY_CLAIM) rc = HV_ERR_CAPACITY;
     }
-    if (rc != HV_OK) {
-        if (tmp) (void)hipFree(tmp);
-        return rc;
-    }
+    if (rc != HV_OK) return rc;
     v->content_version += 1;
     v->extract_epoch += 1;
     v->frame_counter += 1;
@@ -507,7 +468,6 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
     v->last_touch_parity = 0;
     hv_launch_publish_status(v); // the unpacked units are part of the published occupancy
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    if (tmp) (void)hipFree(tmp);
     if (e != hipSuccess) {
         hv_set_error("hv_tsdf_unpack: the scatter failed: %s (the volume holds the claimed units, possibly unwritten: hv_reset it)", hipGetErrorString(e));
         return HV_ERR_DEVICE;

@@ -134,14 +134,11 @@ extern "C" int hv_tsdf_prune(hv_volume *v, int32_t release_empty, const int32_t 
             box.hi[a] = unit_hi[a];
         }
     }
-    HV_HIP(hipSetDevice(v->device));
     // drain the batch pipeline: nothing claims units or reads the table on the second stream while slots move (a later batch
     // starts a fresh chain on the main stream)
-    if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
-    v->pipe_armed = false;
-    int rc = hv_read_counters(v); // synchronises the stream
+    int64_t used = 0;
+    int rc = hv_tsdf_drain(v, "hv_tsdf_prune", false, &used);
     if (rc != HV_OK) return rc;
-    const int64_t used = std::min<int64_t>(std::max<int32_t>(v->h_counters[HV_CNT_BLOCKS], 0), v->cfg.max_blocks);
     if (!box.bounded && !box.release_empty) { // nothing to release by: a no-op
         if (stats != nullptr) *stats = hv_prune_stats{used, 0, 0, used};
         return HV_OK;

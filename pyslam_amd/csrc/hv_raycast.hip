@@ -3,7 +3,7 @@
 // once in include/hipvol.h; tests/raycast_reference.py restates it in numpy.
 //
 // One thread per ray, one wave per 8 x 8 pixel tile (a workgroup of four waves covers 16 x 16 pixels), so that the rays of a wave
-// walk the same units and read neighbouring voxels.  Each lane caches its last unit key -> pool index (hv_tsdf_unit).  The march
+// walk the same units and read neighbouring voxels.  Each lane caches its last unit key -> pool index (hv_tsdf_cell.h).  The march
 // and the refinement run in float32; the normal is GetNormalAt (hv_tsdf_gradient, double), as the point-cloud normals.
 // The kernel reads the table and the pool only.
 #include <cmath>
@@ -28,15 +28,7 @@ struct HvRayOut {
     uint8_t *mask;
 };
 
-// voxel (gx, gy, gz) in global voxel indices: pool index of its unit (or -1) and its word inside the unit's planes
-__device__ __forceinline__ int32_t rc_locate(const HvTable &table, int32_t gx, int32_t gy, int32_t gz, unsigned long long &ck, int32_t &ci,
-                                             int &word) {
-    word = hv_tsdf_word(gx & (HV_TSDF_R - 1), gy & (HV_TSDF_R - 1), gz & (HV_TSDF_R - 1));
-    return hv_tsdf_unit(table, gx >> 4, gy >> 4, gz >> 4, ck, ci);
-}
-
-// the trilinear weights of the 8 voxels around p - 0.5 voxel; corner i: x + (i in {1,2,5,6}), y + (i in {2,3,6,7}), z + (i >= 4)
-// (hv_tsdf_at's corner order and formula, in float)
+// the cell of p in float, by the ray caster's own formula (the corner order and the trilinear form are hv_tsdf_cell.h's)
 __device__ __forceinline__ void rc_cell(const float *p, float vl, int32_t *g0, float *r) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -47,11 +39,6 @@ __device__ __forceinline__ void rc_cell(const float *p, float vl, int32_t *g0, f
     }
 }
 
-__device__ __forceinline__ float rc_lerp(const float *r, const float *f) {
-    return (1 - r[0]) * ((1 - r[1]) * ((1 - r[2]) * f[0] + r[2] * f[4]) + r[1] * ((1 - r[2]) * f[3] + r[2] * f[7])) +
-           r[0] * ((1 - r[1]) * ((1 - r[2]) * f[1] + r[2] * f[5]) + r[1] * ((1 - r[2]) * f[2] + r[2] * f[6]));
-}
-
 // Trilinear tsdf at p; false unless all 8 voxels are observed (weight > threshold)
 __device__ inline bool rc_tsdf_tri(const HvTable &table, const char *__restrict__ pool, const HvRayParams &P, const float *p,
                                    unsigned long long &ck, int32_t &ci, float &out) {
@@ -60,16 +47,16 @@ __device__ inline bool rc_tsdf_tri(const HvTable &table, const char *__restrict_
     rc_cell(p, P.voxel_length, g0, r);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int sx = (i == 1 || i == 2 || i == 5 || i == 6), sy = (i == 2 || i == 3 || i == 6 || i == 7), sz = i >= 4;
-        int word;
-        const int32_t idx = rc_locate(table, g0[0] + sx, g0[1] + sy, g0[2] + sz, ck, ci, word);
+        int sx, sy, sz, word;
+        hv_cell_corner(i, sx, sy, sz);
+        const int32_t idx = hv_tsdf_voxel_at(table, g0[0] + sx, g0[1] + sy, g0[2] + sz, ck, ci, word);
         if (idx < 0) return false;
         const char *u = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
         const uint32_t w = ((const uint32_t *)(u + HV_TSDF_PLANE_BYTES))[word];
         if (!((float)w > P.weight_threshold)) return false;
         f[i] = ((const float *)u)[word];
     }
-    out = rc_lerp(r, f);
+    out = hv_cell_lerp(r, f);
     return true;
 }
 
@@ -82,9 +69,9 @@ __device__ inline void rc_color(const HvTable &table, const char *__restrict__ p
     bool valid = true;
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int sx = (i == 1 || i == 2 || i == 5 || i == 6), sy = (i == 2 || i == 3 || i == 6 || i == 7), sz = i >= 4;
-        int word;
-        const int32_t idx = valid ? rc_locate(table, g0[0] + sx, g0[1] + sy, g0[2] + sz, ck, ci, word) : -1;
+        int sx, sy, sz, word;
+        hv_cell_corner(i, sx, sy, sz);
+        const int32_t idx = valid ? hv_tsdf_voxel_at(table, g0[0] + sx, g0[1] + sy, g0[2] + sz, ck, ci, word) : -1;
         if (idx < 0) {
             valid = false;
             continue;
@@ -97,11 +84,11 @@ __device__ inline void rc_color(const HvTable &table, const char *__restrict__ p
     }
     if (valid) {
 #pragma unroll
-        for (int k = 0; k < 3; ++k) rgb[k] = rc_lerp(r, c[k]) / 255.0f;
+        for (int k = 0; k < 3; ++k) rgb[k] = hv_cell_lerp(r, c[k]) / 255.0f;
         return;
     }
     int word;
-    const int32_t idx = rc_locate(table, (int32_t)floorf(p[0] / P.voxel_length), (int32_t)floorf(p[1] / P.voxel_length),
+    const int32_t idx = hv_tsdf_voxel_at(table, (int32_t)floorf(p[0] / P.voxel_length), (int32_t)floorf(p[1] / P.voxel_length),
                                   (int32_t)floorf(p[2] / P.voxel_length), ck, ci, word);
     const char *u = pool + (int64_t)(idx < 0 ? 0 : idx) * HV_TSDF_UNIT_BYTES;
     const uint32_t w = idx < 0 ? 0u : ((const uint32_t *)(u + HV_TSDF_PLANE_BYTES))[word];
@@ -135,7 +122,7 @@ __global__ __launch_bounds__(256) void k_tsdf_ray_cast(HvTable table, const char
 #pragma unroll
         for (int a = 0; a < 3; ++a) gv[a] = (int32_t)floorf(p[a] / vl);
         int word;
-        const int32_t idx = rc_locate(table, gv[0], gv[1], gv[2], ck, ci, word);
+        const int32_t idx = hv_tsdf_voxel_at(table, gv[0], gv[1], gv[2], ck, ci, word);
         if (idx < 0) { // no unit here: to where the ray leaves the unit's box
             float t = INFINITY;
 #pragma unroll

@@ -11,7 +11,8 @@
 //   solve      one workgroup: the slab rows summed in a fixed order, Cholesky, A update, trace row, flag          k_reg_solve
 // Every iteration is queued up front; a step of a finished call reads the flag and returns; the host waits once for the result.
 // Iterations touch only the near-surface band of the source (the candidate list), not every allocated voxel; neighbours in the
-// list fall into the same destination units, so hv_tsdf_unit's one-entry cache answers most of the eight unit look-ups.
+// list fall into the same destination units, so the one-entry unit cache answers most of the eight unit look-ups (hv_tsdf_cell.h:
+// the cell, its eight voxels, the trilinear value and gradient).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -19,7 +20,7 @@
 
 #include "hv_common.h"
 #include "hv_gauss_newton.h"
-#include "hv_tsdf_sample.h"
+#include "hv_tsdf_cell.h"
 
 namespace {
 
@@ -161,47 +162,24 @@ __global__ __launch_bounds__(RG_BLOCK) void k_reg_linearise(const RgCand *__rest
         const double q2 = (X.R0[6] * d0 + X.R0[7] * d1) + X.R0[8] * d2;
         const double y[3] = {((A[0] * q0 + A[1] * q1) + A[2] * q2) + A[3], ((A[4] * q0 + A[5] * q1) + A[6] * q2) + A[7],
                              ((A[8] * q0 + A[9] * q1) + A[10] * q2) + A[11]};
+        const double p[3] = {X.c[0] + y[0], X.c[1] + y[1], X.c[2] + y[2]};
         int32_t g0[3];
         double r[3];
-        bool ok = true;
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double p = X.c[a] + y[a];
-            const double g = p / X.voxel_length - 0.5;
-            ok = ok && fabs(g) < 1.0e9;
-            const double f = floor(g);
-            g0[a] = ok ? (int32_t)f : 0;
-            r[a] = g - f;
-        }
-        if (!ok) continue;
-        int64_t at[8]; // word offset of the voxel's tsdf from the pool's start
+        if (!hv_cell_locate(p, X.voxel_length, g0, r)) continue;
+        int64_t at[8];
+        if (hv_tsdf_cell_gather(dst, g0, ck, ci, at) != 0xffu) continue;
         bool all = true;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int sx = (c == 1 || c == 2 || c == 5 || c == 6), sy = (c == 2 || c == 3 || c == 6 || c == 7), sz = c >= 4;
-            const int32_t vx = g0[0] + sx, vy = g0[1] + sy, vz = g0[2] + sz;
-            const int32_t idx = hv_tsdf_unit(dst, vx >> 4, vy >> 4, vz >> 4, ck, ci);
-            at[c] = (int64_t)(idx < 0 ? 0 : idx) * (HV_TSDF_UNIT_BYTES / 4) + hv_tsdf_word(vx & (HV_TSDF_R - 1), vy & (HV_TSDF_R - 1), vz & (HV_TSDF_R - 1));
-            all = all && idx >= 0;
-        }
-        if (!all) continue;
 #pragma unroll
         for (int c = 0; c < 8; ++c) all = all && (double)((const uint32_t *)pool)[at[c] + HV_TSDF_RRR] > X.weight_threshold;
         if (!all) continue;
         double f[8];
 #pragma unroll
         for (int c = 0; c < 8; ++c) f[c] = (double)((const float *)pool)[at[c]];
-        const double u0 = 1 - r[0], u1 = 1 - r[1], u2 = 1 - r[2];
-        const double c00 = u2 * f[0] + r[2] * f[4], c01 = u2 * f[3] + r[2] * f[7];
-        const double c10 = u2 * f[1] + r[2] * f[5], c11 = u2 * f[2] + r[2] * f[6];
-        const double b0 = u1 * c00 + r[1] * c01, b1 = u1 * c10 + r[1] * c11;
-        const double phi = u0 * b0 + r[0] * b1;
+        double phi, e[3];
+        hv_cell_lerp_grad(r, f, phi, e);
         const double rho = X.sdf_trunc * (phi - (double)cand.tsdf);
         if (!(fabs(rho) <= X.residual_trunc)) continue;
-        const double e0 = b1 - b0;
-        const double e1 = u0 * (c01 - c00) + r[0] * (c11 - c10);
-        const double e2 = u0 * (u1 * (f[4] - f[0]) + r[1] * (f[7] - f[3])) + r[0] * (u1 * (f[5] - f[1]) + r[1] * (f[6] - f[2]));
-        const double n0 = X.grad_scale * e0, n1 = X.grad_scale * e1, n2 = X.grad_scale * e2;
+        const double n0 = X.grad_scale * e[0], n1 = X.grad_scale * e[1], n2 = X.grad_scale * e[2];
         const double J[6] = {y[1] * n2 - y[2] * n1, y[2] * n0 - y[0] * n2, y[0] * n1 - y[1] * n0, n0, n1, n2};
         const double w = fabs(rho) <= X.huber_delta ? 1.0 : X.huber_delta / fabs(rho);
         int k = 0;
@@ -251,14 +229,6 @@ __global__ __launch_bounds__(HV_GN_SUM_THREADS) void k_reg_solve(RgState *__rest
     if (status != 0) st->done = status;
 }
 
-int register_check_volume(const hv_volume *v, const char *which) {
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_register_volume: %s is not in TSDF mode", which);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "hv_tsdf_register_volume: %s is tile-sharded (it holds partial sums of a voxel)", which);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "hv_tsdf_register_volume: %s is owner-sharded (it holds a part of the map's units)", which);
-    return HV_OK;
-}
-
 // linearise grid: one thread per candidate up to RG_MAX_BLOCKS workgroups.  HV_REGISTER_GRID_BLOCKS (1 .. RG_MAX_BLOCKS) lowers the
 // cap, so that a test reaches the grid-stride remainder with a map of a few units
 int register_grid_cap() {
@@ -274,9 +244,10 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
                                        double *trace, int64_t trace_cap, int64_t *trace_rows) {
     HV_REQUIRE(dst != nullptr && src != nullptr && T != nullptr && prm != nullptr && res != nullptr, HV_ERR_INVALID,
                "hv_tsdf_register_volume: null argument");
-    int rc = register_check_volume(dst, "the destination");
+    const char *fn = "hv_tsdf_register_volume";
+    int rc = hv_tsdf_require_whole_map(dst, fn, "the destination");
     if (rc != HV_OK) return rc;
-    rc = register_check_volume(src, "the source");
+    rc = hv_tsdf_require_whole_map(src, fn, "the source");
     if (rc != HV_OK) return rc;
     HV_REQUIRE(dst != src, HV_ERR_INVALID, "hv_tsdf_register_volume: source and destination are the same volume");
     HV_REQUIRE(dst->cfg.voxel_size == src->cfg.voxel_size && dst->cfg.sdf_trunc == src->cfg.sdf_trunc && dst->cfg.block_size == src->cfg.block_size,
@@ -316,17 +287,13 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
     for (int i = 0; i < 16; ++i) res->T_dst_src[i] = T[i];
     if (trace_rows) *trace_rows = 0;
 
-    HV_HIP(hipSetDevice(dst->device));
     // drain both batch pipelines; the source's pending work is done before the destination's stream reads it
-    for (hv_volume *v : {src, dst}) {
-        if (v->stream_aux) HV_HIP(hipStreamSynchronize(v->stream_aux));
-        v->pipe_armed = false;
-        rc = hv_read_counters(v); // synchronises the stream
-        if (rc != HV_OK) return rc;
-    }
+    int64_t src_used = 0;
+    rc = hv_tsdf_drain(src, fn, false, &src_used);
+    if (rc == HV_OK) rc = hv_tsdf_drain(dst, fn, false, nullptr);
+    if (rc != HV_OK) return rc;
     HV_REQUIRE(src->h_counters[HV_CNT_OVERFLOW] == 0 && !src->overflow_latched, HV_ERR_CAPACITY,
-               "hv_tsdf_register_volume: the source's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)");
-    const int64_t src_used = std::min<int64_t>(std::max<int32_t>(src->h_counters[HV_CNT_BLOCKS], 0), src->cfg.max_blocks);
+               "%s: the source's block pool overflowed earlier (hv_reserve_blocks or hv_reset it first)", fn);
     if (src_used == 0) return HV_OK;
 
     // anchor: the centre of the bounding box of the source's unit keys, and where T_init puts it
@@ -355,7 +322,7 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
     X.residual_trunc = prm->residual_trunc;
     X.huber_delta = prm->huber_delta;
 
-    // scratch, freed before returning: [state][slab][trace][per-unit counts / offsets, src_used + 1 int64], then the candidate list
+    // scratch, freed on return: [state][slab][trace][per-unit counts / offsets, src_used + 1 int64], then the candidate list
     const int steps = prm->max_iterations;
     size_t off = 0;
     auto take = [&off](size_t bytes) { // -> the offset of the next bytes, every piece 256-byte aligned
@@ -367,15 +334,14 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
     const size_t o_slab = take(sizeof(double) * RG_NACC * RG_MAX_BLOCKS);
     const size_t o_trace = take(sizeof(double) * HV_REGISTER_TRACE_STRIDE * (size_t)steps);
     const size_t o_counts = take(sizeof(int64_t) * (size_t)(src_used + 1));
-    void *scratch = nullptr, *list = nullptr;
-    HV_HIP(hipMalloc(&scratch, off));
+    HvScratch S;
+    char *base = nullptr;
+    RgCand *list = nullptr;
+    HV_HIP(S.get(&base, off));
     auto fail = [&](const char *what, hipError_t e) {
-        (void)hipFree(scratch);
-        if (list) (void)hipFree(list);
         hv_set_error("hv_tsdf_register_volume: %s failed: %s", what, hipGetErrorString(e));
         return HV_ERR_DEVICE;
     };
-    char *base = (char *)scratch;
     RgState *st = (RgState *)(base + o_state);
     double *slab = (double *)(base + o_slab);
     double *d_trace = (double *)(base + o_trace);
@@ -390,15 +356,12 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
     if (e == hipSuccess) e = hipMemcpyAsync(&n_cand, d_counts + src_used, sizeof(int64_t), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return fail("the candidate count", e);
-    if (n_cand <= 0) { // no near-surface voxel in the source
-        (void)hipFree(scratch);
-        return HV_OK;
-    }
-    e = hipMalloc(&list, sizeof(RgCand) * (size_t)n_cand);
+    if (n_cand <= 0) return HV_OK; // no near-surface voxel in the source
+    e = S.get(&list, (size_t)n_cand);
     if (e != hipSuccess) return fail("allocating the candidate list", e);
 
     hipLaunchKernelGGL(k_reg_collect<true>, dim3((unsigned)src_used), dim3(256), 0, s, (const unsigned long long *)src->table.block_keys,
-                       (const char *)src->pool, prm->weight_threshold, prm->tsdf_band, d_counts, (RgCand *)list);
+                       (const char *)src->pool, prm->weight_threshold, prm->tsdf_band, d_counts, list);
     hipLaunchKernelGGL(k_reg_init, dim3(1), dim3(64), 0, s, st);
     const int blocks = (int)std::min<int64_t>((n_cand + RG_BLOCK - 1) / RG_BLOCK, register_grid_cap());
     for (int it = 0; it < steps; ++it) {
@@ -420,8 +383,6 @@ extern "C" int hv_tsdf_register_volume(hv_volume *dst, hv_volume *src, const dou
         }
         if (trace_rows) *trace_rows = n;
     }
-    (void)hipFree(list);
-    (void)hipFree(scratch);
 
     // T = Tr(c) A Tr(-c) T_init: M = [R_A, (c + t_A) - R_A c], T = M T_init.  A state that never moved returns T_init as it came.
     bool moved = false;

@@ -3,7 +3,7 @@
 // (locate, value, class) is written once in include/hipvol.h; tests/sample_reference.py restates it in numpy.
 //
 // One template, instantiated by front end (a point list, or the pixels of a depth image) and by output set (colour, gradient).  One
-// lane per point; every lane resolves its eight voxels through hv_tsdf_unit's one-entry (key, index) cache, reads the eight weights,
+// lane per point; every lane takes the cell, its eight voxels and the trilinear form from hv_tsdf_cell.h, reads the eight weights,
 // then the tsdf values, then - only in the instantiation that outputs colour - the colour sums.  In the image form a wave covers an
 // 8 x 8 pixel tile (a workgroup of four waves 16 x 16 pixels, as the ray cast): the back-projected points of a tile fall into fewer
 // units and fewer 64-byte lines than 64 pixels of a row.  No LDS, no float atomics, no scratch; the class counters are integer
@@ -12,7 +12,7 @@
 #include <cmath>
 
 #include "hv_common.h"
-#include "hv_tsdf_sample.h"
+#include "hv_tsdf_cell.h"
 #include "hv_unproject.h"
 
 namespace {
@@ -33,14 +33,6 @@ struct HvSampleOut {
     unsigned long long *count; // [5] image form, or nullptr
 };
 
-__device__ __forceinline__ double sp_lerp(const double *r, const double *f) {
-    const double u0 = 1 - r[0], u1 = 1 - r[1], u2 = 1 - r[2];
-    const double c00 = u2 * f[0] + r[2] * f[4], c01 = u2 * f[3] + r[2] * f[7];
-    const double c10 = u2 * f[1] + r[2] * f[5], c11 = u2 * f[2] + r[2] * f[6];
-    const double b0 = u1 * c00 + r[1] * c01, b1 = u1 * c10 + r[1] * c11;
-    return u0 * b0 + r[0] * b1;
-}
-
 // The contract's locate + value at p.  Outputs the caller did not ask for (COLOR / GRAD false) are not computed; every output is 0
 // for HV_SAMPLE_OUTSIDE and HV_SAMPLE_UNOBSERVED.
 template <bool COLOR, bool GRAD>
@@ -55,33 +47,21 @@ __device__ __forceinline__ int sp_sample(const HvTable &table, const char *__res
     }
     int32_t g0[3];
     double r[3];
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const double g = p[a] / P.voxel_length - 0.5;
-        ok = ok && fabs(g) < 1.0e9;
-        const double f = floor(g);
-        g0[a] = ok ? (int32_t)f : 0;
-        r[a] = g - f;
-    }
-    if (!ok) return HV_SAMPLE_OUTSIDE;
+    if (!hv_cell_locate(p, P.voxel_length, g0, r)) return HV_SAMPLE_OUTSIDE;
     const int nx = r[0] >= 0.5, ny = r[1] >= 0.5, nz = r[2] >= 0.5;
     unsigned long long ck = HV_EMPTY_KEY;
     int32_t ci = -1;
-    int64_t at[8]; // word offset of the voxel's tsdf from the pool's start
-    bool held[8];
+    int64_t at[8];
+    const uint32_t held = hv_tsdf_cell_gather(table, g0, ck, ci, at);
     int64_t near_at = 0;
     bool near_held = false;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const int sx = (c == 1 || c == 2 || c == 5 || c == 6), sy = (c == 2 || c == 3 || c == 6 || c == 7), sz = c >= 4;
-        const int32_t vx = g0[0] + sx, vy = g0[1] + sy, vz = g0[2] + sz;
-        const int32_t idx = hv_tsdf_unit(table, vx >> 4, vy >> 4, vz >> 4, ck, ci);
-        held[c] = idx >= 0;
-        at[c] = (int64_t)(idx < 0 ? 0 : idx) * (HV_TSDF_UNIT_BYTES / 4) + hv_tsdf_word(vx & (HV_TSDF_R - 1), vy & (HV_TSDF_R - 1), vz & (HV_TSDF_R - 1));
+        int sx, sy, sz;
+        hv_cell_corner(c, sx, sy, sz);
         const bool is_near = sx == nx && sy == ny && sz == nz;
         near_at = is_near ? at[c] : near_at;
-        near_held = is_near ? held[c] : near_held;
+        near_held = is_near ? (held >> c) & 1u : near_held;
     }
     if (!near_held) return HV_SAMPLE_OUTSIDE;
     // the eight weights first, the tsdf values after them
@@ -90,9 +70,11 @@ __device__ __forceinline__ int sp_sample(const HvTable &table, const char *__res
     bool all = true;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
-        const int sx = (c == 1 || c == 2 || c == 5 || c == 6), sy = (c == 2 || c == 3 || c == 6 || c == 7), sz = c >= 4;
-        w[c] = held[c] ? words[at[c] + HV_TSDF_RRR] : 0u;
-        all = all && held[c] && (double)w[c] > P.weight_threshold;
+        int sx, sy, sz;
+        hv_cell_corner(c, sx, sy, sz);
+        const bool has = (held >> c) & 1u;
+        w[c] = has ? words[at[c] + HV_TSDF_RRR] : 0u;
+        all = all && has && (double)w[c] > P.weight_threshold;
         wn = (sx == nx && sy == ny && sz == nz) ? w[c] : wn;
     }
     if (!((double)wn > P.weight_threshold)) return HV_SAMPLE_UNOBSERVED;
@@ -108,26 +90,21 @@ __device__ __forceinline__ int sp_sample(const HvTable &table, const char *__res
     double f[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) f[c] = (double)((const float *)pool)[at[c]];
-    const double u0 = 1 - r[0], u1 = 1 - r[1], u2 = 1 - r[2];
-    const double c00 = u2 * f[0] + r[2] * f[4], c01 = u2 * f[3] + r[2] * f[7];
-    const double c10 = u2 * f[1] + r[2] * f[5], c11 = u2 * f[2] + r[2] * f[6];
-    const double b0 = u1 * c00 + r[1] * c01, b1 = u1 * c10 + r[1] * c11;
-    const double phi = u0 * b0 + r[0] * b1;
-    sdf = (float)(P.sdf_trunc * phi);
     if (GRAD) {
-        const double e0 = b1 - b0;
-        const double e1 = u0 * (c01 - c00) + r[0] * (c11 - c10);
-        const double e2 = u0 * (u1 * (f[4] - f[0]) + r[1] * (f[7] - f[3])) + r[0] * (u1 * (f[5] - f[1]) + r[1] * (f[6] - f[2]));
-        grad[0] = (float)(P.grad_scale * e0);
-        grad[1] = (float)(P.grad_scale * e1);
-        grad[2] = (float)(P.grad_scale * e2);
+        double phi, e[3];
+        hv_cell_lerp_grad(r, f, phi, e);
+        sdf = (float)(P.sdf_trunc * phi);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) grad[a] = (float)(P.grad_scale * e[a]);
+    } else {
+        sdf = (float)(P.sdf_trunc * hv_cell_lerp(r, f));
     }
     if (COLOR) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
 #pragma unroll
             for (int c = 0; c < 8; ++c) f[c] = (double)words[at[c] + (2 + k) * HV_TSDF_RRR] / (double)w[c];
-            col[k] = (float)(sp_lerp(r, f) / 255.0);
+            col[k] = (float)(hv_cell_lerp(r, f) / 255.0);
         }
     }
     return HV_SAMPLE_TRILINEAR;
@@ -193,14 +170,6 @@ __global__ __launch_bounds__(256) void k_tsdf_sample(HvTable table, const char *
     }
 }
 
-int sample_check_volume(const hv_volume *v, const char *fn) {
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", fn);
-    HV_REQUIRE(v->tile[0] == 0 && v->tile[1] == 0 && v->tile[2] == 0 && v->tile[3] == 0, HV_ERR_MODE,
-               "%s: the volume is tile-sharded (it holds partial sums of a voxel)", fn);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: the query needs the whole volume (owner-sharded: merge or gather first)", fn);
-    return HV_OK;
-}
-
 HvSampleParams sample_params(const hv_volume *v, double weight_threshold) {
     HvSampleParams P{};
     P.voxel_length = v->cfg.voxel_size;
@@ -231,7 +200,7 @@ extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t p
                                      float *gradient, float *color, float *weight, uint8_t *status, int32_t loc) {
     const char *fn = "hv_tsdf_sample_points";
     HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "%s: null argument", fn);
-    int rc = sample_check_volume(v, fn);
+    int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
     if (rc != HV_OK) return rc;
     HV_REQUIRE(n >= 0 && n <= (1ll << 36), HV_ERR_INVALID, "%s: bad point count %lld", fn, (long long)n);
     HV_REQUIRE(points != nullptr || n == 0, HV_ERR_INVALID, "%s: null points", fn);
@@ -286,7 +255,7 @@ extern "C" int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t dept
                                    int32_t loc) {
     const char *fn = "hv_tsdf_check_frame";
     HV_REQUIRE(v != nullptr && depth != nullptr && intr != nullptr && T_cw != nullptr && params != nullptr, HV_ERR_INVALID, "%s: null argument", fn);
-    int rc = sample_check_volume(v, fn);
+    int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
     if (rc != HV_OK) return rc;
     HV_REQUIRE(depth_dtype == HV_DEPTH_F32 || depth_dtype == HV_DEPTH_U16, HV_ERR_INVALID, "%s: bad depth dtype %d", fn, (int)depth_dtype);
     HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "%s: bad loc %d", fn, (int)loc);

@@ -1449,21 +1449,13 @@ int hv_tsdf_dump(hv_volume *v, int32_t *keys, float *tsdf, float *weight, double
     if (rc != HV_OK) return rc;
     *n_units = nb;
     if (nb == 0 || (keys == nullptr && tsdf == nullptr && weight == nullptr && color == nullptr)) return HV_OK;
-    std::vector<uint64_t> bkeys((size_t)nb);
-    HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost));
-    std::vector<int64_t> order((size_t)nb);
-    std::iota(order.begin(), order.end(), 0);
-    std::vector<int32_t> xyz((size_t)nb * 3);
-    for (int64_t i = 0; i < nb; ++i) hv_unpack_key(bkeys[i], xyz[i * 3], xyz[i * 3 + 1], xyz[i * 3 + 2]);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
-        for (int k = 0; k < 3; ++k)
-            if (xyz[a * 3 + k] != xyz[b * 3 + k]) return xyz[a * 3 + k] < xyz[b * 3 + k];
-        return false;
-    });
+    std::vector<int32_t> order, xyz; // the units and their keys by ascending (x, y, z)
+    rc = hv_tsdf_key_order(v, nb, order, &xyz);
+    if (rc != HV_OK) return rc;
     std::vector<char> unit((size_t)HV_TSDF_UNIT_BYTES);
     for (int64_t o = 0; o < nb; ++o) {
         const int64_t i = order[o];
-        if (keys) memcpy(keys + o * 3, &xyz[i * 3], 12);
+        if (keys) memcpy(keys + o * 3, &xyz[o * 3], 12);
         if (!(tsdf || weight || color)) continue;
         HV_HIP(hipMemcpy(unit.data(), (char *)v->pool + i * unit.size(), unit.size(), hipMemcpyDeviceToHost));
         const float *pt = (const float *)unit.data();

@@ -3,25 +3,13 @@
 // hv_tsdf_at is Open3D's ScalableTSDFVolume::GetTSDFAt: the trilinear interpolation of the eight voxels around a position.  It
 // does not look at weights (a voxel never observed holds its initial tsdf 0) and a missing unit contributes 0.  The unit of the
 // previous fetch is remembered by the caller (ck / ci: most of the fetches of one point fall into one or two units); the
-// arithmetic is Open3D's, in double.  hv_tsdf_gradient is GetNormalAt before normalisation: central differences, at +/- 0.99
-// voxel along each axis, of GetTSDFAt.
+// locate is Open3D's, in double; the corner order and the trilinear form are the contract's (hv_tsdf_cell.h).  hv_tsdf_gradient
+// is GetNormalAt before normalisation: central differences, at +/- 0.99 voxel along each axis, of GetTSDFAt.
 #pragma once
 #include "hv_common.h"
+#include "hv_tsdf_cell.h"
 
 #ifdef __HIPCC__
-// pool index of unit (ux, uy, uz), -1 if absent; the last key looked up and its index are cached in (cached_key, cached_idx)
-__device__ __forceinline__ int32_t hv_tsdf_unit(const HvTable &table, int32_t ux, int32_t uy, int32_t uz, unsigned long long &cached_key,
-                                                int32_t &cached_idx) {
-    if (!hv_key_in_range(ux, uy, uz)) return -1;
-    const unsigned long long key = hv_pack_key(ux, uy, uz);
-    if (key != cached_key) {
-        const int32_t slot = hv_table_find(table, key);
-        cached_key = key;
-        cached_idx = slot >= 0 ? table.vals[slot] : -1;
-    }
-    return cached_idx;
-}
-
 __device__ __forceinline__ float hv_tsdf_voxel(const HvTable &table, const char *__restrict__ pool, int32_t ux, int32_t uy, int32_t uz,
                                                int x, int y, int z, unsigned long long &cached_key, int32_t &cached_idx) {
     const int32_t idx = hv_tsdf_unit(table, ux, uy, uz, cached_key, cached_idx);
@@ -52,16 +40,16 @@ __device__ inline double hv_tsdf_at(const HvTable &table, const char *__restrict
         ck = k0;
         ci = i0;
     }
-    float f[8];
+    double f[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-        const int sx = (i == 1 || i == 2 || i == 5 || i == 6), sy = (i == 2 || i == 3 || i == 6 || i == 7), sz = i >= 4;
+        int sx, sy, sz;
+        hv_cell_corner(i, sx, sy, sz);
         int x = idx0[0] + sx, y = idx0[1] + sy, z = idx0[2] + sz;
         const int32_t ux = index0[0] + (x >= HV_TSDF_R), uy = index0[1] + (y >= HV_TSDF_R), uz = index0[2] + (z >= HV_TSDF_R);
-        f[i] = hv_tsdf_voxel(table, pool, ux, uy, uz, x & (HV_TSDF_R - 1), y & (HV_TSDF_R - 1), z & (HV_TSDF_R - 1), ck, ci);
+        f[i] = (double)hv_tsdf_voxel(table, pool, ux, uy, uz, x & (HV_TSDF_R - 1), y & (HV_TSDF_R - 1), z & (HV_TSDF_R - 1), ck, ci);
     }
-    return (1 - r[0]) * ((1 - r[1]) * ((1 - r[2]) * f[0] + r[2] * f[4]) + r[1] * ((1 - r[2]) * f[3] + r[2] * f[7])) +
-           r[0] * ((1 - r[1]) * ((1 - r[2]) * f[1] + r[2] * f[5]) + r[1] * ((1 - r[2]) * f[2] + r[2] * f[6]));
+    return hv_cell_lerp(r, f);
 }
 
 // GetNormalAt's unnormalised gradient at p (nn[i] = tsdf(p + 0.99 vl e_i) - tsdf(p - 0.99 vl e_i))

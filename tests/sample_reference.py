@@ -29,6 +29,21 @@ def _tri(r, f):
     return phi, (e0, e1, e2)
 
 
+def locate(p, voxel_length):
+    """The contract's cell of points p [n,3] float64 -> (ok [n], g0 [3][n] int64, r [3][n]), as the library leaves them: ok accumulates
+    over the axes, g0 is 0 from the first refused axis on, r of a refused point means nothing."""
+    vl = np.float64(voxel_length)
+    ok = np.ones(len(p), bool)
+    g0, r = [], []
+    for a in range(3):
+        g = p[:, a] / vl - 0.5
+        ok &= np.abs(g) < 1.0e9
+        f = np.floor(g)
+        g0.append(np.where(ok, f, 0.0).astype(np.int64))
+        r.append(g - f)
+    return ok, g0, r
+
+
 def sample_points(dump, voxel_length, sdf_trunc, points, weight_threshold=0.0):
     """-> dict of sdf [n] f32, gradient [n,3] f32, color [n,3] f32, weight [n] f32, status [n] u8, fragile [n] bool for points [n,3]
     (float32 is widened first)."""
@@ -38,15 +53,8 @@ def sample_points(dump, voxel_length, sdf_trunc, points, weight_threshold=0.0):
     empty = len(np.asarray(dump[0]).reshape(-1, 3)) == 0
     grid = None if empty else rr._Grid(dump)
     colour = None if empty else np.asarray(dump[3], np.float64).reshape(len(grid.codes), -1, 3)
-    ok = np.ones(n, bool)
-    g0, r = [], []
     with np.errstate(invalid="ignore", over="ignore"):
-        for a in range(3):
-            g = p[:, a] / vl - 0.5
-            ok &= np.abs(g) < 1.0e9
-            f = np.floor(g)
-            g0.append(np.where(ok, f, 0.0).astype(np.int64))
-            r.append(g - f)
+        ok, g0, r = locate(p, vl)
         g0 = [np.where(ok, x, 0) for x in g0]  # (the library's g0 of a refused point is not used either)
         r = [np.where(ok, x, 0.0) for x in r]
         fragile = np.zeros(n, bool)

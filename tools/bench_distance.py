@@ -116,7 +116,7 @@ def main():
     t0 = time.perf_counter()
     ref = dr.distance_field(dump, bench.VOXEL, small_origin, SMALL_SHAPE, SMALL_RADIUS)
     numpy_s = time.perf_counter() - t0
-    equal = all(np.array_equal(np.ascontiguousarray(getattr(small, name)).view(np.uint8), ref[name].view(np.uint8)) for name in OUTPUTS) \
+    equal = all(np.array_equal(np.ascontiguousarray(getattr(small, name)).view(np.uint8), np.ascontiguousarray(ref[name]).view(np.uint8)) for name in OUTPUTS) \
         and small.stats.as_tuple() == ref["stats"]
 
     print(json.dumps({
