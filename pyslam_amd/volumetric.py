@@ -11,7 +11,9 @@
 All compute happens in libpyslam_hipvol.so on the GPU; nothing here falls back to the CPU.
 Arrays may be numpy (host) or torch CUDA tensors (zero-copy, already resident in HBM).
 """
+import contextlib
 import ctypes
+import functools
 import typing
 
 import numpy as np
@@ -38,6 +40,16 @@ def _result_array(shape, dtype):
     return np.empty(shape, dtype)
 
 
+def _is_torch(a):
+    """A torch tensor, on either device (numpy arrays, lists and bytes-like objects are not)."""
+    return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
+
+
+def _stats(cls, struct):
+    """A *Stats result (a _Stats subclass or a named tuple) from the ctypes struct the library filled, field by field name."""
+    return cls(*[getattr(struct, name) for name in getattr(cls, "_fields", cls.__slots__)])
+
+
 def _as_f64_4x4(T):
     T = np.ascontiguousarray(np.asarray(T, dtype=np.float64))
     if T.shape != (4, 4):
@@ -46,6 +58,53 @@ def _as_f64_4x4(T):
 
 
 _UNSUPPORTED_IMAGE = "[ScalableTSDFVolume::Integrate] Unsupported image format."
+
+
+def _pose_rows(T, frames):
+    """The poses of `frames` frames ([F,4,4], [F,16] or flat) as the library reads them: contiguous float64 [F,16]."""
+    T = np.asarray(T, dtype=np.float64)
+    if T.size != 16 * frames or (T.ndim > 1 and T.shape[0] != frames):
+        raise RuntimeError(_UNSUPPORTED_IMAGE)
+    return np.ascontiguousarray(T.reshape(frames, 16))
+
+
+def _rigid_operand(source, T, who, what):
+    """The operands of a volume-to-volume call: `source` must be a volume, T (None: identity) a 4x4 -> contiguous float64 [4,4]."""
+    if getattr(source, "_h", None) is None:
+        raise TypeError(f"{who}: source must be a volume")
+    T = np.eye(4) if T is None else np.asarray(T, dtype=np.float64)
+    if T.shape != (4, 4):
+        raise ValueError(f"{who}: {what} must be a 4x4 matrix")
+    return np.ascontiguousarray(T, dtype=np.float64)
+
+
+def _points_operand(points, torch_ok=False):
+    """points [N,3] of a grid's integrate -> (operand, wide, N): contiguous float64 when they are float64, else float32 (the
+    binding's two overloads).  torch_ok: a torch tensor stays one (either device); else everything becomes a host array."""
+    pts = points if torch_ok and _is_torch(points) else np.asarray(points)
+    if len(pts.shape) != 2 or pts.shape[1] != 3:
+        raise RuntimeError("points must be a contiguous Nx3 array")
+    wide = str(pts.dtype) in ("float64", "torch.float64")
+    if _is_torch(pts):
+        pts = pts.contiguous() if wide else pts.contiguous().float()
+    else:
+        pts = np.ascontiguousarray(pts, dtype=np.float64 if wide else np.float32)
+    return pts, wide, pts.shape[0]
+
+
+def _colors_operand(colors, n, torch_ok=False):
+    """colors [N,3] uint8 | float32 | None of a grid's integrate -> (contiguous operand, HV_COLOR_*); torch_ok as _points_operand."""
+    if colors is None:
+        return None, L.HV_COLOR_NONE
+    cols = colors.contiguous() if torch_ok and _is_torch(colors) else np.ascontiguousarray(colors)
+    if len(cols.shape) != 2 or cols.shape[1] != 3:
+        raise RuntimeError("colors must be a contiguous Nx3 array")
+    if cols.shape[0] != n:
+        raise RuntimeError("points and colors must have the same size")
+    kind = {"uint8": L.HV_COLOR_U8, "float32": L.HV_COLOR_F32}.get(str(cols.dtype).replace("torch.", ""))
+    if kind is None:
+        raise RuntimeError(f"Colors must be uint8 or float32, got dtype with {cols.dtype}")
+    return cols, kind
 
 
 def _tsdf_operands(depth, color, intrinsic, frames=None, depth_only=False):
@@ -57,10 +116,7 @@ def _tsdf_operands(depth, color, intrinsic, frames=None, depth_only=False):
     Anything else - colour that is not uint8 of the depth's shape + (3,), an intrinsic of another size, depth and colour on
     different devices - raises before any library call.  depth_only=True: the depth operand alone, color is ignored (and
     returned as None)."""
-
-    def is_torch(a):
-        return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
-
+    is_torch = _is_torch
     if not depth_only and is_torch(depth) != is_torch(color):
         # one host array and one torch tensor: only together when the tensor lives on the host
         if L.location(depth) != L.HV_HOST or L.location(color) != L.HV_HOST:
@@ -320,7 +376,7 @@ class DistanceField:
         idx, inside = self.cell_of(points)
         out = np.full(len(idx), np.float32(self.radius) * np.float32(self.voxel_length), np.float32)
         i = idx[inside]
-        if hasattr(self.distance, "is_cuda"):
+        if _is_torch(self.distance):
             import torch
 
             t = torch.from_numpy(i).to(self.distance.device)
@@ -382,7 +438,7 @@ class ComponentRemovalStats(typing.NamedTuple):
 def _packed_operand(buf):
     """A packed map as the C ABI takes it: numpy array, bytes-like object or torch tensor (either device) -> contiguous 1-D uint8,
     numpy for host memory, torch for a GPU."""
-    if hasattr(buf, "is_cuda"):
+    if _is_torch(buf):
         import torch
 
         if buf.dtype != torch.uint8 or buf.dim() != 1:
@@ -423,30 +479,28 @@ def unit_range_of_bounds(bounds, voxel_length, resolution=16):
     return lo.astype(np.int32), hi.astype(np.int32)
 
 
-def _trace_rows(rows):
+_TRACK_HEAD = (("level", int), ("iteration", int), ("status", int), ("inliers", int), ("valid", int), ("sq_error", float))
+_REGISTER_HEAD = (("iteration", int), ("status", int), ("inliers", int), ("candidates", int), ("sq_error", float))
+
+
+def _trace_rows(rows, head=_TRACK_HEAD):
+    """The per-linearisation record of tracking / registration, rows [n, stride] float64 -> one dict per row: the leading scalars
+    that `head` names, then A 4x4, H 6x6 (stored as its upper triangle), g 6, xi 6; a hybrid tracking row holds two more columns."""
     out = []
     iu = np.triu_indices(6)
+    k = len(head)
     for r in rows:
         H = np.zeros((6, 6))
-        H[iu] = r[22:43]
+        H[iu] = r[k + 16:k + 37]
         H = H + np.triu(H, 1).T
-        out.append({"level": int(r[0]), "iteration": int(r[1]), "status": int(r[2]), "inliers": int(r[3]), "valid": int(r[4]),
-                    "sq_error": float(r[5]), "A": r[6:22].reshape(4, 4).copy(), "H": H, "g": r[43:49].copy(), "xi": r[49:55].copy()})
+        out.append({name: kind(r[i]) for i, (name, kind) in enumerate(head)})
+        out[-1].update(A=r[k:k + 16].reshape(4, 4).copy(), H=H, g=r[k + 37:k + 43].copy(), xi=r[k + 43:k + 49].copy())
         if len(r) > L.HV_TRACK_TRACE_STRIDE:  # a hybrid call's row
             out[-1].update(photometric_inliers=int(r[56]), sq_intensity_error=float(r[57]))
     return out
 
 
-def _register_trace_rows(rows):
-    out = []
-    iu = np.triu_indices(6)
-    for r in rows:
-        H = np.zeros((6, 6))
-        H[iu] = r[21:42]
-        H = H + np.triu(H, 1).T
-        out.append({"iteration": int(r[0]), "status": int(r[1]), "inliers": int(r[2]), "candidates": int(r[3]), "sq_error": float(r[4]),
-                    "A": r[5:21].reshape(4, 4).copy(), "H": H, "g": r[42:48].copy(), "xi": r[48:54].copy()})
-    return out
+_NOTHING_TO_ORDER = contextlib.nullcontext()  # what _Volume._ordered() returns for host operands
 
 
 class _Volume:
@@ -482,16 +536,55 @@ class _Volume:
         except Exception:
             pass
 
-    # -- shared introspection -------------------------------------------------------------------
-    def num_blocks(self):
+    # -- the steps every method is made of ------------------------------------------------------------
+    def _int64(self, fn, *args):
+        """fn(handle, *args, &n) -> n: the library's single-integer getters."""
         n = ctypes.c_int64()
-        L.check(self._lib.hv_num_blocks(self._h, ctypes.byref(n)))
+        L.check(fn(self._h, *args, ctypes.byref(n)))
         return n.value
 
-    def max_blocks(self):
+    def _sized_fetch(self, call, *specs):
+        """The two-call fetch: call(*pointers, capacity, &count) with null pointers and capacity 0 asks for the count; unless that
+        is 0 the second call fills zeroed host arrays [count, *row shape], one per spec = (row shape, dtype).  -> the arrays."""
         n = ctypes.c_int64()
-        L.check(self._lib.hv_max_blocks(self._h, ctypes.byref(n)))
-        return n.value
+        L.check(call(*(None,) * len(specs), 0, ctypes.byref(n)))
+        out = [np.zeros((n.value,) + tuple(row), dtype) for row, dtype in specs]
+        if n.value:
+            L.check(call(*(L.ptr(a) for a in out), n.value, ctypes.byref(n)))
+        return out
+
+    def _device(self):
+        """The volume's GPU as a torch.device (made on first use: no host-only path comes here)."""
+        if getattr(self, "_torch_device", None) is None:
+            import torch
+
+            self._torch_device = torch.device("cuda", int(self._cfg.device))
+        return self._torch_device
+
+    def _results(self, spec, device, pinned=True, synchronize=True):
+        """The buffers one call writes its results to: spec {name: (shape, numpy dtype) or None} -> {name: array or None}.  On the
+        host numpy arrays, page-locked when large (_result_array; pinned=False: plain np.empty).  With `device` torch tensors on
+        the volume's GPU (torch has no uint32 arithmetic: such a result is an int32 tensor with the same bits); synchronize: then
+        wait for torch's current stream - the allocator may hand out blocks with work pending on that stream, which a launch
+        outside _ordered() does not wait for."""
+        if not device:
+            make = _result_array if pinned else np.empty
+            return {name: None if s is None else make(s[0], s[1]) for name, s in spec.items()}
+        import torch
+
+        dev = self._device()
+        out = {name: None if s is None else torch.empty(tuple(s[0]), dtype=getattr(torch, np.dtype(s[1]).name.replace("uint32", "int32")),
+                                                        device=dev) for name, s in spec.items()}
+        if synchronize:
+            torch.cuda.current_stream(dev).synchronize()
+        return out
+
+    # -- shared introspection -------------------------------------------------------------------
+    def num_blocks(self):
+        return self._int64(self._lib.hv_num_blocks)
+
+    def max_blocks(self):
+        return self._int64(self._lib.hv_max_blocks)
 
     def reserve_blocks(self, new_max_blocks):
         """Grow the block pool / hash, keeping the contents (also happens automatically when more than half full)."""
@@ -529,8 +622,7 @@ class _Volume:
         import torch
 
         if getattr(self, "_adopted", None) is None:
-            dev = torch.device("cuda", int(self._cfg.device))
-            self._adopted = torch.cuda.Stream(dev)
+            self._adopted = torch.cuda.Stream(self._device())
             self.set_stream(self._adopted.cuda_stream)
         return self._adopted
 
@@ -561,43 +653,44 @@ class _Volume:
         if ts is not None:
             torch.cuda.current_stream(device).wait_stream(ts)
 
+    def _ordered(self, *tensors):
+        """``with self._ordered(operands and results):`` around a launch that reads / writes torch tensors: _torch_in() before,
+        _torch_out() after, also when the launch raises.  Host arrays and None take no part; with nothing on a GPU it does nothing."""
+        for t in tensors:
+            if t is not None and getattr(t, "is_cuda", False):
+                return self._ordered_on(t)
+        return _NOTHING_TO_ORDER
+
+    @contextlib.contextmanager
+    def _ordered_on(self, tensor):
+        ts = self._torch_in(tensor)
+        try:
+            yield
+        finally:
+            if ts is not None:
+                self._torch_out(ts, tensor.device)
+
+    def _publish(self, dev):
+        """After a launch that only WRITES torch tensors (allocated by _results): torch's current stream waits for the volume's."""
+        self._torch_out(self._torch_stream(dev), dev)
+
     def _query_place(self, a, device):
         """Where a query runs: -> (operand at that place, torch device or None).  device=None: where the operand lives (a torch CUDA
         tensor stays on its GPU, anything else is host memory); True / False: the volume's GPU / the host, the operand moved there."""
-        is_torch = hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
         on_gpu = L.location(a) == L.HV_DEVICE
         if device is None:
             device = on_gpu
         if not device:
-            return (a.cpu().numpy() if is_torch else a), None
+            return (a.cpu().numpy() if _is_torch(a) else a), None
         import torch
 
-        dev = torch.device("cuda", int(self._cfg.device))
+        dev = self._device()
         if on_gpu and a.device != dev:
             raise ValueError(f"the operand lives on {a.device}, the volume on {dev}")
         return (a if on_gpu else torch.as_tensor(a).to(dev)), dev
 
-    def _carve(self, camera_frustrum, depth_image, depth_threshold):
-        """carve(camera_frustrum, depth f32 HxW, threshold) of every grid type (voxel_grid_carving.h:47-79).  Host array or
-        torch CUDA tensor (used in place, ordered against torch's stream)."""
-        f = camera_frustrum
-        if hasattr(depth_image, "data_ptr"):
-            depth = depth_image.contiguous().float()
-        else:
-            depth = np.ascontiguousarray(depth_image, dtype=np.float32)
-        if depth.ndim != 2 or depth.shape[0] * depth.shape[1] == 0 or depth.shape[0] != f.height or depth.shape[1] != f.width:
-            return  # "Depth image is empty" / check_image_size(): the reference prints a message and returns
-        loc = L.location(depth)
-        ts = self._torch_in(depth) if loc == L.HV_DEVICE else None
-        L.check(self._lib.hv_carve(self._h, L.ptr(f.intr), f.width, f.height, L.ptr(f.T_cw), f.depth_max, f.depth_min, L.ptr(depth),
-                                   float(depth_threshold), loc))
-        if ts is not None:
-            self._torch_out(ts, depth.device)
-
     def dropped_points(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_dropped_points(self._h, ctypes.byref(n)))
-        return n.value
+        return self._int64(self._lib.hv_dropped_points)
 
     def profile_enable(self, on=True):
         L.check(self._lib.hv_profile_enable(self._h, 1 if on else 0))
@@ -609,27 +702,14 @@ class _Volume:
 
     def profile_launches(self):
         """Durations (ms) of the bracketed launches since profile_enable / the last profile_read, in issue order."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_profile_read_launches(self._h, None, 0, ctypes.byref(n)))
-        out = np.zeros(n.value, np.float32)
-        if n.value:
-            L.check(self._lib.hv_profile_read_launches(self._h, L.ptr(out), n.value, ctypes.byref(n)))
-        return out
+        return self._sized_fetch(functools.partial(self._lib.hv_profile_read_launches, self._h), ((), np.float32))[0]
 
     def filter_shadow_points(self, depth, delta_x=2, delta_y=2, fill_value=-1.0, stream=None):
         """pyslam.utilities.depth.filter_shadow_points(depth, delta_depth=None, ...) on the GPU.
         stream: a torch.cuda.Stream - the launches of a CUDA tensor's filter go to THAT stream (which must be torch's current one:
         the result is allocated on it) instead of the volume's; the filter reads nothing of the volume, so it may run beside the
         volume's kernels (device_pipeline.KeyframeUploader: the next keyframe's depth is filtered while this one is fused)."""
-        if stream is not None:
-            import torch
-
-            d = depth.contiguous().float()
-            out = torch.empty_like(d)
-            L.check(self._lib.hv_filter_shadow_points_on_stream(self._h, L.ptr(d), int(d.shape[0]), int(d.shape[1]), int(delta_x),
-                                                                int(delta_y), float(fill_value), L.ptr(out), int(stream.cuda_stream)))
-            return out
-        if hasattr(depth, "data_ptr"):
+        if stream is not None or _is_torch(depth):
             import torch
 
             d = depth.contiguous().float()
@@ -637,18 +717,18 @@ class _Volume:
         else:
             d = np.ascontiguousarray(depth, dtype=np.float32)
             out = np.empty_like(d)
-        H, W = int(d.shape[0]), int(d.shape[1])
-        ts = self._torch_in(d, out) if L.location(d) == L.HV_DEVICE else None
-        L.check(self._lib.hv_filter_shadow_points(self._h, L.ptr(d), H, W, int(delta_x), int(delta_y), float(fill_value),
-                                                  L.ptr(out), L.location(d)))
-        if ts is not None:
-            self._torch_out(ts, d.device)
+        args = (self._h, L.ptr(d), int(d.shape[0]), int(d.shape[1]), int(delta_x), int(delta_y), float(fill_value), L.ptr(out))
+        if stream is not None:
+            L.check(self._lib.hv_filter_shadow_points_on_stream(*args, int(stream.cuda_stream)))
+        else:
+            with self._ordered(d, out):
+                L.check(self._lib.hv_filter_shadow_points(*args, L.location(d)))
         return out
 
     def remap(self, img, map_x, map_y, linear=False):
         """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU.  Host arrays, or a
         torch CUDA tensor (the maps are then uploaded once and cached): the image never leaves the device."""
-        if hasattr(img, "data_ptr") and img.is_cuda:
+        if _is_torch(img) and img.is_cuda:
             import torch
 
             src = img.contiguous()
@@ -682,9 +762,55 @@ class _Volume:
         return out
 
     def bytes_per_block(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_bytes_per_block(self._h, ctypes.byref(n)))
-        return n.value
+        return self._int64(self._lib.hv_bytes_per_block)
+
+
+class _BlockGrid(_Volume):
+    """What VoxelBlockGrid and the semantic block grids share: a grid of voxel_size with block_size^3 voxels per block."""
+
+    def __init__(self, mode, voxel_size, block_size, device, max_blocks, max_points):
+        voxel_size = float(np.float32(voxel_size))  # pybind narrows to float (py::init<float,int>)
+        super().__init__(mode, voxel_size, 0.0, block_size, 1, device, max_blocks, max_points)
+        self.voxel_size = voxel_size
+        self.block_size = int(block_size)
+
+    def set_owner(self, rank, world_size):
+        """Multi-GPU block ownership (hv_set_owner): fuse and store only the blocks with hash(block key) % world_size == rank (no
+        collective while fusing)."""
+        L.check(self._lib.hv_set_owner(self._h, int(rank), int(world_size)))
+
+    def carve(self, camera_frustrum, depth_image, depth_threshold=1e-2):
+        """carve(camera_frustrum, depth f32 HxW, threshold) of every grid type (voxel_grid_carving.h:47-79).  Host array or
+        torch CUDA tensor (used in place, ordered against torch's stream)."""
+        f = camera_frustrum
+        if _is_torch(depth_image):
+            depth = depth_image.contiguous().float()
+        else:
+            depth = np.ascontiguousarray(depth_image, dtype=np.float32)
+        if depth.ndim != 2 or depth.shape[0] * depth.shape[1] == 0 or depth.shape[0] != f.height or depth.shape[1] != f.width:
+            return  # "Depth image is empty" / check_image_size(): the reference prints a message and returns
+        with self._ordered(depth):
+            L.check(self._lib.hv_carve(self._h, L.ptr(f.intr), f.width, f.height, L.ptr(f.T_cw), f.depth_max, f.depth_min, L.ptr(depth),
+                                       float(depth_threshold), L.location(depth)))
+
+    def remove_low_count_voxels(self, min_count):
+        L.check(self._lib.hv_remove_low_count_voxels(self._h, int(min_count)))
+
+    def clear(self):
+        L.check(self._lib.hv_reset(self._h))
+
+    reset = clear
+
+    def size(self):
+        return self._int64(self._lib.hv_size)
+
+    get_total_voxel_count = size
+
+    def empty(self):
+        return self.num_blocks() == 0
+
+    def get_block_size(self):
+        return self.block_size
 
 
 # ================================================================================================
@@ -1055,7 +1181,7 @@ class VoxelData:
             return list(self.color_sum / np.float32(self.count))
 
 
-class VoxelBlockGrid(_Volume):
+class VoxelBlockGrid(_BlockGrid):
     """``volumetric.VoxelBlockGrid(voxel_size, block_size=8)`` on the GPU.
 
     integrate() results (count, position_sum, color_sum per voxel) are bit-identical to the
@@ -1064,53 +1190,18 @@ class VoxelBlockGrid(_Volume):
     """
 
     def __init__(self, voxel_size, block_size=8, device=0, max_blocks=None, max_points=None):
-        voxel_size = float(np.float32(voxel_size))  # pybind narrows to float (py::init<float,int>)
-        super().__init__(L.HV_MODE_VOXEL_GRID, voxel_size, 0.0, block_size, 1, device, max_blocks, max_points)
-        self.voxel_size = voxel_size
-        self.block_size = int(block_size)
+        super().__init__(L.HV_MODE_VOXEL_GRID, voxel_size, block_size, device, max_blocks, max_points)
 
     # -- integrate -------------------------------------------------------------------------------
     def integrate(self, points, colors=None):
         """points: [N,3] float32 or float64 (the binding's two overloads, volumetric_grid_module.h:738-749: float64 points
         are keyed in double, anything else goes through float32); colors: [N,3] uint8|float32|None."""
-        is_torch = hasattr(points, "data_ptr")
-        if is_torch:
-            if points.dim() != 2 or points.shape[1] != 3:
-                raise RuntimeError("points must be a contiguous Nx3 array")
-            wide = str(points.dtype) == "torch.float64"
-            pts = points.contiguous() if wide else points.contiguous().float()
-            n = pts.shape[0]
-        else:
-            pts = np.asarray(points)
-            if pts.ndim != 2 or pts.shape[1] != 3:
-                raise RuntimeError("points must be a contiguous Nx3 array")
-            wide = pts.dtype == np.float64
-            pts = np.ascontiguousarray(pts, dtype=np.float64 if wide else np.float32)
-            n = pts.shape[0]
+        pts, wide, n = _points_operand(points, torch_ok=True)
         if n == 0:
             return
-        kind, cols = L.HV_COLOR_NONE, None
-        if colors is not None:
-            if hasattr(colors, "data_ptr"):
-                cols = colors.contiguous()
-                shape, dt = tuple(cols.shape), str(cols.dtype)
-                is_u8, is_f32 = dt == "torch.uint8", dt == "torch.float32"
-            else:
-                cols = np.ascontiguousarray(colors)
-                shape, dt = cols.shape, str(cols.dtype)
-                is_u8, is_f32 = cols.dtype == np.uint8, cols.dtype == np.float32
-            if len(shape) != 2 or shape[1] != 3:
-                raise RuntimeError("colors must be a contiguous Nx3 array")
-            if shape[0] != n:
-                raise RuntimeError("points and colors must have the same size")
-            if is_u8:
-                kind = L.HV_COLOR_U8
-            elif is_f32:
-                kind = L.HV_COLOR_F32
-            else:
-                raise RuntimeError(f"Colors must be uint8 or float32, got dtype with {dt}")
-            if L.location(cols) != L.location(pts):
-                raise RuntimeError("points and colors must live on the same device")
+        cols, kind = _colors_operand(colors, n, torch_ok=True)
+        if cols is not None and L.location(cols) != L.location(pts):
+            raise RuntimeError("points and colors must live on the same device")
         fn = self._lib.hv_integrate_points_f64 if wide else self._lib.hv_integrate_points
         L.check(fn(self._h, L.ptr(pts), n, L.ptr(cols), kind, L.location(pts)))
 
@@ -1118,7 +1209,7 @@ class VoxelBlockGrid(_Volume):
         """Fused depth2pointcloud + world transform + integrate for one posed RGB-D frame
         (pyslam/utilities/depth.py:45-85, volumetric_integrator_voxel_grid.py:251-300)."""
         dkind = L.HV_DEPTH_U16 if str(depth.dtype) in ("uint16", "torch.uint16") else L.HV_DEPTH_F32
-        if hasattr(depth, "data_ptr"):  # torch: the kernels read packed f32 / u16 depth and packed u8 colour
+        if _is_torch(depth):  # torch: the kernels read packed f32 / u16 depth and packed u8 colour
             if str(depth.dtype) not in ("torch.float32", "torch.uint16") or not depth.is_contiguous() or not rgb.is_contiguous() \
                     or str(rgb.dtype) != "torch.uint8":
                 raise RuntimeError("integrate_rgbd: device inputs must be contiguous float32|uint16 depth and uint8 colour")
@@ -1143,7 +1234,7 @@ class VoxelBlockGrid(_Volume):
         calls, with one device sort per max_points / (H*W) frames (create the grid with a large max_points)."""
         dkind = L.HV_DEPTH_U16 if str(depth.dtype) in ("uint16", "torch.uint16") else L.HV_DEPTH_F32
         F, H, W = (int(x) for x in depth.shape)
-        if not hasattr(depth, "data_ptr"):
+        if not _is_torch(depth):
             depth = np.ascontiguousarray(depth, dtype=np.uint16 if dkind == L.HV_DEPTH_U16 else np.float32)
             rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
         intr = np.array([fx, fy, cx, cy], dtype=np.float64)
@@ -1154,17 +1245,7 @@ class VoxelBlockGrid(_Volume):
 
     # -- queries ---------------------------------------------------------------------------------
     def _collect(self, call):
-        n = ctypes.c_int64()
-        L.check(call(None, None, 0, ctypes.byref(n)))
-        pts = np.zeros((n.value, 3), np.float32)
-        cols = np.zeros((n.value, 3), np.float32)
-        if n.value:
-            L.check(call(L.ptr(pts), L.ptr(cols), n.value, ctypes.byref(n)))
-        return VoxelGridData(pts, cols)
-
-    def set_owner(self, rank, world_size):
-        """Multi-GPU block ownership: fuse only the blocks with hash(block key) % world_size == rank (no collective while fusing)."""
-        L.check(self._lib.hv_set_owner(self._h, int(rank), int(world_size)))
+        return VoxelGridData(*self._sized_fetch(call, ((3,), np.float32), ((3,), np.float32)))
 
     def get_voxels(self, min_count=1, min_confidence=0.0):
         return self._collect(
@@ -1194,32 +1275,8 @@ class VoxelBlockGrid(_Volume):
             )
         )
 
-    def carve(self, camera_frustrum, depth_image, depth_threshold=1e-2):
-        self._carve(camera_frustrum, depth_image, depth_threshold)
-
-    def remove_low_count_voxels(self, min_count):
-        L.check(self._lib.hv_remove_low_count_voxels(self._h, int(min_count)))
-
     def remove_low_confidence_voxels(self, min_confidence):
         return  # no-op for non-semantic voxels (voxel_block_grid.hpp:650-676)
-
-    def clear(self):
-        L.check(self._lib.hv_reset(self._h))
-
-    reset = clear
-
-    def size(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_size(self._h, ctypes.byref(n)))
-        return n.value
-
-    get_total_voxel_count = size
-
-    def empty(self):
-        return self.num_blocks() == 0
-
-    def get_block_size(self):
-        return self.block_size
 
     # -- parity/debug ----------------------------------------------------------------------------
     def dump(self):
@@ -1230,8 +1287,7 @@ class VoxelBlockGrid(_Volume):
         hashes = np.zeros(nb, np.uint64)
         counts = np.zeros((nb, nv), np.int32)
         sums = np.zeros((nb, nv, 6), np.float32)
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_dump_blocks(self._h, L.ptr(keys), L.ptr(hashes), L.ptr(counts), L.ptr(sums), ctypes.byref(n)))
+        self._int64(self._lib.hv_dump_blocks, L.ptr(keys), L.ptr(hashes), L.ptr(counts), L.ptr(sums))
         return keys, hashes, counts, sums
 
     def keys_from_points(self, points):
@@ -1353,30 +1409,38 @@ class ScalableTSDFVolume(_Volume):
 
     def integrate(self, image, intrinsic, extrinsic):
         """image: RGBDImage (color HxWx3 uint8 RGB, depth HxW uint16 or any real dtype, read as float32); extrinsic = T_cw."""
-        depth, color, dkind, converted = _tsdf_operands(image.depth, image.color, intrinsic)
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        intr = intrinsic.as_array()
-        T = _as_f64_4x4(extrinsic)
-        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_integrate(
-            self._h, L.ptr(depth), dkind, L.ptr(color), H, W, L.ptr(intr), L.ptr(T), image.depth_scale, image.depth_trunc,
-            L.location(depth)))
+        self._frame_call(self._lib.hv_tsdf_integrate, image.depth, image.color, intrinsic, [extrinsic], image.depth_scale, image.depth_trunc)
 
     def integrate_batch(self, depth, color, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """Replay F posed frames ([F,H,W] depth, [F,H,W,3] colour, [F,4,4] T_cw); same result as F
         integrate() calls (the rebuild() use case, volumetric_integrator_base.py:1242-1318)."""
+        self._frame_call(self._lib.hv_tsdf_integrate_batch, depth, color, intrinsic, [extrinsics], float(depth_scale), float(depth_trunc),
+                         batch=True)
+
+    def _batch_operands(self, depth, color, intrinsic, *extrinsics):
         F = int(depth.shape[0]) if len(depth.shape) == 3 else -1
         depth, color, dkind, converted = _tsdf_operands(depth, color, intrinsic, frames=F)
-        T = np.asarray(extrinsics, dtype=np.float64)
-        if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
-            raise RuntimeError(_UNSUPPORTED_IMAGE)
-        if F == 0:
-            return
-        H, W = int(depth.shape[1]), int(depth.shape[2])
-        T = np.ascontiguousarray(T.reshape(F, 16))
-        intr = intrinsic.as_array()
-        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_integrate_batch(
-            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(T), float(depth_scale), float(depth_trunc),
-            L.location(depth)))
+        return F, depth, color, dkind, converted, [_pose_rows(T, F) for T in extrinsics]
+
+    def _frame_call(self, fn, depth, color, intrinsic, poses, depth_scale, depth_trunc, batch=False, stats=False):
+        """The one path of integrate / deintegrate / reintegrate, of one frame (poses: 4x4 each) or, batch=True, of F frames (poses:
+        F each): the operands in the library's layout (_tsdf_operands), the pose check, fn(handle, depth, kind, colour, [F,] H, W,
+        intrinsics, pose(s), depth_scale, depth_trunc, location[, stats]) through _launch_tsdf.  stats: fn fills a
+        hv_deintegrate_stats -> DeintegrationStats, else None.  Zero frames: no call, and the stats stay 0."""
+        if batch:
+            F, depth, color, dkind, converted, poses = self._batch_operands(depth, color, intrinsic, *poses)
+            dims = (F, int(depth.shape[1]), int(depth.shape[2]))
+        else:
+            depth, color, dkind, converted = _tsdf_operands(depth, color, intrinsic)
+            dims = (int(depth.shape[0]), int(depth.shape[1]))
+            poses = [_as_f64_4x4(T) for T in poses]
+        st = L.HvDeintegrateStats() if stats else None
+        if not (batch and dims[0] == 0):
+            intr = intrinsic.as_array()
+            tail = (depth_scale, depth_trunc, L.location(depth)) + ((ctypes.byref(st),) if stats else ())
+            self._launch_tsdf(depth, color, converted, lambda: fn(
+                self._h, L.ptr(depth), dkind, L.ptr(color), *dims, L.ptr(intr), *[L.ptr(T) for T in poses], *tail))
+        return _stats(DeintegrationStats, st) if stats else None
 
     def _launch_tsdf(self, depth, color, converted, call):
         """The kernels gather from the operands asynchronously on the volume's stream: keep them alive until the next call (by
@@ -1396,56 +1460,22 @@ class ScalableTSDFVolume(_Volume):
         hv_tsdf_deintegrate): image and extrinsic must be what that frame was fused with.  Where they are not, and the voxel holds
         more observations than are removed, each colour sum is clamped to [0, 255 * weight] (colours stay in 0..255); the tsdf is
         not clamped.  Waits for the GPU and returns DeintegrationStats."""
-        depth, color, dkind, converted = _tsdf_operands(image.depth, image.color, intrinsic)
-        H, W = int(depth.shape[0]), int(depth.shape[1])
-        intr = intrinsic.as_array()
-        T = _as_f64_4x4(extrinsic)
-        st = L.HvDeintegrateStats()
-        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_deintegrate(
-            self._h, L.ptr(depth), dkind, L.ptr(color), H, W, L.ptr(intr), L.ptr(T), image.depth_scale, image.depth_trunc,
-            L.location(depth), ctypes.byref(st)))
-        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
-
-    def _batch_operands(self, depth, color, intrinsic, *extrinsics):
-        F = int(depth.shape[0]) if len(depth.shape) == 3 else -1
-        depth, color, dkind, converted = _tsdf_operands(depth, color, intrinsic, frames=F)
-        Ts = []
-        for T in extrinsics:
-            T = np.asarray(T, dtype=np.float64)
-            if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
-                raise RuntimeError(_UNSUPPORTED_IMAGE)
-            Ts.append(np.ascontiguousarray(T.reshape(F, 16)))
-        return F, depth, color, dkind, converted, Ts
+        return self._frame_call(self._lib.hv_tsdf_deintegrate, image.depth, image.color, intrinsic, [extrinsic], image.depth_scale,
+                                image.depth_trunc, stats=True)
 
     def deintegrate_batch(self, depth, color, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """Take F frames ([F,H,W] depth, [F,H,W,3] colour, [F,4,4] T_cw they were fused with) back out of the map, in chunks of 64
         frames in order (colour sums clamped as in deintegrate).  Waits for the GPU and returns DeintegrationStats; zero frames is a
         no-op."""
-        F, depth, color, dkind, converted, (T,) = self._batch_operands(depth, color, intrinsic, extrinsics)
-        if F == 0:
-            return DeintegrationStats()
-        H, W = int(depth.shape[1]), int(depth.shape[2])
-        intr = intrinsic.as_array()
-        st = L.HvDeintegrateStats()
-        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_deintegrate_batch(
-            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(T), float(depth_scale), float(depth_trunc),
-            L.location(depth), ctypes.byref(st)))
-        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
+        return self._frame_call(self._lib.hv_tsdf_deintegrate_batch, depth, color, intrinsic, [extrinsics], float(depth_scale),
+                                float(depth_trunc), batch=True, stats=True)
 
     def reintegrate_batch(self, depth, color, intrinsic, old_extrinsics, new_extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """Move F fused frames from the poses they were fused with (old_extrinsics) to corrected ones (new_extrinsics): the
         result of deintegrate_batch(old) followed by integrate_batch(new), bit for bit, with the frames uploaded once.  Waits for
         the GPU and returns the de-integration's DeintegrationStats; zero frames is a no-op."""
-        F, depth, color, dkind, converted, (To, Tn) = self._batch_operands(depth, color, intrinsic, old_extrinsics, new_extrinsics)
-        if F == 0:
-            return DeintegrationStats()
-        H, W = int(depth.shape[1]), int(depth.shape[2])
-        intr = intrinsic.as_array()
-        st = L.HvDeintegrateStats()
-        self._launch_tsdf(depth, color, converted, lambda: self._lib.hv_tsdf_reintegrate_batch(
-            self._h, L.ptr(depth), dkind, L.ptr(color), F, H, W, L.ptr(intr), L.ptr(To), L.ptr(Tn), float(depth_scale),
-            float(depth_trunc), L.location(depth), ctypes.byref(st)))
-        return DeintegrationStats(st.units_listed, st.units_missing, st.voxels_removed, st.voxels_underflow)
+        return self._frame_call(self._lib.hv_tsdf_reintegrate_batch, depth, color, intrinsic, [old_extrinsics, new_extrinsics],
+                                float(depth_scale), float(depth_trunc), batch=True, stats=True)
 
     def prune(self, empty=True, bounds=None):
         """Give units back to the pool (include/hipvol.h, hv_tsdf_prune).  empty: release every unit whose weights are all 0 -
@@ -1460,7 +1490,7 @@ class ScalableTSDFVolume(_Volume):
         st = L.HvPruneStats()
         L.check(self._lib.hv_tsdf_prune(self._h, 1 if empty else 0, None if lo is None else lo.ctypes.data_as(L._pi32),
                                         None if hi is None else hi.ctypes.data_as(L._pi32), ctypes.byref(st)))
-        return PruneStats(st.units_before, st.units_outside, st.units_empty, st.units_after)
+        return _stats(PruneStats, st)
 
     def integrate_volume(self, source, transformation=None):
         """Fuse another TSDF volume into this one (include/hipvol.h, hv_tsdf_integrate_volume): p_self = transformation @ p_source,
@@ -1469,15 +1499,10 @@ class ScalableTSDFVolume(_Volume):
         observations; units are claimed exactly where a voxel is updated.  `source` is only read and must have the same
         voxel_length, sdf_trunc and unit resolution.  To move a map to another frame, merge it ONCE into an empty volume: every merge
         resamples.  Waits for the GPU and returns MergeStats; a source without observed voxels leaves this volume untouched."""
-        if getattr(source, "_h", None) is None:
-            raise TypeError("integrate_volume: source must be a volume")
-        T = np.eye(4) if transformation is None else np.asarray(transformation, dtype=np.float64)
-        if T.shape != (4, 4):
-            raise ValueError("integrate_volume: transformation must be a 4x4 matrix")
-        T = np.ascontiguousarray(T, dtype=np.float64)
+        T = _rigid_operand(source, transformation, "integrate_volume", "transformation")
         st = L.HvMergeStats()
         L.check(self._lib.hv_tsdf_integrate_volume(self._h, source._h, L.ptr(T), ctypes.byref(st)))
-        return MergeStats(st.units_source, st.units_claimed, st.voxels_updated, st.voxels_trilinear, st.voxels_nearest)
+        return _stats(MergeStats, st)
 
     def register_volume(self, source, init=None, max_iterations=30, weight_threshold=3.0, tsdf_band=0.5, residual_trunc=None,
                         huber_delta=None, trace=False):
@@ -1490,12 +1515,7 @@ class ScalableTSDFVolume(_Volume):
         are outliers, beyond huber_delta (default 0.25 sdf_trunc) down-weighted.  Both volumes are only read and must agree in
         voxel_length, sdf_trunc and unit resolution.  Empty maps or no overlap: success False, transformation == init.  Waits for
         the GPU.  trace=True: the per-linearisation record (tests)."""
-        if getattr(source, "_h", None) is None:
-            raise TypeError("register_volume: source must be a volume")
-        T = np.eye(4) if init is None else np.asarray(init, dtype=np.float64)
-        if T.shape != (4, 4):
-            raise ValueError("register_volume: init must be a 4x4 matrix")
-        T = np.ascontiguousarray(T, dtype=np.float64)
+        T = _rigid_operand(source, init, "register_volume", "init")
         prm = L.HvRegisterParams()
         prm.weight_threshold, prm.tsdf_band = float(weight_threshold), float(tsdf_band)
         sdf_trunc = float(getattr(self, "sdf_trunc", 0.0))  # (a volume without one is refused by the library for its mode)
@@ -1511,7 +1531,7 @@ class ScalableTSDFVolume(_Volume):
         return RegistrationResult(np.array(res.T_dst_src, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
                                   np.array(res.information, np.float64).reshape(6, 6), bool(res.success), int(res.iterations),
                                   int(res.inliers), int(res.candidates), np.array(res.anchor, np.float64),
-                                  _register_trace_rows(rows[:n_rows.value]) if trace else None)
+                                  _trace_rows(rows[:n_rows.value], _REGISTER_HEAD) if trace else None)
 
     def integrate_frames(self, depths, colors, intrinsic, extrinsics, depth_scale=1.0, depth_trunc=4.0):
         """integrate_batch for HOST frames held one numpy array per frame (what the integrator worker has after draining
@@ -1520,9 +1540,7 @@ class ScalableTSDFVolume(_Volume):
         F = len(depths)
         if len(colors) != F:
             raise RuntimeError(_UNSUPPORTED_IMAGE)
-        T = np.asarray(extrinsics, dtype=np.float64)
-        if T.size != 16 * F or (T.ndim > 1 and T.shape[0] != F):
-            raise RuntimeError(_UNSUPPORTED_IMAGE)
+        T = _pose_rows(extrinsics, F)
         if F == 0:
             return
         ops = [_tsdf_operands(d, c, intrinsic) for d, c in zip(depths, colors)]
@@ -1532,7 +1550,6 @@ class ScalableTSDFVolume(_Volume):
         depths = [np.asarray(o[0]) for o in ops]  # (host torch tensors: numpy views of the same memory)
         colors = [np.asarray(o[1]) for o in ops]
         H, W = (int(x) for x in depths[0].shape)
-        T = np.ascontiguousarray(T.reshape(F, 16))
         intr = intrinsic.as_array()
         dp = (ctypes.c_void_p * F)(*[d.ctypes.data for d in depths])
         cp = (ctypes.c_void_p * F)(*[c.ctypes.data for c in colors])
@@ -1579,19 +1596,8 @@ class ScalableTSDFVolume(_Volume):
         fn = self._lib.hv_tsdf_extract_mesh if dt == np.float64 else self._lib.hv_tsdf_extract_mesh_f32
         nv, nt = ctypes.c_int64(), ctypes.c_int64()
         L.check(fn(self._h, None, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt)))
-        if device:
-            import torch
-
-            dev = torch.device("cuda", int(self._cfg.device))
-            tdt = torch.float64 if dt == np.float64 else torch.float32
-            verts = torch.empty((nv.value, 3), dtype=tdt, device=dev)
-            cols = torch.empty((nv.value, 3), dtype=tdt, device=dev)
-            tris = torch.empty((nt.value, 3), dtype=torch.int32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
-        else:
-            verts = _result_array((nv.value, 3), dt)
-            cols = _result_array((nv.value, 3), dt)
-            tris = _result_array((nt.value, 3), np.int32)
+        out = self._results({"verts": ((nv.value, 3), dt), "cols": ((nv.value, 3), dt), "tris": ((nt.value, 3), np.int32)}, device)
+        verts, cols, tris = out["verts"], out["cols"], out["tris"]
         if nv.value or nt.value:
             L.check(fn(self._h, L.ptr(verts), L.ptr(cols), nv.value, L.ptr(tris), nt.value, ctypes.byref(nv), ctypes.byref(nt)))
         return TriangleMesh(verts, tris, cols)
@@ -1605,22 +1611,18 @@ class ScalableTSDFVolume(_Volume):
         fn = self._lib.hv_tsdf_extract_points if dt == np.float64 else self._lib.hv_tsdf_extract_points_f32
         n = ctypes.c_int64()
         L.check(fn(self._h, None, None, 0, ctypes.byref(n)))
-        if device:
-            import torch
-
-            dev = torch.device("cuda", int(self._cfg.device))
-            tdt = torch.float64 if dt == np.float64 else torch.float32
-            pts = torch.empty((n.value, 3), dtype=tdt, device=dev)
-            cols = torch.empty((n.value, 3), dtype=tdt, device=dev)
-            torch.cuda.current_stream(dev).synchronize()
-        else:
-            pts = _result_array((n.value, 3), dt)
-            cols = _result_array((n.value, 3), dt)
+        out = self._results({"pts": ((n.value, 3), dt), "cols": ((n.value, 3), dt)}, device)
+        pts, cols = out["pts"], out["cols"]
         nrm = None
         if n.value:
             L.check(fn(self._h, L.ptr(pts), L.ptr(cols), n.value, ctypes.byref(n)))
         if normals:
-            nrm = torch.zeros((n.value, 3), dtype=torch.float64, device=dev) if device else np.zeros((n.value, 3), np.float64)
+            if device:
+                import torch
+
+                nrm = torch.zeros((n.value, 3), dtype=torch.float64, device=self._device())
+            else:
+                nrm = np.zeros((n.value, 3), np.float64)
             if n.value:
                 L.check(self._lib.hv_tsdf_extract_point_normals(self._h, L.ptr(nrm), n.value, ctypes.byref(n)))
         return PointCloud(pts, cols, nrm)
@@ -1643,23 +1645,13 @@ class ScalableTSDFVolume(_Volume):
         shapes = {"depth": (H, W), "vertex": (H, W, 3), "normal": (H, W, 3), "color": (H, W, 3), "mask": (H, W)}
         intr = intrinsic.as_array()
         T = _as_f64_4x4(extrinsic)
-        out = {}
-        if device:
-            import torch
-
-            dev = torch.device("cuda", int(self._cfg.device))
-            for a in attrs:
-                out[a] = torch.empty(shapes[a], dtype=torch.bool if a == "mask" else torch.float32, device=dev)
-            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
-        else:
-            for a in attrs:
-                out[a] = _result_array(shapes[a], np.bool_ if a == "mask" else np.float32)
+        out = self._results({a: (shapes[a], np.bool_ if a == "mask" else np.float32) for a in attrs}, device)
         p = {a: (L.ptr(out[a]) if a in out else None) for a in self.RAY_CAST_ATTRIBUTES}
         L.check(self._lib.hv_tsdf_ray_cast(self._h, H, W, L.ptr(intr), L.ptr(T), float(depth_min), float(depth_max),
                                            float(weight_threshold), float(depth_scale), p["depth"], p["vertex"], p["normal"],
                                            p["color"], p["mask"], L.HV_DEVICE if device else L.HV_HOST))
         if device:
-            self._torch_out(self._torch_stream(dev), dev)
+            self._publish(self._device())
         return out
 
     def track_frame_to_model(self, depth, intrinsic, extrinsic, depth_scale=1.0, depth_min=0.1, depth_max=3.0, weight_threshold=3.0,
@@ -1699,8 +1691,7 @@ class ScalableTSDFVolume(_Volume):
         rows = np.zeros((steps, stride), np.float64) if trace else None
         n_rows = ctypes.c_int64()
         loc = L.location(d)
-        ts = self._torch_in(d) if loc == L.HV_DEVICE else None
-        try:
+        with self._ordered(d):
             if c is None:
                 L.check(self._lib.hv_tsdf_track(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T0), ctypes.byref(prm),
                                                 ctypes.byref(res), L.ptr(rows), steps if trace else 0, ctypes.byref(n_rows), loc))
@@ -1708,9 +1699,6 @@ class ScalableTSDFVolume(_Volume):
                 L.check(self._lib.hv_tsdf_track_color(self._h, L.ptr(d), dkind, L.ptr(c), H, W, L.ptr(intr), L.ptr(T0),
                                                       ctypes.byref(cprm), ctypes.byref(cres), L.ptr(rows), steps if trace else 0,
                                                       ctypes.byref(n_rows), loc))
-        finally:
-            if ts is not None:
-                self._torch_out(ts, d.device)
         n_levels = min(len(iters), L.HV_TRACK_MAX_LEVELS)
         return OdometryResult(np.array(res.T_cw, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
                               np.array(res.information, np.float64).reshape(6, 6), bool(res.success),
@@ -1726,7 +1714,7 @@ class ScalableTSDFVolume(_Volume):
         Reads the volume only.  device=None: results where the input lives - a torch CUDA tensor gives torch CUDA tensors, queued behind
         torch's current stream and ordered before its later work, nothing crosses PCIe; anything else gives numpy arrays.
         device=True / False: torch CUDA tensors on the volume's GPU / numpy arrays, wherever the input lives."""
-        if hasattr(points, "data_ptr") and not isinstance(points, np.ndarray):
+        if _is_torch(points):
             import torch
 
             if points.dtype not in (torch.float32, torch.float64):
@@ -1742,25 +1730,13 @@ class ScalableTSDFVolume(_Volume):
         p, dev = self._query_place(p, device)
         n = int(p.shape[0])
         f64 = str(p.dtype).endswith("float64")
-        shapes = {"sdf": (n,), "gradient": (n, 3) if gradient else None, "color": (n, 3) if color else None, "weight": (n,), "status": (n,)}
-        out = {}
-        for name, shape in shapes.items():
-            if shape is None:
-                out[name] = None
-            elif dev is not None:
-                import torch
-
-                out[name] = torch.empty(shape, dtype=torch.uint8 if name == "status" else torch.float32, device=dev)
-            else:
-                out[name] = np.empty(shape, np.uint8 if name == "status" else np.float32)
-        ts = self._torch_in(p) if dev is not None else None
-        try:
+        f32 = np.float32
+        out = self._results({"sdf": ((n,), f32), "gradient": ((n, 3), f32) if gradient else None, "color": ((n, 3), f32) if color else None,
+                             "weight": ((n,), f32), "status": ((n,), np.uint8)}, dev is not None, pinned=False, synchronize=False)
+        with self._ordered(p):
             L.check(self._lib.hv_tsdf_sample_points(self._h, L.ptr(p), L.HV_F64 if f64 else L.HV_F32, n, float(weight_threshold),
                                                     L.ptr(out["sdf"]), L.ptr(out["gradient"]), L.ptr(out["color"]), L.ptr(out["weight"]),
                                                     L.ptr(out["status"]), L.HV_DEVICE if dev is not None else L.HV_HOST))
-        finally:
-            if ts is not None:
-                self._torch_out(ts, dev)
         return SampleResult(out["sdf"], out["gradient"], out["color"], out["weight"], out["status"])
 
     def check_frame(self, depth, intrinsic, extrinsic, depth_scale=1.0, depth_min=0.1, depth_max=3.0, weight_threshold=0.0,
@@ -1781,21 +1757,12 @@ class ScalableTSDFVolume(_Volume):
         prm.tolerance = 0.5 * float(getattr(self, "sdf_trunc", 0.0)) if tolerance is None else float(tolerance)
         intr = intrinsic.as_array()
         T = _as_f64_4x4(extrinsic)
-        if dev is not None:
-            import torch
-
-            sdf = torch.empty((H, W), dtype=torch.float32, device=dev)
-            cls = torch.empty((H, W), dtype=torch.uint8, device=dev)
-        else:
-            sdf, cls = np.empty((H, W), np.float32), np.empty((H, W), np.uint8)
+        out = self._results({"sdf": ((H, W), np.float32), "cls": ((H, W), np.uint8)}, dev is not None, pinned=False, synchronize=False)
+        sdf, cls = out["sdf"], out["cls"]
         st = L.HvCheckStats()
-        ts = self._torch_in(d) if dev is not None else None
-        try:
+        with self._ordered(d):
             L.check(self._lib.hv_tsdf_check_frame(self._h, L.ptr(d), dkind, H, W, L.ptr(intr), L.ptr(T), ctypes.byref(prm), L.ptr(sdf),
                                                   L.ptr(cls), ctypes.byref(st), L.HV_DEVICE if dev is not None else L.HV_HOST))
-        finally:
-            if ts is not None:
-                self._torch_out(ts, dev)
         return FrameCheck(sdf, cls, FrameCheckStats(*st.count))
 
     DISTANCE_FIELD_OUTPUTS = ("distance", "dist2", "cls")
@@ -1845,27 +1812,16 @@ class ScalableTSDFVolume(_Volume):
         prm.radius, prm.weight_threshold = R, float(weight_threshold)
         dtypes = {"distance": np.float32, "dist2": np.uint32, "cls": np.uint8}
         full = tuple(int(n) for n in full_shape)
-        out = {}
-        dev = None
-        if device:
-            import torch
-
-            dev = torch.device("cuda", int(self._cfg.device))
-            for a in names:  # (torch has no uint32 arithmetic: dist2 is an int32 tensor with the same bits, values <= 2^20)
-                out[a] = torch.empty(full, dtype={"distance": torch.float32, "dist2": torch.int32, "cls": torch.uint8}[a], device=dev)
-            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
-        else:
-            for a in names:
-                out[a] = _result_array(full, dtypes[a])
+        out = self._results({a: (full, dtypes[a]) for a in names}, device)  # (device: dist2 int32, the same bits, values <= 2^20)
         st = L.HvDistanceStats()
         L.check(self._lib.hv_tsdf_distance_field(self._h, ctypes.byref(prm), L.ptr(out.get("distance")), L.ptr(out.get("dist2")),
                                                  L.ptr(out.get("cls")), ctypes.byref(st), L.HV_DEVICE if device else L.HV_HOST))
         if device:
-            self._torch_out(self._torch_stream(dev), dev)
+            self._publish(self._device())
         crop = tuple(slice(grow, grow + int(n)) for n in shape)
         view = {a: (out[a][crop] if a in out else None) for a in self.DISTANCE_FIELD_OUTPUTS}
         return DistanceField(view["distance"], view["dist2"], view["cls"], origin, shape, float(vl), R,
-                             DistanceFieldStats(st.unknown, st.free, st.inside, st.sites, st.far))
+                             _stats(DistanceFieldStats, st))
 
     def surface_components(self, weight_threshold=0.0, sites=False, device=False):
         """The connected pieces of the map's surface, labelled in the sparse unit hash on the GPU: -> SurfaceComponents.  A voxel is
@@ -1886,26 +1842,15 @@ class ScalableTSDFVolume(_Volume):
         shapes = {"seed": ((C, 3), np.int32), "sites": ((C,), np.int64), "lo": ((C, 3), np.int32), "hi": ((C, 3), np.int32)}
         if sites:
             shapes.update({"site_index": ((N, 3), np.int32), "site_label": ((N,), np.int32)})
-        out = {}
-        dev = None
-        if device:
-            import torch
-
-            dev = torch.device("cuda", int(self._cfg.device))
-            for name, (shape, dtype) in shapes.items():
-                out[name] = torch.empty(shape, dtype=getattr(torch, np.dtype(dtype).name), device=dev)
-            torch.cuda.current_stream(dev).synchronize()  # (the allocator may hand out blocks with work pending on torch's stream)
-        else:
-            for name, (shape, dtype) in shapes.items():
-                out[name] = _result_array(shape, dtype)
+        out = self._results(shapes, device)
         if C > 0:
             L.check(call(self._h, float(weight_threshold), L.ptr(out["seed"]), L.ptr(out["sites"]), L.ptr(out["lo"]), L.ptr(out["hi"]), C,
                          L.ptr(out.get("site_index")), L.ptr(out.get("site_label")), N, ctypes.byref(nc), ctypes.byref(ns), ctypes.byref(st),
                          L.HV_DEVICE if device else L.HV_HOST))
             if device:
-                self._torch_out(self._torch_stream(dev), dev)
+                self._publish(self._device())
         return SurfaceComponents(out["seed"], out["sites"], out["lo"], out["hi"], out.get("site_index"), out.get("site_label"),
-                                 SurfaceComponentsStats(st.units, st.sites, st.components, st.largest), self.voxel_length)
+                                 _stats(SurfaceComponentsStats, st), self.voxel_length)
 
     def remove_small_components(self, min_sites, weight_threshold=0.0, margin=None):
         """Clean the map: reset, in place, every surface component with fewer than min_sites sites - the floaters that noisy depth,
@@ -1919,8 +1864,7 @@ class ScalableTSDFVolume(_Volume):
             margin = min(L.HV_COMPONENTS_MAX_MARGIN, int(np.ceil(np.float64(self.sdf_trunc) / np.float64(self.voxel_length))))
         st = L.HvRemoveComponentsStats()
         L.check(self._lib.hv_tsdf_remove_components(self._h, float(weight_threshold), int(min_sites), int(margin), ctypes.byref(st)))
-        return ComponentRemovalStats(st.components, st.components_removed, st.sites, st.sites_removed, st.voxels_reset, st.units_changed,
-                                     st.units_emptied)
+        return _stats(ComponentRemovalStats, st)
 
     # -- parity/debug + multi-GPU ------------------------------------------------------------------
     def dump(self):
@@ -1932,34 +1876,21 @@ class ScalableTSDFVolume(_Volume):
         tsdf = np.zeros((nu, nv), np.float32)
         weight = np.zeros((nu, nv), np.float32)
         color = np.zeros((nu, nv, 3), np.float64)
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_tsdf_dump(self._h, L.ptr(keys), L.ptr(tsdf), L.ptr(weight), L.ptr(color), ctypes.byref(n)))
+        self._int64(self._lib.hv_tsdf_dump, L.ptr(keys), L.ptr(tsdf), L.ptr(weight), L.ptr(color))
         return keys, tsdf, weight, color
 
+    def _keys(self, fn):
+        return self._sized_fetch(functools.partial(fn, self._h), ((3,), np.int32))[0]
+
     def touched_keys(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_tsdf_touched(self._h, None, 0, ctypes.byref(n)))
-        keys = np.zeros((n.value, 3), np.int32)
-        if n.value:
-            L.check(self._lib.hv_tsdf_touched(self._h, L.ptr(keys), n.value, ctypes.byref(n)))
-        return keys
+        return self._keys(self._lib.hv_tsdf_touched)
 
     def unit_keys(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_tsdf_unit_keys(self._h, None, 0, ctypes.byref(n)))
-        keys = np.zeros((n.value, 3), np.int32)
-        if n.value:
-            L.check(self._lib.hv_tsdf_unit_keys(self._h, L.ptr(keys), n.value, ctypes.byref(n)))
-        return keys
+        return self._keys(self._lib.hv_tsdf_unit_keys)
 
     def dirty_keys(self):
         """Units this GPU stamped (i.e. may have updated) since the last mark_merged(), sorted [K,3] int32."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_tsdf_dirty_keys(self._h, None, 0, ctypes.byref(n)))
-        keys = np.zeros((n.value, 3), np.int32)
-        if n.value:
-            L.check(self._lib.hv_tsdf_dirty_keys(self._h, L.ptr(keys), n.value, ctypes.byref(n)))
-        return keys
+        return self._keys(self._lib.hv_tsdf_dirty_keys)
 
     def mark_merged(self):
         L.check(self._lib.hv_tsdf_mark_merged(self._h))
@@ -1976,19 +1907,13 @@ class ScalableTSDFVolume(_Volume):
     def halo_plan_device(self, dirty_all, dirty_counts, held_all, held_counts, world_size, rank, all_dirty_kept=False):
         """The gathered lists ([world, stride] CUDA int64 tensors; counts: host int64 [world]) -> the merge plan, left in the volume.
         -> number of shared units."""
-        n = ctypes.c_int64()
         dc, hc = np.ascontiguousarray(dirty_counts, dtype=np.int64), np.ascontiguousarray(held_counts, dtype=np.int64)
-        L.check(self._lib.hv_merge_halo_plan_device(self._h, L.ptr(dirty_all), L.ptr(dc), int(dirty_all.shape[1]), L.ptr(held_all), L.ptr(hc),
-                                                    int(held_all.shape[1]), int(world_size), int(rank), int(bool(all_dirty_kept)), ctypes.byref(n)))
-        return n.value
+        return self._int64(self._lib.hv_merge_halo_plan_device, L.ptr(dirty_all), L.ptr(dc), int(dirty_all.shape[1]), L.ptr(held_all), L.ptr(hc),
+                           int(held_all.shape[1]), int(world_size), int(rank), int(bool(all_dirty_kept)))
 
     def halo_plan_fetch(self):
         """-> (shared_keys [K,3] int32, action [K] uint8) of the stored plan (host arrays; inspection and tests)."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_merge_halo_plan_fetch(self._h, None, None, 0, ctypes.byref(n)))
-        keys, action = np.zeros((n.value, 3), np.int32), np.zeros(n.value, np.uint8)
-        if n.value:
-            L.check(self._lib.hv_merge_halo_plan_fetch(self._h, L.ptr(keys), L.ptr(action), n.value, ctypes.byref(n)))
+        keys, action = self._sized_fetch(functools.partial(self._lib.hv_merge_halo_plan_fetch, self._h), ((3,), np.int32), ((), np.uint8))
         return keys, action
 
     def halo_pack_planned(self, first, count, payload):
@@ -2020,17 +1945,10 @@ class ScalableTSDFVolume(_Volume):
     def _pack(self, device):
         info = L.HvPackInfo()
         L.check(self._lib.hv_tsdf_pack_size(self._h, ctypes.byref(info)))
-        if device:
-            import torch
-
-            out = torch.empty(info.bytes, dtype=torch.uint8, device=torch.device("cuda", int(self._cfg.device)))
-        else:
-            out = _result_array((info.bytes,), np.uint8)
-        ts = self._torch_in(out)
-        L.check(self._lib.hv_tsdf_pack(self._h, L.ptr(out), info.bytes, L.location(out), ctypes.byref(info)))
-        if device:
-            self._torch_out(ts, out.device)
-        return out, PackStats(info.units, info.voxels, info.bytes)
+        out = self._results({"map": ((info.bytes,), np.uint8)}, device, synchronize=False)["map"]
+        with self._ordered(out):
+            L.check(self._lib.hv_tsdf_pack(self._h, L.ptr(out), info.bytes, L.location(out), ctypes.byref(info)))
+        return out, _stats(PackStats, info)
 
     def pack(self, device=False):
         """The map as one packed buffer, bit for bit (include/hipvol.h "Packed maps"): every allocated unit, and of each the voxels
@@ -2048,12 +1966,10 @@ class ScalableTSDFVolume(_Volume):
         integrate_volume that.  Waits for the GPU and returns PackStats."""
         op = _packed_operand(buf)
         info = L.HvPackInfo()
-        ts = self._torch_in(op)
-        L.check(self._lib.hv_tsdf_unpack(self._h, L.ptr(op), int(op.numel() if hasattr(op, "numel") else op.size), L.location(op),
-                                         ctypes.byref(info)))
-        if ts is not None:
-            self._torch_out(ts, op.device)
-        return PackStats(info.units, info.voxels, info.bytes)
+        with self._ordered(op):
+            L.check(self._lib.hv_tsdf_unpack(self._h, L.ptr(op), int(op.numel() if _is_torch(op) else op.size), L.location(op),
+                                             ctypes.byref(info)))
+        return _stats(PackStats, info)
 
     def save(self, path):
         """pack() into the file `path`: written to a temporary file in the same directory, then moved into place (os.replace), so
@@ -2107,7 +2023,7 @@ class ScalableTSDFVolume(_Volume):
             op = np.fromfile(path_or_buffer, dtype=np.uint8)
         else:
             op = _packed_operand(path_or_buffer)
-            if hasattr(op, "is_cuda"):
+            if _is_torch(op):
                 op = op.cpu().numpy()
         lib = L.load()
         hdr = L.HvPackedHeader()

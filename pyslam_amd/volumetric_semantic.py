@@ -13,13 +13,14 @@ set_depth_threshold, set_depth_decay_rate, clear/reset, size, num_blocks; module
 Also: get_voxels_in_bb / get_voxels_in_camera_frustrum (include_semantics), integrate_segment, get_class_segments.
 The module's "*2" payloads (voxel_data_semantic2.h) are the *Grid2 classes at the end."""
 import ctypes
+import functools
 import weakref
 from collections.abc import Mapping
 
 import numpy as np
 
 from . import _lib as L
-from .volumetric import VoxelData, VoxelGridData, _Volume
+from .volumetric import VoxelData, VoxelGridData, _BlockGrid, _colors_operand, _points_operand
 
 
 class OBBComputationMethod:
@@ -218,17 +219,17 @@ def _is_device(a):
     return a is not None and hasattr(a, "is_cuda") and bool(a.is_cuda)
 
 
-def _device_images(*images, device=0):
+def _device_images(volume, *images):
     """The per-keyframe images of one call, all at ONE location: when any of them is a torch CUDA tensor the numpy ones are
     uploaded (torch's blocking copy), so that a caller can keep a keyframe's depth / label images in HBM across
     filter_shadow_points -> assign_object_ids_to_instance_ids -> remap_instance_ids -> integrate_rgbd instead of staging each
-    of them again in every call.  The images must live on the volume's GPU (`device`: hv_config.device): a tensor of another GPU
-    is an error, not a silent peer access.  -> (list of images, HV_DEVICE | HV_HOST)."""
+    of them again in every call.  The images must live on the volume's GPU (hv_config.device): a tensor of another GPU is an
+    error, not a silent peer access.  -> (list of images, HV_DEVICE | HV_HOST)."""
     if not any(_is_device(a) for a in images):
         return list(images), L.HV_HOST
     import torch
 
-    dev = torch.device("cuda", int(device))
+    dev = volume._device()
     out = []
     for a in images:
         if a is None:
@@ -240,6 +241,14 @@ def _device_images(*images, device=0):
         else:
             out.append(torch.from_numpy(np.ascontiguousarray(a)).to(dev))
     return out, L.HV_DEVICE
+
+
+def _check_device_keyframe(depth, rgb, *labels):
+    """The dtypes the kernels read from a device-resident keyframe."""
+    import torch
+
+    if depth.dtype != torch.float32 or rgb.dtype != torch.uint8 or any(a is not None and a.dtype != torch.int32 for a in labels):
+        raise RuntimeError("device images must be float32 depth, uint8 colour, int32 labels")
 
 
 class LazyIdMap(Mapping):
@@ -279,48 +288,13 @@ class LazyIdMap(Mapping):
         return repr(self._get())
 
 
-def _remap_with_last_map(instance_ids, id_map, volume):
-    """remap_instance_ids with the device-resident map of the volume's last association (hv_remap_instance_ids_last)."""
-    v = volume
-    if _is_device(instance_ids):
-        import torch
-
-        img = instance_ids.contiguous()
-        if img.dim() != 2:
-            raise RuntimeError("Instance ids must be single-channel")
-        if img.dtype != torch.int32:
-            raise RuntimeError("Instance ids must be int32")
-        out = torch.empty_like(img)
-        ts = v._torch_in(img, out)
-        L.check(v._lib.hv_remap_instance_ids_last(v._h, L.ptr(img), int(img.shape[0]), int(img.shape[1]), L.ptr(out), L.HV_DEVICE))
-        v._torch_out(ts, img.device)
-        return out
-    img = np.ascontiguousarray(instance_ids)
-    if img.size == 0:
-        return img
-    if img.ndim != 2:
-        raise RuntimeError("Instance ids must be single-channel")
-    if img.dtype in (np.int8, np.uint8, np.int16, np.uint16):
-        # the binding's narrower instantiations (image_utils_module.h:66-88): looked up as int, written back in the image's own type
-        # (an object id, and the invalid id -1, narrowed the way the C++ assignment does: modulo 2^bits)
-        if len(instance_id_to_object_id) == 0:
-            return img
-        return remap_instance_ids(img.astype(np.int32), instance_id_to_object_id, volume).astype(img.dtype)
-    if img.dtype != np.int32:
-        raise RuntimeError("Unsupported instance id type")
-    out = np.empty_like(img)
-    L.check(v._lib.hv_remap_instance_ids_last(v._h, L.ptr(img), img.shape[0], img.shape[1], L.ptr(out), L.HV_HOST))
-    return out
-
-
 def remap_instance_ids(instance_ids, instance_id_to_object_id, volume=None):
     """volumetric.remap_instance_ids(image int32 HxW, map) (image_utils.h:69-163, binding image_utils_module.h):
     ids absent from the map become -1; an EMPTY map returns the image as it is (the binding's early return, image_utils_module.h:52-58 -
     the C++ template behind it would set every id to -1).  Runs on the GPU of ``volume`` (any volume).  A torch CUDA int32
     image stays on the device (the result is a CUDA tensor).  The map an association on ``volume`` just returned is used where it
-    lies, in device memory."""
-    if isinstance(instance_id_to_object_id, LazyIdMap) and volume is not None and instance_id_to_object_id.on_device_of(volume):
-        return _remap_with_last_map(instance_ids, instance_id_to_object_id, volume)
+    lies, in device memory (hv_remap_instance_ids_last)."""
+    id_map = instance_id_to_object_id
     if _is_device(instance_ids):
         import torch
 
@@ -329,36 +303,33 @@ def remap_instance_ids(instance_ids, instance_id_to_object_id, volume=None):
             raise RuntimeError("Instance ids must be single-channel")
         if img.dtype != torch.int32:
             raise RuntimeError("Instance ids must be int32")
-        if volume is None:
-            volume = _scratch_volume()
-        keys = np.fromiter(instance_id_to_object_id.keys(), np.int32, len(instance_id_to_object_id))
-        vals = np.fromiter(instance_id_to_object_id.values(), np.int32, len(instance_id_to_object_id))
-        out = torch.empty_like(img)
-        ts = volume._torch_in(img, out)
-        L.check(volume._lib.hv_remap_instance_ids(volume._h, L.ptr(img), int(img.shape[0]), int(img.shape[1]), L.ptr(keys), L.ptr(vals),
-                                                  len(keys), L.ptr(out), L.HV_DEVICE))
-        volume._torch_out(ts, img.device)
-        return out
-    img = np.ascontiguousarray(instance_ids)
-    if img.size == 0:
-        return img
-    if img.ndim != 2:
-        raise RuntimeError("Instance ids must be single-channel")
-    if img.dtype in (np.int8, np.uint8, np.int16, np.uint16):
-        # the binding's narrower instantiations (image_utils_module.h:66-88): looked up as int, written back in the image's own type
-        # (an object id, and the invalid id -1, narrowed the way the C++ assignment does: modulo 2^bits)
-        if len(instance_id_to_object_id) == 0:
+        out, loc = torch.empty_like(img), L.HV_DEVICE
+    else:
+        img = np.ascontiguousarray(instance_ids)
+        if img.size == 0:
             return img
-        return remap_instance_ids(img.astype(np.int32), instance_id_to_object_id, volume).astype(img.dtype)
-    if img.dtype != np.int32:
-        raise RuntimeError("Unsupported instance id type")
+        if img.ndim != 2:
+            raise RuntimeError("Instance ids must be single-channel")
+        if img.dtype in (np.int8, np.uint8, np.int16, np.uint16):
+            # the binding's narrower instantiations (image_utils_module.h:66-88): looked up as int, written back in the image's own type
+            # (an object id, and the invalid id -1, narrowed the way the C++ assignment does: modulo 2^bits)
+            if len(id_map) == 0:
+                return img
+            return remap_instance_ids(img.astype(np.int32), id_map, volume).astype(img.dtype)
+        if img.dtype != np.int32:
+            raise RuntimeError("Unsupported instance id type")
+        out, loc = np.empty_like(img), L.HV_HOST
+    H, W = int(img.shape[0]), int(img.shape[1])
+    if isinstance(id_map, LazyIdMap) and volume is not None and id_map.on_device_of(volume):
+        with volume._ordered(img, out):
+            L.check(volume._lib.hv_remap_instance_ids_last(volume._h, L.ptr(img), H, W, L.ptr(out), loc))
+        return out
     if volume is None:
         volume = _scratch_volume()
-    keys = np.fromiter(instance_id_to_object_id.keys(), np.int32, len(instance_id_to_object_id))
-    vals = np.fromiter(instance_id_to_object_id.values(), np.int32, len(instance_id_to_object_id))
-    out = np.empty_like(img)
-    L.check(volume._lib.hv_remap_instance_ids(volume._h, L.ptr(img), img.shape[0], img.shape[1], L.ptr(keys), L.ptr(vals),
-                                              len(keys), L.ptr(out), L.HV_HOST))
+    keys = np.fromiter(id_map.keys(), np.int32, len(id_map))
+    vals = np.fromiter(id_map.values(), np.int32, len(id_map))
+    with volume._ordered(img, out):
+        L.check(volume._lib.hv_remap_instance_ids(volume._h, L.ptr(img), H, W, L.ptr(keys), L.ptr(vals), len(keys), L.ptr(out), loc))
     return out
 
 
@@ -398,17 +369,11 @@ class VoxelSemanticData(VoxelData):
         return self.confidence_counter
 
 
-class _SemanticGridBase(_Volume):
+class _SemanticGridBase(_BlockGrid):
     _MODE = None
 
     def __init__(self, voxel_size=0.05, block_size=8, device=0, max_blocks=None, max_points=None):
-        voxel_size = float(np.float32(voxel_size))
-        super().__init__(self._MODE, voxel_size, 0.0, block_size, 1, device, max_blocks, max_points)
-        self.voxel_size, self.block_size = voxel_size, int(block_size)
-
-    def set_owner(self, rank, world_size):
-        """Multi-GPU block ownership (hv_set_owner): this grid fuses and stores only the blocks owner(block key) == rank."""
-        L.check(self._lib.hv_set_owner(self._h, int(rank), int(world_size)))
+        super().__init__(self._MODE, voxel_size, block_size, device, max_blocks, max_points)
 
     def set_depth_threshold(self, depth_threshold):
         L.check(self._lib.hv_set_depth_threshold(self._h, float(depth_threshold)))
@@ -417,27 +382,10 @@ class _SemanticGridBase(_Volume):
         L.check(self._lib.hv_set_depth_decay_rate(self._h, float(depth_decay_rate)))
 
     def integrate(self, points, colors=None, class_ids=None, instance_ids=None, depths=None):
-        pts = np.asarray(points)
-        if pts.ndim != 2 or pts.shape[1] != 3:
-            raise RuntimeError("points must be a contiguous Nx3 array")
-        pdt = 1 if pts.dtype == np.float64 else 0
-        pts = np.ascontiguousarray(pts, dtype=np.float64 if pdt else np.float32)
-        n = pts.shape[0]
+        pts, wide, n = _points_operand(points)
         if n == 0:
             return
-        kind, cols = L.HV_COLOR_NONE, None
-        if colors is not None:
-            cols = np.ascontiguousarray(colors)
-            if cols.ndim != 2 or cols.shape[1] != 3:
-                raise RuntimeError("colors must be a contiguous Nx3 array")
-            if cols.shape[0] != n:
-                raise RuntimeError("points and colors must have the same size")
-            if cols.dtype == np.uint8:
-                kind = L.HV_COLOR_U8
-            elif cols.dtype == np.float32:
-                kind = L.HV_COLOR_F32
-            else:
-                raise RuntimeError(f"Colors must be uint8 or float32, got dtype with {cols.dtype}")
+        cols, kind = _colors_operand(colors, n)
 
         def ids(a, name):
             if a is None:
@@ -455,7 +403,7 @@ class _SemanticGridBase(_Volume):
                 raise RuntimeError("points and depths must have the same size")
         if inst is not None and cls is None:
             raise RuntimeError("instance_ids but no class_ids is not supported")
-        L.check(self._lib.hv_integrate_points_semantic(self._h, L.ptr(pts), pdt, n, L.ptr(cols), kind, L.ptr(cls), L.ptr(inst),
+        L.check(self._lib.hv_integrate_points_semantic(self._h, L.ptr(pts), 1 if wide else 0, n, L.ptr(cols), kind, L.ptr(cls), L.ptr(inst),
                                                        L.ptr(dep), L.HV_HOST))
 
     def integrate_rgbd(self, depth, rgb, fx, fy, cx, cy, T_cw, class_ids_image=None, object_ids_image=None, max_depth=np.inf,
@@ -464,18 +412,13 @@ class _SemanticGridBase(_Volume):
         (already RGB), label images i32 [H,W] or None, T_cw world->camera."""
         if any(_is_device(a) for a in (depth, rgb, class_ids_image, object_ids_image)):
             # device-resident keyframe (torch CUDA tensors: depth f32, rgb u8, labels i32): nothing is staged
-            import torch
-
             (depth, rgb, cls, obj), loc = _device_images(
-                depth if _is_device(depth) else np.ascontiguousarray(depth, dtype=np.float32),
+                self, depth if _is_device(depth) else np.ascontiguousarray(depth, dtype=np.float32),
                 rgb if _is_device(rgb) else np.ascontiguousarray(rgb, dtype=np.uint8),
                 class_ids_image if class_ids_image is None or _is_device(class_ids_image) else np.ascontiguousarray(class_ids_image, dtype=np.int32),
-                object_ids_image if object_ids_image is None or _is_device(object_ids_image) else np.ascontiguousarray(object_ids_image, dtype=np.int32),
-                device=self._cfg.device)
-            if depth.dtype != torch.float32 or rgb.dtype != torch.uint8 or any(a is not None and a.dtype != torch.int32 for a in (cls, obj)):
-                raise RuntimeError("device images must be float32 depth, uint8 colour, int32 labels")
+                object_ids_image if object_ids_image is None or _is_device(object_ids_image) else np.ascontiguousarray(object_ids_image, dtype=np.int32))
+            _check_device_keyframe(depth, rgb, cls, obj)
             H, W = int(depth.shape[0]), int(depth.shape[1])
-            ts = self._torch_in(depth, rgb, cls, obj)
         else:
             loc = L.HV_HOST
             depth = np.ascontiguousarray(depth, dtype=np.float32)
@@ -491,10 +434,9 @@ class _SemanticGridBase(_Volume):
         intr = np.array([fx, fy, cx, cy], np.float64)
         T = np.ascontiguousarray(T_cw, dtype=np.float64)
         big = float(np.finfo(np.float32).max)
-        L.check(self._lib.hv_integrate_rgbd_semantic(self._h, L.ptr(depth), L.ptr(rgb), L.ptr(cls), L.ptr(obj), H, W, L.ptr(intr), L.ptr(T),
-                                                     float(min_depth), float(min(max_depth, big)), int(bool(use_depths)), loc))
-        if loc == L.HV_DEVICE:
-            self._torch_out(ts, depth.device)
+        with self._ordered(depth, rgb, cls, obj):
+            L.check(self._lib.hv_integrate_rgbd_semantic(self._h, L.ptr(depth), L.ptr(rgb), L.ptr(cls), L.ptr(obj), H, W, L.ptr(intr), L.ptr(T),
+                                                         float(min_depth), float(min(max_depth, big)), int(bool(use_depths)), loc))
 
     def fuse_keyframe(self, camera_frustrum, depth, rgb, class_ids_image, instance_ids_image, fx, fy, cx, cy, T_cw, filter_shadow_points=True,
                       use_instance_ids=True, depth_threshold=0.1, do_carving=False, min_vote_ratio=0.5, min_votes=3, max_depth=np.inf,
@@ -504,60 +446,38 @@ class _SemanticGridBase(_Volume):
         tensors: depth f32, rgb u8, labels i32 or None); queued on the volume's stream, nothing waits.  The same kernels in the same
         order as the separate calls; what goes away is the host time of five calls.  Multi-GPU grids (a pair exchange between vote and
         decide) keep the staged calls."""
-        import torch
-
         if self._pair_exchange is not None or self._pair_exchange_device is not None:
             raise RuntimeError("fuse_keyframe: a sharded grid exchanges its pair lists between vote and decide - use the staged calls")
-        (depth, rgb, cls, inst), _ = _device_images(depth, rgb, class_ids_image, instance_ids_image, device=self._cfg.device)
-        if depth.dtype != torch.float32 or rgb.dtype != torch.uint8 or any(a is not None and a.dtype != torch.int32 for a in (cls, inst)):
-            raise RuntimeError("device images must be float32 depth, uint8 colour, int32 labels")
+        (depth, rgb, cls, inst), _ = _device_images(self, depth, rgb, class_ids_image, instance_ids_image)
+        _check_device_keyframe(depth, rgb, cls, inst)
         H, W = int(depth.shape[0]), int(depth.shape[1])
         f = camera_frustrum
         if tuple(rgb.shape[:2]) != (H, W) or any(a is not None and tuple(a.shape) != (H, W) for a in (cls, inst)) or (f.height, f.width) != (H, W):
             raise RuntimeError("fuse_keyframe: image sizes differ")
         use_inst = bool(use_instance_ids) and inst is not None
         if use_inst and cls is not None:
-            prev = getattr(self, "_last_map_ref", None)
-            prev = prev() if prev is not None else None
-            if prev is not None and prev._d is None:
-                prev._get()  # somebody still holds the previous association's map and has not read it: fetch it before it is replaced
-        ts = self._torch_in(depth, rgb, cls, inst)
+            self._keep_unread_map()
         intr = np.array([fx, fy, cx, cy], np.float64)
         T = np.ascontiguousarray(T_cw, dtype=np.float64)
         f.set_T_cw(T)
         big = float(np.finfo(np.float32).max)
-        L.check(self._lib.hv_semantic_fuse_keyframe(
-            self._h, L.ptr(depth), L.ptr(rgb), L.ptr(cls), L.ptr(inst), H, W, L.ptr(f.intr), f.depth_max, f.depth_min, L.ptr(intr), L.ptr(T),
-            int(bool(filter_shadow_points) and not depth_is_filtered), int(use_inst), float(depth_threshold), int(bool(do_carving)),
-            float(min_vote_ratio), int(min_votes), float(min_depth), float(min(max_depth, big)), int(bool(use_depths))))
-        if use_inst and cls is not None:
-            self._assoc_serial = getattr(self, "_assoc_serial", 0) + 1  # (a LazyIdMap of an earlier association is stale now)
-        self._torch_out(ts, depth.device)
+        with self._ordered(depth, rgb, cls, inst):
+            L.check(self._lib.hv_semantic_fuse_keyframe(
+                self._h, L.ptr(depth), L.ptr(rgb), L.ptr(cls), L.ptr(inst), H, W, L.ptr(f.intr), f.depth_max, f.depth_min, L.ptr(intr), L.ptr(T),
+                int(bool(filter_shadow_points) and not depth_is_filtered), int(use_inst), float(depth_threshold), int(bool(do_carving)),
+                float(min_vote_ratio), int(min_votes), float(min_depth), float(min(max_depth, big)), int(bool(use_depths))))
+            if use_inst and cls is not None:
+                self._assoc_serial = getattr(self, "_assoc_serial", 0) + 1  # (a LazyIdMap of an earlier association is stale now)
 
     def get_voxels(self, min_count=1, min_confidence=0.0):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_get_voxels_semantic(self._h, int(min_count), float(min_confidence), None, None, None, None, None, 0,
-                                                 ctypes.byref(n)))
-        m = n.value
-        out = VoxelGridData(np.zeros((m, 3), np.float64), np.zeros((m, 3), np.float32))
-        out.class_ids, out.object_ids = np.zeros(m, np.int32), np.zeros(m, np.int32)
-        out.confidences = np.zeros(m, np.float32)
-        if m:
-            L.check(self._lib.hv_get_voxels_semantic(self._h, int(min_count), float(min_confidence), L.ptr(out.points),
-                                                     L.ptr(out.colors), L.ptr(out.class_ids), L.ptr(out.object_ids),
-                                                     L.ptr(out.confidences), m, ctypes.byref(n)))
-        return out
+        return self._query(lambda *a: self._lib.hv_get_voxels_semantic(self._h, int(min_count), float(min_confidence), *a))
 
     def _query(self, call):
-        n = ctypes.c_int64()
-        L.check(call(None, None, None, None, None, 0, ctypes.byref(n)))
-        m = n.value
-        out = VoxelGridData(np.zeros((m, 3), np.float64), np.zeros((m, 3), np.float32))
-        out.class_ids, out.object_ids = np.zeros(m, np.int32), np.zeros(m, np.int32)
-        out.confidences = np.zeros(m, np.float32)
-        if m:
-            L.check(call(L.ptr(out.points), L.ptr(out.colors), L.ptr(out.class_ids), L.ptr(out.object_ids), L.ptr(out.confidences), m,
-                         ctypes.byref(n)))
+        """call(points, colors, class ids, object ids, confidences, capacity, &count) -> VoxelGridData with the semantic fields."""
+        i32, f32 = np.int32, np.float32
+        points, colors, class_ids, object_ids, confidences = self._sized_fetch(call, ((3,), np.float64), ((3,), f32), ((), i32), ((), i32), ((), f32))
+        out = VoxelGridData(points, colors)
+        out.class_ids, out.object_ids, out.confidences = class_ids, object_ids, confidences
         return out
 
     @staticmethod
@@ -608,9 +528,6 @@ class _SemanticGridBase(_Volume):
         vg = self.get_voxels(1, -1.0)
         return vg.class_ids, vg.object_ids
 
-    def carve(self, camera_frustrum, depth_image, depth_threshold=1e-2):
-        self._carve(camera_frustrum, depth_image, depth_threshold)
-
     def assign_object_ids_to_instance_ids(self, camera_frustrum, class_ids_image, semantic_instances_image, depth_image=None,
                                           depth_threshold=0.1, do_carving=False, min_vote_ratio=0.5, min_votes=3):
         """-> dict instance_id -> object_id (voxel_semantic_data_association.h:70-373), as a LazyIdMap: vote -> (multi-GPU: exchange
@@ -632,16 +549,14 @@ class _SemanticGridBase(_Volume):
         """This GPU's pair list of stage 1 into `msg`, a torch CUDA int64 tensor of 1 + 2 * ASSOC_PAIRS_CAP words ([n, keys, votes]);
         queued on the volume's stream, ordered against torch's current stream - no host synchronisation."""
         cap = (msg.numel() - 1) // 2
-        ts = self._torch_in(msg)
-        L.check(self._lib.hv_assoc_pairs_export(self._h, L.ptr(msg), cap))
-        self._torch_out(ts, msg.device)
+        with self._ordered(msg):
+            L.check(self._lib.hv_assoc_pairs_export(self._h, L.ptr(msg), cap))
 
     def assoc_pairs_import(self, msgs, world):
         """The ranks' messages back to back (the all-gather's output) become the pair list stage 2 decides on; equal pairs add up."""
         cap = (msgs.numel() // int(world) - 1) // 2
-        ts = self._torch_in(msgs)
-        L.check(self._lib.hv_assoc_pairs_import(self._h, L.ptr(msgs), int(world), cap))
-        self._torch_out(ts, msgs.device)
+        with self._ordered(msgs):
+            L.check(self._lib.hv_assoc_pairs_import(self._h, L.ptr(msgs), int(world), cap))
 
     # -- the association in stages (hv_assoc_*): what a multi-GPU driver interleaves with its exchange ----------------------------
     def assoc_vote(self, camera_frustrum, class_ids_image, semantic_instances_image, depth_image=None, depth_threshold=0.1,
@@ -652,23 +567,20 @@ class _SemanticGridBase(_Volume):
         if class_ids_image is None or semantic_instances_image is None:
             return False
         loc = L.HV_HOST
-        ts = None
         if any(_is_device(a) for a in (class_ids_image, semantic_instances_image, depth_image)):
             # device-resident label / depth images (torch CUDA: int32, int32, float32): used in place
             import torch
 
             (cls, inst, depth), loc = _device_images(
-                class_ids_image if _is_device(class_ids_image) else _i32_image(np.asarray(class_ids_image), "Class ids"),
+                self, class_ids_image if _is_device(class_ids_image) else _i32_image(np.asarray(class_ids_image), "Class ids"),
                 semantic_instances_image if _is_device(semantic_instances_image) else _i32_image(np.asarray(semantic_instances_image), "Instance ids"),
-                depth_image if depth_image is None or _is_device(depth_image) else np.ascontiguousarray(depth_image, dtype=np.float32),
-                device=self._cfg.device)
+                depth_image if depth_image is None or _is_device(depth_image) else np.ascontiguousarray(depth_image, dtype=np.float32))
             if cls.dim() != 2 or inst.dim() != 2 or cls.dtype != torch.int32 or inst.dtype != torch.int32:
                 raise RuntimeError("Class ids / Instance ids must be single-channel int32")
             if tuple(inst.shape) != (f.height, f.width) or tuple(cls.shape) != (f.height, f.width):
                 return False
             if depth is not None and (depth.dtype != torch.float32 or tuple(depth.shape) != (f.height, f.width)):
                 depth = None
-            ts = self._torch_in(cls, inst, depth)
         else:
             cls, inst = np.asarray(class_ids_image), np.asarray(semantic_instances_image)
             if cls.size == 0 or inst.size == 0:
@@ -681,24 +593,24 @@ class _SemanticGridBase(_Volume):
                 depth = np.ascontiguousarray(depth_image, dtype=np.float32)
                 if depth.shape != (f.height, f.width):
                     depth = None  # use_depth_filter = false
+        with self._ordered(cls, inst, depth):
+            self._keep_unread_map()
+            L.check(self._lib.hv_assoc_vote(
+                self._h, L.ptr(f.intr), f.width, f.height, L.ptr(f.T_cw), f.depth_max, f.depth_min, L.ptr(cls), L.ptr(inst), L.ptr(depth),
+                float(depth_threshold), int(bool(do_carving)), loc))
+        return True
+
+    def _keep_unread_map(self):
+        """Before an association replaces the device-resident map of the previous one: if somebody still holds that LazyIdMap and
+        has not read it, fetch it now."""
         prev = getattr(self, "_last_map_ref", None)
         prev = prev() if prev is not None else None
         if prev is not None and prev._d is None:
-            prev._get()  # somebody still holds the previous association's map and has not read it: fetch it before it is replaced
-        L.check(self._lib.hv_assoc_vote(
-            self._h, L.ptr(f.intr), f.width, f.height, L.ptr(f.T_cw), f.depth_max, f.depth_min, L.ptr(cls), L.ptr(inst), L.ptr(depth),
-            float(depth_threshold), int(bool(do_carving)), loc))
-        if loc == L.HV_DEVICE:
-            self._torch_out(ts, cls.device)
-        return True
+            prev._get()
 
     def assoc_pairs(self):
         """-> (keys u64 [n] = instance << 32 | object, votes i32 [n]) of stage 1 (synchronises)."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_assoc_pairs_fetch(self._h, None, None, 0, ctypes.byref(n)))
-        keys, counts = np.zeros(n.value, np.uint64), np.zeros(n.value, np.int32)
-        if n.value:
-            L.check(self._lib.hv_assoc_pairs_fetch(self._h, L.ptr(keys), L.ptr(counts), n.value, ctypes.byref(n)))
+        keys, counts = self._sized_fetch(functools.partial(self._lib.hv_assoc_pairs_fetch, self._h), ((), np.uint64), ((), np.int32))
         return keys, counts
 
     def assoc_set_pairs(self, keys, counts):
@@ -743,41 +655,16 @@ class _SemanticGridBase(_Volume):
     def remove_low_confidence_segments(self, min_confidence):
         L.check(self._lib.hv_remove_low_confidence_segments(self._h, int(min_confidence)))
 
-    def remove_low_count_voxels(self, min_count):
-        L.check(self._lib.hv_remove_low_count_voxels(self._h, int(min_count)))
-
     def remove_low_confidence_voxels(self, min_confidence):
         L.check(self._lib.hv_remove_low_confidence_voxels(self._h, float(min_confidence)))
 
     def label_overflows(self):
         """Label observations the probabilistic payload dropped (a map past 254 pairs / the overflow-node pool exhausted); 0 otherwise."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_label_overflows(self._h, ctypes.byref(n)))
-        return n.value
+        return self._int64(self._lib.hv_label_overflows)
 
     def prob_nodes_used(self):
         """Overflow nodes of the probabilistic label maps handed out so far (hv_prob_nodes_used)."""
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_prob_nodes_used(self._h, ctypes.byref(n)))
-        return n.value
-
-    def clear(self):
-        L.check(self._lib.hv_reset(self._h))
-
-    reset = clear
-
-    def size(self):
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_size(self._h, ctypes.byref(n)))
-        return n.value
-
-    get_total_voxel_count = size
-
-    def empty(self):
-        return self.num_blocks() == 0
-
-    def get_block_size(self):
-        return self.block_size
+        return self._int64(self._lib.hv_prob_nodes_used)
 
     # -- parity/debug ----------------------------------------------------------------------------
     def dump(self):
@@ -796,9 +683,8 @@ class _SemanticGridBase(_Volume):
         nlab = np.zeros((nb, nv), np.int32)
         labels = np.zeros((nb, nv, max_labels, 2), np.int32)
         logp = np.zeros((nb, nv, max_labels), np.float32)
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_dump_blocks_semantic2(self._h, L.ptr(keys), L.ptr(ints), L.ptr(conf), L.ptr(pos), L.ptr(col), L.ptr(nlab),
-                                                   L.ptr(labels), L.ptr(logp), int(max_labels), ctypes.byref(n)))
+        self._int64(self._lib.hv_dump_blocks_semantic2, L.ptr(keys), L.ptr(ints), L.ptr(conf), L.ptr(pos), L.ptr(col), L.ptr(nlab),
+                    L.ptr(labels), L.ptr(logp), int(max_labels))
         return keys, ints, pos, col, conf, nlab, labels, logp
 
     def dump_marginals(self):
@@ -806,8 +692,7 @@ class _SemanticGridBase(_Volume):
         ``get_class_confidence()`` of the two ``*2`` payloads (voxel_data_semantic2.h:60-76, 528-560); -1 for the other two."""
         nb, nv = self.num_blocks(), self.block_size ** 3
         oc, cc = np.zeros((nb, nv), np.float32), np.zeros((nb, nv), np.float32)
-        n = ctypes.c_int64()
-        L.check(self._lib.hv_dump_marginals_semantic(self._h, L.ptr(oc), L.ptr(cc), ctypes.byref(n)))
+        self._int64(self._lib.hv_dump_marginals_semantic, L.ptr(oc), L.ptr(cc))
         return oc, cc
 
 

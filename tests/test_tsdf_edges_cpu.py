@@ -17,6 +17,7 @@ import oracle
 from pyslam_amd import _lib as L
 from pyslam_amd.volumetric import PinholeCameraIntrinsic, RGBDImage, ScalableTSDFVolume, _tsdf_operands
 from tests import tsdf_closed_form as cf
+from tests.recording_lib import RecordingLib
 
 H, W = 7, 9
 K = PinholeCameraIntrinsic(W, H, 8.0, 7.0, 3.3, 4.1)
@@ -116,32 +117,9 @@ def test_operands_that_do_not_fit_are_refused():
 
 
 # ---- the entry points against a recording stand-in for the library -------------------------------------------------------
-class _RecordingLib:
-    """Stands in for libpyslam_hipvol.so: records the TSDF integrate calls, fails on anything else."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        if not name.startswith("hv_tsdf_integrate"):
-            raise AssertionError(f"unexpected library call {name}")
-
-        def record(*args):
-            if name == "hv_tsdf_integrate_frames":  # the frames are borrowed for the call only: read them now
-                F, h, w = args[4:7]
-                dt = ctypes.c_uint16 if args[2] == L.HV_DEPTH_U16 else ctypes.c_float
-                self.frames = [(np.ctypeslib.as_array(ctypes.cast(args[1][f], ctypes.POINTER(dt)), shape=(h, w)).copy(),
-                                np.ctypeslib.as_array(ctypes.cast(args[3][f], ctypes.POINTER(ctypes.c_uint8)), shape=(h, w, 3)).copy())
-                               for f in range(F)]
-            self.calls.append((name, args))
-            return 0
-
-        return record
-
-
 def _volume():
     vol = ScalableTSDFVolume.__new__(ScalableTSDFVolume)  # no hv_create: nothing here needs a device
-    vol._lib = _RecordingLib()
+    vol._lib = RecordingLib()
     vol._h = None
     return vol
 
