@@ -811,14 +811,21 @@ __global__ __launch_bounds__(256) void k_seg_rows(const VOX *__restrict__ pool, 
 // 3 remove_low_count_voxels(a), 4 remove_low_confidence_voxels(fa)
 template <typename VOX>
 __global__ __launch_bounds__(256) void k_sem_segment_op(HvTable table, VOX *__restrict__ pool, int64_t n_voxels, int op, int32_t a, int32_t b,
-                                                         float fa, const unsigned long long *__restrict__ occ) {
+                                                         float fa, const unsigned long long *__restrict__ occ,
+                                                         unsigned long long *__restrict__ mark) {
     const void *nodes = table.prob_nodes;
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= n_voxels) return;
     if (!sem_maybe_occupied(occ, gid)) return; // a voxel that never took a point: every op leaves its zero record as it is
     VOX *v = pool + gid;
     if (op == 0) {
-        if (sem_object_id(v, nodes) == b) sem_set_object_id(v, table, a);
+        if (sem_object_id(v, nodes) == b) {
+            sem_set_object_id(v, table, a);
+            // merging INTO the voxels without an object id (occ == nullptr) gives voxels that never took a point an id: their record
+            // is no longer the zero record, and the operations that follow (remove_segment, the confidence / count removals reset
+            // them in the reference) must find them - they are marked like a voxel that took its first point
+            if (mark != nullptr) atomicOr(&mark[gid >> 6], 1ull << (gid & 63));
+        }
     } else if (op == 1) {
         if (sem_object_id(v, nodes) == a) sem_reset(v);
     } else if (op == 2) {
@@ -1024,7 +1031,8 @@ template <typename VOX> int sem_launch_segment_op(hv_volume *v, int op, int32_t 
     if (nb == 0) return HV_OK;
     const int64_t total = nb * sem_params(v).nvox;
     hipLaunchKernelGGL(k_sem_segment_op<VOX>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (VOX *)v->pool,
-                       total, op, a, b, fa, (op == 0 && b < 0) ? nullptr : v->occ); // (merging INTO the voxels without an object id reaches empty ones too)
+                       total, op, a, b, fa, (op == 0 && b < 0) ? nullptr : v->occ, // (merging INTO the voxels without an object id reaches empty ones too)
+                       (op == 0 && b < 0) ? v->occ : nullptr);
     HV_HIP(hipGetLastError());
     return HV_OK;
 }
