@@ -834,6 +834,64 @@ int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t depth_dtype, in
                         const double *T_cw, const hv_check_params *params, float *sdf /* [H,W] or NULL */,
                         uint8_t *cls /* [H,W] or NULL */, hv_check_stats *stats /* or NULL */, int32_t loc);
 
+/* Point lookup on the block grids: what does the grid hold at given points - the grids' counterpart of hv_tsdf_sample_points, and the
+ * bridge from the TSDF map's surfaces (mesh vertices, ray-cast vertex images, point clouds) to the semantic grids' labels.  This
+ * project's own contract.  Modes: HV_MODE_VOXEL_GRID and the four semantic grids.  The volume is only read.  points [n,3] of point_dtype
+ * (HV_F32 | HV_F64) at loc.  For every point p:
+ *   own voxel  the voxel hv_integrate_points / hv_integrate_points_f64 / hv_integrate_points_semantic would put p in, by the very
+ *              functions those calls key their points with: a float32 point is keyed in float32 (floorf(p_a * inv) with inv =
+ *              1.0f / (float)voxel_size), a float64 point in float64 (floor(p_a * (double)inv)), so a point that was integrated finds
+ *              the voxel it went to.  p has NO voxel - status HV_LOOKUP_INVALID - when a coordinate is not finite, when some
+ *              |p_a * inv| >= 1e9 (evaluated as the mode's integrate does), or when the voxel's block key leaves [-2^20, 2^20).
+ *   qualifies  a voxel qualifies when its block is held by this volume, its count >= max(min_count, 1) and - semantic modes only -
+ *              confidence >= min_confidence, the predicate of hv_get_voxels_semantic through the same accessors (a NaN confidence or a
+ *              NaN min_confidence never passes; min_confidence <= 0 passes every other voxel).  On the plain grid min_confidence is
+ *              ignored.  A voxel is found by a lookup exactly when hv_get_voxels / hv_get_voxels_semantic (min_count, min_confidence)
+ *              lists it.
+ *   choice     the own voxel, if it qualifies: HV_LOOKUP_OWN.  Otherwise, with r = radius in {0, 1, 2}, the candidates are the voxels
+ *              at the integer offsets (dx, dy, dz) in [-r, r]^3 from the own voxel's coordinate; a candidate's block is floor_div(
+ *              coordinate, block_size) per axis, and a candidate whose block key leaves the key range is skipped.  Among the
+ *              qualifying candidates the answer is the one whose MEAN POSITION m - the row hv_get_voxels* lists: the float64
+ *              position_sum / (double)count of a semantic voxel, the float32 position_sum / (float)count of a plain one, widened - is
+ *              nearest p, with p widened to float64 exactly and d2 = ((m0 - p0)^2 + (m1 - p1)^2) + (m2 - p2)^2 in float64, one IEEE
+ *              operation per step in that order, no contraction; equal d2: the smallest offset index (dz + r)(2r + 1)^2 +
+ *              (dy + r)(2r + 1) + (dx + r).  HV_LOOKUP_NEAR.  No qualifying candidate (always so for r = 0): HV_LOOKUP_MISSING.
+ *   outputs    for a found voxel: count; position = m; color = color_sum / (float)count, class_id, object_id, confidence as
+ *              hv_get_voxels / hv_get_voxels_semantic write them.  MISSING and INVALID: count 0, position and colour 0, ids -1,
+ *              confidence 0.
+ *   stats      points = n and the number of points per status, exact (integer atomics, at most one per wave and status).
+ * Outputs: status [n] u8, count [n] i32, position [n,3] f64, color [n,3] f32, class_id [n] i32, object_id [n] i32, confidence [n] f32,
+ * stats; any may be NULL, and a NULL output is not computed.  On HV_MODE_VOXEL_GRID class_id, object_id and confidence must be NULL.
+ * points and the arrays live at loc; HV_HOST is staged by the library and copied back before returning.  With stats != NULL the call
+ * waits for the GPU; with stats == NULL and loc = HV_DEVICE nothing is read back: the call is queued on the volume's stream, behind
+ * every integrate call made before it, and returns without waiting.  Reads only: no claim, no growth, no counter - dumps before and
+ * after are bitwise equal; it writes only the input staging and its output buffers, so caches, the touched lists, the point bins and
+ * the association state stay as they are.  One point's outputs are written by lanes that computed them from that point alone, no atomics on outputs: two calls on
+ * equal inputs give bitwise equal outputs, whatever the pool order.  On an owner-sharded grid (hv_set_owner) the lookup sees the blocks
+ * this rank holds and everything else is MISSING; there is no collective inside the call.
+ * Device work (hv_lookup.hip): one lane per point for the own voxel - one table probe, one record read; radius 0 is only that.  For
+ * radius >= 1 the wave then takes the points still open one by one: the blocks of the neighbourhood are probed once, a lane per
+ * candidate tests the occupancy bit and the count before anything else of the record, a wave min over (d2, offset index) picks the
+ * winner and only its record is read for the outputs.
+ * HV_ERR_MODE for a TSDF volume; HV_ERR_INVALID for a radius outside 0..2, n < 0 (or n > 2^36), NULL points with n > 0, a bad dtype or
+ * loc, a label output on the plain grid.  n == 0 is a successful no-op (stats all 0). */
+#define HV_LOOKUP_MISSING 0
+#define HV_LOOKUP_OWN 1
+#define HV_LOOKUP_NEAR 2
+#define HV_LOOKUP_INVALID 3
+typedef struct hv_lookup_params {
+    int32_t min_count;
+    float min_confidence;
+    int32_t radius;
+} hv_lookup_params;
+typedef struct hv_lookup_stats {
+    int64_t points, own, near, missing, invalid;
+} hv_lookup_stats;
+int hv_lookup_points(hv_volume *v, const void *points /* [n,3] */, int32_t point_dtype /* HV_F32 | HV_F64 */, int64_t n,
+                     const hv_lookup_params *p, uint8_t *status /* [n] */, int32_t *count /* [n] */, double *position /* [n,3] */,
+                     float *color /* [n,3] */, int32_t *class_id /* [n] */, int32_t *object_id /* [n] */, float *confidence /* [n] */,
+                     hv_lookup_stats *stats /* may be NULL */, int32_t loc);
+
 /* Distance field: how far is every cell of a box from the nearest surface of the map - beyond the truncation band, where the map
  * itself holds no value and, in open space, no unit.  A dense signed Euclidean distance over a box of the map's OWN voxel lattice, out
  * to a radius of R voxels, for planners, collision checks and camera-to-surface guards.  This project's own contract.  The volume is

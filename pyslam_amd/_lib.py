@@ -180,6 +180,17 @@ class HvCheckStats(_c.Structure):
     _fields_ = [("count", _i64 * 5)]
 
 
+HV_LOOKUP_MISSING, HV_LOOKUP_OWN, HV_LOOKUP_NEAR, HV_LOOKUP_INVALID = 0, 1, 2, 3
+
+
+class HvLookupParams(_c.Structure):
+    _fields_ = [("min_count", _i32), ("min_confidence", _f32), ("radius", _i32)]
+
+
+class HvLookupStats(_c.Structure):
+    _fields_ = [("points", _i64), ("own", _i64), ("near", _i64), ("missing", _i64), ("invalid", _i64)]
+
+
 HV_DIST_UNKNOWN, HV_DIST_FREE, HV_DIST_INSIDE, HV_DIST_SITE = 0, 1, 2, 4
 HV_DIST_MAX_SHAPE, HV_DIST_MAX_RADIUS = 4096, 1024
 
@@ -296,6 +307,7 @@ SIGNATURES = {
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
+    "hv_lookup_points": (_i32, [_vp, _vp, _i32, _i64, _c.POINTER(HvLookupParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(HvLookupStats), _i32]),
     "hv_tsdf_distance_field": (_i32, [_vp, _c.POINTER(HvDistanceParams), _vp, _vp, _vp, _c.POINTER(HvDistanceStats), _i32]),
     "hv_tsdf_surface_components": (_i32, [_vp, _f64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _pi64, _pi64, _c.POINTER(HvComponentsStats), _i32]),
     "hv_tsdf_remove_components": (_i32, [_vp, _f64, _i64, _i32, _c.POINTER(HvRemoveComponentsStats)]),

@@ -524,7 +524,7 @@ struct hv_volume {
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
     void *raycast_buf = nullptr; // HV_HOST outputs of hv_tsdf_ray_cast (apart from out_*: a cast leaves the extraction caches valid)
     size_t raycast_buf_bytes = 0;
-    void *sample_buf = nullptr;  // hv_tsdf_sample_points / hv_tsdf_check_frame: class counters and HV_HOST outputs (hv_sample.hip)
+    void *sample_buf = nullptr;  // hv_tsdf_sample_points / hv_tsdf_check_frame / hv_lookup_points: counters and HV_HOST outputs (hv_stage_out)
     size_t sample_buf_bytes = 0;
     void *dist_buf = nullptr;    // hv_tsdf_distance_field: counters, the intermediate grid, classes and HV_HOST outputs (hv_distance.hip)
     size_t dist_buf_bytes = 0;
@@ -600,6 +600,9 @@ struct HvScratch {
 int hv_rectify_frames_device(hv_volume *v, hipStream_t s, const void *d_depth, int32_t depth_dtype, const uint8_t *d_rgb, int n_frames,
                              int height, int width, void *d_depth_out, uint8_t *d_rgb_out);
 int hv_stage_in(hv_volume *v, const void *src, size_t bytes, int32_t loc, int which, const void **dev);
+// hv_sample.hip: device addresses of a query's outputs (at most 8) - the caller's own arrays (HV_DEVICE), or 256-byte aligned pieces of
+// v->sample_buf behind `head` bytes (HV_HOST; an output of size 0 gets nullptr), which the caller copies back
+int hv_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes, void *const *user, void **dev, int count);
 // hipMemcpyAsync(H2D) of a caller's array on the volume's stream; waits for the copy when the source is page-locked (the DMA would
 // otherwise read it after the call has returned: the ABI borrows host arrays for the duration of the call only)
 int hv_h2d(hv_volume *v, void *dst, const void *src, size_t bytes);

@@ -179,8 +179,11 @@ HvSampleParams sample_params(const hv_volume *v, double weight_threshold) {
     return P;
 }
 
+} // namespace
+
 // device addresses of a call's outputs: the caller's own (HV_DEVICE), or pieces of the volume's staging buffer behind `head` bytes
-int sample_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes, void *const *user, void **dev, int count) {
+// (declared in hv_common.h: hv_lookup.hip stages its outputs the same way)
+int hv_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes, void *const *user, void **dev, int count) {
     size_t off[8], total = head;
     for (int i = 0; i < count; ++i) {
         off[i] = total;
@@ -193,8 +196,6 @@ int sample_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes
     for (int i = 0; i < count; ++i) dev[i] = loc == HV_HOST ? (sizes[i] ? (char *)v->sample_buf + off[i] : nullptr) : user[i];
     return HV_OK;
 }
-
-} // namespace
 
 extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t point_dtype, int64_t n, double weight_threshold, float *sdf,
                                      float *gradient, float *color, float *weight, uint8_t *status, int32_t loc) {
@@ -214,7 +215,7 @@ extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t p
                              status ? (size_t)n : 0};
     void *user[5] = {sdf, gradient, color, weight, status};
     void *dev[5];
-    rc = sample_stage_out(v, loc, 0, sizes, user, dev, 5);
+    rc = hv_stage_out(v, loc, 0, sizes, user, dev, 5);
     if (rc != HV_OK) return rc;
     const void *d_points = nullptr;
     rc = hv_stage_in(v, points, (size_t)n * 3 * (point_dtype == HV_F64 ? 8 : 4), loc, 0, &d_points);
@@ -294,7 +295,7 @@ extern "C" int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t dept
     const size_t sizes[2] = {sdf ? 4 * npx : 0, cls ? npx : 0};
     void *user[2] = {sdf, cls};
     void *dev[2];
-    rc = sample_stage_out(v, loc, head, sizes, user, dev, 2);
+    rc = hv_stage_out(v, loc, head, sizes, user, dev, 2);
     if (rc != HV_OK) return rc;
     const void *d_depth = nullptr;
     rc = hv_stage_in(v, depth, npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);

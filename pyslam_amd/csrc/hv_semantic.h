@@ -72,6 +72,41 @@ struct HvSemParams {
     int32_t owner_rank, owner_world; // multi-GPU block ownership (hv_set_owner): points of blocks another GPU owns are skipped
 };
 
+// ---- a point's voxel: what the integrate (hv_semantic.hip) and the point lookup (hv_lookup.hip) share ----
+__host__ __device__ static inline int32_t sem_floor_div(int32_t a, int32_t b) {
+    const int64_t aa = a, bb = b;
+    return (int32_t)((aa >= 0) ? (aa / bb) : ((aa - bb + 1) / bb));
+}
+#ifdef __HIPCC__
+// get_voxel_key_inv<Tpos,Tpos>(x, inv_voxel_size_) as update_voxel calls it (voxel_block_grid.hpp:473):
+// float points -> float product; double points -> double product with the float member promoted.
+__device__ __forceinline__ int32_t sem_voxel_coord(float x, float inv) { return (int32_t)floorf(x * inv); }
+__device__ __forceinline__ int32_t sem_voxel_coord(double x, float inv) { return (int32_t)floor(x * (double)inv); }
+
+// block key and local voxel index of a point; false: the point has no voxel (not finite, |p * inv| >= 1e9, block key out of range) or -
+// `foreign` - its block is another GPU's
+__device__ __forceinline__ bool sem_point_block(const HvSemParams &G, double px, double py, double pz, bool is_f64, unsigned long long &bkey,
+                                                uint32_t &lidx, bool &foreign) {
+    const double p[3] = {px, py, pz};
+    bool ok = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) ok = ok && isfinite(p[a]) && fabs(p[a] * (double)G.inv_voxel_size) < 1.0e9;
+    if (!ok) return false;
+    int32_t b[3], l[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int32_t v = is_f64 ? sem_voxel_coord(p[a], G.inv_voxel_size) : sem_voxel_coord((float)p[a], G.inv_voxel_size);
+        b[a] = sem_floor_div(v, G.bs);
+        l[a] = (int32_t)((int64_t)v - (int64_t)b[a] * G.bs);
+    }
+    if (!hv_key_in_range(b[0], b[1], b[2])) return false;
+    bkey = hv_pack_key(b[0], b[1], b[2]);
+    foreign = G.owner_world > 1 && hv_owner_of(bkey, G.owner_world) != G.owner_rank;
+    lidx = (uint32_t)(l[0] + l[1] * G.bs + l[2] * G.bs * G.bs);
+    return !foreign;
+}
+#endif
+
 // The reference calls std::exp / std::log on floats (glibc expf/logf, < 1 ulp and correctly rounded
 // in all but ~1e-3 of the cases); evaluating in double and rounding once reproduces that on the
 // device up to those rare last-bit cases (tests: labels exact, confidences <= 1e-6).

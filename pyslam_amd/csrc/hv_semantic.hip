@@ -28,15 +28,7 @@
 
 static constexpr uint32_t HV_SORT_SENTINEL = 0xFFFFFFFFu;
 
-__host__ __device__ static inline int32_t sem_floor_div(int32_t a, int32_t b) {
-    const int64_t aa = a, bb = b;
-    return (int32_t)((aa >= 0) ? (aa / bb) : ((aa - bb + 1) / bb));
-}
-
-// get_voxel_key_inv<Tpos,Tpos>(x, inv_voxel_size_) as update_voxel calls it (voxel_block_grid.hpp:473):
-// float points -> float product; double points -> double product with the float member promoted.
-__device__ __forceinline__ int32_t sem_voxel_coord(float x, float inv) { return (int32_t)floorf(x * inv); }
-__device__ __forceinline__ int32_t sem_voxel_coord(double x, float inv) { return (int32_t)floor(x * (double)inv); }
+// (sem_floor_div, sem_voxel_coord and sem_point_block - a point's voxel - live in hv_semantic.h: hv_lookup.hip keys its points with them)
 
 template <typename PT>
 __global__ __launch_bounds__(256) void k_sem_keys(HvTable table, const PT *__restrict__ pts, int64_t n, HvSemParams G,
@@ -259,27 +251,6 @@ __global__ __launch_bounds__(256) void k_sem_reduce(HvTable table, VOX *__restri
 // ---- per-keyframe bin path (hv_bins.h): bin -> fold (+ the big bins' ranges), 3 launches instead of the radix sort's ~20 (rounds 4-5:
 // count -> offsets -> scatter -> fold + tasks, and a separate unprojection launch in front of them) ----
 // entries are (local voxel index << IB | point index) with IB = 32 - local_bits (23 for 8^3 blocks: 8 M points per call)
-__device__ __forceinline__ bool sem_point_block(const HvSemParams &G, double px, double py, double pz, bool is_f64, unsigned long long &bkey,
-                                                uint32_t &lidx, bool &foreign) {
-    const double p[3] = {px, py, pz};
-    bool ok = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) ok = ok && isfinite(p[a]) && fabs(p[a] * (double)G.inv_voxel_size) < 1.0e9;
-    if (!ok) return false;
-    int32_t b[3], l[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const int32_t v = is_f64 ? sem_voxel_coord(p[a], G.inv_voxel_size) : sem_voxel_coord((float)p[a], G.inv_voxel_size);
-        b[a] = sem_floor_div(v, G.bs);
-        l[a] = (int32_t)((int64_t)v - (int64_t)b[a] * G.bs);
-    }
-    if (!hv_key_in_range(b[0], b[1], b[2])) return false;
-    bkey = hv_pack_key(b[0], b[1], b[2]);
-    foreign = G.owner_world > 1 && hv_owner_of(bkey, G.owner_world) != G.owner_rank;
-    lidx = (uint32_t)(l[0] + l[1] * G.bs + l[2] * G.bs * G.bs);
-    return !foreign;
-}
-
 template <typename PT>
 __global__ __launch_bounds__(HV_BIN_THREADS) void k_semb_bin(HvTable table, HvBins B, const PT *__restrict__ pts, int64_t n, HvSemParams G,
                                                    const uint32_t *__restrict__ valid_mask_keys) {

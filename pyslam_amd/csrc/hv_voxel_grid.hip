@@ -26,35 +26,7 @@
 
 static constexpr uint32_t HV_SORT_SENTINEL = 0xFFFFFFFFu;
 
-struct HvPointKey {
-    int32_t v[3], b[3], l[3];
-};
-
-// get_voxel_key_inv<Tp,float> + get_block_key + get_local_voxel_key.  Tp = float: floorf(x * inv) in float; Tp = double (the
-// binding's py::array_t<double> overload, volumetric_grid_module.h:738-741): the float inverse voxel size is promoted and the
-// product and floor are double - a float64 point near a cell border keeps its own cell instead of its float32 neighbour's.
-template <typename Tp>
-__device__ __forceinline__ HvPointKey hv_point_key(Tp x, Tp y, Tp z, const HvGridParams &G) {
-    HvPointKey k;
-    const Tp inv = (Tp)G.inv_voxel_size;
-    const Tp f[3] = {floor(x * inv), floor(y * inv), floor(z * inv)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        k.v[a] = (int32_t)f[a];
-        // floor_div (voxel_hashing.h:139-142) without the 64-bit division (3 per point: most of the key kernel's time): an
-        // arithmetic shift for power-of-two blocks, else floor(v * (1 / bs) + 2^-10) in double - exact for |v| < 2^31 and
-        // bs <= 16: a non-integer v / bs is at least 1/16 away from an integer, the product's error is below 2^-20
-        k.b[a] = G.bs_shift >= 0 ? (k.v[a] >> G.bs_shift) : (int32_t)floor(fma((double)k.v[a], 1.0 / (double)G.bs, 0x1p-10));
-        k.l[a] = k.v[a] - k.b[a] * G.bs; // in [0, bs): no overflow (|b * bs| <= |v| + bs)
-    }
-    return k;
-}
-// the point is finite and its voxel index fits the 32-bit key
-template <typename Tp>
-__device__ __forceinline__ bool hv_point_keyable(Tp x, Tp y, Tp z, const HvGridParams &G) {
-    const Tp inv = (Tp)G.inv_voxel_size, lim = (Tp)1.0e9;
-    return isfinite(x) && isfinite(y) && isfinite(z) && fabs(x * inv) < lim && fabs(y * inv) < lim && fabs(z * inv) < lim;
-}
+// (HvPointKey, hv_point_key and hv_point_keyable - a point's voxel - live in hv_query.h: hv_lookup.hip keys its points with them)
 
 // pts64 != nullptr: the caller's points are float64 - keys from the doubles, and the float32 narrowing the voxel sums take
 // (position_sum += static_cast<float>(x), voxel_data.h:54-56) is written to pts for the reduce.
@@ -816,20 +788,7 @@ __global__ __launch_bounds__(256) void k_shadow_mask(const float *__restrict__ d
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-static HvGridParams grid_params(const hv_volume *v) {
-    HvGridParams G;
-    const float vs = (float)v->cfg.voxel_size; // pybind narrows the Python double to float first
-    G.inv_voxel_size = 1.0f / vs;
-    G.bs = v->cfg.block_size;
-    G.nvox = G.bs * G.bs * G.bs;
-    G.local_bits = v->local_bits;
-    G.bs_shift = -1;
-    for (int sh = 0; sh <= 4; ++sh)
-        if ((1 << sh) == G.bs) G.bs_shift = sh;
-    G.owner_rank = v->owner_rank;
-    G.owner_world = v->owner_world;
-    return G;
-}
+// (grid_params: hv_query.h)
 
 static int sort_bits(const hv_volume *v) {
     int slot_bits = 0;

@@ -8,8 +8,24 @@ def _colors_u8(colors):
     return np.clip(np.rint(np.asarray(colors, dtype=np.float64) * 255.0), 0, 255).astype(np.uint8)
 
 
-def write_ply_points(path, points, colors=None, normals=None):
-    """Property order as Open3D's WritePointCloudToPLY: x y z, then nx ny nz when the cloud has normals, then the colours."""
+def _label_fields(header, fields, n, class_ids, object_ids):
+    """Optional per-vertex labels (GeometryLabels of a semantic grid's label_mesh): two `int` properties behind the others."""
+    labels = []
+    for name, ids in (("class_id", class_ids), ("object_id", object_ids)):
+        if ids is None:
+            continue
+        ids = np.asarray(ids, dtype=np.int32).reshape(-1)
+        if len(ids) != n:
+            raise ValueError(f"{name}s: {len(ids)} labels for {n} vertices")
+        header.append(f"property int {name}")
+        fields.append((name, "<i4"))
+        labels.append((name, ids))
+    return labels
+
+
+def write_ply_points(path, points, colors=None, normals=None, class_ids=None, object_ids=None):
+    """Property order as Open3D's WritePointCloudToPLY: x y z, then nx ny nz when the cloud has normals, then the colours; then
+    class_id / object_id (int) when given."""
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     has_c = colors is not None and len(colors) == len(points)
     has_n = normals is not None and len(normals) == len(points)
@@ -22,8 +38,11 @@ def write_ply_points(path, points, colors=None, normals=None):
     if has_c:
         header += ["property uchar red", "property uchar green", "property uchar blue"]
         fields += [("r", "u1"), ("g", "u1"), ("b", "u1")]
+    labels = _label_fields(header, fields, len(points), class_ids, object_ids)
     header.append("end_header")
     rec = np.zeros(len(points), dtype=fields)
+    for name, ids in labels:
+        rec[name] = ids
     rec["x"], rec["y"], rec["z"] = points[:, 0], points[:, 1], points[:, 2]
     if has_n:
         nn = np.asarray(normals, dtype=np.float64).reshape(-1, 3)
@@ -36,7 +55,8 @@ def write_ply_points(path, points, colors=None, normals=None):
         f.write(rec.tobytes())
 
 
-def write_ply_mesh(path, vertices, triangles, vertex_colors=None):
+def write_ply_mesh(path, vertices, triangles, vertex_colors=None, class_ids=None, object_ids=None):
+    """class_ids / object_ids: optional per-vertex labels, written as two `int` vertex properties behind the colours."""
     vertices = np.asarray(vertices, dtype=np.float64).reshape(-1, 3)
     triangles = np.asarray(triangles, dtype=np.int32).reshape(-1, 3)
     has_c = vertex_colors is not None and len(vertex_colors) == len(vertices)
@@ -46,8 +66,11 @@ def write_ply_mesh(path, vertices, triangles, vertex_colors=None):
     if has_c:
         header += ["property uchar red", "property uchar green", "property uchar blue"]
         fields += [("r", "u1"), ("g", "u1"), ("b", "u1")]
+    labels = _label_fields(header, fields, len(vertices), class_ids, object_ids)
     header += [f"element face {len(triangles)}", "property list uchar uint vertex_indices", "end_header"]
     vrec = np.zeros(len(vertices), dtype=fields)
+    for name, ids in labels:
+        vrec[name] = ids
     vrec["x"], vrec["y"], vrec["z"] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
     if has_c:
         c = _colors_u8(vertex_colors)
@@ -61,8 +84,12 @@ def write_ply_mesh(path, vertices, triangles, vertex_colors=None):
         f.write(frec.tobytes())
 
 
+def _label_layout(header_lines):
+    return [(name, "<i4") for name in ("class_id", "object_id") if f"property int {name}" in header_lines]
+
+
 def read_ply(path):
-    """Minimal reader for the two layouts written above (tests / round trips)."""
+    """Minimal reader for the two layouts written above (tests / round trips); label properties are skipped (read_ply_labels)."""
     with open(path, "rb") as f:
         lines = []
         while True:
@@ -76,7 +103,7 @@ def read_ply(path):
         has_c = any("uchar red" in l for l in lines)
         has_n = any("double nx" in l for l in lines)
         fields = ([("x", "<f8"), ("y", "<f8"), ("z", "<f8")] + ([("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")] if has_n else [])
-                  + ([("r", "u1"), ("g", "u1"), ("b", "u1")] if has_c else []))
+                  + ([("r", "u1"), ("g", "u1"), ("b", "u1")] if has_c else []) + _label_layout(lines))
         v = np.frombuffer(f.read(nv * np.dtype(fields).itemsize), dtype=fields)
         faces = None
         if nf:
@@ -101,6 +128,26 @@ def read_ply_normals(path):
             return None
         nv = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
         has_c = any("uchar red" in l for l in lines)
-        fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")] + ([("r", "u1"), ("g", "u1"), ("b", "u1")] if has_c else [])
+        fields = ([("x", "<f8"), ("y", "<f8"), ("z", "<f8"), ("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+                  + ([("r", "u1"), ("g", "u1"), ("b", "u1")] if has_c else []) + _label_layout(lines))
         v = np.frombuffer(f.read(nv * np.dtype(fields).itemsize), dtype=fields)
     return np.stack([v["nx"], v["ny"], v["nz"]], axis=1)
+
+
+def read_ply_labels(path):
+    """-> (class_ids, object_ids) int32 [N] of a PLY written above with labels; None for a property the file does not have."""
+    with open(path, "rb") as f:
+        lines = []
+        while True:
+            line = f.readline().decode("ascii").strip()
+            lines.append(line)
+            if line == "end_header":
+                break
+        nv = int([l for l in lines if l.startswith("element vertex")][0].split()[-1])
+        has_c = any("uchar red" in l for l in lines)
+        has_n = any("double nx" in l for l in lines)
+        fields = ([("x", "<f8"), ("y", "<f8"), ("z", "<f8")] + ([("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")] if has_n else [])
+                  + ([("r", "u1"), ("g", "u1"), ("b", "u1")] if has_c else []) + _label_layout(lines))
+        v = np.frombuffer(f.read(nv * np.dtype(fields).itemsize), dtype=fields)
+    names = v.dtype.names
+    return tuple(np.array(v[name], dtype=np.int32) if name in names else None for name in ("class_id", "object_id"))

@@ -326,6 +326,36 @@ class FrameCheck:
         return f"FrameCheck({', '.join(f'{name}={getattr(self.stats, name)}' for name in self.stats.__slots__)})"
 
 
+# hv_lookup_points' status values (include/hipvol.h)
+LOOKUP_MISSING, LOOKUP_OWN, LOOKUP_NEAR, LOOKUP_INVALID = L.HV_LOOKUP_MISSING, L.HV_LOOKUP_OWN, L.HV_LOOKUP_NEAR, L.HV_LOOKUP_INVALID
+
+
+class LookupStats(_Stats):
+    """Points per status of one lookup_points call (hv_lookup_stats): points = own + near + missing + invalid."""
+
+    __slots__ = ("points", "own", "near", "missing", "invalid")
+
+
+class VoxelLookup:
+    """What lookup_points of a block grid returns, one row per point: status [n] uint8 (LOOKUP_MISSING / LOOKUP_OWN / LOOKUP_NEAR /
+    LOOKUP_INVALID), count [n] int32, position [n,3] float64 (the found voxel's mean position, the row get_voxels lists), color [n,3]
+    float32, class_id / object_id [n] int32 and confidence [n] float32 (None on the plain VoxelBlockGrid / VoxelGrid), stats
+    (LookupStats, or None when not asked for).  MISSING and INVALID rows hold count 0, position and colour 0, ids -1, confidence 0."""
+
+    def __init__(self, status, count, position, color, class_id, object_id, confidence, stats):
+        self.status = status
+        self.count = count
+        self.position = position
+        self.color = color
+        self.class_id = class_id
+        self.object_id = object_id
+        self.confidence = confidence
+        self.stats = stats
+
+    def __repr__(self):
+        return f"VoxelLookup(n={len(self.status)}, labels={self.class_id is not None}, stats={self.stats})"
+
+
 # hv_tsdf_distance_field's cell classes (include/hipvol.h): DIST_SITE is OR-ed onto DIST_FREE or DIST_INSIDE
 DIST_UNKNOWN, DIST_FREE, DIST_INSIDE, DIST_SITE = L.HV_DIST_UNKNOWN, L.HV_DIST_FREE, L.HV_DIST_INSIDE, L.HV_DIST_SITE
 
@@ -795,6 +825,49 @@ class _BlockGrid(_Volume):
 
     def remove_low_count_voxels(self, min_count):
         L.check(self._lib.hv_remove_low_count_voxels(self._h, int(min_count)))
+
+    _HAS_LABELS = False  # the semantic grids: lookup_points fills class_id, object_id and confidence
+
+    def lookup_points(self, points, min_count=1, min_confidence=0.0, radius=0, stats=False, device=None):
+        """What the grid holds at `points` [n,3] (float32 or float64; numpy or torch, either device): -> VoxelLookup.  A point's own
+        voxel is the one integrate() would put it in (float32 points keyed in float32, float64 in float64); it is the answer
+        (LOOKUP_OWN) when it qualifies - its block exists, count >= max(min_count, 1) and, on the semantic grids, confidence >=
+        min_confidence: exactly the voxels get_voxels(min_count, min_confidence) lists.  Otherwise, with radius 1 or 2, the qualifying
+        voxel of the (2 radius + 1)^3 around it whose mean position is nearest the point (LOOKUP_NEAR), else LOOKUP_MISSING; a point
+        that has no voxel (not finite, out of the key range) is LOOKUP_INVALID (include/hipvol.h, hv_lookup_points).  Reads the grid
+        only.  stats=True also counts the statuses (LookupStats) and waits for the GPU.  device as ScalableTSDFVolume.sample_points:
+        None gives results where the input lives - a torch CUDA tensor gives torch CUDA tensors, queued behind torch's current stream
+        and ordered before its later work; True / False: torch CUDA tensors on the grid's GPU / numpy arrays."""
+        if _is_torch(points):
+            import torch
+
+            if points.dtype not in (torch.float32, torch.float64):
+                raise ValueError(f"lookup_points: points must be float32 or float64, got {points.dtype}")
+            p = points.contiguous()
+        else:
+            p = np.asarray(points)
+            if p.dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+                raise ValueError(f"lookup_points: points must be float32 or float64, got {p.dtype}")
+            p = np.ascontiguousarray(p)
+        if len(p.shape) != 2 or int(p.shape[1]) != 3:
+            raise ValueError(f"lookup_points: points must have shape [n, 3], got {tuple(p.shape)}")
+        p, dev = self._query_place(p, device)
+        n = int(p.shape[0])
+        f64 = str(p.dtype).endswith("float64")
+        i32, f32 = np.int32, np.float32
+        lab = self._HAS_LABELS
+        out = self._results({"status": ((n,), np.uint8), "count": ((n,), i32), "position": ((n, 3), np.float64), "color": ((n, 3), f32),
+                             "class_id": ((n,), i32) if lab else None, "object_id": ((n,), i32) if lab else None,
+                             "confidence": ((n,), f32) if lab else None}, dev is not None, pinned=False, synchronize=False)
+        prm = L.HvLookupParams(int(min_count), float(min_confidence), int(radius))
+        st = L.HvLookupStats() if stats else None
+        with self._ordered(p):
+            L.check(self._lib.hv_lookup_points(self._h, L.ptr(p), L.HV_F64 if f64 else L.HV_F32, n, ctypes.byref(prm), L.ptr(out["status"]),
+                                               L.ptr(out["count"]), L.ptr(out["position"]), L.ptr(out["color"]), L.ptr(out["class_id"]),
+                                               L.ptr(out["object_id"]), L.ptr(out["confidence"]), ctypes.byref(st) if stats else None,
+                                               L.HV_DEVICE if dev is not None else L.HV_HOST))
+        return VoxelLookup(out["status"], out["count"], out["position"], out["color"], out["class_id"], out["object_id"], out["confidence"],
+                           LookupStats(st.points, st.own, st.near, st.missing, st.invalid) if stats else None)
 
     def clear(self):
         L.check(self._lib.hv_reset(self._h))

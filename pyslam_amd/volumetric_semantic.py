@@ -20,7 +20,7 @@ from collections.abc import Mapping
 import numpy as np
 
 from . import _lib as L
-from .volumetric import VoxelData, VoxelGridData, _BlockGrid, _colors_operand, _points_operand
+from .volumetric import PointCloud, TriangleMesh, VoxelData, VoxelGridData, _BlockGrid, _colors_operand, _points_operand
 
 
 class OBBComputationMethod:
@@ -369,8 +369,23 @@ class VoxelSemanticData(VoxelData):
         return self.confidence_counter
 
 
+class GeometryLabels:
+    """What label_mesh of a semantic grid returns, one entry per vertex / point / pixel of the geometry, in its leading shape:
+    class_ids and object_ids int32 (-1 where nothing was found), confidences float32 (0 there), status uint8 (LOOKUP_*)."""
+
+    def __init__(self, class_ids, object_ids, confidences, status):
+        self.class_ids = class_ids
+        self.object_ids = object_ids
+        self.confidences = confidences
+        self.status = status
+
+    def __repr__(self):
+        return f"GeometryLabels(shape={tuple(self.status.shape)})"
+
+
 class _SemanticGridBase(_BlockGrid):
     _MODE = None
+    _HAS_LABELS = True
 
     def __init__(self, voxel_size=0.05, block_size=8, device=0, max_blocks=None, max_points=None):
         super().__init__(self._MODE, voxel_size, block_size, device, max_blocks, max_points)
@@ -471,6 +486,20 @@ class _SemanticGridBase(_BlockGrid):
 
     def get_voxels(self, min_count=1, min_confidence=0.0):
         return self._query(lambda *a: self._lib.hv_get_voxels_semantic(self._h, int(min_count), float(min_confidence), *a))
+
+    def label_mesh(self, geometry, min_count=1, min_confidence=0.0, radius=1, device=None):
+        """Labels for what a TSDF map emits: geometry = a TriangleMesh (its vertices), a PointCloud (its points) or an [..., 3]
+        float32 / float64 array (numpy or torch, either device), for example ray_cast(...)["vertex"] -> GeometryLabels in the
+        geometry's leading shape.  Every point is looked up by lookup_points(min_count, min_confidence, radius); the geometry is not
+        modified.  device as lookup_points: None gives the labels where the geometry lives."""
+        pts = geometry.vertices if isinstance(geometry, TriangleMesh) else geometry.points if isinstance(geometry, PointCloud) else geometry
+        if not hasattr(pts, "shape"):
+            pts = np.asarray(pts)
+        if len(pts.shape) < 1 or int(pts.shape[-1]) != 3:
+            raise ValueError(f"label_mesh: points must have shape [..., 3], got {tuple(pts.shape)}")
+        lead = tuple(int(d) for d in pts.shape[:-1])
+        r = self.lookup_points(pts.reshape(-1, 3), min_count, min_confidence, radius, device=device)
+        return GeometryLabels(r.class_id.reshape(lead), r.object_id.reshape(lead), r.confidence.reshape(lead), r.status.reshape(lead))
 
     def _query(self, call):
         """call(points, colors, class ids, object ids, confidences, capacity, &count) -> VoxelGridData with the semantic fields."""
