@@ -14,6 +14,9 @@
 // The touched list is eight lists, one per XCD (one returning atomic per workgroup on ONE word is 11 ns each, ~14 us per 640x480
 // frame; MI355X_MICROARCH.md "dequeue": shard the head per XCD).
 #pragma once
+#include <algorithm>
+#include <mutex>
+
 #include "hv_common.h"
 
 static constexpr int HV_BIN_K0 = 256;         // inline entries per table slot (1 KiB; a 640x480 / 5 mm frame puts ~24 points in a block)
@@ -230,10 +233,60 @@ __device__ __forceinline__ void hv_bins_for_each(const HvTable &table, const HvB
     }
 }
 
-// the next call's list lengths (one thread of the fold)
-__device__ __forceinline__ void hv_bins_clear_next(const HvBins &B) {
+// The fold's prologue, by ONE thread of the launch (the helper picks it): the next call's list lengths are cleared, the largest-bin
+// mark of hv_bins_push is handed to *largest (nullptr: nobody asks) and reset - the association uses that counter too -, and the
+// pool's occupancy is published for the next call's capacity gate.
+__device__ __forceinline__ void hv_bins_fold_prologue(const HvTable &table, const HvBins &B, HvStatus *status, int32_t status_seq, int32_t *largest) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
 #pragma unroll
     for (int x = 0; x < HV_BIN_LISTS; ++x) B.len[((B.parity ^ 1) * HV_BIN_LISTS + x) * HV_BIN_LEN_STRIDE] = 0;
+    if (largest) *largest = table.counters[HV_CNT_OUT2];
+    table.counters[HV_CNT_OUT2] = 0;
+    hv_publish_status(table, status, status_seq);
+}
+
+// The heads of the voxel runs of one block's sorted entries s[0 .. m) (voxel index = entry >> idx_bits): body(e, lidx) for every
+// e = first, first + stride, ... whose predecessor belongs to another voxel.  The head folds its run s[e], s[e + 1], ... in point order.
+template <typename F>
+__device__ __forceinline__ void hv_bins_for_each_run(const uint32_t *s, int m, int idx_bits, int first, int stride, F body) {
+    for (int e = first; e < m; e += stride) {
+        const uint32_t lidx = s[e] >> idx_bits;
+        if (e > 0 && (s[e - 1] >> idx_bits) == lidx) continue; // not the head of its voxel's run
+        body(e, lidx);
+    }
+}
+
+// A bin beyond the LDS window is folded in pieces: the entries of bin `slot` (nb of them) with a voxel index in [lo, hi) and - for
+// w >= 0 - a point index in [w, w + cap) are compacted, in bin order, into s[0 .. cap) by a WAVE (ballots); m counts them.
+// -> false when they are more than cap (only possible for w < 0: a window of cap point indices holds at most cap entries, point
+// indices are distinct).  LOADS: wave-loads of entries in flight together (each may walk the page table: the semantic task kernel
+// keeps four, the VOXEL_GRID wave fold - at 64 registers for 8 waves per SIMD - one).
+template <int LOADS>
+__device__ __forceinline__ bool hv_bins_gather(const HvBins &B, int32_t slot, int nb, int idx_bits, uint32_t lo, uint32_t hi, int64_t w, int cap,
+                                               uint32_t *s, int &m) {
+    const int lane = hv_lane_id();
+    const uint32_t idx_mask = (1u << idx_bits) - 1u;
+    m = 0;
+    for (int e0 = 0; e0 < nb; e0 += LOADS * HV_WAVE) {
+        uint32_t ent[LOADS];
+#pragma unroll
+        for (int k = 0; k < LOADS; ++k) { // independent loads
+            const int e = e0 + k * HV_WAVE + lane;
+            ent[k] = e < nb ? hv_bins_entry(B, slot, e) : 0xFFFFFFFFu;
+        }
+#pragma unroll
+        for (int k = 0; k < LOADS; ++k) {
+            const int e = e0 + k * HV_WAVE + lane;
+            const uint32_t li = ent[k] >> idx_bits;
+            const int64_t p = ent[k] & idx_mask;
+            const bool in = e < nb && li - lo < hi - lo /* lo <= li < hi, one unsigned compare */ && (w < 0 || (p >= w && p < w + cap));
+            const unsigned long long bm = __ballot(in);
+            if (m + __popcll(bm) > cap) return false;
+            if (in) s[m + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u))] = ent[k]; // (set bits below this lane)
+            m += __popcll(bm);
+        }
+    }
+    return true;
 }
 
 __device__ __forceinline__ void hv_vgb_bitonic_wave(uint32_t *s, int m2) { // ascending, m2 a power of two >= 64
@@ -261,15 +314,23 @@ __device__ __forceinline__ void hv_vgb_bitonic_wave(uint32_t *s, int m2) { // as
 // probabilistic semantic fold at 128 registers, 8 for the VOXEL_GRID fold), asked once per kernel.
 template <typename K>
 static unsigned hv_bins_fold_grid(hv_volume *v, K kernel, size_t dyn_lds) {
-    static std::vector<std::pair<const void *, unsigned>> cache; // (one process-wide answer per kernel: the library is gfx950 only)
-    for (const auto &c : cache)
-        if (c.first == (const void *)kernel) return c.second;
+    struct Entry {
+        const void *kernel;
+        size_t dyn_lds;
+        int device;
+        unsigned grid;
+    };
+    static std::mutex mu; // (volumes of several threads fold at once)
+    static std::vector<Entry> cache;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Entry &c : cache)
+        if (c.kernel == (const void *)kernel && c.dyn_lds == dyn_lds && c.device == v->device) return c.grid;
     int per_cu = 0, cus = 256;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, v->device) == hipSuccess && prop.multiProcessorCount > 0) cus = prop.multiProcessorCount;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, dyn_lds) != hipSuccess || per_cu < 1) per_cu = 4;
     const unsigned grid = (unsigned)(per_cu * cus);
-    cache.emplace_back((const void *)kernel, grid);
+    cache.push_back(Entry{(const void *)kernel, dyn_lds, v->device, grid});
     return grid;
 }
 
@@ -321,4 +382,40 @@ static inline HvBins hv_bins_begin(hv_volume *v, int idx_bits) {
     v->bins.epoch = v->bins_epoch;
     v->bins.idx_bits = idx_bits;
     return v->bins;
+}
+
+// The bin path's host half, once for the VOXEL_GRID and the semantic integrate: clean bins, a fresh epoch, the caller's bin pass
+// (`bin_launch(B)`), and - when the capacity gate could not vouch for the call (`checked`) - the synchronous look at the claims:
+// blocks that did not fit make the pool grow and the pass run again, from clean arrays (the table may have moved).  Then the parity
+// flips and the call gets its status sequence number; *B and *status_seq are what the fold launches take.
+// The caller has made every allocation of its own (records, task list) BEFORE this: between the bin pass and the fold nothing can
+// fail but a launch, and hv_bins_folded marks the bins unclean then - counts of a bin pass without its fold would otherwise be
+// taken for clean ones, and every later call would lose those blocks' points.
+template <typename BinLaunch>
+static int hv_bins_claim(hv_volume *v, int idx_bits, bool checked, BinLaunch bin_launch, HvBins *B, int32_t *status_seq) {
+    for (int attempt = 0;; ++attempt) {
+        int rc = hv_bins_ensure(v);
+        if (rc != HV_OK) return rc;
+        *B = hv_bins_begin(v, idx_bits);
+        bin_launch(*B);
+        if (!checked) break;
+        rc = hv_claims_fit(v);
+        if (rc == HV_OK) break;
+        v->bins_clean = false; // counts / lists of the aborted claim pass are void
+        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
+    }
+    v->bins.parity ^= 1;
+    *status_seq = hv_next_status_seq(v);
+    return HV_OK;
+}
+// ... and its end, after the fold launches
+static inline int hv_bins_folded(hv_volume *v) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        v->bins_clean = false;
+        hv_set_error("bin / fold launch failed: %s", hipGetErrorString(e));
+        return HV_ERR_DEVICE;
+    }
+    v->frame_counter += 1;
+    return HV_OK;
 }

@@ -7,6 +7,10 @@
 //   linear  : fixed-point bilinear, INTER_BITS = 5: sx = cvRound(map_x * 32), ix = sx >> 5, fx = sx & 31;
 //             8-bit images use integer weights (32-fx)(32-fy)*32 ... summing to 2^15 and
 //             (sum + 2^14) >> 15; float images use the same 1/32-quantised weights in float.
+//
+// ... and filter_shadow_points (pyslam/utilities/depth.py:103-146), the depth image's other per-keyframe preparation (below).
+#include <algorithm>
+
 #include "hv_common.h"
 
 enum { HV_IMG_U8 = 0, HV_IMG_F32 = 1, HV_IMG_I32 = 2 };
@@ -176,3 +180,208 @@ extern "C" int hv_remap(hv_volume *v, const void *src, int32_t src_kind, int32_t
     HV_HIP(hipStreamSynchronize(v->stream));
     return HV_OK;
 }
+
+
+// ---- filter_shadow_points (pyslam/utilities/depth.py:103-146) -----------------------------------
+// |d(r,c) - d(r-dy,c)| and |d(r,c) - d(r,c-dx)|; threshold = 3 * 1.4826 * median(positive deltas)
+// (float32 arithmetic, as numpy evaluates it for a float32 image); both endpoints of a large jump
+// are replaced by fill_value.  The global median is an exact radix SELECT on the deltas' bit patterns (order-preserving for
+// positive floats): three histogram passes over the image (12 + 12 + 8 bits), each followed by a one-workgroup pick of the
+// bin(s) that hold the two middle ranks; the deltas are recomputed in every pass (two subtractions) instead of being stored,
+// and the threshold stays in device memory for the mask kernel - no sort, no host round trip.  (Round 2: the deltas were
+// written out, radix-sorted (19 launches) and the middle elements copied to the host - 0.33 ms of a 1.2 ms semantic keyframe,
+// profiles/r03/kernel_stats_semantic.csv.)
+// state words: [0] number of positive deltas, [1] [2] remaining ranks of the two middle elements, [3] [4] their key prefixes,
+// [5] the threshold (float bits)
+enum { HV_SH_N = 0, HV_SH_RANK0 = 1, HV_SH_RANK1 = 2, HV_SH_PRE0 = 3, HV_SH_PRE1 = 4, HV_SH_THR = 5, HV_SH_TICKET = 8 /* + pass */, HV_SH_WORDS = 16 };
+static constexpr int HV_SH_BINS01 = 4096, HV_SH_BINS2 = 256;
+static constexpr int HV_SH_GRID = 256; // workgroups of a histogram pass
+static constexpr int HV_SH_HIST_WORDS = HV_SH_BINS01 + 2 * HV_SH_BINS01 + 2 * HV_SH_BINS2;
+
+// one workgroup: the bin holding each of the two ranks, the rank inside it.  (Round 5 tried the pick as the tail of the histogram
+// launch - run by its last workgroup to finish, the histogram read back with L2-level loads -: three launches less per keyframe and
+// 18 us MORE, 69.6 us for the three passes against 51.5: the 4096 bypassing loads of one workgroup cost more than a 5 us launch.)
+template <int PASS>
+__device__ __forceinline__ void hv_shadow_pick(const uint32_t *__restrict__ hist, uint32_t *__restrict__ state) {
+    constexpr int BINS = PASS == 2 ? HV_SH_BINS2 : HV_SH_BINS01;
+    constexpr int PER = BINS / 256;
+    constexpr int BITS = PASS == 2 ? 8 : 12;
+    __shared__ uint32_t s_scan[256];
+    __shared__ uint32_t s_rank[2];
+    const int t = threadIdx.x;
+    for (int target = 0; target < 2; ++target) {
+        const uint32_t *h = hist + (PASS == 0 ? 0 : target * BINS);
+        uint32_t local[PER], sum = 0u;
+#pragma unroll
+        for (int k = 0; k < PER; ++k) {
+            local[k] = h[t * PER + k];
+            sum += local[k];
+        }
+        s_scan[t] = sum;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) { // Hillis-Steele inclusive scan
+            const uint32_t addv = t >= off ? s_scan[t - off] : 0u;
+            __syncthreads();
+            s_scan[t] += addv;
+            __syncthreads();
+        }
+        if (PASS == 0 && t == 0) {
+            const uint32_t n = s_scan[255];
+            if (target == 0) state[HV_SH_N] = n;
+            s_rank[target] = n ? (target == 0 ? (n - 1u) / 2u : n / 2u) : 0u; // ranks of np.median's two middle elements
+        }
+        if (PASS > 0 && t == 0) s_rank[target] = state[HV_SH_RANK0 + target];
+        __syncthreads();
+        const uint32_t rank = s_rank[target];
+        const uint32_t incl = s_scan[t];
+        uint32_t before = incl - sum;
+        if (rank >= before && rank < incl) { // exactly one thread when the rank exists
+#pragma unroll
+            for (int k = 0; k < PER; ++k) {
+                if (rank < before + local[k]) {
+                    const uint32_t prefix = PASS == 0 ? 0u : state[HV_SH_PRE0 + target];
+                    state[HV_SH_PRE0 + target] = (prefix << BITS) | (uint32_t)(t * PER + k);
+                    state[HV_SH_RANK0 + target] = rank - before;
+                    break;
+                }
+                before += local[k];
+            }
+        }
+        __syncthreads();
+    }
+    if (PASS == 2 && t == 0) {
+        float thr = __uint_as_float(0x7fc00000u); // np.median of an empty array -> nan -> nothing is masked
+        if (state[HV_SH_N]) {
+            const float a = __uint_as_float(state[HV_SH_PRE0]), b = __uint_as_float(state[HV_SH_PRE1]);
+            const float mad = state[HV_SH_PRE0] == state[HV_SH_PRE1] ? a : (a + b) * 0.5f; // np.median -> np.mean of the two middle float32
+            const float sigma = 1.4826f * mad;
+            thr = 3.0f * sigma;
+        }
+        state[HV_SH_THR] = __float_as_uint(thr);
+    }
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void k_shadow_hist(const float *__restrict__ depth, int H, int W, int dx, int dy,
+                                                      uint32_t *__restrict__ state, uint32_t *__restrict__ hist) {
+    constexpr int BINS = PASS == 2 ? HV_SH_BINS2 : HV_SH_BINS01;
+    constexpr int NB = (PASS == 0 ? 1 : 2) * BINS;
+    __shared__ uint32_t s_h[NB];
+    for (int i = threadIdx.x; i < NB; i += 256) s_h[i] = 0u;
+    __syncthreads();
+    const uint32_t p0 = PASS > 0 ? state[HV_SH_PRE0] : 0u, p1 = PASS > 0 ? state[HV_SH_PRE1] : 0u;
+    auto add = [&](float v) {
+        if (!(v > 0.0f)) return; // NaN compares false, like numpy's `delta_values > 0`
+        const uint32_t key = __float_as_uint(v);
+        if (PASS == 0) {
+            atomicAdd(&s_h[key >> 20], 1u);
+        } else if (PASS == 1) {
+            if ((key >> 20) == p0) atomicAdd(&s_h[(key >> 8) & 0xfffu], 1u);
+            if ((key >> 20) == p1) atomicAdd(&s_h[BINS + ((key >> 8) & 0xfffu)], 1u);
+        } else {
+            if ((key >> 8) == p0) atomicAdd(&s_h[key & 0xffu], 1u);
+            if ((key >> 8) == p1) atomicAdd(&s_h[BINS + (key & 0xffu)], 1u);
+        }
+    };
+    const int npx = H * W;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += gridDim.x * 256) {
+        const int r = i / W, c = i - r * W;
+        const float d = depth[i];
+        if (dy > 0 && r >= dy) add(fabsf(d - depth[i - dy * W]));
+        if (dx > 0 && c >= dx) add(fabsf(d - depth[i - dx]));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < NB; i += 256)
+        if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
+}
+
+template <int PASS>
+__global__ __launch_bounds__(256) void k_shadow_pick(const uint32_t *__restrict__ hist, uint32_t *__restrict__ state) {
+    hv_shadow_pick<PASS>(hist, state);
+}
+
+__global__ __launch_bounds__(256) void k_shadow_mask(const float *__restrict__ depth, int H, int W, int dx, int dy,
+                                                      const uint32_t *__restrict__ state, float fill, float *__restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)H * W) return;
+    const float thr = __uint_as_float(state[HV_SH_THR]);
+    const int r = (int)(i / W), c = (int)(i % W);
+    const float d = depth[i];
+    bool m = false;
+    if (dy > 0) {
+        if (r >= dy) m |= fabsf(d - depth[i - (int64_t)dy * W]) > thr;
+        if (r + dy < H) m |= fabsf(depth[i + (int64_t)dy * W] - d) > thr;
+    }
+    if (dx > 0) {
+        if (c >= dx) m |= fabsf(d - depth[i - dx]) > thr;
+        if (c + dx < W) m |= fabsf(depth[i + dx] - d) > thr;
+    }
+    out[i] = m ? fill : d;
+}
+
+extern "C" {
+
+// the seven launches of the filter on `st`: head = [histograms][state] (zeroed here), dd -> d_out (device images)
+static int shadow_filter_launch(const float *dd, int32_t height, int32_t width, int32_t delta_x, int32_t delta_y, float fill_value,
+                                float *d_out, uint32_t *head, hipStream_t st) {
+    const int64_t npx = (int64_t)height * width;
+    uint32_t *hist0 = head, *hist1 = hist0 + HV_SH_BINS01, *hist2 = hist1 + 2 * HV_SH_BINS01;
+    uint32_t *state = hist0 + HV_SH_HIST_WORDS;
+    HV_HIP(hipMemsetAsync(hist0, 0, sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS), st));
+    // one workgroup per CU (1024 measured the same, round 6: the passes are bound by the LDS atomics of a few dozen hot bins)
+    const unsigned hist_grid = (unsigned)std::min<int64_t>((npx + 255) / 256, HV_SH_GRID);
+    hipLaunchKernelGGL(k_shadow_hist<0>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist0);
+    hipLaunchKernelGGL(k_shadow_pick<0>, dim3(1), dim3(256), 0, st, hist0, state);
+    hipLaunchKernelGGL(k_shadow_hist<1>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist1);
+    hipLaunchKernelGGL(k_shadow_pick<1>, dim3(1), dim3(256), 0, st, hist1, state);
+    hipLaunchKernelGGL(k_shadow_hist<2>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist2);
+    hipLaunchKernelGGL(k_shadow_pick<2>, dim3(1), dim3(256), 0, st, hist2, state);
+    hipLaunchKernelGGL(k_shadow_mask, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, fill_value, d_out);
+    HV_HIP(hipGetLastError());
+    return HV_OK;
+}
+
+int hv_filter_shadow_points(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,
+                            int32_t delta_y, float fill_value, float *out, int32_t loc) {
+    HV_REQUIRE(v != nullptr && depth != nullptr && out != nullptr, HV_ERR_INVALID, "hv_filter_shadow_points: null argument");
+    HV_REQUIRE(height > 0 && width > 0 && delta_x >= 0 && delta_y >= 0 && delta_x < width && delta_y < height,
+               HV_ERR_INVALID, "hv_filter_shadow_points: bad image size or deltas");
+    HV_HIP(hipSetDevice(v->device));
+    const int64_t npx = (int64_t)height * width;
+    HV_REQUIRE(npx < (int64_t)1 << 30, HV_ERR_INVALID, "hv_filter_shadow_points: image too large");
+    const void *d_depth = nullptr;
+    int rc = hv_stage_in(v, depth, sizeof(float) * npx, loc, 0, &d_depth);
+    if (rc != HV_OK) return rc;
+    // scratch: [histograms][state][out npx]
+    const size_t head = sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS);
+    rc = hv_ensure_buffer(v, &v->out_c, &v->out_c_bytes, head + sizeof(float) * npx);
+    if (rc != HV_OK) return rc;
+    float *d_out = loc == HV_DEVICE ? out : (float *)((char *)v->out_c + head);
+    rc = shadow_filter_launch((const float *)d_depth, height, width, delta_x, delta_y, fill_value, d_out, (uint32_t *)v->out_c, v->stream);
+    if (rc != HV_OK) return rc;
+    // host images: copied back and complete on return; device images: queued on the volume's stream like every other launch
+    if (loc == HV_HOST) {
+        HV_HIP(hipMemcpyAsync(out, d_out, sizeof(float) * npx, hipMemcpyDeviceToHost, v->stream));
+        HV_HIP(hipStreamSynchronize(v->stream));
+    }
+    return HV_OK;
+}
+
+int hv_filter_shadow_points_on_stream(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,
+                                      int32_t delta_y, float fill_value, float *out, void *stream) {
+    HV_REQUIRE(v != nullptr && depth != nullptr && out != nullptr, HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: null argument");
+    HV_REQUIRE(height > 0 && width > 0 && delta_x >= 0 && delta_y >= 0 && delta_x < width && delta_y < height,
+               HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: bad image size or deltas");
+    HV_REQUIRE((int64_t)height * width < (int64_t)1 << 30, HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: image too large");
+    HV_HIP(hipSetDevice(v->device));
+    // the filter touches nothing of the volume: it may run beside the volume's own launches (a keyframe's depth is filtered on the
+    // upload side while the previous keyframe is fused).  Histograms and state of its own, four sets used in turn.
+    constexpr int SETS = 4;
+    const size_t head = sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS);
+    if (v->shadow_ring == nullptr) HV_HIP(hipMalloc(&v->shadow_ring, head * SETS));
+    uint32_t *scratch = (uint32_t *)((char *)v->shadow_ring + head * (size_t)v->shadow_ring_next);
+    v->shadow_ring_next = (v->shadow_ring_next + 1) % SETS;
+    return shadow_filter_launch(depth, height, width, delta_x, delta_y, fill_value, out, scratch, (hipStream_t)stream);
+}
+
+} // extern "C"

@@ -2,8 +2,13 @@
 // query description with its host-side setup (reference: camera_frustrum.cpp:175-264,
 // voxel_block_grid.hpp:827-835, 1339-1349).
 #pragma once
+#include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
+#include <numeric>
+#include <vector>
 
 #include "hv_common.h"
 
@@ -106,8 +111,8 @@ __device__ __forceinline__ bool hv_frustum_contains(const HvQuery &Q, float xw, 
     return hv_frustum_contains_d(Q, (double)xw, (double)yw, (double)zw, uvd);
 }
 
-static inline void fill_frustum_query(HvQuery &Q, const hv_volume *v, const float *intr, int width, int height,
-                               const double *T_cw, float depth_max, float depth_min) {
+static inline void fill_frustum_query(HvQuery &Q, const float *intr, int width, int height, const double *T_cw, float depth_max,
+                                      float depth_min) {
     Q.fx = intr[0];
     Q.fy = intr[1];
     Q.cx = intr[2];
@@ -144,12 +149,12 @@ static inline void fill_frustum_query(HvQuery &Q, const hv_volume *v, const floa
             }
         }
     }
-    (void)v;
 }
 
 // bbox -> voxel/block key range, voxel_block_grid.hpp:827-835: get_voxel_key_inv<double,double>
 // with the float inv_voxel_size_ promoted to double.
-static inline void fill_key_range(HvQuery &Q, const HvGridParams &G) {
+static inline void fill_key_range(HvQuery &Q, const hv_volume *v) {
+    const HvGridParams G = grid_params(v); // (voxel size and block size: the same in every grid mode)
     for (int k = 0; k < 3; ++k) {
         Q.vmin[k] = (int32_t)std::floor(Q.bb[k] * (double)G.inv_voxel_size);
         Q.vmax[k] = (int32_t)std::floor(Q.bb[3 + k] * (double)G.inv_voxel_size);
@@ -158,6 +163,81 @@ static inline void fill_key_range(HvQuery &Q, const HvGridParams &G) {
     }
 }
 
+// The three queries of get_voxels / get_voxels_in_bb / get_voxels_in_camera_frustrum (and, as kind 3, carve), ready for a kernel.
+static inline HvQuery hv_query_all(int32_t min_count) {
+    HvQuery Q;
+    memset(&Q, 0, sizeof(Q));
+    Q.min_count = min_count;
+    return Q;
+}
+static inline HvQuery hv_query_in_bb(const hv_volume *v, const double *bbox, int32_t min_count) {
+    HvQuery Q = hv_query_all(min_count);
+    Q.kind = 1;
+    for (int k = 0; k < 6; ++k) Q.bb[k] = bbox[k];
+    fill_key_range(Q, v);
+    return Q;
+}
+static inline HvQuery hv_query_in_frustum(const hv_volume *v, const float *intr, int width, int height, const double *T_cw, float depth_max,
+                                          float depth_min, int32_t min_count, int32_t kind = 2) {
+    HvQuery Q = hv_query_all(min_count);
+    Q.kind = kind;
+    fill_frustum_query(Q, intr, width, height, T_cw, depth_max, depth_min);
+    fill_key_range(Q, v);
+    return Q;
+}
+
+// ---- host halves the VOXEL_GRID and the semantic scans share --------------------------------------
+// a wave per block of the pool, grid-stride: workgroups of 256
+static inline unsigned hv_wave_per_block_grid(int64_t nb) { return (unsigned)std::min<int64_t>((nb + 3) / 4, 8192); }
+
+// the prologue of a scan over the allocated blocks: the volume's device, the number of blocks (0: an empty map, nothing to launch)
+static inline int hv_scan_begin(hv_volume *v, int64_t *nb) {
+    HV_HIP(hipSetDevice(v->device));
+    return hv_num_blocks(v, nb);
+}
+
+// A collecting scan: `launch()` queues the kernel that counts its rows in HV_CNT_OUT (and writes the first `cap` of them to device
+// arrays); *n receives the count, and min(*n, cap) rows of every {host, device, bytes per row} triple in `back` are copied back.
+struct HvRowsBack {
+    void *host;
+    const void *dev;
+    size_t row_bytes;
+};
+template <typename Launch>
+static int hv_collect_rows(hv_volume *v, int64_t cap, int64_t *n, Launch launch, std::initializer_list<HvRowsBack> back) {
+    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
+    launch();
+    HV_HIP(hipGetLastError());
+    const int rc = hv_read_counters(v);
+    if (rc != HV_OK) return rc;
+    *n = v->h_counters[HV_CNT_OUT];
+    const int64_t m = std::min(*n, cap);
+    if (m <= 0 || back.size() == 0) return HV_OK;
+    for (const HvRowsBack &b : back) HV_HIP(hipMemcpyAsync(b.host, b.dev, b.row_bytes * (size_t)m, hipMemcpyDeviceToHost, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+// The map's blocks in ascending (x, y, z) key order, as the dumps list them: xyz[i] = key of pool block i, order[o] = the pool block
+// at place o.
+static inline int hv_blocks_in_key_order(hv_volume *v, int64_t nb, std::vector<std::array<int32_t, 3>> &xyz, std::vector<int64_t> &order) {
+    std::vector<uint64_t> bkeys((size_t)nb);
+    HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost));
+    xyz.resize((size_t)nb);
+    for (int64_t i = 0; i < nb; ++i) hv_unpack_key(bkeys[i], xyz[i][0], xyz[i][1], xyz[i][2]);
+    order.resize((size_t)nb);
+    std::iota(order.begin(), order.end(), 0);
+    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return xyz[a] < xyz[b]; });
+    return HV_OK;
+}
+
+// a frame's depth and colour planes (npx pixels: of one frame, or of a batch's frames behind each other) on the device
+static inline int hv_stage_frame(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int64_t npx, int32_t loc,
+                                 const void **d_depth, const uint8_t **d_rgb) {
+    int rc = hv_stage_in(v, depth, (size_t)npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, d_depth);
+    if (rc == HV_OK) rc = hv_stage_in(v, rgb, (size_t)npx * 3, loc, 1, (const void **)d_rgb);
+    return rc;
+}
 
 // semantic-payload implementations behind the mode-independent entry points (hv_semantic_ops.hip)
 int hv_sem_carve(hv_volume *v, const HvQuery &Q, const float *d_depth, int64_t n_blocks);

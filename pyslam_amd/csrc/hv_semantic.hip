@@ -23,10 +23,8 @@
 #include "hv_query.h"
 #include "hv_semantic.h"
 #include "hv_bins.h"
+#include "hv_sort_path.h"
 #include "hv_unproject.h"
-#include <rocprim/device/device_radix_sort.hpp>
-
-static constexpr uint32_t HV_SORT_SENTINEL = 0xFFFFFFFFu;
 
 // (sem_floor_div, sem_voxel_coord and sem_point_block - a point's voxel - live in hv_semantic.h: hv_lookup.hip keys its points with them)
 
@@ -112,6 +110,20 @@ struct HvSemArrays {
     }
 };
 // record: {x, y, z, rgb8 | class, instance, depth, -}; colours through the fold's 256-entry table of (float)(c / 255.0) (depth.py:76)
+__device__ __forceinline__ HvSemPoint sem_rec_decode(const float4 &a, const float4 &b, const float *lut) {
+    HvSemPoint q;
+    q.x = (double)a.x;
+    q.y = (double)a.y;
+    q.z = (double)a.z;
+    const uint32_t c = __float_as_uint(a.w);
+    q.c0 = lut[c & 255u];
+    q.c1 = lut[(c >> 8) & 255u];
+    q.c2 = lut[(c >> 16) & 255u];
+    q.cls = (int32_t)__float_as_uint(b.x);
+    q.obj = (int32_t)__float_as_uint(b.y);
+    q.depth = b.z;
+    return q;
+}
 struct HvSemRecs {
     const float4 *__restrict__ rec;
     const float *lut; // LDS
@@ -121,18 +133,7 @@ struct HvSemRecs {
     __device__ __forceinline__ bool has_depth() const { return depth; }
     __device__ __forceinline__ HvSemPoint get(int64_t p) const {
         const float4 a = rec[2 * p], b = rec[2 * p + 1];
-        HvSemPoint q;
-        q.x = (double)a.x;
-        q.y = (double)a.y;
-        q.z = (double)a.z;
-        const uint32_t c = __float_as_uint(a.w);
-        q.c0 = lut[c & 255u];
-        q.c1 = lut[(c >> 8) & 255u];
-        q.c2 = lut[(c >> 16) & 255u];
-        q.cls = (int32_t)__float_as_uint(b.x);
-        q.obj = (int32_t)__float_as_uint(b.y);
-        q.depth = b.z;
-        return q;
+        return sem_rec_decode(a, b, lut);
     }
 };
 
@@ -147,18 +148,7 @@ struct HvSemStaged {
     __device__ __forceinline__ bool has_depth() const { return depth; }
     __device__ __forceinline__ HvSemPoint get(int64_t e) const {
         const float4 a = stage[2 * e], b = stage[2 * e + 1];
-        HvSemPoint q;
-        q.x = (double)a.x;
-        q.y = (double)a.y;
-        q.z = (double)a.z;
-        const uint32_t c = __float_as_uint(a.w);
-        q.c0 = lut[c & 255u];
-        q.c1 = lut[(c >> 8) & 255u];
-        q.c2 = lut[(c >> 16) & 255u];
-        q.cls = (int32_t)__float_as_uint(b.x);
-        q.obj = (int32_t)__float_as_uint(b.y);
-        q.depth = b.z;
-        return q;
+        return sem_rec_decode(a, b, lut);
     }
 };
 static constexpr int HV_SEMB_STAGE = 128; // bins up to this size fold from staged records (32 bytes each in the sort's spare windows)
@@ -372,37 +362,36 @@ __device__ __forceinline__ HvSemRecs sem_src_prepare(const HvSemRecs &src, float
     return r;
 }
 
+// One block's sorted entries s[0 .. m) folded by a wave: the head lane of every voxel run folds the run, its points read from `src` by
+// point index
+template <typename VOX, typename SRC>
+__device__ __forceinline__ void semb_fold_sorted(const HvTable &table, VOX *__restrict__ pool, int64_t block_base, const HvSemParams &G, const SRC &src,
+                                                 unsigned long long *__restrict__ occ, const uint32_t *s, int m, int idx_bits) {
+    const uint32_t idx_mask = (1u << idx_bits) - 1u;
+    hv_bins_for_each_run(s, m, idx_bits, hv_lane_id(), HV_WAVE, [&](int e, uint32_t lidx) {
+        sem_fold_run<VOX>(table, pool, block_base + lidx, G, src, occ,
+                          [&](int j) -> int64_t { return (e + j < m && (s[e + j] >> idx_bits) == lidx) ? (int64_t)(s[e + j] & idx_mask) : -1; });
+    });
+}
+
 // One wave per touched block: its bin is brought into (voxel, point index) order in the wave's LDS window (semb_sort_window)
 // and the head lane of every voxel run folds the run in point order - the reference's sequential order, bit-identical to the radix
-// path.  Bins beyond the window go to k_semb_fold_tasks (or, without a task list, through voxel ranges / point windows here).
+// path.  Bins beyond the window go to k_semb_fold_tasks.
 template <typename VOX, typename SRC>
 __global__ __launch_bounds__(256, HV_SEMB_FOLD_MIN_WAVES) void k_semb_fold_wave(HvTable table, VOX *__restrict__ pool, HvBins B, HvSemParams G, SRC src_in,
-                                                         unsigned long long *__restrict__ occ, int64_t n_points, HvStatus *status, int32_t status_seq,
+                                                         unsigned long long *__restrict__ occ, HvStatus *status, int32_t status_seq,
                                                          int32_t *__restrict__ task_count, int4 *__restrict__ tasks, int task_cap, int wcap) {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_dyn[]; // per wave: [wcap src][wcap dst][nvox + 64 offsets]; wcap = the window, a power of two (HV_SEM_WCAP)
     __shared__ float s_lut[256];
     const SRC src = sem_src_prepare(src_in, s_lut);
     const int idx_bits = B.idx_bits, parity = B.parity;
     const HvBinLists L = hv_bins_lists(B);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        task_count[parity ^ 1] = 0;        // the next call's task list
-        hv_bins_clear_next(B);             // the next call's list lengths
-        table.counters[HV_CNT_OUT2] = 0;   // (hv_bins_push's largest-bin mark: the association uses this counter too)
-        hv_publish_status(table, status, status_seq);
-    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) task_count[parity ^ 1] = 0; // the next call's task list
+    hv_bins_fold_prologue(table, B, status, status_seq, nullptr);
     const int wave = threadIdx.x >> 6, lane = hv_lane_id();
     const int per_wave = 2 * wcap + G.nvox + 64;
     uint32_t *s = s_dyn + wave * per_wave, *s_dst = s + wcap, *off = s + 2 * wcap;
     const uint32_t idx_mask = (1u << idx_bits) - 1u;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    auto fold_sorted = [&](int m, int64_t block_base) {
-        for (int e = lane; e < m; e += HV_WAVE) {
-            const uint32_t lidx = s[e] >> idx_bits;
-            if (e > 0 && (s[e - 1] >> idx_bits) == lidx) continue; // not the head of its voxel's run
-            sem_fold_run<VOX>(table, pool, block_base + lidx, G, src, occ,
-                              [&](int j) -> int64_t { return (e + j < m && (s[e + j] >> idx_bits) == lidx) ? (int64_t)(s[e + j] & idx_mask) : -1; });
-        }
-    };
     const bool can_stage = (size_t)(wcap + G.nvox + 64) * sizeof(uint32_t) >= (size_t)HV_SEMB_STAGE * 32;
     hv_bins_for_each(table, B, L, blockIdx.x * 4 + wave, gridDim.x * 4, [&](const HvBinHeader &h) {
         const int32_t slot = h.slot, nb = h.nb, idx = h.idx;
@@ -461,69 +450,25 @@ __global__ __launch_bounds__(256, HV_SEMB_FOLD_MIN_WAVES) void k_semb_fold_wave(
                     asm volatile("" ::"v"(warm)); // (the voxel lines have arrived)
                     hv_wave_lds_sync();
                     const HvSemStaged staged{stage, src.lut, src.labels, src.depth};
-                    for (int e = lane; e < nb; e += HV_WAVE) {
-                        const uint32_t lidx = s[e] >> idx_bits;
-                        if (e > 0 && (s[e - 1] >> idx_bits) == lidx) continue; // not the head of its voxel's run
+                    hv_bins_for_each_run(s, nb, idx_bits, lane, HV_WAVE, [&](int e, uint32_t lidx) {
                         sem_fold_run<VOX>(table, pool, block_base + lidx, G, staged, occ,
                                           [&](int j) -> int64_t { return (e + j < nb && (s[e + j] >> idx_bits) == lidx) ? (int64_t)(e + j) : -1; });
-                    }
+                    });
                     return;
                 }
             }
-            fold_sorted(nb, block_base);
+            semb_fold_sorted<VOX>(table, pool, block_base, G, src, occ, s, nb, idx_bits);
             return;
         }
-        if (tasks != nullptr) {
-            // A bin beyond the window (a wall at 0.7 m puts ~3 000 points of a 640x480 keyframe into one 8 cm block) would be a
-            // long serial job for this wave while the other waves of the launch have long left: it is cut into its voxel-index
-            // ranges of 64 and handed to k_semb_fold_tasks, one wave per range.
-            const int n_ranges = (G.nvox + 63) / 64;
-            int32_t at = 0;
-            if (lane == 0) at = atomicAdd(&task_count[parity], n_ranges);
-            at = __shfl(at, 0);
-            if (at + n_ranges <= task_cap) {
-                if (lane < n_ranges) tasks[at + lane] = make_int4(idx, lane, nb, slot);
-                return;
-            }
-            if (lane == 0) atomicSub(&task_count[parity], n_ranges); // (no room: this wave does it itself, below)
-        }
-        // voxel-index ranges narrow enough for a range's entries to fit the window; a range that still overflows (very many points
-        // in few voxels) is folded in point-index windows (a voxel's points still arrive in order)
-        int parts = 2;
-        while (nb / parts > wcap / 2 && parts < G.nvox) parts <<= 1;
-        const int width = (G.nvox + parts - 1) / parts;
-        for (int lo = 0; lo < G.nvox; lo += width) {
-            const uint32_t hi = (uint32_t)(lo + width);
-            for (int64_t w = -1; w < n_points; w += wcap) { // w = -1: the whole range at once
-                hv_wave_lds_sync();
-                int m = 0;
-                bool overflow = false;
-                for (int e0 = 0; e0 < nb; e0 += HV_WAVE) {
-                    const int e = e0 + lane;
-                    const uint32_t ent = e < nb ? hv_bins_entry(B, slot, e) : 0u;
-                    const uint32_t li = ent >> idx_bits;
-                    const int64_t p = ent & idx_mask;
-                    const bool in = e < nb && li >= (uint32_t)lo && li < hi && (w < 0 || (p >= w && p < w + wcap));
-                    const unsigned long long bm = __ballot(in);
-                    if (m + __popcll(bm) > wcap) {
-                        overflow = true;
-                        break;
-                    }
-                    if (in) s[m + __popcll(bm & lt)] = ent;
-                    m += __popcll(bm);
-                }
-                if (overflow) {
-                    w = -(int64_t)wcap; // next: w = 0
-                    continue;
-                }
-                if (m > 0) {
-                    hv_wave_lds_sync();
-                    semb_sort_window(s, s_dst, off, m, idx_bits, G.nvox);
-                    fold_sorted(m, block_base);
-                }
-                if (w < 0) break;
-            }
-        }
+        // A bin beyond the window (a wall at 0.7 m puts ~3 000 points of a 640x480 keyframe into one 8 cm block) would be a
+        // long serial job for this wave while the other waves of the launch have long left: it is cut into its voxel-index
+        // ranges of 64 and handed to k_semb_fold_tasks, one wave per range.  The list has room for every such bin of a call
+        // (sem_task_cap); the bound on the write is there for the reader of this kernel alone.
+        const int n_ranges = (G.nvox + 63) / 64;
+        int32_t at = 0;
+        if (lane == 0) at = atomicAdd(&task_count[parity], n_ranges);
+        at = __shfl(at, 0);
+        if (lane < n_ranges && at + lane < task_cap) tasks[at + lane] = make_int4(idx, lane, nb, slot);
     });
 }
 
@@ -539,58 +484,25 @@ __global__ __launch_bounds__(256, HV_SEMB_FOLD_MIN_WAVES) void k_semb_fold_tasks
     const SRC src = sem_src_prepare(src_in, s_lut);
     const int idx_bits = B.idx_bits;
     const int n_tasks = min(task_count[B.parity], task_cap);
-    const int wave = threadIdx.x >> 6, lane = hv_lane_id();
+    const int wave = threadIdx.x >> 6;
     const int per_wave = 2 * wcap + G.nvox + 64;
     uint32_t *s = s_dyn + wave * per_wave, *s_dst = s + wcap, *off = s + 2 * wcap;
-    const uint32_t idx_mask = (1u << idx_bits) - 1u;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     for (int t = blockIdx.x * 4 + wave; t < n_tasks; t += gridDim.x * 4) {
         const int4 task = tasks[t];
         const int64_t block_base = (int64_t)task.x * G.nvox;
         const uint32_t lo = (uint32_t)task.y * 64u, hi = lo + 64u;
         const int nb = task.z, slot = task.w;
-        auto fold_sorted = [&](int m) {
-            for (int e = lane; e < m; e += HV_WAVE) {
-                const uint32_t lidx = s[e] >> idx_bits;
-                if (e > 0 && (s[e - 1] >> idx_bits) == lidx) continue;
-                sem_fold_run<VOX>(table, pool, block_base + lidx, G, src, occ,
-                                  [&](int j) -> int64_t { return (e + j < m && (s[e + j] >> idx_bits) == lidx) ? (int64_t)(s[e + j] & idx_mask) : -1; });
-            }
-        };
         for (int64_t w = -1; w < n_points; w += wcap) { // w = -1: the whole range at once; on overflow: point-index windows
             hv_wave_lds_sync();
-            int m = 0;
-            bool overflow = false;
-            for (int e0 = 0; e0 < nb && !overflow; e0 += 4 * HV_WAVE) {
-                uint32_t ent[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { // four independent loads in flight
-                    const int e = e0 + k * HV_WAVE + lane;
-                    ent[k] = e < nb ? hv_bins_entry(B, slot, e) : 0xFFFFFFFFu;
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int e = e0 + k * HV_WAVE + lane;
-                    const uint32_t li = ent[k] >> idx_bits;
-                    const int64_t p = ent[k] & idx_mask;
-                    const bool in = e < nb && li >= lo && li < hi && (w < 0 || (p >= w && p < w + wcap));
-                    const unsigned long long bm = __ballot(in);
-                    if (m + __popcll(bm) > wcap) {
-                        overflow = true;
-                        break;
-                    }
-                    if (in) s[m + __popcll(bm & lt)] = ent[k];
-                    m += __popcll(bm);
-                }
-            }
-            if (overflow) { // (only possible for w = -1: a window holds at most WCAP distinct point indices)
+            int m;
+            if (!hv_bins_gather<4>(B, slot, nb, idx_bits, lo, hi, w, wcap, s, m)) { // (only possible for w = -1)
                 w = -(int64_t)wcap; // next iteration: w = 0
                 continue;
             }
             if (m > 0) {
                 hv_wave_lds_sync();
                 semb_sort_window(s, s_dst, off, m, idx_bits, G.nvox);
-                fold_sorted(m);
+                semb_fold_sorted<VOX>(table, pool, block_base, G, src, occ, s, m, idx_bits);
             }
             if (w < 0) break; // the range fitted: done
         }
@@ -695,65 +607,51 @@ __global__ __launch_bounds__(256) void k_sem_collect(HvTable table, const VOX *_
 }
 
 // ------------------------------------------------------------------------------------------------
-static int sem_sort_bits(const hv_volume *v) {
-    int slot_bits = 0;
-    while ((1ull << slot_bits) < v->table_capacity) slot_bits++;
-    return std::min(32, slot_bits + v->local_bits + 1);
-}
-
 // The fold's LDS window per wave (entries): bins beyond it go to the task kernel as voxel ranges.  512 leaves room for the 16 waves
 // per CU the kernel's registers allow (1024: 12 waves; measured round 4)
 static int sem_wcap() { return 512; }
 static size_t sem_fold_lds(int wcap, int nvox) { return 4 * sizeof(uint32_t) * (size_t)(2 * wcap + nvox + 64); } // two windows + per-voxel offsets per wave
+// Entries of the big bins' task list that a call of n points can need.  A bin beyond the window holds at least wcap + 1 of the
+// call's points, so there are at most n / (wcap + 1) <= n / wcap of them, and each becomes one task per 64 voxel indices of its
+// block: the list never fills, and k_semb_fold_wave has no second way to fold such a bin.  (With n < 2^(32 - local_bits), which
+// the entry layout asks for, and nvox <= 2^local_bits this is about 2^17 entries: the limit below is not met by any call the bin
+// path takes otherwise; it is stated so that the list's size is bounded by something written down.)
+static constexpr int64_t HV_SEMB_TASK_LIMIT = 1 << 22;
+static int64_t sem_task_cap(int64_t n, int nvox) { return (n / sem_wcap() + 1) * ((nvox + 63) / 64); }
 static bool sem_bins_usable(const hv_volume *v, int64_t n) {
     const char *force = getenv("HV_SEM_PATH"); // HV_SEM_PATH=sort keeps the device-wide radix sort: A/B, tests
     const int nvox = v->cfg.block_size * v->cfg.block_size * v->cfg.block_size;
-    return hv_bins_usable(v, n, 32 - v->local_bits) && sem_fold_lds(sem_wcap(), nvox) <= 64 * 1024 && !(force && strcmp(force, "sort") == 0);
+    return hv_bins_usable(v, n, 32 - v->local_bits) && sem_fold_lds(sem_wcap(), nvox) <= 64 * 1024 && sem_task_cap(n, nvox) <= HV_SEMB_TASK_LIMIT &&
+           !(force && strcmp(force, "sort") == 0);
 }
 
 // The bin path's launches after the capacity gate: `bin(B)` launches the bin pass (arrays or frame), then the fold over `src`.
 template <typename VOX, typename SRC, typename BinLaunch>
 static int sem_bins_run(hv_volume *v, int64_t n, bool checked, const SRC &src, BinLaunch bin) {
     const HvSemParams G = sem_params(v);
-    const int idx_bits = 32 - v->local_bits;
     const int wcap = sem_wcap();
     const size_t lds_bytes = sem_fold_lds(wcap, G.nvox);
-    int rc = HV_OK;
-    HvBins B{};
-    for (int attempt = 0;; ++attempt) {
-        rc = hv_bins_ensure(v);
-        if (rc != HV_OK) return rc;
-        B = hv_bins_begin(v, idx_bits);
-        bin(B);
-        if (!checked) break;
-        rc = hv_claims_fit(v); // blocks that did not fit: grow and claim again (the bins restart from clean arrays)
-        if (rc == HV_OK) break;
-        v->bins_clean = false;
-        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-    }
-    v->bins.parity ^= 1;
-    const int32_t seq = hv_next_status_seq(v);
-    const unsigned fold_grid = hv_bins_fold_grid(v, k_semb_fold_wave<VOX, SRC>, lds_bytes); // persistent waves (hv_bins_for_each)
-    VOX *bpool = (VOX *)v->pool;
-    // task list of the big bins: [2 counters (one per parity)][tasks]; at most n / wcap bins are big
-    const int task_cap = (int)std::min<int64_t>((n / wcap + 1) * ((G.nvox + 63) / 64), 1 << 22);
+    // task list of the big bins: [2 counters (one per parity)][tasks]; made before the bin pass (hv_bins_claim)
+    const int task_cap = (int)sem_task_cap(n, G.nvox);
     const size_t task_bytes = 256 + sizeof(int4) * (size_t)task_cap;
     if (v->semb_tasks == nullptr || v->semb_tasks_bytes < task_bytes) {
-        rc = hv_ensure_buffer(v, &v->semb_tasks, &v->semb_tasks_bytes, task_bytes);
+        const int rc = hv_ensure_buffer(v, &v->semb_tasks, &v->semb_tasks_bytes, task_bytes);
         if (rc != HV_OK) return rc;
         HV_HIP(hipMemsetAsync(v->semb_tasks, 0, 256, v->stream));
     }
     int32_t *task_count = (int32_t *)v->semb_tasks;
     int4 *tasks = (int4 *)((char *)v->semb_tasks + 256);
-    const bool use_tasks = true;
-    hipLaunchKernelGGL((k_semb_fold_wave<VOX, SRC>), dim3(fold_grid), dim3(256), lds_bytes, v->stream, v->table, bpool, B, G, src, v->occ, n,
-                       v->d_status, seq, task_count, use_tasks ? tasks : (int4 *)nullptr, task_cap, wcap);
-    if (use_tasks)
-        hipLaunchKernelGGL((k_semb_fold_tasks<VOX, SRC>), dim3(1024), dim3(256), lds_bytes, v->stream, v->table, bpool, B,
-                           (const int32_t *)task_count, (const int4 *)tasks, task_cap, G, src, v->occ, n, wcap);
-    HV_HIP(hipGetLastError());
-    v->frame_counter += 1;
-    return HV_OK;
+    HvBins B{};
+    int32_t seq = 0;
+    const int rc = hv_bins_claim(v, 32 - v->local_bits, checked, bin, &B, &seq);
+    if (rc != HV_OK) return rc;
+    const unsigned fold_grid = hv_bins_fold_grid(v, k_semb_fold_wave<VOX, SRC>, lds_bytes); // persistent waves (hv_bins_for_each)
+    VOX *bpool = (VOX *)v->pool;
+    hipLaunchKernelGGL((k_semb_fold_wave<VOX, SRC>), dim3(fold_grid), dim3(256), lds_bytes, v->stream, v->table, bpool, B, G, src, v->occ,
+                       v->d_status, seq, task_count, tasks, task_cap, wcap);
+    hipLaunchKernelGGL((k_semb_fold_tasks<VOX, SRC>), dim3(1024), dim3(256), lds_bytes, v->stream, v->table, bpool, B,
+                       (const int32_t *)task_count, (const int4 *)tasks, task_cap, G, src, v->occ, n, wcap);
+    return hv_bins_folded(v);
 }
 
 template <typename VOX, typename PT>
@@ -776,41 +674,21 @@ static int sem_integrate(hv_volume *v, const PT *d_pts, int64_t n, const void *d
             return sem_bins_run<VOX>(v, n, checked, HvSemArrays<PT, HV_COLOR_F32>{d_pts, d_cols, d_cls, d_inst, d_depths}, bin);
         return sem_bins_run<VOX>(v, n, checked, HvSemArrays<PT, HV_COLOR_NONE>{d_pts, d_cols, d_cls, d_inst, d_depths}, bin);
     }
-    size_t bytes = 0;
-    HV_HIP(rocprim::radix_sort_pairs(nullptr, bytes, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in, v->sort_vals_out,
-                                     (size_t)n, 0, sem_sort_bits(v), v->stream));
-    rc = hv_ensure_buffer(v, &v->sort_tmp, &v->sort_tmp_bytes, bytes);
-    if (rc != HV_OK) return rc;
-    for (int attempt = 0;; ++attempt) {
-        hipLaunchKernelGGL(k_sem_keys<PT>, dim3(blocks), dim3(256), 0, v->stream, v->table, d_pts, n, G, v->sort_keys_in,
-                           v->sort_vals_in, valid_mask_keys);
-        if (!checked) break;
-        rc = hv_claims_fit(v); // blocks that did not fit: grow, claim again (sort keys embed table slots)
-        if (rc == HV_OK) break;
-        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-        HV_HIP(rocprim::radix_sort_pairs(nullptr, bytes, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in, v->sort_vals_out,
-                                         (size_t)n, 0, sem_sort_bits(v), v->stream));
-        rc = hv_ensure_buffer(v, &v->sort_tmp, &v->sort_tmp_bytes, bytes);
-        if (rc != HV_OK) return rc;
-    }
-    bytes = v->sort_tmp_bytes;
-    HV_HIP(rocprim::radix_sort_pairs(v->sort_tmp, bytes, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in,
-                                     v->sort_vals_out, (size_t)n, 0, sem_sort_bits(v), v->stream));
-    VOX *pool = (VOX *)v->pool;
-    if (color_kind == HV_COLOR_U8) {
-        hipLaunchKernelGGL((k_sem_reduce<VOX, PT, HV_COLOR_U8>), dim3(blocks), dim3(256), 0, v->stream, v->table, pool,
-                           v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols, d_cls, d_inst, d_depths, v->occ);
-    } else if (color_kind == HV_COLOR_F32) {
-        hipLaunchKernelGGL((k_sem_reduce<VOX, PT, HV_COLOR_F32>), dim3(blocks), dim3(256), 0, v->stream, v->table, pool,
-                           v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols, d_cls, d_inst, d_depths, v->occ);
-    } else {
-        hipLaunchKernelGGL((k_sem_reduce<VOX, PT, HV_COLOR_NONE>), dim3(blocks), dim3(256), 0, v->stream, v->table, pool,
-                           v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols, d_cls, d_inst, d_depths, v->occ);
-    }
-    hv_launch_publish_status(v); // pool occupancy for the next call's hv_capacity_gate
-    HV_HIP(hipGetLastError());
-    v->frame_counter += 1;
-    return HV_OK;
+    return hv_sort_path(
+        v, n, checked,
+        [&]() {
+            hipLaunchKernelGGL(k_sem_keys<PT>, dim3(blocks), dim3(256), 0, v->stream, v->table, d_pts, n, G, v->sort_keys_in, v->sort_vals_in,
+                               valid_mask_keys);
+        },
+        [&]() {
+#define HV_LAUNCH_REDUCE(KIND)                                                                                                             \
+    hipLaunchKernelGGL((k_sem_reduce<VOX, PT, KIND>), dim3(blocks), dim3(256), 0, v->stream, v->table, (VOX *)v->pool, v->sort_keys_out,     \
+                       v->sort_vals_out, n, G, d_pts, d_cols, d_cls, d_inst, d_depths, v->occ)
+            if (color_kind == HV_COLOR_U8) HV_LAUNCH_REDUCE(HV_COLOR_U8);
+            else if (color_kind == HV_COLOR_F32) HV_LAUNCH_REDUCE(HV_COLOR_F32);
+            else HV_LAUNCH_REDUCE(HV_COLOR_NONE);
+#undef HV_LAUNCH_REDUCE
+        });
 }
 
 // stage a host array into a dedicated slice of the volume's scratch (5 inputs -> one growing buffer)
@@ -884,12 +762,10 @@ static int sem_run_collect(hv_volume *v, const HvQuery &Q, int32_t min_count, fl
                            int32_t *class_ids, int32_t *object_ids, float *confidences, int64_t cap, int64_t *n) {
     HV_REQUIRE(v != nullptr && n != nullptr, HV_ERR_INVALID, "hv_get_voxels_semantic: null argument");
     HV_REQUIRE(hv_is_semantic(v), HV_ERR_MODE, "hv_get_voxels_semantic: volume is not a semantic grid");
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
     *n = 0;
-    if (nb == 0) return HV_OK;
+    int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const bool want = points && colors && class_ids && object_ids && confidences && cap > 0;
     double *d_pts = nullptr;
     float *d_cols = nullptr, *d_conf = nullptr;
@@ -903,28 +779,14 @@ static int sem_run_collect(hv_volume *v, const HvQuery &Q, int32_t min_count, fl
         d_obj = d_cls + cap;
         d_conf = (float *)(d_obj + cap);
     }
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    const dim3 grid((unsigned)std::min<int64_t>((nb + 3) / 4, 8192)); // a wave per block, grid-stride
     // (min_count <= 0 asks for voxels that never took a point as well: the occupancy bits cannot be used then)
     const unsigned long long *occ = min_count >= 1 ? v->occ : nullptr;
-    HV_SEM_DISPATCH(v, hipLaunchKernelGGL(k_sem_collect<VOX>, grid, dim3(256), 0, v->stream, v->table, (const VOX *)v->pool, nb, sem_params(v), Q, min_count,
-                                          min_confidence, d_pts, d_cols, d_cls, d_obj, d_conf, want ? cap : 0, occ));
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v);
-    if (rc != HV_OK) return rc;
-    *n = v->h_counters[HV_CNT_OUT];
-    if (want) {
-        const int64_t m = std::min(*n, cap);
-        if (m > 0) {
-            HV_HIP(hipMemcpyAsync(points, d_pts, 24 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipMemcpyAsync(colors, d_cols, 12 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipMemcpyAsync(class_ids, d_cls, 4 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipMemcpyAsync(object_ids, d_obj, 4 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipMemcpyAsync(confidences, d_conf, 4 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipStreamSynchronize(v->stream));
-        }
-    }
-    return HV_OK;
+    auto launch = [&]() {
+        HV_SEM_DISPATCH(v, hipLaunchKernelGGL(k_sem_collect<VOX>, dim3(hv_wave_per_block_grid(nb)), dim3(256), 0, v->stream, v->table, (const VOX *)v->pool, nb,
+                                              sem_params(v), Q, min_count, min_confidence, d_pts, d_cols, d_cls, d_obj, d_conf, want ? cap : 0, occ));
+    };
+    return hv_collect_rows(v, want ? cap : 0, n, launch,
+                           {{points, d_pts, 24}, {colors, d_cols, 12}, {class_ids, d_cls, 4}, {object_ids, d_obj, 4}, {confidences, d_conf, 4}});
 }
 
 extern "C" {
@@ -1009,10 +871,9 @@ int hv_integrate_rgbd_semantic(hv_volume *v, const float *depth, const uint8_t *
     HV_REQUIRE(npx <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_rgbd_semantic: image exceeds max_points");
     HV_HIP(hipSetDevice(v->device));
     // the frame's depth and colour planes on the device (staged on the volume's stream when they come from the host)
-    const void *d_depth = nullptr, *d_rgb = nullptr;
-    int rc = hv_stage_in(v, depth, (size_t)npx * 4, loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, rgb, (size_t)npx * 3, loc, 1, &d_rgb);
+    const void *d_depth = nullptr;
+    const uint8_t *d_rgb = nullptr;
+    int rc = hv_stage_frame(v, depth, HV_DEPTH_F32, rgb, npx, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     // label planes: staged behind each other in the output scratch when they come from the host
     const int32_t *d_cls = class_ids_image, *d_obj = object_ids_image;
@@ -1041,13 +902,13 @@ int hv_integrate_rgbd_semantic(hv_volume *v, const float *depth, const uint8_t *
         const HvUnprojectParams U = unproject_params(HV_DEPTH_F32, 1.0, height, width, intr, T_cw, min_depth, max_depth);
         auto bin = [&](const HvBins &B) {
             hipLaunchKernelGGL(k_semb_bin_frame, dim3((unsigned)((npx + HV_BIN_THREADS - 1) / HV_BIN_THREADS)), dim3(HV_BIN_THREADS), 0, v->stream, v->table, B, G, U, d_depth,
-                               (const uint8_t *)d_rgb, d_cls, d_obj, (float4 *)v->bin_rec);
+                               d_rgb, d_cls, d_obj, (float4 *)v->bin_rec);
         };
         const HvSemRecs src{(const float4 *)v->bin_rec, nullptr, d_cls != nullptr, use_depths != 0};
         HV_SEM_DISPATCH(v, return sem_bins_run<VOX>(v, npx, checked, src, bin));
     }
     // (inputs beyond the bin path's limits: unprojected rows, then the radix path)
-    rc = hv_unproject_frame(v, d_depth, HV_DEPTH_F32, 1.0, (const uint8_t *)d_rgb, height, width, intr, T_cw, min_depth, max_depth, HV_DEVICE, nullptr);
+    rc = hv_unproject_frame(v, d_depth, HV_DEPTH_F32, 1.0, d_rgb, height, width, intr, T_cw, min_depth, max_depth, HV_DEVICE, nullptr);
     if (rc != HV_OK) return rc;
     // depths = camera z of the point = the pixel's depth (…voxel_semantic_grid.py:418-424)
     const float *d_depths = use_depths ? (const float *)d_depth : nullptr;
@@ -1057,23 +918,14 @@ int hv_integrate_rgbd_semantic(hv_volume *v, const float *depth, const uint8_t *
 
 int hv_get_voxels_semantic(hv_volume *v, int32_t min_count, float min_confidence, double *points, float *colors,
                            int32_t *class_ids, int32_t *object_ids, float *confidences, int64_t cap, int64_t *n) {
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    return sem_run_collect(v, Q, min_count, min_confidence, points, colors, class_ids, object_ids, confidences, cap, n);
+    return sem_run_collect(v, hv_query_all(min_count), min_count, min_confidence, points, colors, class_ids, object_ids, confidences, cap, n);
 }
 
 int hv_get_voxels_semantic_in_bb(hv_volume *v, const double *bbox, int32_t min_count, float min_confidence, double *points,
                                  float *colors, int32_t *class_ids, int32_t *object_ids, float *confidences, int64_t cap,
                                  int64_t *n) {
     HV_REQUIRE(v != nullptr && bbox != nullptr, HV_ERR_INVALID, "hv_get_voxels_semantic_in_bb: null argument");
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 1;
-    for (int k = 0; k < 6; ++k) Q.bb[k] = bbox[k];
-    const HvSemParams G = sem_params(v);
-    HvGridParams GP{G.inv_voxel_size, G.bs, G.nvox, G.local_bits};
-    fill_key_range(Q, GP);
-    return sem_run_collect(v, Q, min_count, min_confidence, points, colors, class_ids, object_ids, confidences, cap, n);
+    return sem_run_collect(v, hv_query_in_bb(v, bbox, min_count), min_count, min_confidence, points, colors, class_ids, object_ids, confidences, cap, n);
 }
 
 int hv_get_voxels_semantic_in_frustum(hv_volume *v, const float *intr_f32, int32_t width, int32_t height, const double *T_cw,
@@ -1081,14 +933,8 @@ int hv_get_voxels_semantic_in_frustum(hv_volume *v, const float *intr_f32, int32
                                       float *colors, int32_t *class_ids, int32_t *object_ids, float *confidences, int64_t cap,
                                       int64_t *n) {
     HV_REQUIRE(v != nullptr && intr_f32 != nullptr && T_cw != nullptr, HV_ERR_INVALID, "hv_get_voxels_semantic_in_frustum: null argument");
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 2;
-    fill_frustum_query(Q, v, intr_f32, width, height, T_cw, depth_max, depth_min);
-    const HvSemParams G = sem_params(v);
-    HvGridParams GP{G.inv_voxel_size, G.bs, G.nvox, G.local_bits};
-    fill_key_range(Q, GP);
-    return sem_run_collect(v, Q, min_count, min_confidence, points, colors, class_ids, object_ids, confidences, cap, n);
+    return sem_run_collect(v, hv_query_in_frustum(v, intr_f32, width, height, T_cw, depth_max, depth_min, min_count), min_count, min_confidence, points, colors,
+                           class_ids, object_ids, confidences, cap, n);
 }
 
 static int sem_dump_blocks(hv_volume *v, int32_t *keys, int32_t *ints, float *conf, double *pos_sums, float *col_sums, int32_t *label_counts,
@@ -1100,13 +946,10 @@ static int sem_dump_blocks(hv_volume *v, int32_t *keys, int32_t *ints, float *co
     if (rc != HV_OK) return rc;
     *n_blocks = nb;
     if (nb == 0 || (!keys && !ints && !conf && !pos_sums && !col_sums && !label_counts && !labels && !log_probs && !obj_conf && !cls_conf)) return HV_OK;
-    std::vector<uint64_t> bkeys((size_t)nb);
-    HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost));
-    std::vector<std::array<int32_t, 3>> xyz((size_t)nb);
-    for (int64_t i = 0; i < nb; ++i) hv_unpack_key(bkeys[i], xyz[i][0], xyz[i][1], xyz[i][2]);
-    std::vector<int64_t> order((size_t)nb);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return xyz[a] < xyz[b]; });
+    std::vector<std::array<int32_t, 3>> xyz;
+    std::vector<int64_t> order;
+    rc = hv_blocks_in_key_order(v, nb, xyz, order);
+    if (rc != HV_OK) return rc;
     HV_SEM_DISPATCH(v, return sem_dump<VOX>(v, nb, order, xyz, keys, ints, conf, pos_sums, col_sums, label_counts, labels, log_probs, max_labels, obj_conf, cls_conf));
     return HV_OK; // (not reached)
 }

@@ -1024,11 +1024,9 @@ struct HvSegmentsCache {
 };
 
 template <typename VOX> int sem_launch_segment_op(hv_volume *v, int op, int32_t a, int32_t b, float fa) {
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
-    if (nb == 0) return HV_OK;
+    const int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const int64_t total = nb * sem_params(v).nvox;
     hipLaunchKernelGGL(k_sem_segment_op<VOX>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (VOX *)v->pool,
                        total, op, a, b, fa, (op == 0 && b < 0) ? nullptr : v->occ, // (merging INTO the voxels without an object id reaches empty ones too)
@@ -1043,7 +1041,7 @@ void hv_segments_cache_free(void *cache) { delete static_cast<HvSegmentsCache *>
 
 int hv_sem_carve(hv_volume *v, const HvQuery &Q, const float *d_depth, int64_t nb) {
     const HvSemParams G = sem_params(v);
-    const dim3 grid((unsigned)std::min<int64_t>((nb + 3) / 4, 8192)); // a wave per block, grid-stride
+    const dim3 grid(hv_wave_per_block_grid(nb));
     HV_SEM_DISPATCH(v, hipLaunchKernelGGL(k_sem_carve<VOX>, grid, dim3(256), 0, v->stream, v->table, (VOX *)v->pool, nb, G, Q, d_depth, v->occ));
     HV_HIP(hipGetLastError());
     return HV_OK;
@@ -1055,21 +1053,14 @@ int hv_sem_segment_op(hv_volume *v, int op, int32_t a, int32_t b, float fa) {
 }
 
 int hv_sem_size(hv_volume *v, int64_t *n) {
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
     *n = 0;
-    if (nb == 0) return HV_OK;
+    const int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const int nvox = sem_params(v).nvox;
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    const dim3 grid((unsigned)std::min<int64_t>((nb + 3) / 4, 8192));
-    HV_SEM_DISPATCH(v, hipLaunchKernelGGL(k_sem_count_nonempty<VOX>, grid, dim3(256), 0, v->stream, v->table, (const VOX *)v->pool, nb, nvox, v->occ));
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v);
-    if (rc != HV_OK) return rc;
-    *n = v->h_counters[HV_CNT_OUT];
-    return HV_OK;
+    return hv_collect_rows(v, 0, n, [&]() {
+        HV_SEM_DISPATCH(v, hipLaunchKernelGGL(k_sem_count_nonempty<VOX>, dim3(hv_wave_per_block_grid(nb)), dim3(256), 0, v->stream, v->table, (const VOX *)v->pool, nb, nvox, v->occ));
+    }, {});
 }
 
 extern "C" {
@@ -1236,17 +1227,7 @@ int hv_assoc_vote(hv_volume *v, const float *intr_f32, int32_t width, int32_t he
     A.pending_cap = (int32_t)std::min<int64_t>(S.pending_cap, INT32_MAX);
     v->assoc_pending_cap = A.pending_cap;
     { // (always: nb >= 1, and the kernel scans the image as well)
-        HvQuery Q;
-        memset(&Q, 0, sizeof(Q));
-        Q.kind = 2;
-        Q.min_count = 1;
-        fill_frustum_query(Q, v, intr_f32, width, height, T_cw, depth_max, depth_min);
-        HvGridParams GP{};
-        GP.inv_voxel_size = G.inv_voxel_size;
-        GP.bs = G.bs;
-        GP.nvox = G.nvox;
-        GP.local_bits = G.local_bits;
-        fill_key_range(Q, GP);
+        const HvQuery Q = hv_query_in_frustum(v, intr_f32, width, height, T_cw, depth_max, depth_min, 1);
         // (four blocks per wave, one per 16-lane group, was measured in round 5 - profiles/r05/README.md: +2-3 % at 2 mm, -11 % at 1 cm - and dropped)
         const dim3 grid((unsigned)std::min<int64_t>((nb + 3) / 4, 4096)); // persistent: 16 workgroups per CU
         // the probabilistic payload's copy of the record takes 149 registers: three workgroups per CU, nothing spilled (measured
@@ -1501,7 +1482,7 @@ int hv_object_segments_compute(hv_volume *v, int32_t min_count, float min_confid
     if (rc != HV_OK) return rc;
     if (nb == 0) return HV_OK;
     const int nvox = sem_params(v).nvox;
-    const dim3 grid((unsigned)std::min<int64_t>((nb + 3) / 4, 8192));
+    const dim3 grid(hv_wave_per_block_grid(nb));
     // pass 1: count; pass 2: emit (object id, voxel index) keys
     int64_t m = 0;
     for (int pass = 0; pass < 2; ++pass) {

@@ -21,10 +21,8 @@
 #include "hv_common.h"
 #include "hv_query.h"
 #include "hv_bins.h"
+#include "hv_sort_path.h"
 #include "hv_unproject.h"
-#include <rocprim/device/device_radix_sort.hpp>
-
-static constexpr uint32_t HV_SORT_SENTINEL = 0xFFFFFFFFu;
 
 // (HvPointKey, hv_point_key and hv_point_keyable - a point's voxel - live in hv_query.h: hv_lookup.hip keys its points with them)
 
@@ -305,19 +303,34 @@ __global__ __launch_bounds__(HV_BIN_THREADS) void k_vgb_bin(HvTable table, HvBin
 // runs at 89.9 us per 640x480 frame against 45.4 us for the four launches of the point-ordered bucket path: 2.1 M scattered
 // float atomics per frame are slower than sorting 12 points per block in LDS.  Taken out again.)
 // update_voxel_direct (voxel_block_grid.hpp:524-614) folded over the sorted entries s[0 .. m) of one block: the head of every voxel
-// run, one per `stride` threads
+// run, one per `stride` threads.  `point(j, r)` yields position and colour of sorted entry j: from the bin pass's records in global
+// memory, or from the rows a wave staged in LDS at the entries' ranks.
 template <int REC>
-__device__ __forceinline__ void hv_vgb_fold_sorted(const uint32_t *s, int m, int first, int stride, HvVoxel *__restrict__ block,
-                                                   const void *__restrict__ rec, const float *lut) {
-    for (int e = first; e < m; e += stride) {
-        const uint32_t lidx = s[e] >> HV_VGB_IDX_BITS;
-        if (e > 0 && (s[e - 1] >> HV_VGB_IDX_BITS) == lidx) continue; // not the head of its voxel's run
+struct HvVgbRecs {
+    const uint32_t *s;
+    const void *__restrict__ rec;
+    const float *lut;
+    __device__ __forceinline__ void operator()(int j, float r[6]) const {
+        hv_rec_fetch<REC>(rec, (int64_t)(s[j] & ((1u << HV_VGB_IDX_BITS) - 1u)), lut, r);
+    }
+};
+template <int REC>
+struct HvVgbStaged {
+    const float *stage; // 6 floats per sorted entry
+    __device__ __forceinline__ void operator()(int j, float r[6]) const {
+#pragma unroll
+        for (int k = 0; k < (REC != HV_REC_NONE ? 6 : 3); ++k) r[k] = stage[j * 6 + k];
+    }
+};
+template <int REC, typename SRC>
+__device__ __forceinline__ void hv_vgb_fold_sorted(const uint32_t *s, int m, int first, int stride, HvVoxel *__restrict__ block, const SRC &point) {
+    hv_bins_for_each_run(s, m, HV_VGB_IDX_BITS, first, stride, [&](int e, uint32_t lidx) {
         HvVoxel *vx = block + lidx;
         HvVoxel acc = *vx;
         int j = e;
-        do {
+        do { // in point order
             float r[6];
-            hv_rec_fetch<REC>(rec, (int64_t)(s[j] & ((1u << HV_VGB_IDX_BITS) - 1u)), lut, r);
+            point(j, r);
             acc.pos[0] += r[0];
             acc.pos[1] += r[1];
             acc.pos[2] += r[2];
@@ -330,7 +343,7 @@ __device__ __forceinline__ void hv_vgb_fold_sorted(const uint32_t *s, int m, int
             ++j;
         } while (j < m && (s[j] >> HV_VGB_IDX_BITS) == lidx);
         *vx = acc;
-    }
+    });
 }
 
 __device__ __forceinline__ void hv_vgb_bitonic(uint32_t *s, int m2) { // ascending, m2 a power of two, all threads of the block
@@ -365,14 +378,10 @@ __global__ __launch_bounds__(256) void k_vgb_fold_wave(HvTable table, HvVoxel *_
     __shared__ float s_lut[256];
     hv_rec_lut<REC>(s_lut);
     const HvBinLists L = hv_bins_lists(B);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        hv_bins_clear_next(B);                            // the next call's list lengths
-        status->pad = table.counters[HV_CNT_OUT2];        // largest bin of this frame
-        table.counters[HV_CNT_OUT2] = 0;
-        hv_publish_status(table, status, status_seq);
-    }
+    hv_bins_fold_prologue(table, B, status, status_seq, &status->pad); // (pad: the largest bin of this frame)
     const int wave = threadIdx.x >> 6, lane = hv_lane_id();
     uint32_t *s = s_all[wave];
+    const HvVgbRecs<REC> recs{s, rec, s_lut};
     hv_bins_for_each(table, B, L, blockIdx.x * 4 + wave, gridDim.x * 4, [&](const HvBinHeader &h) {
         const int32_t slot = h.slot, nb = h.nb, idx = h.idx;
         const uint32_t head = h.head; // (a bin holds ~24 points: for most bins the header's 64 entries are all of them)
@@ -441,30 +450,11 @@ __global__ __launch_bounds__(256) void k_vgb_fold_wave(HvTable table, HvVoxel *_
                 }
                 asm volatile("" ::"v"(warm)); // (the voxel lines have arrived)
                 hv_wave_lds_sync();
-                for (int e = lane; e < nb; e += HV_WAVE) {
-                    const uint32_t lidx = s[e] >> HV_VGB_IDX_BITS;
-                    if (e > 0 && (s[e - 1] >> HV_VGB_IDX_BITS) == lidx) continue; // not the head of its voxel's run
-                    HvVoxel *vx = block + lidx;
-                    HvVoxel acc = *vx;
-                    int j = e;
-                    do { // update_voxel_direct, in point order
-                        acc.pos[0] += stage[j * 6 + 0];
-                        acc.pos[1] += stage[j * 6 + 1];
-                        acc.pos[2] += stage[j * 6 + 2];
-                        if (REC != HV_REC_NONE) {
-                            acc.col[0] += stage[j * 6 + 3];
-                            acc.col[1] += stage[j * 6 + 4];
-                            acc.col[2] += stage[j * 6 + 5];
-                        }
-                        acc.count = acc.count == 0 ? 1 : acc.count + 1;
-                        ++j;
-                    } while (j < nb && (s[j] >> HV_VGB_IDX_BITS) == lidx);
-                    *vx = acc;
-                }
+                hv_vgb_fold_sorted<REC>(s, nb, lane, HV_WAVE, block, HvVgbStaged<REC>{stage});
                 return;
             }
             hv_wave_lds_sync();
-            hv_vgb_fold_sorted<REC>(s, nb, lane, HV_WAVE, block, rec, s_lut);
+            hv_vgb_fold_sorted<REC>(s, nb, lane, HV_WAVE, block, recs);
             return;
         }
         if (nb <= HV_VGB_WCAP) {
@@ -473,29 +463,19 @@ __global__ __launch_bounds__(256) void k_vgb_fold_wave(HvTable table, HvVoxel *_
             for (int e = lane; e < m2; e += HV_WAVE) s[e] = e < nb ? hv_bins_entry(B, slot, e) : 0xFFFFFFFFu;
             hv_wave_lds_sync();
             hv_vgb_bitonic_wave(s, m2);
-            hv_vgb_fold_sorted<REC>(s, nb, lane, HV_WAVE, block, rec, s_lut);
+            hv_vgb_fold_sorted<REC>(s, nb, lane, HV_WAVE, block, recs);
             return;
         }
         for (int64_t w = 0; w < n_points; w += HV_VGB_WCAP) { // point-index windows, ascending: a voxel's points stay in order
             hv_wave_lds_sync();
-            int m = 0;
-            for (int e0 = 0; e0 < nb; e0 += HV_WAVE) {
-                const int e = e0 + lane;
-                const uint32_t ent = e < nb ? hv_bins_entry(B, slot, e) : 0u;
-                const int64_t p = ent & ((1u << HV_VGB_IDX_BITS) - 1u);
-                const bool in = e < nb && p >= w && p < w + HV_VGB_WCAP;
-                const unsigned long long bm = __ballot(in);
-                const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-                if (in) s[m + __popcll(bm & lt)] = ent;
-                m += __popcll(bm);
-            }
-            if (m == 0) continue;
+            int m;
+            if (!hv_bins_gather<1>(B, slot, nb, HV_VGB_IDX_BITS, 0u, 0xFFFFFFFFu, w, HV_VGB_WCAP, s, m) || m == 0) continue; // (a window never overflows)
             int m2 = HV_WAVE;
             while (m2 < m) m2 <<= 1;
             for (int e = m + lane; e < m2; e += HV_WAVE) s[e] = 0xFFFFFFFFu;
             hv_wave_lds_sync();
             hv_vgb_bitonic_wave(s, m2);
-            hv_vgb_fold_sorted<REC>(s, m, lane, HV_WAVE, block, rec, s_lut);
+            hv_vgb_fold_sorted<REC>(s, m, lane, HV_WAVE, block, recs);
         }
     });
 }
@@ -508,12 +488,8 @@ __global__ __launch_bounds__(256) void k_vgb_fold(HvTable table, HvVoxel *__rest
     __shared__ int s_m;
     hv_rec_lut<REC>(s_lut);
     const HvBinLists L = hv_bins_lists(B);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        hv_bins_clear_next(B);                            // the next call's list lengths
-        status->pad = table.counters[HV_CNT_OUT2];        // largest bin of this frame
-        table.counters[HV_CNT_OUT2] = 0;
-        hv_publish_status(table, status, status_seq);
-    }
+    const HvVgbRecs<REC> recs{s, rec, s_lut};
+    hv_bins_fold_prologue(table, B, status, status_seq, &status->pad); // (pad: the largest bin of this frame)
     for (int t = blockIdx.x; t < L.total; t += gridDim.x) {
         const int32_t slot = hv_bins_touched(B, L, t);
         const int32_t nb = B.cnt[slot];
@@ -528,7 +504,7 @@ __global__ __launch_bounds__(256) void k_vgb_fold(HvTable table, HvVoxel *__rest
             for (int e = threadIdx.x; e < m2; e += blockDim.x) s[e] = e < nb ? hv_bins_entry(B, slot, e) : 0xFFFFFFFFu;
             __syncthreads();
             hv_vgb_bitonic(s, m2);
-            hv_vgb_fold_sorted<REC>(s, nb, threadIdx.x, blockDim.x, block, rec, s_lut);
+            hv_vgb_fold_sorted<REC>(s, nb, threadIdx.x, blockDim.x, block, recs);
             continue;
         }
         // a bin larger than the LDS window: fold the points of index window [w, w + CAP) at a time, windows ascending - a
@@ -550,7 +526,7 @@ __global__ __launch_bounds__(256) void k_vgb_fold(HvTable table, HvVoxel *__rest
             for (int e = m + threadIdx.x; e < m2; e += blockDim.x) s[e] = 0xFFFFFFFFu;
             __syncthreads();
             hv_vgb_bitonic(s, m2);
-            hv_vgb_fold_sorted<REC>(s, m, threadIdx.x, blockDim.x, block, rec, s_lut);
+            hv_vgb_fold_sorted<REC>(s, m, threadIdx.x, blockDim.x, block, recs);
         }
     }
 }
@@ -648,160 +624,10 @@ __global__ __launch_bounds__(256) void k_vg_probe_keys(const float *__restrict__
 }
 
 
-// ---- filter_shadow_points (pyslam/utilities/depth.py:103-146) -----------------------------------
-// |d(r,c) - d(r-dy,c)| and |d(r,c) - d(r,c-dx)|; threshold = 3 * 1.4826 * median(positive deltas)
-// (float32 arithmetic, as numpy evaluates it for a float32 image); both endpoints of a large jump
-// are replaced by fill_value.  The global median is an exact radix SELECT on the deltas' bit patterns (order-preserving for
-// positive floats): three histogram passes over the image (12 + 12 + 8 bits), each followed by a one-workgroup pick of the
-// bin(s) that hold the two middle ranks; the deltas are recomputed in every pass (two subtractions) instead of being stored,
-// and the threshold stays in device memory for the mask kernel - no sort, no host round trip.  (Round 2: the deltas were
-// written out, radix-sorted (19 launches) and the middle elements copied to the host - 0.33 ms of a 1.2 ms semantic keyframe,
-// profiles/r03/kernel_stats_semantic.csv.)
-// state words: [0] number of positive deltas, [1] [2] remaining ranks of the two middle elements, [3] [4] their key prefixes,
-// [5] the threshold (float bits)
-enum { HV_SH_N = 0, HV_SH_RANK0 = 1, HV_SH_RANK1 = 2, HV_SH_PRE0 = 3, HV_SH_PRE1 = 4, HV_SH_THR = 5, HV_SH_TICKET = 8 /* + pass */, HV_SH_WORDS = 16 };
-static constexpr int HV_SH_BINS01 = 4096, HV_SH_BINS2 = 256;
-static constexpr int HV_SH_GRID = 256; // workgroups of a histogram pass
-static constexpr int HV_SH_HIST_WORDS = HV_SH_BINS01 + 2 * HV_SH_BINS01 + 2 * HV_SH_BINS2;
-
-// one workgroup: the bin holding each of the two ranks, the rank inside it.  (Round 5 tried the pick as the tail of the histogram
-// launch - run by its last workgroup to finish, the histogram read back with L2-level loads -: three launches less per keyframe and
-// 18 us MORE, 69.6 us for the three passes against 51.5: the 4096 bypassing loads of one workgroup cost more than a 5 us launch.)
-template <int PASS>
-__device__ __forceinline__ void hv_shadow_pick(const uint32_t *__restrict__ hist, uint32_t *__restrict__ state) {
-    constexpr int BINS = PASS == 2 ? HV_SH_BINS2 : HV_SH_BINS01;
-    constexpr int PER = BINS / 256;
-    constexpr int BITS = PASS == 2 ? 8 : 12;
-    __shared__ uint32_t s_scan[256];
-    __shared__ uint32_t s_rank[2];
-    const int t = threadIdx.x;
-    for (int target = 0; target < 2; ++target) {
-        const uint32_t *h = hist + (PASS == 0 ? 0 : target * BINS);
-        uint32_t local[PER], sum = 0u;
-#pragma unroll
-        for (int k = 0; k < PER; ++k) {
-            local[k] = h[t * PER + k];
-            sum += local[k];
-        }
-        s_scan[t] = sum;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) { // Hillis-Steele inclusive scan
-            const uint32_t addv = t >= off ? s_scan[t - off] : 0u;
-            __syncthreads();
-            s_scan[t] += addv;
-            __syncthreads();
-        }
-        if (PASS == 0 && t == 0) {
-            const uint32_t n = s_scan[255];
-            if (target == 0) state[HV_SH_N] = n;
-            s_rank[target] = n ? (target == 0 ? (n - 1u) / 2u : n / 2u) : 0u; // ranks of np.median's two middle elements
-        }
-        if (PASS > 0 && t == 0) s_rank[target] = state[HV_SH_RANK0 + target];
-        __syncthreads();
-        const uint32_t rank = s_rank[target];
-        const uint32_t incl = s_scan[t];
-        uint32_t before = incl - sum;
-        if (rank >= before && rank < incl) { // exactly one thread when the rank exists
-#pragma unroll
-            for (int k = 0; k < PER; ++k) {
-                if (rank < before + local[k]) {
-                    const uint32_t prefix = PASS == 0 ? 0u : state[HV_SH_PRE0 + target];
-                    state[HV_SH_PRE0 + target] = (prefix << BITS) | (uint32_t)(t * PER + k);
-                    state[HV_SH_RANK0 + target] = rank - before;
-                    break;
-                }
-                before += local[k];
-            }
-        }
-        __syncthreads();
-    }
-    if (PASS == 2 && t == 0) {
-        float thr = __uint_as_float(0x7fc00000u); // np.median of an empty array -> nan -> nothing is masked
-        if (state[HV_SH_N]) {
-            const float a = __uint_as_float(state[HV_SH_PRE0]), b = __uint_as_float(state[HV_SH_PRE1]);
-            const float mad = state[HV_SH_PRE0] == state[HV_SH_PRE1] ? a : (a + b) * 0.5f; // np.median -> np.mean of the two middle float32
-            const float sigma = 1.4826f * mad;
-            thr = 3.0f * sigma;
-        }
-        state[HV_SH_THR] = __float_as_uint(thr);
-    }
-}
-
-template <int PASS>
-__global__ __launch_bounds__(256) void k_shadow_hist(const float *__restrict__ depth, int H, int W, int dx, int dy,
-                                                      uint32_t *__restrict__ state, uint32_t *__restrict__ hist) {
-    constexpr int BINS = PASS == 2 ? HV_SH_BINS2 : HV_SH_BINS01;
-    constexpr int NB = (PASS == 0 ? 1 : 2) * BINS;
-    __shared__ uint32_t s_h[NB];
-    for (int i = threadIdx.x; i < NB; i += 256) s_h[i] = 0u;
-    __syncthreads();
-    const uint32_t p0 = PASS > 0 ? state[HV_SH_PRE0] : 0u, p1 = PASS > 0 ? state[HV_SH_PRE1] : 0u;
-    auto add = [&](float v) {
-        if (!(v > 0.0f)) return; // NaN compares false, like numpy's `delta_values > 0`
-        const uint32_t key = __float_as_uint(v);
-        if (PASS == 0) {
-            atomicAdd(&s_h[key >> 20], 1u);
-        } else if (PASS == 1) {
-            if ((key >> 20) == p0) atomicAdd(&s_h[(key >> 8) & 0xfffu], 1u);
-            if ((key >> 20) == p1) atomicAdd(&s_h[BINS + ((key >> 8) & 0xfffu)], 1u);
-        } else {
-            if ((key >> 8) == p0) atomicAdd(&s_h[key & 0xffu], 1u);
-            if ((key >> 8) == p1) atomicAdd(&s_h[BINS + (key & 0xffu)], 1u);
-        }
-    };
-    const int npx = H * W;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < npx; i += gridDim.x * 256) {
-        const int r = i / W, c = i - r * W;
-        const float d = depth[i];
-        if (dy > 0 && r >= dy) add(fabsf(d - depth[i - dy * W]));
-        if (dx > 0 && c >= dx) add(fabsf(d - depth[i - dx]));
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NB; i += 256)
-        if (s_h[i]) atomicAdd(&hist[i], s_h[i]);
-}
-
-template <int PASS>
-__global__ __launch_bounds__(256) void k_shadow_pick(const uint32_t *__restrict__ hist, uint32_t *__restrict__ state) {
-    hv_shadow_pick<PASS>(hist, state);
-}
-
-__global__ __launch_bounds__(256) void k_shadow_mask(const float *__restrict__ depth, int H, int W, int dx, int dy,
-                                                      const uint32_t *__restrict__ state, float fill, float *__restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)H * W) return;
-    const float thr = __uint_as_float(state[HV_SH_THR]);
-    const int r = (int)(i / W), c = (int)(i % W);
-    const float d = depth[i];
-    bool m = false;
-    if (dy > 0) {
-        if (r >= dy) m |= fabsf(d - depth[i - (int64_t)dy * W]) > thr;
-        if (r + dy < H) m |= fabsf(depth[i + (int64_t)dy * W] - d) > thr;
-    }
-    if (dx > 0) {
-        if (c >= dx) m |= fabsf(d - depth[i - dx]) > thr;
-        if (c + dx < W) m |= fabsf(depth[i + dx] - d) > thr;
-    }
-    out[i] = m ? fill : d;
-}
-
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
 // (grid_params: hv_query.h)
-
-static int sort_bits(const hv_volume *v) {
-    int slot_bits = 0;
-    while ((1ull << slot_bits) < v->table_capacity) slot_bits++;
-    return std::min(32, slot_bits + v->local_bits + 1);
-}
-
-static int ensure_sort_tmp(hv_volume *v, int64_t n) {
-    size_t bytes = 0;
-    HV_HIP(rocprim::radix_sort_pairs(nullptr, bytes, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in,
-                                     v->sort_vals_out, (size_t)n, 0, sort_bits(v), v->stream));
-    return hv_ensure_buffer(v, &v->sort_tmp, &v->sort_tmp_bytes, bytes);
-}
 
 // keys -> group -> ordered reduce over device-resident points/colours.  Single frames (n < 2^20 points) take the bin path
 // (2 launches), larger inputs - the batched replay - the device-wide radix sort; HV_VG_PATH=sort forces the latter (A/B, tests).
@@ -829,10 +655,8 @@ static int integrate_device_points(hv_volume *v, const float *d_pts, int64_t n, 
         if (rc != HV_OK) return rc;
         hv_profile_begin(v); // measurement hook: the two launches of one integrate call
         HvBins B{};
-        for (int attempt = 0;; ++attempt) {
-            rc = hv_bins_ensure(v);
-            if (rc != HV_OK) return rc;
-            B = hv_bins_begin(v, HV_VGB_IDX_BITS);
+        int32_t seq = 0;
+        rc = hv_bins_claim(v, HV_VGB_IDX_BITS, checked, [&](const HvBins &B) {
 #define HV_LAUNCH_BIN(FUSED, REC)                                                                                      \
     hipLaunchKernelGGL((k_vgb_bin<FUSED, REC>), dim3((unsigned)((n + HV_BIN_THREADS - 1) / HV_BIN_THREADS)), dim3(HV_BIN_THREADS), 0, v->stream, v->table, B, d_pts, d_pts64, d_cols, n, G, \
                        d_valid, frame ? frame->U : HvUnprojectParams{}, frame ? frame->d_depth : (const void *)nullptr,  \
@@ -842,14 +666,8 @@ static int integrate_device_points(hv_volume *v, const float *d_pts, int64_t n, 
             else if (rec_kind == HV_REC_F32) HV_LAUNCH_BIN(false, HV_REC_F32);
             else HV_LAUNCH_BIN(false, HV_REC_NONE);
 #undef HV_LAUNCH_BIN
-            if (!checked) break;
-            rc = hv_claims_fit(v); // blocks that did not fit: grow and claim again (the bins restart from clean arrays)
-            if (rc == HV_OK) break;
-            v->bins_clean = false; // counts / lists of the aborted claim pass are void (and the table may have moved)
-            if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-        }
-        v->bins.parity ^= 1;
-        const int32_t seq = hv_next_status_seq(v);
+        }, &B, &seq);
+        if (rc != HV_OK) return rc;
         // one wave per bin, or - when the last finished frame had bins beyond a wave's LDS window (coarse voxels, very
         // close surfaces) - one workgroup per bin; both are exact for any bin size
         const bool big = v->h_status->pad > HV_VGB_WCAP;
@@ -870,57 +688,40 @@ static int integrate_device_points(hv_volume *v, const float *d_pts, int64_t n, 
         else HV_LAUNCH_FOLD(HV_REC_NONE);
 #undef HV_LAUNCH_FOLD
         hv_profile_end(v, n);
-        HV_HIP(hipGetLastError());
-        v->frame_counter += 1;
-        return HV_OK;
+        return hv_bins_folded(v);
     }
     if (frame) { // radix path on a frame: unproject first (validity flags go straight into the sort-key input buffer)
         hv_launch_unproject(v->stream, n, frame->d_depth, frame->d_rgb, frame->U, (float *)d_pts, (float *)d_cols, v->sort_keys_out);
         d_valid = v->sort_keys_out;
     }
-    rc = ensure_sort_tmp(v, n);
-    if (rc != HV_OK) return rc;
     hv_profile_begin(v); // measurement hook: keys + sort + ordered reduce of one integrate call
-    for (int attempt = 0;; ++attempt) {
-        hipLaunchKernelGGL(k_vg_keys, dim3(blocks), dim3(256), 0, v->stream, v->table, (float *)d_pts, n, G, v->sort_keys_in,
-                           v->sort_vals_in, d_valid, d_pts64);
-        if (!checked) break;
-        rc = hv_claims_fit(v); // blocks that did not fit: grow, claim again (sort keys embed table slots)
-        if (rc == HV_OK) break;
-        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-        rc = ensure_sort_tmp(v, n);
-        if (rc != HV_OK) return rc;
-    }
-    size_t tmp_bytes = v->sort_tmp_bytes;
-    HV_HIP(rocprim::radix_sort_pairs(v->sort_tmp, tmp_bytes, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in,
-                                     v->sort_vals_out, (size_t)n, 0, sort_bits(v), v->stream));
-    if (color_kind == HV_COLOR_U8) {
-        hipLaunchKernelGGL(k_vg_reduce<HV_COLOR_U8>, dim3(blocks), dim3(256), 0, v->stream, v->table,
-                           (HvVoxel *)v->pool, v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols);
-    } else if (color_kind == HV_COLOR_F32) {
-        hipLaunchKernelGGL(k_vg_reduce<HV_COLOR_F32>, dim3(blocks), dim3(256), 0, v->stream, v->table,
-                           (HvVoxel *)v->pool, v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols);
-    } else {
-        hipLaunchKernelGGL(k_vg_reduce<HV_COLOR_NONE>, dim3(blocks), dim3(256), 0, v->stream, v->table,
-                           (HvVoxel *)v->pool, v->sort_keys_out, v->sort_vals_out, n, G, d_pts, d_cols);
-    }
-    hv_launch_publish_status(v); // pool occupancy for the next call's hv_capacity_gate
-    hv_profile_end(v, n);
-    HV_HIP(hipGetLastError());
-    v->frame_counter += 1;
-    return HV_OK;
+    rc = hv_sort_path(
+        v, n, checked,
+        [&]() {
+            hipLaunchKernelGGL(k_vg_keys, dim3(blocks), dim3(256), 0, v->stream, v->table, (float *)d_pts, n, G, v->sort_keys_in, v->sort_vals_in,
+                               d_valid, d_pts64);
+        },
+        [&]() {
+#define HV_LAUNCH_REDUCE(KIND)                                                                                                                \
+    hipLaunchKernelGGL(k_vg_reduce<KIND>, dim3(blocks), dim3(256), 0, v->stream, v->table, (HvVoxel *)v->pool, v->sort_keys_out, v->sort_vals_out, \
+                       n, G, d_pts, d_cols)
+            if (color_kind == HV_COLOR_U8) HV_LAUNCH_REDUCE(HV_COLOR_U8);
+            else if (color_kind == HV_COLOR_F32) HV_LAUNCH_REDUCE(HV_COLOR_F32);
+            else HV_LAUNCH_REDUCE(HV_COLOR_NONE);
+#undef HV_LAUNCH_REDUCE
+        });
+    if (rc == HV_OK) hv_profile_end(v, n);
+    return rc;
 }
 
 static int run_collect(hv_volume *v, const HvQuery &Q, float *points, float *colors, int64_t cap, int64_t *n,
                        int32_t loc) {
     HV_REQUIRE(n != nullptr, HV_ERR_INVALID, "get_voxels: null count pointer");
     HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID, HV_ERR_MODE, "get_voxels: volume is not in VOXEL_GRID mode");
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
     *n = 0;
-    if (nb == 0) return HV_OK;
+    int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const HvGridParams G = grid_params(v);
     const int64_t total = nb * G.nvox;
     const bool want = points != nullptr && colors != nullptr && cap > 0;
@@ -938,71 +739,50 @@ static int run_collect(hv_volume *v, const HvQuery &Q, float *points, float *col
             d_cols = (float *)v->out_b;
         }
     }
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    hipLaunchKernelGGL(k_vg_collect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const HvVoxel *)v->pool, nb, G, Q, d_pts, d_cols, want ? cap : 0);
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v);
+    auto launch = [&]() {
+        hipLaunchKernelGGL(k_vg_collect, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
+                           (const HvVoxel *)v->pool, nb, G, Q, d_pts, d_cols, want ? cap : 0);
+    };
+    if (want && loc == HV_HOST) return hv_collect_rows(v, cap, n, launch, {{points, d_pts, 12}, {colors, d_cols, 12}});
+    return hv_collect_rows(v, 0, n, launch, {});
+}
+
+// One body for the float32 and the float64 points of integrate(points, colors): the doubles are keyed as doubles, and the key kernel
+// leaves the float32 narrowing the voxel sums take in scratch_points.
+static int integrate_points(hv_volume *v, const char *who, const void *points, bool f64, int64_t n, const void *colors, int32_t color_dtype,
+                            int32_t loc) {
+    HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "%s: null volume", who);
+    HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID, HV_ERR_MODE, "%s: volume is not in VOXEL_GRID mode", who);
+    if (n == 0) return HV_OK; // integrate_raw: `if (num_points == 0) return;`
+    HV_REQUIRE(points != nullptr && n > 0, HV_ERR_INVALID, "points must be a contiguous Nx3 array");
+    HV_REQUIRE(color_dtype == HV_COLOR_NONE || color_dtype == HV_COLOR_U8 || color_dtype == HV_COLOR_F32,
+               HV_ERR_INVALID, "Colors must be uint8 or float32");
+    HV_REQUIRE(color_dtype == HV_COLOR_NONE || colors != nullptr, HV_ERR_INVALID,
+               "points and colors must have the same size");
+    HV_REQUIRE(n <= v->cfg.max_points, HV_ERR_CAPACITY, "%s: %lld points exceed max_points=%lld", who, (long long)n,
+               (long long)v->cfg.max_points);
+    HV_HIP(hipSetDevice(v->device));
+    const void *d_pts = nullptr, *d_cols = nullptr;
+    int rc = hv_stage_in(v, points, (f64 ? sizeof(double) : sizeof(float)) * 3 * (size_t)n, loc, 0, &d_pts);
     if (rc != HV_OK) return rc;
-    *n = v->h_counters[HV_CNT_OUT];
-    if (want && loc == HV_HOST) {
-        const int64_t m = std::min(*n, cap);
-        if (m > 0) {
-            HV_HIP(hipMemcpyAsync(points, d_pts, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipMemcpyAsync(colors, d_cols, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, v->stream));
-            HV_HIP(hipStreamSynchronize(v->stream));
-        }
+    if (color_dtype != HV_COLOR_NONE) {
+        rc = hv_stage_in(v, colors, (color_dtype == HV_COLOR_U8 ? 1 : 4) * 3 * (size_t)n, loc, 1, &d_cols);
+        if (rc != HV_OK) return rc;
     }
-    return HV_OK;
+    if (f64) return integrate_device_points(v, v->scratch_points, n, d_cols, color_dtype, nullptr, nullptr, (const double *)d_pts);
+    return integrate_device_points(v, (const float *)d_pts, n, d_cols, color_dtype, nullptr);
 }
 
 extern "C" {
 
 int hv_integrate_points(hv_volume *v, const float *points, int64_t n, const void *colors, int32_t color_dtype,
                         int32_t loc) {
-    HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "hv_integrate_points: null volume");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID, HV_ERR_MODE, "hv_integrate_points: volume is not in VOXEL_GRID mode");
-    if (n == 0) return HV_OK; // integrate_raw: `if (num_points == 0) return;`
-    HV_REQUIRE(points != nullptr && n > 0, HV_ERR_INVALID, "points must be a contiguous Nx3 array");
-    HV_REQUIRE(color_dtype == HV_COLOR_NONE || color_dtype == HV_COLOR_U8 || color_dtype == HV_COLOR_F32,
-               HV_ERR_INVALID, "Colors must be uint8 or float32");
-    HV_REQUIRE(color_dtype == HV_COLOR_NONE || colors != nullptr, HV_ERR_INVALID,
-               "points and colors must have the same size");
-    HV_REQUIRE(n <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_points: %lld points exceed max_points=%lld",
-               (long long)n, (long long)v->cfg.max_points);
-    HV_HIP(hipSetDevice(v->device));
-    const void *d_pts = nullptr, *d_cols = nullptr;
-    int rc = hv_stage_in(v, points, sizeof(float) * 3 * (size_t)n, loc, 0, &d_pts);
-    if (rc != HV_OK) return rc;
-    if (color_dtype != HV_COLOR_NONE) {
-        rc = hv_stage_in(v, colors, (color_dtype == HV_COLOR_U8 ? 1 : 4) * 3 * (size_t)n, loc, 1, &d_cols);
-        if (rc != HV_OK) return rc;
-    }
-    return integrate_device_points(v, (const float *)d_pts, n, d_cols, color_dtype, nullptr);
+    return integrate_points(v, "hv_integrate_points", points, false, n, colors, color_dtype, loc);
 }
 
 int hv_integrate_points_f64(hv_volume *v, const double *points, int64_t n, const void *colors, int32_t color_dtype,
                             int32_t loc) {
-    HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "hv_integrate_points_f64: null volume");
-    HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID, HV_ERR_MODE, "hv_integrate_points_f64: volume is not in VOXEL_GRID mode");
-    if (n == 0) return HV_OK; // integrate_raw: `if (num_points == 0) return;`
-    HV_REQUIRE(points != nullptr && n > 0, HV_ERR_INVALID, "points must be a contiguous Nx3 array");
-    HV_REQUIRE(color_dtype == HV_COLOR_NONE || color_dtype == HV_COLOR_U8 || color_dtype == HV_COLOR_F32,
-               HV_ERR_INVALID, "Colors must be uint8 or float32");
-    HV_REQUIRE(color_dtype == HV_COLOR_NONE || colors != nullptr, HV_ERR_INVALID,
-               "points and colors must have the same size");
-    HV_REQUIRE(n <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_points_f64: %lld points exceed max_points=%lld",
-               (long long)n, (long long)v->cfg.max_points);
-    HV_HIP(hipSetDevice(v->device));
-    const void *d_pts64 = nullptr, *d_cols = nullptr;
-    int rc = hv_stage_in(v, points, sizeof(double) * 3 * (size_t)n, loc, 0, &d_pts64);
-    if (rc != HV_OK) return rc;
-    if (color_dtype != HV_COLOR_NONE) {
-        rc = hv_stage_in(v, colors, (color_dtype == HV_COLOR_U8 ? 1 : 4) * 3 * (size_t)n, loc, 1, &d_cols);
-        if (rc != HV_OK) return rc;
-    }
-    // keys from the doubles; the key kernel leaves the float32 narrowing the voxel sums take in scratch_points
-    return integrate_device_points(v, v->scratch_points, n, d_cols, color_dtype, nullptr, nullptr, (const double *)d_pts64);
+    return integrate_points(v, "hv_integrate_points_f64", points, true, n, colors, color_dtype, loc);
 }
 
 } // extern "C" (reopened below)
@@ -1026,15 +806,12 @@ static int unproject_device(hv_volume *v, const void *d_depth, int32_t depth_dty
 int hv_unproject_frame(hv_volume *v, const void *depth, int32_t depth_dtype, double depth_scale, const uint8_t *rgb,
                        int32_t height, int32_t width, const double *intr, const double *T_cw, double min_depth,
                        double max_depth, int32_t loc, const void **d_depth_out) {
-    const int64_t npx = (int64_t)height * width;
-    const void *d_depth = nullptr, *d_rgb = nullptr;
-    int rc = hv_stage_in(v, depth, (size_t)npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, rgb, (size_t)npx * 3, loc, 1, &d_rgb);
+    const void *d_depth = nullptr;
+    const uint8_t *d_rgb = nullptr;
+    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, (int64_t)height * width, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     if (d_depth_out) *d_depth_out = d_depth;
-    return unproject_device(v, d_depth, depth_dtype, depth_scale, (const uint8_t *)d_rgb, height, width, intr, T_cw, min_depth,
-                            max_depth, 0);
+    return unproject_device(v, d_depth, depth_dtype, depth_scale, d_rgb, height, width, intr, T_cw, min_depth, max_depth, 0);
 }
 
 // Batched replay (rebuild() / offline reconstruction): F posed frames are unprojected into one point array and fused
@@ -1053,17 +830,16 @@ extern "C" int hv_integrate_rgbd_points_batch(hv_volume *v, const void *depth, i
     HV_REQUIRE(npx <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_rgbd_points_batch: image exceeds max_points");
     HV_HIP(hipSetDevice(v->device));
     const size_t dsz = depth_dtype == HV_DEPTH_U16 ? 2 : 4;
-    const void *d_depth = nullptr, *d_rgb = nullptr;
-    int rc = hv_stage_in(v, depth, (size_t)npx * dsz * n_frames, loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, rgb, (size_t)npx * 3 * n_frames, loc, 1, &d_rgb);
+    const void *d_depth = nullptr;
+    const uint8_t *d_rgb = nullptr;
+    int rc = hv_stage_frame(v, depth, depth_dtype, rgb, npx * n_frames, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     const int per_chunk = (int)std::max<int64_t>(1, v->cfg.max_points / npx);
     for (int f0 = 0; f0 < n_frames; f0 += per_chunk) {
         const int nf = std::min(per_chunk, n_frames - f0);
         for (int f = 0; f < nf; ++f) {
             rc = unproject_device(v, (const char *)d_depth + npx * dsz * (size_t)(f0 + f), depth_dtype, depth_scale,
-                                  (const uint8_t *)d_rgb + npx * 3 * (size_t)(f0 + f), height, width, intr,
+                                  d_rgb + npx * 3 * (size_t)(f0 + f), height, width, intr,
                                   T_cw + 16 * (size_t)(f0 + f), min_depth, max_depth, (int64_t)f * npx);
             if (rc != HV_OK) return rc;
         }
@@ -1105,104 +881,27 @@ extern "C" int hv_integrate_rgbd_points(hv_volume *v, const void *depth, int32_t
     HV_REQUIRE(npx <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_rgbd_points: image exceeds max_points");
     HV_HIP(hipSetDevice(v->device));
     HvFrameSource frame;
-    const void *d_depth = nullptr, *d_rgb = nullptr;
-    int rc = hv_stage_in(v, depth, (size_t)npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, rgb, (size_t)npx * 3, loc, 1, &d_rgb);
+    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, npx, loc, &frame.d_depth, &frame.d_rgb);
     if (rc != HV_OK) return rc;
     frame.U = unproject_params(depth_dtype, depth_scale, height, width, intr, T_cw, min_depth, max_depth);
-    frame.d_depth = d_depth;
-    frame.d_rgb = (const uint8_t *)d_rgb;
     return integrate_device_points(v, v->scratch_points, npx, v->scratch_colors, HV_COLOR_F32, nullptr, &frame);
 }
 
 extern "C" {
 
-// the seven launches of the filter on `st`: head = [histograms][state] (zeroed here), dd -> d_out (device images)
-static int shadow_filter_launch(const float *dd, int32_t height, int32_t width, int32_t delta_x, int32_t delta_y, float fill_value,
-                                float *d_out, uint32_t *head, hipStream_t st) {
-    const int64_t npx = (int64_t)height * width;
-    uint32_t *hist0 = head, *hist1 = hist0 + HV_SH_BINS01, *hist2 = hist1 + 2 * HV_SH_BINS01;
-    uint32_t *state = hist0 + HV_SH_HIST_WORDS;
-    HV_HIP(hipMemsetAsync(hist0, 0, sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS), st));
-    // one workgroup per CU (1024 measured the same, round 6: the passes are bound by the LDS atomics of a few dozen hot bins)
-    const unsigned hist_grid = (unsigned)std::min<int64_t>((npx + 255) / 256, HV_SH_GRID);
-    hipLaunchKernelGGL(k_shadow_hist<0>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist0);
-    hipLaunchKernelGGL(k_shadow_pick<0>, dim3(1), dim3(256), 0, st, hist0, state);
-    hipLaunchKernelGGL(k_shadow_hist<1>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist1);
-    hipLaunchKernelGGL(k_shadow_pick<1>, dim3(1), dim3(256), 0, st, hist1, state);
-    hipLaunchKernelGGL(k_shadow_hist<2>, dim3(hist_grid), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, hist2);
-    hipLaunchKernelGGL(k_shadow_pick<2>, dim3(1), dim3(256), 0, st, hist2, state);
-    hipLaunchKernelGGL(k_shadow_mask, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, st, dd, height, width, delta_x, delta_y, state, fill_value, d_out);
-    HV_HIP(hipGetLastError());
-    return HV_OK;
-}
-
-int hv_filter_shadow_points(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,
-                            int32_t delta_y, float fill_value, float *out, int32_t loc) {
-    HV_REQUIRE(v != nullptr && depth != nullptr && out != nullptr, HV_ERR_INVALID, "hv_filter_shadow_points: null argument");
-    HV_REQUIRE(height > 0 && width > 0 && delta_x >= 0 && delta_y >= 0 && delta_x < width && delta_y < height,
-               HV_ERR_INVALID, "hv_filter_shadow_points: bad image size or deltas");
-    HV_HIP(hipSetDevice(v->device));
-    const int64_t npx = (int64_t)height * width;
-    HV_REQUIRE(npx < (int64_t)1 << 30, HV_ERR_INVALID, "hv_filter_shadow_points: image too large");
-    const void *d_depth = nullptr;
-    int rc = hv_stage_in(v, depth, sizeof(float) * npx, loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
-    // scratch: [histograms][state][out npx]
-    const size_t head = sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS);
-    rc = hv_ensure_buffer(v, &v->out_c, &v->out_c_bytes, head + sizeof(float) * npx);
-    if (rc != HV_OK) return rc;
-    float *d_out = loc == HV_DEVICE ? out : (float *)((char *)v->out_c + head);
-    rc = shadow_filter_launch((const float *)d_depth, height, width, delta_x, delta_y, fill_value, d_out, (uint32_t *)v->out_c, v->stream);
-    if (rc != HV_OK) return rc;
-    // host images: copied back and complete on return; device images: queued on the volume's stream like every other launch
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(out, d_out, sizeof(float) * npx, hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
-    return HV_OK;
-}
-
-int hv_filter_shadow_points_on_stream(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,
-                                      int32_t delta_y, float fill_value, float *out, void *stream) {
-    HV_REQUIRE(v != nullptr && depth != nullptr && out != nullptr, HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: null argument");
-    HV_REQUIRE(height > 0 && width > 0 && delta_x >= 0 && delta_y >= 0 && delta_x < width && delta_y < height,
-               HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: bad image size or deltas");
-    HV_REQUIRE((int64_t)height * width < (int64_t)1 << 30, HV_ERR_INVALID, "hv_filter_shadow_points_on_stream: image too large");
-    HV_HIP(hipSetDevice(v->device));
-    // the filter touches nothing of the volume: it may run beside the volume's own launches (a keyframe's depth is filtered on the
-    // upload side while the previous keyframe is fused).  Histograms and state of its own, four sets used in turn.
-    constexpr int SETS = 4;
-    const size_t head = sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS);
-    if (v->shadow_ring == nullptr) HV_HIP(hipMalloc(&v->shadow_ring, head * SETS));
-    uint32_t *scratch = (uint32_t *)((char *)v->shadow_ring + head * (size_t)v->shadow_ring_next);
-    v->shadow_ring_next = (v->shadow_ring_next + 1) % SETS;
-    return shadow_filter_launch(depth, height, width, delta_x, delta_y, fill_value, out, scratch, (hipStream_t)stream);
-}
-
+// (non-semantic voxels: count criterion only, voxel_block_grid.hpp:749-751 - min_confidence is not used)
 int hv_get_voxels(hv_volume *v, int32_t min_count, float min_confidence, float *points, float *colors,
                   int64_t cap, int64_t *n, int32_t loc) {
     HV_REQUIRE(v != nullptr, HV_ERR_INVALID, "hv_get_voxels: null volume");
-    (void)min_confidence; // non-semantic voxels: count criterion only (voxel_block_grid.hpp:749-751)
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 0;
-    Q.min_count = min_count;
-    return run_collect(v, Q, points, colors, cap, n, loc);
+    (void)min_confidence;
+    return run_collect(v, hv_query_all(min_count), points, colors, cap, n, loc);
 }
 
 int hv_get_voxels_in_bb(hv_volume *v, const double *bbox, int32_t min_count, float min_confidence, float *points,
                         float *colors, int64_t cap, int64_t *n, int32_t loc) {
     HV_REQUIRE(v != nullptr && bbox != nullptr, HV_ERR_INVALID, "hv_get_voxels_in_bb: null argument");
     (void)min_confidence;
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 1;
-    Q.min_count = min_count;
-    for (int k = 0; k < 6; ++k) Q.bb[k] = bbox[k];
-    fill_key_range(Q, grid_params(v));
-    return run_collect(v, Q, points, colors, cap, n, loc);
+    return run_collect(v, hv_query_in_bb(v, bbox, min_count), points, colors, cap, n, loc);
 }
 
 int hv_get_voxels_in_frustum(hv_volume *v, const float *intr_f32, int32_t width, int32_t height, const double *T_cw,
@@ -1211,13 +910,7 @@ int hv_get_voxels_in_frustum(hv_volume *v, const float *intr_f32, int32_t width,
     HV_REQUIRE(v != nullptr && intr_f32 != nullptr && T_cw != nullptr, HV_ERR_INVALID,
                "hv_get_voxels_in_frustum: null argument");
     (void)min_confidence;
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 2;
-    Q.min_count = min_count;
-    fill_frustum_query(Q, v, intr_f32, width, height, T_cw, depth_max, depth_min);
-    fill_key_range(Q, grid_params(v));
-    return run_collect(v, Q, points, colors, cap, n, loc);
+    return run_collect(v, hv_query_in_frustum(v, intr_f32, width, height, T_cw, depth_max, depth_min, min_count), points, colors, cap, n, loc);
 }
 
 int hv_carve(hv_volume *v, const float *intr_f32, int32_t width, int32_t height, const double *T_cw, float depth_max,
@@ -1226,22 +919,16 @@ int hv_carve(hv_volume *v, const float *intr_f32, int32_t width, int32_t height,
     const bool semantic = hv_mode_is_semantic(v->cfg.mode);
     HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID || semantic, HV_ERR_MODE, "hv_carve: volume is not a voxel grid");
     if (depth == nullptr || width <= 0 || height <= 0) return HV_OK; // "Depth image is empty": reference returns
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
-    if (nb == 0) return HV_OK;
+    int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const void *d_depth = nullptr;
     rc = hv_stage_in(v, depth, sizeof(float) * (size_t)width * height, loc, 0, &d_depth);
     if (rc != HV_OK) return rc;
-    HvQuery Q;
-    memset(&Q, 0, sizeof(Q));
-    Q.kind = 3;
-    Q.min_count = 1; // iterate_voxels_in_camera_frustrum default, voxel_block_grid.h:161-163
+    // (min_count 1: iterate_voxels_in_camera_frustrum default, voxel_block_grid.h:161-163)
+    HvQuery Q = hv_query_in_frustum(v, intr_f32, width, height, T_cw, depth_max, depth_min, 1, 3);
     Q.carve_threshold = depth_threshold;
-    fill_frustum_query(Q, v, intr_f32, width, height, T_cw, depth_max, depth_min);
     const HvGridParams G = grid_params(v);
-    fill_key_range(Q, G);
     if (semantic) return hv_sem_carve(v, Q, (const float *)d_depth, nb);
     const int64_t total = nb * G.nvox;
     hipLaunchKernelGGL(k_vg_carve, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
@@ -1255,11 +942,9 @@ int hv_remove_low_count_voxels(hv_volume *v, int32_t min_count) {
     if (hv_mode_is_semantic(v->cfg.mode))
         return hv_sem_segment_op(v, 3, min_count, 0, 0.f);
     HV_REQUIRE(v->cfg.mode == HV_MODE_VOXEL_GRID, HV_ERR_MODE, "hv_remove_low_count_voxels: not a voxel grid");
-    HV_HIP(hipSetDevice(v->device));
     int64_t nb = 0;
-    int rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
-    if (nb == 0) return HV_OK;
+    const int rc = hv_scan_begin(v, &nb);
+    if (rc != HV_OK || nb == 0) return rc;
     const int64_t total = nb * grid_params(v).nvox;
     hipLaunchKernelGGL(k_vg_remove_low_count, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream,
                        (HvVoxel *)v->pool, total, min_count);
@@ -1282,13 +967,10 @@ int hv_dump_blocks(hv_volume *v, int32_t *keys, uint64_t *hashes, int32_t *count
     *n_blocks = nb;
     if (nb == 0 || (!keys && !hashes && !counts && !sums)) return HV_OK;
     const HvGridParams G = grid_params(v);
-    std::vector<uint64_t> bkeys((size_t)nb);
-    HV_HIP(hipMemcpy(bkeys.data(), v->table.block_keys, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost));
-    std::vector<std::array<int32_t, 3>> xyz((size_t)nb);
-    for (int64_t i = 0; i < nb; ++i) hv_unpack_key(bkeys[i], xyz[i][0], xyz[i][1], xyz[i][2]);
-    std::vector<int64_t> order((size_t)nb);
-    std::iota(order.begin(), order.end(), 0);
-    std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return xyz[a] < xyz[b]; });
+    std::vector<std::array<int32_t, 3>> xyz;
+    std::vector<int64_t> order;
+    rc = hv_blocks_in_key_order(v, nb, xyz, order);
+    if (rc != HV_OK) return rc;
     std::vector<HvVoxel> host;
     if (counts || sums) {
         host.resize((size_t)nb * G.nvox);
