@@ -1104,6 +1104,98 @@ int hv_tsdf_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_pack_info
 int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv_pack_info *info);
 int hv_tsdf_packed_check(const void *host_src, int64_t bytes, hv_packed_header *out);
 
+/* Packed grids: the same for HV_MODE_VOXEL_GRID and the four semantic block grids - a compact, BIT-EXACT form of the whole map (counts,
+ * position and colour sums, object and class ids, both confidence counters, the per-voxel label maps in insertion order, the next
+ * object id), made and consumed on the GPU.  This project's own format; this comment is its contract.
+ * One flat little-endian byte buffer.  Every section starts on a 64-byte boundary, padding bytes are zero, and the buffer ends on
+ * one: total_bytes = the end of the last section rounded up to 64.
+ *   header, 192 bytes
+ *     off  type        field
+ *       0  8 bytes     magic "HVGRIDPK"
+ *       8  uint32      version = HV_GRID_PACK_VERSION (1)
+ *      12  uint32      header_bytes = 192
+ *      16  float64     voxel_size
+ *      24  int32       mode (the HV_MODE_* value: 0, 1, 2, 11 or 12)
+ *      28  int32       block_size bs, 1..16
+ *      32  int32       record_bytes: 32 (mode 0), 64 (modes 1, 11), 128 (modes 2, 12)
+ *      36  int32       next_object_id: the process-wide counter (hv_peek_next_object_id) at pack time
+ *      40  float32     depth_threshold  (hv_set_depth_threshold)
+ *      44  float32     depth_decay_rate (hv_set_depth_decay_rate)
+ *      48  int64       blocks B
+ *      56  int64       voxels N (stored records)
+ *      64  int64       extra_pairs P
+ *      72  int64       total_bytes
+ *      80  8 x uint64  byte offsets of the eight sections below, in this order
+ *     144  48 bytes    reserved = 0
+ *   keys        int32  [B,3]   block keys, strictly ascending by (x, then y, then z) - the order of hv_dump_blocks: the same map gives the
+ *                              same bytes whatever its pool order
+ *   offsets     uint64 [B+1]   offsets[0] = 0, offsets[B] = N; block b's records are [offsets[b], offsets[b+1])
+ *   masks       uint64 [B,W]   W = ceil(bs^3 / 64); bit (k & 63) of word (k >> 6) is set when local voxel k = lx + ly * bs + lz * bs^2 is
+ *                              STORED; bits at or above bs^3 are zero
+ *   records     N x record_bytes   block after block, within a block by ascending k.  A record is the pool record bit for bit - HvVoxel,
+ *                              HvSemVoxel, HvSem2Voxel, HvProbVoxel or HvProb2Voxel, as 32-bit words:
+ *                                mode 0        0 count, 1-3 position sums f32, 4-6 colour sums f32, 7 padding
+ *                                modes 1, 11   0 count, 1 object id + 1, 2 class id + 1, 3 (object) confidence counter, 4-9 position sums f64,
+ *                                              10-12 colour sums f32, 13 class confidence counter (mode 11; padding in mode 1), 14-15 padding
+ *                                modes 2, 12   0 count, 1 meta, 2-7 position sums f64, 8-10 colour sums f32, 11-16 the ids of the 6 inline
+ *                                              label pairs, 17-22 their class ids (mode 12: which map, 0 object / 1 class), 23-28 their
+ *                                              log-probabilities f32, 29 chain link, 30-31 padding
+ *                              meta = n | (b1 << 8) | (b2 << 16): n = pairs of the label map (0..254), b1 = 1 + index of the cached most
+ *                              likely pair (mode 12: object entry) or 0, b2 (mode 12 only) = 1 + index of the cached most likely class
+ *                              entry or 0.  Padding words and the chain link are written as ZERO.
+ *   extras      uint8  [N]     modes 2, 12 (size 0 otherwise): max(n - 6, 0) = the pairs of the voxel's map beyond the 6 inline ones, 0..248
+ *   extra_obj, extra_cls  int32 [P] each   P = sum of extras: the extra pairs of every voxel in record order, within a voxel in insertion
+ *                              order (pair 6, 7, ...)
+ *   extra_logp  float32 [P]    same order
+ * A voxel is STORED when any word of its record other than padding and the chain link is non-zero as a bit pattern.  A reset
+ * probabilistic voxel that only kept its overflow chain is NOT stored (the chain is capacity, not content).  EVERY allocated block is
+ * stored, also with mask 0 (hv_num_blocks survives the trip).  NOT stored, NOT restored: pool size, owner settings, streams, the
+ * association's scratch (votes, the decided map), hv_dropped_points, hv_label_overflows, the segments cache.
+ *   hv_grid_packed_check  host only, no GPU.  Checks, in this order, and names the first rule that fails (HV_ERR_INVALID): at least 192
+ *              bytes; magic; version; header_bytes; mode one of the five; block_size in [1,16]; record_bytes matches the mode; blocks, voxels,
+ *              extra_pairs >= 0; extra_pairs == 0 for a mode without label maps; blocks, voxels and extra_pairs no more than the buffer could
+ *              hold (12, record_bytes and 12 bytes apiece); total_bytes == bytes; every section offset 64-byte aligned; every section behind
+ *              the header and inside the buffer with the size B, N and P imply; no two sections overlap; keys in [-2^20, 2^20); keys
+ *              strictly ascending; offsets[0] == 0; offsets non-decreasing; offsets[B] == N; offsets[b+1] - offsets[b] ==
+ *              popcount(masks[b]); no mask bit at or above bs^3; every extras entry <= 248; sum of extras == P.
+ *              Fills *out (may be NULL) with the header fields once the header rules hold, and its chain_nodes once every rule holds.
+ *   hv_grid_pack_size     waits; info = {B, N, P, exact buffer size}.
+ *   hv_grid_pack          dst (cap bytes) at loc = HV_HOST or HV_DEVICE (the volume's GPU).  cap too small: HV_ERR_CAPACITY, info filled
+ *              in, nothing written.  Only READS the volume: the dumps, hv_lookup_points, the association state (an unfetched map included)
+ *              are what they were.  An empty grid packs to a valid buffer with B = N = P = 0.
+ *   hv_grid_unpack        src (bytes) at loc.  Runs hv_grid_packed_check BEFORE it launches anything - on a host buffer as it lies; of a
+ *              device buffer it copies the header, then the keys / offsets / masks / extras sections to the host, never the records.
+ *              Requires a grid of the header's mode and block_size whose voxel_size is BITWISE equal to the header's (HV_ERR_INVALID),
+ *              hv_num_blocks == 0 (HV_ERR_INVALID) and no owner sharding (HV_ERR_MODE, as for a TSDF volume).  For modes 2 and 12 a
+ *              read-only pass over the records (indices inside [0, N) only) then checks what the metadata cannot: n <= 254, extras ==
+ *              max(n - 6, 0), b1 <= n and (mode 12) b2 <= n (HV_ERR_INVALID).  Then: the overflow-node pool must hold
+ *              sum ceil(extras / 10) nodes (HV_ERR_CAPACITY, the need named); the keys are claimed and the claims verified (a pool that is
+ *              too small grows before anything is written, or HV_ERR_CAPACITY); ALL bs^3 records of every block are written, the
+ *              packed record where the bit is set and zero where it is not, and the block's occupancy bits = its mask; the chains are
+ *              rebuilt (voxel i gets ceil(extras[i] / 10) consecutive nodes, filled in order, the unused slots of the last one zero).
+ *              On ANY error the volume is unchanged.  Afterwards the node counter (hv_prob_nodes_used) = nodes rebuilt, no association is
+ *              pending, the segments cache is dropped, the content version is bumped, and the process-wide next object id is
+ *              max(its value, the header's) - never lowered.  depth_threshold and depth_decay_rate are settings: the volume keeps its own.
+ * All of them drain pending work and wait for the GPU; HV_ERR_MODE for a TSDF volume and for an owner-sharded grid (hv_set_owner with
+ * world_size > 1: it holds a part of the map's blocks). */
+#define HV_GRID_PACK_VERSION 1
+#define HV_GRID_PACK_HEADER_BYTES 192
+typedef struct hv_grid_pack_info {
+    int64_t blocks, voxels, extra_pairs, bytes;
+} hv_grid_pack_info;
+typedef struct hv_grid_packed_header {
+    double voxel_size;
+    int32_t mode, block_size, record_bytes, version, next_object_id;
+    float depth_threshold, depth_decay_rate;
+    int32_t reserved;
+    int64_t blocks, voxels, extra_pairs, bytes;
+    int64_t chain_nodes; /* sum of ceil(extras / 10): the overflow nodes hv_grid_unpack rebuilds */
+} hv_grid_packed_header;
+int hv_grid_pack_size(hv_volume *v, hv_grid_pack_info *info);
+int hv_grid_pack(hv_volume *v, void *dst, int64_t cap, int32_t loc, hv_grid_pack_info *info);
+int hv_grid_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv_grid_pack_info *info);
+int hv_grid_packed_check(const void *host_src, int64_t bytes, hv_grid_packed_header *out);
+
 /* ---- halo merge of image-tile-sharded volumes (SURVEY 8b `hv_merge_halo`, 8e; north-star "RCCL all-reduce of
  * overlapping-block TSDF/weight").  pySLAM has no multi-GPU path (no NCCL/MPI/torch.distributed call anywhere in the
  * reference): these are new.  With hv_tsdf_set_tile each GPU fuses the voxels that project into its image tile, so units

@@ -161,6 +161,33 @@ class HvPackedHeader(_c.Structure):
     ]
 
 
+HV_GRID_PACK_VERSION = 1
+HV_GRID_PACK_HEADER_BYTES = 192
+
+
+class HvGridPackInfo(_c.Structure):
+    _fields_ = [("blocks", _i64), ("voxels", _i64), ("extra_pairs", _i64), ("bytes", _i64)]
+
+
+class HvGridPackedHeader(_c.Structure):
+    _fields_ = [
+        ("voxel_size", _f64),
+        ("mode", _i32),
+        ("block_size", _i32),
+        ("record_bytes", _i32),
+        ("version", _i32),
+        ("next_object_id", _i32),
+        ("depth_threshold", _f32),
+        ("depth_decay_rate", _f32),
+        ("reserved", _i32),
+        ("blocks", _i64),
+        ("voxels", _i64),
+        ("extra_pairs", _i64),
+        ("bytes", _i64),
+        ("chain_nodes", _i64),
+    ]
+
+
 HV_F32, HV_F64 = 0, 1
 HV_SAMPLE_OUTSIDE, HV_SAMPLE_UNOBSERVED, HV_SAMPLE_NEAREST, HV_SAMPLE_TRILINEAR = 0, 1, 2, 3
 HV_CHECK_INVALID, HV_CHECK_UNKNOWN, HV_CHECK_CONSISTENT, HV_CHECK_IN_FRONT, HV_CHECK_BEHIND = 0, 1, 2, 3, 4
@@ -320,6 +347,10 @@ SIGNATURES = {
     "hv_tsdf_pack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvPackInfo)]),
     "hv_tsdf_unpack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvPackInfo)]),
     "hv_tsdf_packed_check": (_i32, [_vp, _i64, _c.POINTER(HvPackedHeader)]),
+    "hv_grid_pack_size": (_i32, [_vp, _c.POINTER(HvGridPackInfo)]),
+    "hv_grid_pack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvGridPackInfo)]),
+    "hv_grid_unpack": (_i32, [_vp, _vp, _i64, _i32, _c.POINTER(HvGridPackInfo)]),
+    "hv_grid_packed_check": (_i32, [_vp, _i64, _c.POINTER(HvGridPackedHeader)]),
     "hv_tsdf_dirty_keys": (_i32, [_vp, _vp, _i64, _pi64]),
     "hv_tsdf_mark_merged": (_i32, [_vp]),
     "hv_set_owner": (_i32, [_vp, _i32, _i32]),

@@ -648,6 +648,9 @@ int hv_create(const hv_config *cfg, hv_volume **out) {
     if (hv_mode_has_label_maps(cfg->mode)) v->sem_depth_threshold = 5.0f; // voxel_data_semantic.h:251-254, voxel_data_semantic2.h:258-261
     v->local_bits = 0;
     while ((1ll << v->local_bits) < nvox) v->local_bits++;
+    // (one-voxel blocks: the semantic bin entries are local index << (32 - local_bits) | point index, and a shift by 32 is not a
+    // shift - the fold took the point index for the local index and counted a block's second point in the next pool record)
+    if (v->local_bits < 1) v->local_bits = 1;
 
     v->table_capacity = next_pow2((uint64_t)cfg->max_blocks * 4);
     if (v->table_capacity < 1024) v->table_capacity = 1024;

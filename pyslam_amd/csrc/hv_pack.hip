@@ -14,7 +14,7 @@
 #include <vector>
 
 #include "hv_common.h"
-#include <rocprim/device/device_scan.hpp>
+#include "hv_pack_shared.h"
 
 namespace {
 
@@ -22,8 +22,6 @@ constexpr int HV_PACK_SECTIONS = 8;
 constexpr int HV_PACK_MASK_WORDS = HV_TSDF_RRR / 32; // 128
 const char *const HV_PACK_SECTION_NAMES[HV_PACK_SECTIONS] = {"keys", "offsets", "masks", "tsdf", "weight", "sum_r", "sum_g", "sum_b"};
 const char HV_PACK_MAGIC[8] = {'H', 'V', 'T', 'S', 'D', 'F', 'P', 'K'};
-
-inline uint64_t pack_align(uint64_t x) { return (x + 63) & ~(uint64_t)63; }
 
 void pack_section_sizes(int64_t U, int64_t N, uint64_t size[HV_PACK_SECTIONS]) {
     size[0] = 12ull * (uint64_t)U;
@@ -40,20 +38,8 @@ struct PackLayout {
 PackLayout pack_layout(int64_t U, int64_t N) {
     PackLayout L;
     pack_section_sizes(U, N, L.size);
-    uint64_t cur = HV_PACK_HEADER_BYTES;
-    for (int s = 0; s < HV_PACK_SECTIONS; ++s) {
-        L.off[s] = cur;
-        cur = pack_align(cur + L.size[s]);
-    }
-    L.total = (int64_t)cur;
+    L.total = pack_place_sections(HV_PACK_SECTIONS, HV_PACK_HEADER_BYTES, L.size, L.off);
     return L;
-}
-
-template <typename T>
-inline T rd(const void *p) { // (a caller's buffer need not be aligned)
-    T x;
-    memcpy(&x, p, sizeof(T));
-    return x;
 }
 
 struct PackHeader {
@@ -86,17 +72,8 @@ int pack_check_header(const unsigned char *h, int64_t bytes, PackHeader *H, hv_p
                (long long)H->total, (long long)bytes);
     pack_section_sizes(H->U, H->N, H->size);
     for (int s = 0; s < HV_PACK_SECTIONS; ++s) H->off[s] = rd<uint64_t>(h + 64 + 8 * s);
-    for (int s = 0; s < HV_PACK_SECTIONS; ++s)
-        HV_REQUIRE((H->off[s] & 63) == 0, HV_ERR_INVALID, "hv_tsdf_packed_check: section %s offset %llu is not 64-byte aligned",
-                   HV_PACK_SECTION_NAMES[s], (unsigned long long)H->off[s]);
-    for (int s = 0; s < HV_PACK_SECTIONS; ++s)
-        HV_REQUIRE(H->off[s] >= HV_PACK_HEADER_BYTES && H->off[s] <= (uint64_t)bytes && H->size[s] <= (uint64_t)bytes - H->off[s], HV_ERR_INVALID,
-                   "hv_tsdf_packed_check: section %s (offset %llu, %llu bytes) lies outside the buffer", HV_PACK_SECTION_NAMES[s],
-                   (unsigned long long)H->off[s], (unsigned long long)H->size[s]);
-    for (int a = 0; a < HV_PACK_SECTIONS; ++a)
-        for (int b = a + 1; b < HV_PACK_SECTIONS; ++b)
-            HV_REQUIRE(H->size[a] == 0 || H->size[b] == 0 || H->off[a] + H->size[a] <= H->off[b] || H->off[b] + H->size[b] <= H->off[a], HV_ERR_INVALID,
-                       "hv_tsdf_packed_check: sections %s and %s overlap", HV_PACK_SECTION_NAMES[a], HV_PACK_SECTION_NAMES[b]);
+    const int rc = pack_check_sections("hv_tsdf_packed_check", HV_PACK_SECTIONS, HV_PACK_SECTION_NAMES, H->off, H->size, HV_PACK_HEADER_BYTES, bytes);
+    if (rc != HV_OK) return rc;
     if (out != nullptr) {
         out->voxel_length = H->voxel_length;
         out->sdf_trunc = H->sdf_trunc;
@@ -111,29 +88,8 @@ int pack_check_header(const unsigned char *h, int64_t bytes, PackHeader *H, hv_p
 
 // the rules on the three metadata sections (host copies, any alignment)
 int pack_check_meta(const unsigned char *keys, const unsigned char *offsets, const unsigned char *masks, int64_t U, int64_t N) {
-    for (int64_t u = 0; u < U; ++u) {
-        const int32_t x = rd<int32_t>(keys + 12 * u), y = rd<int32_t>(keys + 12 * u + 4), z = rd<int32_t>(keys + 12 * u + 8);
-        HV_REQUIRE(hv_key_in_range(x, y, z), HV_ERR_INVALID, "hv_tsdf_packed_check: key %lld (%d, %d, %d) is out of range [-2^20, 2^20)",
-                   (long long)u, x, y, z);
-    }
-    for (int64_t u = 1; u < U; ++u) {
-        bool less = false;
-        for (int a = 0; a < 3; ++a) {
-            const int32_t p = rd<int32_t>(keys + 12 * (u - 1) + 4 * a), q = rd<int32_t>(keys + 12 * u + 4 * a);
-            if (p != q) {
-                less = p < q;
-                break;
-            }
-        }
-        HV_REQUIRE(less, HV_ERR_INVALID, "hv_tsdf_packed_check: keys are not strictly ascending at unit %lld", (long long)u);
-    }
-    HV_REQUIRE(rd<uint64_t>(offsets) == 0, HV_ERR_INVALID, "hv_tsdf_packed_check: offsets[0] is %llu, not 0",
-               (unsigned long long)rd<uint64_t>(offsets));
-    for (int64_t u = 0; u < U; ++u)
-        HV_REQUIRE(rd<uint64_t>(offsets + 8 * (u + 1)) >= rd<uint64_t>(offsets + 8 * u), HV_ERR_INVALID,
-                   "hv_tsdf_packed_check: offsets decrease at unit %lld", (long long)u);
-    HV_REQUIRE(rd<uint64_t>(offsets + 8 * U) == (uint64_t)N, HV_ERR_INVALID, "hv_tsdf_packed_check: offsets[U] (%llu) differs from voxels (%lld)",
-               (unsigned long long)rd<uint64_t>(offsets + 8 * U), (long long)N);
+    const int rc = pack_check_keys_offsets("hv_tsdf_packed_check", "unit", 'U', keys, offsets, U, N);
+    if (rc != HV_OK) return rc;
     for (int64_t u = 0; u < U; ++u) {
         int pop = 0;
         for (int w = 0; w < HV_PACK_MASK_WORDS; ++w) pop += __builtin_popcount(rd<uint32_t>(masks + 4 * (HV_PACK_MASK_WORDS * u + w)));
@@ -273,14 +229,12 @@ int pack_prepare(hv_volume *v, const char *fn, PackScratch &S) {
     int rc = hv_tsdf_require_whole_map(v, fn, "the volume");
     if (rc != HV_OK) return rc;
     int64_t U = 0;
-    rc = hv_tsdf_drain(v, fn, true, &U);
+    std::vector<int32_t> order;
+    rc = pack_key_order(v, fn, &U, order, S.keys);
     if (rc != HV_OK) return rc;
     S.U = U;
     S.N = 0;
     if (U == 0) return HV_OK;
-    std::vector<int32_t> order;
-    rc = hv_tsdf_key_order(v, U, order, &S.keys);
-    if (rc != HV_OK) return rc;
     // [order U i32][masks U*128 u32][counts U+1 u64][offsets U+1 u64], each part on a 256-byte boundary
     auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t b_order = up(sizeof(int32_t) * (size_t)U), b_masks = up(sizeof(uint32_t) * HV_PACK_MASK_WORDS * (size_t)U),
@@ -295,12 +249,8 @@ int pack_prepare(hv_volume *v, const char *fn, PackScratch &S) {
     HV_HIP(hipMemsetAsync(S.counts + U, 0, sizeof(uint64_t), v->stream)); // the scan's extra element: its output there is N
     hipLaunchKernelGGL(k_pack_mask, dim3((unsigned)U), dim3(256), 0, v->stream, (const char *)v->pool, (const int32_t *)S.order, S.masks, S.counts);
     HV_HIP(hipGetLastError());
-    size_t tmp = 0;
-    HV_HIP(rocprim::exclusive_scan(nullptr, tmp, S.counts, S.offsets, 0ull, (size_t)(U + 1), rocprim::plus<unsigned long long>(), v->stream));
-    rc = hv_ensure_buffer(v, &v->sort_tmp, &v->sort_tmp_bytes, tmp);
+    rc = pack_exclusive_scan(v, S.counts, S.offsets, (size_t)(U + 1));
     if (rc != HV_OK) return rc;
-    tmp = v->sort_tmp_bytes;
-    HV_HIP(rocprim::exclusive_scan(v->sort_tmp, tmp, S.counts, S.offsets, 0ull, (size_t)(U + 1), rocprim::plus<unsigned long long>(), v->stream));
     unsigned long long n = 0;
     HV_HIP(hipMemcpyAsync(&n, S.offsets + U, sizeof(n), hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream));
@@ -404,19 +354,15 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
         rc = pack_check_header((const unsigned char *)src, bytes, &H, nullptr);
         if (rc != HV_OK) return rc;
     } else {
-        // (on the volume's stream: a caller orders the buffer's producers against that stream)
         unsigned char header[HV_PACK_HEADER_BYTES];
-        HV_HIP(hipMemcpyAsync(header, src, sizeof(header), hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
+        rc = unpack_fetch_header(v, src, header, sizeof(header));
+        if (rc != HV_OK) return rc;
         rc = pack_check_header(header, bytes, &H, nullptr);
         if (rc != HV_OK) return rc;
+        const int which[3] = {0, 1, 2};
         std::vector<unsigned char> meta[3];
-        for (int s = 0; s < 3; ++s) {
-            meta[s].resize((size_t)std::max<uint64_t>(H.size[s], 8));
-            if (H.size[s] > 0)
-                HV_HIP(hipMemcpyAsync(meta[s].data(), (const char *)src + H.off[s], (size_t)H.size[s], hipMemcpyDeviceToHost, v->stream));
-        }
-        HV_HIP(hipStreamSynchronize(v->stream));
+        rc = unpack_fetch_sections(v, src, H.off, H.size, which, 3, meta);
+        if (rc != HV_OK) return rc;
         rc = pack_check_meta(meta[0].data(), meta[1].data(), meta[2].data(), H.U, H.N);
         if (rc != HV_OK) return rc;
     }
@@ -441,15 +387,7 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
     const char *d = loc == HV_HOST ? (const char *)tmp : (const char *)src;
     // claim first, and verify (this call waits for the GPU anyway): a pool that is too small grows before a voxel is written, or the
     // claim pass is rolled back and the volume is what it was
-    bool checked_unused = false;
-    rc = hv_capacity_gate(v, &checked_unused);
-    for (int attempt = 0; rc == HV_OK; ++attempt) {
-        hv_launch_tsdf_import_claim(v, (const int32_t *)(d + H.off[0]), H.U);
-        rc = hv_claims_fit(v);
-        if (rc == HV_OK) break;
-        if (rc == HV_RETRY_CLAIM && attempt < 8) rc = HV_OK;
-        else if (rc == HV_RETRY_CLAIM) rc = HV_ERR_CAPACITY;
-    }
+    rc = unpack_claim_keys(v, (const int32_t *)(d + H.off[0]), H.U);
     if (rc != HV_OK) return rc;
     v->content_version += 1;
     v->extract_epoch += 1;
@@ -472,6 +410,7 @@ int hv_tsdf_unpack(hv_volume *v, const void *src, int64_t bytes, int32_t loc, hv
         hv_set_error("hv_tsdf_unpack: the scatter failed: %s (the volume holds the claimed units, possibly unwritten: hv_reset it)", hipGetErrorString(e));
         return HV_ERR_DEVICE;
     }
+    unpack_occupancy_exact(v, H.U);
     return HV_OK;
 }
 

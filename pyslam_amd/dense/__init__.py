@@ -7,6 +7,7 @@ keeps the volume resident in HBM.
 from .volumetric_integrator_types import VolumetricIntegratorType  # noqa: F401
 from .volumetric_integrator_base import (  # noqa: F401
     VolumetricIntegrationKeyframeData,
+    VolumetricIntegrationMapTaskType,
     VolumetricIntegrationMesh,
     VolumetricIntegrationOutput,
     VolumetricIntegrationPointCloud,

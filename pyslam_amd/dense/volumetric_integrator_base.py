@@ -45,6 +45,13 @@ class VolumetricIntegrationTaskType(Enum):  # base.py:91-97
     UPDATE_OUTPUT = 5
 
 
+class VolumetricIntegrationMapTaskType(Enum):
+    """The task types of save_map / load_map: the volume's packed map (pack / unpack of pyslam_amd.volumetric), lossless.  Not in the
+    reference, and kept apart from VolumetricIntegrationTaskType, which mirrors the reference's enum member for member."""
+    SAVE_MAP = 6
+    LOAD_MAP = 7
+
+
 class VolumetricIntegrationKeyframeData:  # base.py:101-137
     """Picklable snapshot of the keyframe fields the dense path consumes."""
 
@@ -418,6 +425,61 @@ class VolumetricIntegratorBase:
     def load(self, path):  # base.py:595-604: a stub in the reference too
         return None
 
+    kPackedMapFile = "dense_map.hvmap"  # beside dense_map.ply
+
+    def save_map(self, path):
+        """The worker's volume as a packed map (bit-exact: volume.save) in `path`/dense_map.hvmap; returns when it is written.
+        RuntimeError when the worker could not write it (its log has the reason)."""
+        self._map_request(VolumetricIntegrationMapTaskType.SAVE_MAP, path)
+
+    def load_map(self, path):
+        """Replace the content of the worker's volume by the packed map in `path`/dense_map.hvmap (reset, then unpack); keyframes
+        queued afterwards integrate on top of it.  Returns when it is done.  RuntimeError when the worker could not load it - a
+        missing, damaged or foreign file (its log has the reason); the worker's map is then what it was."""
+        self._map_request(VolumetricIntegrationMapTaskType.LOAD_MAP, path)
+
+    kMapRequestFailed = 2  # save_request_completed: 0 pending, 1 done, 2 a map task failed (set back to 1 by the caller)
+
+    def _map_request(self, task_type, path):
+        if self.save_request_completed.value == 0:
+            return
+        task = VolumetricIntegrationTask(task_type=task_type, load_save_path=os.path.join(path, self.kPackedMapFile))
+        self.save_request_completed.value = 0
+        self.add_task(task, front=False)  # behind the keyframes already queued: the map holds them
+        with self.save_request_condition:
+            while self.save_request_completed.value == 0 and self.is_running.value == 1:
+                self.save_request_condition.wait(timeout=1.0)
+        if self.save_request_completed.value == self.kMapRequestFailed:
+            self.save_request_completed.value = 1
+            raise RuntimeError(f"{task_type.name} of {task.load_save_path} failed in the worker (see its log); its map is unchanged")
+
+    def _map_task(self, task):
+        """Worker side of save_map / load_map on self.volume.  -> the output that acknowledges the request; its `error` is None, or
+        what went wrong - the volume is then what it was: the file is read and validated before the volume is touched, and a map
+        the volume refuses after that (another voxel size, another kind of map) is undone from a packed copy of the old content."""
+        out = VolumetricIntegrationOutput(task.task_type)
+        out.error = None
+        path = task.load_save_path
+        try:
+            if task.task_type == VolumetricIntegrationMapTaskType.SAVE_MAP:
+                os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+                self.volume.save(path)
+            else:
+                buf = self.volume._read_packed(path)
+                self.volume.packed_info(buf)  # the library's validator on the whole file: ValueError names the broken rule
+                before = self.volume.pack(device=True)
+                self.volume.reset()
+                try:
+                    self.volume.unpack(buf)
+                except Exception:
+                    self.volume.reset()
+                    self.volume.unpack(before)
+                    raise
+        except Exception as e:
+            traceback.print_exc()
+            out.error = f"{type(e).__name__}: {e}"
+        return out
+
     def request_reset(self):  # base.py:606-631
         with self.reset_mutex:
             if self.reset_requested.value == 1:
@@ -752,9 +814,10 @@ class VolumetricIntegratorBase:
                     else:
                         q_out.put(last_output)
                     q_out_condition.notify_all()
-            elif last_output.task_type == VolumetricIntegrationTaskType.SAVE:
+            elif last_output.task_type in (VolumetricIntegrationTaskType.SAVE, VolumetricIntegrationMapTaskType.SAVE_MAP,
+                                           VolumetricIntegrationMapTaskType.LOAD_MAP):
                 with save_request_condition:
-                    save_request_completed.value = 1
+                    save_request_completed.value = self.kMapRequestFailed if getattr(last_output, "error", None) else 1
                     save_request_condition.notify_all()
 
     @staticmethod

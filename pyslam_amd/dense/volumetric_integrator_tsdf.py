@@ -7,6 +7,7 @@ import numpy as np
 from .parameters import get_parameters
 from .volumetric_integrator_base import (
     TimerFps,
+    VolumetricIntegrationMapTaskType,
     VolumetricIntegrationMesh,
     VolumetricIntegrationOutput,
     VolumetricIntegrationPointCloud,
@@ -124,6 +125,8 @@ class VolumetricIntegratorTsdf(VolumetricIntegratorBase):
                                 pc = self.volume.extract_point_cloud()
                             self._save_points(save_path, pc.points, pc.colors, getattr(pc, "normals", None))
                         last_output = VolumetricIntegrationOutput(ttype)
+                    elif isinstance(ttype, VolumetricIntegrationMapTaskType):
+                        last_output = self._map_task(self.last_input_task)
                     elif ttype == VolumetricIntegrationTaskType.UPDATE_OUTPUT:
                         do_output = True
                     if do_output:

@@ -9,6 +9,7 @@ import numpy as np
 from .parameters import get_parameters
 from .volumetric_integrator_base import (
     TimerFps,
+    VolumetricIntegrationMapTaskType,
     VolumetricIntegrationOutput,
     VolumetricIntegrationPointCloud,
     VolumetricIntegrationTaskType,
@@ -127,6 +128,8 @@ class VolumetricIntegratorVoxelGrid(VolumetricIntegratorBase):
                         if len(points) > 0:
                             self._save_points(self.last_input_task.load_save_path, points, colors)
                         last_output = VolumetricIntegrationOutput(ttype)
+                    elif isinstance(ttype, VolumetricIntegrationMapTaskType):
+                        last_output = self._map_task(self.last_input_task)
                     elif ttype == VolumetricIntegrationTaskType.UPDATE_OUTPUT:
                         do_output = True
                     if do_output:

@@ -15,6 +15,7 @@ import numpy as np
 from .parameters import get_parameters
 from .volumetric_integrator_base import (
     TimerFps,
+    VolumetricIntegrationMapTaskType,
     VolumetricIntegrationOutput,
     VolumetricIntegrationPointCloud,
     VolumetricIntegrationTaskType,
@@ -342,6 +343,8 @@ class VolumetricIntegratorVoxelSemanticGrid(VolumetricIntegratorBase):
                             self._save_points(self.last_input_task.load_save_path, points, colors)
                         last_output = VolumetricIntegrationOutput(ttype)
                         self.last_output = last_output
+                    elif isinstance(ttype, VolumetricIntegrationMapTaskType):
+                        last_output = self._map_task(self.last_input_task)
                     elif ttype == VolumetricIntegrationTaskType.UPDATE_OUTPUT:
                         do_output = True
                     if do_output:

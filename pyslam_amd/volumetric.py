@@ -276,6 +276,14 @@ class PackStats(_Stats):
     __slots__ = ("units", "voxels", "bytes")
 
 
+class GridPackStats(_Stats):
+    """What the block grids' unpack / save return (hv_grid_pack_info): blocks = blocks of the packed grid, empty ones included;
+    voxels = stored voxel records; extra_pairs = label pairs beyond the six a record holds inline (the two probabilistic
+    payloads; 0 otherwise); bytes = size of the packed buffer."""
+
+    __slots__ = ("blocks", "voxels", "extra_pairs", "bytes")
+
+
 # hv_tsdf_sample_points' status and hv_tsdf_check_frame's class values (include/hipvol.h)
 SAMPLE_OUTSIDE, SAMPLE_UNOBSERVED, SAMPLE_NEAREST, SAMPLE_TRILINEAR = (L.HV_SAMPLE_OUTSIDE, L.HV_SAMPLE_UNOBSERVED, L.HV_SAMPLE_NEAREST,
                                                                       L.HV_SAMPLE_TRILINEAR)
@@ -478,6 +486,25 @@ def _packed_operand(buf):
     if a.dtype != np.uint8 or a.ndim != 1:
         raise ValueError(f"a packed map is a 1-D uint8 buffer, got {a.dtype} with shape {a.shape}")
     return np.ascontiguousarray(a)
+
+
+def _packed_info(abi, path_or_buffer):
+    """The header of a packed map or grid as a dict, after the library's validator (abi = a class's _PACKED) has passed the WHOLE
+    buffer: a file path, or a buffer as unpack() takes it.  Needs no GPU.  ValueError with the validator's message."""
+    import os
+
+    prefix, _, Header, _, fields = abi
+    if isinstance(path_or_buffer, (str, os.PathLike)):
+        op = np.fromfile(path_or_buffer, dtype=np.uint8)
+    else:
+        op = _packed_operand(path_or_buffer)
+        if _is_torch(op):
+            op = op.cpu().numpy()
+    lib = L.load()
+    hdr = Header()
+    if getattr(lib, prefix + "packed_check")(L.ptr(op), int(op.size), ctypes.byref(hdr)) != L.HV_OK:
+        raise ValueError((lib.hv_last_error() or (prefix + "packed_check failed").encode()).decode())
+    return {name: getattr(hdr, name) for name in fields}
 
 
 _UNIT_KEY_BIAS = 1 << 20  # the library packs a unit index into 21 bits per axis: [-2^20, 2^20)
@@ -791,6 +818,56 @@ class _Volume:
         L.check(self._lib.hv_remap(self._h, L.ptr(img), kind, C, H, W, L.ptr(mx), L.ptr(my), 1 if linear else 0, L.ptr(out), L.HV_HOST))
         return out
 
+    # -- packed maps: what ScalableTSDFVolume and the block grids share (the class names its C ABI in _PACKED) ----------------------
+    _PACKED = None  # (function prefix, info struct, header struct, stats class, header fields)
+
+    def _pack(self, device):
+        prefix, Info, _, Stats, _ = self._PACKED
+        info = Info()
+        L.check(getattr(self._lib, prefix + "pack_size")(self._h, ctypes.byref(info)))
+        out = self._results({"map": ((info.bytes,), np.uint8)}, device, synchronize=False)["map"]
+        with self._ordered(out):
+            L.check(getattr(self._lib, prefix + "pack")(self._h, L.ptr(out), info.bytes, L.location(out), ctypes.byref(info)))
+        return out, _stats(Stats, info)
+
+    def _unpack(self, buf):
+        prefix, Info, _, Stats, _ = self._PACKED
+        op = _packed_operand(buf)
+        info = Info()
+        with self._ordered(op):
+            L.check(getattr(self._lib, prefix + "unpack")(self._h, L.ptr(op), int(op.numel() if _is_torch(op) else op.size), L.location(op),
+                                                          ctypes.byref(info)))
+        return _stats(Stats, info)
+
+    def _save(self, path):
+        import os
+        import tempfile
+
+        buf, stats = self._pack(False)
+        path = os.fspath(path)
+        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
+        try:
+            with os.fdopen(fd, "wb") as f:
+                f.write(memoryview(buf))
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return stats
+
+    @staticmethod
+    def _read_packed(path):
+        import os
+
+        size = os.path.getsize(path)
+        buf = _result_array((size,), np.uint8)  # page-locked when large: the upload is one DMA
+        with open(path, "rb") as f:
+            got = f.readinto(memoryview(buf))
+        if got != size:
+            raise ValueError(f"{path}: read {got} of {size} bytes")
+        return buf
+
     def bytes_per_block(self):
         return self._int64(self._lib.hv_bytes_per_block)
 
@@ -873,6 +950,84 @@ class _BlockGrid(_Volume):
         L.check(self._lib.hv_reset(self._h))
 
     reset = clear
+
+    # -- packed grids: keeping and moving a map (include/hipvol.h "Packed grids"; hv_grid_pack.hip) ---------------------------------
+    _PACKED = ("hv_grid_", L.HvGridPackInfo, L.HvGridPackedHeader, GridPackStats,
+               ("voxel_size", "mode", "block_size", "record_bytes", "version", "next_object_id", "depth_threshold", "depth_decay_rate",
+                "blocks", "voxels", "extra_pairs", "bytes", "chain_nodes"))
+    _MODE = None  # the HV_MODE_* value of the concrete grid class
+    _NODES_PER_BLOCK, _MIN_NODES = 4, 1 << 16  # the overflow-node pool hv_create gives a probabilistic grid
+    _ALIAS_BLOCK_SIZE = None  # the direct-hash aliases: the block size their constructors fix
+
+    @classmethod
+    def _load_blocks(cls, hdr, max_blocks=None):
+        """The pool load() asks for: max_blocks or max(1024, 2 * blocks), raised to ceil(chain_nodes / 4) when the node pool that
+        comes with it (4 nodes per block, at least 65536) would not hold the map's chains."""
+        blocks = int(max_blocks or max(1024, 2 * hdr["blocks"]))
+        if hdr["chain_nodes"] > max(cls._MIN_NODES, cls._NODES_PER_BLOCK * blocks):
+            blocks = -(-hdr["chain_nodes"] // cls._NODES_PER_BLOCK)
+        return blocks
+
+    def pack(self, device=False):
+        """The whole grid as one packed buffer, bit for bit (include/hipvol.h "Packed grids"): every allocated block, of each the
+        voxels that hold anything - counts, position and colour sums, ids, both confidence counters, the label maps in insertion
+        order - and the process's next object id.  -> 1-D uint8, a numpy array, or with device=True a torch CUDA tensor on the
+        grid's GPU (nothing crosses PCIe).  Only reads the grid; waits for the GPU.  Pool size, owner settings, association
+        scratch, dropped_points() and label_overflows() are not part of a map."""
+        return self._pack(device)[0]
+
+    def unpack(self, buf):
+        """Fill this EMPTY grid (num_blocks() == 0; same class, block_size and voxel_size, bit for bit) from a packed buffer: numpy,
+        bytes-like or a torch uint8 tensor on either device.  The buffer is validated before a kernel writes anything; a corrupt or
+        foreign buffer, a non-empty or owner-sharded grid, a pool that cannot hold the map raise HipVolError with the library's
+        message and leave the grid unchanged.  Afterwards the grid holds the map that was packed, bit for bit, and every call
+        that is a function of the map answers as before; the POOL order is not part of a map (blocks are claimed in key order),
+        so what depends on it may differ: the row order of get_voxels(), and the class id of an object segment whose voxels
+        carry several classes (it is that of the segment's first voxel in pool order).  The
+        process's next object id is raised to the map's if it was lower.  The grid keeps its own depth threshold and decay rate
+        (load() applies the map's).  Waits for the GPU and returns GridPackStats."""
+        keep = getattr(self, "_keep_unread_map", None)  # (semantic grids: the id map of an association before a clear())
+        if keep is not None:
+            keep()
+        return self._unpack(buf)
+
+    def save(self, path):
+        """pack() into the file `path`: written to a temporary file in the same directory, then moved into place (os.replace), so
+        a reader never sees half a map.  -> GridPackStats."""
+        return self._save(path)
+
+    @classmethod
+    def load(cls, path, device=0, max_blocks=None, max_points=None):
+        """A new grid of this class holding the map save() wrote to `path`: voxel_size and block_size from the file's header, the
+        pool sized max_blocks or max(1024, 2 * blocks) - and large enough that the overflow-node pool (4 nodes per block, at least
+        65536) holds the map's chains; an explicit max_blocks that is too small for them is raised as well (_load_blocks) - and the
+        header's depth threshold and decay rate applied.  The grid is made by the class's own constructor.  ValueError when the
+        file holds a grid of another mode than this class's, or a block_size a direct-hash alias does not have."""
+        buf = cls._read_packed(path)
+        hdr = cls.packed_info(buf)
+        if cls._MODE is None or hdr["mode"] != cls._MODE:
+            raise ValueError(f"{path}: a packed grid of mode {hdr['mode']} cannot be loaded as {cls.__name__} (mode {cls._MODE})")
+        kw = dict(device=device, max_blocks=cls._load_blocks(hdr, max_blocks), max_points=max_points)
+        if cls._ALIAS_BLOCK_SIZE is None:
+            vol = cls(hdr["voxel_size"], hdr["block_size"], **kw)
+        elif hdr["block_size"] == cls._ALIAS_BLOCK_SIZE:
+            vol = cls(hdr["voxel_size"], **kw)
+        else:
+            raise ValueError(f"{path}: a packed grid of block_size {hdr['block_size']} cannot be loaded as {cls.__name__}, whose "
+                             f"blocks have {cls._ALIAS_BLOCK_SIZE}^3 voxels")
+        if hdr["mode"] != L.HV_MODE_VOXEL_GRID:
+            vol.set_depth_threshold(hdr["depth_threshold"])
+            vol.set_depth_decay_rate(hdr["depth_decay_rate"])
+        vol.unpack(buf)
+        return vol
+
+    @staticmethod
+    def packed_info(path_or_buffer):
+        """The header of a packed grid - {voxel_size, mode, block_size, record_bytes, version, next_object_id, depth_threshold,
+        depth_decay_rate, blocks, voxels, extra_pairs, bytes, chain_nodes} - after the library's validator (hv_grid_packed_check)
+        has passed the WHOLE buffer: a file path, or a buffer as unpack() takes it.  Needs no GPU.  ValueError with the validator's
+        message, which names the first rule that failed."""
+        return _packed_info(_BlockGrid._PACKED, path_or_buffer)
 
     def size(self):
         return self._int64(self._lib.hv_size)
@@ -1262,6 +1417,8 @@ class VoxelBlockGrid(_BlockGrid):
     unordered_map iteration order), so compare outputs as sets.
     """
 
+    _MODE = L.HV_MODE_VOXEL_GRID
+
     def __init__(self, voxel_size, block_size=8, device=0, max_blocks=None, max_points=None):
         super().__init__(L.HV_MODE_VOXEL_GRID, voxel_size, block_size, device, max_blocks, max_points)
 
@@ -1382,6 +1539,8 @@ class VoxelGrid(VoxelBlockGrid):
     by its scalar branch (HasColors = is_same<Tc, float>, voxel_grid.hpp:493-498) — mirrored here; with float32
     points + float32 colours an AVX2/SSE build accumulates batches of 4 in double (voxel_grid_simd.hpp) — not
     mirrored (the non-SIMD build, which is what the oracle compiles, matches bit for bit)."""
+
+    _ALIAS_BLOCK_SIZE = 8
 
     def __init__(self, voxel_size=0.05, device=0, max_blocks=None, max_points=None):
         super().__init__(voxel_size, 8, device=device, max_blocks=max_blocks, max_points=max_points)
@@ -2015,13 +2174,8 @@ class ScalableTSDFVolume(_Volume):
         L.check(self._lib.hv_tsdf_import_numerators(self._h, L.ptr(keys), keys.shape[0], L.ptr(payload), L.location(payload)))
 
     # -- packed maps: keeping and moving a map (include/hipvol.h "Packed maps"; hv_pack.hip) ---------------------------------------
-    def _pack(self, device):
-        info = L.HvPackInfo()
-        L.check(self._lib.hv_tsdf_pack_size(self._h, ctypes.byref(info)))
-        out = self._results({"map": ((info.bytes,), np.uint8)}, device, synchronize=False)["map"]
-        with self._ordered(out):
-            L.check(self._lib.hv_tsdf_pack(self._h, L.ptr(out), info.bytes, L.location(out), ctypes.byref(info)))
-        return out, _stats(PackStats, info)
+    _PACKED = ("hv_tsdf_", L.HvPackInfo, L.HvPackedHeader, PackStats,
+               ("voxel_length", "sdf_trunc", "resolution", "version", "units", "voxels", "bytes"))
 
     def pack(self, device=False):
         """The map as one packed buffer, bit for bit (include/hipvol.h "Packed maps"): every allocated unit, and of each the voxels
@@ -2037,43 +2191,12 @@ class ScalableTSDFVolume(_Volume):
         the volume unchanged.  Afterwards the volume behaves, call for call, like the one that was packed; every unit counts as
         dirty (dirty_keys()).  To merge a packed map into a map that already holds something, unpack it into a fresh volume and
         integrate_volume that.  Waits for the GPU and returns PackStats."""
-        op = _packed_operand(buf)
-        info = L.HvPackInfo()
-        with self._ordered(op):
-            L.check(self._lib.hv_tsdf_unpack(self._h, L.ptr(op), int(op.numel() if _is_torch(op) else op.size), L.location(op),
-                                             ctypes.byref(info)))
-        return _stats(PackStats, info)
+        return self._unpack(buf)
 
     def save(self, path):
         """pack() into the file `path`: written to a temporary file in the same directory, then moved into place (os.replace), so
         a reader never sees half a map.  -> PackStats."""
-        import os
-        import tempfile
-
-        buf, stats = self._pack(False)
-        path = os.fspath(path)
-        fd, tmp = tempfile.mkstemp(prefix=os.path.basename(path) + ".", suffix=".tmp", dir=os.path.dirname(os.path.abspath(path)))
-        try:
-            with os.fdopen(fd, "wb") as f:
-                f.write(memoryview(buf))
-            os.replace(tmp, path)
-        except BaseException:
-            if os.path.exists(tmp):
-                os.unlink(tmp)
-            raise
-        return stats
-
-    @staticmethod
-    def _read_packed(path):
-        import os
-
-        size = os.path.getsize(path)
-        buf = _result_array((size,), np.uint8)  # page-locked when large: the upload is one DMA
-        with open(path, "rb") as f:
-            got = f.readinto(memoryview(buf))
-        if got != size:
-            raise ValueError(f"{path}: read {got} of {size} bytes")
-        return buf
+        return self._save(path)
 
     @classmethod
     def load(cls, path, device=0, max_blocks=None):
@@ -2090,17 +2213,4 @@ class ScalableTSDFVolume(_Volume):
         """The header of a packed map - {voxel_length, sdf_trunc, resolution, version, units, voxels, bytes} - after the library's
         validator (hv_tsdf_packed_check) has passed the WHOLE buffer: a file path, or a buffer as unpack() takes it.  Needs no GPU.
         ValueError with the validator's message, which names the first rule that failed."""
-        import os
-
-        if isinstance(path_or_buffer, (str, os.PathLike)):
-            op = np.fromfile(path_or_buffer, dtype=np.uint8)
-        else:
-            op = _packed_operand(path_or_buffer)
-            if _is_torch(op):
-                op = op.cpu().numpy()
-        lib = L.load()
-        hdr = L.HvPackedHeader()
-        if lib.hv_tsdf_packed_check(L.ptr(op), int(op.size), ctypes.byref(hdr)) != L.HV_OK:
-            raise ValueError((lib.hv_last_error() or b"hv_tsdf_packed_check failed").decode())
-        return {"voxel_length": hdr.voxel_length, "sdf_trunc": hdr.sdf_trunc, "resolution": hdr.resolution, "version": hdr.version,
-                "units": hdr.units, "voxels": hdr.voxels, "bytes": hdr.bytes}
+        return _packed_info(ScalableTSDFVolume._PACKED, path_or_buffer)

@@ -749,12 +749,16 @@ class VoxelSemanticGrid(VoxelBlockSemanticGrid):
     """``volumetric.VoxelSemanticGrid(voxel_size)``: the direct-hash variant of the voting grid
     (cpp/volumetric/voxel_semantic_grid.h); same payload and observable results as the block grid."""
 
+    _ALIAS_BLOCK_SIZE = 8
+
     def __init__(self, voxel_size=0.05, device=0, max_blocks=None, max_points=None):
         super().__init__(voxel_size, 8, device=device, max_blocks=max_blocks, max_points=max_points)
 
 
 class VoxelSemanticGridProbabilistic(VoxelBlockSemanticProbabilisticGrid):
     """``volumetric.VoxelSemanticGridProbabilistic(voxel_size)`` (direct-hash variant, same payload)."""
+
+    _ALIAS_BLOCK_SIZE = 8
 
     def __init__(self, voxel_size=0.05, device=0, max_blocks=None, max_points=None):
         super().__init__(voxel_size, 8, device=device, max_blocks=max_blocks, max_points=max_points)
@@ -763,12 +767,16 @@ class VoxelSemanticGridProbabilistic(VoxelBlockSemanticProbabilisticGrid):
 class VoxelSemanticGrid2(VoxelBlockSemanticGrid2):
     """``volumetric.VoxelSemanticGrid2(voxel_size)`` (direct-hash variant, same payload; volumetric_grid_module.h:987-990)."""
 
+    _ALIAS_BLOCK_SIZE = 8
+
     def __init__(self, voxel_size=0.05, device=0, max_blocks=None, max_points=None):
         super().__init__(voxel_size, 8, device=device, max_blocks=max_blocks, max_points=max_points)
 
 
 class VoxelSemanticGridProbabilistic2(VoxelBlockSemanticProbabilisticGrid2):
     """``volumetric.VoxelSemanticGridProbabilistic2(voxel_size)`` (direct-hash variant, same payload; :1000-1004)."""
+
+    _ALIAS_BLOCK_SIZE = 8
 
     def __init__(self, voxel_size=0.05, device=0, max_blocks=None, max_points=None):
         super().__init__(voxel_size, 8, device=device, max_blocks=max_blocks, max_points=max_points)
