@@ -457,10 +457,10 @@ struct hv_volume {
     void *semb_tasks = nullptr;              // semantic bucket path: the big buckets' (block, voxel range) tasks
     size_t semb_tasks_bytes = 0;
 
-    // staging for HV_HOST inputs
-    void *stage_a = nullptr;
-    void *stage_b = nullptr;
-    size_t stage_a_bytes = 0, stage_b_bytes = 0;
+    // staging of a call's HV_HOST arguments, inputs and outputs alike, behind its device scratch (HvStage).  Apart from out_*: a
+    // ray cast, a sample or a lookup leaves the extraction caches valid
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
     // pipelined staging of host-resident FRAMES (hv_stage_frames): caller memory -> one of two page-locked slots (worker
     // threads) -> DMA on a copy stream into one of two device sets, so that the next sub-chunk is copied by the CPU while
     // the previous one crosses PCIe, and batch k+1 crosses PCIe while batch k is swept
@@ -522,10 +522,6 @@ struct hv_volume {
     void *out_b = nullptr;
     void *out_c = nullptr;
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
-    void *raycast_buf = nullptr; // HV_HOST outputs of hv_tsdf_ray_cast (apart from out_*: a cast leaves the extraction caches valid)
-    size_t raycast_buf_bytes = 0;
-    void *sample_buf = nullptr;  // hv_tsdf_sample_points / hv_tsdf_check_frame / hv_lookup_points: counters and HV_HOST outputs (hv_stage_out)
-    size_t sample_buf_bytes = 0;
     void *dist_buf = nullptr;    // hv_tsdf_distance_field: counters, the intermediate grid, classes and HV_HOST outputs (hv_distance.hip)
     size_t dist_buf_bytes = 0;
     void *track_buf = nullptr;   // hv_tsdf_track: source pyramid, model casts, reduction slab, state and trace (device)
@@ -599,16 +595,54 @@ struct HvScratch {
 // hv_prep.hip: n_frames device-resident frames through the volume's rectify maps, queued on `s`
 int hv_rectify_frames_device(hv_volume *v, hipStream_t s, const void *d_depth, int32_t depth_dtype, const uint8_t *d_rgb, int n_frames,
                              int height, int width, void *d_depth_out, uint8_t *d_rgb_out);
-int hv_stage_in(hv_volume *v, const void *src, size_t bytes, int32_t loc, int which, const void **dev);
-// hv_sample.hip: device addresses of a query's outputs (at most 8) - the caller's own arrays (HV_DEVICE), or 256-byte aligned pieces of
-// v->sample_buf behind `head` bytes (HV_HOST; an output of size 0 gets nullptr), which the caller copies back
-int hv_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes, void *const *user, void **dev, int count);
-// hipMemcpyAsync(H2D) of a caller's array on the volume's stream; waits for the copy when the source is page-locked (the DMA would
-// otherwise read it after the call has returned: the ABI borrows host arrays for the duration of the call only)
-int hv_h2d(hv_volume *v, void *dst, const void *src, size_t bytes);
-// several arrays of one call: queue them with hv_h2d_lazy (sets *pending when a source is page-locked), then ONE hv_h2d_fence
+// ---- host / device arguments of one call (hv_stage.hip) ----
+// Every entry point takes `loc`: HV_DEVICE arrays are used in place, HV_HOST inputs are copied into a staging buffer of the volume,
+// HV_HOST outputs are laid out in it and copied back before the call returns.  One call, three steps:
+//   declare  head(bytes): device scratch at the front of the buffer (counters, histograms), for either loc; in(src, bytes) /
+//            out(dst, bytes) return an index; a null pointer or zero bytes declares an absent argument
+//   commit   HV_DEVICE: every pointer passes through (the buffer is touched only for a head).  HV_HOST: the pieces are laid out
+//            256-byte aligned behind the head, the buffer grows ONCE (hv_ensure_buffer frees and reallocates: a pointer handed out
+//            before a later growth would dangle), then every input is queued with hv_h2d_lazy and ONE hv_h2d_fence waits for those
+//            whose source is page-locked.  dev(i) is valid from here on (null for an absent argument)
+//   finish   HV_HOST: the present outputs are copied back (rows(m) before it: m rows of those declared with a row size); `extra`
+//            receives extra_bytes of the head (or of extra_dev); the stream is synchronised once, and only if something was copied
+struct HvStage {
+    static constexpr int MAX_PIECES = 8;
+    struct Piece {
+        void *user;
+        size_t bytes, row_bytes;
+        bool out, staged;
+        void *dev;
+    };
+    hv_volume *v;
+    int32_t loc;
+    size_t head_bytes = 0;
+    void *head_dev = nullptr;
+    int count = 0;
+    bool overflow = false;
+    Piece piece[MAX_PIECES];
+    HvStage(hv_volume *volume, int32_t where) : v(volume), loc(where) {}
+    void head(size_t bytes) { head_bytes = bytes; }
+    // where: HV_HOST / HV_DEVICE for an argument that does not follow the call's loc (key lists that are host memory by contract)
+    int in(const void *src, size_t bytes, int32_t where = -1) { return add(const_cast<void *>(src), bytes, 0, false, where); }
+    int out(void *dst, size_t bytes, size_t row_bytes = 0) { return add(dst, bytes, row_bytes, true, -1); }
+    int commit(void **buf, size_t *cur);
+    template <typename T> T *dev(int i) const { return (T *)piece[i].dev; }
+    void rows(int64_t m);
+    int finish(void *extra = nullptr, size_t extra_bytes = 0, const void *extra_dev = nullptr);
+    int add(void *user, size_t bytes, size_t row_bytes, bool is_out, int32_t where);
+};
+// hipMemcpyAsync(H2D) of a caller's array on the volume's stream (hv_stage.hip).  A page-locked source is read by the DMA engine after
+// the call returns, and the ABI borrows host arrays for the duration of the call only: queue a call's arrays with hv_h2d_lazy (sets
+// *pending when a source is page-locked), then ONE hv_h2d_fence
 int hv_h2d_lazy(hv_volume *v, void *dst, const void *src, size_t bytes, bool *pending);
 int hv_h2d_fence(hv_volume *v, bool pending);
+int hv_h2d(hv_volume *v, void *dst, const void *src, size_t bytes); // one array: hv_h2d_lazy + hv_h2d_fence
+bool hv_host_is_registered(const void *p, size_t bytes); // hv_core.hip: inside a range page-locked with hv_host_register
+// the commonest call: a frame's depth and colour planes (npx pixels: of one frame, or of a batch's frames behind each other; rgb may
+// be null) as its only staged arguments
+int hv_stage_frame(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, size_t npx, int32_t loc, const void **d_depth,
+                   const uint8_t **d_rgb);
 // Host-resident frames -> device (pipelined, see hv_volume::hs_*).  Frame f's depth is depth_ptrs[f] when depth_ptrs is given,
 // else depth_base + f * depth_frame_bytes (same for colour).  Returns the device arrays (frames contiguous) and the set whose
 // hs_dev_ready event the consuming stream has to wait for; hv_stage_frames_consumed records hs_dev_free on that stream after

@@ -679,8 +679,13 @@ extern "C" int hv_tsdf_surface_components(hv_volume *v, double weight_threshold,
     HV_REQUIRE(!want_table || component_cap >= L.components, HV_ERR_INVALID, "%s: %lld components, room for %lld", fn, (long long)L.components,
                (long long)component_cap);
     HV_REQUIRE(!want_list || site_cap >= L.sites, HV_ERR_INVALID, "%s: %lld sites, room for %lld", fn, (long long)L.sites, (long long)site_cap);
+    // (the sizes are known only now, after the labelling: an empty map has no outputs)
     const size_t c = (size_t)L.components, n = (size_t)L.sites;
-    const bool dev = loc == HV_DEVICE;
+    HvStage st(v, loc);
+    const int o_seed = st.out(seed, 12 * c), o_sites = st.out(sites, 8 * c), o_lo = st.out(lo, 12 * c), o_hi = st.out(hi, 12 * c);
+    const int o_index = st.out(site_index, 12 * n), o_label = st.out(site_label, 4 * n);
+    rc = st.commit(&v->stage, &v->stage_bytes);
+    if (rc != HV_OK) return rc;
     if (c > 0) {
         uint32_t *perm = nullptr, *rank = nullptr;
         if (want_table || site_label != nullptr) {
@@ -706,41 +711,24 @@ extern "C" int hv_tsdf_surface_components(hv_volume *v, double weight_threshold,
             hv_profile_end(v, 0);
             perm = perm_a;
         }
-        int32_t *d_seed = seed, *d_lo = lo, *d_hi = hi;
-        int64_t *d_sites = sites;
-        if (!dev) {
-            if (seed != nullptr) HV_HIP(S.get(&d_seed, 3 * c));
-            if (sites != nullptr) HV_HIP(S.get(&d_sites, c));
-            if (lo != nullptr) HV_HIP(S.get(&d_lo, 3 * c));
-            if (hi != nullptr) HV_HIP(S.get(&d_hi, 3 * c));
-        }
         hv_profile_begin(v);
         hipLaunchKernelGGL(k_cc_table, dim3((unsigned)((c + 255) / 256)), dim3(256), 0, v->stream, (const uint32_t *)perm, (const uint32_t *)L.cnt,
-                           (const int32_t *)L.box, (uint32_t)c, rank, d_seed, d_sites, d_lo, d_hi, (int64_t)0, L.result);
+                           (const int32_t *)L.box, (uint32_t)c, rank, st.dev<int32_t>(o_seed), st.dev<int64_t>(o_sites), st.dev<int32_t>(o_lo),
+                           st.dev<int32_t>(o_hi), (int64_t)0, L.result);
         hv_profile_end(v, 0);
-        int32_t *d_index = site_index, *d_label = site_label;
         if (want_list) {
-            if (!dev && site_index != nullptr) HV_HIP(S.get(&d_index, 3 * n));
-            if (!dev && site_label != nullptr) HV_HIP(S.get(&d_label, n));
             hv_profile_begin(v);
             hipLaunchKernelGGL(k_cc_list, dim3((unsigned)L.units), dim3(256), 0, v->stream, (const unsigned long long *)v->table.block_keys,
                                (const uint16_t *)L.mask, (const uint16_t *)L.rowpre, (const uint32_t *)L.count, (const uint32_t *)L.base,
-                               (const uint32_t *)L.parent, (const uint32_t *)L.aux, (const uint32_t *)rank, d_index, d_label);
+                               (const uint32_t *)L.parent, (const uint32_t *)L.aux, (const uint32_t *)rank, st.dev<int32_t>(o_index),
+                               st.dev<int32_t>(o_label));
             hv_profile_end(v, L.units);
         }
         HV_HIP(hipGetLastError());
-        if (!dev) {
-            if (seed != nullptr) HV_HIP(hipMemcpyAsync(seed, d_seed, 12 * c, hipMemcpyDeviceToHost, v->stream));
-            if (sites != nullptr) HV_HIP(hipMemcpyAsync(sites, d_sites, 8 * c, hipMemcpyDeviceToHost, v->stream));
-            if (lo != nullptr) HV_HIP(hipMemcpyAsync(lo, d_lo, 12 * c, hipMemcpyDeviceToHost, v->stream));
-            if (hi != nullptr) HV_HIP(hipMemcpyAsync(hi, d_hi, 12 * c, hipMemcpyDeviceToHost, v->stream));
-            if (site_index != nullptr) HV_HIP(hipMemcpyAsync(site_index, d_index, 12 * n, hipMemcpyDeviceToHost, v->stream));
-            if (site_label != nullptr) HV_HIP(hipMemcpyAsync(site_label, d_label, 4 * n, hipMemcpyDeviceToHost, v->stream));
-        }
     }
     unsigned long long h[CC_R_WORDS];
-    HV_HIP(hipMemcpyAsync(h, L.result, sizeof(h), hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipStreamSynchronize(v->stream)); // the scratch is freed on return: everything queued has run
+    rc = st.finish(h, sizeof(h), L.result); // (always waits: the scratch is freed on return, everything queued has run)
+    if (rc != HV_OK) return rc;
     if (stats != nullptr) {
         stats->units = L.units;
         stats->sites = L.sites;

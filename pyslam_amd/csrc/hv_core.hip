@@ -49,20 +49,6 @@ void hv_invert4x4(const double *m, double *out) {
     for (int i = 0; i < 16; ++i) out[i] = a[i] * inv_det;
 }
 
-int hv_ensure_buffer(hv_volume *v, void **buf, size_t *cur, size_t want) {
-    if (*cur >= want && *buf != nullptr) return HV_OK;
-    if (*buf) {
-        HV_HIP(hipStreamSynchronize(v->stream));
-        HV_HIP(hipFree(*buf));
-        *buf = nullptr;
-        *cur = 0;
-    }
-    size_t bytes = want < 4096 ? 4096 : want + want / 4;
-    HV_HIP(hipMalloc(buf, bytes));
-    *cur = bytes;
-    return HV_OK;
-}
-
 int hv_read_counters(hv_volume *v) {
     HV_HIP(hipMemcpyAsync(v->h_counters, v->table.counters, sizeof(int32_t) * HV_CNT_COUNT,
                           hipMemcpyDeviceToHost, v->stream));
@@ -109,66 +95,6 @@ int hv_tsdf_key_order(hv_volume *v, int64_t used, std::vector<int32_t> &order, s
         if (xyz_in_order != nullptr) memcpy(&(*xyz_in_order)[r * 3], ranked[r].data(), 12);
     }
     return HV_OK;
-}
-
-// HV_HOST inputs are copied into a device staging buffer on the volume's stream; HV_DEVICE inputs
-// are used in place.
-int hv_stage_in(hv_volume *v, const void *src, size_t bytes, int32_t loc, int which, const void **dev) {
-    if (src == nullptr || bytes == 0) {
-        *dev = nullptr;
-        return HV_OK;
-    }
-    if (loc == HV_DEVICE) {
-        *dev = src;
-        return HV_OK;
-    }
-    void **buf = which == 0 ? &v->stage_a : &v->stage_b;
-    size_t *cur = which == 0 ? &v->stage_a_bytes : &v->stage_b_bytes;
-    int rc = hv_ensure_buffer(v, buf, cur, bytes);
-    if (rc != HV_OK) return rc;
-    rc = hv_h2d(v, *buf, src, bytes);
-    if (rc != HV_OK) return rc;
-    *dev = *buf;
-    return HV_OK;
-}
-
-// Host -> device copy of a caller's array on the volume's stream.  The C ABI borrows HV_HOST arrays "for the duration of the call":
-// a pageable source is read by the runtime before hipMemcpyAsync returns, but a PAGE-LOCKED source (the front's shared-memory ring
-// after hv_host_register, a torch pinned tensor, hipHostMalloc memory) is read by the DMA engine later, when the stream gets there -
-// the caller may have refilled the memory by then (a ring slot released while its copy was still queued).  So the
-// host waits for the copy when the source is page-locked; the kernels behind it stay asynchronous.
-static bool hv_host_is_registered(const void *p, size_t bytes);
-static bool hv_host_is_pinned(const void *p, size_t bytes) {
-    if (hv_host_is_registered(p, bytes)) return true;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError(); // plain malloc / numpy memory: "invalid value", not an error of ours
-        return false;
-    }
-    return attr.type == hipMemoryTypeHost;
-}
-
-int hv_h2d_lazy(hv_volume *v, void *dst, const void *src, size_t bytes, bool *pending) {
-    if (bytes == 0) return HV_OK;
-    HV_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, v->stream));
-    if (hv_host_is_pinned(src, bytes)) *pending = true;
-    return HV_OK;
-}
-
-// (an event right behind the copies, not the whole stream: a caller whose keyframes sit in page-locked memory would otherwise wait
-// for every kernel queued before this call as well - ADVICE r05)
-int hv_h2d_fence(hv_volume *v, bool pending) {
-    if (!pending) return HV_OK;
-    if (v->ev_h2d == nullptr) HV_HIP(hipEventCreateWithFlags(&v->ev_h2d, hipEventDisableTiming));
-    HV_HIP(hipEventRecord(v->ev_h2d, v->stream));
-    HV_HIP(hipEventSynchronize(v->ev_h2d));
-    return HV_OK;
-}
-
-int hv_h2d(hv_volume *v, void *dst, const void *src, size_t bytes) {
-    bool pending = false;
-    const int rc = hv_h2d_lazy(v, dst, src, bytes, &pending);
-    return rc != HV_OK ? rc : hv_h2d_fence(v, pending);
 }
 
 // ---- pipelined staging of host-resident frames ------------------------------------------------------------------------
@@ -274,7 +200,7 @@ std::mutex g_host_ranges_m;
 std::vector<HvHostRange> g_host_ranges;
 
 } // namespace
-static bool hv_host_is_registered(const void *p, size_t bytes) {
+bool hv_host_is_registered(const void *p, size_t bytes) {
     std::lock_guard<std::mutex> lk(g_host_ranges_m);
     for (const HvHostRange &r : g_host_ranges)
         if ((const char *)p >= r.lo && (const char *)p + bytes <= r.hi) return true;
@@ -725,9 +651,9 @@ void hv_destroy(hv_volume *v) {
     if (v->hs_stream) (void)hipStreamDestroy(v->hs_stream);
     void *bufs[] = {v->table.keys, v->table.vals, v->table.block_keys, v->table.counters, v->pool,
                     v->touched_stamp, v->touched_list, v->touched_mask, v->frame_px,
-                    v->stage_a, v->stage_b, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in,
+                    v->stage, v->sort_keys_in, v->sort_keys_out, v->sort_vals_in,
                     v->sort_vals_out, v->sort_tmp, v->scratch_points, v->scratch_colors, v->out_a,
-                    v->out_b, v->out_c, v->rect_map_x, v->rect_map_y, v->rect_buf, v->batch_buf, v->assoc_buf, v->mult_table, v->bins.cnt, v->bins.inl, v->bins.touched, v->bins.len, v->bins.pg_keys, v->bins.pg_data, v->bin_rec, v->batch_buf2, v->unit_masks, v->occ, v->semb_tasks, v->table.prob_nodes, v->shadow_ring, v->mc_cache, v->pc_cache, v->kf_buf, v->halo_plan, v->raycast_buf, v->track_buf, v->deint_buf, v->sample_buf, v->dist_buf};
+                    v->out_b, v->out_c, v->rect_map_x, v->rect_map_y, v->rect_buf, v->batch_buf, v->assoc_buf, v->mult_table, v->bins.cnt, v->bins.inl, v->bins.touched, v->bins.len, v->bins.pg_keys, v->bins.pg_data, v->bin_rec, v->batch_buf2, v->unit_masks, v->occ, v->semb_tasks, v->table.prob_nodes, v->shadow_ring, v->mc_cache, v->pc_cache, v->kf_buf, v->halo_plan, v->track_buf, v->deint_buf, v->dist_buf};
     for (void *b : bufs)
         if (b) (void)hipFree(b);
     if (v->h_counters) (void)hipHostFree(v->h_counters);

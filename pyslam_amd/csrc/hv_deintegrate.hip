@@ -333,18 +333,6 @@ static int deint_read_stats(hv_volume *v, hv_deintegrate_stats *stats) {
     return HV_OK;
 }
 
-// Frames at `loc` -> device (HV_HOST: the staging buffers, one copy for the whole call).
-static int deint_stage(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int32_t n_frames, int32_t H, int32_t W,
-                       int32_t loc, const void **d_depth, const uint8_t **d_rgb) {
-    const size_t npx = (size_t)H * W * (size_t)n_frames;
-    int rc = hv_stage_in(v, depth, npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, d_depth);
-    if (rc != HV_OK) return rc;
-    const void *c = nullptr;
-    rc = hv_stage_in(v, rgb, npx * 3, loc, 1, &c);
-    *d_rgb = (const uint8_t *)c;
-    return rc;
-}
-
 extern "C" {
 
 int hv_tsdf_deintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int32_t n_frames, int32_t height,
@@ -355,7 +343,7 @@ int hv_tsdf_deintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dty
     HV_HIP(hipSetDevice(v->device));
     const void *d_depth = nullptr;
     const uint8_t *d_rgb = nullptr;
-    rc = deint_stage(v, depth, depth_dtype, rgb, n_frames, height, width, loc, &d_depth, &d_rgb);
+    rc = hv_stage_frame(v, depth, depth_dtype, rgb, (size_t)height * width * (size_t)n_frames, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     rc = tsdf_deintegrate_device(v, d_depth, depth_dtype, d_rgb, n_frames, height, width, intr, T_cw, depth_scale, depth_trunc, true,
                                  stats != nullptr);
@@ -378,7 +366,7 @@ int hv_tsdf_reintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dty
     HV_HIP(hipSetDevice(v->device));
     const void *d_depth = nullptr;
     const uint8_t *d_rgb = nullptr;
-    rc = deint_stage(v, depth, depth_dtype, rgb, n_frames, height, width, loc, &d_depth, &d_rgb);
+    rc = hv_stage_frame(v, depth, depth_dtype, rgb, (size_t)height * width * (size_t)n_frames, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     // the frames go through the camera's rectify maps once, for both halves (rect_buf holds all of them)
     rc = tsdf_rectify(v, v->stream, &d_depth, depth_dtype, &d_rgb, n_frames, height, width);

@@ -188,29 +188,20 @@ extern "C" int hv_tsdf_distance_field(hv_volume *v, const hv_distance_params *p,
 
     // the transform runs when something needs it; a call for the classes alone stops after the classification
     const bool passes = distance != nullptr || dist2 != nullptr || stats != nullptr;
-    const bool dev = loc == HV_DEVICE;
-    // scratch: [5 counters, 256 B][grid u32: the caller's dist2 when that is device memory][classes: ditto][distance for HV_HOST]
+    // head: [5 counters, 256 B][grid u32, unless the caller's dist2 takes it][classes, unless the caller's cls does]; an output the
+    // caller asked for is the caller's own array (HV_DEVICE) or a staged piece (HV_HOST)
     const size_t n = (size_t)cells, pad = 255;
-    size_t off_grid = 0, off_cls = 0, off_dist = 0, total = 256;
-    if (passes && !(dev && dist2 != nullptr)) {
-        off_grid = total;
-        total += (4 * n + pad) & ~pad;
-    }
-    if (!(dev && cls != nullptr)) {
-        off_cls = total;
-        total += (n + pad) & ~pad;
-    }
-    if (!dev && distance != nullptr) {
-        off_dist = total;
-        total += (4 * n + pad) & ~pad;
-    }
-    const int rc = hv_ensure_buffer(v, &v->dist_buf, &v->dist_buf_bytes, total);
+    const size_t off_grid = 256, off_cls = off_grid + (passes && dist2 == nullptr ? (4 * n + pad) & ~pad : 0);
+    HvStage st(v, loc);
+    st.head(off_cls + (cls == nullptr ? (n + pad) & ~pad : 0));
+    const int o_dist = st.out(distance, 4 * n), o_grid = st.out(dist2, 4 * n), o_cls = st.out(cls, n);
+    int rc = st.commit(&v->dist_buf, &v->dist_buf_bytes);
     if (rc != HV_OK) return rc;
-    char *buf = (char *)v->dist_buf;
+    char *buf = (char *)st.head_dev;
     unsigned long long *d_count = stats != nullptr ? (unsigned long long *)buf : nullptr;
-    uint32_t *d_grid = !passes ? nullptr : (off_grid ? (uint32_t *)(buf + off_grid) : dist2);
-    uint8_t *d_cls = off_cls ? (uint8_t *)(buf + off_cls) : cls;
-    float *d_dist = distance == nullptr ? nullptr : (off_dist ? (float *)(buf + off_dist) : distance);
+    uint32_t *d_grid = !passes ? nullptr : (dist2 != nullptr ? st.dev<uint32_t>(o_grid) : (uint32_t *)(buf + off_grid));
+    uint8_t *d_cls = cls != nullptr ? st.dev<uint8_t>(o_cls) : (uint8_t *)(buf + off_cls);
+    float *d_dist = st.dev<float>(o_dist);
     // reads only, as hv_tsdf_ray_cast: the next batch starts a fresh touch + pack chain behind this call
     v->pipe_armed = false;
 
@@ -251,22 +242,15 @@ extern "C" int hv_tsdf_distance_field(hv_volume *v, const hv_distance_params *p,
         hv_profile_end(v, 0);
     }
     HV_HIP(hipGetLastError());
-    if (!dev) {
-        if (distance != nullptr) HV_HIP(hipMemcpyAsync(distance, d_dist, 4 * n, hipMemcpyDeviceToHost, v->stream));
-        if (dist2 != nullptr) HV_HIP(hipMemcpyAsync(dist2, d_grid, 4 * n, hipMemcpyDeviceToHost, v->stream));
-        if (cls != nullptr) HV_HIP(hipMemcpyAsync(cls, d_cls, n, hipMemcpyDeviceToHost, v->stream));
-    }
+    unsigned long long h[DF_N_COUNT];
+    rc = st.finish(stats != nullptr ? h : nullptr, sizeof(h));
+    if (rc != HV_OK) return rc;
     if (stats != nullptr) {
-        unsigned long long h[DF_N_COUNT];
-        HV_HIP(hipMemcpyAsync(h, d_count, sizeof(h), hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
         stats->unknown = (int64_t)h[DF_N_UNKNOWN];
         stats->free = (int64_t)h[DF_N_FREE];
         stats->inside = (int64_t)h[DF_N_INSIDE];
         stats->sites = (int64_t)h[DF_N_SITES];
         stats->far = (int64_t)h[DF_N_FAR];
-    } else if (!dev) {
-        HV_HIP(hipStreamSynchronize(v->stream));
     }
     return HV_OK;
 }

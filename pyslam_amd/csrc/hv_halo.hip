@@ -329,25 +329,16 @@ int hv_tsdf_export_numerators(hv_volume *v, const int32_t *keys, int64_t k, floa
     HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_tsdf_export_numerators: not a TSDF volume");
     if (k == 0) return HV_OK;
     HV_HIP(hipSetDevice(v->device));
-    const void *d_keys = nullptr;
-    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
+    HvStage st(v, loc); // (the keys are host memory by contract)
+    const int i_keys = st.in(keys, sizeof(int32_t) * 3 * (size_t)k, HV_HOST), o_payload = st.out(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const size_t bytes = sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k;
-    float *d_payload = payload;
-    if (loc == HV_HOST) {
-        v->mesh_cache_version = v->points_cache_version = 0; // out_a is about to be overwritten
-        rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, bytes);
-        if (rc != HV_OK) return rc;
-        d_payload = (float *)v->out_a;
-    }
     const int64_t total = k * HV_TSDF_RRR;
     hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const char *)v->pool, (const int32_t *)d_keys, k, d_payload);
+                       (const char *)v->pool, st.dev<const int32_t>(i_keys), k, st.dev<float>(o_payload));
     HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(payload, d_payload, bytes, hipMemcpyDeviceToHost, v->stream));
-    }
-    HV_HIP(hipStreamSynchronize(v->stream));
+    if ((rc = st.finish()) != HV_OK) return rc;
+    HV_HIP(hipStreamSynchronize(v->stream)); // (a device payload too: this call has always been complete on return)
     return HV_OK;
 }
 
@@ -359,11 +350,11 @@ int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, cons
     v->content_version += 1;
     v->extract_epoch += 1; // (writes voxels without stamping their units)
     HV_HIP(hipSetDevice(v->device));
-    const void *d_keys = nullptr, *d_payload = nullptr;
-    int rc = hv_stage_in(v, keys, sizeof(int32_t) * 3 * k, HV_HOST, 0, &d_keys);
+    HvStage st(v, loc); // (the keys are host memory by contract)
+    const int i_keys = st.in(keys, sizeof(int32_t) * 3 * (size_t)k, HV_HOST), i_payload = st.in(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k, loc, 1, &d_payload);
-    if (rc != HV_OK) return rc;
+    const void *d_keys = st.dev<const void>(i_keys), *d_payload = st.dev<const void>(i_payload);
     // the imported units are claimed first and the claims verified (this call synchronises anyway): a pool that is too small
     // grows before anything is written, or the call fails with the volume unchanged (a gather onto a root whose
     // pool was sized like every other rank's)
@@ -542,21 +533,16 @@ int hv_merge_halo_unpack(hv_volume *v, const int32_t *shared_keys, int64_t k, co
     v->content_version += 1;
     v->extract_epoch += 1; // (writes voxels without stamping their units)
     HV_HIP(hipSetDevice(v->device));
-    // keys + actions in one staging buffer, payload in the other
-    std::vector<char> host((size_t)k * 13);
-    memcpy(host.data(), shared_keys, (size_t)k * 12);
-    memcpy(host.data() + (size_t)k * 12, action, (size_t)k);
-    const void *d_ka = nullptr, *d_payload = nullptr;
-    int rc = hv_stage_in(v, host.data(), host.size(), HV_HOST, 0, &d_ka);
-    if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k, loc, 1, &d_payload);
+    HvStage st(v, loc); // (the keys and the actions are host memory by contract)
+    const int i_keys = st.in(shared_keys, (size_t)k * 12, HV_HOST), i_action = st.in(action, (size_t)k, HV_HOST),
+              i_payload = st.in(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
+    const int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
     const int64_t total = k * HV_TSDF_RRR;
     hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (char *)v->pool, (const int32_t *)d_ka, k, (const float *)d_payload,
-                       (const uint8_t *)d_ka + (size_t)k * 12);
+                       (char *)v->pool, st.dev<const int32_t>(i_keys), k, st.dev<const float>(i_payload), st.dev<const uint8_t>(i_action));
     HV_HIP(hipGetLastError());
-    HV_HIP(hipStreamSynchronize(v->stream)); // `host` goes out of scope
+    HV_HIP(hipStreamSynchronize(v->stream)); // (this call has always been complete on return)
     return HV_OK;
 }
 

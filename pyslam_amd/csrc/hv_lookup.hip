@@ -324,18 +324,16 @@ extern "C" int hv_lookup_points(hv_volume *v, const void *points, int32_t point_
     if (n == 0) return HV_OK;
     HV_HIP(hipSetDevice(v->device));
 
-    // staging: [4 status counters, 256 B][the outputs] (the outputs only for HV_HOST)
+    // head: the 4 status counters
     const size_t un = (size_t)n;
-    const size_t head = stats != nullptr ? 256 : 0;
-    const size_t sizes[7] = {status ? un : 0,       count ? 4 * un : 0,     position ? 24 * un : 0,  color ? 12 * un : 0,
-                             class_id ? 4 * un : 0, object_id ? 4 * un : 0, confidence ? 4 * un : 0};
-    void *user[7] = {status, count, position, color, class_id, object_id, confidence};
-    void *dev[7];
-    int rc = hv_stage_out(v, loc, head, sizes, user, dev, 7);
+    HvStage st(v, loc);
+    st.head(stats != nullptr ? 256 : 0);
+    const int i_points = st.in(points, un * 3 * (point_dtype == HV_F64 ? 8 : 4));
+    const int o_status = st.out(status, un), o_count = st.out(count, 4 * un), o_position = st.out(position, 24 * un), o_color = st.out(color, 12 * un),
+              o_class = st.out(class_id, 4 * un), o_object = st.out(object_id, 4 * un), o_conf = st.out(confidence, 4 * un);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const void *d_points = nullptr;
-    rc = hv_stage_in(v, points, un * 3 * (point_dtype == HV_F64 ? 8 : 4), loc, 0, &d_points);
-    if (rc != HV_OK) return rc;
+    const void *d_points = st.dev<const void>(i_points);
 
     HvLookupArgs A{};
     A.G = grid_params(v);
@@ -344,14 +342,14 @@ extern "C" int hv_lookup_points(hv_volume *v, const void *points, int32_t point_
     A.min_confidence = p->min_confidence;
     A.radius = p->radius;
     A.occ = plain ? nullptr : v->occ;
-    A.status = (uint8_t *)dev[0];
-    A.count = (int32_t *)dev[1];
-    A.position = (double *)dev[2];
-    A.color = (float *)dev[3];
-    A.class_id = (int32_t *)dev[4];
-    A.object_id = (int32_t *)dev[5];
-    A.confidence = (float *)dev[6];
-    A.stat = stats != nullptr ? (unsigned long long *)v->sample_buf : nullptr;
+    A.status = st.dev<uint8_t>(o_status);
+    A.count = st.dev<int32_t>(o_count);
+    A.position = st.dev<double>(o_position);
+    A.color = st.dev<float>(o_color);
+    A.class_id = st.dev<int32_t>(o_class);
+    A.object_id = st.dev<int32_t>(o_object);
+    A.confidence = st.dev<float>(o_conf);
+    A.stat = (unsigned long long *)st.head_dev;
     if (A.stat != nullptr) HV_HIP(hipMemsetAsync(A.stat, 0, 4 * sizeof(unsigned long long), v->stream));
     const bool f64 = point_dtype == HV_F64;
     hv_profile_begin(v);
@@ -362,21 +360,15 @@ extern "C" int hv_lookup_points(hv_volume *v, const void *points, int32_t point_
     }
     hv_profile_end(v, 0);
     HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        for (int i = 0; i < 7; ++i)
-            if (sizes[i]) HV_HIP(hipMemcpyAsync(user[i], dev[i], sizes[i], hipMemcpyDeviceToHost, v->stream));
-    }
+    unsigned long long h_count[4];
+    rc = st.finish(stats != nullptr ? h_count : nullptr, sizeof(h_count));
+    if (rc != HV_OK) return rc;
     if (stats != nullptr) {
-        unsigned long long h_count[4];
-        HV_HIP(hipMemcpyAsync(h_count, A.stat, sizeof(h_count), hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
         stats->points = n;
         stats->missing = (int64_t)h_count[HV_LOOKUP_MISSING];
         stats->own = (int64_t)h_count[HV_LOOKUP_OWN];
         stats->near = (int64_t)h_count[HV_LOOKUP_NEAR];
         stats->invalid = (int64_t)h_count[HV_LOOKUP_INVALID];
-    } else if (loc == HV_HOST) {
-        HV_HIP(hipStreamSynchronize(v->stream));
     }
     return HV_OK;
 }

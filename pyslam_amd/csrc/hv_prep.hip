@@ -144,24 +144,13 @@ extern "C" int hv_remap(hv_volume *v, const void *src, int32_t src_kind, int32_t
     const int64_t npx = (int64_t)height * width;
     const size_t esz = src_kind == HV_IMG_U8 ? 1 : 4;
     const size_t img_bytes = esz * channels * npx, map_bytes = sizeof(float) * npx;
-    const void *d_src = src;
-    const float *d_mx = map_x, *d_my = map_y;
-    void *d_dst = dst;
-    if (loc == HV_HOST) {
-        int rc = hv_ensure_buffer(v, &v->stage_b, &v->stage_b_bytes, 2 * img_bytes + 2 * map_bytes + 1024);
-        if (rc != HV_OK) return rc;
-        char *base = (char *)v->stage_b;
-        float *mx = (float *)base, *my = mx + npx;
-        char *s = (char *)(my + npx);
-        s += (256 - ((uintptr_t)s & 255)) & 255;
-        char *d = s + ((img_bytes + 255) & ~(size_t)255);
-        bool pinned_src = false; // (page-locked sources are read by the DMA engine after hipMemcpyAsync returns: hv_h2d)
-        if ((rc = hv_h2d_lazy(v, mx, map_x, map_bytes, &pinned_src)) != HV_OK) return rc;
-        if ((rc = hv_h2d_lazy(v, my, map_y, map_bytes, &pinned_src)) != HV_OK) return rc;
-        if ((rc = hv_h2d_lazy(v, s, src, img_bytes, &pinned_src)) != HV_OK) return rc;
-        if ((rc = hv_h2d_fence(v, pinned_src)) != HV_OK) return rc;
-        d_src = s; d_mx = mx; d_my = my; d_dst = d;
-    }
+    HvStage st(v, loc);
+    const int i_mx = st.in(map_x, map_bytes), i_my = st.in(map_y, map_bytes), i_src = st.in(src, img_bytes), o_dst = st.out(dst, img_bytes);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
+    if (rc != HV_OK) return rc;
+    const void *d_src = st.dev<const void>(i_src);
+    const float *d_mx = st.dev<const float>(i_mx), *d_my = st.dev<const float>(i_my);
+    void *d_dst = st.dev<void>(o_dst);
     const dim3 grid((unsigned)((npx + 255) / 256)), block(256);
     if (!linear) {
         if (src_kind == HV_IMG_U8)
@@ -176,8 +165,8 @@ extern "C" int hv_remap(hv_volume *v, const void *src, int32_t src_kind, int32_t
         hipLaunchKernelGGL(k_remap_linear_f32, grid, block, 0, v->stream, (const float *)d_src, height, width, channels, d_mx, d_my, (float *)d_dst);
     }
     HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) HV_HIP(hipMemcpyAsync(dst, d_dst, img_bytes, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipStreamSynchronize(v->stream));
+    if ((rc = st.finish()) != HV_OK) return rc;
+    HV_HIP(hipStreamSynchronize(v->stream)); // (device images too: this call has always been complete on return)
     return HV_OK;
 }
 
@@ -349,22 +338,17 @@ int hv_filter_shadow_points(hv_volume *v, const float *depth, int32_t height, in
     HV_HIP(hipSetDevice(v->device));
     const int64_t npx = (int64_t)height * width;
     HV_REQUIRE(npx < (int64_t)1 << 30, HV_ERR_INVALID, "hv_filter_shadow_points: image too large");
-    const void *d_depth = nullptr;
-    int rc = hv_stage_in(v, depth, sizeof(float) * npx, loc, 0, &d_depth);
+    // head: [histograms][state]
+    HvStage st(v, loc);
+    st.head(sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS));
+    const int i_depth = st.in(depth, sizeof(float) * npx), o_out = st.out(out, sizeof(float) * npx);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    // scratch: [histograms][state][out npx]
-    const size_t head = sizeof(uint32_t) * (HV_SH_HIST_WORDS + HV_SH_WORDS);
-    rc = hv_ensure_buffer(v, &v->out_c, &v->out_c_bytes, head + sizeof(float) * npx);
-    if (rc != HV_OK) return rc;
-    float *d_out = loc == HV_DEVICE ? out : (float *)((char *)v->out_c + head);
-    rc = shadow_filter_launch((const float *)d_depth, height, width, delta_x, delta_y, fill_value, d_out, (uint32_t *)v->out_c, v->stream);
+    rc = shadow_filter_launch(st.dev<const float>(i_depth), height, width, delta_x, delta_y, fill_value, st.dev<float>(o_out), (uint32_t *)st.head_dev,
+                              v->stream);
     if (rc != HV_OK) return rc;
     // host images: copied back and complete on return; device images: queued on the volume's stream like every other launch
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(out, d_out, sizeof(float) * npx, hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
-    return HV_OK;
+    return st.finish();
 }
 
 int hv_filter_shadow_points_on_stream(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,

@@ -231,14 +231,6 @@ static inline int hv_blocks_in_key_order(hv_volume *v, int64_t nb, std::vector<s
     return HV_OK;
 }
 
-// a frame's depth and colour planes (npx pixels: of one frame, or of a batch's frames behind each other) on the device
-static inline int hv_stage_frame(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *rgb, int64_t npx, int32_t loc,
-                                 const void **d_depth, const uint8_t **d_rgb) {
-    int rc = hv_stage_in(v, depth, (size_t)npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, d_depth);
-    if (rc == HV_OK) rc = hv_stage_in(v, rgb, (size_t)npx * 3, loc, 1, (const void **)d_rgb);
-    return rc;
-}
-
 // semantic-payload implementations behind the mode-independent entry points (hv_semantic_ops.hip)
 int hv_sem_carve(hv_volume *v, const HvQuery &Q, const float *d_depth, int64_t n_blocks);
 int hv_sem_segment_op(hv_volume *v, int op, int32_t a, int32_t b, float fa);

@@ -293,33 +293,18 @@ extern "C" int hv_tsdf_ray_cast(hv_volume *v, int32_t height, int32_t width, con
     HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "hv_tsdf_ray_cast: bad loc %d", (int)loc);
     HV_HIP(hipSetDevice(v->device));
 
-    // outputs: in place (HV_DEVICE) or in one staging buffer of the volume, copied back before returning (HV_HOST)
+    // outputs: in place (HV_DEVICE) or in the volume's staging buffer, copied back before returning (HV_HOST)
     const size_t npx = (size_t)height * (size_t)width;
-    const size_t sizes[5] = {depth ? 4 * npx : 0, vertex ? 12 * npx : 0, normal ? 12 * npx : 0, color ? 12 * npx : 0, mask ? npx : 0};
-    void *user[5] = {depth, vertex, normal, color, mask};
-    void *dev[5] = {depth, vertex, normal, color, mask};
-    if (loc == HV_HOST) {
-        size_t off[5], total = 0;
-        for (int i = 0; i < 5; ++i) {
-            off[i] = total;
-            total += (sizes[i] + 255) & ~(size_t)255;
-        }
-        if (total > 0) {
-            const int rc = hv_ensure_buffer(v, &v->raycast_buf, &v->raycast_buf_bytes, total);
-            if (rc != HV_OK) return rc;
-        }
-        for (int i = 0; i < 5; ++i) dev[i] = sizes[i] ? (char *)v->raycast_buf + off[i] : nullptr;
-    }
+    HvStage st(v, loc);
+    const int o_depth = st.out(depth, 4 * npx), o_vertex = st.out(vertex, 12 * npx), o_normal = st.out(normal, 12 * npx), o_color = st.out(color, 12 * npx),
+              o_mask = st.out(mask, npx);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
+    if (rc != HV_OK) return rc;
     // a batch issued after this call must not start claiming units (its touch + pack launch on the auxiliary stream) while the
     // cast still reads the table: the next hv_tsdf_integrate_batch starts a fresh chain behind it
     v->pipe_armed = false;
-    const int rc = hv_ray_cast_launch(v, height, width, intr, T_cw, depth_min, depth_max, weight_threshold, depth_scale, (float *)dev[0],
-                                      (float *)dev[1], (float *)dev[2], (float *)dev[3], (uint8_t *)dev[4]);
+    rc = hv_ray_cast_launch(v, height, width, intr, T_cw, depth_min, depth_max, weight_threshold, depth_scale, st.dev<float>(o_depth),
+                            st.dev<float>(o_vertex), st.dev<float>(o_normal), st.dev<float>(o_color), st.dev<uint8_t>(o_mask));
     if (rc != HV_OK) return rc;
-    if (loc == HV_HOST) {
-        for (int i = 0; i < 5; ++i)
-            if (sizes[i]) HV_HIP(hipMemcpyAsync(user[i], dev[i], sizes[i], hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
-    return HV_OK;
+    return st.finish();
 }

@@ -181,22 +181,6 @@ HvSampleParams sample_params(const hv_volume *v, double weight_threshold) {
 
 } // namespace
 
-// device addresses of a call's outputs: the caller's own (HV_DEVICE), or pieces of the volume's staging buffer behind `head` bytes
-// (declared in hv_common.h: hv_lookup.hip stages its outputs the same way)
-int hv_stage_out(hv_volume *v, int32_t loc, size_t head, const size_t *sizes, void *const *user, void **dev, int count) {
-    size_t off[8], total = head;
-    for (int i = 0; i < count; ++i) {
-        off[i] = total;
-        if (loc == HV_HOST) total += (sizes[i] + 255) & ~(size_t)255;
-    }
-    if (total > 0) {
-        const int rc = hv_ensure_buffer(v, &v->sample_buf, &v->sample_buf_bytes, total);
-        if (rc != HV_OK) return rc;
-    }
-    for (int i = 0; i < count; ++i) dev[i] = loc == HV_HOST ? (sizes[i] ? (char *)v->sample_buf + off[i] : nullptr) : user[i];
-    return HV_OK;
-}
-
 extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t point_dtype, int64_t n, double weight_threshold, float *sdf,
                                      float *gradient, float *color, float *weight, uint8_t *status, int32_t loc) {
     const char *fn = "hv_tsdf_sample_points";
@@ -211,20 +195,19 @@ extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t p
     if (n == 0) return HV_OK;
     HV_HIP(hipSetDevice(v->device));
 
-    const size_t sizes[5] = {sdf ? 4 * (size_t)n : 0, gradient ? 12 * (size_t)n : 0, color ? 12 * (size_t)n : 0, weight ? 4 * (size_t)n : 0,
-                             status ? (size_t)n : 0};
-    void *user[5] = {sdf, gradient, color, weight, status};
-    void *dev[5];
-    rc = hv_stage_out(v, loc, 0, sizes, user, dev, 5);
+    const size_t un = (size_t)n;
+    HvStage st(v, loc);
+    const int i_points = st.in(points, un * 3 * (point_dtype == HV_F64 ? 8 : 4));
+    const int o_sdf = st.out(sdf, 4 * un), o_grad = st.out(gradient, 12 * un), o_color = st.out(color, 12 * un), o_weight = st.out(weight, 4 * un),
+              o_status = st.out(status, un);
+    rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const void *d_points = nullptr;
-    rc = hv_stage_in(v, points, (size_t)n * 3 * (point_dtype == HV_F64 ? 8 : 4), loc, 0, &d_points);
-    if (rc != HV_OK) return rc;
+    const void *d_points = st.dev<const void>(i_points);
     // reads only, as hv_tsdf_ray_cast: the next batch starts a fresh touch + pack chain behind this call
     v->pipe_armed = false;
 
     const HvSampleParams P = sample_params(v, weight_threshold);
-    const HvSampleOut O{(float *)dev[0], (float *)dev[1], (float *)dev[2], (float *)dev[3], (uint8_t *)dev[4], nullptr};
+    const HvSampleOut O{st.dev<float>(o_sdf), st.dev<float>(o_grad), st.dev<float>(o_color), st.dev<float>(o_weight), st.dev<uint8_t>(o_status), nullptr};
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
     const bool f64 = point_dtype == HV_F64, c = color != nullptr, g = gradient != nullptr;
     hv_profile_begin(v);
@@ -243,12 +226,7 @@ extern "C" int hv_tsdf_sample_points(hv_volume *v, const void *points, int32_t p
 #undef HV_SAMPLE_LAUNCH
     hv_profile_end(v, 0);
     HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        for (int i = 0; i < 5; ++i)
-            if (sizes[i]) HV_HIP(hipMemcpyAsync(user[i], dev[i], sizes[i], hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
-    return HV_OK;
+    return st.finish();
 }
 
 extern "C" int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t height, int32_t width, const double *intr,
@@ -289,17 +267,15 @@ extern "C" int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t dept
     HV_REQUIRE(ortho <= 1.0e-6 && det >= 0.0, HV_ERR_INVALID, "%s: T_cw is not rigid (|R^T R - I|_inf = %.3g, det = %.3g)", fn, ortho, det);
     HV_HIP(hipSetDevice(v->device));
 
-    // staging: [5 class counters, 256 B][sdf][class] (the outputs only for HV_HOST)
+    // head: the 5 class counters
     const size_t npx = (size_t)height * (size_t)width;
-    const size_t head = stats != nullptr ? 256 : 0;
-    const size_t sizes[2] = {sdf ? 4 * npx : 0, cls ? npx : 0};
-    void *user[2] = {sdf, cls};
-    void *dev[2];
-    rc = hv_stage_out(v, loc, head, sizes, user, dev, 2);
+    HvStage st(v, loc);
+    st.head(stats != nullptr ? 256 : 0);
+    const int i_depth = st.in(depth, npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4));
+    const int o_sdf = st.out(sdf, 4 * npx), o_cls = st.out(cls, npx);
+    rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const void *d_depth = nullptr;
-    rc = hv_stage_in(v, depth, npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
-    if (rc != HV_OK) return rc;
+    const void *d_depth = st.dev<const void>(i_depth);
     v->pipe_armed = false; // reads only, as hv_tsdf_ray_cast
 
     HvSampleParams P = sample_params(v, params->weight_threshold);
@@ -317,25 +293,18 @@ extern "C" int hv_tsdf_check_frame(hv_volume *v, const void *depth, int32_t dept
     P.height = height;
     P.width = width;
     P.depth_is_u16 = depth_dtype == HV_DEPTH_U16;
-    unsigned long long *d_count = stats != nullptr ? (unsigned long long *)v->sample_buf : nullptr;
+    unsigned long long *d_count = (unsigned long long *)st.head_dev;
     if (d_count != nullptr) HV_HIP(hipMemsetAsync(d_count, 0, 5 * sizeof(unsigned long long), v->stream));
-    const HvSampleOut O{(float *)dev[0], nullptr, nullptr, nullptr, (uint8_t *)dev[1], d_count};
+    const HvSampleOut O{st.dev<float>(o_sdf), nullptr, nullptr, nullptr, st.dev<uint8_t>(o_cls), d_count};
     hv_profile_begin(v);
     hipLaunchKernelGGL((k_tsdf_sample<true, false, false, false>), dim3((unsigned)((width + 15) / 16), (unsigned)((height + 15) / 16)), dim3(256),
                        0, v->stream, v->table, (const char *)v->pool, d_depth, (int64_t)npx, P, O);
     hv_profile_end(v, 0);
     HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        for (int i = 0; i < 2; ++i)
-            if (sizes[i]) HV_HIP(hipMemcpyAsync(user[i], dev[i], sizes[i], hipMemcpyDeviceToHost, v->stream));
-    }
-    if (stats != nullptr) {
-        unsigned long long h_count[5];
-        HV_HIP(hipMemcpyAsync(h_count, d_count, sizeof(h_count), hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
+    unsigned long long h_count[5];
+    rc = st.finish(stats != nullptr ? h_count : nullptr, sizeof(h_count));
+    if (rc != HV_OK) return rc;
+    if (stats != nullptr)
         for (int k = 0; k < 5; ++k) stats->count[k] = (int64_t)h_count[k];
-    } else if (loc == HV_HOST) {
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
     return HV_OK;
 }

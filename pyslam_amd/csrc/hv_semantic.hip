@@ -691,23 +691,6 @@ static int sem_integrate(hv_volume *v, const PT *d_pts, int64_t n, const void *d
         });
 }
 
-// stage a host array into a dedicated slice of the volume's scratch (5 inputs -> one growing buffer)
-static int sem_stage(hv_volume *v, const void *src, size_t bytes, int32_t loc, char *&cursor, const void **dev) {
-    if (src == nullptr) {
-        *dev = nullptr;
-        return HV_OK;
-    }
-    if (loc == HV_DEVICE) {
-        *dev = src;
-        return HV_OK;
-    }
-    const int rc = hv_h2d(v, cursor, src, bytes); // (waits for the copy when the source is page-locked)
-    if (rc != HV_OK) return rc;
-    *dev = cursor;
-    cursor += (bytes + 255) & ~(size_t)255;
-    return HV_OK;
-}
-
 template <typename VOX>
 static int sem_dump(hv_volume *v, int64_t nb, const std::vector<int64_t> &order, const std::vector<std::array<int32_t, 3>> &xyz,
                     int32_t *keys, int32_t *ints, float *conf, double *pos_sums, float *col_sums, int32_t *label_counts,
@@ -836,19 +819,14 @@ int hv_integrate_points_semantic(hv_volume *v, const void *points, int32_t point
                (long long)n, (long long)v->cfg.max_points);
     HV_HIP(hipSetDevice(v->device));
     const size_t psz = point_dtype == 1 ? 8 : 4;
-    const size_t need = 3 * psz * n + 12 * (size_t)n + 3 * 4 * (size_t)n + 5 * 256;
-    if (loc == HV_HOST) {
-        int rc = hv_ensure_buffer(v, &v->stage_a, &v->stage_a_bytes, need);
-        if (rc != HV_OK) return rc;
-    }
-    char *cursor = (char *)v->stage_a;
-    const void *d_pts, *d_cols, *d_cls, *d_inst, *d_dep;
-    int rc = sem_stage(v, points, 3 * psz * n, loc, cursor, &d_pts);
-    if (rc == HV_OK) rc = sem_stage(v, color_dtype == HV_COLOR_NONE ? nullptr : colors, (color_dtype == HV_COLOR_U8 ? 3 : 12) * (size_t)n, loc, cursor, &d_cols);
-    if (rc == HV_OK) rc = sem_stage(v, class_ids, 4 * (size_t)n, loc, cursor, &d_cls);
-    if (rc == HV_OK) rc = sem_stage(v, instance_ids, 4 * (size_t)n, loc, cursor, &d_inst);
-    if (rc == HV_OK) rc = sem_stage(v, depths, 4 * (size_t)n, loc, cursor, &d_dep);
+    const size_t un = (size_t)n;
+    HvStage st(v, loc);
+    const int i_pts = st.in(points, 3 * psz * un), i_cols = st.in(color_dtype == HV_COLOR_NONE ? nullptr : colors, (color_dtype == HV_COLOR_U8 ? 3 : 12) * un),
+              i_cls = st.in(class_ids, 4 * un), i_inst = st.in(instance_ids, 4 * un), i_dep = st.in(depths, 4 * un);
+    const int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
+    const void *d_pts = st.dev<const void>(i_pts), *d_cols = st.dev<const void>(i_cols), *d_cls = st.dev<const void>(i_cls),
+               *d_inst = st.dev<const void>(i_inst), *d_dep = st.dev<const void>(i_dep);
     if (point_dtype == 1) {
         HV_SEM_DISPATCH(v, return sem_integrate<VOX, double>(v, (const double *)d_pts, n, d_cols, color_dtype, (const int32_t *)d_cls, (const int32_t *)d_inst,
                                                              (const float *)d_dep));
@@ -870,27 +848,16 @@ int hv_integrate_rgbd_semantic(hv_volume *v, const float *depth, const uint8_t *
     const int64_t npx = (int64_t)height * width;
     HV_REQUIRE(npx <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_rgbd_semantic: image exceeds max_points");
     HV_HIP(hipSetDevice(v->device));
-    // the frame's depth and colour planes on the device (staged on the volume's stream when they come from the host)
-    const void *d_depth = nullptr;
-    const uint8_t *d_rgb = nullptr;
-    int rc = hv_stage_frame(v, depth, HV_DEPTH_F32, rgb, npx, loc, &d_depth, &d_rgb);
+    // the frame's depth, colour and label planes on the device (staged on the volume's stream when they come from the host)
+    const size_t un = (size_t)npx;
+    HvStage st(v, loc);
+    const int i_depth = st.in(depth, 4 * un), i_rgb = st.in(rgb, 3 * un), i_cls = st.in(class_ids_image, 4 * un),
+              i_obj = st.in(object_ids_image, 4 * un);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    // label planes: staged behind each other in the output scratch when they come from the host
-    const int32_t *d_cls = class_ids_image, *d_obj = object_ids_image;
-    if (loc == HV_HOST && class_ids_image != nullptr) {
-        const size_t plane = (sizeof(int32_t) * (size_t)npx + 255) & ~(size_t)255;
-        rc = hv_ensure_buffer(v, &v->out_c, &v->out_c_bytes, 2 * plane);
-        if (rc != HV_OK) return rc;
-        char *st = (char *)v->out_c;
-        bool pinned_src = false;
-        if ((rc = hv_h2d_lazy(v, st, class_ids_image, sizeof(int32_t) * npx, &pinned_src)) != HV_OK) return rc;
-        d_cls = (const int32_t *)st;
-        if (object_ids_image != nullptr) {
-            if ((rc = hv_h2d_lazy(v, st + plane, object_ids_image, sizeof(int32_t) * npx, &pinned_src)) != HV_OK) return rc;
-            d_obj = (const int32_t *)(st + plane);
-        }
-        if ((rc = hv_h2d_fence(v, pinned_src)) != HV_OK) return rc;
-    }
+    const void *d_depth = st.dev<const void>(i_depth);
+    const uint8_t *d_rgb = st.dev<const uint8_t>(i_rgb);
+    const int32_t *d_cls = st.dev<const int32_t>(i_cls), *d_obj = st.dev<const int32_t>(i_obj);
     if (sem_bins_usable(v, npx)) {
         // production: the bin pass unprojects the pixel itself and leaves a 32-byte record per point for the fold
         bool checked = false;

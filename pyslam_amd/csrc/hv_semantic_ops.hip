@@ -11,18 +11,15 @@
 // Association on the GPU: one thread per allocated voxel tests the frustum and the class / depth
 // gates, then votes (instance_id, object_id) into a small device hash with wave-aggregated atomics
 // (ballot + shuffle: one atomic per distinct pair per wave); voxels without an object id are appended
-// to a pending list (wave-ballot compaction).  The few distinct pairs go to the host, which applies
-// the reference's winner / min_votes / min_vote_ratio rules verbatim and hands the final
-// instance -> object table back for the pending voxels.  New object ids come from a process-wide
+// to a pending list (wave-ballot compaction).  The few distinct pairs stay on the device: one
+// workgroup applies the reference's winner / min_votes / min_vote_ratio rules (k_sem_assoc_rules) and
+// the pending voxels take their ids from its instance -> object table.  New object ids come from a process-wide
 // counter like the reference's (voxel_semantic_shared_data.h:26-34); they are assigned in ascending
 // instance-id order (the reference assigns them in its hash-map iteration order: same set of new
 // ids, possibly permuted between the instances that need one in the same call).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
-#include <map>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "hv_common.h"
@@ -1099,6 +1096,27 @@ int hv_remove_low_confidence_voxels(hv_volume *v, float min_confidence) {
     return hv_sem_segment_op(v, 4, 0, 0, min_confidence);
 }
 
+// remap_instance_ids over an image at `loc`.  flat != null: the map [n_map instance ids, ascending][their object ids] in host memory,
+// uploaded into the call's head; else the map of the volume's last association, where k_sem_assoc_rules left it (d_inst, d_obj, d_n_map)
+static int remap_ids(hv_volume *v, const int32_t *instance_ids, int64_t n, const int32_t *flat, int64_t n_map, const int32_t *d_inst,
+                     const int32_t *d_obj, const int32_t *d_n_map, int32_t *out, int32_t loc) {
+    const size_t img_bytes = sizeof(int32_t) * (size_t)n, map_bytes = flat != nullptr ? sizeof(int32_t) * 2 * (size_t)n_map : 0;
+    HvStage st(v, loc);
+    st.head(map_bytes);
+    const int i_ids = st.in(instance_ids, img_bytes), o_out = st.out(out, img_bytes);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
+    if (rc != HV_OK) return rc;
+    if (map_bytes > 0) {
+        HV_HIP(hipMemcpyAsync(st.head_dev, flat, map_bytes, hipMemcpyHostToDevice, v->stream));
+        d_inst = (const int32_t *)st.head_dev;
+        d_obj = d_inst + n_map;
+    }
+    hipLaunchKernelGGL(k_remap_instance_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, st.dev<const int32_t>(i_ids), n, d_inst, d_obj,
+                       (int32_t)n_map, d_n_map, st.dev<int32_t>(o_out));
+    HV_HIP(hipGetLastError());
+    return st.finish();
+}
+
 int hv_remap_instance_ids(hv_volume *v, const int32_t *instance_ids, int32_t height, int32_t width, const int32_t *map_inst,
                           const int32_t *map_obj, int64_t n_map, int32_t *out, int32_t loc) {
     HV_REQUIRE(v != nullptr && instance_ids != nullptr && out != nullptr, HV_ERR_INVALID, "hv_remap_instance_ids: null argument");
@@ -1112,25 +1130,8 @@ int hv_remap_instance_ids(hv_volume *v, const int32_t *instance_ids, int32_t hei
     std::sort(m.begin(), m.end());
     std::vector<int32_t> flat((size_t)n_map * 2);
     for (int64_t i = 0; i < n_map; ++i) { flat[i] = m[i].first; flat[n_map + i] = m[i].second; }
-    const size_t img_bytes = sizeof(int32_t) * (size_t)n;
-    const size_t map_bytes = sizeof(int32_t) * 2 * (size_t)n_map;
-    int rc = hv_ensure_buffer(v, &v->stage_b, &v->stage_b_bytes, 2 * img_bytes + map_bytes + 512);
+    const int rc = remap_ids(v, instance_ids, n, flat.data(), n_map, nullptr, nullptr, nullptr, out, loc);
     if (rc != HV_OK) return rc;
-    char *base = (char *)v->stage_b;
-    int32_t *d_map = (int32_t *)base;
-    const int32_t *d_in = instance_ids;
-    int32_t *d_out = out;
-    char *cursor = base + ((map_bytes + 255) & ~(size_t)255);
-    if (n_map > 0) HV_HIP(hipMemcpyAsync(d_map, flat.data(), map_bytes, hipMemcpyHostToDevice, v->stream));
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(cursor, instance_ids, img_bytes, hipMemcpyHostToDevice, v->stream));
-        d_in = (const int32_t *)cursor;
-        d_out = (int32_t *)(cursor + img_bytes);
-    }
-    hipLaunchKernelGGL(k_remap_instance_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, d_in, n, d_map,
-                       d_map + n_map, (int32_t)n_map, (const int32_t *)nullptr, d_out);
-    HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) HV_HIP(hipMemcpyAsync(out, d_out, img_bytes, hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream)); // `flat` is host memory
     return HV_OK;
 }
@@ -1193,25 +1194,14 @@ int hv_assoc_vote(hv_volume *v, const float *intr_f32, int32_t width, int32_t he
     AssocScratch S;
     rc = assoc_scratch(v, &S);
     if (rc != HV_OK) return rc;
-    // images: three planes staged back to back when they come from the host
-    const int32_t *d_cls = class_ids_image, *d_inst = instance_ids_image;
-    const float *d_depth = depth_image;
-    if (loc == HV_HOST) {
-        const size_t plane = (sizeof(int32_t) * (size_t)n_px + 255) & ~(size_t)255;
-        rc = hv_ensure_buffer(v, &v->stage_b, &v->stage_b_bytes, 3 * plane);
-        if (rc != HV_OK) return rc;
-        char *st = (char *)v->stage_b;
-        bool pinned_src = false; // (page-locked sources - the front's registered ring - are read by the DMA engine later: hv_h2d)
-        if ((rc = hv_h2d_lazy(v, st, class_ids_image, sizeof(int32_t) * n_px, &pinned_src)) != HV_OK) return rc;
-        if ((rc = hv_h2d_lazy(v, st + plane, instance_ids_image, sizeof(int32_t) * n_px, &pinned_src)) != HV_OK) return rc;
-        d_cls = (const int32_t *)st;
-        d_inst = (const int32_t *)(st + plane);
-        if (depth_image != nullptr) {
-            if ((rc = hv_h2d_lazy(v, st + 2 * plane, depth_image, sizeof(float) * n_px, &pinned_src)) != HV_OK) return rc;
-            d_depth = (const float *)(st + 2 * plane);
-        }
-        if ((rc = hv_h2d_fence(v, pinned_src)) != HV_OK) return rc;
-    }
+    // images: three planes, staged when they come from the host
+    HvStage st(v, loc);
+    const int i_cls = st.in(class_ids_image, sizeof(int32_t) * (size_t)n_px), i_inst = st.in(instance_ids_image, sizeof(int32_t) * (size_t)n_px),
+              i_depth = st.in(depth_image, sizeof(float) * (size_t)n_px);
+    rc = st.commit(&v->stage, &v->stage_bytes);
+    if (rc != HV_OK) return rc;
+    const int32_t *d_cls = st.dev<const int32_t>(i_cls), *d_inst = st.dev<const int32_t>(i_inst);
+    const float *d_depth = st.dev<const float>(i_depth);
     if (v->assoc_clean != v->assoc_buf || v->assoc_clean_bytes != v->assoc_buf_bytes) { // a new allocation, or a call that failed before its compaction
         HV_HIP(hipMemsetAsync(S.vkeys, 0xFF, sizeof(uint64_t) * HV_VOTE_CAP, v->stream));
         HV_HIP(hipMemsetAsync(S.vcounts, 0, sizeof(int32_t) * HV_VOTE_CAP, v->stream));
@@ -1276,10 +1266,10 @@ int hv_assoc_pairs_set(hv_volume *v, const uint64_t *pair_keys, const int32_t *p
     int rc = assoc_scratch(v, &S);
     if (rc != HV_OK) return rc;
     const int32_t n32 = (int32_t)n_pairs;
-    if (n_pairs > 0) {
-        HV_HIP(hipMemcpyAsync(S.ckeys, pair_keys, sizeof(uint64_t) * n_pairs, hipMemcpyHostToDevice, v->stream));
-        HV_HIP(hipMemcpyAsync(S.ccounts, pair_counts, sizeof(int32_t) * n_pairs, hipMemcpyHostToDevice, v->stream));
-    }
+    bool pinned_src = false; // (a page-locked source is read by the DMA engine later: hv_h2d_lazy)
+    if ((rc = hv_h2d_lazy(v, S.ckeys, pair_keys, sizeof(uint64_t) * (size_t)n_pairs, &pinned_src)) != HV_OK) return rc;
+    if ((rc = hv_h2d_lazy(v, S.ccounts, pair_counts, sizeof(int32_t) * (size_t)n_pairs, &pinned_src)) != HV_OK) return rc;
+    if ((rc = hv_h2d_fence(v, pinned_src)) != HV_OK) return rc;
     HV_HIP(hipMemcpyAsync(&v->table.counters[HV_CNT_OUT], &n32, sizeof(int32_t), hipMemcpyHostToDevice, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream)); // the arguments are host memory
     return HV_OK;
@@ -1383,24 +1373,7 @@ int hv_remap_instance_ids_last(hv_volume *v, const int32_t *instance_ids, int32_
     AssocScratch S;
     int rc = assoc_scratch(v, &S);
     if (rc != HV_OK) return rc;
-    const int32_t *d_in = instance_ids;
-    int32_t *d_out = out;
-    const size_t img_bytes = sizeof(int32_t) * (size_t)n;
-    if (loc == HV_HOST) {
-        rc = hv_ensure_buffer(v, &v->stage_b, &v->stage_b_bytes, 2 * img_bytes + 512);
-        if (rc != HV_OK) return rc;
-        HV_HIP(hipMemcpyAsync(v->stage_b, instance_ids, img_bytes, hipMemcpyHostToDevice, v->stream));
-        d_in = (const int32_t *)v->stage_b;
-        d_out = (int32_t *)((char *)v->stage_b + img_bytes);
-    }
-    hipLaunchKernelGGL(k_remap_instance_ids, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, d_in, n, S.map_inst, S.map_obj, 0,
-                       (const int32_t *)S.n_map, d_out);
-    HV_HIP(hipGetLastError());
-    if (loc == HV_HOST) {
-        HV_HIP(hipMemcpyAsync(out, d_out, img_bytes, hipMemcpyDeviceToHost, v->stream));
-        HV_HIP(hipStreamSynchronize(v->stream));
-    }
-    return HV_OK;
+    return remap_ids(v, instance_ids, n, nullptr, 0, S.map_inst, S.map_obj, S.n_map, out, loc);
 }
 
 // One semantic keyframe in ONE host call (round 6): the stages above in the integrator's order, on device-resident images.  At

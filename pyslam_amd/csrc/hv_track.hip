@@ -355,21 +355,17 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
     double *d_trace = (double *)(base + o_trace);
 
     const void *d_depth = nullptr;
+    const uint8_t *d_color = nullptr;
     const size_t npx0 = (size_t)height * (size_t)width;
-    rc = hv_stage_in(v, depth, npx0 * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
+    rc = hv_stage_frame(v, depth, depth_dtype, HYBRID ? color : nullptr, npx0, loc, &d_depth, &d_color);
     if (rc != HV_OK) return rc;
-    const void *d_color = nullptr;
-    if (HYBRID) {
-        rc = hv_stage_in(v, color, npx0 * 3, loc, 1, &d_color);
-        if (rc != HV_OK) return rc;
-    }
     // reads only, as hv_tsdf_ray_cast: the next batch starts a fresh touch + pack chain behind this call
     v->pipe_armed = false;
 
     hipLaunchKernelGGL(k_track_init<NACC>, dim3(1), dim3(64), 0, v->stream, st);
     hv_profile_begin(v);
     hipLaunchKernelGGL(k_track_source<HYBRID>, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
-                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, (const uint8_t *)d_color, v->color_bgr, (int64_t)npx0, (float)prm->depth_scale,
+                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, d_color, v->color_bgr, (int64_t)npx0, (float)prm->depth_scale,
                        prm->depth_min, prm->depth_max, (float *)(base + o_src[0]), intensity(0));
     hv_profile_end(v, 0);
     for (int l = 1; l < nl; ++l) {

@@ -1176,12 +1176,11 @@ int hv_tsdf_integrate(hv_volume *v, const void *depth, int32_t depth_dtype, cons
     if (rc != HV_OK) return rc;
     HV_HIP(hipSetDevice(v->device));
     const size_t npx = (size_t)height * width;
-    const void *d_depth = nullptr, *d_rgb = nullptr;
-    rc = hv_stage_in(v, depth, npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4), loc, 0, &d_depth);
+    const void *d_depth = nullptr;
+    const uint8_t *d_rgb = nullptr;
+    rc = hv_stage_frame(v, depth, depth_dtype, rgb, npx, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
-    rc = hv_stage_in(v, rgb, npx * 3, loc, 1, &d_rgb);
-    if (rc != HV_OK) return rc;
-    return tsdf_integrate_one(v, d_depth, depth_dtype, (const uint8_t *)d_rgb, height, width, intr, T_cw,
+    return tsdf_integrate_one(v, d_depth, depth_dtype, d_rgb, height, width, intr, T_cw,
                               depth_scale, depth_trunc);
 }
 

@@ -762,13 +762,12 @@ static int integrate_points(hv_volume *v, const char *who, const void *points, b
     HV_REQUIRE(n <= v->cfg.max_points, HV_ERR_CAPACITY, "%s: %lld points exceed max_points=%lld", who, (long long)n,
                (long long)v->cfg.max_points);
     HV_HIP(hipSetDevice(v->device));
-    const void *d_pts = nullptr, *d_cols = nullptr;
-    int rc = hv_stage_in(v, points, (f64 ? sizeof(double) : sizeof(float)) * 3 * (size_t)n, loc, 0, &d_pts);
+    HvStage st(v, loc);
+    const int i_pts = st.in(points, (f64 ? sizeof(double) : sizeof(float)) * 3 * (size_t)n),
+              i_cols = st.in(color_dtype != HV_COLOR_NONE ? colors : nullptr, (color_dtype == HV_COLOR_U8 ? 1 : 4) * 3 * (size_t)n);
+    const int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    if (color_dtype != HV_COLOR_NONE) {
-        rc = hv_stage_in(v, colors, (color_dtype == HV_COLOR_U8 ? 1 : 4) * 3 * (size_t)n, loc, 1, &d_cols);
-        if (rc != HV_OK) return rc;
-    }
+    const void *d_pts = st.dev<const void>(i_pts), *d_cols = st.dev<const void>(i_cols);
     if (f64) return integrate_device_points(v, v->scratch_points, n, d_cols, color_dtype, nullptr, nullptr, (const double *)d_pts);
     return integrate_device_points(v, (const float *)d_pts, n, d_cols, color_dtype, nullptr);
 }
@@ -808,7 +807,7 @@ int hv_unproject_frame(hv_volume *v, const void *depth, int32_t depth_dtype, dou
                        double max_depth, int32_t loc, const void **d_depth_out) {
     const void *d_depth = nullptr;
     const uint8_t *d_rgb = nullptr;
-    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, (int64_t)height * width, loc, &d_depth, &d_rgb);
+    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, (size_t)height * width, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     if (d_depth_out) *d_depth_out = d_depth;
     return unproject_device(v, d_depth, depth_dtype, depth_scale, d_rgb, height, width, intr, T_cw, min_depth, max_depth, 0);
@@ -832,7 +831,7 @@ extern "C" int hv_integrate_rgbd_points_batch(hv_volume *v, const void *depth, i
     const size_t dsz = depth_dtype == HV_DEPTH_U16 ? 2 : 4;
     const void *d_depth = nullptr;
     const uint8_t *d_rgb = nullptr;
-    int rc = hv_stage_frame(v, depth, depth_dtype, rgb, npx * n_frames, loc, &d_depth, &d_rgb);
+    int rc = hv_stage_frame(v, depth, depth_dtype, rgb, (size_t)npx * (size_t)n_frames, loc, &d_depth, &d_rgb);
     if (rc != HV_OK) return rc;
     const int per_chunk = (int)std::max<int64_t>(1, v->cfg.max_points / npx);
     for (int f0 = 0; f0 < n_frames; f0 += per_chunk) {
@@ -881,7 +880,7 @@ extern "C" int hv_integrate_rgbd_points(hv_volume *v, const void *depth, int32_t
     HV_REQUIRE(npx <= v->cfg.max_points, HV_ERR_CAPACITY, "hv_integrate_rgbd_points: image exceeds max_points");
     HV_HIP(hipSetDevice(v->device));
     HvFrameSource frame;
-    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, npx, loc, &frame.d_depth, &frame.d_rgb);
+    const int rc = hv_stage_frame(v, depth, depth_dtype, rgb, (size_t)npx, loc, &frame.d_depth, &frame.d_rgb);
     if (rc != HV_OK) return rc;
     frame.U = unproject_params(depth_dtype, depth_scale, height, width, intr, T_cw, min_depth, max_depth);
     return integrate_device_points(v, v->scratch_points, npx, v->scratch_colors, HV_COLOR_F32, nullptr, &frame);
@@ -922,9 +921,11 @@ int hv_carve(hv_volume *v, const float *intr_f32, int32_t width, int32_t height,
     int64_t nb = 0;
     int rc = hv_scan_begin(v, &nb);
     if (rc != HV_OK || nb == 0) return rc;
-    const void *d_depth = nullptr;
-    rc = hv_stage_in(v, depth, sizeof(float) * (size_t)width * height, loc, 0, &d_depth);
+    HvStage st(v, loc);
+    const int i_depth = st.in(depth, sizeof(float) * (size_t)width * height);
+    rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
+    const void *d_depth = st.dev<const void>(i_depth);
     // (min_count 1: iterate_voxels_in_camera_frustrum default, voxel_block_grid.h:161-163)
     HvQuery Q = hv_query_in_frustum(v, intr_f32, width, height, T_cw, depth_max, depth_min, 1, 3);
     Q.carve_threshold = depth_threshold;
@@ -1001,24 +1002,18 @@ int hv_keys_from_points(hv_volume *v, const float *points, int64_t n, int32_t *v
                HV_ERR_INVALID, "hv_keys_from_points: null argument");
     if (n == 0) return HV_OK;
     HV_HIP(hipSetDevice(v->device));
-    const void *d_pts = nullptr;
-    int rc = hv_stage_in(v, points, sizeof(float) * 3 * (size_t)n, HV_HOST, 0, &d_pts);
+    const size_t un = (size_t)n;
+    HvStage st(v, HV_HOST);
+    const int i_pts = st.in(points, sizeof(float) * 3 * un);
+    const int o_vk = st.out(voxel_keys, sizeof(int32_t) * 3 * un), o_bk = st.out(block_keys, sizeof(int32_t) * 3 * un),
+              o_lk = st.out(local_keys, sizeof(int32_t) * 3 * un), o_hash = st.out(block_hashes, sizeof(uint64_t) * un);
+    const int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, sizeof(int32_t) * 9 * (size_t)n);
-    if (rc != HV_OK) return rc;
-    rc = hv_ensure_buffer(v, &v->out_b, &v->out_b_bytes, sizeof(uint64_t) * (size_t)n);
-    if (rc != HV_OK) return rc;
-    int32_t *d_vk = (int32_t *)v->out_a, *d_bk = d_vk + 3 * n, *d_lk = d_bk + 3 * n;
     HvGridParams G = grid_params(v);
-    hipLaunchKernelGGL(k_vg_probe_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream,
-                       (const float *)d_pts, n, G, d_vk, d_bk, d_lk, (unsigned long long *)v->out_b);
+    hipLaunchKernelGGL(k_vg_probe_keys, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, st.dev<const float>(i_pts), n, G,
+                       st.dev<int32_t>(o_vk), st.dev<int32_t>(o_bk), st.dev<int32_t>(o_lk), st.dev<unsigned long long>(o_hash));
     HV_HIP(hipGetLastError());
-    HV_HIP(hipMemcpyAsync(voxel_keys, d_vk, sizeof(int32_t) * 3 * n, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipMemcpyAsync(block_keys, d_bk, sizeof(int32_t) * 3 * n, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipMemcpyAsync(local_keys, d_lk, sizeof(int32_t) * 3 * n, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipMemcpyAsync(block_hashes, v->out_b, sizeof(uint64_t) * n, hipMemcpyDeviceToHost, v->stream));
-    HV_HIP(hipStreamSynchronize(v->stream));
-    return HV_OK;
+    return st.finish();
 }
 
 } // extern "C"
