@@ -252,6 +252,8 @@ int hv_merge_halo_plan_device(hv_volume *v, const int64_t *d_dirty_all, const in
                               int64_t *n_shared) {
     HV_REQUIRE(v != nullptr && dirty_counts != nullptr && held_counts != nullptr && n_shared != nullptr, HV_ERR_INVALID,
                "hv_merge_halo_plan_device: null argument");
+    v->halo_plan_n = 0; // (before the checks below: a refused call leaves no plan of earlier lists behind)
+    *n_shared = 0;
     HV_REQUIRE(world_size >= 1 && world_size <= 64 && rank >= 0 && rank < world_size, HV_ERR_INVALID, "hv_merge_halo_plan_device: bad rank / world size");
     HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "hv_merge_halo_plan_device: not a TSDF volume");
     HV_HIP(hipSetDevice(v->device));
@@ -265,8 +267,6 @@ int hv_merge_halo_plan_device(hv_volume *v, const int64_t *d_dirty_all, const in
         S.held_off[r + 1] = S.held_off[r] + held_counts[r];
     }
     const int64_t n = S.dirty_off[world_size] + S.held_off[world_size];
-    v->halo_plan_n = 0;
-    *n_shared = 0;
     if (n == 0) return HV_OK;
     HV_REQUIRE(n < (1ll << 31) && d_dirty_all != nullptr && d_held_all != nullptr, HV_ERR_INVALID, "hv_merge_halo_plan_device: bad lists");
     // scratch: [keys in n u64][keys out n u64][vals in n i32][vals out n i32][flag n i32][pos n + 1 i32][act n u8] + the sort's own
