@@ -1205,13 +1205,17 @@ int hv_grid_packed_check(const void *host_src, int64_t bytes, hv_grid_packed_hea
  *   3. hv_merge_halo_plan_held every rank, same input -> same output: the keys that some rank updated since its last merge
  *                              AND that two ranks or more hold (second all-gather: hv_tsdf_unit_keys), in sorted order, and
  *                              what THIS rank does with each: 1 = keeps it (the lowest holding rank), 2 = zeroes its copy (a
- *                              no-op where the rank has none).  (hv_merge_halo_plan: the same from the dirty lists alone -
- *                              keys listed by >= 2 ranks, lowest listing rank keeps, EVERY other rank zeroes: a unit that is
- *                              updated by one rank per window is never consolidated by it.)
+ *                              no-op where the rank has none).  A rank counts as a holder ONCE, however often its held list
+ *                              names the key - on the host and in the device plan below (one rule: csrc/hv_halo_plan.h).
+ *                              (hv_merge_halo_plan: the same from the dirty lists alone - keys listed by >= 2 ranks, lowest
+ *                              listing rank keeps, EVERY other rank zeroes: a unit that is updated by one rank per window is
+ *                              never consolidated by it.  It IS hv_merge_halo_plan_held(keys, counts, keys, counts): every
+ *                              lister taken as a holder; a rank lists a key once, so the lowest lister is the lowest holder.)
  *   4. hv_merge_halo_pack      additive numerators {sum w*tsdf, w, sum r, sum g, sum b} of the shared units only, dense
  *                              [K, 16^3, 5] f32 in plan order (zeros where the rank does not hold a unit)
  *   5. (caller) all-reduce(sum) of that buffer - message size = shared units x 81 920 B, not the whole volume
  *   6. hv_merge_halo_unpack    keeper: state := reduced numerators; other holders: unit zeroed (they go on fusing deltas)
+ *                              (hv_tsdf_import_numerators is the same write with every unit kept, after claiming the units)
  *   7. hv_tsdf_mark_merged
  * Afterwards the sum over ranks of every unit's numerators is still the single-GPU total, and every unit that went through
  * the merge is complete on exactly one rank (with the _held plan: every unit two ranks hold).  The library does the device work; the caller owns the transport (pyslam_amd/distributed.py:
@@ -1234,8 +1238,8 @@ int hv_merge_halo_unpack(hv_volume *v, const int32_t *shared_keys, int64_t k, co
  *                                   upper bound of both lengths, to size them); the two lengths come back to the host (they size the
  *                                   all-gather)
  *   2. (caller) all-gather of the counts and of the padded lists -> [world][stride] device buffers
- *   3. hv_merge_halo_plan_device    radix sort of (key, rank, held) + two small kernels: the plan of hv_merge_halo_plan_held, in
- *                                   packed-key order, left IN THE VOLUME; *n_shared comes back to the host (it sizes the payload).
+ *   3. hv_merge_halo_plan_device    radix sort of (key, rank, held) + two small kernels: the plan of hv_merge_halo_plan_held (the
+ *                                   same rule on every run of equal keys), in packed-key order, left IN THE VOLUME; *n_shared comes back to the host (it sizes the payload).
  *                                   all_dirty_kept != 0: one rank takes every dirty unit through the path as its own keeper.
  *   4. hv_merge_halo_pack_planned / 6. _unpack_planned   units [first, first + count) of the stored plan, device payload, queued on the
  *                                   volume's stream (the caller orders its all-reduce against that stream)

@@ -659,6 +659,7 @@ int hv_ray_cast_launch(hv_volume *v, int32_t height, int32_t width, const double
                        double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
                        float *color, uint8_t *mask);
 void hv_segments_cache_free(void *cache); // hv_semantic_ops.hip
-// hv_halo.hip: k_tsdf_import_claim over k unit keys [k,3] in device memory, queued on the volume's stream (the caller verifies the
-// claims with hv_claims_fit)
-void hv_launch_tsdf_import_claim(hv_volume *v, const int32_t *d_keys, int64_t k);
+// hv_halo.hip: claim the k unit / block keys [k,3] (device memory) of a call that is handed keys, and verify the claims - capacity
+// gate, k_tsdf_import_claim, hv_claims_fit, at most 8 retries.  A pool that is too small grows before anything is written, or the
+// claim pass is rolled back, the volume is what it was and the call fails with HV_ERR_CAPACITY.  Waits for the GPU.
+int hv_claim_keys(hv_volume *v, const int32_t *d_keys, int64_t k);

@@ -1,13 +1,18 @@
 // libpyslam_hipvol.so - the exchange of TSDF units between GPUs: numerators export / import (a gather onto one rank) and the halo
 // merge of image-tile-sharded volumes (include/hipvol.h "halo merge", pyslam_amd/distributed.py::merge_halo).
 //
-// The library packs and unpacks on the device (k_tsdf_export / _import / _halo_unpack: a unit travels as five float numerators per
+// The library packs and unpacks on the device (k_tsdf_export / k_tsdf_halo_unpack: a unit travels as five float numerators per
 // voxel, tsdf * w, w and the colour sums, so that an all-reduce adds observations); the caller runs the collectives with whatever
 // transport it has - torch.distributed over RCCL in pyslam_amd/distributed.py.
 //
+// Each rule stands once: the plan rule in hv_halo_plan.h (hv_halo_run_rule: the host plans and k_halo_decide walk the runs of equal
+// keys with it); the unit <-> payload codec in hv_voxel_numerators / hv_voxel_from_numerators, with one export and one unpack launch
+// (an import is an unpack that keeps every unit) behind the staged and the _planned entry points; the dirty lister k_halo_lists
+// behind hv_tsdf_dirty_keys and hv_merge_halo_lists_device; the claim-until-it-fits loop in hv_claim_keys.
+//
 // The halo merge needs every rank's list of units written since its last merge and its list of units held, and from the
 // all-gathered lists the plan: the keys some rank updated that two ranks or more hold, with this rank's action.  Two forms:
-//   host    hv_tsdf_dirty_keys + hv_merge_halo_plan / _plan_held (a std::sort of (key, rank) pairs) + hv_merge_halo_pack / _unpack;
+//   host    hv_tsdf_dirty_keys + hv_merge_halo_plan / _plan_held (a std::sort of the entries) + hv_merge_halo_pack / _unpack;
 //   device  (round 6) the lists are written as packed 64-bit keys into DEVICE buffers of the caller (torch
 //           tensors: what RCCL's all_gather_into_tensor takes), the plan is a device radix sort + two small kernels, and the shared
 //           keys / actions stay in the volume for hv_merge_halo_pack_planned / _unpack_planned.  What still crosses to the host is
@@ -20,6 +25,7 @@
 #include <vector>
 
 #include "hv_common.h"
+#include "hv_halo_plan.h"
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
@@ -70,24 +76,9 @@ __global__ __launch_bounds__(256) void k_halo_decide(const unsigned long long *_
     uint8_t a = 0;
     const unsigned long long key = keys[i];
     if (i == 0 || keys[i - 1] != key) {
-        bool any_dirty = false;
-        int holders = 0, keeper = -1;
-        for (int64_t j = i; j < n && keys[j] == key; ++j) {
-            const int32_t v = vals[j];
-            if (v & 1) {
-                if (keeper < 0) keeper = v >> 1;
-                ++holders;
-            } else {
-                any_dirty = true;
-            }
-        }
-        if (all_dirty_kept) { // one rank taking its own dirty units through the collective path (force_collectives): it keeps them all
-            f = any_dirty ? 1 : 0;
-            a = 1;
-        } else if (any_dirty && holders >= 2) {
-            f = 1;
-            a = keeper == rank ? 1 : 2;
-        }
+        int64_t m = 1;
+        while (i + m < n && keys[i + m] == key) ++m;
+        f = hv_halo_run_rule(vals + i, m, rank, all_dirty_kept != 0, &a) ? 1 : 0;
     }
     flag[i] = f;
     act[i] = a;
@@ -105,29 +96,44 @@ __global__ __launch_bounds__(256) void k_halo_emit(const unsigned long long *__r
     out_act[at] = act[i];
 }
 
-// ---- numerators export / import (multi-GPU merge) ----------------------------------------------
+// ---- the unit <-> payload codec: a voxel travels as five float numerators {tsdf * w, w, sum r, sum g, sum b} ----
+__device__ __forceinline__ void hv_voxel_numerators(const char *unit, int word, float *out) {
+    const float tsdf = ((const float *)unit)[word];
+    const uint32_t w = ((const uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word];
+    out[0] = tsdf * (float)w;
+    out[1] = (float)w;
+#pragma unroll
+    for (int c = 2; c < 5; ++c) out[c] = (float)((const uint32_t *)(unit + c * HV_TSDF_PLANE_BYTES))[word];
+}
+// ... and back: the voxel's state := the numerators n, or zero where n is null.  A weight of 0 gives tsdf 0 whatever the numerator.
+__device__ __forceinline__ void hv_voxel_from_numerators(char *unit, int word, const float *n) {
+    float tsdf = 0.f;
+    uint32_t p[5] = {0u, 0u, 0u, 0u, 0u};
+    if (n != nullptr) {
+        tsdf = n[1] > 0.f ? n[0] / n[1] : 0.f;
+#pragma unroll
+        for (int c = 1; c < 5; ++c) p[c] = (uint32_t)n[c];
+    }
+    ((float *)unit)[word] = tsdf;
+#pragma unroll
+    for (int c = 1; c < 5; ++c) ((uint32_t *)(unit + c * HV_TSDF_PLANE_BYTES))[word] = p[c];
+}
+// entry ui of a key list [k,3] -> the pool index of its unit, or -1 (key out of range, or no such unit in this volume)
+__device__ __forceinline__ int32_t hv_keyed_unit(const HvTable &table, const int32_t *__restrict__ keys, int64_t ui) {
+    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
+    if (!hv_key_in_range(kx, ky, kz)) return -1;
+    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
+    return slot >= 0 ? table.vals[slot] : -1;
+}
+
+// one thread per voxel of every listed unit; zeros for a unit this volume does not hold
 __global__ void k_tsdf_export(HvTable table, const char *__restrict__ pool, const int32_t *__restrict__ keys,
                               int64_t k, float *__restrict__ payload) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= k * HV_TSDF_RRR) return;
-    const int64_t ui = gid / HV_TSDF_RRR;
-    const int word = (int)(gid % HV_TSDF_RRR);
     float out[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (hv_key_in_range(kx, ky, kz)) {
-        const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-        const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-        if (idx >= 0) {
-            const char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
-            const float tsdf = ((const float *)(unit))[word];
-            const uint32_t w = ((const uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word];
-            out[0] = tsdf * (float)w;
-            out[1] = (float)w;
-            out[2] = (float)((const uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word];
-            out[3] = (float)((const uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word];
-            out[4] = (float)((const uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word];
-        }
-    }
+    const int32_t idx = hv_keyed_unit(table, keys, gid / HV_TSDF_RRR);
+    if (idx >= 0) hv_voxel_numerators(pool + (int64_t)idx * HV_TSDF_UNIT_BYTES, (int)(gid % HV_TSDF_RRR), out);
     float *dst = payload + gid * 5;
 #pragma unroll
     for (int c = 0; c < 5; ++c) dst[c] = out[c];
@@ -144,84 +150,78 @@ __global__ void k_tsdf_import_claim(HvTable table, const int32_t *__restrict__ k
     hv_table_insert(table, hv_pack_key(kx, ky, kz));
 }
 
-__global__ void k_tsdf_import(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys,
-                              int64_t k, const float *__restrict__ payload) {
-    const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= k * HV_TSDF_RRR) return;
-    const int64_t ui = gid / HV_TSDF_RRR;
-    const int word = (int)(gid % HV_TSDF_RRR);
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (!hv_key_in_range(kx, ky, kz)) return;
-    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
-    if (idx < 0) return;
-    const float *src = payload + gid * 5;
-    char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
-    const float w = src[1];
-    ((float *)unit)[word] = w > 0.f ? src[0] / w : 0.f;
-    ((uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word] = (uint32_t)w;
-    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[2];
-    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[3];
-    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word] = (uint32_t)src[4];
-}
-
-// ---- halo merge (image-tile sharding): units stamped since the last merge, and the unpack ------------
-__global__ void k_tsdf_collect_dirty(HvTable table, const int32_t *__restrict__ stamp, int32_t merge_stamp, int32_t n_blocks,
-                                     int32_t *__restrict__ keys, int32_t cap) {
-    const int32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    bool dirty = false;
-    int32_t kx = 0, ky = 0, kz = 0;
-    if (idx < n_blocks) {
-        const unsigned long long key = table.block_keys[idx];
-        const int32_t slot = hv_table_find(table, key);
-        dirty = slot >= 0 && stamp[slot] > merge_stamp;
-        hv_unpack_key(key, kx, ky, kz);
-    }
-    const int32_t at = hv_wave_append(&table.counters[HV_CNT_OUT], dirty);
-    if (dirty && at < cap) {
-        keys[at * 3 + 0] = kx;
-        keys[at * 3 + 1] = ky;
-        keys[at * 3 + 2] = kz;
-    }
-}
-
 // action[u]: 0 = leave the unit alone (this GPU does not hold it), 1 = replace its state by the reduced numerators (this GPU
-// keeps the unit), 2 = zero it (another GPU keeps it; this one goes on fusing deltas into an empty unit)
+// keeps the unit), 2 = zero it (another GPU keeps it; this one goes on fusing deltas into an empty unit).  A null action: 1 for
+// every unit (hv_tsdf_import_numerators).  A unit this volume does not hold is left out.
 __global__ void k_tsdf_halo_unpack(HvTable table, char *__restrict__ pool, const int32_t *__restrict__ keys, int64_t k,
                                    const float *__restrict__ payload, const uint8_t *__restrict__ action) {
     const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= k * HV_TSDF_RRR) return;
     const int64_t ui = gid / HV_TSDF_RRR;
-    const int act = action[ui];
+    const int act = action != nullptr ? action[ui] : 1;
     if (act == 0) return;
-    const int word = (int)(gid % HV_TSDF_RRR);
-    const int32_t kx = keys[ui * 3], ky = keys[ui * 3 + 1], kz = keys[ui * 3 + 2];
-    if (!hv_key_in_range(kx, ky, kz)) return;
-    const int32_t slot = hv_table_find(table, hv_pack_key(kx, ky, kz));
-    const int32_t idx = slot >= 0 ? table.vals[slot] : -1;
+    const int32_t idx = hv_keyed_unit(table, keys, ui);
     if (idx < 0) return;
-    char *unit = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
-    float tsdf = 0.f;
-    uint32_t w = 0u, r = 0u, g = 0u, b = 0u;
-    if (act == 1) {
-        const float *src = payload + gid * 5;
-        const float wf = src[1];
-        tsdf = wf > 0.f ? src[0] / wf : 0.f;
-        w = (uint32_t)wf;
-        r = (uint32_t)src[2];
-        g = (uint32_t)src[3];
-        b = (uint32_t)src[4];
-    }
-    ((float *)unit)[word] = tsdf;
-    ((uint32_t *)(unit + HV_TSDF_PLANE_BYTES))[word] = w;
-    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[word] = r;
-    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[word] = g;
-    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[word] = b;
+    hv_voxel_from_numerators(pool + (int64_t)idx * HV_TSDF_UNIT_BYTES, (int)(gid % HV_TSDF_RRR), act == 1 ? payload + gid * 5 : nullptr);
 }
 
-// the claim pass of the calls that are handed unit keys (hv_tsdf_import_numerators here, hv_tsdf_unpack in hv_pack.hip)
-void hv_launch_tsdf_import_claim(hv_volume *v, const int32_t *d_keys, int64_t k) {
-    hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table, d_keys, k);
+// ---- the launches the staged and the _planned entry points share: k keys [k,3] and the payload in device memory, queued on the
+// volume's stream ----
+static int halo_launch_export(hv_volume *v, const int32_t *d_keys, int64_t k, float *d_payload) {
+    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((k * HV_TSDF_RRR + 255) / 256)), dim3(256), 0, v->stream, v->table, (const char *)v->pool, d_keys, k,
+                       d_payload);
+    HV_HIP(hipGetLastError());
+    return HV_OK;
+}
+static int halo_launch_unpack(hv_volume *v, const int32_t *d_keys, int64_t k, const float *d_payload, const uint8_t *d_action) {
+    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((k * HV_TSDF_RRR + 255) / 256)), dim3(256), 0, v->stream, v->table, (char *)v->pool, d_keys, k,
+                       d_payload, d_action);
+    HV_HIP(hipGetLastError());
+    return HV_OK;
+}
+// the dirty list (and the held list, where `held` is given) of the volume's nb units as packed keys; waits for the one number the
+// caller sizes its next step by: *n_dirty is the true count, also above dirty_cap
+static int halo_launch_lists(hv_volume *v, int64_t nb, unsigned long long *dirty, int64_t dirty_cap, unsigned long long *held, int64_t held_cap,
+                             int64_t *n_dirty) {
+    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
+    hipLaunchKernelGGL(k_halo_lists, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v->stream, v->table, (const int32_t *)v->touched_stamp,
+                       v->merge_stamp, (int32_t)nb, dirty, dirty_cap, held, held_cap);
+    HV_HIP(hipGetLastError());
+    const int rc = hv_read_counters(v); // (synchronises)
+    if (rc != HV_OK) return rc;
+    *n_dirty = v->h_counters[HV_CNT_OUT];
+    return HV_OK;
+}
+
+// the claim pass of the calls that are handed keys (hv_tsdf_import_numerators here, the unpacks of hv_pack.hip / hv_grid_pack.hip)
+// - always verified, these calls wait for the GPU anyway: a pool that is too small grows before anything is written, or the call
+// fails with the volume unchanged (a gather onto a root whose pool was sized like every other rank's)
+int hv_claim_keys(hv_volume *v, const int32_t *d_keys, int64_t k) {
+    bool checked_unused = false;
+    int rc = hv_capacity_gate(v, &checked_unused);
+    for (int attempt = 0; rc == HV_OK; ++attempt) {
+        hipLaunchKernelGGL(k_tsdf_import_claim, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, v->stream, v->table, d_keys, k);
+        rc = hv_claims_fit(v);
+        if (rc != HV_RETRY_CLAIM) break;
+        rc = attempt < 8 ? HV_OK : HV_ERR_CAPACITY;
+    }
+    return rc;
+}
+
+// the argument checks of the two host plans, then the one plan (hv_halo_plan.h)
+static int halo_plan_checked(const char *fn, const int32_t *dirty_keys, const int64_t *dirty_counts, const int32_t *held_keys,
+                             const int64_t *held_counts, int32_t world_size, int32_t rank, int32_t *shared_keys, uint8_t *action, int64_t cap,
+                             int64_t *n_shared) {
+    HV_REQUIRE(dirty_counts != nullptr && held_counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size,
+               HV_ERR_INVALID, "%s: bad argument", fn);
+    int64_t nd = 0, nh = 0;
+    for (int r = 0; r < world_size; ++r) {
+        nd += dirty_counts[r];
+        nh += held_counts[r];
+    }
+    HV_REQUIRE((nd == 0 || dirty_keys != nullptr) && (nh == 0 || held_keys != nullptr), HV_ERR_INVALID, "%s: null key list", fn);
+    *n_shared = hv_halo_plan_host(dirty_keys, dirty_counts, held_keys, held_counts, world_size, rank, shared_keys, action, cap);
+    return HV_OK;
 }
 
 extern "C" {
@@ -237,14 +237,7 @@ int hv_merge_halo_lists_device(hv_volume *v, int64_t *d_dirty_keys, int64_t dirt
     *n_dirty = 0;
     *n_held = nb;
     if (nb == 0 || d_dirty_keys == nullptr || d_held_keys == nullptr) return HV_OK; // (size query: an upper bound of both lists is nb)
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    hipLaunchKernelGGL(k_halo_lists, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v->stream, v->table, (const int32_t *)v->touched_stamp,
-                       v->merge_stamp, (int32_t)nb, (unsigned long long *)d_dirty_keys, dirty_cap, (unsigned long long *)d_held_keys, held_cap);
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v); // (synchronises: the one number the gather's size depends on)
-    if (rc != HV_OK) return rc;
-    *n_dirty = v->h_counters[HV_CNT_OUT];
-    return HV_OK;
+    return halo_launch_lists(v, nb, (unsigned long long *)d_dirty_keys, dirty_cap, (unsigned long long *)d_held_keys, held_cap, n_dirty);
 }
 
 int hv_merge_halo_plan_device(hv_volume *v, const int64_t *d_dirty_all, const int64_t *dirty_counts, int64_t dirty_stride, const int64_t *d_held_all,
@@ -333,10 +326,7 @@ int hv_tsdf_export_numerators(hv_volume *v, const int32_t *keys, int64_t k, floa
     const int i_keys = st.in(keys, sizeof(int32_t) * 3 * (size_t)k, HV_HOST), o_payload = st.out(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
     int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const int64_t total = k * HV_TSDF_RRR;
-    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const char *)v->pool, st.dev<const int32_t>(i_keys), k, st.dev<float>(o_payload));
-    HV_HIP(hipGetLastError());
+    if ((rc = halo_launch_export(v, st.dev<const int32_t>(i_keys), k, st.dev<float>(o_payload))) != HV_OK) return rc;
     if ((rc = st.finish()) != HV_OK) return rc;
     HV_HIP(hipStreamSynchronize(v->stream)); // (a device payload too: this call has always been complete on return)
     return HV_OK;
@@ -354,23 +344,9 @@ int hv_tsdf_import_numerators(hv_volume *v, const int32_t *keys, int64_t k, cons
     const int i_keys = st.in(keys, sizeof(int32_t) * 3 * (size_t)k, HV_HOST), i_payload = st.in(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
     int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const void *d_keys = st.dev<const void>(i_keys), *d_payload = st.dev<const void>(i_payload);
-    // the imported units are claimed first and the claims verified (this call synchronises anyway): a pool that is too small
-    // grows before anything is written, or the call fails with the volume unchanged (a gather onto a root whose
-    // pool was sized like every other rank's)
-    bool checked = false;
-    rc = hv_capacity_gate(v, &checked);
-    if (rc != HV_OK) return rc;
-    for (int attempt = 0;; ++attempt) {
-        hv_launch_tsdf_import_claim(v, (const int32_t *)d_keys, k);
-        rc = hv_claims_fit(v);
-        if (rc == HV_OK) break;
-        if (rc != HV_RETRY_CLAIM || attempt >= 8) return rc == HV_RETRY_CLAIM ? HV_ERR_CAPACITY : rc;
-    }
-    const int64_t total = k * HV_TSDF_RRR;
-    hipLaunchKernelGGL(k_tsdf_import, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (char *)v->pool, (const int32_t *)d_keys, k, (const float *)d_payload);
-    HV_HIP(hipGetLastError());
+    const int32_t *d_keys = st.dev<const int32_t>(i_keys);
+    if ((rc = hv_claim_keys(v, d_keys, k)) != HV_OK) return rc; // the imported units are claimed first: nothing is written unless they fit
+    if ((rc = halo_launch_unpack(v, d_keys, k, st.dev<const float>(i_payload), nullptr)) != HV_OK) return rc; // (no actions: every unit is kept)
     hv_launch_publish_status(v); // the imported units are part of the published occupancy (a later rollback keeps them)
     HV_HIP(hipStreamSynchronize(v->stream));
     return HV_OK;
@@ -389,19 +365,17 @@ int hv_tsdf_dirty_keys(hv_volume *v, int32_t *keys, int64_t cap, int64_t *n) {
     *n = 0;
     if (nb == 0) return HV_OK;
     v->mesh_cache_version = v->points_cache_version = 0; // out_a is reused below
-    rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, sizeof(int32_t) * 3 * (size_t)nb);
+    rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, sizeof(uint64_t) * (size_t)nb);
     if (rc != HV_OK) return rc;
-    HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_OUT], 0, sizeof(int32_t), v->stream));
-    hipLaunchKernelGGL(k_tsdf_collect_dirty, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (const int32_t *)v->touched_stamp, v->merge_stamp, (int32_t)nb, (int32_t *)v->out_a, (int32_t)nb);
-    HV_HIP(hipGetLastError());
-    rc = hv_read_counters(v);
+    int64_t nd = 0;
+    rc = halo_launch_lists(v, nb, (unsigned long long *)v->out_a, nb, nullptr, 0, &nd);
     if (rc != HV_OK) return rc;
-    const int64_t nd = v->h_counters[HV_CNT_OUT];
     *n = nd;
     if (keys == nullptr || nd == 0) return HV_OK;
+    std::vector<uint64_t> packed((size_t)nd);
+    HV_HIP(hipMemcpy(packed.data(), v->out_a, sizeof(uint64_t) * (size_t)nd, hipMemcpyDeviceToHost));
     std::vector<std::array<int32_t, 3>> out((size_t)nd);
-    HV_HIP(hipMemcpy(out.data(), v->out_a, sizeof(int32_t) * 3 * (size_t)nd, hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < nd; ++i) hv_unpack_key(packed[i], out[i][0], out[i][1], out[i][2]);
     std::sort(out.begin(), out.end());
     const int64_t m = std::min(nd, cap);
     for (int64_t i = 0; i < m; ++i) memcpy(keys + i * 3, out[i].data(), 12);
@@ -415,109 +389,18 @@ int hv_tsdf_mark_merged(hv_volume *v) {
     return HV_OK;
 }
 
+// the plan from the dirty lists alone: the held plan with every lister taken as a holder (a rank lists a key once, so the lowest
+// lister is the lowest holder)
 int hv_merge_halo_plan(const int32_t *gathered_keys, const int64_t *counts, int32_t world_size, int32_t rank,
                        int32_t *shared_keys, uint8_t *action, int64_t cap, int64_t *n_shared) {
-    HV_REQUIRE(counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size, HV_ERR_INVALID,
-               "hv_merge_halo_plan: bad argument");
-    // (key, rank) pairs of every rank's dirty list, sorted by key then rank; a key listed by >= 2 ranks is shared
-    struct Entry { std::array<int32_t, 3> key; int32_t rank; };
-    int64_t total = 0;
-    for (int r = 0; r < world_size; ++r) total += counts[r];
-    HV_REQUIRE(total == 0 || gathered_keys != nullptr, HV_ERR_INVALID, "hv_merge_halo_plan: null key list");
-    std::vector<Entry> all((size_t)total);
-    int64_t at = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < counts[r]; ++i, ++at) {
-            memcpy(all[at].key.data(), gathered_keys + at * 3, 12);
-            all[at].rank = r;
-        }
-    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) { return a.key != b.key ? a.key < b.key : a.rank < b.rank; });
-    int64_t ns = 0;
-    for (int64_t i = 0; i < total;) {
-        int64_t j = i;
-        bool mine = false;
-        while (j < total && all[j].key == all[i].key) {
-            mine |= all[j].rank == rank;
-            ++j;
-        }
-        if (j - i >= 2) { // listed by two ranks or more (a rank lists a key once)
-            if (shared_keys != nullptr && action != nullptr && ns < cap) {
-                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
-                // the lowest listing rank keeps the unit; EVERY other rank zeroes its copy if it has one - also a rank that holds
-                // the unit from an earlier window without having listed it now: the pack step exports whatever a rank holds,
-                // so a holder that kept its copy would be counted twice (unpack is a no-op where the unit does not exist)
-                action[ns] = all[i].rank == rank ? 1 : 2;
-                (void)mine;
-            }
-            ++ns;
-        }
-        i = j;
-    }
-    *n_shared = ns;
-    return HV_OK;
+    return halo_plan_checked("hv_merge_halo_plan", gathered_keys, counts, gathered_keys, counts, world_size, rank, shared_keys, action, cap, n_shared);
 }
 
 int hv_merge_halo_plan_held(const int32_t *dirty_keys, const int64_t *dirty_counts, const int32_t *held_keys,
                             const int64_t *held_counts, int32_t world_size, int32_t rank, int32_t *shared_keys, uint8_t *action,
                             int64_t cap, int64_t *n_shared) {
-    HV_REQUIRE(dirty_counts != nullptr && held_counts != nullptr && n_shared != nullptr && world_size >= 1 && rank >= 0 && rank < world_size,
-               HV_ERR_INVALID, "hv_merge_halo_plan_held: bad argument");
-    // (key, rank, kind) of every rank's two lists; a key is merged when some rank updated it since its last merge AND two
-    // ranks or more hold it: afterwards the lowest HOLDING rank has the complete unit and every other holder zeros
-    struct Entry { std::array<int32_t, 3> key; int32_t rank; int32_t dirty; };
-    int64_t nd = 0, nh = 0;
-    for (int r = 0; r < world_size; ++r) {
-        nd += dirty_counts[r];
-        nh += held_counts[r];
-    }
-    HV_REQUIRE((nd == 0 || dirty_keys != nullptr) && (nh == 0 || held_keys != nullptr), HV_ERR_INVALID, "hv_merge_halo_plan_held: null key list");
-    std::vector<Entry> all((size_t)(nd + nh));
-    int64_t at = 0, src = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < dirty_counts[r]; ++i, ++at, ++src) {
-            memcpy(all[at].key.data(), dirty_keys + src * 3, 12);
-            all[at].rank = r;
-            all[at].dirty = 1;
-        }
-    src = 0;
-    for (int r = 0; r < world_size; ++r)
-        for (int64_t i = 0; i < held_counts[r]; ++i, ++at, ++src) {
-            memcpy(all[at].key.data(), held_keys + src * 3, 12);
-            all[at].rank = r;
-            all[at].dirty = 0;
-        }
-    std::sort(all.begin(), all.end(), [](const Entry &a, const Entry &b) {
-        if (a.key != b.key) return a.key < b.key;
-        if (a.rank != b.rank) return a.rank < b.rank;
-        return a.dirty < b.dirty;
-    });
-    int64_t ns = 0;
-    const int64_t total = nd + nh;
-    for (int64_t i = 0; i < total;) {
-        int64_t j = i;
-        int holders = 0, keeper = -1, last_holder = -1;
-        bool any_dirty = false;
-        while (j < total && all[j].key == all[i].key) {
-            if (all[j].dirty) {
-                any_dirty = true;
-            } else if (all[j].rank != last_holder) {
-                last_holder = all[j].rank;
-                if (keeper < 0) keeper = all[j].rank;
-                ++holders;
-            }
-            ++j;
-        }
-        if (any_dirty && holders >= 2) {
-            if (shared_keys != nullptr && action != nullptr && ns < cap) {
-                memcpy(shared_keys + ns * 3, all[i].key.data(), 12);
-                action[ns] = keeper == rank ? 1 : 2;
-            }
-            ++ns;
-        }
-        i = j;
-    }
-    *n_shared = ns;
-    return HV_OK;
+    return halo_plan_checked("hv_merge_halo_plan_held", dirty_keys, dirty_counts, held_keys, held_counts, world_size, rank, shared_keys, action, cap,
+                             n_shared);
 }
 
 int hv_merge_halo_pack(hv_volume *v, const int32_t *shared_keys, int64_t k, float *payload, int32_t loc) {
@@ -536,12 +419,10 @@ int hv_merge_halo_unpack(hv_volume *v, const int32_t *shared_keys, int64_t k, co
     HvStage st(v, loc); // (the keys and the actions are host memory by contract)
     const int i_keys = st.in(shared_keys, (size_t)k * 12, HV_HOST), i_action = st.in(action, (size_t)k, HV_HOST),
               i_payload = st.in(payload, sizeof(float) * 5 * HV_TSDF_RRR * (size_t)k);
-    const int rc = st.commit(&v->stage, &v->stage_bytes);
+    int rc = st.commit(&v->stage, &v->stage_bytes);
     if (rc != HV_OK) return rc;
-    const int64_t total = k * HV_TSDF_RRR;
-    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table,
-                       (char *)v->pool, st.dev<const int32_t>(i_keys), k, st.dev<const float>(i_payload), st.dev<const uint8_t>(i_action));
-    HV_HIP(hipGetLastError());
+    rc = halo_launch_unpack(v, st.dev<const int32_t>(i_keys), k, st.dev<const float>(i_payload), st.dev<const uint8_t>(i_action));
+    if (rc != HV_OK) return rc;
     HV_HIP(hipStreamSynchronize(v->stream)); // (this call has always been complete on return)
     return HV_OK;
 }
@@ -554,11 +435,7 @@ int hv_merge_halo_pack_planned(hv_volume *v, int64_t first, int64_t count, float
     HV_REQUIRE(first >= 0 && count >= 0 && first + count <= v->halo_plan_n, HV_ERR_INVALID, "hv_merge_halo_pack_planned: range outside the plan");
     if (count == 0) return HV_OK;
     HV_HIP(hipSetDevice(v->device));
-    const int64_t total = count * HV_TSDF_RRR;
-    hipLaunchKernelGGL(k_tsdf_export, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (const char *)v->pool,
-                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload);
-    HV_HIP(hipGetLastError());
-    return HV_OK;
+    return halo_launch_export(v, (const int32_t *)v->halo_plan + 3 * first, count, d_payload);
 }
 
 int hv_merge_halo_unpack_planned(hv_volume *v, int64_t first, int64_t count, const float *d_payload) {
@@ -569,12 +446,8 @@ int hv_merge_halo_unpack_planned(hv_volume *v, int64_t first, int64_t count, con
     v->content_version += 1;
     v->extract_epoch += 1; // (writes voxels without stamping their units)
     HV_HIP(hipSetDevice(v->device));
-    const int64_t total = count * HV_TSDF_RRR;
-    hipLaunchKernelGGL(k_tsdf_halo_unpack, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, v->stream, v->table, (char *)v->pool,
-                       (const int32_t *)v->halo_plan + 3 * first, count, d_payload,
-                       (const uint8_t *)v->halo_plan + (size_t)v->halo_plan_n * 12 + first);
-    HV_HIP(hipGetLastError());
-    return HV_OK;
+    return halo_launch_unpack(v, (const int32_t *)v->halo_plan + 3 * first, count, d_payload,
+                              (const uint8_t *)v->halo_plan + (size_t)v->halo_plan_n * 12 + first);
 }
 
 } // extern "C"

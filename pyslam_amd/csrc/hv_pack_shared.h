@@ -110,15 +110,7 @@ inline int unpack_fetch_sections(hv_volume *v, const void *d_src, const uint64_t
 inline int unpack_claim_keys(hv_volume *v, const int32_t *d_keys, int64_t n) {
     const int64_t max_new = v->max_new_per_call;
     const double avg_new = v->avg_new_per_call;
-    bool checked_unused = false;
-    int rc = hv_capacity_gate(v, &checked_unused);
-    for (int attempt = 0; rc == HV_OK; ++attempt) {
-        hv_launch_tsdf_import_claim(v, d_keys, n);
-        rc = hv_claims_fit(v);
-        if (rc == HV_OK) break;
-        if (rc == HV_RETRY_CLAIM && attempt < 8) rc = HV_OK;
-        else if (rc == HV_RETRY_CLAIM) rc = HV_ERR_CAPACITY;
-    }
+    const int rc = hv_claim_keys(v, d_keys, n);
     v->max_new_per_call = max_new;
     v->avg_new_per_call = avg_new;
     return rc;

@@ -48,6 +48,38 @@ def union_keys(key_sets):
     return np.unique(allk, axis=0)
 
 
+def _backend(group):
+    """-> (on_gpu, device) of a process group: backend "nccl" (RCCL) moves tensors of the current GPU, every other backend host tensors."""
+    import torch
+    import torch.distributed as dist
+
+    on_gpu = dist.get_backend(group) == "nccl"
+    return on_gpu, torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+
+
+def gather_rows(rows, world_size, group=None):
+    """All ranks' arrays of rows ([n_i, ...] of one dtype torch carries and one row shape) -> list of host arrays in rank order, the
+    same on every rank.  Two collectives: the counts (one all-gather), then one [world, longest, ...] buffer gathered in place and
+    downloaded once - over RCCL the rows make ONE device round trip."""
+    import torch
+    import torch.distributed as dist
+
+    _, dev = _backend(group)
+    rows = np.ascontiguousarray(rows)
+    n_local = torch.tensor([len(rows)], dtype=torch.int64, device=dev)
+    counts_t = torch.zeros(world_size, dtype=torch.int64, device=dev)
+    dist.all_gather_into_tensor(counts_t, n_local, group=group)
+    counts = [int(c) for c in counts_t.cpu().tolist()]
+    local = torch.from_numpy(rows)
+    buf = torch.zeros((max(max(counts), 1),) + rows.shape[1:], dtype=local.dtype, device=dev)
+    if len(rows):
+        buf[: len(rows)].copy_(local, non_blocking=False)
+    gathered = torch.empty((world_size,) + buf.shape, dtype=local.dtype, device=dev)
+    dist.all_gather_into_tensor(gathered.view(-1), buf.view(-1), group=group)
+    host = gathered.cpu().numpy()
+    return [host[r, :c] for r, c in enumerate(counts)]
+
+
 class ShardedTSDF:
     BUCKET_BYTES = 64 << 20
 
@@ -86,22 +118,18 @@ class ShardedTSDF:
         self.volume.integrate_batch(depth, color, intrinsic, extrinsics, depth_scale, depth_trunc)
 
     # -- merge -----------------------------------------------------------------------------------
-    def _gather_keys(self, keys, dist, torch, dev):
-        """All ranks' key lists ([n_i, 3] int32) -> list of host arrays.  The plan that consumes them is host code
-        (hv_merge_halo_plan_held), so this is where the keys are meant to end; over RCCL they make ONE device round trip:
-        counts (one all-gather), then one [world, cap, 3] buffer gathered in place and downloaded once."""
-        n_local = torch.tensor([keys.shape[0]], dtype=torch.int64, device=dev)
-        counts_t = torch.zeros(self.world_size, dtype=torch.int64, device=dev)
-        dist.all_gather_into_tensor(counts_t, n_local, group=self.group)
-        counts = [int(c) for c in counts_t.cpu().tolist()]
-        cap = max(max(counts), 1)
-        buf = torch.zeros((cap, 3), dtype=torch.int32, device=dev)
-        if keys.shape[0]:
-            buf[: keys.shape[0]].copy_(torch.from_numpy(np.ascontiguousarray(keys)), non_blocking=False)
-        gathered = torch.empty((self.world_size, cap, 3), dtype=torch.int32, device=dev)
-        dist.all_gather_into_tensor(gathered.view(-1), buf.view(-1), group=self.group)
-        host = gathered.cpu().numpy()
-        return [host[r, :c] for r, c in enumerate(counts)]
+    def _buckets(self, k, dev):
+        """The walk of every pack -> collective -> unpack loop over k units: (first unit, payload [units, res^3, 5] float32 on `dev`)
+        per BUCKET_BYTES bucket.  torch.empty: the export kernel (volume's own HIP stream) writes every element, so no fill kernel on
+        torch's stream can race with it.  A loop drops its payload (``del``) before it asks for the next: one bucket is alive at a time."""
+        import torch
+
+        res3 = self.volume.res ** 3
+        units_per_bucket = max(1, self.BUCKET_BYTES // (res3 * 5 * 4))
+        for b0 in range(0, k, units_per_bucket):
+            payload = torch.empty((min(units_per_bucket, k - b0), res3, 5), dtype=torch.float32, device=dev)
+            yield b0, payload
+            del payload
 
     def merge(self, root=0):
         """Sum-reduce all ranks' volumes into rank `root`; the other ranks are cleared.
@@ -112,20 +140,12 @@ class ShardedTSDF:
         import torch
         import torch.distributed as dist
 
-        on_gpu = dist.get_backend(self.group) == "nccl"
-        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
-        keys = union_keys(self._gather_keys(self.volume.unit_keys(), dist, torch, dev))
+        on_gpu, dev = _backend(self.group)
+        keys = union_keys(gather_rows(np.asarray(self.volume.unit_keys(), np.int32).reshape(-1, 3), self.world_size, self.group))
         k = keys.shape[0]
-        if k == 0:
-            return 0
-        res3 = self.volume.res ** 3
-        units_per_bucket = max(1, self.BUCKET_BYTES // (res3 * 5 * 4))
-        for b0 in range(0, k, units_per_bucket):
-            sub = keys[b0 : b0 + units_per_bucket]
-            # torch.empty: the export kernel (volume's own HIP stream, synchronised on return) writes
-            # every element, so no fill kernel on torch's stream can race with it
-            payload = torch.empty((sub.shape[0], res3, 5), dtype=torch.float32, device=dev)
-            self.volume.export_numerators(sub, out=payload if on_gpu else payload.numpy())
+        for b0, payload in self._buckets(k, dev):
+            sub = keys[b0 : b0 + len(payload)]
+            self.volume.export_numerators(sub, out=payload if on_gpu else payload.numpy())  # (synchronised on return)
             dist.reduce(payload, dst=root, op=dist.ReduceOp.SUM, group=self.group)
             if on_gpu:
                 torch.cuda.current_stream().synchronize()  # RCCL result visible before the import kernel reads it
@@ -137,7 +157,7 @@ class ShardedTSDF:
                 # import claims the units first and grows the root's pool when they do not fit.)
                 self.volume.import_numerators(sub, payload if on_gpu else payload.numpy())
             del payload
-        if self.rank != root:
+        if k and self.rank != root:
             self.volume.reset()
         return k
 
@@ -157,17 +177,15 @@ class ShardedTSDF:
         from . import _lib as L
 
         lib = L.load()
-        on_gpu = dist.get_backend(self.group) == "nccl"
-        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+        on_gpu, dev = _backend(self.group)
         if on_gpu and hasattr(self.volume, "halo_lists_device"):
             return self._merge_halo_device(dist, torch, dev)
         mine = np.ascontiguousarray(self.volume.dirty_keys(), dtype=np.int32).reshape(-1, 3)
         held = np.ascontiguousarray(self.volume.unit_keys(), dtype=np.int32).reshape(-1, 3)
 
         def gathered(keys):
-            lists = self._gather_keys(keys, dist, torch, dev)
-            return (np.ascontiguousarray(np.concatenate([x.reshape(-1, 3) for x in lists], axis=0), dtype=np.int32),
-                    np.array([len(x) for x in lists], dtype=np.int64))
+            lists = gather_rows(keys, self.world_size, self.group)
+            return np.ascontiguousarray(np.concatenate(lists, axis=0)), np.array([len(x) for x in lists], dtype=np.int64)
 
         (dk, dc), (hk, hc) = gathered(mine), gathered(held)
         n = ctypes.c_int64()
@@ -185,11 +203,8 @@ class ShardedTSDF:
             k = len(shared)
             action = np.ones(k, np.uint8)
         self.last_halo = {"shared_keys": shared, "action": action, "dirty": len(mine), "payload_bytes": 0}
-        res3 = self.volume.res ** 3
-        units_per_bucket = max(1, self.BUCKET_BYTES // (res3 * 5 * 4))
-        for b0 in range(0, k, units_per_bucket):
-            sub, act = shared[b0 : b0 + units_per_bucket], action[b0 : b0 + units_per_bucket]
-            payload = torch.empty((sub.shape[0], res3, 5), dtype=torch.float32, device=dev)
+        for b0, payload in self._buckets(k, dev):
+            sub, act = shared[b0 : b0 + len(payload)], action[b0 : b0 + len(payload)]
             self.volume.export_numerators(sub, out=payload if on_gpu else payload.numpy())  # == hv_merge_halo_pack
             dist.all_reduce(payload, op=dist.ReduceOp.SUM, group=self.group)
             if on_gpu:
@@ -199,7 +214,6 @@ class ShardedTSDF:
             del payload
         self.volume.mark_merged()
         return k, len(mine)
-
 
     def _merge_halo_device(self, dist, torch, dev):
         """merge_halo over RCCL with the key lists and the plan in device memory (hv_halo.hip): the lists are written into torch
@@ -228,17 +242,13 @@ class ShardedTSDF:
         k = vol.halo_plan_device(dirty_all, np.ascontiguousarray(all_counts[:, 0]), held_all, np.ascontiguousarray(all_counts[:, 1]),
                                  self.world_size, self.rank, all_dirty_kept=own_all)
         self.last_halo = _LazyHalo(vol, n_dirty)
-        res3 = vol.res ** 3
-        units_per_bucket = max(1, self.BUCKET_BYTES // (res3 * 5 * 4))
-        for b0 in range(0, k, units_per_bucket):
-            cnt = min(units_per_bucket, k - b0)
-            payload = torch.empty((cnt, res3, 5), dtype=torch.float32, device=dev)
-            vol.halo_pack_planned(b0, cnt, payload)
+        for b0, payload in self._buckets(k, dev):
+            vol.halo_pack_planned(b0, len(payload), payload)
             vol.synchronize()  # the pack (volume's stream) before the all-reduce (torch's stream)
             dist.all_reduce(payload, op=dist.ReduceOp.SUM, group=self.group)
             torch.cuda.current_stream().synchronize()  # RCCL result visible before the unpack kernel reads it
             self.last_halo["payload_bytes"] += payload.numel() * 4
-            vol.halo_unpack_planned(b0, cnt, payload)
+            vol.halo_unpack_planned(b0, len(payload), payload)
             vol.synchronize()  # (the payload is dropped below)
             del payload
         vol.mark_merged()
@@ -303,25 +313,10 @@ class ShardedVoxelGrid:
         pts, cols = np.ascontiguousarray(v.points, np.float32), np.ascontiguousarray(v.colors, np.float32)
         if self.world_size == 1 and not self.force_collectives:
             return pts, cols
-        import torch
-        import torch.distributed as dist
-
-        on_gpu = dist.get_backend(self.group) == "nccl"
-        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
-        n_local = torch.tensor([len(pts)], dtype=torch.int64, device=dev)
-        counts = [torch.zeros_like(n_local) for _ in range(self.world_size)]
-        dist.all_gather(counts, n_local, group=self.group)
-        counts = [int(c.item()) for c in counts]
-        cap = max(max(counts), 1)
-        buf = torch.zeros((cap, 6), dtype=torch.float32, device=dev)
-        if len(pts):
-            buf[: len(pts), :3] = torch.from_numpy(pts).to(dev)
-            buf[: len(pts), 3:] = torch.from_numpy(cols).to(dev)
-        gathered = [torch.zeros_like(buf) for _ in range(self.world_size)]
-        dist.all_gather(gathered, buf, group=self.group)
+        lists = gather_rows(np.concatenate([pts.reshape(-1, 3), cols.reshape(-1, 3)], axis=1), self.world_size, self.group)
         if self.rank != root:
             return None
-        rows = np.concatenate([g[:c].cpu().numpy() for g, c in zip(gathered, counts)], axis=0)
+        rows = np.concatenate(lists, axis=0)
         return rows[:, :3], rows[:, 3:]
 
 
@@ -344,7 +339,7 @@ class ShardedSemanticGrid:
         if self.world_size > 1 or self.force_collectives:
             import torch.distributed as dist
 
-            if dist.is_initialized() and dist.get_backend(self.group) == "nccl":
+            if dist.is_initialized() and _backend(self.group)[0]:
                 self.grid._pair_exchange_device = self.all_gather_pairs_device
             else:
                 self.grid._pair_exchange = self.all_gather_pairs
@@ -370,31 +365,13 @@ class ShardedSemanticGrid:
         """-> the ranks' (keys u64, votes i32) lists merged - identical on every rank: equal pairs (the image's 'instance seen' markers
         are contributed by every rank, and an object's voxels live on several) are added up, so the merged list is no longer than a
         single GPU's would be and the decide stage's 4096-pair limit is not reached by repetition."""
-        import torch
-        import torch.distributed as dist
-
-        on_gpu = dist.get_backend(self.group) == "nccl"
-        dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
-        keys = np.ascontiguousarray(keys, np.uint64)
-        counts = np.ascontiguousarray(counts, np.int32)
-        n_local = torch.tensor([len(keys)], dtype=torch.int64, device=dev)
-        sizes = [torch.zeros_like(n_local) for _ in range(self.world_size)]
-        dist.all_gather(sizes, n_local, group=self.group)
-        sizes = [int(x.item()) for x in sizes]
+        # one row per pair: the key's bits as int64 and the votes widened to int64
+        local = np.stack([np.ascontiguousarray(keys, np.uint64).view(np.int64), np.asarray(counts, np.int64)], axis=1)
+        lists = gather_rows(local, self.world_size, self.group)
+        sizes = [len(x) for x in lists]
         cap = max(max(sizes), 1)
-        # one message per rank: [cap] int64 keys followed by [cap] votes widened to int64
-        buf = torch.zeros(2 * cap, dtype=torch.int64, device=dev)
-        if len(keys):
-            buf[: len(keys)] = torch.from_numpy(keys.view(np.int64)).to(dev)
-            buf[cap : cap + len(keys)] = torch.from_numpy(counts.astype(np.int64)).to(dev)
-        gathered = [torch.zeros_like(buf) for _ in range(self.world_size)]
-        dist.all_gather(gathered, buf, group=self.group)
-        ks, cs = [], []
-        for g, m in zip(gathered, sizes):
-            g = g.cpu().numpy()
-            ks.append(g[:m].view(np.uint64))
-            cs.append(g[cap : cap + m].astype(np.int32))
-        all_k, all_c = np.concatenate(ks), np.concatenate(cs)
+        both = np.concatenate(lists, axis=0)
+        all_k, all_c = np.ascontiguousarray(both[:, 0]).view(np.uint64), both[:, 1].astype(np.int32)
         uk, inv = np.unique(all_k, return_inverse=True)  # (sorted: the same order on every rank)
         uc = np.zeros(len(uk), np.int64)
         np.add.at(uc, inv, all_c.astype(np.int64))
@@ -411,23 +388,9 @@ class ShardedSemanticGrid:
                                np.asarray(v.object_ids, np.float64)[:, None], np.asarray(v.confidences, np.float64)[:, None]], axis=1) \
             if len(v.points) else np.zeros((0, 9), np.float64)
         if self.world_size > 1 or self.force_collectives:
-            import torch
-            import torch.distributed as dist
-
-            on_gpu = dist.get_backend(self.group) == "nccl"
-            dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
-            n_local = torch.tensor([len(rows)], dtype=torch.int64, device=dev)
-            sizes = [torch.zeros_like(n_local) for _ in range(self.world_size)]
-            dist.all_gather(sizes, n_local, group=self.group)
-            sizes = [int(x.item()) for x in sizes]
-            cap = max(max(sizes), 1)
-            buf = torch.zeros((cap, 9), dtype=torch.float64, device=dev)
-            if len(rows):
-                buf[: len(rows)] = torch.from_numpy(rows).to(dev)
-            gathered = [torch.zeros_like(buf) for _ in range(self.world_size)]
-            dist.all_gather(gathered, buf, group=self.group)
+            lists = gather_rows(rows, self.world_size, self.group)
             if self.rank != root:
                 return None
-            rows = np.concatenate([g[:m].cpu().numpy() for g, m in zip(gathered, sizes)], axis=0)
+            rows = np.concatenate(lists, axis=0)
         return (rows[:, 0:3], rows[:, 3:6].astype(np.float32), rows[:, 6].astype(np.int32), rows[:, 7].astype(np.int32),
                 rows[:, 8].astype(np.float32))

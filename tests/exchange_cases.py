@@ -3,7 +3,8 @@ families, each built once and only read:
 
 KEY-LIST CASES (key_list_cases): per rank a dirty list and a held list of unit keys, worlds 1, 2, 3, 8 and 64, no voxel content.
   padded(case) gives the gathered form the device plan takes: [world, stride] packed keys with stride = the longest list + 5 and
-  the padding filled with LIVE keys of other ranks - a reader that looks behind a rank's count finds plausible entries.
+  the padding filled with LIVE keys of other ranks - a reader that looks behind a rank's count finds plausible entries.  One
+  case ("w3 held twice") has a rank list keys twice as held - one holder all the same; every other list is free of repeats.
 UNIT STATES (unit_cases): per rank a state of tests/pack_reference.py (word order, tsdf as bit patterns) for 2, 3 and 8 ranks, at
   most 24 units per rank: random units with 30 % unobserved voxels, one-voxel units, voxels of weight 0 whose tsdf bits are not
   zero, colour sums at 0 and at 255 * w; with a key list (absent units under every action, an out-of-range key, for export a
@@ -30,16 +31,19 @@ NV = ps.NV
 
 # ---- key lists -----------------------------------------------------------------------------------------------------------------
 class KeyLists:
-    def __init__(self, name, world, entries, seed=0):
-        """entries: [(key, ranks that list it dirty, ranks that hold it)]; each rank's lists come out shuffled."""
+    def __init__(self, name, world, entries, seed=0, held_twice=()):
+        """entries: [(key, ranks that list it dirty, ranks that hold it)]; each rank's lists come out shuffled.  held_twice:
+        [(key, rank)] - the rank lists that key a second time as held; every other list is free of repeats."""
         self.name, self.world = name, world
         rng = np.random.default_rng(1000 + seed)
         self.entries = [(tuple(int(v) for v in k), tuple(sorted(d)), tuple(sorted(h))) for k, d, h in entries]
         assert len({k for k, _, _ in self.entries}) == len(self.entries)
+        self.held_twice = tuple((tuple(int(v) for v in k), int(r)) for k, r in held_twice)
+        assert all(any(k == e[0] and r in e[2] for e in self.entries) for k, r in self.held_twice) and len(set(self.held_twice)) == len(self.held_twice)
         self.dirty, self.held = [], []
         for r in range(world):
             d = [k for k, dr, _ in self.entries if r in dr]
-            h = [k for k, _, hr in self.entries if r in hr]
+            h = [k for k, _, hr in self.entries if r in hr] + [k for k, q in self.held_twice if q == r]
             self.dirty.append(np.array([d[i] for i in rng.permutation(len(d))], np.int32).reshape(-1, 3))
             self.held.append(np.array([h[i] for i in rng.permutation(len(h))], np.int32).reshape(-1, 3))
         self.dirty_counts = np.array([len(x) for x in self.dirty], np.int64)
@@ -150,6 +154,9 @@ def key_list_cases():
         KeyLists("w3 first empty", 3, _on_two_of_three(_RULES3, 1, 2), 5),
         KeyLists("w3 middle empty", 3, _on_two_of_three(_RULES3, 0, 2) + _mixed(30, 3, 12, z=20, skip=(1,)), 6),
         KeyLists("w3 last empty", 3, _on_two_of_three(_RULES3, 0, 1), 7),
+        # a rank that lists a key twice as held is ONE holder: (6, 1, 0) has one holder and is not shared, (6, 1, 1) has two, keeper 1
+        KeyLists("w3 held twice", 3, [((6, 1, 0), (0,), (1,)), ((6, 1, 1), (0,), (1, 2)), ((6, 1, 2), (2,), (2,))], 15,
+                 held_twice=[((6, 1, 0), 1), ((6, 1, 1), 1)]),
         KeyLists("w3 all empty", 3, []),
         KeyLists("w8 all empty", 8, []),
         _straddle(8, 241, 0, 8, "w8 straddle total 257"),  # the run of 16 covers sorted entries 241 .. 256

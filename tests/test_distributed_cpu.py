@@ -509,3 +509,49 @@ def test_semantic_pair_lists_are_all_gathered_in_rank_order(tmp_path, world):
     z = np.load(tmp_path / "sem_rows.npz")
     assert len(z["points"]) == sum(4 + r for r in range(world))
     assert sorted(z["cls"].tolist()) == sorted(sum(([r] * (4 + r) for r in range(world)), []))
+
+
+# ---- the one padded gather behind every ragged all-gather --------------------------------------------------------------------------
+def _gather_rows_local(rank, kind):
+    """Rank `rank`'s rows of the gather test: ranks 0, 1, 2 hold 1, 0 and 5 rows; the values name the rank and the row."""
+    n = (1, 0, 5)[rank]
+    rng = np.random.default_rng(40 + rank)
+    if kind == "keys":
+        return rng.integers(-(1 << 20), 1 << 20, (n, 3)).astype(np.int32)
+    if kind == "words":
+        return rng.integers(-(1 << 62), 1 << 62, n).astype(np.int64)
+    return rng.standard_normal((n, 9))
+
+
+def _gather_rows_worker(rank, world, port, tmpdir):
+    sys.path.insert(0, ROOT)
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    import torch.distributed as dist
+
+    from pyslam_amd.distributed import gather_rows
+
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    out = {}
+    for kind in ("keys", "words", "rows"):
+        for r, a in enumerate(gather_rows(_gather_rows_local(rank, kind), world)):
+            out[f"{kind}{r}"] = a
+    np.savez(os.path.join(tmpdir, f"gather_rows{rank}.npz"), **out)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_gather_rows_returns_every_ranks_rows_exactly_and_in_rank_order(tmp_path):
+    """pyslam_amd.distributed.gather_rows over gloo with three ranks that hold 1, 0 and 5 rows: [n,3] int32, [n] int64 and [n,9]
+    float64 rows come back on EVERY rank as the ranks' own arrays - dtype, shape and bits - in rank order."""
+    import torch.multiprocessing as mp
+
+    port = 29500 + ((os.getpid() + 1555) % 2000)
+    mp.spawn(_gather_rows_worker, args=(3, port, str(tmp_path)), nprocs=3, join=True)
+    for rank in range(3):
+        z = np.load(tmp_path / f"gather_rows{rank}.npz")
+        for kind in ("keys", "words", "rows"):
+            for r in range(3):
+                want, got = _gather_rows_local(r, kind), z[f"{kind}{r}"]
+                assert got.dtype == want.dtype and got.shape == want.shape, (rank, kind, r, got.dtype, got.shape)
+                assert got.tobytes() == want.tobytes(), (rank, kind, r)

@@ -59,6 +59,32 @@ def test_restated_plan_equals_the_host_plan_and_both_orders_list_the_same_set(ca
         assert rows(ER.plan_held_padded(*EC.padded(case), case.world, rank)) == rows(packed)
 
 
+@pytest.mark.parametrize("case", EC.key_list_cases(), ids=lambda c: c.name)
+def test_the_older_plan_is_the_held_plan_with_the_dirty_lists_as_held_lists(case):
+    """hv_merge_halo_plan(keys, counts) == hv_merge_halo_plan_held(keys, counts, keys, counts), keys and actions, on every rank: a
+    key listed by two ranks or more, the lowest lister keeps (a rank lists a key once in its dirty list)."""
+    from pyslam_amd import _lib as L
+
+    lib = L.load()
+    dk = np.ascontiguousarray(np.concatenate(case.dirty))
+    cap = len(dk) + 1
+    listers = {}
+    for r, d in enumerate(case.dirty):
+        for k in d.tolist():
+            listers.setdefault(tuple(k), []).append(r)
+    assert all(len(set(v)) == len(v) for v in listers.values())
+    for rank in range(case.world):
+        n_old, n_held = ctypes.c_int64(), ctypes.c_int64()
+        old = np.zeros((cap, 3), np.int32), np.zeros(cap, np.uint8)
+        held = np.zeros((cap, 3), np.int32), np.zeros(cap, np.uint8)
+        L.check(lib.hv_merge_halo_plan(L.ptr(dk), L.ptr(case.dirty_counts), case.world, rank, L.ptr(old[0]), L.ptr(old[1]), cap, ctypes.byref(n_old)))
+        L.check(lib.hv_merge_halo_plan_held(L.ptr(dk), L.ptr(case.dirty_counts), L.ptr(dk), L.ptr(case.dirty_counts), case.world, rank,
+                                            L.ptr(held[0]), L.ptr(held[1]), cap, ctypes.byref(n_held)))
+        assert n_old.value == n_held.value and rows(old) == rows(held), (case.name, rank)
+        want = [k + (1 if min(v) == rank else 2,) for k, v in sorted(listers.items()) if len(v) >= 2]
+        assert rows(old)[:n_old.value] == want, (case.name, rank)
+
+
 def _first_difference(right, wrong, cases, label):
     for case in cases:
         for rank in label(case):
@@ -119,6 +145,14 @@ def test_key_list_cases_hold_what_they_promise():
     assert len(c.dirty[0]) and not (c.held[0] == np.array((0, 0, 1))).all(1).any() and (c.dirty[0] == np.array((0, 0, 1))).all(1).any()
     # the two orders differ on it
     assert ER.plan_held(c.dirty, c.held, 3, 0, order="xyz")[0].tolist() != ER.plan_held(c.dirty, c.held, 3, 0, order="packed")[0].tolist()
+    # a rank that lists a key twice as held is one holder: no other case repeats a key within a list
+    for c in cases.values():
+        repeats = [len(x) - len({tuple(k) for k in x.tolist()}) for x in c.dirty + c.held]
+        assert sum(repeats) == len(c.held_twice) and (c.name == "w3 held twice") == bool(c.held_twice), c.name
+    c = cases["w3 held twice"]
+    assert sorted(map(tuple, c.held[1].tolist())) == [(6, 1, 0), (6, 1, 0), (6, 1, 1), (6, 1, 1)] and c.held[2].tolist().count([6, 1, 1]) == 1
+    assert not len(c.held[0]) and sorted(map(tuple, c.dirty[0].tolist())) == [(6, 1, 0), (6, 1, 1)]
+    assert [rows(ER.plan_held(c.dirty, c.held, 3, r)) for r in range(3)] == [[(6, 1, 1, 2)], [(6, 1, 1, 1)], [(6, 1, 1, 2)]]
     # a key held by all ranks and dirty on all, its run of 2 * world entries across sorted entries 255 | 256
     for name in ("w8 straddle total 257", "w64 straddle"):
         c = cases[name]
