@@ -211,6 +211,12 @@ __device__ __forceinline__ void hv_wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
+// how many lanes of ballot mask m lie below the calling lane: its place among the lanes that answered true
+__device__ __forceinline__ int hv_wave_rank(unsigned long long m) {
+    const int lane = hv_lane_id();
+    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    return (int)__popcll(m & lt);
+}
 // Wave-aggregated append: every lane with `pred` gets a distinct index from *counter; one atomic
 // per wave (ballot + popcount prefix).
 __device__ inline int32_t hv_wave_append(int32_t *counter, bool pred) {
@@ -221,9 +227,40 @@ __device__ inline int32_t hv_wave_append(int32_t *counter, bool pred) {
     int32_t base = 0;
     if (lane == leader) base = atomicAdd(counter, (int32_t)__popcll(m));
     base = __shfl(base, leader);
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
-    return pred ? base + (int32_t)__popcll(m & lt) : -1;
+    return pred ? base + (int32_t)hv_wave_rank(m) : -1;
 }
+// hv_wave_append with a window in front: a wave that appends many times to ONE list keeps what it finds in CAP entries of LDS (`buf`:
+// this wave's own) and takes its places in the list with one returning atomic per flush - per CAP - 64 .. CAP entries instead of one
+// per push (a scan of a 2 mm map makes 120 k pushes; queued behind a single counter, ~10 ns each, they were most of such a kernel).
+// push() and flush() are called by all 64 lanes together; emit(at, value) places one entry, called for every place below `cap` (the
+// counter still counts all of them: the caller learns how many there were).  The list's order is the atomics' order: not fixed.
+template <typename T, int CAP>
+struct HvWaveWindow {
+    static_assert(CAP > HV_WAVE, "a push needs room for one entry per lane");
+    T *buf;
+    int32_t *counter;
+    int n; // entries waiting (wave-uniform)
+    template <typename Emit>
+    __device__ __forceinline__ void flush(int64_t cap, Emit emit) {
+        if (n == 0) return;
+        hv_wave_lds_sync();
+        int32_t base = 0;
+        if (hv_lane_id() == 0) base = atomicAdd(counter, n);
+        base = __shfl(base, 0);
+        for (int i = hv_lane_id(); i < n; i += HV_WAVE)
+            if ((int64_t)base + i < cap) emit((int64_t)base + i, buf[i]);
+        hv_wave_lds_sync();
+        n = 0;
+    }
+    template <typename Emit>
+    __device__ __forceinline__ void push(bool pred, T value, int64_t cap, Emit emit) {
+        const unsigned long long m = __ballot(pred);
+        if (m == 0ull) return;
+        if (pred) buf[n + hv_wave_rank(m)] = value;
+        n += (int)__popcll(m);
+        if (n > CAP - HV_WAVE) flush(cap, emit);
+    }
+};
 
 // Wave reductions (xor butterfly: every lane ends with the result); T = int32_t, uint32_t, uint64_t, float or double.
 template <typename T>

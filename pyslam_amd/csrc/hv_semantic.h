@@ -13,6 +13,7 @@
 #include <cstdint>
 
 #include "hv_common.h"
+#include "hv_query.h"
 
 // ---- voting payload: 64 B, ids stored +1 so the zeroed pool means object -1 / class -1 ------------
 struct __attribute__((aligned(16))) HvSemVoxel {
@@ -139,6 +140,12 @@ struct HvProbPair {
     int32_t obj, cls;
     float logp;
 };
+// the order update_cache() picks by (voxel_data_semantic.h:575-601): the larger log-probability, the smaller key among equals
+__host__ __device__ inline bool prob_better(const HvProbPair &p, const HvProbPair &than) {
+    return p.logp > than.logp || (p.logp == than.logp && prob_key(p.obj, p.cls) < prob_key(than.obj, than.cls));
+}
+// false for NaN and +-inf
+__host__ __device__ inline bool hv_finite(float x) { return x - x == 0.0f; }
 __host__ __device__ inline const HvProbNode *prob_node_of(const HvProbVoxel *v, const HvProbNode *nodes, int &i) {
     i -= HV_PROB_K;
     uint32_t n = v->next;
@@ -171,7 +178,7 @@ __host__ __device__ inline int prob_argmax(const HvProbVoxel *v, const HvProbNod
     HvProbPair bp{0, 0, 0.f};
     for (int i = 0; i < nlab; ++i) {
         const HvProbPair p = prob_get<CHAIN>(v, nodes, i);
-        if (best < 0 || p.logp > bp.logp || (p.logp == bp.logp && prob_key(p.obj, p.cls) < prob_key(bp.obj, bp.cls))) {
+        if (best < 0 || prob_better(p, bp)) {
             best = i;
             bp = p;
         }
@@ -199,28 +206,35 @@ __host__ __device__ inline float prob_log_add_exp(float a, float b) {
     const float m = (a < b) ? b : a;
     return m + hv_logf_cr(hv_expf_cr(a - m) + hv_expf_cr(b - m));
 }
-// get_log_normalization(), voxel_data_semantic.h:620-637: incremental log-add-exp in map (key) order
-__host__ __device__ inline float prob_log_normalization(const HvProbVoxel *v, const HvProbNode *nodes, int nlab) {
-    float acc = -INFINITY;
+// f(log-probability) for the entries of a label list in ascending key order - the order in which the reference walks its std::map
+// and therefore adds floats; which >= 0: only the entries of that "*2" map (cls == which: ascending id).  The list is in insertion order
+// and short: every step scans it for the smallest key beyond the last one.
+template <typename F>
+__host__ __device__ inline void prob_in_key_order(const HvProbVoxel *v, const HvProbNode *nodes, int n, int which, F f) {
     int64_t last = 0;
-    for (int step = 0; step < nlab; ++step) {
-        int pick = -1;
+    for (int step = 0; step < n; ++step) {
+        bool found = false;
         int64_t pk = 0;
         float plp = 0.f;
-        for (int i = 0; i < nlab; ++i) {
+        for (int i = 0; i < n; ++i) {
             const HvProbPair p = prob_get(v, nodes, i);
             const int64_t k = prob_key(p.obj, p.cls);
-            if (step > 0 && k <= last) continue;
-            if (pick < 0 || k < pk) {
-                pick = i;
+            if ((which >= 0 && p.cls != which) || (step > 0 && k <= last)) continue;
+            if (!found || k < pk) {
+                found = true;
                 pk = k;
                 plp = p.logp;
             }
         }
-        if (pick < 0) break;
-        acc = prob_log_add_exp(acc, plp);
+        if (!found) break;
+        f(plp);
         last = pk;
     }
+}
+// get_log_normalization(), voxel_data_semantic.h:620-637: incremental log-add-exp in map (key) order
+__host__ __device__ inline float prob_log_normalization(const HvProbVoxel *v, const HvProbNode *nodes, int nlab) {
+    float acc = -INFINITY;
+    prob_in_key_order(v, nodes, nlab, -1, [&](float lp) { acc = prob_log_add_exp(acc, lp); });
     return acc;
 }
 // compute_confidence(), voxel_data_semantic.h:562-572 (the cached confidence_ is refreshed on every update)
@@ -237,16 +251,12 @@ __host__ __device__ inline float sem_confidence(const HvProbVoxel *v, const void
 // without evaluating the confidence where its sign is known: the confidence of a map whose log-probabilities are all finite is
 // exp(best - log sum exp) in (0, 1] (or 0 for an empty / unlabelled best pair), so only a map holding a NaN or an infinity (a NaN
 // depth handed to the integrate) takes the exp / log chain; the answer is the reference's in every case.
-__host__ __device__ inline bool sem_confidence_not_negative(const HvSemVoxel *v, const void * = nullptr) { return sem_confidence(v) >= 0.0f; }
-__host__ __device__ inline bool sem_confidence_not_negative(const HvProbVoxel *v, const void *nodes_) {
-    const HvProbNode *nodes = (const HvProbNode *)nodes_;
-    const int nlab = prob_nlab(v->meta);
+// (sem_confidence_not_negative itself: below the last payload, one for the four)
+__host__ __device__ inline bool prob_all_finite(const HvProbVoxel *v, const HvProbNode *nodes) {
+    const int n = prob_nlab(v->meta);
     bool finite = true;
-    for (int i = 0; i < nlab; ++i) {
-        const float lp = prob_get(v, nodes, i).logp;
-        finite = finite && (lp - lp == 0.0f); // false for NaN and +-inf
-    }
-    return finite ? true : sem_confidence(v, nodes_) >= 0.0f;
+    for (int i = 0; i < n; ++i) finite = finite && hv_finite(prob_get(v, nodes, i).logp);
+    return finite;
 }
 // get_confidence_counter(), voxel_data_semantic.h:505-511
 __host__ __device__ inline int32_t sem_confidence_counter(const HvProbVoxel *v, const void *nodes) {
@@ -266,6 +276,20 @@ __host__ __device__ inline void sem_set_object_id(HvProbVoxel *v, const HvTable 
     }
 }
 
+// log evidence of one observation: update_semantics / update_semantics_with_depth,
+// voxel_data_semantic.h:419-447
+__host__ __device__ inline float prob_observation_log_prob(bool has_depth, float depth, const HvSemParams &G) {
+    if (!has_depth || depth <= G.depth_threshold) return HV_BASE_LOG_PROB;
+    const float confidence = hv_expf_cr(-(depth - G.depth_threshold) * G.depth_decay_rate);
+    return confidence * HV_BASE_LOG_PROB;
+}
+// the "*2" probabilistic payload: update_semantics (confidence 1: log 1 = 0) / update_semantics_with_depth, voxel_data_semantic2.h:371-388
+// (no BASE_LOG_PROB_PER_OBSERVATION there)
+__host__ __device__ inline float prob2_observation_log_prob(bool has_depth, float depth, const HvSemParams &G) {
+    if (!has_depth) return hv_logf_cr(1.0f);
+    return depth <= G.depth_threshold ? 0.0f : -(depth - G.depth_threshold) * G.depth_decay_rate;
+}
+
 #ifdef __HIPCC__
 // The fold keeps the voxel it works on as a LOCAL copy (sem_fold_run: read once, folded, written once).  An inline slot reached with
 // a run-time index (`v->logp[i]`) forces that copy into scratch memory - the probabilistic fold kernels carried 144 bytes of it per
@@ -274,7 +298,7 @@ __host__ __device__ inline void sem_set_object_id(HvProbVoxel *v, const HvTable 
 // node pool (global memory) either way.  Only the fold uses them: on a voxel in GLOBAL memory one indexed load beats six.
 // (all six slots are read, unconditionally, and the VALUES are selected: loads in the arms of a branch are merged by the optimiser
 // into one load through a selected address)
-__device__ __forceinline__ HvProbPair prob_slot_get(const HvProbVoxel *v, int i) {
+__host__ __device__ __forceinline__ HvProbPair prob_slot_get(const HvProbVoxel *v, int i) {
     HvProbPair p{v->obj[0], v->cls[0], v->logp[0]};
 #pragma unroll
     for (int k = 1; k < HV_PROB_K; ++k) {
@@ -288,7 +312,7 @@ __device__ __forceinline__ HvProbPair prob_slot_get(const HvProbVoxel *v, int i)
 }
 // (every slot is stored, with its old or its new value: a conditional store per slot is merged by the optimiser into ONE store through
 // a pointer picked from the six slots - a run-time address again)
-__device__ __forceinline__ void prob_slot_set(HvProbVoxel *v, int i, int32_t obj, int32_t cls, float lp) {
+__host__ __device__ __forceinline__ void prob_slot_set(HvProbVoxel *v, int i, int32_t obj, int32_t cls, float lp) {
 #pragma unroll
     for (int k = 0; k < HV_PROB_K; ++k) {
         v->obj[k] = i == k ? obj : v->obj[k];
@@ -296,12 +320,19 @@ __device__ __forceinline__ void prob_slot_set(HvProbVoxel *v, int i, int32_t obj
         v->logp[k] = i == k ? lp : v->logp[k];
     }
 }
-__device__ __forceinline__ void prob_slot_set_logp(HvProbVoxel *v, int i, float lp) {
+__host__ __device__ __forceinline__ void prob_slot_set_logp(HvProbVoxel *v, int i, float lp) {
 #pragma unroll
     for (int k = 0; k < HV_PROB_K; ++k) v->logp[k] = i == k ? lp : v->logp[k];
 }
+// hv_finite over the first n inline slots of a copy
+__host__ __device__ __forceinline__ bool prob_slots_finite(const HvProbVoxel &r, int n) {
+    bool finite = true;
+#pragma unroll
+    for (int k = 0; k < HV_PROB_K; ++k) finite = finite && (k >= n || hv_finite(r.logp[k]));
+    return finite;
+}
 template <bool CHAIN>
-__device__ __forceinline__ HvProbPair prob_get_r(const HvProbVoxel *v, const HvProbNode *nodes, int i) {
+__host__ __device__ __forceinline__ HvProbPair prob_get_r(const HvProbVoxel *v, const HvProbNode *nodes, int i) {
     HvProbPair p = prob_slot_get(v, i); // (for i >= HV_PROB_K: slot 0, replaced below)
     if (CHAIN && i >= HV_PROB_K) {
         const HvProbNode *nd = prob_node_of(v, nodes, i);
@@ -310,7 +341,7 @@ __device__ __forceinline__ HvProbPair prob_get_r(const HvProbVoxel *v, const HvP
     return p;
 }
 template <bool CHAIN>
-__device__ __forceinline__ void prob_set_logp_r(HvProbVoxel *v, HvProbNode *nodes, int i, float lp) {
+__host__ __device__ __forceinline__ void prob_set_logp_r(HvProbVoxel *v, HvProbNode *nodes, int i, float lp) {
     if (!CHAIN || i < HV_PROB_K) {
         prob_slot_set_logp(v, i, lp);
         return;
@@ -320,11 +351,11 @@ __device__ __forceinline__ void prob_set_logp_r(HvProbVoxel *v, HvProbNode *node
 }
 // prob_argmax for the local copy: the same scan in slot order (inline slots first, then the chain)
 template <bool CHAIN>
-__device__ __forceinline__ int prob_argmax_r(const HvProbVoxel *v, const HvProbNode *nodes, int nlab) {
+__host__ __device__ __forceinline__ int prob_argmax_r(const HvProbVoxel *v, const HvProbNode *nodes, int nlab) {
     int best = -1;
     HvProbPair bp{0, 0, 0.f};
     auto take = [&](int i, const HvProbPair p) {
-        if (best < 0 || p.logp > bp.logp || (p.logp == bp.logp && prob_key(p.obj, p.cls) < prob_key(bp.obj, bp.cls))) {
+        if (best < 0 || prob_better(p, bp)) {
             best = i;
             bp = p;
         }
@@ -342,62 +373,98 @@ __device__ __forceinline__ int prob_argmax_r(const HvProbVoxel *v, const HvProbN
         }
     return best;
 }
-// One semantic observation folded into a probabilistic voxel: initialize_semantics_log_prob
-// (count == 0, voxel_data_semantic.h:311-324) or update_semantics_log_prob (:358-417).  Returns false when the pair is new and
-// cannot be stored (254 pairs, or the node pool is exhausted): the observation is dropped and counted.
+// The node pool of a volume.  It comes as three scalars, not as `const HvTable &`: where one of the functions below is not inlined, the
+// address of the kernel's by-value table would escape into the call and the whole struct would be spilled to scratch memory at the
+// kernel's entry.
+struct HvNodePool {
+    HvProbNode *nodes;
+    int32_t *counters;
+    int32_t cap;
+};
+__host__ __device__ __forceinline__ HvNodePool hv_node_pool(const HvTable &table) { return {(HvProbNode *)table.prob_nodes, table.counters, table.prob_node_cap}; }
+// One node out of the pool, its `next` cleared: its index, or -1 when there is no pool or none is left (the counter stays the number of
+// nodes handed out: ADVICE r04).  The label list's only atomic; compiled for the host (tools/host_check) it is a plain increment.
+__host__ __device__ inline int32_t prob_node_grab(HvNodePool pool) {
+    if (pool.nodes == nullptr) return -1;
+#ifdef __HIP_DEVICE_COMPILE__
+    const int32_t id = atomicAdd(&pool.counters[HV_CNT_PROB_NODES], 1);
+    if (id >= pool.cap) {
+        atomicSub(&pool.counters[HV_CNT_PROB_NODES], 1);
+        return -1;
+    }
+#else
+    const int32_t id = pool.counters[HV_CNT_PROB_NODES];
+    if (id >= pool.cap) return -1;
+    pool.counters[HV_CNT_PROB_NODES] = id + 1;
+#endif
+    pool.nodes[id].next = 0u;
+    return id;
+}
+// entry `n` (the next free index) of a label list gets (obj, cls, lp): inline, or in the chain's node (n - K) / NK, which may have to be
+// linked in first (a chain left behind by a reset or collapsed map is taken up again).  false: 254 entries, or the node pool is exhausted.
+// The only code that links a node.
 template <bool CHAIN>
-__device__ inline bool prob_fold_t(HvProbVoxel *v, const HvTable &table, bool first, int32_t obj, int32_t cls, float lp) {
-    HvProbNode *nodes = (HvProbNode *)table.prob_nodes;
-    int nlab = prob_nlab(v->meta), best = prob_best(v->meta);
+__host__ __device__ inline bool prob_append_t(HvProbVoxel *v, HvNodePool pool, int n, int32_t obj, int32_t cls, float lp) {
+    HvProbNode *nodes = pool.nodes;
+    if (n >= HV_PROB_MAX) return false;
+    if (!CHAIN || n < HV_PROB_K) {
+        prob_slot_set(v, n, obj, cls, lp);
+        return true;
+    }
+    if ((n - HV_PROB_K) % HV_PROB_NK == 0) {
+        // the link the new node hangs on: the voxel's own `next`, or the last node's (no pointer into the local voxel is formed:
+        // one that may point there or into the node pool would pin the copy in memory)
+        const int hops = (n - HV_PROB_K) / HV_PROB_NK;
+        HvProbNode *tail = nullptr;
+        if (hops > 0) {
+            uint32_t k = v->next;
+            for (int hop = hops - 1; hop > 0; --hop) k = nodes[k - 1].next;
+            tail = &nodes[k - 1];
+        }
+        const uint32_t own_next = v->next;
+        if ((tail ? tail->next : own_next) == 0u) {
+            const int32_t id = prob_node_grab(pool);
+            if (id < 0) return false;
+            if (tail) tail->next = (uint32_t)id + 1u;
+            v->next = tail ? own_next : (uint32_t)id + 1u;
+        }
+    }
+    int j = n;
+    HvProbNode *nd = (HvProbNode *)prob_node_of(v, nodes, j);
+    nd->obj[j] = obj;
+    nd->cls[j] = cls;
+    nd->logp[j] = lp;
+    return true;
+}
+// entry (obj, cls) of the list - for the "*2" payloads (id, which map) -, -1 if there is none
+template <bool CHAIN>
+__host__ __device__ __forceinline__ int prob_find(const HvProbVoxel *v, const HvProbNode *nodes, int n, int32_t obj, int32_t cls) {
     int idx = -1;
 #pragma unroll
     for (int i = 0; i < HV_PROB_K; ++i) {
-        const bool hit = (int)(v->obj[i] == obj) & (int)(v->cls[i] == cls) & (int)(i < nlab);
+        const bool hit = (int)(v->obj[i] == obj) & (int)(v->cls[i] == cls) & (int)(i < n);
         idx = hit ? i : idx;
     }
     if (CHAIN)
-        for (int i = HV_PROB_K; i < nlab; ++i) {
+        for (int i = HV_PROB_K; i < n; ++i) {
             int j = i;
             const HvProbNode *nd = prob_node_of(v, nodes, j);
             if (nd->obj[j] == obj && nd->cls[j] == cls) idx = i;
         }
+    return idx;
+}
+// One semantic observation folded into a probabilistic voxel: initialize_semantics_log_prob
+// (count == 0, voxel_data_semantic.h:311-324) or update_semantics_log_prob (:358-417).  Returns false when the pair is new and
+// cannot be stored (254 pairs, or the node pool is exhausted): the observation is dropped and counted.
+template <bool CHAIN>
+__host__ __device__ inline bool prob_fold_t(HvProbVoxel *v, HvNodePool pool, bool first, int32_t obj, int32_t cls, float lp) {
+    HvProbNode *nodes = pool.nodes;
+    int nlab = prob_nlab(v->meta), best = prob_best(v->meta);
     float best_lp = best >= 0 ? prob_get_r<CHAIN>(v, nodes, best).logp : 0.f;
+    int idx = prob_find<CHAIN>(v, nodes, nlab, obj, cls);
     if (idx < 0) {
-        // a new pair goes to index nlab: inline, or in the chain's node (nlab - K) / NK, which may have to be linked in first
-        if (nlab >= HV_PROB_MAX) return false;
-        if (CHAIN && nlab >= HV_PROB_K && (nlab - HV_PROB_K) % HV_PROB_NK == 0) {
-            // the link the new node hangs on: the voxel's own `next`, or the last node's (no pointer into the local voxel is formed:
-            // one that may point there or into the node pool would pin the copy in memory)
-            const int hops = (nlab - HV_PROB_K) / HV_PROB_NK;
-            HvProbNode *tail = nullptr;
-            if (hops > 0) {
-                uint32_t n = v->next;
-                for (int hop = hops - 1; hop > 0; --hop) n = nodes[n - 1].next;
-                tail = &nodes[n - 1];
-            }
-            const uint32_t own_next = v->next;
-            if ((tail ? tail->next : own_next) == 0u) { // (a chain left behind by a collapsed map is taken up again)
-                if (nodes == nullptr) return false;
-                const int32_t id = atomicAdd(&table.counters[HV_CNT_PROB_NODES], 1);
-                if (id >= table.prob_node_cap) {
-                    atomicSub(&table.counters[HV_CNT_PROB_NODES], 1); // (the counter stays the number of nodes handed out)
-                    return false;
-                }
-                nodes[id].next = 0u;
-                if (tail) tail->next = (uint32_t)id + 1u;
-                v->next = tail ? own_next : (uint32_t)id + 1u;
-            }
-        }
+        if (!prob_append_t<CHAIN>(v, pool, nlab, obj, cls, lp)) return false;
         idx = nlab++;
-        if (!CHAIN || idx < HV_PROB_K) {
-            prob_slot_set(v, idx, obj, cls, lp);
-        } else {
-            int j = idx;
-            HvProbNode *nd = (HvProbNode *)prob_node_of(v, nodes, j);
-            nd->obj[j] = obj;
-            nd->cls[j] = cls;
-            nd->logp[j] = lp;
-        }
         if (first) {
             best = idx;
         } else if (best >= 0) {
@@ -426,8 +493,31 @@ __device__ inline bool prob_fold_t(HvProbVoxel *v, const HvTable &table, bool fi
     return true;
 }
 // (a map that stays inside the inline slots after this observation takes the version without the node walk)
-__device__ inline bool prob_fold(HvProbVoxel *v, const HvTable &table, bool first, int32_t obj, int32_t cls, float lp) {
-    return prob_nlab(v->meta) < HV_PROB_K ? prob_fold_t<false>(v, table, first, obj, cls, lp) : prob_fold_t<true>(v, table, first, obj, cls, lp);
+__host__ __device__ inline bool prob_fold(HvProbVoxel *v, HvNodePool pool, bool first, int32_t obj, int32_t cls, float lp) {
+    return prob_nlab(v->meta) < HV_PROB_K ? prob_fold_t<false>(v, pool, first, obj, cls, lp) : prob_fold_t<true>(v, pool, first, obj, cls, lp);
+}
+// sem_observe: one labelled observation of a voxel (first: the voxel had no point yet), one overload per payload - update_voxel_direct's
+// initialize_semantics[_with_depth] / update_semantics[_with_depth].  Returns the number of observations it could not store.
+__host__ __device__ inline int sem_observe(HvProbVoxel *v, HvNodePool pool, bool first, int32_t obj, int32_t cls, bool with_depth, float depth,
+                                           const HvSemParams &G) {
+    return prob_fold(v, pool, first, obj, cls, prob_observation_log_prob(with_depth, depth, G)) ? 0 : 1;
+}
+// voting, voxel_data_semantic.h:137-198 (*_with_depth: depth >= kDepthThreshold leaves the label state alone)
+__host__ __device__ inline int sem_observe(HvSemVoxel *v, HvNodePool, bool first, int32_t obj, int32_t cls, bool with_depth, float depth,
+                                           const HvSemParams &G) {
+    if (with_depth && !(depth < G.depth_threshold)) return 0;
+    if (first) { // initialize_semantics
+        v->obj1 = obj + 1;
+        v->cls1 = cls + 1;
+        v->counter = 1;
+    } else if (v->obj1 == obj + 1 && v->cls1 == cls + 1) { // update_semantics
+        v->counter++;
+    } else if (--v->counter <= 0) {
+        v->obj1 = obj + 1;
+        v->cls1 = cls + 1;
+        v->counter = 1;
+    }
+    return 0;
 }
 #endif
 
@@ -468,21 +558,21 @@ __host__ __device__ inline float sem_confidence(const HvSem2Voxel *v, const void
     const float o = sem2_ratio(v->obj_counter, v->count), c = sem2_ratio(v->cls_counter, v->count);
     return c < o ? c : o;
 }
-__host__ __device__ inline bool sem_confidence_not_negative(const HvSem2Voxel *v, const void * = nullptr) { return sem_confidence(v) >= 0.0f; }
 // get_confidence_counter(): std::min of the two counters, :55-57
 __host__ __device__ inline int32_t sem_confidence_counter(const HvSem2Voxel *v, const void * = nullptr) {
     return v->cls_counter < v->obj_counter ? v->cls_counter : v->obj_counter;
 }
 __host__ __device__ inline void sem_set_object_id(HvSem2Voxel *v, const HvTable &, int32_t id) { v->obj1 = id + 1; }
-// one labelled observation: initialize_semantics[_with_depth] (count == 0) / update_semantics[_with_depth], :120-195
-__host__ __device__ inline void sem2_fold(HvSem2Voxel *v, bool first, bool gate, int32_t obj, int32_t cls) {
-    if (!gate) return; // (*_with_depth: depth >= kDepthThreshold leaves the label state alone)
+// initialize_semantics[_with_depth] (first) / update_semantics[_with_depth], :120-195: object id and class id vote on their own
+__host__ __device__ inline int sem_observe(HvSem2Voxel *v, HvNodePool, bool first, int32_t obj, int32_t cls, bool with_depth, float depth,
+                                           const HvSemParams &G) {
+    if (with_depth && !(depth < G.depth_threshold)) return 0; // (leaves the label state alone)
     if (first) {
         v->obj1 = obj + 1;
         v->cls1 = cls + 1;
         v->obj_counter = 1;
         v->cls_counter = 1;
-        return;
+        return 0;
     }
     if (v->obj1 == obj + 1) {
         v->obj_counter++;
@@ -496,6 +586,7 @@ __host__ __device__ inline void sem2_fold(HvSem2Voxel *v, bool first, bool gate,
         v->cls1 = cls + 1;
         v->cls_counter = 1;
     }
+    return 0;
 }
 
 // ---- VoxelSemanticDataProbabilistic2 (voxel_data_semantic2.h:256-787): two std::map<int, float> per voxel, object id -> log-probability
@@ -510,6 +601,12 @@ __host__ __device__ inline void sem2_fold(HvSem2Voxel *v, bool first, bool gate,
 //   for, never stored.
 struct __attribute__((aligned(16))) HvProb2Voxel : HvProbVoxel {};
 static_assert(sizeof(HvProb2Voxel) == 128, "HvProb2Voxel must be 128 bytes");
+// which payload a voxel type is (the kernels are templates over the four; `maps`: the record is HvProbVoxel's, with an overflow chain)
+template <typename VOX> struct HvPay;
+template <> struct HvPay<HvSemVoxel> { static constexpr int kind = 0; static constexpr bool maps = false; };
+template <> struct HvPay<HvProbVoxel> { static constexpr int kind = 1; static constexpr bool maps = true; };
+template <> struct HvPay<HvSem2Voxel> { static constexpr int kind = 2; static constexpr bool maps = false; };
+template <> struct HvPay<HvProb2Voxel> { static constexpr int kind = 3; static constexpr bool maps = true; };
 __host__ __device__ inline int prob2_best_obj(uint32_t meta) { return (int)((meta >> 8) & 0xffu) - 1; }
 __host__ __device__ inline int prob2_best_cls(uint32_t meta) { return (int)((meta >> 16) & 0xffu) - 1; }
 __host__ __device__ inline uint32_t prob2_meta(int n, int best_obj, int best_cls) {
@@ -521,7 +618,11 @@ struct HvProb2Best {
     bool any;   // the map has entries at all
 };
 // update_object_cache / update_class_cache, :601-645: the first entry in KEY order whose log-probability is greater than every one before
-// it, starting from -inf (an entry at -inf or NaN never wins) = the largest log-probability, the smallest id among equals
+// it, starting from -inf (an entry at -inf or NaN never wins) = the largest log-probability, the smallest id among equals.  Does entry
+// (id, lp) take the place of the best one so far (`won`: there is one)?
+__host__ __device__ inline bool prob2_better(int32_t id, float lp, int32_t best_id, float best_lp, bool won) {
+    return lp > best_lp || (won && lp == best_lp && id < best_id);
+}
 __host__ __device__ inline HvProb2Best prob2_argmax(const HvProbVoxel *v, const HvProbNode *nodes, int n, int which) {
     HvProb2Best b{-1, -INFINITY, false};
     bool won = false;
@@ -529,12 +630,10 @@ __host__ __device__ inline HvProb2Best prob2_argmax(const HvProbVoxel *v, const 
         const HvProbPair p = prob_get(v, nodes, i);
         if (p.cls != which) continue;
         b.any = true;
-        if (p.logp > b.lp) {
+        if (prob2_better(p.obj, p.logp, b.id, b.lp, won)) {
             b.id = p.obj;
-            b.lp = p.logp;
+            b.lp = p.logp > b.lp ? p.logp : b.lp; // (an equal entry hands over its id only: -0 and +0 are equal)
             won = true;
-        } else if (won && p.logp == b.lp && p.obj < b.id) {
-            b.id = p.obj;
         }
     }
     return b;
@@ -561,24 +660,7 @@ __host__ __device__ inline float prob2_log_normalization(const HvProbVoxel *v, c
     }
     if (m == 0) return 0.0f;
     float sum = 0.0f;
-    int32_t last = 0;
-    for (int step = 0; step < m; ++step) { // entries of this map in ascending id order
-        int pick = -1;
-        int32_t pid = 0;
-        float plp = 0.f;
-        for (int i = 0; i < n; ++i) {
-            const HvProbPair p = prob_get(v, nodes, i);
-            if (p.cls != which || (step > 0 && p.obj <= last)) continue;
-            if (pick < 0 || p.obj < pid) {
-                pick = i;
-                pid = p.obj;
-                plp = p.logp;
-            }
-        }
-        if (pick < 0) break;
-        sum += hv_expf_cr(plp - mx);
-        last = pid;
-    }
+    prob_in_key_order(v, nodes, n, which, [&](float lp) { sum += hv_expf_cr(lp - mx); });
     return mx + hv_logf_cr(sum);
 }
 __host__ __device__ inline int32_t sem_object_id(const HvProb2Voxel *v, const void *nodes) { return prob2_most_likely(v, (const HvProbNode *)nodes, 0).id; }
@@ -608,15 +690,12 @@ __host__ __device__ inline float sem_object_confidence(const HvSemVoxel *, const
 __host__ __device__ inline float sem_class_confidence(const HvSemVoxel *, const void * = nullptr) { return -1.0f; }
 __host__ __device__ inline float sem_object_confidence(const HvProbVoxel *, const void * = nullptr) { return -1.0f; }
 __host__ __device__ inline float sem_class_confidence(const HvProbVoxel *, const void * = nullptr) { return -1.0f; }
-__host__ __device__ inline bool sem_confidence_not_negative(const HvProb2Voxel *v, const void *nodes_) {
-    const HvProbNode *nodes = (const HvProbNode *)nodes_;
-    const int n = prob_nlab(v->meta);
-    bool finite = true;
-    for (int i = 0; i < n; ++i) {
-        const float lp = prob_get(v, nodes, i).logp;
-        finite = finite && (lp - lp == 0.0f);
+template <typename VOX>
+__host__ __device__ inline bool sem_confidence_not_negative(const VOX *v, const void *nodes = nullptr) {
+    if constexpr (HvPay<VOX>::maps) {
+        if (prob_all_finite(v, (const HvProbNode *)nodes)) return true; // (exp(finite), or the 0 of an unlabelled voxel)
     }
-    return finite ? true : sem_confidence(v, nodes_) >= 0.0f; // (all finite: exp(finite) or the 0 of an unlabelled voxel)
+    return sem_confidence(v, nodes) >= 0.0f;
 }
 // get_confidence_counter(), :506-511
 __host__ __device__ inline int32_t sem_confidence_counter(const HvProb2Voxel *v, const void *nodes) {
@@ -624,86 +703,39 @@ __host__ __device__ inline int32_t sem_confidence_counter(const HvProb2Voxel *v,
 }
 
 #ifdef __HIPCC__
-// entry `n` (the next free index) of a label list gets (obj, cls, lp): inline, or in the chain's node (n - K) / NK, which may have to be
-// linked in first (a chain left behind by a reset or collapsed map is taken up again).  false: 254 entries, or the node pool is exhausted.
-// (the node pool comes as three scalars, not as `const HvTable &`: where one of these functions is not inlined, the address of the
-// kernel's by-value table would escape into the call and the whole struct would be spilled to scratch memory at the kernel's entry)
-struct HvNodePool {
-    HvProbNode *nodes;
-    int32_t *counters;
-    int32_t cap;
-};
-__device__ __forceinline__ HvNodePool hv_node_pool(const HvTable &table) { return {(HvProbNode *)table.prob_nodes, table.counters, table.prob_node_cap}; }
-template <bool CHAIN>
-__device__ inline bool prob_append_t(HvProbVoxel *v, HvNodePool pool, int n, int32_t obj, int32_t cls, float lp) {
-    HvProbNode *nodes = pool.nodes;
-    if (n >= HV_PROB_MAX) return false;
-    if (!CHAIN || n < HV_PROB_K) {
-        prob_slot_set(v, n, obj, cls, lp);
-        return true;
-    }
-    if ((n - HV_PROB_K) % HV_PROB_NK == 0) {
-        const int hops = (n - HV_PROB_K) / HV_PROB_NK;
-        HvProbNode *tail = nullptr;
-        if (hops > 0) {
-            uint32_t k = v->next;
-            for (int hop = hops - 1; hop > 0; --hop) k = nodes[k - 1].next;
-            tail = &nodes[k - 1];
-        }
-        const uint32_t own_next = v->next;
-        if ((tail ? tail->next : own_next) == 0u) {
-            if (nodes == nullptr) return false;
-            const int32_t id = atomicAdd(&pool.counters[HV_CNT_PROB_NODES], 1);
-            if (id >= pool.cap) {
-                atomicSub(&pool.counters[HV_CNT_PROB_NODES], 1);
-                return false;
-            }
-            nodes[id].next = 0u;
-            if (tail) tail->next = (uint32_t)id + 1u;
-            v->next = tail ? own_next : (uint32_t)id + 1u;
-        }
-    }
-    int j = n;
-    HvProbNode *nd = (HvProbNode *)prob_node_of(v, nodes, j);
-    nd->obj[j] = obj;
-    nd->cls[j] = cls;
-    nd->logp[j] = lp;
-    return true;
-}
-// entry (id, which) of the list, -1 if there is none
-template <bool CHAIN>
-__device__ __forceinline__ int prob2_find(const HvProbVoxel *v, const HvProbNode *nodes, int n, int32_t id, int32_t which) {
-    int idx = -1;
+// prob2_most_likely(...).id for a copy whose n entries are all inline: cached entry c, else the argmax of map `which` (scalars only:
+// nothing of the copy may be reached through a run-time index)
+__host__ __device__ __forceinline__ int32_t prob2_slots_most_likely(const HvProbVoxel &r, int n, int which, int c) {
+    int32_t id = -1;
+    float lp = -INFINITY;
+    bool won = false;
 #pragma unroll
-    for (int i = 0; i < HV_PROB_K; ++i) {
-        const bool hit = (int)(v->obj[i] == id) & (int)(v->cls[i] == which) & (int)(i < n);
-        idx = hit ? i : idx;
+    for (int k = 0; k < HV_PROB_K; ++k) {
+        const bool mine = k < n && r.cls[k] == which;
+        const bool take = mine && (c >= 0 ? k == c : prob2_better(r.obj[k], r.logp[k], id, lp, won));
+        id = take ? r.obj[k] : id;
+        lp = take ? r.logp[k] : lp;
+        won = won || take;
     }
-    if (CHAIN)
-        for (int i = HV_PROB_K; i < n; ++i) {
-            int j = i;
-            const HvProbNode *nd = prob_node_of(v, nodes, j);
-            if (nd->obj[j] == id && nd->cls[j] == which) idx = i;
-        }
-    return idx;
+    return id;
 }
 // initialize_semantics_log_prob (first: the entries are ASSIGNED half the log-probability and become the cached most likely ones,
 // :311-326) / update_semantics_log_prob (found: += half, new: = half; both caches dropped, :339-369).  Returns the number of entries that
 // could not be stored (0-2).
 template <bool CHAIN>
-__device__ inline int prob2_fold_t(HvProbVoxel *v, HvNodePool table, bool first, int32_t obj, int32_t cls, float lp) {
+__host__ __device__ inline int prob2_fold_t(HvProbVoxel *v, HvNodePool table, bool first, int32_t obj, int32_t cls, float lp) {
     HvProbNode *nodes = table.nodes;
     int n = prob_nlab(v->meta);
     const float half = lp * 0.5f;
     int lost = 0;
-    int io = prob2_find<CHAIN>(v, nodes, n, obj, 0);
+    int io = prob_find<CHAIN>(v, nodes, n, obj, 0);
     if (io < 0) {
         if (prob_append_t<CHAIN>(v, table, n, obj, 0, half)) io = n++;
         else ++lost;
     } else {
         prob_set_logp_r<CHAIN>(v, nodes, io, first ? half : prob_get_r<CHAIN>(v, nodes, io).logp + half);
     }
-    int ic = prob2_find<CHAIN>(v, nodes, n, cls, 1);
+    int ic = prob_find<CHAIN>(v, nodes, n, cls, 1);
     if (ic < 0) {
         if (prob_append_t<CHAIN>(v, table, n, cls, 1, half)) ic = n++;
         else ++lost;
@@ -713,52 +745,34 @@ __device__ inline int prob2_fold_t(HvProbVoxel *v, HvNodePool table, bool first,
     v->meta = first ? prob2_meta(n, io, ic) : prob2_meta(n, -1, -1);
     return lost;
 }
-__device__ __forceinline__ int prob2_fold(HvProbVoxel *v, const HvTable &table, bool first, int32_t obj, int32_t cls, float lp) {
-    const HvNodePool pool = hv_node_pool(table);
+__host__ __device__ __forceinline__ int prob2_fold(HvProbVoxel *v, HvNodePool pool, bool first, int32_t obj, int32_t cls, float lp) {
     return prob_nlab(v->meta) + 2 <= HV_PROB_K ? prob2_fold_t<false>(v, pool, first, obj, cls, lp) : prob2_fold_t<true>(v, pool, first, obj, cls, lp);
 }
 // set_object_id(), :424-452 (merge_segments, the association's deferred assignment): the id's entry takes the log-probability of the
-// current most likely object (0 when there is none) and becomes the cached most likely one; the class cache is recomputed.
-__device__ inline void prob2_set_object_id(HvProb2Voxel *v, HvNodePool table, int32_t id) {
+// current most likely object (0 when there is none) and becomes the cached most likely one; the class cache is recomputed.  false: the
+// entry is new and could not be stored.
+__host__ __device__ inline bool prob2_set_object_id(HvProb2Voxel *v, HvNodePool table, int32_t id) {
     HvProbNode *nodes = table.nodes;
     int n = prob_nlab(v->meta);
     const HvProb2Best b = prob2_most_likely(v, nodes, 0);
     const float target = (b.any && b.id != -1 && b.lp != -INFINITY) ? b.lp : 0.0f;
-    int io = prob2_find<true>(v, nodes, n, id, 0);
+    int io = prob_find<true>(v, nodes, n, id, 0);
     if (io < 0) {
-        if (prob_append_t<true>(v, table, n, id, 0, target)) {
-            io = n++;
-        } else {
-            atomicAdd(&table.counters[HV_CNT_LABEL_OVERFLOW], 1);
-        }
+        if (prob_append_t<true>(v, table, n, id, 0, target)) io = n++;
     } else {
         prob_set_logp<true>(v, nodes, io, target);
     }
     v->meta = prob2_meta(n, io, -1);
+    return io >= 0;
 }
-__device__ __forceinline__ void sem_set_object_id(HvProb2Voxel *v, const HvTable &table, int32_t id) { prob2_set_object_id(v, hv_node_pool(table), id); }
+__device__ __forceinline__ void sem_set_object_id(HvProb2Voxel *v, const HvTable &table, int32_t id) {
+    if (!prob2_set_object_id(v, hv_node_pool(table), id)) atomicAdd(&table.counters[HV_CNT_LABEL_OVERFLOW], 1);
+}
+__host__ __device__ inline int sem_observe(HvProb2Voxel *v, HvNodePool pool, bool first, int32_t obj, int32_t cls, bool with_depth, float depth,
+                                           const HvSemParams &G) {
+    return prob2_fold(v, pool, first, obj, cls, prob2_observation_log_prob(with_depth, depth, G));
+}
 #endif
-
-// log evidence of one observation: update_semantics / update_semantics_with_depth,
-// voxel_data_semantic.h:419-447
-__host__ __device__ inline float prob_observation_log_prob(bool has_depth, float depth, const HvSemParams &G) {
-    if (!has_depth || depth <= G.depth_threshold) return HV_BASE_LOG_PROB;
-    const float confidence = hv_expf_cr(-(depth - G.depth_threshold) * G.depth_decay_rate);
-    return confidence * HV_BASE_LOG_PROB;
-}
-// the "*2" probabilistic payload: update_semantics (confidence 1: log 1 = 0) / update_semantics_with_depth, voxel_data_semantic2.h:371-388
-// (no BASE_LOG_PROB_PER_OBSERVATION there)
-__host__ __device__ inline float prob2_observation_log_prob(bool has_depth, float depth, const HvSemParams &G) {
-    if (!has_depth) return hv_logf_cr(1.0f);
-    return depth <= G.depth_threshold ? 0.0f : -(depth - G.depth_threshold) * G.depth_decay_rate;
-}
-
-// which payload a voxel type is (the kernels are templates over the four; `maps`: the record is HvProbVoxel's, with an overflow chain)
-template <typename VOX> struct HvPay;
-template <> struct HvPay<HvSemVoxel> { static constexpr int kind = 0; static constexpr bool maps = false; };
-template <> struct HvPay<HvProbVoxel> { static constexpr int kind = 1; static constexpr bool maps = true; };
-template <> struct HvPay<HvSem2Voxel> { static constexpr int kind = 2; static constexpr bool maps = false; };
-template <> struct HvPay<HvProb2Voxel> { static constexpr int kind = 3; static constexpr bool maps = true; };
 
 // The occupancy bit of voxel `gid` (pool order): false = the voxel never took a point, its record need not be read.  The lanes
 // of a wave ask for 64 consecutive voxels: one 8-byte word.
@@ -767,6 +781,43 @@ __device__ __forceinline__ bool sem_maybe_occupied(const unsigned long long *__r
 }
 
 #ifdef __HIPCC__
+// The key box of a query (Q.kind != 0; the carve and the vote: the frustum's): block key in bmin..bmax ...
+__device__ __forceinline__ bool sem_block_in_query_box(const HvQuery &Q, const int32_t bk[3]) {
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) in = in && bk[a] >= Q.bmin[a] && bk[a] <= Q.bmax[a];
+    return in;
+}
+// ... and the key of voxel l of that block in vmin..vmax
+__device__ __forceinline__ bool sem_in_query_box(const HvQuery &Q, const HvSemParams &G, const int32_t bk[3], int l) {
+    if (!sem_block_in_query_box(Q, bk)) return false;
+    const int32_t lc[3] = {l % G.bs, (l / G.bs) % G.bs, l / (G.bs * G.bs)};
+    bool in = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const int32_t vk = bk[a] * G.bs + lc[a];
+        in = in && vk >= Q.vmin[a] && vk <= Q.vmax[a];
+    }
+    return in;
+}
+// One output row of get_voxels / get_object_segments: averaged position and colour, class, object, confidence
+template <typename VOX>
+__device__ __forceinline__ void sem_write_row(const VOX *v, const void *nodes, int32_t obj, int64_t at, double *__restrict__ out_pts,
+                                              float *__restrict__ out_cols, int32_t *__restrict__ out_cls, int32_t *__restrict__ out_obj,
+                                              float *__restrict__ out_conf) {
+    const int32_t count = v->count;
+    const double c = (double)count;
+    const float cf = (float)count;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        out_pts[at * 3 + k] = v->pos[k] / c;
+        out_cols[at * 3 + k] = v->col[k] / cf;
+    }
+    out_cls[at] = sem_class_id(v, nodes);
+    out_obj[at] = obj;
+    out_conf[at] = sem_confidence(v, nodes);
+}
+
 // r-th (0-based) set bit of a 64-bit word that has more than r bits set
 __device__ __forceinline__ int sem_select_bit(unsigned long long w, int r) {
     int pos = 0;

@@ -165,6 +165,7 @@ __device__ __forceinline__ void sem_fold_run(const HvTable &table, VOX *__restri
     int32_t count = acc.count;
     if (count == 0) atomicOr(&occ[vid >> 6], 1ull << (vid & 63)); // first point of this voxel (or the first after a reset)
     int overflowed = 0;
+    const HvNodePool nodes = hv_node_pool(table);
     const bool labels = src.has_labels(), with_depth = src.has_depth();
     for (int j = 0;; ++j) {
         const int64_t p = next(j);
@@ -178,38 +179,7 @@ __device__ __forceinline__ void sem_fold_run(const HvTable &table, VOX *__restri
             acc.col[1] += q.c1;
             acc.col[2] += q.c2;
         }
-        if (labels) {
-            const int32_t obj = q.obj, cls = q.cls;
-            if constexpr (HvPay<VOX>::kind == 0) {
-                HvSemVoxel *sv = (HvSemVoxel *)&acc;
-                const bool gate = with_depth ? (q.depth < G.depth_threshold) : true; // *_with_depth, voxel_data_semantic.h:168-198
-                if (count == 0) {
-                    if (gate) { // initialize_semantics
-                        sv->obj1 = obj + 1;
-                        sv->cls1 = cls + 1;
-                        sv->counter = 1;
-                    }
-                } else if (gate) { // update_semantics
-                    if (sv->obj1 == obj + 1 && sv->cls1 == cls + 1) {
-                        sv->counter++;
-                    } else {
-                        sv->counter--;
-                        if (sv->counter <= 0) {
-                            sv->obj1 = obj + 1;
-                            sv->cls1 = cls + 1;
-                            sv->counter = 1;
-                        }
-                    }
-                }
-            } else if constexpr (HvPay<VOX>::kind == 2) {
-                sem2_fold(&acc, count == 0, with_depth ? (q.depth < G.depth_threshold) : true, obj, cls);
-            } else if constexpr (HvPay<VOX>::kind == 3) {
-                overflowed += prob2_fold(&acc, table, count == 0, obj, cls, prob2_observation_log_prob(with_depth, q.depth, G));
-            } else {
-                const float lp = prob_observation_log_prob(with_depth, q.depth, G);
-                if (!prob_fold(&acc, table, count == 0, obj, cls, lp)) ++overflowed;
-            }
-        }
+        if (labels) overflowed += sem_observe(&acc, nodes, count == 0, q.obj, q.cls, with_depth, q.depth, G);
         count = count == 0 ? 1 : count + 1;
     }
     acc.count = count;
@@ -524,46 +494,18 @@ __global__ __launch_bounds__(256) void k_sem_collect(HvTable table, const VOX *_
     constexpr int BUF = 512;
     __shared__ uint32_t s_buf[4][BUF];
     const int wave = threadIdx.x / HV_WAVE, lane = hv_lane_id();
-    uint32_t *buf = s_buf[wave];
-    int n_buf = 0;       // rows waiting in the window (wave-uniform)
+    HvWaveWindow<uint32_t, BUF> rows{s_buf[wave], &table.counters[HV_CNT_OUT], 0};
     int64_t n_found = 0; // size query (out_pts == nullptr): rows of this wave, added to the counter once
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    auto flush = [&]() {
-        if (n_buf == 0) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int32_t base = 0;
-        if (lane == 0) base = atomicAdd(&table.counters[HV_CNT_OUT], n_buf);
-        base = __shfl(base, 0);
-        for (int i = lane; i < n_buf; i += HV_WAVE) {
-            const int64_t at = (int64_t)base + i;
-            if (at >= cap) continue;
-            const VOX *v = pool + buf[i];
-            const int32_t count = v->count;
-            const double c = (double)count;
-            const float cf = (float)count;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                out_pts[at * 3 + k] = v->pos[k] / c;
-                out_cols[at * 3 + k] = v->col[k] / cf;
-            }
-            out_cls[at] = sem_class_id(v, table.prob_nodes);
-            out_obj[at] = sem_object_id(v, table.prob_nodes);
-            out_conf[at] = sem_confidence(v, table.prob_nodes);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        n_buf = 0;
+    auto emit = [&](int64_t at, uint32_t gid) {
+        const VOX *v = pool + gid;
+        sem_write_row(v, table.prob_nodes, sem_object_id(v, table.prob_nodes), at, out_pts, out_cols, out_cls, out_obj, out_conf);
     };
     const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x / HV_WAVE);
     for (int64_t b = (int64_t)blockIdx.x * (blockDim.x / HV_WAVE) + wave; b < n_blocks; b += n_waves) {
         int32_t bk[3] = {0, 0, 0};
         if (Q.kind != 0) {
             hv_unpack_key(table.block_keys[b], bk[0], bk[1], bk[2]);
-            bool out = false; // the block's key range against the query's: wave-uniform
-#pragma unroll
-            for (int a = 0; a < 3; ++a) out = out || bk[a] < Q.bmin[a] || bk[a] > Q.bmax[a];
-            if (out) continue;
+            if (!sem_block_in_query_box(Q, bk)) continue; // wave-uniform
         }
         sem_for_occupied(occ, b, G.nvox, false, [&](int64_t gid, bool active) {
             bool pred = false;
@@ -572,13 +514,7 @@ __global__ __launch_bounds__(256) void k_sem_collect(HvTable table, const VOX *_
                 const int32_t count = v->count;
                 pred = count >= min_count && sem_confidence(v, table.prob_nodes) >= min_confidence;
                 if (pred && Q.kind != 0) {
-                    const int l = (int)(gid - b * G.nvox);
-                    const int32_t lc[3] = {l % G.bs, (l / G.bs) % G.bs, l / (G.bs * G.bs)};
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        const int32_t vk = bk[a] * G.bs + lc[a];
-                        if (vk < Q.vmin[a] || vk > Q.vmax[a]) pred = false;
-                    }
+                    pred = sem_in_query_box(Q, G, bk, (int)(gid - b * G.nvox));
                     if (pred) {
                         const double c = (double)count;
                         const double p0 = v->pos[0] / c, p1 = v->pos[1] / c, p2 = v->pos[2] / c;
@@ -591,18 +527,11 @@ __global__ __launch_bounds__(256) void k_sem_collect(HvTable table, const VOX *_
                     }
                 }
             }
-            const unsigned long long m = __ballot(pred);
-            if (m == 0ull) return;
-            if (out_pts == nullptr) {
-                n_found += __popcll(m);
-                return;
-            }
-            if (pred) buf[n_buf + __popcll(m & lt)] = (uint32_t)gid;
-            n_buf += __popcll(m);
-            if (n_buf > BUF - HV_WAVE) flush();
+            if (out_pts == nullptr) n_found += __popcll(__ballot(pred));
+            else rows.push(pred, (uint32_t)gid, cap, emit);
         });
     }
-    if (out_pts != nullptr) flush();
+    if (out_pts != nullptr) rows.flush(cap, emit);
     else if (lane == 0 && n_found) atomicAdd(&table.counters[HV_CNT_OUT], (int32_t)n_found);
 }
 

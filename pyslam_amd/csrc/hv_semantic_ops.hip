@@ -52,94 +52,47 @@ static int hv_dev_next_id(int device, int32_t **out) {
 }
 
 template <typename VOX> __device__ __forceinline__ void sem_reset(VOX *v) {
+    uint32_t chain = 0u; // a voxel with label maps keeps its overflow nodes for the map it grows next
+    if constexpr (HvPay<VOX>::maps) chain = v->next;
     uint4 *q = (uint4 *)v;
-    uint32_t chain = 0u; // a probabilistic voxel keeps its overflow nodes for the label map it grows next
-    if constexpr (HvPay<VOX>::maps) chain = ((const HvProbVoxel *)v)->next;
 #pragma unroll
     for (int i = 0; i < (int)(sizeof(VOX) / 16); ++i) q[i] = make_uint4(0u, 0u, 0u, 0u);
     if constexpr (HvPay<VOX>::maps) {
-        if (chain != 0u) ((HvProbVoxel *)v)->next = chain;
+        if (chain != 0u) v->next = chain;
     }
 }
 
-// The visit predicate of iterate_voxels_in_camera_frustrum (min_count = 1, min_confidence = 0).
-template <typename VOX>
-__device__ __forceinline__ bool sem_visit(const HvQuery &Q, const HvTable &table, const VOX *v, int64_t b, int l,
-                                          const HvSemParams &G, float *uvd) {
-    const int32_t count = v->count;
-    if (count < 1) return false;
-    if (!sem_confidence_not_negative(v, table.prob_nodes)) return false; // (confidence >= 0)
-    int32_t bk[3];
-    hv_unpack_key(table.block_keys[b], bk[0], bk[1], bk[2]);
-    const int32_t lc[3] = {l % G.bs, (l / G.bs) % G.bs, l / (G.bs * G.bs)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (bk[a] < Q.bmin[a] || bk[a] > Q.bmax[a]) return false;
-        const int32_t vk = bk[a] * G.bs + lc[a];
-        if (vk < Q.vmin[a] || vk > Q.vmax[a]) return false;
-    }
-    const double c = (double)count;
-    return hv_frustum_contains_d(Q, v->pos[0] / c, v->pos[1] / c, v->pos[2] / c, uvd);
-}
-
-// What the association vote asks of a voxel, read in ONE batch of loads (round 6).  The pointer-based accessors above look at a voxel
-// in global memory field by field behind branches - count, then the label map, then the block key, then the position sums - and the
-// compiler keeps that order: four to five dependent trips to the cache per visit before the image is even looked at.  Here the record
-// (64 / 128 bytes) is loaded whole into registers beside the block key, everything is decided from the copy (the inline label slots
-// through constant indices: hv_semantic.h), and only a map with overflow nodes, an invalid cache or a non-finite log-probability
-// goes back to the pointer-based functions (same answers by construction: they are the fallback).
-struct HvVoteHot {
+// What the visit predicate of iterate_voxels_in_camera_frustrum (min_count = 1, min_confidence = 0: the association vote, the carve)
+// and the vote ask of a voxel, read in ONE batch of loads.  The pointer-based accessors look at a voxel in global memory
+// field by field behind branches - count, then the label map, then the block key, then the position sums - and the compiler keeps
+// that order: four to five dependent trips to the cache per visit before the image is even looked at.  Here the record (64 / 128
+// bytes) is loaded whole into registers beside the block key, everything is decided from the copy (the inline label slots through
+// constant indices: hv_semantic.h), and only a map with overflow nodes, an invalid cache or a non-finite log-probability goes back
+// to the pointer-based functions (same answers by construction: they are the fallback).
+struct HvSemHot {
     int32_t count, cls, obj;
-    bool conf_ok;
+    bool conf_ok; // get_confidence() >= 0
     double pos[3];
 };
-__device__ __forceinline__ HvVoteHot vote_hot(const HvSemVoxel *v, const void *) {
+// (the two counter records differ in the confidence line alone, but stay two functions: as one template - an `if constexpr` around
+// that line - the voting payload's vote kernel takes 98 registers instead of 95 and loses its fifth wave per SIMD)
+__device__ __forceinline__ HvSemHot sem_hot(const HvSemVoxel *v, const void *) {
     const uint4 a = *(const uint4 *)v; // count, obj1, cls1, counter
-    HvVoteHot h;
+    HvSemHot h;
     h.count = (int32_t)a.x;
     h.obj = (int32_t)a.y - 1;
     h.cls = (int32_t)a.z - 1;
     h.pos[0] = v->pos[0];
     h.pos[1] = v->pos[1];
     h.pos[2] = v->pos[2];
-    // get_confidence() >= 0 (sem_confidence above): counter / count clamped to 1, 0 for an empty voxel
+    // get_confidence() >= 0 (sem_confidence): counter / count clamped to 1, 0 for an empty voxel
     const float r = (float)(int32_t)a.w / (float)h.count;
     h.conf_ok = h.count == 0 || (r < 1.0f ? r : 1.0f) >= 0.0f;
     return h;
 }
-__device__ __forceinline__ HvVoteHot vote_hot(const HvProbVoxel *v, const void *nodes_) {
-    const HvProbNode *nodes = (const HvProbNode *)nodes_;
-    const HvProbVoxel r = *v; // eight 16-byte loads in flight together; only constant indices below: the copy stays in registers
-    HvVoteHot h;
-    h.count = r.count;
-    h.pos[0] = r.pos[0];
-    h.pos[1] = r.pos[1];
-    h.pos[2] = r.pos[2];
-    const int nlab = prob_nlab(r.meta), best = prob_best(r.meta);
-    bool finite = true;
-#pragma unroll
-    for (int k = 0; k < HV_PROB_K; ++k) {
-        const float lp = r.logp[k];
-        finite = finite && (k >= nlab || lp - lp == 0.0f);
-    }
-    if (nlab == 0) {
-        h.cls = h.obj = -1;
-        h.conf_ok = true;
-    } else if (nlab <= HV_PROB_K && best >= 0 && finite) { // the common case: decided from the copy
-        const HvProbPair p = prob_slot_get(&r, best);
-        h.cls = p.cls;
-        h.obj = p.obj;
-        h.conf_ok = true;
-    } else { // overflow nodes / no cached best pair / a NaN or an infinity in the map
-        h.cls = sem_class_id(v, nodes);
-        h.obj = sem_object_id(v, nodes);
-        h.conf_ok = sem_confidence_not_negative(v, nodes);
-    }
-    return h;
-}
-__device__ __forceinline__ HvVoteHot vote_hot(const HvSem2Voxel *v, const void *) {
+__device__ __forceinline__ HvSemHot sem_hot(const HvSem2Voxel *v, const void *) {
     const uint4 a = *(const uint4 *)v; // count, obj1, cls1, obj_counter
-    HvVoteHot h;
+    HvSemHot h;
     h.count = (int32_t)a.x;
     h.obj = (int32_t)a.y - 1;
     h.cls = (int32_t)a.z - 1;
@@ -151,61 +104,46 @@ __device__ __forceinline__ HvVoteHot vote_hot(const HvSem2Voxel *v, const void *
     h.conf_ok = h.count == 0 || (c < o ? c : o) >= 0.0f;
     return h;
 }
-__device__ __forceinline__ HvVoteHot vote_hot(const HvProb2Voxel *v, const void *nodes_) {
+// the two map records: copy, count, position and finiteness are shared, they differ in how class and object are chosen
+template <typename VOX>
+__device__ __forceinline__ HvSemHot sem_hot(const VOX *v, const void *nodes_) {
+    static_assert(HvPay<VOX>::maps, "the counter records have their own");
+    HvSemHot h;
     const HvProbNode *nodes = (const HvProbNode *)nodes_;
-    const HvProbVoxel r = *v;
-    HvVoteHot h;
+    const HvProbVoxel r = *v; // eight 16-byte loads in flight together; only constant indices below: the copy stays in registers
     h.count = r.count;
-    h.pos[0] = r.pos[0];
-    h.pos[1] = r.pos[1];
-    h.pos[2] = r.pos[2];
-    const int n = prob_nlab(r.meta);
-    bool finite = true;
 #pragma unroll
-    for (int k = 0; k < HV_PROB_K; ++k) {
-        const float lp = r.logp[k];
-        finite = finite && (k >= n || lp - lp == 0.0f);
-    }
+    for (int k = 0; k < 3; ++k) h.pos[k] = r.pos[k];
+    constexpr bool pairs = HvPay<VOX>::kind == 1;
+    const int n = prob_nlab(r.meta);
+    const bool finite = prob_slots_finite(r, n);
     if (n == 0) {
         h.cls = h.obj = -1;
         h.conf_ok = true;
-    } else if (n <= HV_PROB_K && finite) { // the common case: both most likely ids from the copy (cached entry, else the argmax of its map)
-        auto most_likely = [&](int which, int c) { // (scalars only: nothing of the copy may be reached through a run-time index)
-            int32_t id = -1;
-            float lp = -INFINITY;
-            bool won = false;
-#pragma unroll
-            for (int k = 0; k < HV_PROB_K; ++k) {
-                const bool mine = k < n && r.cls[k] == which;
-                const bool take = mine && (c >= 0 ? k == c : (r.logp[k] > lp || (won && r.logp[k] == lp && r.obj[k] < id)));
-                id = take ? r.obj[k] : id;
-                lp = take ? r.logp[k] : lp;
-                won = won || take;
-            }
-            return id;
-        };
-        h.obj = most_likely(0, prob2_best_obj(r.meta));
-        h.cls = most_likely(1, prob2_best_cls(r.meta));
+    } else if (n <= HV_PROB_K && finite && (!pairs || prob_best(r.meta) >= 0)) { // the common case: decided from the copy
+        if constexpr (pairs) { // the cached most likely pair
+            const HvProbPair p = prob_slot_get(&r, prob_best(r.meta));
+            h.cls = p.cls;
+            h.obj = p.obj;
+        } else { // both most likely ids (cached entry, else the argmax of its map)
+            h.obj = prob2_slots_most_likely(r, n, 0, prob2_best_obj(r.meta));
+            h.cls = prob2_slots_most_likely(r, n, 1, prob2_best_cls(r.meta));
+        }
         h.conf_ok = true;
-    } else { // overflow nodes / a NaN or an infinity in the maps
+    } else { // overflow nodes / no cached best pair / a NaN or an infinity in the map
+        // (the carve reads count, conf_ok and pos alone: inlined there, the two id lookups are dead code and compile away)
         h.cls = sem_class_id(v, nodes);
         h.obj = sem_object_id(v, nodes);
         h.conf_ok = sem_confidence_not_negative(v, nodes);
     }
     return h;
 }
-// sem_visit on the copy
-__device__ __forceinline__ bool sem_visit_hot(const HvQuery &Q, unsigned long long block_key, int l, const HvSemParams &G, const HvVoteHot &h, float *uvd) {
+// the visit predicate on the copy; uvd: the voxel's pixel and depth
+__device__ __forceinline__ bool sem_visit(const HvQuery &Q, unsigned long long block_key, int l, const HvSemParams &G, const HvSemHot &h, float *uvd) {
     if (h.count < 1 || !h.conf_ok) return false;
     int32_t bk[3];
     hv_unpack_key(block_key, bk[0], bk[1], bk[2]);
-    const int32_t lc[3] = {l % G.bs, (l / G.bs) % G.bs, l / (G.bs * G.bs)};
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        if (bk[a] < Q.bmin[a] || bk[a] > Q.bmax[a]) return false;
-        const int32_t vk = bk[a] * G.bs + lc[a];
-        if (vk < Q.vmin[a] || vk > Q.vmax[a]) return false;
-    }
+    if (!sem_in_query_box(Q, G, bk, l)) return false;
     const double c = (double)h.count;
     return hv_frustum_contains_d(Q, h.pos[0] / c, h.pos[1] / c, h.pos[2] / c, uvd);
 }
@@ -216,7 +154,7 @@ __device__ __forceinline__ bool sem_visit_hot(const HvQuery &Q, unsigned long lo
 // u >= 0, u < W, v >= 0, v < H, each linear in camera coordinates - no voxel of the block can pass CameraFrustrum::contains and
 // the wave leaves without reading a single voxel record (a keyframe sees a fraction of the map; the scan is otherwise
 // bs^3 x 64..128 bytes per allocated block whether it is in view or not).  Lanes 0-7 test one corner each.
-__device__ __forceinline__ bool sem_block_outside_frustum_key(const HvQuery &Q, unsigned long long block_key, const HvSemParams &G) {
+__device__ __forceinline__ bool sem_block_outside_frustum(const HvQuery &Q, unsigned long long block_key, const HvSemParams &G) {
     int32_t bk[3];
     hv_unpack_key(block_key, bk[0], bk[1], bk[2]);
     const int lane = hv_lane_id();
@@ -236,22 +174,19 @@ __device__ __forceinline__ bool sem_block_outside_frustum_key(const HvQuery &Q, 
            (__ballot(out3) & corners) == corners || (__ballot(out4) & corners) == corners || (__ballot(out5) & corners) == corners;
 }
 
-__device__ __forceinline__ bool sem_block_outside_frustum(const HvQuery &Q, const HvTable &table, int64_t b, const HvSemParams &G) {
-    return sem_block_outside_frustum_key(Q, table.block_keys[b], G);
-}
-
 template <typename VOX>
 __global__ __launch_bounds__(256) void k_sem_carve(HvTable table, VOX *__restrict__ pool, int64_t n_blocks, HvSemParams G,
                                                     HvQuery Q, const float *__restrict__ depth, const unsigned long long *__restrict__ occ) {
     // one wave per block, its occupied voxels only (sem_for_occupied)
     const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x / HV_WAVE);
     for (int64_t b = (int64_t)blockIdx.x * (blockDim.x / HV_WAVE) + threadIdx.x / HV_WAVE; b < n_blocks; b += n_waves) {
-        if ((G.nvox & 63) == 0 && sem_block_outside_frustum(Q, table, b, G)) continue; // wave-uniform
+        const unsigned long long bkey = table.block_keys[b];
+        if ((G.nvox & 63) == 0 && sem_block_outside_frustum(Q, bkey, G)) continue; // wave-uniform
         sem_for_occupied(occ, b, G.nvox, false, [&](int64_t gid, bool active) {
             if (!active) return;
             VOX *v = pool + gid;
             float uvd[3];
-            if (!sem_visit(Q, table, v, b, (int)(gid - b * G.nvox), G, uvd)) return;
+            if (!sem_visit(Q, bkey, (int)(gid - b * G.nvox), G, sem_hot(v, table.prob_nodes), uvd)) return;
             const float image_depth = depth[(int64_t)(int)uvd[1] * Q.width + (int)uvd[0]];
             if (image_depth <= 0.0f || !isfinite(image_depth)) return;
             if (uvd[2] < image_depth - Q.carve_threshold) sem_reset(v);
@@ -363,22 +298,8 @@ __global__ __launch_bounds__(256, MINWG) void k_sem_assoc_vote(HvTable table, VO
     // with a pending lane - tens of thousands on a single word, ~10 ns each, serialised - was most of this kernel.
     constexpr int PEND_BUF = 256;
     __shared__ int2 s_pend[4][PEND_BUF];
-    int2 *pend = s_pend[threadIdx.x / HV_WAVE];
-    int n_pend = 0; // (wave-uniform)
-    const unsigned long long lane_lt = hv_lane_id() == 0 ? 0ull : (~0ull >> (64 - hv_lane_id()));
-    auto flush_pending = [&]() {
-        if (n_pend == 0) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int32_t base = 0;
-        if (hv_lane_id() == 0) base = atomicAdd(&table.counters[HV_CNT_AUX], n_pend);
-        base = __shfl(base, 0);
-        for (int k = hv_lane_id(); k < n_pend; k += HV_WAVE)
-            if (base + k < A.pending_cap) pending[base + k] = pend[k];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        n_pend = 0;
-    };
+    HvWaveWindow<int2, PEND_BUF> pend{s_pend[threadIdx.x / HV_WAVE], &table.counters[HV_CNT_AUX], 0};
+    auto pend_emit = [&](int64_t at, int2 p) { pending[at] = p; };
     // The occupied voxels of the blocks in view are QUEUED per wave in LDS and visited 64 at a time, every lane busy (round 6).  A
     // 2 mm keyframe faces 160 k blocks holding 15 occupied voxels each on average: visited block by block, a wave went through its
     // two dependent round trips (record -> image pixels) once per block with a quarter of its lanes, 160 k times per keyframe; from
@@ -398,9 +319,9 @@ __global__ __launch_bounds__(256, MINWG) void k_sem_assoc_vote(HvTable table, VO
         if (active) {
             VOX *v = pool + gid;
             const unsigned long long bkey = table.block_keys[b]; // (requested with the record)
-            const HvVoteHot h = vote_hot(v, table.prob_nodes);
+            const HvSemHot h = sem_hot(v, table.prob_nodes);
             float uvd[3];
-            if (sem_visit_hot(Q, bkey, (int)(gid - b * G.nvox), G, h, uvd)) {
+            if (sem_visit(Q, bkey, (int)(gid - b * G.nvox), G, h, uvd)) {
                 // the three pixels in one trip as well
                 const int64_t px = (int64_t)(int)uvd[1] * Q.width + (int)uvd[0];
                 const int32_t image_class = cls_img[px];
@@ -434,12 +355,7 @@ __global__ __launch_bounds__(256, MINWG) void k_sem_assoc_vote(HvTable table, VO
             }
         }
         vote_wave_local(s_votes, vkeys, vcounts, &table.counters[HV_CNT_OUT2], key);
-        const unsigned long long pm = __ballot(is_pending);
-        if (pm) {
-            if (is_pending) pend[n_pend + __popcll(pm & lane_lt)] = make_int2((int32_t)gid, inst);
-            n_pend += __popcll(pm);
-            if (n_pend > PEND_BUF - HV_WAVE) flush_pending();
-        }
+        pend.push(is_pending, make_int2((int32_t)gid, inst), A.pending_cap, pend_emit);
     };
     auto drain_queue = [&](bool all) { // ONE instance of the visit in the kernel
         hv_wave_lds_sync();
@@ -458,7 +374,7 @@ __global__ __launch_bounds__(256, MINWG) void k_sem_assoc_vote(HvTable table, VO
     };
     auto enqueue = [&](int64_t gid, bool active) {
         const unsigned long long m = __ballot(active);
-        if (active) queue[n_q + (int)__popcll(m & lane_lt)] = (int32_t)gid;
+        if (active) queue[n_q + hv_wave_rank(m)] = (int32_t)gid;
         n_q += (int)__popcll(m);
         if (n_q > Q_CAP - HV_WAVE) drain_queue(false);
     };
@@ -477,12 +393,12 @@ __global__ __launch_bounds__(256, MINWG) void k_sem_assoc_vote(HvTable table, VO
             next_word = (words && lane < W) ? occ[(b + n_waves) * W + lane] : 0ull;
         }
         if (words && !__any(word != 0ull)) continue;                                      // nothing ever landed in this block
-        if ((G.nvox & 63) == 0 && sem_block_outside_frustum_key(Q, bkey, G)) continue; // wave-uniform
+        if ((G.nvox & 63) == 0 && sem_block_outside_frustum(Q, bkey, G)) continue; // wave-uniform
         if (words) sem_for_occupied_word(word, b, G.nvox, enqueue);
         else sem_for_occupied(occ, b, G.nvox, false, enqueue);
     }
     drain_queue(true);
-    flush_pending();
+    pend.flush(A.pending_cap, pend_emit);
     // the image scan of voxel_semantic_data_association.h:316-331 - every instance id with a valid class - into the same workgroup table:
     // a launch of its own until round 6 (18 us at 1296x968, 10 us at 640x480 for a pass over two images); here it fills the tail of this
     // kernel, where most waves have run out of blocks (the table takes the markers in any order)
@@ -738,23 +654,9 @@ __global__ __launch_bounds__(256) void k_seg_collect(HvTable table, const VOX *_
     constexpr int BUF = 512;
     __shared__ unsigned long long s_buf[4][BUF];
     const int wave = threadIdx.x / HV_WAVE, lane = hv_lane_id();
-    unsigned long long *buf = s_buf[wave];
-    int n_buf = 0;
+    HvWaveWindow<unsigned long long, BUF> keys{s_buf[wave], &table.counters[HV_CNT_OUT], 0};
     int64_t n_found = 0;
-    const unsigned long long lt = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-    auto flush = [&]() {
-        if (n_buf == 0) return;
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        int32_t base = 0;
-        if (lane == 0) base = atomicAdd(&table.counters[HV_CNT_OUT], n_buf);
-        base = __shfl(base, 0);
-        for (int i = lane; i < n_buf; i += HV_WAVE)
-            if ((int64_t)base + i < cap) out_keys[(int64_t)base + i] = buf[i];
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        n_buf = 0;
-    };
+    auto emit = [&](int64_t at, unsigned long long key) { out_keys[at] = key; };
     const int64_t n_waves = (int64_t)gridDim.x * (blockDim.x / HV_WAVE);
     for (int64_t b = (int64_t)blockIdx.x * (blockDim.x / HV_WAVE) + wave; b < n_blocks; b += n_waves) {
         sem_for_occupied(occ, b, nvox, false, [&](int64_t gid, bool active) {
@@ -768,18 +670,11 @@ __global__ __launch_bounds__(256) void k_seg_collect(HvTable table, const VOX *_
                     pred = obj >= 0;
                 }
             }
-            const unsigned long long m = __ballot(pred);
-            if (m == 0ull) return;
-            if (out_keys == nullptr) {
-                n_found += __popcll(m);
-                return;
-            }
-            if (pred) buf[n_buf + __popcll(m & lt)] = ((unsigned long long)(uint32_t)obj << 32) | (unsigned long long)(uint32_t)gid;
-            n_buf += __popcll(m);
-            if (n_buf > BUF - HV_WAVE) flush();
+            if (out_keys == nullptr) n_found += __popcll(__ballot(pred));
+            else keys.push(pred, ((unsigned long long)(uint32_t)obj << 32) | (unsigned long long)(uint32_t)gid, cap, emit);
         });
     }
-    if (out_keys != nullptr) flush();
+    if (out_keys != nullptr) keys.flush(cap, emit);
     else if (lane == 0 && n_found) atomicAdd(&table.counters[HV_CNT_OUT], (int32_t)n_found);
 }
 
@@ -791,17 +686,7 @@ __global__ __launch_bounds__(256) void k_seg_rows(const VOX *__restrict__ pool, 
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const unsigned long long k = keys[i];
-    const VOX *v = pool + (uint32_t)(k & 0xffffffffull);
-    const double c = (double)v->count;
-    const float cf = (float)v->count;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        out_pts[i * 3 + a] = v->pos[a] / c;
-        out_cols[i * 3 + a] = v->col[a] / cf;
-    }
-    out_obj[i] = (int32_t)(k >> 32);
-    out_cls[i] = sem_class_id(v, nodes);
-    out_conf[i] = sem_confidence(v, nodes);
+    sem_write_row(pool + (uint32_t)(k & 0xffffffffull), nodes, (int32_t)(k >> 32), i, out_pts, out_cols, out_cls, out_obj, out_conf);
 }
 
 // op 0 merge_segments(a <- b), 1 remove_segment(a), 2 remove_low_confidence_segments(int a),

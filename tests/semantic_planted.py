@@ -366,6 +366,30 @@ def dense_pending_case(bs):
     return c
 
 
+def dense_rows_case(bs):
+    """One fully occupied bs^3 block and a second, sparse one (five voxels).  A wave scans a block 64 voxels at a time and pushes
+    what it finds into its 512-entry window - rows of get_voxels, keys of get_object_segments - which flushes from inside a push once
+    more than 448 wait.  Objects 10-12 by y, each of one class (1-3); bs voxels of the dense block (x = 0 of the top y layer) and two
+    of the sparse one have no object id: rows of get_voxels, keys of no segment.  One point in every fourth voxel, two in the others.
+    - bs 8: 512 rows and 504 keys: seven pushes fill a window to at most 448, the eighth flushes it; the scan's end finds it empty.
+    - bs 12: 1728 rows and 1716 keys: every window flushes three times with the rest of the block still to come, so the pushes after
+      a flush start at 0 again; with a count above 1 asked for (1296 rows, 1287 keys) the pushes are partial and the flushes fall at
+      449..512 entries instead of at 512.
+    c.planted = (object id or -1, points) of every voxel."""
+    c = Case(f"dense_rows-bs{bs}", bs, IDENTITY)
+    ix, iy, iz = np.meshgrid(np.arange(bs), np.arange(bs), np.arange(4 * bs, 5 * bs), indexing="ij")
+    sx, sy, sz = np.array([0, 1, 3, bs - 2, bs - 1]), np.array([0, 1, 3, bs - 2, bs - 1]), np.array([0, 1, 3, bs - 2, bs - 1])
+    ix, iy, iz = (np.concatenate([a.ravel(), b]) for a, b in zip((ix, iy, iz), (2 * bs + sx, sy, 4 * bs + sz)))
+    pts = np.stack([(ix + 0.5) / 16.0, (iy + 0.5) / 16.0, (iz + 0.5) / 16.0], 1)
+    obj = np.where((iy == bs - 1) & (ix % bs == 0), -1, iy % 3 + 10)
+    obj[-2:] = -1
+    rep = np.where((ix + iy + iz) % 4 == 0, 1, 2)
+    c.integrate(pts, iy % 3 + 1, obj, repeat=rep)
+    c.planted = (obj, rep)
+    assert c.n_blocks() == 2
+    return c
+
+
 def scene_from_pairs(name, pairs, min_vote_ratio, min_votes, next_id, bs=8, calls=1):
     """A scene whose only association call casts exactly `pairs`: for (instance, object, n) n voxels with that object id (none for
     PENDING) under pixels of that instance, for (instance, SEEN, _) a pixel of that instance over no voxel; a SEEN marker is implied

@@ -321,6 +321,68 @@ def test_merge_into_the_voxels_without_an_object_id_reaches_empty_voxels(kind):
             assert ids_multiset(*gpu.g.get_ids()) == ids_multiset(*r.get_ids())
 
 
+def sorted_rows(points, colors, cls, obj, conf):
+    order = np.lexsort(np.asarray(points).T[::-1])
+    return [np.asarray(a)[order] for a in (points, colors, cls, obj, conf)]
+
+
+@pytest.mark.parametrize("bs", [8, 12])
+@pytest.mark.parametrize("kind", KINDS)
+def test_a_full_block_flushes_the_row_windows_in_the_middle_of_a_scan(kind, bs):
+    """get_voxels and get_object_segments on sp.dense_rows_case: one wave gets a whole block's rows, and its window of 512 flushes from
+    inside a push once more than 448 wait - on the block's last push at block size 8 (512 rows, 504 keys), three times with rows of
+    the same block still to come at block size 12 (1728 rows, 1716 keys; partial pushes where a count above 1 is asked for); five
+    voxels go to another wave.  Row sets against the oracles and the planted numbers: positions, colours and ids exact, confidences
+    to the file's tolerance.  get_voxels once more with output capacities below the row count - inside the first flush and between
+    later ones: the count is still the whole count, the rows written are distinct rows of the full set (which ones is the order
+    of the waves).  get_object_segments sizes its own output from a counting pass: there is no capacity to set."""
+    import ctypes
+
+    from pyslam_amd import _lib as L
+
+    case = sp.dense_rows_case(bs)
+    obj, rep = case.planted
+    gpu = GpuGrid(kind, case.bs)
+    refs = [mk(kind, sp.VOXEL, case.bs) for mk in ORACLES]
+    for g in [gpu] + refs:
+        sp.drive(g, case)
+    tol = 0.0 if kind in EXACT else 2e-6
+    total = bs ** 3 + 5
+    assert gpu.g.size() == total == len(obj)
+    for min_count in (1, 2):  # get_voxels keeps count >= min_count
+        got = gpu.g.get_voxels(min_count, 0.0)
+        rows = sorted_rows(got.points, got.colors, got.class_ids, got.object_ids, got.confidences)
+        assert len(rows[0]) == int((rep >= min_count).sum())
+        np.testing.assert_array_equal(np.sort(rows[3]), np.sort(obj[rep >= min_count]))
+        for r in refs:
+            exp = sorted_rows(*r.get_voxels(min_count, 0.0))
+            for a, b in zip(rows[:4], exp[:4]):
+                np.testing.assert_array_equal(a, b)
+            np.testing.assert_allclose(rows[4], exp[4], rtol=0, atol=tol)
+    for min_count in (0, 1):  # get_object_segments keeps count > min_count
+        segs = gpu.g.get_object_segments(min_count, 0.0)
+        planted = [(o, int(((obj == o) & (rep > min_count)).sum())) for o in (10, 11, 12)]
+        assert [(int(o.object_id), len(o.points)) for o in segs.object_vector] == planted
+        for r in refs:
+            exp = r.get_object_segments(min_count, 0.0)
+            assert [(int(o.object_id), int(o.class_id), len(o.points)) for o in segs.object_vector] == [(o["object_id"], o["class_id"], len(o["points"])) for o in exp]
+            for a, b in zip(segs.object_vector, exp):
+                for x, y in ((a.points, b["points"]), (a.colors, b["colors"])):
+                    np.testing.assert_array_equal(x[np.lexsort(a.points.T[::-1])], y[np.lexsort(b["points"].T[::-1])])
+                assert abs(a.confidence_min - b["conf_min"]) <= tol and abs(a.confidence_max - b["conf_max"]) <= tol
+    got = gpu.g.get_voxels(1, 0.0)
+    rows = sorted_rows(got.points, got.colors, got.class_ids, got.object_ids, got.confidences)
+    full = {tuple(np.concatenate([rows[0][i], rows[1][i], [rows[2][i], rows[3][i], rows[4][i]]]).tolist()) for i in range(total)}
+    assert len(full) == total
+    for cap in (100, 460) + ((1100,) if bs == 12 else ()):
+        out = [np.zeros((cap, 3), np.float64), np.zeros((cap, 3), np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float32)]
+        n = ctypes.c_int64()
+        L.check(gpu.g._lib.hv_get_voxels_semantic(gpu.g._h, 1, 0.0, *(L.ptr(a) for a in out), cap, ctypes.byref(n)))
+        assert n.value == total
+        some = {tuple(np.concatenate([out[0][i], out[1][i], [out[2][i], out[3][i], out[4][i]]]).tolist()) for i in range(cap)}
+        assert len(some) == cap and some <= full
+
+
 # ---- e. the vote kernel against the staged interface --------------------------------------------------------------------------------
 @pytest.mark.parametrize("kind", KINDS)
 @pytest.mark.parametrize("which", ["many_pairs", "dense_pending"])
