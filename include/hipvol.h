@@ -445,6 +445,38 @@ int hv_tsdf_extract_mesh(hv_volume *v, double *vertices, double *vertex_colors, 
 int hv_tsdf_extract_mesh_f32(hv_volume *v, float *vertices, float *vertex_colors, int64_t cap_vertices,
                              int32_t *triangles, int64_t cap_triangles, int64_t *n_vertices,
                              int64_t *n_triangles);
+/* A simplified mesh by vertex clustering (Open3D users reach for simplify_vertex_clustering on the host; here the full mesh never
+ * leaves the device, nor is it written).  This project's own contract.  Let FULL be the mesh hv_tsdf_extract_mesh returns for the
+ * volume as it is now: V vertices and T triangles, float64, in that call's order.
+ *   Owner and cell.  Every full vertex v lies on the edge from its OWNER voxel g(v) to g(v) + e_axis; g is the global integer voxel
+ *     index, unit key * 16 + (x, y, z), its centre at (g + 0.5) * voxel_length.  With cell = k voxels, k in {2, 4, 8, 16}:
+ *     cell(v) = floor_div(g(v), k) per component (towards -inf: unit keys are negative too).  No floating-point value takes part.
+ *     A CLUSTER is the set of full vertices with the same cell; it lies inside one unit.
+ *   Vertices.  One per non-empty cluster (also one no kept triangle references).  Clusters of the unit that comes first in FULL come
+ *     first (FULL's vertices are grouped by unit); inside a unit they ascend by (cx, cy, cz), x-major.  Position and colour are each
+ *     (the members' float64 values, FULL's bit for bit, added one by one in ascending full vertex index starting from the first
+ *     member) / (double)count, per component; _f32 rounds that double once, as hv_tsdf_extract_mesh_f32 does.
+ *   Triangles.  A full triangle (a, b, c) maps to the cluster numbers (A, B, C); it is DROPPED when two of them are equal, otherwise
+ *     rotated so that its smallest number comes first (orientation kept).  The output is the set of DISTINCT rotated triples, sorted
+ *     lexicographically; (A, B, C) and (A, C, B) are different triangles and both stay, as in Open3D's clustering.
+ *   vertex_cluster i32 [V], optional (NULL): for every full vertex the number of its simplified vertex - to carry per-vertex data
+ *     (hv_lookup_points labels, ...) from one mesh to the other.
+ *   Normals are not part of the result: sample the map at the simplified vertices (hv_tsdf_sample_points with gradients).
+ * Reads only: no growth, stamp or claim; the cached full mesh / point cloud stand (results and scratch are separate), and two calls
+ * give bitwise equal outputs.  The result depends on pool order only through FULL's unit order.  An empty map, or one without a
+ * surface, gives 0 / 0 and is not an error.
+ * Count-then-fill, as hv_tsdf_extract_mesh: *n_vertices, *n_triangles and *n_full_vertices (= V) are always written; with vertices
+ * or vertex_colors NULL the call is a size query.  triangles may be NULL on its own (a result with vertices and no triangle, whose
+ * zero-row array has no address): the other arrays are still filled.  The result is kept under (contents, cell, type), so the pair computes
+ * once.  At most cap_* rows of each array are written; destinations may be host or device memory.
+ * Errors: HV_ERR_MODE as hv_tsdf_extract_mesh; HV_ERR_INVALID for a cell outside {2, 4, 8, 16}, a unit resolution other than 16,
+ * or a null count pointer. */
+int hv_tsdf_extract_mesh_clustered(hv_volume *v, int32_t cell, double *vertices, double *vertex_colors, int64_t cap_vertices,
+                                   int32_t *triangles, int64_t cap_triangles, int32_t *vertex_cluster, int64_t cap_full_vertices,
+                                   int64_t *n_vertices, int64_t *n_triangles, int64_t *n_full_vertices);
+int hv_tsdf_extract_mesh_clustered_f32(hv_volume *v, int32_t cell, float *vertices, float *vertex_colors, int64_t cap_vertices,
+                                       int32_t *triangles, int64_t cap_triangles, int32_t *vertex_cluster, int64_t cap_full_vertices,
+                                       int64_t *n_vertices, int64_t *n_triangles, int64_t *n_full_vertices);
 /* extract_point_cloud() (volumetric_integrator_tsdf.py:246,267): points/colors f64 [N,3]. */
 int hv_tsdf_extract_points(hv_volume *v, double *points, double *colors, int64_t cap, int64_t *n);
 /* ... with float32 points / colors (the float64 rows rounded once, as hv_tsdf_extract_mesh_f32). */

@@ -554,6 +554,18 @@ struct hv_volume {
     void *mc_cache = nullptr; // [edge_mask cap*192 u64][counts cap+1 u64][word_prefix cap*192 u32][cases cap*4096 u8]
     void *pc_cache = nullptr; // [count cap+1 i32]
 
+    // Vertex-clustered mesh (hv_tsdf_extract_mesh_clustered): results and scratch of their own, so that neither this mesh nor the full
+    // one in out_a / out_b clobbers the other.  Cached under (content_version, cell, type): count-then-fill computes once.
+    void *cl_verts = nullptr; // [vertices 3 nv][colours 3 nv] float64 or float32, [vertex_cluster n_full] i32
+    void *cl_tris = nullptr;  // [nt,3] i32
+    void *cl_units = nullptr; // per unit: occupied-cell masks, cluster and candidate-triangle counts and bases
+    void *cl_tmp = nullptr;   // candidate triples, both sides of the two sort passes, flags and positions
+    size_t cl_verts_bytes = 0, cl_tris_bytes = 0, cl_units_bytes = 0, cl_tmp_bytes = 0;
+    uint64_t cl_version = 0;  // content_version the result belongs to (0: none)
+    int32_t cl_cell = 0;
+    bool cl_f32 = false;
+    int64_t cl_nv = 0, cl_nt = 0, cl_nfull = 0;
+
     // output scratch (grown on demand)
     void *out_a = nullptr;
     void *out_b = nullptr;

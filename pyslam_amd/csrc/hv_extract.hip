@@ -18,6 +18,8 @@
 //   k_mc_triangles  (workgroup) reads the stored cube cases and emits triangles whose vertex indices are
 //                   base[unit(edge)] + rank(edge) - no hash map, no atomics in the emit passes; like the vertices and the
 //                   points, the unit's triangles are dealt out evenly over the threads (rank -> column by binary search).
+// Vertex-clustered mesh (hv_tsdf_extract_mesh_clustered): the same classification, then k_cl_cells / k_cl_vertices / k_cl_triangles
+// and a sort instead of the two emit passes - see the section behind k_mc_triangles.
 // Point cloud: k_pc_extract<false> counts the unit's crossings from the masks, scan, k_pc_extract<true> finds them again and
 // gathers the values of the crossing voxels only - no slab, no atomics.
 // Vertex/triangle *order* differs from Open3D's unordered_map iteration order (so does Open3D's
@@ -29,6 +31,7 @@
 #include "hv_common.h"
 #include "hv_tsdf_sample.h"
 #include "mc_tables.h"
+#include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
 
 static constexpr int MASK_WORDS = 3 * HV_TSDF_RRR / 64; // 192
@@ -317,6 +320,43 @@ __device__ __forceinline__ int hv_nth_set_bit(unsigned long long m, int n) { // 
     return pos;
 }
 
+// The marching-cubes vertex on the edge from voxel `lin` of unit idx (key ux, uy, uz) to its +axis neighbour: position and colour in
+// float64, as Open3D interpolates them.  The ONE expression of both: k_mc_vertices writes these values, k_cl_vertices averages them,
+// and the clustered mesh is defined on the full mesh's values bit for bit.
+__device__ __forceinline__ void mc_vertex_value(const HvTable &table, const char *__restrict__ pool, int idx, int32_t ux, int32_t uy,
+                                                int32_t uz, int axis, int lin, const HvMcParams &M, double pt[3], double col[3]) {
+    const char *u0 = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
+    // owner voxel and its +axis neighbour
+    const int z = lin / HV_TSDF_RR, x = (lin / HV_TSDF_R) % HV_TSDF_R, y = lin % HV_TSDF_R;
+    int nx = x + (axis == 0), ny = y + (axis == 1), nz = z + (axis == 2);
+    int nidx = idx;
+    if (nx >= HV_TSDF_R || ny >= HV_TSDF_R || nz >= HV_TSDF_R) {
+        const int32_t slot = hv_table_find(table, hv_pack_key(ux + (nx >= HV_TSDF_R), uy + (ny >= HV_TSDF_R), uz + (nz >= HV_TSDF_R)));
+        nidx = slot >= 0 ? table.vals[slot] : -1;
+        nx &= HV_TSDF_R - 1; ny &= HV_TSDF_R - 1; nz &= HV_TSDF_R - 1;
+    }
+    const double f0 = fabs((double)((const float *)u0)[lin]);
+    const double w0 = (double)((const uint32_t *)(u0 + HV_TSDF_PLANE_BYTES))[lin];
+    double c0[3], c1[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) c0[k] = ((double)((const uint32_t *)(u0 + (2 + k) * HV_TSDF_PLANE_BYTES))[lin] / w0) / 255.0;
+    double f1 = 0.0;
+    if (nidx >= 0) {
+        const char *u1 = pool + (int64_t)nidx * HV_TSDF_UNIT_BYTES;
+        const int nl = hv_tsdf_word(nx, ny, nz);
+        f1 = fabs((double)((const float *)u1)[nl]);
+        const double w1 = (double)((const uint32_t *)(u1 + HV_TSDF_PLANE_BYTES))[nl];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c1[k] = ((double)((const uint32_t *)(u1 + (2 + k) * HV_TSDF_PLANE_BYTES))[nl] / w1) / 255.0;
+    }
+    pt[0] = M.half_voxel_length + M.voxel_length * (double)(ux * HV_TSDF_R + x);
+    pt[1] = M.half_voxel_length + M.voxel_length * (double)(uy * HV_TSDF_R + y);
+    pt[2] = M.half_voxel_length + M.voxel_length * (double)(uz * HV_TSDF_R + z);
+    pt[axis] += f0 * M.voxel_length / (f0 + f1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) col[k] = (f1 * c0[k] + f0 * c1[k]) / (f0 + f1);
+}
+
 // OUT = double: Open3D's arrays; OUT = float: the same float64 values rounded once on the way out (hv_tsdf_extract_mesh_f32 - what
 // pySLAM's viewer casts them to, config_parameters.py:290-291; half the bytes written here and half the bytes across PCIe).
 template <typename OUT>
@@ -343,7 +383,6 @@ __global__ __launch_bounds__(64) void k_mc_vertices(HvTable table, const char *_
     __builtin_amdgcn_wave_barrier();
     int32_t ux, uy, uz;
     hv_unpack_key(table.block_keys[idx], ux, uy, uz);
-    const char *u0 = pool + (int64_t)idx * HV_TSDF_UNIT_BYTES;
     for (int r = lane; r < total; r += HV_WAVE) {
         const int64_t vi = vbase + r;
         if (vi >= cap) return;
@@ -356,39 +395,68 @@ __global__ __launch_bounds__(64) void k_mc_vertices(HvTable table, const char *_
         const int word = lo;
         const int axis = (word % 12) >> 2;
         const int lin = ((word / 12) * 4 + (word & 3)) * 64 + hv_nth_set_bit(s_mask[word], r - (int)s_prefix[word]);
-        // owner voxel and its +axis neighbour
-        const int z = lin / HV_TSDF_RR, x = (lin / HV_TSDF_R) % HV_TSDF_R, y = lin % HV_TSDF_R;
-        int nx = x + (axis == 0), ny = y + (axis == 1), nz = z + (axis == 2);
-        int nidx = idx;
-        if (nx >= HV_TSDF_R || ny >= HV_TSDF_R || nz >= HV_TSDF_R) {
-            const int32_t slot = hv_table_find(table, hv_pack_key(ux + (nx >= HV_TSDF_R), uy + (ny >= HV_TSDF_R), uz + (nz >= HV_TSDF_R)));
-            nidx = slot >= 0 ? table.vals[slot] : -1;
-            nx &= HV_TSDF_R - 1; ny &= HV_TSDF_R - 1; nz &= HV_TSDF_R - 1;
-        }
-        const double f0 = fabs((double)((const float *)u0)[lin]);
-        const double w0 = (double)((const uint32_t *)(u0 + HV_TSDF_PLANE_BYTES))[lin];
-        double c0[3], c1[3] = {0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c0[k] = ((double)((const uint32_t *)(u0 + (2 + k) * HV_TSDF_PLANE_BYTES))[lin] / w0) / 255.0;
-        double f1 = 0.0;
-        if (nidx >= 0) {
-            const char *u1 = pool + (int64_t)nidx * HV_TSDF_UNIT_BYTES;
-            const int nl = hv_tsdf_word(nx, ny, nz);
-            f1 = fabs((double)((const float *)u1)[nl]);
-            const double w1 = (double)((const uint32_t *)(u1 + HV_TSDF_PLANE_BYTES))[nl];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) c1[k] = ((double)((const uint32_t *)(u1 + (2 + k) * HV_TSDF_PLANE_BYTES))[nl] / w1) / 255.0;
-        }
-        double pt[3] = {M.half_voxel_length + M.voxel_length * (double)(ux * HV_TSDF_R + x),
-                        M.half_voxel_length + M.voxel_length * (double)(uy * HV_TSDF_R + y),
-                        M.half_voxel_length + M.voxel_length * (double)(uz * HV_TSDF_R + z)};
-        pt[axis] += f0 * M.voxel_length / (f0 + f1);
+        double pt[3], col[3];
+        mc_vertex_value(table, pool, idx, ux, uy, uz, axis, lin, M, pt, col);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             vertices[vi * 3 + k] = (OUT)pt[k];
-            colors[vi * 3 + k] = (OUT)((f1 * c0[k] + f0 * c1[k]) / (f0 + f1));
+            colors[vi * 3 + k] = (OUT)col[k];
         }
     }
+}
+
+// The walk over a unit's triangles, shared by k_mc_triangles and k_cl_triangles (a workgroup of 256: thread <-> column x * 16 + y, pk =
+// the column's 16 cube cases).  mc_triangle_ranks: each column's 16 triangle counts as nibbles (s_nib) and the exclusive prefix of the
+// columns' totals (s_pre[256] = the unit's) - rank of a thread's triangles inside the unit: wave prefix + the 4 wave totals.
+__device__ __forceinline__ void mc_triangle_ranks(const uint4 pk, const uint8_t *s_tcnt, unsigned long long *s_nib, int *s_wave, int *s_pre) {
+    const uint32_t packed[4] = {pk.x, pk.y, pk.z, pk.w};
+    int tris = 0;
+    unsigned long long nib = 0ull; // nibble z: triangles of the column's cube z (at most 5)
+#pragma unroll
+    for (int z = 0; z < HV_TSDF_R; ++z) {
+        const int c = s_tcnt[(packed[z >> 2] >> ((z & 3) * 8)) & 255u];
+        tris += c;
+        nib |= (unsigned long long)c << (4 * z);
+    }
+    s_nib[threadIdx.x] = nib;
+    const int lane = hv_lane_id(), wave = threadIdx.x >> 6;
+    int incl = tris;
+#pragma unroll
+    for (int o = 1; o < HV_WAVE; o <<= 1) {
+        const int up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    if (lane == HV_WAVE - 1) s_wave[wave] = incl;
+    __syncthreads();
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += s_wave[w];
+    s_pre[threadIdx.x] = before + incl - tris;
+    if (threadIdx.x == 255) s_pre[256] = before + incl;
+    __syncthreads();
+}
+
+// The unit's triangles are dealt out evenly (as the vertices and the points are): triangle r belongs to the column whose exclusive
+// count is the last one <= r; inside the column it is found by walking the 16 counts.  -> its cube (x, y, z), the cube's case and
+// i = the index of its first edge in the case's row of the triangle table.
+__device__ __forceinline__ void mc_locate_triangle(int r, const int *s_pre, const unsigned long long *s_nib, const uint4 *s_cases, int &x,
+                                                   int &y, int &z, int &cube, int &i) {
+    int lo = 0, hi = 256; // s_pre[lo] <= r < s_pre[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (s_pre[mid] <= r) lo = mid; else hi = mid;
+    }
+    x = lo >> 4;
+    y = lo & 15;
+    unsigned long long cw = s_nib[lo];
+    int j = r - s_pre[lo];
+    for (z = 0; z < HV_TSDF_R - 1; ++z) {
+        const int c = (int)(cw & 15ull);
+        if (j < c) break;
+        j -= c;
+        cw >>= 4;
+    }
+    cube = ((const uint8_t *)&s_cases[lo])[z];
+    i = 3 * j;
 }
 
 // Reads the cube cases k_mc_classify left (16 bytes per thread: its column) instead of staging the slab again.  Everything a
@@ -426,51 +494,11 @@ __global__ __launch_bounds__(256) void k_mc_triangles(HvTable table, int n_units
     s_cases[threadIdx.x] = pk;
     __syncthreads();
     if (threadIdx.x < 8) s_vbase[threadIdx.x] = s_nbr[threadIdx.x] >= 0 ? (int32_t)(uint32_t)bases[s_nbr[threadIdx.x]] : 0;
-    const uint32_t packed[4] = {pk.x, pk.y, pk.z, pk.w};
-    int tris = 0;
-    unsigned long long nib = 0ull; // nibble z: triangles of the column's cube z (at most 5)
-#pragma unroll
-    for (int z = 0; z < HV_TSDF_R; ++z) {
-        const int c = s_tcnt[(packed[z >> 2] >> ((z & 3) * 8)) & 255u];
-        tris += c;
-        nib |= (unsigned long long)c << (4 * z);
-    }
-    s_nib[threadIdx.x] = nib;
-    // rank of this thread's triangles inside the unit: wave prefix + the 4 wave totals
-    const int lane = hv_lane_id(), wave = threadIdx.x >> 6;
-    int incl = tris;
-#pragma unroll
-    for (int o = 1; o < HV_WAVE; o <<= 1) {
-        const int up = __shfl_up(incl, o);
-        if (lane >= o) incl += up;
-    }
-    if (lane == HV_WAVE - 1) s_wave[wave] = incl;
-    __syncthreads();
-    int before = 0;
-    for (int w = 0; w < wave; ++w) before += s_wave[w];
-    // The unit's triangles are dealt out evenly (as the vertices and the points are): triangle r belongs to the column whose
-    // exclusive count is the last one <= r; inside the column it is found by walking the 16 counts.
-    s_pre[threadIdx.x] = before + incl - tris;
-    if (threadIdx.x == 255) s_pre[256] = before + incl;
-    __syncthreads();
+    mc_triangle_ranks(pk, s_tcnt, s_nib, s_wave, s_pre);
     for (int r = threadIdx.x; r < total; r += 256) {
         const int64_t at = tbase + r;
-        int lo = 0, hi = 256; // s_pre[lo] <= r < s_pre[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (s_pre[mid] <= r) lo = mid; else hi = mid;
-        }
-        const int x = lo >> 4, y = lo & 15;
-        unsigned long long cw = s_nib[lo];
-        int j = r - s_pre[lo], z = 0;
-        for (; z < HV_TSDF_R - 1; ++z) {
-            const int c = (int)(cw & 15ull);
-            if (j < c) break;
-            j -= c;
-            cw >>= 4;
-        }
-        const int cube = ((const uint8_t *)&s_cases[lo])[z];
-        const int i = 3 * j;
+        int x, y, z, cube, i;
+        mc_locate_triangle(r, s_pre, s_nib, s_cases, x, y, z, cube, i);
         const int order[3] = {i, i + 2, i + 1}; // Open3D emits (e[i], e[i+2], e[i+1])
         int32_t vid[3];
 #pragma unroll
@@ -496,6 +524,329 @@ __global__ __launch_bounds__(256) void k_mc_triangles(HvTable table, int n_units
             triangles[at * 3 + 2] = vid[2];
         }
     }
+}
+
+// ---- vertex-clustered mesh (hv_tsdf_extract_mesh_clustered; contract in include/hipvol.h) ----
+// A marching-cubes vertex belongs to the voxel that owns its edge, a cell is 2^ks voxels on a side and divides the unit: every
+// cluster lies inside one unit, its number is the unit's first cluster number plus the rank of its cell among the unit's occupied
+// cells (x-major), and all of it follows from the per-unit caches of k_mc_classify.  The full vertex and triangle arrays are never
+// written.
+//   k_cl_cells      (workgroup) the unit's edge masks -> the bitmask of its occupied cells (at most 512 bits) and their number
+//   rocPRIM scan    first cluster number of every unit
+//   k_cl_vertices   (wave) the unit's vertices in cluster-major order, 64 at a time: every lane evaluates mc_vertex_value of one
+//                   member, the first lane of each run of one cluster adds the run in lane order: plain float64 adds in the order
+//                   of the contract, one divide, no atomics on values
+//   k_cl_triangles  (workgroup) the walk of k_mc_triangles with cluster numbers for vertex ids; degenerate triples dropped, the
+//                   rest rotated smallest first; pass 1 counts the unit's survivors, pass 2 writes them behind the scanned base
+//   rocPRIM sort    two stable radix passes (on C, then on A and B packed), k_cl_flag + scan + k_cl_compact keep the first of
+//                   every run: the distinct triples in lexicographic order.  The order inside a unit's candidates (an LDS counter)
+//                   does not reach the result: the sort key is the whole triple.
+static constexpr int CL_OCC_WORDS = 8; // 512 cells of a unit at cell = 2 voxels
+
+// cell of voxel (x, y, z) inside its unit, x-major: ((x >> ks) * m + (y >> ks)) * m + (z >> ks), m = 16 >> ks cells per axis
+__device__ __forceinline__ int cl_cell(int x, int y, int z, int ks) {
+    const int ms = 4 - ks;
+    return ((((x >> ks) << ms) | (y >> ks)) << ms) | (z >> ks);
+}
+
+// number of occupied cells below `cell` in a unit's mask
+__device__ __forceinline__ int cl_rank(const unsigned long long *occ, int cell) {
+    int before = 0;
+    for (int w = 0; w < (cell >> 6); ++w) before += __popcll(occ[w]);
+    return before + __popcll(occ[cell >> 6] & ((1ull << (cell & 63)) - 1ull));
+}
+
+__global__ __launch_bounds__(MASK_WORDS) void k_cl_cells(int n_units, const unsigned long long *__restrict__ edge_mask,
+                                                         const unsigned long long *__restrict__ bases, int ks,
+                                                         unsigned long long *__restrict__ occ, int32_t *__restrict__ count) {
+    __shared__ uint32_t s_occ[2 * CL_OCC_WORDS];
+    const int idx = blockIdx.x;
+    if (idx >= n_units) return;
+    if (threadIdx.x < 2 * CL_OCC_WORDS) s_occ[threadIdx.x] = 0u;
+    if (idx == 0 && threadIdx.x == 0) count[n_units] = 0; // the scan's extra element
+    __syncthreads();
+    // (a unit without vertices was left by k_mc_classify before it wrote its words: they are not read)
+    if ((uint32_t)bases[idx + 1] != (uint32_t)bases[idx]) {
+        const int word = threadIdx.x, z = word / 12, quarter = word & 3;
+        unsigned long long m = edge_mask[(int64_t)idx * MASK_WORDS + word];
+        while (m) {
+            const int b = __builtin_ctzll(m);
+            m &= m - 1ull;
+            const int c = cl_cell(quarter * 4 + (b >> 4), b & 15, z, ks);
+            atomicOr(&s_occ[c >> 5], 1u << (c & 31));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < CL_OCC_WORDS) {
+        const unsigned long long w = (unsigned long long)s_occ[2 * threadIdx.x] | ((unsigned long long)s_occ[2 * threadIdx.x + 1] << 32);
+        occ[(int64_t)idx * CL_OCC_WORDS + threadIdx.x] = w;
+        int c = __popcll(w);
+#pragma unroll
+        for (int o = 1; o < CL_OCC_WORDS; o <<= 1) c += __shfl_xor(c, o);
+        if (threadIdx.x == 0) count[idx] = c;
+    }
+}
+
+// the bits of edge-mask word (z, axis, quarter) whose owner voxel lies in the cell at (x0, y0) of k voxels: x in [x0, x0 + k), y in [y0, y0 + k)
+__device__ __forceinline__ unsigned long long cl_inside(int quarter, int x0, int y0, int k) {
+    const unsigned long long ybits = (unsigned long long)(((1u << k) - 1u) << y0); // y0 .. y0 + k - 1 of one x
+    unsigned long long inside = 0ull;
+#pragma unroll
+    for (int xx = 0; xx < 4; ++xx) {
+        const int x = quarter * 4 + xx;
+        if (x >= x0 && x < x0 + k) inside |= ybits << (16 * xx);
+    }
+    return inside;
+}
+
+// One WAVE per unit.  The unit's vertices are taken in CLUSTER-MAJOR order - clusters ascending, inside a cluster ascending vertex
+// rank, which is the order of the contract's sums - 64 at a time: item i belongs to the cluster whose exclusive member count is the
+// last one <= i (binary search over the per-cluster prefix), and is that cluster's (i - prefix)-th member, found by walking the
+// edge-mask words that meet the cell in word order.  Every lane evaluates its vertex (all their loads in flight together) and puts
+// the six float64 values into LDS; the first lane of every run of equal clusters then adds its run in lane order - plain adds, the
+// partial sum of a cluster that continues in the next 64 carried in LDS - and the lane that ends a cluster divides and writes.
+// At cell 16 the unit is ONE cluster and member m is the unit's vertex m: found through the word prefixes, as k_mc_vertices does.
+template <typename OUT>
+__global__ __launch_bounds__(64) void k_cl_vertices(HvTable table, const char *__restrict__ pool, int n_units,
+                                                     const unsigned long long *__restrict__ edge_mask,
+                                                     const uint32_t *__restrict__ word_prefix,
+                                                     const unsigned long long *__restrict__ bases,
+                                                     const unsigned long long *__restrict__ occ, const int32_t *__restrict__ cbase, int ks,
+                                                     HvMcParams M, OUT *__restrict__ vertices, OUT *__restrict__ colors,
+                                                     int32_t *__restrict__ vertex_cluster) {
+    constexpr int MAX_CELLS = 64 * CL_OCC_WORDS;
+    __shared__ unsigned long long s_mask[MASK_WORDS];
+    __shared__ uint32_t s_prefix[MASK_WORDS + 1];
+    __shared__ unsigned long long s_occ[CL_OCC_WORDS];
+    __shared__ uint16_t s_cell[MAX_CELLS];     // cell of the unit's j-th cluster
+    __shared__ uint32_t s_first[MAX_CELLS + 1]; // members of the clusters before j
+    __shared__ double s_val[HV_WAVE][6];
+    __shared__ double s_carry[2][6]; // read [chunk & 1], written [(chunk + 1) & 1]: the reader and the writer of one chunk never share a slot
+    const int idx = blockIdx.x;
+    if (idx >= n_units) return;
+    const int lane = threadIdx.x;
+    const int cb = cbase[idx], n_clusters = cbase[idx + 1] - cb;
+    if (n_clusters == 0) return;
+    const int64_t vbase = (int64_t)(uint32_t)bases[idx];
+    const int total = (int)((uint32_t)bases[idx + 1] - (uint32_t)vbase);
+    for (int w = lane; w < MASK_WORDS; w += HV_WAVE) {
+        s_mask[w] = edge_mask[(int64_t)idx * MASK_WORDS + w];
+        s_prefix[w] = word_prefix[(int64_t)idx * MASK_WORDS + w];
+    }
+    if (lane == 0) s_prefix[MASK_WORDS] = (uint32_t)total;
+    if (lane < CL_OCC_WORDS) s_occ[lane] = occ[(int64_t)idx * CL_OCC_WORDS + lane];
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const int k = 1 << ks, ms = 4 - ks, mm = (1 << ms) - 1;
+    // clusters j = lane * per .. lane * per + per - 1: their cells and member counts, then the exclusive prefix of the counts
+    const int per = (n_clusters + HV_WAVE - 1) / HV_WAVE; // <= 8
+    uint32_t mine = 0;
+    for (int t = 0; t < per; ++t) {
+        const int j = lane * per + t;
+        if (j >= n_clusters) break;
+        int w = 0, left = j; // the j-th occupied cell of the unit
+        for (; w < CL_OCC_WORDS - 1; ++w) {
+            const int c = __popcll(s_occ[w]);
+            if (left < c) break;
+            left -= c;
+        }
+        const int cell = w * 64 + hv_nth_set_bit(s_occ[w], left);
+        const int x0 = (cell >> (2 * ms)) << ks, y0 = ((cell >> ms) & mm) << ks, z0 = (cell & mm) << ks;
+        uint32_t members = (uint32_t)total; // (cell 16: the whole unit)
+        if (ks < 4) {
+            members = 0;
+            for (int z = z0; z < z0 + k; ++z)
+                for (int axis = 0; axis < 3; ++axis)
+                    for (int quarter = x0 >> 2; quarter <= (x0 + k - 1) >> 2; ++quarter)
+                        members += (uint32_t)__popcll(s_mask[z * 12 + axis * 4 + quarter] & cl_inside(quarter, x0, y0, k));
+        }
+        s_cell[j] = (uint16_t)cell;
+        s_first[j] = mine; // (relative to the lane's first cluster, for now)
+        mine += members;
+    }
+    uint32_t incl = mine;
+#pragma unroll
+    for (int o = 1; o < HV_WAVE; o <<= 1) {
+        const uint32_t up = __shfl_up(incl, o);
+        if (lane >= o) incl += up;
+    }
+    for (int t = 0; t < per; ++t) {
+        const int j = lane * per + t;
+        if (j < n_clusters) s_first[j] += incl - mine;
+    }
+    if (lane == 0) s_first[n_clusters] = (uint32_t)total;
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    int32_t ux, uy, uz;
+    hv_unpack_key(table.block_keys[idx], ux, uy, uz);
+    for (int base = 0; base < total; base += HV_WAVE) {
+        const int i = base + lane;
+        const bool live = i < total;
+        int j = -1, m = 0;
+        if (live) {
+            int lo = 0, hi = n_clusters; // s_first[lo] <= i < s_first[hi]
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (s_first[mid] <= (uint32_t)i) lo = mid; else hi = mid;
+            }
+            j = lo;
+            m = i - (int)s_first[j];
+            const int cell = s_cell[j];
+            const int x0 = (cell >> (2 * ms)) << ks, y0 = ((cell >> ms) & mm) << ks, z0 = (cell & mm) << ks;
+            // member m of the cell: the words that meet it in word order (mc_word: z, axis, quarter), their bits in bit order
+            int left = m, word = 0, b = 0;
+            bool found = false;
+            if (ks == 4) { // the word holding vertex m of the unit: the last one whose exclusive prefix is <= m
+                int wl = 0, wh = MASK_WORDS;
+                while (wh - wl > 1) {
+                    const int mid = (wl + wh) >> 1;
+                    if (s_prefix[mid] <= (uint32_t)m) wl = mid; else wh = mid;
+                }
+                word = wl;
+                b = hv_nth_set_bit(s_mask[word], m - (int)s_prefix[word]);
+                found = true;
+            }
+            for (int z = z0; z < z0 + k && !found; ++z)
+                for (int axis = 0; axis < 3 && !found; ++axis)
+                    for (int quarter = x0 >> 2; quarter <= (x0 + k - 1) >> 2; ++quarter) {
+                        const unsigned long long in = s_mask[z * 12 + axis * 4 + quarter] & cl_inside(quarter, x0, y0, k);
+                        const int c = __popcll(in);
+                        if (left < c) {
+                            word = z * 12 + axis * 4 + quarter;
+                            b = hv_nth_set_bit(in, left);
+                            found = true;
+                            break;
+                        }
+                        left -= c;
+                    }
+            const int axis = (word % 12) >> 2;
+            const int lin = ((word / 12) * 4 + (word & 3)) * 64 + b;
+            double pt[3], col[3];
+            mc_vertex_value(table, pool, idx, ux, uy, uz, axis, lin, M, pt, col);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                s_val[lane][c] = pt[c];
+                s_val[lane][3 + c] = col[c];
+            }
+            const int r = (int)s_prefix[word] + __popcll(s_mask[word] & ((1ull << b) - 1ull));
+            vertex_cluster[vbase + r] = cb + j;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        // the first lane of a run of one cluster adds the run in lane order, behind what the previous 64 left of that cluster
+        const int parity = (base / HV_WAVE) & 1;
+        if (live && (lane == 0 || m == 0)) {
+            const int size = (int)(s_first[j + 1] - s_first[j]);
+            const int run = min(size - m, HV_WAVE - lane);
+            double sum[6];
+#pragma unroll
+            for (int c = 0; c < 6; ++c) sum[c] = m == 0 ? s_val[lane][c] : s_carry[parity][c] + s_val[lane][c];
+            for (int t = 1; t < run; ++t)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) sum[c] += s_val[lane + t][c];
+            if (m + run == size) {
+                const double cnt = (double)size;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    vertices[(int64_t)(cb + j) * 3 + c] = (OUT)(sum[c] / cnt);
+                    colors[(int64_t)(cb + j) * 3 + c] = (OUT)(sum[3 + c] / cnt);
+                }
+            } else { // (only the last run of the 64 can be cut)
+#pragma unroll
+                for (int c = 0; c < 6; ++c) s_carry[parity ^ 1][c] = sum[c];
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+
+// FILL = false: count[unit] = the unit's non-degenerate triangles (units without triangles keep the 0 the host wrote).
+// FILL = true: their rotated triples, A and B packed as A << bits | B, behind base[unit].
+template <bool FILL>
+__global__ __launch_bounds__(256) void k_cl_triangles(HvTable table, int n_units, const uint8_t *__restrict__ cases,
+                                                       const unsigned long long *__restrict__ bases,
+                                                       const unsigned long long *__restrict__ occ, const int32_t *__restrict__ cbase, int ks,
+                                                       int32_t *__restrict__ count, const int32_t *__restrict__ base, int bits,
+                                                       unsigned long long *__restrict__ out_ab, uint32_t *__restrict__ out_c) {
+    __shared__ int s_nbr[8];
+    __shared__ int32_t s_cb[8];
+    __shared__ unsigned long long s_occ[8][CL_OCC_WORDS];
+    __shared__ int s_wave[4];
+    __shared__ uint8_t s_tcnt[256];
+    __shared__ signed char s_tt[256 * 16];
+    __shared__ uint4 s_cases[256];
+    __shared__ unsigned long long s_nib[256];
+    __shared__ int s_pre[257];
+    __shared__ int s_kept;
+    const int idx = blockIdx.x;
+    if (idx >= n_units) return;
+    const int total = (int)((bases[idx + 1] >> 32) - (bases[idx] >> 32));
+    if (total == 0) return;
+    load_neighbours(table, idx, s_nbr);
+    s_tcnt[threadIdx.x] = c_tri_count[threadIdx.x];
+    ((uint4 *)s_tt)[threadIdx.x] = ((const uint4 *)&c_tri_table[0][0])[threadIdx.x];
+    const uint4 pk = ((const uint4 *)(cases + (int64_t)idx * HV_TSDF_RRR))[threadIdx.x];
+    s_cases[threadIdx.x] = pk;
+    if (threadIdx.x == 0) s_kept = 0;
+    __syncthreads();
+    if (threadIdx.x < 8) s_cb[threadIdx.x] = s_nbr[threadIdx.x] >= 0 ? cbase[s_nbr[threadIdx.x]] : 0;
+    if (threadIdx.x < 8 * CL_OCC_WORDS) {
+        const int nb = s_nbr[threadIdx.x >> 3];
+        s_occ[threadIdx.x >> 3][threadIdx.x & 7] = nb >= 0 ? occ[(int64_t)nb * CL_OCC_WORDS + (threadIdx.x & 7)] : 0ull;
+    }
+    mc_triangle_ranks(pk, s_tcnt, s_nib, s_wave, s_pre);
+    int kept = 0;
+    for (int r = threadIdx.x; r < total; r += 256) {
+        int x, y, z, cube, i;
+        mc_locate_triangle(r, s_pre, s_nib, s_cases, x, y, z, cube, i);
+        const int order[3] = {i, i + 2, i + 1}; // Open3D emits (e[i], e[i+2], e[i+1])
+        int32_t cid[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            int n, axis, lin;
+            edge_owner(x, y, z, s_tt[cube * 16 + order[k]], n, axis, lin);
+            cid[k] = s_cb[n] + cl_rank(s_occ[n], cl_cell((lin >> 4) & 15, lin & 15, lin >> 8, ks));
+        }
+        const int32_t A = cid[0], B = cid[1], C = cid[2];
+        if (A == B || B == C || A == C) continue;
+        if (!FILL) {
+            ++kept;
+        } else {
+            // smallest number first, orientation kept
+            const int32_t a = A < B ? (A < C ? A : C) : (B < C ? B : C);
+            const int32_t b = a == A ? B : a == B ? C : A;
+            const int32_t c = a == A ? C : a == B ? A : B;
+            const int64_t at = (int64_t)base[idx] + atomicAdd(&s_kept, 1);
+            out_ab[at] = ((unsigned long long)(uint32_t)a << bits) | (unsigned long long)(uint32_t)b;
+            out_c[at] = (uint32_t)c;
+        }
+    }
+    if (!FILL) {
+#pragma unroll
+        for (int o = 1; o < HV_WAVE; o <<= 1) kept += __shfl_xor(kept, o);
+        if (hv_lane_id() == 0 && kept) atomicAdd(&s_kept, kept);
+        __syncthreads();
+        if (threadIdx.x == 0) count[idx] = s_kept;
+    }
+}
+
+// flag[i] = the sorted triple i differs from its predecessor (flag[n] = 0: the scan's extra element)
+__global__ __launch_bounds__(256) void k_cl_flag(const unsigned long long *__restrict__ ab, const uint32_t *__restrict__ c, int64_t n,
+                                                  int32_t *__restrict__ flag) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > n) return;
+    flag[i] = i < n && (i == 0 || ab[i] != ab[i - 1] || c[i] != c[i - 1]) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void k_cl_compact(const unsigned long long *__restrict__ ab, const uint32_t *__restrict__ c, int64_t n,
+                                                     const int32_t *__restrict__ pos, int bits, int32_t *__restrict__ triangles) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || pos[i + 1] == pos[i]) return;
+    const int64_t at = pos[i];
+    triangles[at * 3 + 0] = (int32_t)(ab[i] >> bits);
+    triangles[at * 3 + 1] = (int32_t)(ab[i] & ((1ull << bits) - 1ull));
+    triangles[at * 3 + 2] = (int32_t)c[i];
 }
 
 // ScalableTSDFVolume::ExtractPointCloud: a voxel (weight != 0, tsdf in [-0.98, 0.98)) and its +x / +y / +z neighbour of the
@@ -738,23 +1089,17 @@ static int unit_masks_compute(hv_volume *v, int n, HvUnitMasks *out) {
     return HV_OK;
 }
 
-static int mesh_compute(hv_volume *v, bool f32) {
-    int rc = upload_tables(v->device);
-    if (rc != HV_OK) return rc;
-    int64_t nb = 0;
-    rc = hv_num_blocks(v, &nb);
-    if (rc != HV_OK) return rc;
-    v->mesh_cache_version = 0;
-    v->points_cache_version = 0; // shares out_a
-    v->mesh_cache_nv = v->mesh_cache_nt = 0;
-    if (nb == 0) {
-        v->mesh_cache_version = v->content_version;
-        return HV_OK;
-    }
-    const int n = (int)nb;
+// The per-unit marching-cubes caches for the volume's current contents: masks, classification (only where something changed), the
+// scan of the per-unit counts into out_c, and the totals.  Neither out_a nor out_b is touched.
+struct HvMcCache {
+    unsigned long long *edge_mask, *bases; // bases [n + 1]: vertices in the low 32 bits, triangles in the high 32 bits of one word per unit
+    uint32_t *word_prefix;
+    uint8_t *cases;
+};
+static int mesh_classify(hv_volume *v, int n, HvMcCache *C, int64_t *nv, int64_t *nt) {
     hv_profile_begin(v); // measurement hook: column masks + classify + scan
     HvUnitMasks UM;
-    rc = unit_masks_compute(v, n, &UM);
+    int rc = unit_masks_compute(v, n, &UM);
     if (rc != HV_OK) return rc;
     // per-unit cache: [edge_mask cap*192 u64][counts cap+1 u64][word_prefix cap*192 u32][cases cap*4096 u8]; scratch: [bases n+1 u64]
     // counts / bases: vertices in the low 32 bits, triangles in the high 32 bits of one word per unit
@@ -784,8 +1129,33 @@ static int mesh_compute(hv_volume *v, bool f32) {
     unsigned long long total64 = 0ull;
     HV_HIP(hipMemcpyAsync(&total64, bases + n, sizeof(total64), hipMemcpyDeviceToHost, v->stream));
     HV_HIP(hipStreamSynchronize(v->stream));
-    const int64_t totals[2] = {(int64_t)(uint32_t)total64, (int64_t)(total64 >> 32)};
-    const int64_t nv = totals[0], nt = totals[1];
+    *nv = (int64_t)(uint32_t)total64;
+    *nt = (int64_t)(total64 >> 32);
+    *C = HvMcCache{edge_mask, bases, word_prefix, cases};
+    return HV_OK;
+}
+
+static int mesh_compute(hv_volume *v, bool f32) {
+    int rc = upload_tables(v->device);
+    if (rc != HV_OK) return rc;
+    int64_t nb = 0;
+    rc = hv_num_blocks(v, &nb);
+    if (rc != HV_OK) return rc;
+    v->mesh_cache_version = 0;
+    v->points_cache_version = 0; // shares out_a
+    v->mesh_cache_nv = v->mesh_cache_nt = 0;
+    if (nb == 0) {
+        v->mesh_cache_version = v->content_version;
+        return HV_OK;
+    }
+    const int n = (int)nb;
+    HvMcCache C;
+    int64_t nv = 0, nt = 0;
+    rc = mesh_classify(v, n, &C, &nv, &nt);
+    if (rc != HV_OK) return rc;
+    unsigned long long *edge_mask = C.edge_mask, *bases = C.bases;
+    uint32_t *word_prefix = C.word_prefix;
+    uint8_t *cases = C.cases;
     if (nv > 0 || nt > 0) {
         rc = hv_ensure_buffer(v, &v->out_a, &v->out_a_bytes, (f32 ? sizeof(float) : sizeof(double)) * 6 * (size_t)std::max<int64_t>(nv, 1));
         if (rc != HV_OK) return rc;
@@ -851,6 +1221,181 @@ int hv_tsdf_extract_mesh(hv_volume *v, double *vertices, double *vertex_colors, 
 int hv_tsdf_extract_mesh_f32(hv_volume *v, float *vertices, float *vertex_colors, int64_t cap_vertices,
                              int32_t *triangles, int64_t cap_triangles, int64_t *n_vertices, int64_t *n_triangles) {
     return extract_mesh_as<float>(v, vertices, vertex_colors, cap_vertices, triangles, cap_triangles, n_vertices, n_triangles, "hv_tsdf_extract_mesh_f32");
+}
+
+// One D2H of a scan's last element (waits for the stream).
+static int fetch_i32(hv_volume *v, const int32_t *d, int64_t *out) {
+    int32_t h = 0;
+    HV_HIP(hipMemcpyAsync(&h, d, sizeof(h), hipMemcpyDeviceToHost, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    *out = h;
+    return HV_OK;
+}
+
+// The clustered mesh of the volume's current contents at cell = 1 << ks voxels into cl_verts ([vertices 3 nv][colours 3 nv] OUT,
+// [vertex_cluster n_full i32]) and cl_tris, recorded under (content_version, cell, type): a count-then-fill pair computes once.
+// Results and scratch are the clustered mesh's own (cl_*): the full mesh in out_a / out_b and the point cloud stand.
+// The host waits four times - for the totals of the classification, the clusters, the candidates and the distinct triples: each sizes
+// the next buffer.  Memory kept until hv_destroy (grown on demand, 25 % headroom): cl_units 80 B per unit, cl_verts 48 (24 as float32)
+// B per cluster + 4 B per full vertex (the map is always written: the size query does the work and does not know whether the fill
+// will ask for it), cl_tris 12 B per triangle, cl_tmp 32 B per candidate triple (both sides of the two sort passes, flags, positions).
+static int cluster_compute(hv_volume *v, int ks, bool f32) {
+    int rc = upload_tables(v->device);
+    if (rc != HV_OK) return rc;
+    int64_t nb = 0;
+    rc = hv_num_blocks(v, &nb);
+    if (rc != HV_OK) return rc;
+    v->cl_version = 0;
+    v->cl_nv = v->cl_nt = v->cl_nfull = 0;
+    v->cl_cell = 1 << ks;
+    v->cl_f32 = f32;
+    const int n = (int)nb;
+    HvMcCache C;
+    int64_t n_full = 0, nt_full = 0;
+    if (n > 0) {
+        rc = mesh_classify(v, n, &C, &n_full, &nt_full);
+        if (rc != HV_OK) return rc;
+    }
+    if (n_full == 0) { // an empty map, or one without a surface
+        v->cl_version = v->content_version;
+        return HV_OK;
+    }
+    // per-unit scratch: [occ n*8 u64][cluster count n+1][cluster base n+1][triangle count n+1][triangle base n+1] i32
+    const size_t n1 = (size_t)n + 1;
+    rc = hv_ensure_buffer(v, &v->cl_units, &v->cl_units_bytes, sizeof(uint64_t) * CL_OCC_WORDS * (size_t)n + sizeof(int32_t) * 4 * n1);
+    if (rc != HV_OK) return rc;
+    unsigned long long *occ = (unsigned long long *)v->cl_units;
+    int32_t *ccount = (int32_t *)(occ + CL_OCC_WORDS * (size_t)n), *cbase = ccount + n1, *tcount = cbase + n1, *tbase = tcount + n1;
+    hv_profile_begin(v); // measurement hooks, one per stage: cells + scan | cluster vertices | candidate count + scan | candidates, sorts, flags + scan | compaction
+    hipLaunchKernelGGL(k_cl_cells, dim3(n), dim3(MASK_WORDS), 0, v->stream, n, C.edge_mask, C.bases, ks, occ, ccount);
+    HV_HIP(hipGetLastError());
+    rc = exclusive_scan_i32(v, ccount, cbase, n + 1);
+    if (rc != HV_OK) return rc;
+    hv_profile_end(v, n);
+    int64_t nv = 0;
+    rc = fetch_i32(v, cbase + n, &nv);
+    if (rc != HV_OK) return rc;
+    const size_t elem = f32 ? sizeof(float) : sizeof(double);
+    rc = hv_ensure_buffer(v, &v->cl_verts, &v->cl_verts_bytes, elem * 6 * (size_t)nv + sizeof(int32_t) * (size_t)n_full);
+    if (rc != HV_OK) return rc;
+    int32_t *d_map = (int32_t *)((char *)v->cl_verts + elem * 6 * (size_t)nv);
+    HvMcParams M{v->cfg.voxel_size, v->cfg.voxel_size * 0.5};
+    hv_profile_begin(v);
+    if (f32) {
+        float *d_vert = (float *)v->cl_verts;
+        hipLaunchKernelGGL(k_cl_vertices<float>, dim3(n), dim3(64), 0, v->stream, v->table, (const char *)v->pool, n, C.edge_mask, C.word_prefix,
+                           C.bases, occ, cbase, ks, M, d_vert, d_vert + 3 * nv, d_map);
+    } else {
+        double *d_vert = (double *)v->cl_verts;
+        hipLaunchKernelGGL(k_cl_vertices<double>, dim3(n), dim3(64), 0, v->stream, v->table, (const char *)v->pool, n, C.edge_mask, C.word_prefix,
+                           C.bases, occ, cbase, ks, M, d_vert, d_vert + 3 * nv, d_map);
+    }
+    hv_profile_end(v, 0);
+    HV_HIP(hipGetLastError());
+    int64_t n_cand = 0, nt = 0;
+    if (nt_full > 0) {
+        hv_profile_begin(v);
+        HV_HIP(hipMemsetAsync(tcount, 0, sizeof(int32_t) * n1, v->stream));
+        hipLaunchKernelGGL(k_cl_triangles<false>, dim3(n), dim3(256), 0, v->stream, v->table, n, (const uint8_t *)C.cases, C.bases, occ, cbase, ks,
+                           tcount, (const int32_t *)nullptr, 0, (unsigned long long *)nullptr, (uint32_t *)nullptr);
+        HV_HIP(hipGetLastError());
+        rc = exclusive_scan_i32(v, tcount, tbase, n + 1);
+        if (rc != HV_OK) return rc;
+        hv_profile_end(v, 0);
+        rc = fetch_i32(v, tbase + n, &n_cand);
+        if (rc != HV_OK) return rc;
+    }
+    if (n_cand > 0) {
+        int bits = 1; // of a cluster number
+        while (((int64_t)1 << bits) < nv) ++bits;
+        // candidates: [ab 2 x n_cand u64][c 2 x n_cand u32][flag n_cand+1][pos n_cand+1] i32
+        const size_t nc = (size_t)n_cand;
+        rc = hv_ensure_buffer(v, &v->cl_tmp, &v->cl_tmp_bytes, sizeof(uint64_t) * 2 * nc + sizeof(uint32_t) * 2 * nc + sizeof(int32_t) * 2 * (nc + 1));
+        if (rc != HV_OK) return rc;
+        unsigned long long *ab0 = (unsigned long long *)v->cl_tmp, *ab1 = ab0 + nc;
+        uint32_t *c0 = (uint32_t *)(ab1 + nc), *c1 = c0 + nc;
+        int32_t *flag = (int32_t *)(c1 + nc), *pos = flag + nc + 1;
+        hv_profile_begin(v);
+        hipLaunchKernelGGL(k_cl_triangles<true>, dim3(n), dim3(256), 0, v->stream, v->table, n, (const uint8_t *)C.cases, C.bases, occ, cbase, ks,
+                           (int32_t *)nullptr, (const int32_t *)tbase, bits, ab0, c0);
+        HV_HIP(hipGetLastError());
+        // lexicographic order of (A, B, C): a stable pass on C, then a stable pass on A << bits | B
+        size_t b1 = 0, b2 = 0;
+        HV_HIP(rocprim::radix_sort_pairs(nullptr, b1, c0, c1, ab0, ab1, nc, 0, (unsigned)bits, v->stream));
+        HV_HIP(rocprim::radix_sort_pairs(nullptr, b2, ab1, ab0, c1, c0, nc, 0, (unsigned)(2 * bits), v->stream));
+        rc = hv_ensure_buffer(v, &v->sort_tmp, &v->sort_tmp_bytes, std::max(b1, b2));
+        if (rc != HV_OK) return rc;
+        b1 = b2 = v->sort_tmp_bytes;
+        HV_HIP(rocprim::radix_sort_pairs(v->sort_tmp, b1, c0, c1, ab0, ab1, nc, 0, (unsigned)bits, v->stream));
+        HV_HIP(rocprim::radix_sort_pairs(v->sort_tmp, b2, ab1, ab0, c1, c0, nc, 0, (unsigned)(2 * bits), v->stream));
+        hipLaunchKernelGGL(k_cl_flag, dim3((unsigned)((n_cand + 256) / 256)), dim3(256), 0, v->stream, ab0, c0, n_cand, flag);
+        HV_HIP(hipGetLastError());
+        rc = exclusive_scan_i32(v, flag, pos, (int)(n_cand + 1));
+        if (rc != HV_OK) return rc;
+        hv_profile_end(v, 0);
+        rc = fetch_i32(v, pos + n_cand, &nt);
+        if (rc != HV_OK) return rc;
+        rc = hv_ensure_buffer(v, &v->cl_tris, &v->cl_tris_bytes, sizeof(int32_t) * 3 * (size_t)nt);
+        if (rc != HV_OK) return rc;
+        hv_profile_begin(v);
+        hipLaunchKernelGGL(k_cl_compact, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, v->stream, ab0, c0, n_cand, (const int32_t *)pos, bits,
+                           (int32_t *)v->cl_tris);
+        hv_profile_end(v, 0);
+        HV_HIP(hipGetLastError());
+    }
+    v->cl_nv = nv;
+    v->cl_nt = nt;
+    v->cl_nfull = n_full;
+    v->cl_version = v->content_version;
+    return HV_OK;
+}
+
+} // extern "C"
+template <typename OUT>
+static int extract_clustered_as(hv_volume *v, int32_t cell, OUT *vertices, OUT *vertex_colors, int64_t cap_vertices, int32_t *triangles,
+                                int64_t cap_triangles, int32_t *vertex_cluster, int64_t cap_full_vertices, int64_t *n_vertices,
+                                int64_t *n_triangles, int64_t *n_full_vertices, const char *who) {
+    HV_REQUIRE(v != nullptr && n_vertices != nullptr && n_triangles != nullptr && n_full_vertices != nullptr, HV_ERR_INVALID, "%s: null argument", who);
+    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", who);
+    HV_REQUIRE(cell == 2 || cell == 4 || cell == 8 || cell == 16, HV_ERR_INVALID, "%s: cell must be 2, 4, 8 or 16 voxels, got %d", who, (int)cell);
+    HV_REQUIRE(v->cfg.block_size == HV_TSDF_R, HV_ERR_INVALID, "%s: the unit resolution must be %d", who, HV_TSDF_R);
+    HV_HIP(hipSetDevice(v->device));
+    constexpr bool f32 = sizeof(OUT) == sizeof(float);
+    if (v->cl_version != v->content_version || v->cl_cell != cell || v->cl_f32 != f32) {
+        const int rc = cluster_compute(v, cell == 2 ? 1 : cell == 4 ? 2 : cell == 8 ? 3 : 4, f32);
+        if (rc != HV_OK) return rc;
+    }
+    *n_vertices = v->cl_nv;
+    *n_triangles = v->cl_nt;
+    *n_full_vertices = v->cl_nfull;
+    if (vertices == nullptr || vertex_colors == nullptr) return HV_OK; // the size query
+    // (a caller's zero-row array may have no address: a mesh of clusters no triangle joins has vertices and no triangle)
+    const int64_t nv = std::min<int64_t>(v->cl_nv, cap_vertices), nt = triangles != nullptr ? std::min<int64_t>(v->cl_nt, cap_triangles) : 0;
+    const int64_t nm = vertex_cluster != nullptr ? std::min<int64_t>(v->cl_nfull, cap_full_vertices) : 0;
+    const OUT *d_vert = (const OUT *)v->cl_verts, *d_col = d_vert + 3 * v->cl_nv;
+    if (nv > 0) {
+        HV_HIP(hipMemcpyAsync(vertices, d_vert, sizeof(OUT) * 3 * nv, hipMemcpyDefault, v->stream));
+        HV_HIP(hipMemcpyAsync(vertex_colors, d_col, sizeof(OUT) * 3 * nv, hipMemcpyDefault, v->stream));
+    }
+    if (nt > 0) HV_HIP(hipMemcpyAsync(triangles, v->cl_tris, sizeof(int32_t) * 3 * nt, hipMemcpyDefault, v->stream));
+    if (nm > 0) HV_HIP(hipMemcpyAsync(vertex_cluster, d_col + 3 * v->cl_nv, sizeof(int32_t) * nm, hipMemcpyDefault, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+
+extern "C" {
+int hv_tsdf_extract_mesh_clustered(hv_volume *v, int32_t cell, double *vertices, double *vertex_colors, int64_t cap_vertices,
+                                   int32_t *triangles, int64_t cap_triangles, int32_t *vertex_cluster, int64_t cap_full_vertices,
+                                   int64_t *n_vertices, int64_t *n_triangles, int64_t *n_full_vertices) {
+    return extract_clustered_as<double>(v, cell, vertices, vertex_colors, cap_vertices, triangles, cap_triangles, vertex_cluster, cap_full_vertices,
+                                        n_vertices, n_triangles, n_full_vertices, "hv_tsdf_extract_mesh_clustered");
+}
+
+int hv_tsdf_extract_mesh_clustered_f32(hv_volume *v, int32_t cell, float *vertices, float *vertex_colors, int64_t cap_vertices,
+                                       int32_t *triangles, int64_t cap_triangles, int32_t *vertex_cluster, int64_t cap_full_vertices,
+                                       int64_t *n_vertices, int64_t *n_triangles, int64_t *n_full_vertices) {
+    return extract_clustered_as<float>(v, cell, vertices, vertex_colors, cap_vertices, triangles, cap_triangles, vertex_cluster, cap_full_vertices,
+                                       n_vertices, n_triangles, n_full_vertices, "hv_tsdf_extract_mesh_clustered_f32");
 }
 
 static int points_compute(hv_volume *v, bool f32) {

@@ -65,6 +65,10 @@ class Parameters:
     # them in kDenseMappingDtypeVertices / kDenseMappingDtypeColors (float32: what the viewer casts them to) - the float64 values
     # rounded once on the device (hv_tsdf_extract_mesh_f32), a third fewer bytes per tick.  Saved files always come from float64.
     kVolumetricIntegrationTsdfOutputInDenseMappingDtype = False
+    # TSDF output ticks: 0 = the full mesh (extract_triangle_mesh); 2 / 4 / 8 / 16 = the mesh simplified by vertex clustering on the
+    # device with cells of that many voxels (extract_simplified_mesh): far fewer triangles for the viewer to redraw and far fewer
+    # bytes per tick.  Saved files always hold the full mesh.
+    kVolumetricIntegrationTsdfOutputMeshCell = 0
 
 
 def get_parameters():

@@ -136,7 +136,11 @@ class VolumetricIntegratorTsdf(VolumetricIntegratorBase):
                                 and self.dtype_vertices == np.float32 and self.dtype_colors == np.float32):
                             kw["dtype"] = np.float32  # (opt-in: float64 rounded once on the device instead of by the consumer)
                         if Parameters.kVolumetricIntegrationTsdfExtractMesh:
-                            mesh_out = VolumetricIntegrationMesh(self.volume.extract_triangle_mesh(**kw))
+                            cell = int(getattr(Parameters, "kVolumetricIntegrationTsdfOutputMeshCell", 0) or 0)
+                            if cell:  # a lighter mesh for the viewer (SAVE above always writes the full one)
+                                mesh_out = VolumetricIntegrationMesh(self.volume.extract_simplified_mesh(cell=cell, **kw))
+                            else:
+                                mesh_out = VolumetricIntegrationMesh(self.volume.extract_triangle_mesh(**kw))
                         else:
                             pc_out = VolumetricIntegrationPointCloud(self.volume.extract_point_cloud(**kw))
                         last_output = VolumetricIntegrationOutput(ttype, self.last_integrated_id, pc_out, mesh_out)

@@ -1607,10 +1607,12 @@ class RGBDImage:
 
 
 class TriangleMesh:
-    def __init__(self, vertices, triangles, vertex_colors):
+    def __init__(self, vertices, triangles, vertex_colors, vertex_cluster=None):
         self.vertices = vertices
         self.triangles = triangles
         self.vertex_colors = vertex_colors
+        if vertex_cluster is not None:  # extract_simplified_mesh(vertex_map=True): int32 [V], full vertex -> simplified vertex
+            self.vertex_cluster = vertex_cluster
         self.vertex_normals = np.zeros((0, 3), np.float64)  # compute_vertex_normals() is not called by pySLAM
 
 
@@ -1833,6 +1835,31 @@ class ScalableTSDFVolume(_Volume):
         if nv.value or nt.value:
             L.check(fn(self._h, L.ptr(verts), L.ptr(cols), nv.value, L.ptr(tris), nt.value, ctypes.byref(nv), ctypes.byref(nt)))
         return TriangleMesh(verts, tris, cols)
+
+    SIMPLIFIED_MESH_CELLS = (2, 4, 8, 16)
+
+    def extract_simplified_mesh(self, cell=4, device=False, dtype=None, vertex_map=False):
+        """The mesh of extract_triangle_mesh() simplified by vertex clustering on the device (include/hipvol.h,
+        hv_tsdf_extract_mesh_clustered): one vertex per cube of `cell` voxels (2, 4, 8 or 16) that holds full-mesh vertices - the mean
+        of their positions and colours - and the distinct non-degenerate triangles between those, sorted.  For viewers, links and
+        files that do not want millimetre triangles: the full mesh is neither written nor copied.  device and dtype as in
+        extract_triangle_mesh.  vertex_map=True: the mesh also carries .vertex_cluster, int32 [V] - for every vertex of
+        extract_triangle_mesh() the number of its simplified vertex (to carry per-vertex data such as label_mesh results over).
+        Normals are not part of the result: sample_points(mesh.vertices, gradient=True) gives them.  The map is only read."""
+        if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or int(cell) not in self.SIMPLIFIED_MESH_CELLS:
+            raise ValueError(f"extract_simplified_mesh: cell must be one of {self.SIMPLIFIED_MESH_CELLS} voxels, got {cell!r}")
+        cell = int(cell)
+        dt = self._out_dtype(dtype)
+        fn = self._lib.hv_tsdf_extract_mesh_clustered if dt == np.float64 else self._lib.hv_tsdf_extract_mesh_clustered_f32
+        nv, nt, nf = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+        L.check(fn(self._h, cell, None, None, 0, None, 0, None, 0, ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(nf)))
+        out = self._results({"verts": ((nv.value, 3), dt), "cols": ((nv.value, 3), dt), "tris": ((nt.value, 3), np.int32),
+                             "map": ((nf.value,), np.int32) if vertex_map else None}, device)
+        verts, cols, tris, vmap = out["verts"], out["cols"], out["tris"], out["map"]
+        if nv.value or nt.value:
+            L.check(fn(self._h, cell, L.ptr(verts), L.ptr(cols), nv.value, L.ptr(tris), nt.value, L.ptr(vmap), nf.value if vertex_map else 0,
+                       ctypes.byref(nv), ctypes.byref(nt), ctypes.byref(nf)))
+        return TriangleMesh(verts, tris, cols, vertex_cluster=vmap)
 
     def extract_point_cloud(self, normals=False, device=False, dtype=None):
         """o3d's extract_point_cloud().  normals=True also computes the per-point normals Open3D attaches (GetNormalAt: the
