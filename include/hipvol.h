@@ -123,7 +123,15 @@ int hv_integrate_rgbd_points_batch(hv_volume *v, const void *depth, int32_t dept
 
 /* cv2.remap(src, map_x, map_y, INTER_LINEAR | INTER_NEAREST, BORDER_CONSTANT 0) as pySLAM's undistortion
  * uses it (volumetric_integrator_base.py:1017-1043).  src_kind 0: uint8 (channels interleaved), 1: float32,
- * 2: int32 (nearest only); maps float32 [H,W]; all arrays live at `loc`.  OpenCV semantics restated, unpinned. */
+ * 2: int32 (nearest only); maps float32 [H,W] - the image's own height and width, the caller checks that; all arrays live at
+ * `loc`.  OpenCV semantics restated, unpinned (tests/remap_reference.py states them once more, tests/test_gpu_remap_planted.py):
+ *   coordinates  r = round-half-to-even of the float32 map entry (nearest) or of 32 times it, multiplied in float32 (linear).  An
+ *                entry that is NaN or +-inf, or whose r does not fit int32, is OUTSIDE the image.
+ *   border       constant 0 (0.0 for float32) for every tap outside [0,H) x [0,W).
+ *   nearest      dst = src[r(map_y), r(map_x)]; values are copied, never converted.
+ *   linear       sx = r(32 map_x): ix = sx >> 5, fx = sx & 31 (arithmetic shift, two's-complement mask), the same in y; uint8: integer
+ *                weights (32-fx)(32-fy)32 ... summing to 2^15, (sum + 2^14) >> 15; float32: the weights (1-fx/32)(1-fy/32) ...,
+ *                four products added in float32 in the order (0,0) (0,1) (1,0) (1,1) (a zero weight times inf is NaN). */
 int hv_remap(hv_volume *v, const void *src, int32_t src_kind, int32_t channels, int32_t height, int32_t width,
              const float *map_x, const float *map_y, int32_t linear, void *dst, int32_t loc);
 
@@ -394,7 +402,10 @@ int hv_tsdf_reintegrate_batch(hv_volume *v, const void *depth, int32_t depth_dty
  * maps from cv2.initUndistortRectifyMap, :758-786).  With maps set (float32 [H,W], at `loc`; copied), every frame handed to
  * hv_tsdf_integrate / _batch / _frames goes through them first - one launch per batch, beside the batch's touch + pack launch, the
  * depth in its own storage type (float32 or uint16: 5 bytes per pixel for a TUM-style keyframe end to end) - and the caller passes
- * the RECTIFIED intrinsics.  map_x == NULL clears them.  OpenCV's remap semantics restated (hv_remap): unpinned. */
+ * the RECTIFIED intrinsics.  map_x == NULL clears them.  OpenCV's remap semantics restated (hv_remap): unpinned.  The rules are
+ * hv_remap's, coordinate for coordinate: a NaN or +-inf map entry, or one whose rounded value does not fit int32, is outside the
+ * image - depth 0 (nothing is fused there) and colour 0.  Frames of another size than the maps' are refused (HV_ERR_INVALID);
+ * HV_ERR_MODE for a volume that is not a TSDF volume. */
 int hv_tsdf_set_rectify_maps(hv_volume *v, const float *map_x, const float *map_y, int32_t height, int32_t width, int32_t loc);
 
 /* Channel order of the colour frames handed to hv_tsdf_integrate*: 0 = R, G, B (Open3D's RGBDImage, the default), 1 = B, G, R -

@@ -10,10 +10,17 @@
 //
 // ... and filter_shadow_points (pyslam/utilities/depth.py:103-146), the depth image's other per-keyframe preparation (below).
 #include <algorithm>
+#include <climits>
 
 #include "hv_common.h"
 
 enum { HV_IMG_U8 = 0, HV_IMG_F32 = 1, HV_IMG_I32 = 2 };
+
+// cvRound of a map coordinate (nearest), or of 32 times it (linear): round-half-to-even.  A coordinate that is NaN or +-inf, or whose
+// rounded value does not fit int32, is OUTSIDE the image: INT_MIN here, like x86's cvRound, so that neither it nor the tap next to
+// it (ix + 1) can land in [0, W).  v_cvt_i32_f32 alone gives 0 for NaN: row / column 0 of the source.  Every finite value below
+// 2^31 in magnitude rounds exactly as before.
+__device__ __forceinline__ int hv_map_round(float v) { return fabsf(v) < 2147483648.0f ? __float2int_rn(v) : INT_MIN; }
 
 template <typename T> __device__ __forceinline__ T px_or_zero(const T *src, int H, int W, int C, int y, int x, int c) {
     return (x >= 0 && x < W && y >= 0 && y < H) ? src[((int64_t)y * W + x) * C + c] : (T)0;
@@ -25,7 +32,7 @@ __global__ __launch_bounds__(256) void k_remap_nearest(const T *__restrict__ src
                                                         T *__restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)H * W) return;
-    const int sx = __float2int_rn(mx[i]), sy = __float2int_rn(my[i]);
+    const int sx = hv_map_round(mx[i]), sy = hv_map_round(my[i]);
     for (int c = 0; c < C; ++c) dst[i * C + c] = px_or_zero(src, H, W, C, sy, sx, c);
 }
 
@@ -34,7 +41,7 @@ __global__ __launch_bounds__(256) void k_remap_linear_u8(const uint8_t *__restri
                                                           uint8_t *__restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)H * W) return;
-    const int sx = __float2int_rn(mx[i] * 32.0f), sy = __float2int_rn(my[i] * 32.0f);
+    const int sx = hv_map_round(mx[i] * 32.0f), sy = hv_map_round(my[i] * 32.0f);
     const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
     const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
     for (int c = 0; c < C; ++c) {
@@ -50,7 +57,7 @@ __global__ __launch_bounds__(256) void k_remap_linear_f32(const float *__restric
                                                            float *__restrict__ dst) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)H * W) return;
-    const int sx = __float2int_rn(mx[i] * 32.0f), sy = __float2int_rn(my[i] * 32.0f);
+    const int sx = hv_map_round(mx[i] * 32.0f), sy = hv_map_round(my[i] * 32.0f);
     const int ix = sx >> 5, iy = sy >> 5;
     const float fx = (float)(sx & 31) * (1.0f / 32.0f), fy = (float)(sy & 31) * (1.0f / 32.0f);
     for (int c = 0; c < C; ++c) {
@@ -73,8 +80,8 @@ __global__ __launch_bounds__(256) void k_rectify_frames(const D *__restrict__ de
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npx) return;
     const float fxm = mx[i], fym = my[i];
-    const int nx = __float2int_rn(fxm), ny = __float2int_rn(fym);
-    const int sx = __float2int_rn(fxm * 32.0f), sy = __float2int_rn(fym * 32.0f);
+    const int nx = hv_map_round(fxm), ny = hv_map_round(fym);
+    const int sx = hv_map_round(fxm * 32.0f), sy = hv_map_round(fym * 32.0f);
     const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
     const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
     for (int f = 0; f < n_frames; ++f) {

@@ -631,13 +631,14 @@ class VolumetricIntegratorBase:
         K = np.array([[camera.fx, 0.0, camera.cx], [0.0, camera.fy, camera.cy], [0.0, 0.0, 1.0]])
         self.new_K, self.calib_map1, self.calib_map2 = K, None, None
         if np.linalg.norm(D) > 1e-10:
-            from ..prep import get_optimal_new_camera_matrix, init_undistort_rectify_map
+            from ..prep import RectifyMaps, get_optimal_new_camera_matrix, init_undistort_rectify_map
 
             if getattr(Parameters, "kDepthImageUndistortionUseOptimalNewCameraMatrixWithAlphaScale", True):
                 alpha = getattr(Parameters, "kDepthImageUndistortionOptimalNewCameraMatrixWithAlphaScaleValue", 0.7)
                 self.new_K, _ = get_optimal_new_camera_matrix(K, D, (camera.width, camera.height), alpha,
                                                               (camera.width, camera.height))
             self.calib_map1, self.calib_map2 = init_undistort_rectify_map(K, D, self.new_K, (camera.width, camera.height))
+            self.calib_maps = RectifyMaps(self.calib_map1, self.calib_map2)  # (a device copy for device depth, made once)
         self.rectified_fx, self.rectified_fy = float(self.new_K[0, 0]), float(self.new_K[1, 1])
         self.rectified_cx, self.rectified_cy = float(self.new_K[0, 2]), float(self.new_K[1, 2])
         self.dtype_vertices = np.dtype(Parameters.kDenseMappingDtypeVertices)
@@ -691,7 +692,7 @@ class VolumetricIntegratorBase:
         elif self.calib_map1 is not None:  # base.py:1017-1043: colour bilinear, depth and labels nearest
             m1, m2 = self.calib_map1, self.calib_map2
             color = self.volume.remap(np.ascontiguousarray(color), m1, m2, linear=True)
-            depth = self.volume.remap(depth, m1, m2, linear=False)
+            depth = self.volume.remap(depth, *self.calib_maps.for_image(depth), linear=False)
             if semantic is not None:
                 semantic = self.volume.remap(np.ascontiguousarray(semantic, dtype=np.int32), m1, m2, linear=False)
             if instances is not None:

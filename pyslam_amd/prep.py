@@ -93,6 +93,27 @@ def init_undistort_rectify_map(K, D, new_K, image_size):
     return np.ascontiguousarray(map_x), np.ascontiguousarray(map_y)
 
 
+class RectifyMaps:
+    """A pair of maps fixed for a camera's lifetime, for volume.remap: host arrays for host images, and for a CUDA image a device
+    copy made once per device (remap itself keeps nothing between calls).  The host arrays are this object's own read-only copies,
+    so the device copy cannot fall behind them."""
+
+    def __init__(self, map_x, map_y):
+        self.map_x, self.map_y = (np.array(m, dtype=np.float32, order="C") for m in (map_x, map_y))
+        assert self.map_x.ndim == 2 and self.map_x.shape == self.map_y.shape
+        self.map_x.setflags(write=False), self.map_y.setflags(write=False)
+        self._dev = {}
+
+    def for_image(self, img):
+        if not getattr(img, "is_cuda", False):
+            return self.map_x, self.map_y
+        if img.device not in self._dev:
+            import torch
+
+            self._dev[img.device] = tuple(torch.tensor(m).to(img.device) for m in (self.map_x, self.map_y))
+        return self._dev[img.device]
+
+
 class Undistorter:
     """Holds the maps on the GPU side of a volume and applies the reference's per-frame remaps:
     colour INTER_LINEAR, depth / labels INTER_NEAREST (volumetric_integrator_base.py:1017-1043)."""
@@ -101,17 +122,18 @@ class Undistorter:
         self.volume = volume
         K = np.asarray(K, dtype=np.float64)
         self.new_K = get_optimal_new_camera_matrix(K, D, (width, height), alpha, (width, height))[0] if use_optimal_new_K else K
-        self.map_x, self.map_y = init_undistort_rectify_map(K, D, self.new_K, (width, height))
+        self.maps = RectifyMaps(*init_undistort_rectify_map(K, D, self.new_K, (width, height)))
+        self.map_x, self.map_y = self.maps.map_x, self.maps.map_y
 
     @property
     def intrinsics(self):
         return float(self.new_K[0, 0]), float(self.new_K[1, 1]), float(self.new_K[0, 2]), float(self.new_K[1, 2])
 
     def color(self, img_u8):
-        return self.volume.remap(img_u8, self.map_x, self.map_y, linear=True)
+        return self.volume.remap(img_u8, *self.maps.for_image(img_u8), linear=True)
 
     def depth(self, depth_f32):
-        return self.volume.remap(depth_f32, self.map_x, self.map_y, linear=False)
+        return self.volume.remap(depth_f32, *self.maps.for_image(depth_f32), linear=False)
 
     def labels(self, label_i32):
-        return self.volume.remap(label_i32, self.map_x, self.map_y, linear=False)
+        return self.volume.remap(label_i32, *self.maps.for_image(label_i32), linear=False)

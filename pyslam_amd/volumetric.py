@@ -45,6 +45,13 @@ def _is_torch(a):
     return hasattr(a, "data_ptr") and not isinstance(a, np.ndarray)
 
 
+def _check_map_shapes(map_x, map_y, H, W):
+    """hv_remap takes one height and width for image and maps: smaller maps would be read past their end."""
+    for name, m in (("map_x", map_x), ("map_y", map_y)):
+        if tuple(np.shape(m)) != (H, W):
+            raise RuntimeError(f"remap: {name} has shape {tuple(np.shape(m))}, the image is {H}x{W} (maps are [H, W])")
+
+
 def _stats(cls, struct):
     """A *Stats result (a _Stats subclass or a named tuple) from the ctypes struct the library filled, field by field name."""
     return cls(*[getattr(struct, name) for name in getattr(cls, "_fields", cls.__slots__)])
@@ -783,8 +790,10 @@ class _Volume:
         return out
 
     def remap(self, img, map_x, map_y, linear=False):
-        """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU.  Host arrays, or a
-        torch CUDA tensor (the maps are then uploaded once and cached): the image never leaves the device."""
+        """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU; the maps are [H, W] like the image.
+        Host arrays, or a torch CUDA tensor: the image never leaves the device, and maps that are float32 CUDA tensors are read
+        where they lie (prep.RectifyMaps keeps such a pair across frames); host maps are uploaded by this call.  The result depends
+        on this call's arguments alone: nothing is cached here."""
         if _is_torch(img) and img.is_cuda:
             import torch
 
@@ -792,13 +801,10 @@ class _Volume:
             kind = {torch.uint8: 0, torch.float32: 1, torch.int32: 2}.get(src.dtype)
             if kind is None:
                 raise RuntimeError(f"remap: unsupported image dtype {src.dtype}")
-            key = (id(map_x), id(map_y))
-            if getattr(self, "_dev_maps_key", None) != key:
-                self._dev_maps = (torch.from_numpy(np.ascontiguousarray(map_x, dtype=np.float32)).to(src.device),
-                                  torch.from_numpy(np.ascontiguousarray(map_y, dtype=np.float32)).to(src.device))
-                self._dev_maps_key = key
-            mx, my = self._dev_maps
             H, W = int(src.shape[0]), int(src.shape[1])
+            _check_map_shapes(map_x, map_y, H, W)
+            mx, my = (m.to(device=src.device, dtype=torch.float32).contiguous() for m in
+                      (m if _is_torch(m) else torch.tensor(np.asarray(m, dtype=np.float32)) for m in (map_x, map_y)))
             C = 1 if src.dim() == 2 else int(src.shape[2])
             out = torch.empty_like(src)
             torch.cuda.current_stream(src.device).synchronize()  # producers ran on torch's stream, hv_remap on the volume's
@@ -812,6 +818,7 @@ class _Volume:
             raise RuntimeError(f"remap: unsupported image dtype {img.dtype}")
         H, W = img.shape[:2]
         C = 1 if img.ndim == 2 else img.shape[2]
+        _check_map_shapes(map_x, map_y, H, W)
         mx = np.ascontiguousarray(map_x, dtype=np.float32)
         my = np.ascontiguousarray(map_y, dtype=np.float32)
         out = np.empty_like(img)
