@@ -408,6 +408,71 @@ __device__ __forceinline__ void hv_sweep_item(const unsigned item, const unsigne
     part = (int)(within % parts);
 }
 
+// Epilogue of a sweep item: the plane words of a lane's updated voxels, read-modify-written in PASSES of ZB voxels along z.
+// A pass first issues every plane load of its updated voxels (TW: tsdf and weight too, else only the three colour sums), waits for
+// them ONCE, and then runs voxel by voxel: `finish(z, w)` turns the loaded words into the words to store, the five stores follow in
+// plane order with no wait between them.  A wave so pays about one memory round trip per pass; written voxel by voxel (`+=` on
+// the colour planes inside each voxel's block) it paid one per voxel, the loads of voxel k + 1 counted behind the stores of voxel
+// k (gfx9: one vmcnt for both), plus one per four voxels for tsdf and weight.  `updated(z)` is the lane's own condition, the same in both halves
+// of a pass: a lane with nothing to add touches no word, and a z plane no lane updates is skipped by the execz branch - no traffic
+// is added.  The wait is explicit because the compiler cannot see that the two halves run under the same condition: left to place
+// the waits itself it puts one in front of every store ("the load into this register may still be pending"), which counts the
+// stores before it too.
+// (Compiled and dropped, profiles/sweep_epilogue: passes of 8 voxels - whole columns keep 128 registers with 1 spilled outside the
+// frame loop and measure the same as passes of 4, z halves spill 36; passes of 16 - 181 spilled; the loads of pass p + 1 issued
+// before the stores of pass p, two word sets alternating - 28 spilled and a longer frame loop.)
+static constexpr int HV_WAIT_VMCNT0 = 0x0f70; // s_waitcnt vmcnt(0), expcnt and lgkmcnt left at their maxima (gfx9 encoding)
+struct HvPlaneWords {
+    float vt;
+    uint32_t vw, r, g, b;
+};
+template <int ZH, int ZB, bool TW, typename Updated, typename Finish>
+__device__ __forceinline__ void hv_sweep_epilogue(char *__restrict__ unit, const int wordb, Updated updated, Finish finish) {
+    constexpr int NP = ZH / ZB;
+    static_assert(ZH % ZB == 0, "whole passes");
+    auto load = [&](const int p, HvPlaneWords (&w)[ZB]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < ZB; ++k) {
+            const int z = p * ZB + k;
+            if (updated(z)) {
+                const int q = wordb + z * HV_TSDF_RR;
+                if (TW) {
+                    w[k].vt = ((const float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
+                    w[k].vw = ((const uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
+                }
+                w[k].r = ((const uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q];
+                w[k].g = ((const uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q];
+                w[k].b = ((const uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q];
+            }
+        }
+    };
+    auto store = [&](const int p, const HvPlaneWords (&w)[ZB]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < ZB; ++k) {
+            const int z = p * ZB + k;
+            if (updated(z)) {
+                const int q = wordb + z * HV_TSDF_RR;
+                HvPlaneWords o = w[k];
+                finish(z, o);
+                ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = o.vt;
+                ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = o.vw;
+                ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] = o.r;
+                ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] = o.g;
+                ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] = o.b;
+            }
+        }
+    };
+#pragma unroll
+    for (int p = 0; p < NP; ++p) {
+        HvPlaneWords w[ZB];
+        load(p, w);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(HV_WAIT_VMCNT0);
+        store(p, w);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
 // the bitwise form's shape: a lane owns ZH voxels along z, a wave 64 columns x ZH z = one of a unit's 64 / ZH tasks
 static constexpr int HV_SWEEP_ZH = 4;
 static constexpr int HV_SWEEP_SPLIT = 8; // workgroups per unit
@@ -643,19 +708,17 @@ __global__ __launch_bounds__(64 * HV_SWEEP_WAVES, HV_SWEEP_WPE) void k_tsdf_swee
             apply_frame(g);
             if (!mask) break;
         }
-#pragma unroll
-        for (int zz = 0; zz < ZH; ++zz) {
-            const float wfz = (zz & 1) ? WF[zz / 2].y : WF[zz / 2].x;
-            const uint32_t nw = (uint32_t)wfz;
-            if (nw != vw[zz]) { // updated by at least one frame: fold the batch's colour into the planes
-                const int q = wordb + zz * HV_TSDF_RR;
-                ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = (zz & 1) ? VT[zz / 2].y : VT[zz / 2].x;
-                ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = nw;
-                ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] += arb[zz] & 0xffffu;
-                ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] += ag[zz] >> 8;
-                ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] += arb[zz] >> 16;
-            }
-        }
+        // updated by at least one frame: fold the batch's colour into the planes (hv_sweep_epilogue: the colour loads of the pass first)
+        auto new_weight = [&](const int zz) __attribute__((always_inline)) { return (uint32_t)((zz & 1) ? WF[zz / 2].y : WF[zz / 2].x); };
+        hv_sweep_epilogue<ZH, ZH, false>(
+            unit, wordb, [&](const int zz) __attribute__((always_inline)) { return new_weight(zz) != vw[zz]; },
+            [&](const int zz, HvPlaneWords &w) __attribute__((always_inline)) {
+                w.vt = (zz & 1) ? VT[zz / 2].y : VT[zz / 2].x;
+                w.vw = new_weight(zz);
+                w.r += arb[zz] & 0xffffu;
+                w.g += ag[zz] >> 8;
+                w.b += arb[zz] >> 16;
+            });
     }
 }
 
@@ -673,7 +736,8 @@ __global__ __launch_bounds__(64 * HV_SWEEP_WAVES, HV_SWEEP_WPE) void k_tsdf_swee
 //    the zero an out-of-range buffer load returns) gives sdf <= -pc2 < -sdf_trunc and fails the truncation test by itself;
 //  * the image-tile test of the tile-sharded mode folds into the image-range compare (the range constants become the tile's).
 // The observation count rides in byte 3 of the packed colour word (HV_REC_ONE, set by the pack role): one masked add accumulates
-// green and the count.  tsdf / weight planes are only read when the item is done, and only by lanes with n > 0.
+// green and the count.  tsdf / weight planes are only read when the item is done, and only by lanes with n > 0: the epilogue
+// (hv_sweep_epilogue) reads and writes the five planes of a column in passes of 4 voxels, one memory round trip per pass.
 // A lane owns one (x, y) column of the unit and all 16 z of it, a wave 64 columns (one column group), a unit is 4 wave tasks:
 //  * the z-walk starts at z = 0 for every lane: no replay of the reference's repeated float additions, and the per-frame set-up (the
 //    rigid transform of the column's base point, the frame's buffer descriptor, the prefetch of the next frame's constants) is paid
@@ -706,6 +770,7 @@ __global__ __launch_bounds__(64, 4) void k_tsdf_sweep_column(
     constexpr int ZH = 16 / ZS;
     constexpr int NG = ZH / GV;
     constexpr int PARTS = 4 * ZS;  // work items per unit: its 4 column groups x ZS z ranges
+    constexpr int ZB = 4;          // voxels per epilogue pass (hv_sweep_epilogue)
     typedef uint32_t hv_u3 __attribute__((ext_vector_type(3)));
     int n_units = table.counters[HV_CNT_TOUCH(parity)];
     if (n_units > table.max_blocks) n_units = table.max_blocks;
@@ -929,34 +994,17 @@ __global__ __launch_bounds__(64, 4) void k_tsdf_sweep_column(
             fold_frame(kb, fb, ka, mask);
             if (!mask) break;
         }
-        // one running-mean step per voxel for the whole batch, four voxels of the column at a time
-#pragma unroll
-        for (int z4 = 0; z4 < ZH; z4 += 4) {
-            float vt[4];
-            uint32_t vw[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                if (agn[z4 + k] >> 24) {
-                    const int q = wordb + (z4 + k) * HV_TSDF_RR;
-                    vt[k] = ((const float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q];
-                    vw[k] = ((const uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q];
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int z = z4 + k;
-                const uint32_t n = agn[z] >> 24;
-                if (n) {
-                    const int q = wordb + z * HV_TSDF_RR;
-                    const uint32_t nw = vw[k] + n;
-                    ((float *)(unit + 0 * HV_TSDF_PLANE_BYTES))[q] = (vt[k] * (float)vw[k] + S[z]) / (float)nw;
-                    ((uint32_t *)(unit + 1 * HV_TSDF_PLANE_BYTES))[q] = nw;
-                    ((uint32_t *)(unit + 2 * HV_TSDF_PLANE_BYTES))[q] += arb[z] & 0xffffu;
-                    ((uint32_t *)(unit + 3 * HV_TSDF_PLANE_BYTES))[q] += (agn[z] >> 8) & 0xffffu;
-                    ((uint32_t *)(unit + 4 * HV_TSDF_PLANE_BYTES))[q] += arb[z] >> 16;
-                }
-            }
-        }
+        // one running-mean step per voxel for the whole batch, in passes over the column (hv_sweep_epilogue)
+        hv_sweep_epilogue<ZH, ZB, true>(
+            unit, wordb, [&](const int z) __attribute__((always_inline)) { return (agn[z] >> 24) != 0u; },
+            [&](const int z, HvPlaneWords &w) __attribute__((always_inline)) {
+                const uint32_t nw = w.vw + (agn[z] >> 24);
+                w.vt = (w.vt * (float)w.vw + S[z]) / (float)nw;
+                w.vw = nw;
+                w.r += arb[z] & 0xffffu;
+                w.g += (agn[z] >> 8) & 0xffffu;
+                w.b += arb[z] >> 16;
+            });
     }
 }
 
