@@ -150,6 +150,53 @@ int hv_filter_shadow_points(hv_volume *v, const float *depth, int32_t height, in
 int hv_filter_shadow_points_on_stream(hv_volume *v, const float *depth, int32_t height, int32_t width, int32_t delta_x,
                                       int32_t delta_y, float fill_value, float *out, void *stream);
 
+/* ---- census semi-global stereo matching ------------------------------------------------------------
+ * hv_stereo_sgm: a rectified uint8 pair -> disparity (int16, sixteenths of a pixel, -16 = invalid: the format of
+ * cv2.StereoSGBM.compute, so disparity / 16 works as in pyslam/depth_estimation/depth_estimator_base.py:69-131
+ * DepthEstimatorSgbm) and metric depth (float32, 0 = none).  The weight-free stereo estimator of the package: OpenCV is not a
+ * dependency and parity with its SGBM is not claimed; the algorithm is fixed by the rules below, restated in numpy in
+ * tests/stereo_reference.py, and the library is held to that restatement bit for bit.  Integer arithmetic except rule 10;
+ * D = num_disparities, the minimum disparity is 0.
+ *   1 grey        one channel as is; three channels g = (c0 + 2 c1 + c2 + 2) >> 2 (the same for RGB and BGR)
+ *   2 census      window 9 wide x 7 high, centred, centre excluded (62 bits); bit = neighbour < centre; pixels outside the image
+ *                 take the nearest edge pixel
+ *   3 cost        C(y,x,d) = popcount(censusL(y,x) ^ censusR(y,x-d)) for x - d >= 0, else 64
+ *   4 paths       4: left->right, right->left, top->bottom, bottom->top; 8: and the four diagonals.  With q the pixel before p on
+ *                 the path and M(q) = min_k L(q,k):  L(p,d) = C(p,d) + min(L(q,d), L(q,d-1) + P1, L(q,d+1) + P1, M(q) + P2) - M(q),
+ *                 the d-1 / d+1 terms absent outside [0,D);  L(p,d) = C(p,d) where q lies outside the image.  S = the sum of L over
+ *                 the paths (0 < P1 <= P2 <= 1023: S <= 8 (64 + P2) fits uint16)
+ *   5 winner      d* = the smallest d attaining min_d S(p,d)
+ *   6 uniqueness  invalid if some d with |d - d*| > 1 has S(p,d) (100 - uniqueness_ratio) < S(p,d*) 100
+ *   7 left-right  (max_diff >= 0; a negative value disables the rule)  dR(y,xr) = the smallest d attaining the minimum of
+ *                 S(y,xr+d,d) over xr + d < W;  invalid if x - d* < 0 or |dR(y,x-d*) - d*| > max_diff
+ *   8 sub-pixel   for 0 < d* < D-1: den = max(S(d*-1) + S(d*+1) - 2 S(d*), 1), d16 = 16 d* + ((S(d*-1) - S(d*+1)) 16 + den) / (2 den)
+ *                 with C division (toward zero); otherwise d16 = 16 d*
+ *   9 disparity   d16 for valid pixels, -16 for invalid ones
+ *  10 depth       (bf * 16f) / float(d16): one float32 multiply, one correctly rounded divide; 0 where d16 <= 0, where the result is
+ *                 < min_depth, or > max_depth when max_depth is finite
+ * No speckle filter: hv_filter_shadow_points and hv_tsdf_remove_components exist downstream.
+ * left / right: [height,width] (channels 1) or [height,width,3] uint8, both outputs [height,width]; either output may be NULL, not
+ * both.  `loc` as in hv_filter_shadow_points: host arrays are complete on return, a device call is queued on the volume's stream
+ * and returns.  Works on a volume of any mode and reads nothing of it.  Scratch is owned by the handle, grown on demand and freed by
+ * hv_destroy: height width (2 num_disparities + 22) bytes (S uint16, two census images, the left winners and the right image's
+ * best keys), each part rounded up to 256 bytes.
+ * HV_ERR_INVALID before anything is launched or written: a NULL image or params, both outputs NULL, channels not 1 or 3, height or
+ * width < 1 (or > 32768, or 2^30 pixels and more), num_disparities not a multiple of 16 in 16..256, not 0 < p1 <= p2 <= 1023,
+ * uniqueness_ratio outside 0..99, paths not 4 or 8, bf not finite and positive while depth_out is given.  HV_ERR_CAPACITY when the
+ * scratch cannot be allocated. */
+typedef struct hv_stereo_params {
+    int32_t num_disparities;  /* 128 */
+    int32_t p1, p2;           /* 10, 120 */
+    int32_t uniqueness_ratio; /* 15 */
+    int32_t max_diff;         /* 1 */
+    int32_t paths;            /* 8 */
+    float bf;                 /* baseline times focal length, metres x pixels (read only when depth_out is given) */
+    float min_depth, max_depth; /* 0, +inf */
+} hv_stereo_params;
+int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
+                  const hv_stereo_params *params, int16_t *disparity_out /* may be NULL */, float *depth_out /* may be NULL */,
+                  int32_t loc);
+
 /* get_voxels(min_count, min_confidence) (voxel_block_grid.hpp:717-819): rows = sum / count.
  * Pass points == NULL to query *n only.  At most `cap` rows are written; *n is the full count. */
 int hv_get_voxels(hv_volume *v, int32_t min_count, float min_confidence, float *points,

@@ -242,6 +242,11 @@ class HvRemoveComponentsStats(_c.Structure):
                 ("units_changed", _i64), ("units_emptied", _i64)]
 
 
+class HvStereoParams(_c.Structure):
+    _fields_ = [("num_disparities", _i32), ("p1", _i32), ("p2", _i32), ("uniqueness_ratio", _i32), ("max_diff", _i32), ("paths", _i32),
+                ("bf", _f32), ("min_depth", _f32), ("max_depth", _f32)]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -266,6 +271,7 @@ SIGNATURES = {
     "hv_remap": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32]),
     "hv_filter_shadow_points": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32]),
     "hv_filter_shadow_points_on_stream": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
+    "hv_stereo_sgm": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(HvStereoParams), _vp, _vp, _i32]),
     "hv_get_voxels": (_i32, [_vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_bb": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_frustum": (_i32, [_vp, _vp, _i32, _i32, _vp, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),

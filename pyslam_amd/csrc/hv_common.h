@@ -578,6 +578,9 @@ struct hv_volume {
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)
     void *shadow_ring = nullptr;
     int shadow_ring_next = 0;
+    // hv_stereo_sgm: [S npx D u16][census left npx u64][census right npx u64][d_left npx i16][right keys npx u32] (hv_stereo.hip)
+    void *stereo_buf = nullptr;
+    size_t stereo_buf_bytes = 0;
     // the halo merge's plan of hv_merge_halo_plan_device (hv_halo.hip): [shared keys n*3 i32][action n u8], device memory
     void *halo_plan = nullptr;
     size_t halo_plan_bytes = 0;

@@ -648,11 +648,16 @@ class VolumetricIntegratorBase:
         # (constructor kwarg `depth_estimator_factory(camera) -> object with infer(img, img_right)`), or taken from
         # real pySLAM when it is importable; see pyslam_amd/depth_estimation.py for the device-resident wrapper.
         self.depth_estimator = None
+        self.depth_estimator_pending = False
         self.img_id_to_depth = {}
         if getattr(Parameters, "kVolumetricIntegrationUseDepthEstimator", False):
             make = constructor_kwargs.get("depth_estimator_factory")
             if make is not None:
                 self.depth_estimator = make(camera)
+            elif getattr(Parameters, "kVolumetricIntegrationDepthEstimatorType", None) == "DEPTH_SGM_HIP":
+                # the package's own weight-free estimator (hv_stereo_sgm).  It runs on the volume, which the subclass creates after
+                # this: made on first use (estimate_depth_if_needed_and_rectify)
+                self.depth_estimator_pending = True
             else:
                 try:
                     from pyslam.depth_estimation.depth_estimator_factory import DepthEstimatorType, depth_estimator_factory  # type: ignore
@@ -673,6 +678,11 @@ class VolumetricIntegratorBase:
         color, depth = keyframe_data.img, keyframe_data.depth
         pts3d = None
         if depth is None or getattr(depth, "size", 1) == 0:
+            if self.depth_estimator is None and getattr(self, "depth_estimator_pending", False):
+                from ..depth_estimation import DepthEstimatorSgm
+
+                self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera)
+                self.depth_estimator_pending = False
             if self.depth_estimator is None:
                 return None, None, None, None, None  # skip this keyframe
             if keyframe_data.id in self.img_id_to_depth:

@@ -9,7 +9,9 @@ of libpyslam_hipvol take the tensor's device pointer (HV_DEVICE).
 
 No network weights are available offline, so the module is injected: any ``torch.nn.Module`` mapping
 (left, right) float tensors [1,3,H,W] to a disparity [1,1,H,W] or [H,W] works; ``StubStereoNet`` is a tiny
-deterministic stand-in used by the tests (RAFT-Stereo itself is out of this package's scope)."""
+deterministic stand-in used by the tests (RAFT-Stereo itself is out of this package's scope); its disparity has nothing to
+do with the scene.  ``DepthEstimatorSgm`` needs no weights: census semi-global matching on the GPU (hv_stereo_sgm), depth
+in the same place, selected in the dense front by kVolumetricIntegrationDepthEstimatorType = "DEPTH_SGM_HIP"."""
 import numpy as np
 
 
@@ -51,6 +53,37 @@ class DepthEstimatorStereoTorch:
             torch.cuda.current_stream(self.device).synchronize()  # the volume's HIP stream consumes it next
             return depth, None
         return depth.cpu().numpy(), None
+
+
+class DepthEstimatorSgm:
+    """The weight-free stereo estimator: census semi-global matching on the GPU (_Volume.stereo_sgm, hv_stereo_sgm), in the
+    place of the reference's DepthEstimatorSgbm (pyslam/depth_estimation/depth_estimator_base.py:69-131, a cv2.StereoSGBM).
+    infer(image, image_right) -> (depth, None): the pair is uploaded once and the depth stays a float32 CUDA tensor when
+    `keep_on_device`, a numpy array otherwise; disparity_map is the int16 disparity in sixteenths (-16 = invalid), in the same
+    place.  An invalid pixel has depth 0 (the reference wrapper's bf is not reproduced).  sgm_params: num_disparities, p1, p2,
+    uniqueness_ratio, max_diff, paths."""
+
+    def __init__(self, volume, camera, keep_on_device=True, min_depth=0.0, max_depth=np.inf, **sgm_params):
+        self.volume = volume
+        self.camera = camera
+        self.keep_on_device = keep_on_device
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self.sgm_params = dict(sgm_params)
+        self.disparity_map = None
+
+    def infer(self, image, image_right=None):
+        if image_right is None:
+            raise ValueError("Image right is None. Are you using a stereo dataset? If not, you cant use a stereo depth estimator here.")
+        bf = float(getattr(self.camera, "bf", 1.0) or 1.0)
+        left, right = np.ascontiguousarray(image), np.ascontiguousarray(image_right)
+        if self.keep_on_device:
+            import torch
+
+            dev = self.volume._device()
+            left, right = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)
+        self.disparity_map, depth = self.volume.stereo_sgm(left, right, bf=bf, min_depth=self.min_depth, max_depth=self.max_depth,
+                                                           **self.sgm_params)
+        return depth, None
 
 
 def make_stub_stereo_net(seed=0):

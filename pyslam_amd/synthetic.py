@@ -158,6 +158,17 @@ class SyntheticRGBD:
             depth = depth.astype(np.float32)
         return depth, np.ascontiguousarray(rgb), T_cw
 
+    def stereo(self, i, baseline):
+        """A rectified stereo pair of pose i: the left eye is the stream's camera, the right eye the same camera moved by
+        `baseline` metres along its x axis.  -> (rgb_left, rgb_right, depth_left float32 metres without sensor noise, T_cw);
+        the true disparity of a left pixel is fx * baseline / depth_left."""
+        T_cw, T_wc = trajectory_pose(i, self.n_poses)
+        T_right = T_wc.copy()
+        T_right[:3, 3] = T_wc[:3, 3] + T_wc[:3, 0] * float(baseline)
+        depth, rgb_left, _ = render(T_wc, self.width, self.height, self.fx, self.fy, self.cx, self.cy, self.dist)
+        _, rgb_right, _ = render(T_right, self.width, self.height, self.fx, self.fy, self.cx, self.cy, self.dist)
+        return np.ascontiguousarray(rgb_left), np.ascontiguousarray(rgb_right), depth.astype(np.float32), T_cw
+
     def labels(self, i):
         return render(trajectory_pose(i, self.n_poses)[1], self.width, self.height, self.fx, self.fy, self.cx, self.cy, self.dist)[2]
 

@@ -789,6 +789,56 @@ class _Volume:
                 L.check(self._lib.hv_filter_shadow_points(*args, L.location(d)))
         return out
 
+    def stereo_sgm(self, left, right, num_disparities=128, p1=10, p2=120, uniqueness_ratio=15, max_diff=1, paths=8, bf=None,
+                   min_depth=0.0, max_depth=np.inf):
+        """Census semi-global stereo matching of a rectified uint8 pair, [H,W] or [H,W,3] (hv_stereo_sgm, the rules in
+        include/hipvol.h) -> (disparity int16 [H,W] in sixteenths of a pixel, -16 = invalid; depth float32 [H,W] metres = bf 16 /
+        disparity, 0 = none - or None when bf is None).  numpy arrays in, numpy arrays out; torch CUDA tensors in, tensors on the
+        same GPU out, queued on the volume's stream.  Works on a volume of any mode and reads nothing of it."""
+        on_gpu = L.location(left) == L.HV_DEVICE
+        if on_gpu != (L.location(right) == L.HV_DEVICE):
+            raise ValueError("stereo_sgm: left and right must live in the same place")
+        if on_gpu:
+            import torch
+
+            if left.dtype != torch.uint8 or right.dtype != torch.uint8:
+                raise ValueError("stereo_sgm: the images must be uint8")
+            if left.device != self._device() or right.device != self._device():
+                raise ValueError(f"stereo_sgm: the images live on {left.device} / {right.device}, the volume on {self._device()}")
+            a, b = left.contiguous(), right.contiguous()
+        else:
+            a, b = (x.cpu().numpy() if _is_torch(x) else np.asarray(x) for x in (left, right))
+            if a.dtype != np.uint8 or b.dtype != np.uint8:
+                raise ValueError("stereo_sgm: the images must be uint8")
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+        if tuple(a.shape) != tuple(b.shape) or a.ndim not in (2, 3):
+            raise ValueError(f"stereo_sgm: left {tuple(a.shape)} and right {tuple(b.shape)} must be two images of one shape")
+        H, W = int(a.shape[0]), int(a.shape[1])
+        channels = 1 if a.ndim == 2 else int(a.shape[2])
+        # what hv_stereo_sgm answers with HV_ERR_INVALID, refused here before anything is allocated
+        if channels not in (1, 3):
+            raise ValueError(f"stereo_sgm: images must have 1 or 3 channels, got {channels}")
+        if H < 1 or W < 1:
+            raise ValueError(f"stereo_sgm: empty image {tuple(a.shape)}")
+        if not (16 <= int(num_disparities) <= 256 and int(num_disparities) % 16 == 0):
+            raise ValueError(f"stereo_sgm: num_disparities must be a multiple of 16 in 16..256, got {num_disparities}")
+        if not 0 < int(p1) <= int(p2) <= 1023:
+            raise ValueError(f"stereo_sgm: need 0 < p1 <= p2 <= 1023, got p1 = {p1}, p2 = {p2}")
+        if not 0 <= int(uniqueness_ratio) <= 99:
+            raise ValueError(f"stereo_sgm: uniqueness_ratio must be in 0..99, got {uniqueness_ratio}")
+        if int(paths) not in (4, 8):
+            raise ValueError(f"stereo_sgm: paths must be 4 or 8, got {paths}")
+        if bf is not None and not 0.0 < float(bf) <= float(np.finfo(np.float32).max):  # (the library reads a float32)
+            raise ValueError(f"stereo_sgm: bf must be finite and positive, got {bf}")
+        prm = L.HvStereoParams(int(num_disparities), int(p1), int(p2), int(uniqueness_ratio), int(max_diff), int(paths),
+                               float(bf) if bf is not None else 0.0, float(min_depth), float(max_depth))
+        out = self._results({"disparity": ((H, W), np.int16), "depth": ((H, W), np.float32) if bf is not None else None}, on_gpu,
+                            pinned=False, synchronize=False)
+        with self._ordered(a, b, out["disparity"], out["depth"]):
+            L.check(self._lib.hv_stereo_sgm(self._h, L.ptr(a), L.ptr(b), H, W, channels, ctypes.byref(prm), L.ptr(out["disparity"]),
+                                            L.ptr(out["depth"]), L.location(a)))
+        return out["disparity"], out["depth"]
+
     def remap(self, img, map_x, map_y, linear=False):
         """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU; the maps are [H, W] like the image.
         Host arrays, or a torch CUDA tensor: the image never leaves the device, and maps that are float32 CUDA tensors are read
