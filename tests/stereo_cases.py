@@ -45,6 +45,98 @@ def textured_pair(H, W, channels, seed):
     return (left[..., 0], right[..., 0]) if channels == 1 else (left, right)
 
 
+def smooth_texture(rng, H, W, channels=1):
+    """Random uint8 [H,W,channels] after a 3-tap blur along both axes: the texture of textured_pair."""
+    tex = rng.integers(0, 256, (H, W, channels)).astype(np.float64)
+    for axis in (0, 1):
+        tex = (np.roll(tex, 1, axis) + 2 * tex + np.roll(tex, -1, axis)) / 4
+    return np.clip(np.rint(tex), 0, 255).astype(np.uint8)
+
+
+def staircase(W, shifts, rows=4, channels=1, seed=1):
+    """Smooth texture, the right image cut in bands of `rows` rows, band b moved by shifts[b]: right[band, x] = left[band, x + k],
+    so that a left pixel of band b has the disparity shifts[b].  -> (left, right) uint8 [rows len(shifts), W] or [.., W, 3]"""
+    tex = smooth_texture(np.random.default_rng(seed), rows * len(shifts), W + max(shifts), channels)
+    left = tex[:, :W]
+    right = np.empty_like(left)
+    for b, k in enumerate(shifts):
+        right[b * rows:(b + 1) * rows] = tex[b * rows:(b + 1) * rows, k:k + W]
+    if channels == 1:
+        left, right = left[..., 0], right[..., 0]
+    return np.ascontiguousarray(left), np.ascontiguousarray(right)
+
+
+def shifted_noise(H, W, k, seed):
+    """planted_shift with a little noise of its own in the right image, so that costs tie and nearly tie.  -> (left, right) [H,W]"""
+    rng = np.random.default_rng(seed)
+    left, right = planted_shift(H, W, k, seed)
+    noisy = right.astype(np.int32) + rng.integers(-6, 7, right.shape)
+    return left, np.clip(noisy, 0, 255).astype(np.uint8)
+
+
+def left_of_image_pair(H=8, W=28, k=3, columns=3, seed=0):
+    """right = left moved by k, then the first columns of left replaced by 255 - right: the census of a left pixel at x < k looks
+    least unlike a right pixel that lies outside the image's left edge.  -> (left, right) [H,W]"""
+    left, right = planted_shift(H, W, k, seed)
+    left = left.copy()
+    left[:, :columns] = 255 - right[:, :columns]
+    return left, right
+
+
+# the shifts of the staircases: on both sides of every border between two rows of 16 lanes of the path kernel's wave (16, 32, 48
+# for D = 64; twice and four times that for D = 128 and 256, where a lane holds 2 and 4 disparities), and the ends of the range
+_STAIR_64 = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49, 62, 63)
+_STAIR_128 = (2, 30, 32, 34, 62, 64, 66, 94, 96, 98, 124, 127)
+_STAIR_256 = (3, 60, 64, 68, 124, 128, 132, 188, 192, 196, 252, 255)
+BF_24 = float(np.array([0x4166B3A7], np.uint32).view(np.float32)[0])  # 14.41886...: a float32 whose mantissa uses all 24 bits
+_SGM = dict(p1=10, p2=120, uniqueness_ratio=15, max_diff=1, paths=8, bf=BF_24, min_depth=0.0, max_depth=np.inf)
+# cases whose events need their own number of paths; every other case is also run with the other one on the GPU
+OWN_PATHS = ("wide_2x257_D256_p1023", "equality_u0", "equality_u20", "equality_u50", "left_of_image_maxdiff1", "left_of_image_maxdiff-1",
+             "maxdiff3_9x40", "depth_cuts_9x40")
+
+
+def _planted():
+    cases = []
+
+    def add(name, pair, **params):
+        cases.append((name, pair[0], pair[1], {**_SGM, **params}))
+
+    add("stair_D64", staircase(140, _STAIR_64), num_disparities=64)
+    add("stair_D128", staircase(220, _STAIR_128), num_disparities=128)
+    add("stair_D256", staircase(330, _STAIR_256), num_disparities=256)
+    add("stair_D64_rgb", staircase(140, _STAIR_64, channels=3), num_disparities=64)
+    # wide rows: one, two (the second of one pixel) and three tiles of 256 of the winner kernel; a band of one row per shift
+    for W in (256, 257, 513):
+        add(f"wide_3x{W}_D16", staircase(W, (3, 9, 15), rows=1, seed=W), num_disparities=16)
+        add(f"wide_3x{W}_D256", staircase(W, (40, 130, 250), rows=1, seed=W), num_disparities=256)
+    add("wide_2x257_D256_p1023", staircase(257, (70, 200), rows=1, seed=2), num_disparities=256, p1=1023, p2=1023)  # the largest keys
+    # path starts: n = H, W and H + W - 1 starts per direction, four to a workgroup; W = 6, 41, 43, 40 and H + W - 1 = 46, 46, 47,
+    # 48, 49 take every residue mod 4
+    for H, W in ((41, 6), (6, 41), (5, 43), (9, 40), (7, 43)):
+        add(f"starts_{H}x{W}", textured_pair(H, W, 1, seed=H * 100 + W), num_disparities=16)
+    # rule 6 at equality: the seeds that tools/search_stereo_cases.py settled on
+    for u, seed in ((0, 995), (20, 166), (50, 55)):
+        add(f"equality_u{u}", shifted_noise(6, 24, 5, seed), num_disparities=16, uniqueness_ratio=u)
+    # a unique winner that points left of the image, with the left-right check and without it
+    for max_diff in (1, -1):
+        add(f"left_of_image_maxdiff{max_diff}", left_of_image_pair(), num_disparities=16, paths=4, p1=100, p2=1023, uniqueness_ratio=0,
+            max_diff=max_diff)
+    add("maxdiff3_9x40", textured_pair(9, 40, 1, seed=24), num_disparities=16, max_diff=3)
+    # depth cuts that some pixel's depth equals: the pair has pixels with d16 = 115 (the near cut) and d16 = 33 (the far cut), and
+    # rule 10 is one float32 multiplication and one division
+    near, far = (float(np.float32(BF_24) * np.float32(16.0) / np.float32(d16)) for d16 in (115, 33))
+    add("depth_cuts_9x40", textured_pair(9, 40, 1, seed=940), num_disparities=16, min_depth=near, max_depth=far)
+    return cases
+
+
+PLANTED = _planted()  # [(name, left, right, params)]
+
+
+def planted(name):
+    """-> (left, right, params) of the named case"""
+    return next(c[1:] for c in PLANTED if c[0] == name)
+
+
 def synthetic_pair(i, config="tiny_160x120_2cm", baseline=BASELINE):
     """-> (rgb_left, rgb_right, depth_left, T_cw, stream) of pose i"""
     from pyslam_amd.synthetic import SyntheticRGBD
