@@ -174,7 +174,8 @@ int hv_filter_shadow_points_on_stream(hv_volume *v, const float *depth, int32_t 
  *   9 disparity   d16 for valid pixels, -16 for invalid ones
  *  10 depth       (bf * 16f) / float(d16): one float32 multiply, one correctly rounded divide; 0 where d16 <= 0, where the result is
  *                 < min_depth, or > max_depth when max_depth is finite
- * No speckle filter: hv_filter_shadow_points and hv_tsdf_remove_components exist downstream.
+ * The speckle filter of cv2.StereoSGBM (speckleWindowSize, speckleRange) is a step of its own: hv_stereo_sgm_speckle runs it on the
+ * disparity of rule 9 before anything leaves the device, hv_filter_speckles on any image (both below).
  * left / right: [height,width] (channels 1) or [height,width,3] uint8, both outputs [height,width]; either output may be NULL, not
  * both.  `loc` as in hv_filter_shadow_points: host arrays are complete on return, a device call is queued on the volume's stream
  * and returns.  Works on a volume of any mode and reads nothing of it.  Scratch is owned by the handle, grown on demand and freed by
@@ -196,6 +197,53 @@ typedef struct hv_stereo_params {
 int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
                   const hv_stereo_params *params, int16_t *disparity_out /* may be NULL */, float *depth_out /* may be NULL */,
                   int32_t loc);
+
+/* ---- speckle filter: small connected regions of a disparity or depth image ------------------------------
+ * hv_filter_speckles: the rule of cv2.filterSpeckles(img, newVal, maxSpeckleSize, maxDiff), as cv2.StereoSGBM.compute applies it
+ * to its disparity (pyslam/depth_estimation/depth_estimator_base.py:97-108 sets speckleWindowSize = 50, speckleRange = 1).  OpenCV
+ * is not a dependency: parity is by rule, restated in numpy in tests/speckle_reference.py, and the library is held to that
+ * restatement bit for bit (tests/golden/speckle_opencv.npz pins it to OpenCV wherever tools/make_golden_speckle.py has run).
+ * image: [height,width] of kind HV_SPECKLE_I16 (disparity in sixteenths) or HV_SPECKLE_F32 (depth).
+ *   S1 valid      a pixel is valid iff value != new_val: an integer compare for int16, the IEEE compare for float32 (NaN is valid;
+ *                 -0.0 is invalid when new_val is 0.0).  new_val is converted to the image's type: for int16 it must be an integer in
+ *                 -32768..32767, for float32 it is rounded to float32
+ *   S2 link       two 4-neighbours link iff both are valid and |a - b| <= max_diff.  int16: the difference is taken in int32 (-32768
+ *                 against 32767 is 65535, no wrap) and compared with floor(max_diff); float32: fabsf(a - b) <= (float)max_diff in
+ *                 float32 (NaN and inf - inf never link).  The comparison is between ADJACENT pixels, not against a seed
+ *   S3 component  the classes of the transitive closure of S2 over the valid pixels
+ *   S4 label      the smallest row-major index y width + x in the component; -1 for an invalid pixel
+ *   S5 size       the component's pixel count (int32; height width < 2^30)
+ *   S6 removal    every pixel of a component with size <= max_speckle_size is set to new_val; every other pixel is copied bit for
+ *                 bit.  max_speckle_size = 0 removes nothing; labels and stats are produced all the same
+ *   S7 depth      depth_inout (optional, float32 [height,width]) gets 0.0f where S6 removed the pixel, every other pixel keeps its bits
+ * stats (all exact, independent of the order of execution): valid_pixels, components, largest (the largest size, 0 without a valid
+ * pixel), removed_components, removed_pixels.
+ * out: [height,width] of the image's kind, may be image itself (in place); labels_out: int32 [height,width].  `loc` as in
+ * hv_filter_shadow_points: host arrays are staged by the library and complete on return; a device call is queued on the volume's
+ * stream and returns - unless stats is given: the call then waits for the stream.  Works on a volume of any mode and reads nothing
+ * of the map.  Scratch (a parent and a size array, 8 bytes per pixel) is owned by the handle, grown on demand and freed by
+ * hv_destroy.
+ * HV_ERR_INVALID before anything is launched or written: a NULL handle, image or out; a kind other than the two; height or width
+ * < 1 or > 32768, or 2^30 pixels and more; max_speckle_size < 0; max_diff negative, NaN or infinite (int16: above 65535); an int16
+ * new_val that is no integer of the type; an out, labels_out or depth_inout that overlaps image other than out == image exactly.
+ * HV_ERR_CAPACITY when the scratch cannot be allocated.
+ *
+ * hv_stereo_sgm_speckle: hv_stereo_sgm followed, on the device, by the filter on the disparity of rule 9 with new_val = -16,
+ * max_speckle_size = speckle_window_size and max_diff = 16 speckle_range (cv2.StereoSGBM's own call); depth_out (rule 10) is zeroed
+ * by S7.  With host images the disparity does not visit the host between the two steps.  speckle_window_size in 1..2^30 (0 is
+ * refused: hv_stereo_sgm is that call), speckle_range in 0..4095; everything else as hv_stereo_sgm.  stats (may be NULL, host
+ * memory) are the filter's; when given, the call waits for the stream. */
+typedef enum hv_speckle_kind { HV_SPECKLE_I16 = 0, HV_SPECKLE_F32 = 1 } hv_speckle_kind;
+typedef struct hv_speckle_stats {
+    int64_t valid_pixels, components, largest, removed_components, removed_pixels;
+} hv_speckle_stats;
+int hv_filter_speckles(hv_volume *v, const void *image, int32_t kind /* HV_SPECKLE_I16 | HV_SPECKLE_F32 */, int32_t height, int32_t width,
+                       double new_val, int64_t max_speckle_size, double max_diff, void *out, float *depth_inout /* may be NULL */,
+                       int32_t *labels_out /* may be NULL */, hv_speckle_stats *stats /* may be NULL, host */, int32_t loc);
+int hv_stereo_sgm_speckle(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
+                          const hv_stereo_params *params, int32_t speckle_window_size, int32_t speckle_range,
+                          int16_t *disparity_out /* may be NULL */, float *depth_out /* may be NULL */,
+                          hv_speckle_stats *stats /* may be NULL, host */, int32_t loc);
 
 /* get_voxels(min_count, min_confidence) (voxel_block_grid.hpp:717-819): rows = sum / count.
  * Pass points == NULL to query *n only.  At most `cap` rows are written; *n is the full count. */

@@ -247,6 +247,13 @@ class HvStereoParams(_c.Structure):
                 ("bf", _f32), ("min_depth", _f32), ("max_depth", _f32)]
 
 
+HV_SPECKLE_I16, HV_SPECKLE_F32 = 0, 1
+
+
+class HvSpeckleStats(_c.Structure):
+    _fields_ = [("valid_pixels", _i64), ("components", _i64), ("largest", _i64), ("removed_components", _i64), ("removed_pixels", _i64)]
+
+
 # name -> (restype, argtypes); mirrors include/hipvol.h one to one
 SIGNATURES = {
     "hv_last_error": (_c.c_char_p, []),
@@ -272,6 +279,9 @@ SIGNATURES = {
     "hv_filter_shadow_points": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _i32]),
     "hv_filter_shadow_points_on_stream": (_i32, [_vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "hv_stereo_sgm": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(HvStereoParams), _vp, _vp, _i32]),
+    "hv_filter_speckles": (_i32, [_vp, _vp, _i32, _i32, _i32, _f64, _i64, _f64, _vp, _vp, _vp, _c.POINTER(HvSpeckleStats), _i32]),
+    "hv_stereo_sgm_speckle": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(HvStereoParams), _i32, _i32, _vp, _vp,
+                                     _c.POINTER(HvSpeckleStats), _i32]),
     "hv_get_voxels": (_i32, [_vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_bb": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_frustum": (_i32, [_vp, _vp, _i32, _i32, _vp, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),

@@ -581,6 +581,9 @@ struct hv_volume {
     // hv_stereo_sgm: [S npx D u16][census left npx u64][census right npx u64][d_left npx i16][right keys npx u32] (hv_stereo.hip)
     void *stereo_buf = nullptr;
     size_t stereo_buf_bytes = 0;
+    // hv_filter_speckles: [parent npx i32][size npx i32] (hv_speckle.hip)
+    void *speckle_buf = nullptr;
+    size_t speckle_buf_bytes = 0;
     // the halo merge's plan of hv_merge_halo_plan_device (hv_halo.hip): [shared keys n*3 i32][action n u8], device memory
     void *halo_plan = nullptr;
     size_t halo_plan_bytes = 0;
@@ -711,6 +714,10 @@ int hv_ray_cast_launch(hv_volume *v, int32_t height, int32_t width, const double
                        double depth_max, double weight_threshold, double depth_scale, float *depth, float *vertex, float *normal,
                        float *color, uint8_t *mask);
 void hv_segments_cache_free(void *cache); // hv_semantic_ops.hip
+// hv_speckle.hip: one speckle filter queued on the volume's stream over device arrays (arguments checked by the caller; out may be
+// image itself).  d_stats: 5 uint64 of device memory in the order of hv_speckle_stats, zeroed here, or null.
+int hv_speckle_launch(hv_volume *v, const char *fn, const void *image, int32_t kind, int32_t height, int32_t width, double new_val,
+                      int64_t max_speckle_size, double max_diff, void *out, float *depth, int32_t *labels, unsigned long long *d_stats);
 // hv_halo.hip: claim the k unit / block keys [k,3] (device memory) of a call that is handed keys, and verify the claims - capacity
 // gate, k_tsdf_import_claim, hv_claims_fit, at most 8 retries.  A pool that is too small grows before anything is written, or the
 // claim pass is rolled back, the volume is what it was and the call fails with HV_ERR_CAPACITY.  Waits for the GPU.

@@ -249,10 +249,11 @@ static void st_launch_path(hipStream_t s, const uint64_t *cl, const uint64_t *cr
 
 static size_t st_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
-extern "C" {
-
-int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
-                  const hv_stereo_params *params, int16_t *disparity_out, float *depth_out, int32_t loc) {
+// The body of both entry points.  speckle_window 0: hv_stereo_sgm, launch for launch.  Positive: the disparity of rule 9 is filtered
+// where it lies on the device (hv_speckle_launch, in place) and rule 10's depth is zeroed where a pixel went.
+static int st_run(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
+                  const hv_stereo_params *params, int32_t speckle_window, int32_t speckle_range, int16_t *disparity_out, float *depth_out,
+                  hv_speckle_stats *stats, int32_t loc) {
     HV_REQUIRE(v != nullptr && left != nullptr && right != nullptr && params != nullptr, HV_ERR_INVALID, "hv_stereo_sgm: null argument");
     HV_REQUIRE(disparity_out != nullptr || depth_out != nullptr, HV_ERR_INVALID, "hv_stereo_sgm: no output asked for");
     HV_REQUIRE(channels == 1 || channels == 3, HV_ERR_INVALID, "hv_stereo_sgm: channels must be 1 or 3");
@@ -271,7 +272,8 @@ int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32
     // scratch of the handle: [S npx D u16][census left npx u64][census right npx u64][d_left npx i16][right keys npx u32]
     const size_t s_bytes = st_align((size_t)npx * D * 2), c_bytes = st_align((size_t)npx * 8), d_bytes = st_align((size_t)npx * 2),
                  r_bytes = st_align((size_t)npx * 4);
-    const size_t want = s_bytes + 2 * c_bytes + d_bytes + r_bytes;
+    const size_t x_bytes = speckle_window > 0 && disparity_out == nullptr ? d_bytes : 0;
+    const size_t want = s_bytes + 2 * c_bytes + d_bytes + r_bytes + x_bytes;
     if (v->stereo_buf == nullptr || v->stereo_buf_bytes < want) {
         if (v->stereo_buf != nullptr) {
             HV_HIP(hipStreamSynchronize(v->stream));
@@ -294,6 +296,7 @@ int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32
     uint32_t *rk = (uint32_t *)(base + s_bytes + 2 * c_bytes + d_bytes);
 
     HvStage st(v, loc);
+    if (speckle_window > 0 && stats != nullptr) st.head(sizeof(unsigned long long) * 5);
     const int i_left = st.in(left, (size_t)npx * channels), i_right = st.in(right, (size_t)npx * channels);
     const int o_disp = st.out(disparity_out, sizeof(int16_t) * npx), o_depth = st.out(depth_out, sizeof(float) * npx);
     int rc = st.commit(&v->stage, &v->stage_bytes);
@@ -325,12 +328,39 @@ int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32
                        P.uniqueness_ratio, dl, rk);
     hv_profile_end(v, 0);
     hv_profile_begin(v);
+    // (the filter needs rule 9's disparity on the device: in scratch of the handle when the caller asks for depth alone)
+    int16_t *disp = st.dev<int16_t>(o_disp);
+    if (speckle_window > 0 && disp == nullptr) disp = (int16_t *)(base + s_bytes + 2 * c_bytes + d_bytes + r_bytes);
     hipLaunchKernelGGL(k_stereo_finish, dim3(px_grid), dim3(256), 0, s, S, dl, rk, height, width, D, P.max_diff, P.bf, P.min_depth, P.max_depth,
-                       st.dev<int16_t>(o_disp), st.dev<float>(o_depth));
+                       disp, st.dev<float>(o_depth));
     hv_profile_end(v, npx);
     HV_HIP(hipGetLastError());
     // host images: copied back and complete on return; device images: queued on the volume's stream like every other launch
-    return st.finish();
+    if (speckle_window <= 0) return st.finish();
+    rc = hv_speckle_launch(v, "hv_stereo_sgm_speckle", disp, HV_SPECKLE_I16, height, width, -16.0, speckle_window, 16.0 * speckle_range, disp,
+                           st.dev<float>(o_depth), nullptr, (unsigned long long *)st.head_dev);
+    if (rc != HV_OK) return rc;
+    unsigned long long h[5] = {0, 0, 0, 0, 0};
+    rc = st.finish(stats != nullptr ? h : nullptr, sizeof h);  // (stats: waits for the stream, for either loc)
+    if (rc != HV_OK) return rc;
+    if (stats != nullptr) *stats = hv_speckle_stats{(int64_t)h[0], (int64_t)h[1], (int64_t)h[2], (int64_t)h[3], (int64_t)h[4]};
+    return HV_OK;
+}
+
+extern "C" {
+
+int hv_stereo_sgm(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
+                  const hv_stereo_params *params, int16_t *disparity_out, float *depth_out, int32_t loc) {
+    return st_run(v, left, right, height, width, channels, params, 0, 0, disparity_out, depth_out, nullptr, loc);
+}
+
+int hv_stereo_sgm_speckle(hv_volume *v, const uint8_t *left, const uint8_t *right, int32_t height, int32_t width, int32_t channels,
+                          const hv_stereo_params *params, int32_t speckle_window_size, int32_t speckle_range, int16_t *disparity_out,
+                          float *depth_out, hv_speckle_stats *stats, int32_t loc) {
+    HV_REQUIRE(speckle_window_size >= 1 && speckle_window_size <= 1 << 30, HV_ERR_INVALID,
+               "hv_stereo_sgm_speckle: speckle_window_size must be in 1..2^30 (hv_stereo_sgm is the call without the filter)");
+    HV_REQUIRE(speckle_range >= 0 && speckle_range <= 4095, HV_ERR_INVALID, "hv_stereo_sgm_speckle: speckle_range must be in 0..4095");
+    return st_run(v, left, right, height, width, channels, params, speckle_window_size, speckle_range, disparity_out, depth_out, stats, loc);
 }
 
 } // extern "C"

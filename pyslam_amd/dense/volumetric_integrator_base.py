@@ -681,7 +681,13 @@ class VolumetricIntegratorBase:
             if self.depth_estimator is None and getattr(self, "depth_estimator_pending", False):
                 from ..depth_estimation import DepthEstimatorSgm
 
-                self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera)
+                # the reference's DepthEstimatorSgbm filters speckles with (50, 1); here the filter is off until the window is set
+                window = int(getattr(Parameters, "kVolumetricIntegrationSgmSpeckleWindowSize", 0))
+                if window > 0:
+                    self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera, speckle_window_size=window,
+                                                             speckle_range=int(getattr(Parameters, "kVolumetricIntegrationSgmSpeckleRange", 1)))
+                else:
+                    self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera)
                 self.depth_estimator_pending = False
             if self.depth_estimator is None:
                 return None, None, None, None, None  # skip this keyframe

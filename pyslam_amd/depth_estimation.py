@@ -61,7 +61,8 @@ class DepthEstimatorSgm:
     infer(image, image_right) -> (depth, None): the pair is uploaded once and the depth stays a float32 CUDA tensor when
     `keep_on_device`, a numpy array otherwise; disparity_map is the int16 disparity in sixteenths (-16 = invalid), in the same
     place.  An invalid pixel has depth 0 (the reference wrapper's bf is not reproduced).  sgm_params: num_disparities, p1, p2,
-    uniqueness_ratio, max_diff, paths."""
+    uniqueness_ratio, max_diff, paths, speckle_window_size, speckle_range (the reference's speckle filter is
+    speckle_window_size=50, speckle_range=1; the default 0 runs none)."""
 
     def __init__(self, volume, camera, keep_on_device=True, min_depth=0.0, max_depth=np.inf, **sgm_params):
         self.volume = volume

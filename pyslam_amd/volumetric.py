@@ -371,6 +371,28 @@ class VoxelLookup:
         return f"VoxelLookup(n={len(self.status)}, labels={self.class_id is not None}, stats={self.stats})"
 
 
+class SpeckleStats(_Stats):
+    """What one speckle filter found (hv_speckle_stats): valid_pixels = pixels that differ from new_val, components = connected
+    regions among them, largest = the largest region's pixel count, removed_components / removed_pixels = what the size rule took."""
+
+    __slots__ = ("valid_pixels", "components", "largest", "removed_components", "removed_pixels")
+
+
+class SpeckleResult:
+    """What filter_speckles returns when more than the image is asked for: image (the filtered image), depth (the companion depth
+    with 0 where a pixel was removed, or None), labels (int32 [H,W]: the smallest row-major index of the pixel's region, -1 for an
+    invalid pixel, or None), stats (SpeckleStats or None)."""
+
+    def __init__(self, image, depth, labels, stats):
+        self.image = image
+        self.depth = depth
+        self.labels = labels
+        self.stats = stats
+
+    def __repr__(self):
+        return f"SpeckleResult(shape={tuple(self.image.shape)}, depth={self.depth is not None}, labels={self.labels is not None}, stats={self.stats})"
+
+
 # hv_tsdf_distance_field's cell classes (include/hipvol.h): DIST_SITE is OR-ed onto DIST_FREE or DIST_INSIDE
 DIST_UNKNOWN, DIST_FREE, DIST_INSIDE, DIST_SITE = L.HV_DIST_UNKNOWN, L.HV_DIST_FREE, L.HV_DIST_INSIDE, L.HV_DIST_SITE
 
@@ -789,12 +811,77 @@ class _Volume:
                 L.check(self._lib.hv_filter_shadow_points(*args, L.location(d)))
         return out
 
+    def filter_speckles(self, image, max_speckle_size, max_diff, new_val=None, depth=None, labels=False, stats=False):
+        """cv2.filterSpeckles(image, new_val, max_speckle_size, max_diff) on the GPU (hv_filter_speckles, rules S1 - S7 in
+        include/hipvol.h): the pixels of every 4-connected region of at most max_speckle_size pixels - neighbours belong together
+        when both differ from new_val and from each other by at most max_diff - are set to new_val.  image: [H,W] int16 (disparity in
+        sixteenths; new_val defaults to -16) or float32 (depth; new_val defaults to 0.0).  numpy in, numpy out; a torch CUDA tensor
+        on the volume's GPU in, tensors on that GPU out, queued on the volume's stream.  The inputs are never written.
+        -> the filtered image; with depth= (a float32 [H,W] companion that gets 0 where a pixel is removed), labels=True or
+        stats=True a SpeckleResult (stats=True waits for the GPU).  Works on a volume of any mode and reads nothing of it."""
+        on_gpu = L.location(image) == L.HV_DEVICE
+        if on_gpu:
+            import torch
+
+            kinds = {torch.int16: L.HV_SPECKLE_I16, torch.float32: L.HV_SPECKLE_F32}
+            if image.device != self._device():
+                raise ValueError(f"filter_speckles: the image lives on {image.device}, the volume on {self._device()}")
+            a = image.contiguous()
+        else:
+            a = image.cpu().numpy() if _is_torch(image) else np.asarray(image)
+            kinds = {np.dtype(np.int16): L.HV_SPECKLE_I16, np.dtype(np.float32): L.HV_SPECKLE_F32}
+            a = np.ascontiguousarray(a)
+        if a.dtype not in kinds:
+            raise ValueError(f"filter_speckles: the image must be int16 or float32, got {a.dtype}")
+        kind = kinds[a.dtype]
+        if a.ndim != 2:
+            raise ValueError(f"filter_speckles: the image must be [H, W], got {tuple(a.shape)}")
+        H, W = int(a.shape[0]), int(a.shape[1])
+        # what hv_filter_speckles answers with HV_ERR_INVALID, refused here before anything is allocated
+        if H < 1 or W < 1 or H > 32768 or W > 32768 or H * W >= 1 << 30:
+            raise ValueError(f"filter_speckles: bad image size {tuple(a.shape)}")
+        if int(max_speckle_size) != max_speckle_size or int(max_speckle_size) < 0:
+            raise ValueError(f"filter_speckles: max_speckle_size must be an integer >= 0, got {max_speckle_size}")
+        md = float(max_diff)
+        if not (0.0 <= md < np.inf) or (kind == L.HV_SPECKLE_I16 and md > 65535.0):
+            raise ValueError(f"filter_speckles: max_diff must be finite and not negative (int16: at most 65535), got {max_diff}")
+        nv = float(new_val) if new_val is not None else (-16.0 if kind == L.HV_SPECKLE_I16 else 0.0)
+        if kind == L.HV_SPECKLE_I16 and not (-32768.0 <= nv <= 32767.0 and nv == np.floor(nv)):
+            raise ValueError(f"filter_speckles: new_val of an int16 image must be an integer in -32768..32767, got {new_val}")
+        d = None
+        if depth is not None:
+            if (L.location(depth) == L.HV_DEVICE) != on_gpu:
+                raise ValueError("filter_speckles: image and depth must live in the same place")
+            if on_gpu:
+                if depth.dtype != torch.float32 or depth.device != self._device():
+                    raise ValueError(f"filter_speckles: depth must be a float32 tensor on {self._device()}")
+                d = depth.clone(memory_format=torch.contiguous_format)  # (the library writes it in place: the caller's stays)
+            else:
+                d = depth.cpu().numpy() if _is_torch(depth) else np.asarray(depth)
+                if d.dtype != np.float32:
+                    raise ValueError(f"filter_speckles: depth must be float32, got {d.dtype}")
+                d = np.array(d, dtype=np.float32, order="C", copy=True)
+            if tuple(d.shape) != (H, W):
+                raise ValueError(f"filter_speckles: depth {tuple(d.shape)} must have the image's shape {(H, W)}")
+        out = self._results({"image": ((H, W), np.int16 if kind == L.HV_SPECKLE_I16 else np.float32),
+                             "labels": ((H, W), np.int32) if labels else None}, on_gpu, pinned=False, synchronize=False)
+        st = L.HvSpeckleStats() if stats else None
+        with self._ordered(a, d, out["image"], out["labels"]):
+            L.check(self._lib.hv_filter_speckles(self._h, L.ptr(a), kind, H, W, nv, int(max_speckle_size), md, L.ptr(out["image"]), L.ptr(d),
+                                                 L.ptr(out["labels"]), ctypes.byref(st) if stats else None, L.location(a)))
+        if depth is None and not labels and not stats:
+            return out["image"]
+        return SpeckleResult(out["image"], d, out["labels"], _stats(SpeckleStats, st) if stats else None)
+
     def stereo_sgm(self, left, right, num_disparities=128, p1=10, p2=120, uniqueness_ratio=15, max_diff=1, paths=8, bf=None,
-                   min_depth=0.0, max_depth=np.inf):
+                   min_depth=0.0, max_depth=np.inf, speckle_window_size=0, speckle_range=1):
         """Census semi-global stereo matching of a rectified uint8 pair, [H,W] or [H,W,3] (hv_stereo_sgm, the rules in
         include/hipvol.h) -> (disparity int16 [H,W] in sixteenths of a pixel, -16 = invalid; depth float32 [H,W] metres = bf 16 /
         disparity, 0 = none - or None when bf is None).  numpy arrays in, numpy arrays out; torch CUDA tensors in, tensors on the
-        same GPU out, queued on the volume's stream.  Works on a volume of any mode and reads nothing of it."""
+        same GPU out, queued on the volume's stream.  Works on a volume of any mode and reads nothing of it.
+        speckle_window_size > 0 (cv2.StereoSGBM's speckleWindowSize; the reference sets 50) removes, on the device, the connected
+        regions of at most that many pixels whose neighbouring disparities differ by at most speckle_range pixels
+        (hv_stereo_sgm_speckle; filter_speckles is the step on its own): disparity -16 and depth 0 there.  0: no filter."""
         on_gpu = L.location(left) == L.HV_DEVICE
         if on_gpu != (L.location(right) == L.HV_DEVICE):
             raise ValueError("stereo_sgm: left and right must live in the same place")
@@ -830,13 +917,21 @@ class _Volume:
             raise ValueError(f"stereo_sgm: paths must be 4 or 8, got {paths}")
         if bf is not None and not 0.0 < float(bf) <= float(np.finfo(np.float32).max):  # (the library reads a float32)
             raise ValueError(f"stereo_sgm: bf must be finite and positive, got {bf}")
+        if int(speckle_window_size) != speckle_window_size or not 0 <= int(speckle_window_size) <= 1 << 30:
+            raise ValueError(f"stereo_sgm: speckle_window_size must be an integer in 0..2^30, got {speckle_window_size}")
+        if int(speckle_range) != speckle_range or not 0 <= int(speckle_range) <= 4095:
+            raise ValueError(f"stereo_sgm: speckle_range must be an integer in 0..4095, got {speckle_range}")
         prm = L.HvStereoParams(int(num_disparities), int(p1), int(p2), int(uniqueness_ratio), int(max_diff), int(paths),
                                float(bf) if bf is not None else 0.0, float(min_depth), float(max_depth))
         out = self._results({"disparity": ((H, W), np.int16), "depth": ((H, W), np.float32) if bf is not None else None}, on_gpu,
                             pinned=False, synchronize=False)
         with self._ordered(a, b, out["disparity"], out["depth"]):
-            L.check(self._lib.hv_stereo_sgm(self._h, L.ptr(a), L.ptr(b), H, W, channels, ctypes.byref(prm), L.ptr(out["disparity"]),
-                                            L.ptr(out["depth"]), L.location(a)))
+            if int(speckle_window_size) == 0:
+                L.check(self._lib.hv_stereo_sgm(self._h, L.ptr(a), L.ptr(b), H, W, channels, ctypes.byref(prm), L.ptr(out["disparity"]),
+                                                L.ptr(out["depth"]), L.location(a)))
+            else:
+                L.check(self._lib.hv_stereo_sgm_speckle(self._h, L.ptr(a), L.ptr(b), H, W, channels, ctypes.byref(prm), int(speckle_window_size),
+                                                        int(speckle_range), L.ptr(out["disparity"]), L.ptr(out["depth"]), None, L.location(a)))
         return out["disparity"], out["depth"]
 
     def remap(self, img, map_x, map_y, linear=False):

@@ -8,6 +8,12 @@ Prints one JSON line; per variant ("paths8", "paths4"):
   valid_share      share of pixels with a disparity (first pair)
   flow_kf_per_s    keyframes per second of: pair (host uint8) -> upload -> stereo_sgm -> shadow filter -> TSDF integrate at 10 mm,
                    N_KEYFRAMES keyframes, best of FLOW_REPEATS passes on a fresh volume
+  with_filter      the same call with speckle_window_size = 50, speckle_range = 1 (the reference's values): stages_ms (the four brackets
+                   of the matcher, then the filter's four [local, cross, flatten, apply]), kernel_ms, filter_kernel_ms, filter_share (of
+                   the matcher's kernel time in the same calls), device_wall_ms, flow_kf_per_s
+  host_wall_ms / with_filter.host_wall_ms   wall time of one call on host arrays into host arrays
+"filter": hv_filter_speckles alone at 50 / 1 (device tensors, kernel time of its four brackets): "matcher_output" on the disparity
+of the first pair (paths 8), "all_equal" on a constant image - one region, the contention case of the size count.
 and "stub_net": the same flow with DepthEstimatorStereoTorch on make_stub_stereo_net() in the matcher's place (a 5x5 convolution
 whose disparity has nothing to do with the scene: the figure the stereo configuration was quoted with before).
 
@@ -42,6 +48,27 @@ def pairs(s, n, cache):
     if cache:
         np.savez(cache, left=left, right=right, T=T)
     return left, right, T
+
+
+def timed_calls(vol, call):
+    """WARMUP + REPEATS calls, each between two synchronisations -> {"stages": [REPEATS, brackets] kernel ms, "walls": [REPEATS] ms}"""
+    stages, walls = [], []
+    for rep in range(WARMUP + REPEATS):
+        vol.synchronize()
+        torch.cuda.synchronize()
+        vol.profile_enable(True)
+        t0 = time.perf_counter()
+        call()
+        vol.synchronize()
+        torch.cuda.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        per_stage = [float(x) for x in vol.profile_launches()]
+        vol.profile_read()
+        vol.profile_enable(False)
+        if rep >= WARMUP:
+            stages.append(per_stage)
+            walls.append(wall)
+    return {"stages": np.asarray(stages, np.float64), "walls": walls}
 
 
 def main():
@@ -102,11 +129,30 @@ def main():
                 stages.append(per_stage)
                 walls.append(wall)
         st = np.asarray(stages, np.float64)
+        filtered = timed_calls(vol, lambda: vol.stereo_sgm(dl, dr, num_disparities=D, paths=paths, bf=bf, speckle_window_size=50, speckle_range=1))
+        fst = filtered["stages"]
+        host = timed_calls(vol, lambda: vol.stereo_sgm(left[0], right[0], num_disparities=D, paths=paths, bf=bf))
+        host_filtered = timed_calls(vol, lambda: vol.stereo_sgm(left[0], right[0], num_disparities=D, paths=paths, bf=bf, speckle_window_size=50,
+                                                                 speckle_range=1))
+        kf_f, units_f = flow(lambda v, a, b: v.stereo_sgm(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), num_disparities=D, paths=paths,
+                                                          bf=bf, speckle_window_size=50, speckle_range=1)[1])
+        with_filter = {"stages_ms": [round(float(x), 3) for x in np.median(fst, axis=0)], "kernel_ms": med(fst.sum(axis=1)),
+                       "filter_kernel_ms": med(fst[:, 4:].sum(axis=1)),
+                       "filter_share": round(float(np.median(fst[:, 4:].sum(axis=1) / fst[:, :4].sum(axis=1))), 4),
+                       "device_wall_ms": med(filtered["walls"]), "host_wall_ms": med(host_filtered["walls"]), "flow_kf_per_s": kf_f,
+                       "flow_units": units_f}
         kf, units = flow(lambda v, a, b: v.stereo_sgm(torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), num_disparities=D, paths=paths, bf=bf)[1])
         out[name] = {"stages_ms": [round(float(x), 3) for x in np.median(st, axis=0)], "kernel_ms": med(st.sum(axis=1)),
                      "kernel_ms_spread": [round(float(st.sum(axis=1).min()), 3), round(float(st.sum(axis=1).max()), 3)],
                      "device_wall_ms": med(walls), "device_wall_ms_spread": [round(min(walls), 3), round(max(walls), 3)],
-                     "valid_share": round(float((disp >= 0).float().mean().item()), 4), "flow_kf_per_s": kf, "flow_units": units}
+                     "valid_share": round(float((disp >= 0).float().mean().item()), 4), "flow_kf_per_s": kf, "flow_units": units,
+                     "host_wall_ms": med(host["walls"]), "with_filter": with_filter}
+    disp8 = vol.stereo_sgm(dl, dr, num_disparities=D, paths=8, bf=bf)[0]
+    out["filter"] = {}
+    for name, image in (("matcher_output", disp8), ("all_equal", torch.full_like(disp8, 160))):
+        t = timed_calls(vol, lambda: vol.filter_speckles(image, 50, 16))["stages"]
+        out["filter"][name] = {"stages_ms": [round(float(x), 4) for x in np.median(t, axis=0)], "kernel_ms": round(float(np.median(t.sum(axis=1))), 4),
+                               "kernel_ms_spread": [round(float(t.sum(axis=1).min()), 4), round(float(t.sum(axis=1).max()), 4)]}
     cam = type("Camera", (), {"bf": bf})()
     stub = DepthEstimatorStereoTorch(make_stub_stereo_net(), cam, "cuda", keep_on_device=True)
     kf, units = flow(lambda v, a, b: stub.infer(a, b)[0])
