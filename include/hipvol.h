@@ -245,6 +245,61 @@ int hv_stereo_sgm_speckle(hv_volume *v, const uint8_t *left, const uint8_t *righ
                           int16_t *disparity_out /* may be NULL */, float *depth_out /* may be NULL */,
                           hv_speckle_stats *stats /* may be NULL, host */, int32_t loc);
 
+/* ---- plane-sweep depth for posed monocular keyframes ----------------------------------------------------
+ * hv_mvs_sgm: a uint8 reference image and 1..4 source images of the same shape, each with a 3x4 matrix that takes the reference
+ * pixel and an inverse depth to the source pixel -> the winning plane per reference pixel (int16, sixteenths of a plane, -16 =
+ * invalid: the format of the stereo disparity, so hv_filter_speckles and every consumer of one take it as is) and metric z-depth in
+ * the reference camera (float32, 0 = none).  The weight-free counterpart of the reference's multi-view estimators
+ * (pyslam/depth_estimation/depth_estimator_mvdust3r.py, depth_estimator_mast3r.py) for a posed single-camera stream; parity with
+ * a network is not claimed.  The algorithm is fixed by the rules below, restated in numpy in tests/mvs_reference.py, and the library
+ * is held to that restatement bit for bit.  D = num_planes, N = n_sources; "stereo rule n" is rule n of hv_stereo_sgm above.
+ *   M1 grey, census  stereo rules 1 and 2, unchanged, for the reference image and every source image
+ *   M2 planes        the inverse depth of plane k is w_k = w0 + float(16 k) * step16 in float32: one multiply, one add.
+ *                    w0 = float32(1 / max_depth), 0 for an infinite max_depth; step16 = float32((1 / min_depth - 1 / max_depth) /
+ *                    (16 (D - 1))), both computed in double on the host with exactly these operations and rounded once.  Plane 0 is
+ *                    the farthest
+ *   M3 projection    source view s is a float32 3x4 matrix [A_s | b_s], row-major (for a pinhole pair A = K_s R_sr K_r^-1 and
+ *                    b = K_s t_sr).  For the reference pixel (x, y), in float32 and in this order, ONE multiply and ONE add per
+ *                    term (no fused multiply-add, no fast reciprocal or divide):
+ *                      a_i = (A_i0 * float(x) + A_i1 * float(y)) + A_i2        q_i = a_i + w_k * b_i
+ *                      u = q_0 / q_2, v = q_1 / q_2 (IEEE division)             ur = rintf(u), vr = rintf(v) (ties to even)
+ *                    The view SEES (x, y, k) iff q_2 > 0, 0 <= ur <= W-1 and 0 <= vr <= H-1 all hold as float comparisons (a NaN
+ *                    fails); the source pixel is then (int ur, int vr)
+ *   M4 cost          n = the views that see (x, y, k), sum = the sum of popcount(census_ref(x,y) ^ census_s(ur,vr)) over them:
+ *                    C = (2 sum + n) / (2 n) with C division if n >= min_views, else 64
+ *   M5 paths, winner, uniqueness   stereo rules 4, 5 and 6 on this C.  There is no left-right check
+ *   M6 seen          invalid if fewer than min_views views see (x, y, k*)
+ *   M7 sub-pixel     stereo rule 8 on S gives k16; an invalid pixel gets -16
+ *   M8 speckles      speckle_window_size > 0: hv_filter_speckles on k16 with max_speckle_size = speckle_window_size, max_diff =
+ *                    16 speckle_range and new_val = -16, on the device, exactly as hv_stereo_sgm_speckle does it
+ *   M9 depth         wv = w0 + float(k16) * step16, depth = 1.0f / wv; 0 where the pixel is invalid (after M8) or wv <= 0
+ *  M10 outputs       index_out int16 [height,width] and depth_out float32 [height,width]; either may be NULL, not both
+ * ref: [height,width] (channels 1) or [height,width,3]; sources: n_sources such images behind each other; both at `loc`, as are the
+ * outputs (`loc` as in hv_stereo_sgm, staged by the library for HV_HOST).  views: float[n_sources][12], HOST memory for either loc.
+ * stats (may be NULL, host memory) are the filter's; read only with a filter, and the call then waits for the stream.  Works on a
+ * volume of any mode and reads nothing of it.  Scratch is the handle's stereo scratch, grown on demand: height width (3 D + 8 (1 + N)
+ * + 2) bytes (S uint16, C uint8, 1 + N census images, the winners), each part rounded up to 256 bytes, plus 2 bytes per pixel when a
+ * filter runs and index_out is NULL, plus the filter's own scratch.
+ * HV_ERR_INVALID before anything is launched or written: a NULL image, views or params; both outputs NULL; channels not 1 or 3;
+ * n_sources outside 1..4; min_views outside 1..n_sources; num_planes not a multiple of 16 in 16..256; not 0 < p1 <= p2 <= 1023;
+ * uniqueness_ratio outside 0..99; paths not 4 or 8; min_depth not finite and positive (or so small that step16 is not finite);
+ * max_depth <= min_depth or NaN; a matrix entry that is not finite; the image-size limits of hv_stereo_sgm; speckle_window_size
+ * outside 0..2^30 or, with a filter, speckle_range outside 0..4095.  HV_ERR_CAPACITY when the scratch cannot be allocated. */
+typedef struct hv_mvs_params {
+    int32_t num_planes;          /* 128 */
+    int32_t p1, p2;              /* 10, 120 */
+    int32_t uniqueness_ratio;    /* 15 */
+    int32_t min_views;           /* 1 */
+    int32_t paths;               /* 8 */
+    double min_depth, max_depth; /* metres; max_depth may be +inf */
+    int32_t speckle_window_size; /* 0: no filter */
+    int32_t speckle_range;       /* 1 */
+} hv_mvs_params;
+int hv_mvs_sgm(hv_volume *v, const uint8_t *ref, const uint8_t *sources, int32_t n_sources, int32_t height, int32_t width,
+               int32_t channels, const float *views /* float[n_sources][12], host */, const hv_mvs_params *params,
+               int16_t *index_out /* may be NULL */, float *depth_out /* may be NULL */,
+               hv_speckle_stats *stats /* may be NULL, host */, int32_t loc);
+
 /* get_voxels(min_count, min_confidence) (voxel_block_grid.hpp:717-819): rows = sum / count.
  * Pass points == NULL to query *n only.  At most `cap` rows are written; *n is the full count. */
 int hv_get_voxels(hv_volume *v, int32_t min_count, float min_confidence, float *points,

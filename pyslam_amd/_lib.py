@@ -247,6 +247,11 @@ class HvStereoParams(_c.Structure):
                 ("bf", _f32), ("min_depth", _f32), ("max_depth", _f32)]
 
 
+class HvMvsParams(_c.Structure):
+    _fields_ = [("num_planes", _i32), ("p1", _i32), ("p2", _i32), ("uniqueness_ratio", _i32), ("min_views", _i32), ("paths", _i32),
+                ("min_depth", _f64), ("max_depth", _f64), ("speckle_window_size", _i32), ("speckle_range", _i32)]
+
+
 HV_SPECKLE_I16, HV_SPECKLE_F32 = 0, 1
 
 
@@ -282,6 +287,7 @@ SIGNATURES = {
     "hv_filter_speckles": (_i32, [_vp, _vp, _i32, _i32, _i32, _f64, _i64, _f64, _vp, _vp, _vp, _c.POINTER(HvSpeckleStats), _i32]),
     "hv_stereo_sgm_speckle": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(HvStereoParams), _i32, _i32, _vp, _vp,
                                      _c.POINTER(HvSpeckleStats), _i32]),
+    "hv_mvs_sgm": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _c.POINTER(HvMvsParams), _vp, _vp, _c.POINTER(HvSpeckleStats), _i32]),
     "hv_get_voxels": (_i32, [_vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_bb": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_frustum": (_i32, [_vp, _vp, _i32, _i32, _vp, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),

@@ -43,6 +43,16 @@ class Parameters:
     kVolumetricIntegrationUseDepthEstimator = False
     kVolumetricIntegrationDepthEstimatorType = "DEPTH_RAFT_STEREO"
     kVolumetricIntegrationDepthEstimationFilterShadowPoints = True
+    # kVolumetricIntegrationDepthEstimatorType = "DEPTH_MVS_HIP": plane-sweep depth for a posed single-camera stream
+    # (depth_estimation.DepthEstimatorMvs; read by that type alone).  Depths and baselines in metres
+    kVolumetricIntegrationMvsNumPlanes = 128
+    kVolumetricIntegrationMvsMinDepth = 0.5
+    kVolumetricIntegrationMvsMaxDepth = float("inf")
+    kVolumetricIntegrationMvsMaxSources = 2
+    kVolumetricIntegrationMvsMinBaseline = 0.05
+    kVolumetricIntegrationMvsMaxBaseline = 0.5
+    kVolumetricIntegrationMvsSpeckleWindowSize = 0
+    kVolumetricIntegrationMvsSpeckleRange = 1
     # semantic integration, config_parameters.py:364-380
     kVolumetricSemanticProbabilisticIntegrationUseDepth = True
     kVolumetricSemanticProbabilisticIntegrationDepthThresholdIndoor = 5.0

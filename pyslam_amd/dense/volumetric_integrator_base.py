@@ -658,6 +658,14 @@ class VolumetricIntegratorBase:
                 # the package's own weight-free estimator (hv_stereo_sgm).  It runs on the volume, which the subclass creates after
                 # this: made on first use (estimate_depth_if_needed_and_rectify)
                 self.depth_estimator_pending = True
+            elif getattr(Parameters, "kVolumetricIntegrationDepthEstimatorType", None) == "DEPTH_MVS_HIP":
+                # the weight-free estimator for a posed single-camera stream (hv_mvs_sgm), made on first use like the one above.  Its
+                # projection is a pinhole's: lens distortion is out of its scope
+                if self.calib_map1 is not None:
+                    raise ValueError('"DEPTH_MVS_HIP" matches pinhole images and this camera has lens distortion: undistort first '
+                                     "(hand the front undistorted keyframes and a camera without distortion coefficients)")
+                self.depth_estimator_pending = True
+                self.depth_estimator_kind = "DEPTH_MVS_HIP"
             else:
                 try:
                     from pyslam.depth_estimation.depth_estimator_factory import DepthEstimatorType, depth_estimator_factory  # type: ignore
@@ -679,11 +687,18 @@ class VolumetricIntegratorBase:
         pts3d = None
         if depth is None or getattr(depth, "size", 1) == 0:
             if self.depth_estimator is None and getattr(self, "depth_estimator_pending", False):
-                from ..depth_estimation import DepthEstimatorSgm
+                from ..depth_estimation import DepthEstimatorMvs, DepthEstimatorSgm
 
                 # the reference's DepthEstimatorSgbm filters speckles with (50, 1); here the filter is off until the window is set
                 window = int(getattr(Parameters, "kVolumetricIntegrationSgmSpeckleWindowSize", 0))
-                if window > 0:
+                if getattr(self, "depth_estimator_kind", None) == "DEPTH_MVS_HIP":
+                    P = lambda name, default: getattr(Parameters, "kVolumetricIntegrationMvs" + name, default)
+                    self.depth_estimator = DepthEstimatorMvs(
+                        self.volume, self.camera, min_depth=float(P("MinDepth", 0.5)), max_depth=float(P("MaxDepth", np.inf)),
+                        max_sources=int(P("MaxSources", 2)), min_baseline=float(P("MinBaseline", 0.05)), max_baseline=float(P("MaxBaseline", 0.5)),
+                        num_planes=int(P("NumPlanes", 128)), speckle_window_size=int(P("SpeckleWindowSize", 0)),
+                        speckle_range=int(P("SpeckleRange", 1)))
+                elif window > 0:
                     self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera, speckle_window_size=window,
                                                              speckle_range=int(getattr(Parameters, "kVolumetricIntegrationSgmSpeckleRange", 1)))
                 else:
@@ -694,7 +709,12 @@ class VolumetricIntegratorBase:
             if keyframe_data.id in self.img_id_to_depth:
                 depth = self.img_id_to_depth[keyframe_data.id]
             else:
-                depth, pts3d = self.depth_estimator.infer(color, keyframe_data.img_right)
+                if hasattr(self.depth_estimator, "infer_posed"):  # a multi-view estimator: keyframe and pose (Tcw)
+                    depth, pts3d = self.depth_estimator.infer_posed(color, keyframe_data.pose)
+                    if depth is None:
+                        return None, None, None, None, None  # too few earlier keyframes at a usable baseline: skip this keyframe
+                else:
+                    depth, pts3d = self.depth_estimator.infer(color, keyframe_data.img_right)
                 if getattr(Parameters, "kVolumetricIntegrationDepthEstimationFilterShadowPoints", True):
                     depth = self.volume.filter_shadow_points(depth)
         is_dev = hasattr(depth, "data_ptr")

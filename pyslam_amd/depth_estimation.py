@@ -11,7 +11,9 @@ No network weights are available offline, so the module is injected: any ``torch
 (left, right) float tensors [1,3,H,W] to a disparity [1,1,H,W] or [H,W] works; ``StubStereoNet`` is a tiny
 deterministic stand-in used by the tests (RAFT-Stereo itself is out of this package's scope); its disparity has nothing to
 do with the scene.  ``DepthEstimatorSgm`` needs no weights: census semi-global matching on the GPU (hv_stereo_sgm), depth
-in the same place, selected in the dense front by kVolumetricIntegrationDepthEstimatorType = "DEPTH_SGM_HIP"."""
+in the same place, selected in the dense front by kVolumetricIntegrationDepthEstimatorType = "DEPTH_SGM_HIP".
+``DepthEstimatorMvs`` needs none either, and no second camera: plane-sweep matching of a posed keyframe against earlier keyframes
+(hv_mvs_sgm), selected by "DEPTH_MVS_HIP"."""
 import numpy as np
 
 
@@ -84,6 +86,68 @@ class DepthEstimatorSgm:
             left, right = torch.from_numpy(left).to(dev), torch.from_numpy(right).to(dev)
         self.disparity_map, depth = self.volume.stereo_sgm(left, right, bf=bf, min_depth=self.min_depth, max_depth=self.max_depth,
                                                            **self.sgm_params)
+        return depth, None
+
+
+class DepthEstimatorMvs:
+    """The weight-free estimator for a posed single-camera stream: plane-sweep semi-global matching of a keyframe against earlier
+    keyframes on the GPU (_Volume.multiview_sgm, hv_mvs_sgm), in the place the reference gives its multi-view networks
+    (pyslam/depth_estimation/depth_estimator_mvdust3r.py, depth_estimator_mast3r.py).  Selected in the dense front by
+    kVolumetricIntegrationDepthEstimatorType = "DEPTH_MVS_HIP".  The camera is a pinhole (fx, fy, cx, cy): undistort first.
+
+    infer_posed(image, T_cw) -> (depth, None): T_cw is the keyframe's world-to-camera pose.  The estimator keeps a ring of the last
+    `ring_size` keyframes (image and pose; with keep_on_device the uploaded image) and matches the new one against the most recent
+    ones, at most max_sources, whose camera centres lie between min_baseline and max_baseline metres from its own.  While fewer
+    than min_views (an mvs_param, 1 by default) qualify it returns (None, None): the front skips such a keyframe.  depth is z-depth
+    in metres, a float32 CUDA tensor with keep_on_device and a numpy array otherwise, 0 = none; index_map is the int16 plane index
+    in sixteenths (-16 = invalid) in the same place, sources_used the ring positions of the chosen keyframes (0 = the last one).
+    mvs_params: num_planes, p1, p2, uniqueness_ratio, min_views, paths, speckle_window_size, speckle_range."""
+
+    def __init__(self, volume, camera, keep_on_device=True, *, min_depth, max_depth=np.inf, max_sources=2, min_baseline,
+                 max_baseline=np.inf, ring_size=8, **mvs_params):
+        if not 1 <= int(max_sources) <= 4:
+            raise ValueError(f"DepthEstimatorMvs: max_sources must be in 1..4, got {max_sources}")
+        if not 0.0 <= float(min_baseline) <= float(max_baseline):
+            raise ValueError(f"DepthEstimatorMvs: need 0 <= min_baseline <= max_baseline, got {min_baseline} and {max_baseline}")
+        if int(ring_size) < int(max_sources):
+            raise ValueError(f"DepthEstimatorMvs: ring_size {ring_size} cannot hold max_sources = {max_sources} keyframes")
+        self.volume = volume
+        self.camera = camera
+        self.keep_on_device = keep_on_device
+        self.min_depth, self.max_depth = float(min_depth), float(max_depth)
+        self.max_sources, self.ring_size = int(max_sources), int(ring_size)
+        self.min_baseline, self.max_baseline = float(min_baseline), float(max_baseline)
+        self.mvs_params = dict(mvs_params)
+        self.ring = []  # [(image, T_cw, camera centre)], the last keyframe first
+        self.index_map = None
+        self.sources_used = ()
+
+    def infer(self, image, image_right=None):
+        raise ValueError("DepthEstimatorMvs matches a keyframe against earlier keyframes: call infer_posed(image, T_cw) "
+                         "(a stereo pair goes to DepthEstimatorSgm)")
+
+    def infer_posed(self, image, T_cw):
+        T = np.array(T_cw, dtype=np.float64).reshape(4, 4)
+        centre = -T[:3, :3].T @ T[:3, 3]
+        ref = np.ascontiguousarray(image)
+        if self.keep_on_device:
+            import torch
+
+            ref = torch.from_numpy(ref).to(self.volume._device())
+        chosen = []
+        for k, (_, _, c) in enumerate(self.ring):
+            if len(chosen) < self.max_sources and self.min_baseline <= float(np.linalg.norm(c - centre)) <= self.max_baseline:
+                chosen.append(k)
+        sources = [self.ring[k][0] for k in chosen]
+        poses = [self.ring[k][1] for k in chosen]
+        self.ring = ([(ref, T, centre)] + self.ring)[:self.ring_size]
+        self.sources_used = tuple(chosen)
+        if len(chosen) < max(int(self.mvs_params.get("min_views", 1)), 1):
+            self.index_map = None
+            return None, None
+        K = tuple(float(getattr(self.camera, a)) for a in ("fx", "fy", "cx", "cy"))
+        self.index_map, depth = self.volume.multiview_sgm(ref, sources, intrinsic=K, T_ref=T, T_sources=np.stack(poses), min_depth=self.min_depth,
+                                                          max_depth=self.max_depth, **self.mvs_params)
         return depth, None
 
 

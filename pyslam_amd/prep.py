@@ -93,6 +93,40 @@ def init_undistort_rectify_map(K, D, new_K, image_size):
     return np.ascontiguousarray(map_x), np.ascontiguousarray(map_y)
 
 
+def _k3x3(K):
+    """A 3x3 camera matrix from a 3x3 array, (fx, fy, cx, cy), or an object with those four attributes."""
+    if all(hasattr(K, a) for a in ("fx", "fy", "cx", "cy")):
+        K = (K.fx, K.fy, K.cx, K.cy)
+    K = np.asarray(K, dtype=np.float64)
+    if K.shape == (4,):
+        K = np.array([[K[0], 0.0, K[2]], [0.0, K[1], K[3]], [0.0, 0.0, 1.0]])
+    if K.shape != (3, 3):
+        raise ValueError(f"a camera matrix must be 3x3 or (fx, fy, cx, cy), got shape {K.shape}")
+    return K
+
+
+def plane_sweep_views(K_ref, T_ref_cw, K_src, T_src_cw):
+    """The 3x4 matrices [A | b] that multiview_sgm looks a reference pixel up with (include/hipvol.h rule M3): for a point at z-depth
+    1 / w along the reference pixel p = (x, y, 1), the source pixel is the dehomogenised A p + w b, with A = K_s R_sr K_r^-1 and
+    b = K_s t_sr, where X_s = R_sr X_r + t_sr is T_src_cw T_ref_cw^-1.  K: 3x3, (fx, fy, cx, cy) or an object with those attributes
+    (K_src: one for all sources, or one per source); T_cw: world-to-camera 4x4, T_src_cw [N,4,4] or one 4x4.  Computed in float64
+    and rounded once.  -> float32 [N,3,4]"""
+    T_ref = np.asarray(T_ref_cw, dtype=np.float64).reshape(4, 4)
+    T_src = np.asarray(T_src_cw, dtype=np.float64).reshape(-1, 4, 4)
+    if isinstance(K_src, (list, tuple)) and len(K_src) == len(T_src) and not np.isscalar(K_src[0]):
+        Ks = [_k3x3(k) for k in K_src]
+    else:
+        Ks = [_k3x3(K_src)] * len(T_src)
+    Kr_inv = np.linalg.inv(_k3x3(K_ref))
+    T_rc = np.linalg.inv(T_ref)
+    out = np.empty((len(T_src), 3, 4), np.float64)
+    for s, (K, T) in enumerate(zip(Ks, T_src)):
+        T_sr = T @ T_rc
+        out[s, :, :3] = K @ T_sr[:3, :3] @ Kr_inv
+        out[s, :, 3] = K @ T_sr[:3, 3]
+    return np.ascontiguousarray(out.astype(np.float32))
+
+
 class RectifyMaps:
     """A pair of maps fixed for a camera's lifetime, for volume.remap: host arrays for host images, and for a CUDA image a device
     copy made once per device (remap itself keeps nothing between calls).  The host arrays are this object's own read-only copies,

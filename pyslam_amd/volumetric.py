@@ -934,6 +934,101 @@ class _Volume:
                                                         int(speckle_range), L.ptr(out["disparity"]), L.ptr(out["depth"]), None, L.location(a)))
         return out["disparity"], out["depth"]
 
+    def multiview_sgm(self, ref, sources, views=None, *, intrinsic=None, T_ref=None, T_sources=None, min_depth, max_depth=np.inf,
+                      num_planes=128, p1=10, p2=120, uniqueness_ratio=15, min_views=1, paths=8, speckle_window_size=0, speckle_range=1,
+                      index=True, depth=True):
+        """Plane-sweep depth for a posed reference image and 1..4 source images of the same shape, uint8 [H,W] or [H,W,3]
+        (hv_mvs_sgm, the rules M1 - M10 in include/hipvol.h): num_planes fronto-parallel planes of the reference camera at evenly
+        spaced inverse depths from 1 / max_depth (plane 0) to 1 / min_depth, census cost through the per-view 3x4 matrices, then the
+        semi-global stages of stereo_sgm.  -> (index int16 [H,W] in sixteenths of a plane, -16 = invalid: the format of a disparity;
+        depth float32 [H,W], z-depth in the reference camera in metres, 0 = none); index=False / depth=False leaves that one out
+        (None in its place).  sources: a list of images or one [N,H,W(,3)] array.  Pass views, [N,3,4] float32 (A p + w b is the
+        source pixel of the point at depth 1 / w along p), or intrinsic (a PinholeCameraIntrinsic, 3x3 or (fx, fy, cx, cy)) with the
+        world-to-camera poses T_ref [4,4] and T_sources [N,4,4], which prep.plane_sweep_views turns into the matrices.  numpy arrays
+        in, numpy arrays out; torch CUDA tensors on the volume's GPU in, tensors out, queued on the volume's stream.  min_views: the
+        views that must see a plane of a pixel for its cost to count.  speckle_window_size > 0 filters the index as stereo_sgm does
+        its disparity.  Works on a volume of any mode and reads nothing of it."""
+        on_gpu = L.location(ref) == L.HV_DEVICE
+        is_list = isinstance(sources, (list, tuple))
+        src_list = list(sources) if is_list else [sources]
+        if not src_list or any((L.location(s) == L.HV_DEVICE) != on_gpu for s in src_list):
+            raise ValueError("multiview_sgm: ref and sources must live in the same place")
+        if on_gpu:
+            import torch
+
+            if ref.dtype != torch.uint8 or any(s.dtype != torch.uint8 for s in src_list):
+                raise ValueError("multiview_sgm: the images must be uint8")
+            if any(t.device != self._device() for t in [ref] + src_list):
+                raise ValueError(f"multiview_sgm: the images must live on the volume's GPU {self._device()}")
+            a, stack = ref.contiguous(), torch.stack
+        else:
+            a = ref.cpu().numpy() if _is_torch(ref) else np.asarray(ref)
+            src_list = [s.cpu().numpy() if _is_torch(s) else np.asarray(s) for s in src_list]
+            if a.dtype != np.uint8 or any(s.dtype != np.uint8 for s in src_list):
+                raise ValueError("multiview_sgm: the images must be uint8")
+            a, stack = np.ascontiguousarray(a), np.stack
+        # a list of images of the reference's shape becomes one block; an array or tensor must be [N] + that shape already
+        want = tuple(a.shape) if is_list else (int(src_list[0].shape[0]),) + tuple(a.shape) if src_list[0].ndim else None
+        if a.ndim not in (2, 3) or any(tuple(s.shape) != want for s in src_list):
+            raise ValueError(f"multiview_sgm: the sources must be 1..4 images of the reference's shape {tuple(a.shape)}")
+        b = stack(src_list) if is_list else src_list[0].contiguous() if on_gpu else np.ascontiguousarray(src_list[0])
+        N, H, W = int(b.shape[0]), int(a.shape[0]), int(a.shape[1])
+        channels = 1 if a.ndim == 2 else int(a.shape[2])
+        # what hv_mvs_sgm answers with HV_ERR_INVALID, refused here before anything is allocated
+        if channels not in (1, 3):
+            raise ValueError(f"multiview_sgm: images must have 1 or 3 channels, got {channels}")
+        if H < 1 or W < 1 or H > 32768 or W > 32768 or H * W >= 1 << 30:
+            raise ValueError(f"multiview_sgm: bad image size {tuple(a.shape)}")
+        if not 1 <= N <= 4:
+            raise ValueError(f"multiview_sgm: need 1..4 source views, got {N}")
+        if not index and not depth:
+            raise ValueError("multiview_sgm: no output asked for")
+        if int(min_views) != min_views or not 1 <= int(min_views) <= N:
+            raise ValueError(f"multiview_sgm: min_views must be in 1..{N}, got {min_views}")
+        if not (16 <= int(num_planes) <= 256 and int(num_planes) % 16 == 0):
+            raise ValueError(f"multiview_sgm: num_planes must be a multiple of 16 in 16..256, got {num_planes}")
+        if not 0 < int(p1) <= int(p2) <= 1023:
+            raise ValueError(f"multiview_sgm: need 0 < p1 <= p2 <= 1023, got p1 = {p1}, p2 = {p2}")
+        if not 0 <= int(uniqueness_ratio) <= 99:
+            raise ValueError(f"multiview_sgm: uniqueness_ratio must be in 0..99, got {uniqueness_ratio}")
+        if int(paths) not in (4, 8):
+            raise ValueError(f"multiview_sgm: paths must be 4 or 8, got {paths}")
+        lo, hi = float(min_depth), float(max_depth)
+        if not 0.0 < lo < np.inf:
+            raise ValueError(f"multiview_sgm: min_depth must be finite and positive, got {min_depth}")
+        if not hi > lo:
+            raise ValueError(f"multiview_sgm: need max_depth > min_depth, got {max_depth} and {min_depth}")
+        if (1.0 / lo - (0.0 if np.isinf(hi) else 1.0 / hi)) / (16.0 * (int(num_planes) - 1)) > float(np.finfo(np.float32).max):
+            raise ValueError(f"multiview_sgm: min_depth {min_depth} is too small: the plane step overflows float32")
+        if int(speckle_window_size) != speckle_window_size or not 0 <= int(speckle_window_size) <= 1 << 30:
+            raise ValueError(f"multiview_sgm: speckle_window_size must be an integer in 0..2^30, got {speckle_window_size}")
+        if int(speckle_range) != speckle_range or not 0 <= int(speckle_range) <= 4095:
+            raise ValueError(f"multiview_sgm: speckle_range must be an integer in 0..4095, got {speckle_range}")
+        if (views is None) == (intrinsic is None):
+            raise ValueError("multiview_sgm: pass either views or intrinsic with T_ref and T_sources")
+        if views is None:
+            if T_ref is None or T_sources is None:
+                raise ValueError("multiview_sgm: intrinsic needs the poses T_ref and T_sources")
+            from .prep import plane_sweep_views
+
+            m = plane_sweep_views(intrinsic, T_ref, intrinsic, T_sources)
+        else:
+            if T_ref is not None or T_sources is not None:
+                raise ValueError("multiview_sgm: pass either views or intrinsic with T_ref and T_sources")
+            m = np.ascontiguousarray(views.cpu().numpy() if _is_torch(views) else views, dtype=np.float32)
+        if m.size != 12 * N or tuple(m.shape[-2:]) != (3, 4):
+            raise ValueError(f"multiview_sgm: views must be [{N}, 3, 4], got {tuple(m.shape)}")
+        if not np.isfinite(m).all():
+            raise ValueError("multiview_sgm: a view matrix entry is not finite")
+        prm = L.HvMvsParams(int(num_planes), int(p1), int(p2), int(uniqueness_ratio), int(min_views), int(paths), lo, hi,
+                            int(speckle_window_size), int(speckle_range))
+        out = self._results({"index": ((H, W), np.int16) if index else None, "depth": ((H, W), np.float32) if depth else None}, on_gpu,
+                            pinned=False, synchronize=False)
+        with self._ordered(a, b, out["index"], out["depth"]):
+            L.check(self._lib.hv_mvs_sgm(self._h, L.ptr(a), L.ptr(b), N, H, W, channels, L.ptr(m), ctypes.byref(prm), L.ptr(out["index"]),
+                                         L.ptr(out["depth"]), None, L.location(a)))
+        return out["index"], out["depth"]
+
     def remap(self, img, map_x, map_y, linear=False):
         """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU; the maps are [H, W] like the image.
         Host arrays, or a torch CUDA tensor: the image never leaves the device, and maps that are float32 CUDA tensors are read
