@@ -299,10 +299,11 @@ __device__ __forceinline__ void hv_touch_batch_patch(const HvTable &table, const
 // ================================================================================================
 // Multi-frame sweep (hv_tsdf_integrate_batch; the rebuild()/offline-replay use case,
 // volumetric_integrator_base.py:1242-1318).  B <= 64 posed frames are resident in HBM:
-//   k_tsdf_prep_touch_batch  one launch for all B frames: packs every frame and ORs bit f into the 64-bit
-//                            frame mask of each unit frame f touches (one wave per 8x8 sample patch,
-//                            hv_touch_patch); the first toucher of a unit in the batch appends it to the
-//                            union list
+//   k_tsdf_prep_touch_batch  one launch for all B frames: packs every frame (a pack thread writes the records of its 4
+//                            pixels for HV_PACK_FRAMES consecutive frames, all of their loads in flight before the first
+//                            wait: hv_pack_px4_frames) and ORs bit f into the 64-bit frame mask of each unit frame f
+//                            touches (one wave per 8x8 sample patch, hv_touch_patch); the first toucher of a unit in the
+//                            batch appends it to the union list
 //   sweep                    per union unit: a lane's voxels are folded over every frame bit in ascending (= chronological) order
 //                            in registers and stored once - k_tsdf_sweep_column (production) or k_tsdf_sweep (bitwise)
 //   k_tsdf_batch_finish      clears the batch's frame masks and list counter
@@ -328,27 +329,45 @@ __global__ __launch_bounds__(256) void k_tsdf_prep_touch_batch(HvTable table, in
     // memory round trips (depth -> hash probe -> mask / stamp -> atomics; a patch on a long depth discontinuity walks
     // several such chains), the pack blocks are pure streaming: dispatched last they fill the machine while the touch
     // chains drain, instead of the launch ending on the chains of the last frame.
-    int f, bx;
-    const bool touch_role = (int)blockIdx.x < n_touch_blocks * n_frames;
-    if (touch_role) {
-        f = (int)blockIdx.x / n_touch_blocks;
-        bx = (int)blockIdx.x % n_touch_blocks;
-    } else {
+    __shared__ __attribute__((aligned(16))) HvTouchScratch scratch[4]; // per wave: the touch role's bitmap and list, the pack role's stage
+    static_assert(sizeof(HvTouchScratch) >= HV_WAVE * 48, "a wave stages 64 x 4 records of 12 bytes");
+    if ((int)blockIdx.x >= n_touch_blocks * n_frames) {
+        // ---- pack role: a thread packs the same pixel quads of the HV_PACK_FRAMES consecutive frames of its group ----
+        // (everything the pack reads from a frame's constants - image size, depth type and scale, colour order, tile - is the
+        // same for every frame of a batch: the group's first frame stands for all of them)
         const int b = (int)blockIdx.x - n_touch_blocks * n_frames;
-        f = b / n_prep_blocks;
-        bx = b % n_prep_blocks;
-    }
-    const HvFrameParams &P = Ps[f];
-    const int64_t npx = (int64_t)P.H * P.W;
-    const void *depth_f = depth_raw + (int64_t)f * depth_stride;
-    const uint8_t *rgb_f = rgb + (int64_t)f * npx * 3;
-    if (!touch_role) {
-        // pack role: 4 pixels per thread - every wave access is a contiguous burst (prep blocks cover 1024 pixels each)
-        hv_pack_px4(P, f, ((int64_t)bx * blockDim.x + threadIdx.x) * 4, depth_f, rgb_f, frame_px, mult12);
+        const int f0 = (b / n_prep_blocks) * HV_PACK_FRAMES;
+        const int nf = min(HV_PACK_FRAMES, n_frames - f0);
+        const HvFrameParams &P = Ps[f0];
+        const int64_t npx = (int64_t)P.H * P.W;
+        const int64_t i0 = ((int64_t)(b % n_prep_blocks) * blockDim.x + threadIdx.x) * 4; // (prep blocks cover 1024 pixels each)
+        if (mult12 != nullptr && (npx & 3) == 0 && nf == HV_PACK_FRAMES && i0 < npx) {
+            if (P.tiled && (P.W & 3) == 0) { // as hv_pack_px4: only the tile's rows and columns (+ 4 pixels) are packed
+                const int u = (int)(i0 % P.W), v = (int)(i0 / P.W);
+                if (u + 3 < P.tile_u0 - 4 || u >= P.tile_u1 + 4 || v < P.tile_v0 - 4 || v >= P.tile_v1 + 4) return;
+            }
+            // every choice a wave makes as one is made here, outside the load sequence
+            uint4 *stage = (uint4 *)&scratch[threadIdx.x / HV_WAVE];
+            const bool whole_wave = __ballot(1) == ~0ull;
+            if (P.depth_is_u16) {
+                if (whole_wave) hv_pack_px4_frames<true, true>(P, f0, i0, depth_raw, depth_stride, rgb, frame_px, mult12, stage);
+                else hv_pack_px4_frames<true, false>(P, f0, i0, depth_raw, depth_stride, rgb, frame_px, mult12, nullptr);
+            } else {
+                if (whole_wave) hv_pack_px4_frames<false, true>(P, f0, i0, depth_raw, depth_stride, rgb, frame_px, mult12, stage);
+                else hv_pack_px4_frames<false, false>(P, f0, i0, depth_raw, depth_stride, rgb, frame_px, mult12, nullptr);
+            }
+            return;
+        }
+        // the ragged last group of a batch, 8-byte records, an image that is no whole number of quads: frame by frame
+        for (int k = 0; k < nf; ++k)
+            hv_pack_px4(P, f0 + k, i0, depth_raw + (int64_t)(f0 + k) * depth_stride, rgb + (int64_t)(f0 + k) * npx * 3, frame_px, mult12);
         return;
     }
+    const int f = (int)blockIdx.x / n_touch_blocks;
+    const int bx = (int)blockIdx.x % n_touch_blocks;
+    const HvFrameParams &P = Ps[f];
+    const void *depth_f = depth_raw + (int64_t)f * depth_stride;
     // ---- touch role: one wave per 8x8 sample patch (hv_touch_patch) ----
-    __shared__ HvTouchScratch scratch[4];
     const int patch = bx * 4 + (int)(threadIdx.x / HV_WAVE);
     if (patch < hv_touch_patches(P))
         hv_touch_batch_patch(table, P, depth_f, patch, scratch[threadIdx.x / HV_WAVE], f, frame_mask, stamp, list, batch_stamp, parity);
@@ -1376,6 +1395,7 @@ int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const
         }
         HV_HIP(hipEventRecord(v->params_ev[ri], ps));
         const int n_prep_blocks = (int)((npx + 1023) / 1024); // 4 pixels per thread
+        const int n_pack_groups = (B + HV_PACK_FRAMES - 1) / HV_PACK_FRAMES; // a pack thread handles its pixels in a whole group of frames
         const int n_touch_blocks = (hv_touch_patches(width, height, v->cfg.depth_sampling_stride) + 3) / 4;
         // this chunk's frames (through the camera's rectify maps first, when the volume has them: hv_tsdf_set_rectify_maps)
         const void *c_depth = (const char *)d_depth + npx * dsz * (size_t)f0;
@@ -1387,7 +1407,7 @@ int tsdf_integrate_batch_impl(hv_volume *v, const void *depth, const void *const
             // leaves its own parity's count behind (never while a chain runs)
             if (!v->touch_counters_clean) HV_HIP(hipMemsetAsync(&v->table.counters[HV_CNT_TOUCH0], 0, HV_CNT_TOUCH_SPAN_BYTES, v->stream));
             v->touch_counters_clean = true;
-            hipLaunchKernelGGL(k_tsdf_prep_touch_batch, dim3((n_prep_blocks + n_touch_blocks) * B), dim3(256), 0, ps,
+            hipLaunchKernelGGL(k_tsdf_prep_touch_batch, dim3(n_touch_blocks * B + n_prep_blocks * n_pack_groups), dim3(256), 0, ps,
                                v->table, v->touched_stamp, d_mask_rw, d_list, batch_stamp,
                                (const char *)c_depth, (int64_t)(npx * dsz), c_rgb, d_px, (const HvFrameParams *)d_params, n_prep_blocks, n_touch_blocks, B, parity,
                                rec12 ? d_mult : (const float *)nullptr);

@@ -427,6 +427,79 @@ __device__ __forceinline__ void hv_pack_px4(const HvFrameParams &P, const int f,
     }
 }
 
+// Frame-grouped pack role of the batch path's 12-byte records: pixels [i0, i0 + 4) of the HV_PACK_FRAMES consecutive frames from f0 (a
+// wave's lanes hold consecutive quads, so every wave access is one frame's contiguous 1 KB of depth, 768 B of RGB or 3 KB of records).
+// The multiplier quad is loaded once, then every frame's depth quad and three RGB dwords are issued before the first of them is waited
+// for.  The group size and the depth type are compile-time so that the loads stand in one straight block (a frame count or a depth type
+// only known at run time puts a branch and a full wait between the frames).  The caller guarantees a whole quad inside the image.
+// The records are byte for byte hv_pack_px4's: hv_convert_depth's operations, the same colour order and count byte.
+// STAGE (every lane of the wave is here): the wave's 3 KB of records of a frame go through `stage` (3 KB of LDS of the wave's own), so
+// that each of the three store instructions writes 1 KB contiguously; straight from the registers a lane's 16 bytes lie 48 bytes apart
+// and every instruction touches all 24 lines.  Alone the launch of a 64-frame batch takes 129 us with it, 145 us without
+// (profiles/pack_groups).
+static constexpr int HV_PACK_FRAMES = 2; // frames per pack thread (4: one more register granule and slower, profiles/pack_groups)
+
+template <bool U16, bool STAGE>
+__device__ __forceinline__ void hv_pack_px4_frames(const HvFrameParams &P, const int f0, const int64_t i0, const char *depth_raw,
+                                                   const int64_t depth_stride, const uint8_t *rgb, uint2 *__restrict__ frame_px,
+                                                   const float *__restrict__ mult12, uint4 *stage) {
+    constexpr int NF = HV_PACK_FRAMES;
+    const int64_t npx = (int64_t)P.H * P.W;
+    const float4 m = *(const float4 *)(mult12 + i0);
+    uint4 raw[NF]; // depth as loaded: four floats, or four uint16 in .x and .y
+    uint32_t w[NF][3];
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+        const char *depth_f = depth_raw + (int64_t)(f0 + k) * depth_stride;
+        if (U16) {
+            const uint2 r2 = *(const uint2 *)((const uint16_t *)depth_f + i0);
+            raw[k] = make_uint4(r2.x, r2.y, 0u, 0u);
+        } else {
+            raw[k] = *(const uint4 *)((const float *)depth_f + i0);
+        }
+        const uint32_t *c4 = (const uint32_t *)(rgb + ((int64_t)(f0 + k) * npx + i0) * 3); // a multiple of 12 bytes: dword aligned
+        w[k][0] = c4[0]; w[k][1] = c4[1]; w[k][2] = c4[2];
+    }
+#pragma unroll
+    for (int k = 0; k < NF; ++k) {
+        float d[4];
+        if (U16) {
+            d[0] = (float)(raw[k].x & 0xffffu); d[1] = (float)(raw[k].x >> 16);
+            d[2] = (float)(raw[k].y & 0xffffu); d[3] = (float)(raw[k].y >> 16);
+        } else {
+            d[0] = __uint_as_float(raw[k].x); d[1] = __uint_as_float(raw[k].y);
+            d[2] = __uint_as_float(raw[k].z); d[3] = __uint_as_float(raw[k].w);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { // hv_convert_depth
+            d[j] = d[j] / P.depth_scale_f;
+            if ((double)d[j] >= P.depth_trunc_d) d[j] = 0.0f;
+        }
+        const uint32_t w0 = w[k][0], w1 = w[k][1], w2 = w[k][2];
+        const uint32_t col[4] = {hv_colour_order(w0 & 0xffffffu, P.bgr) | HV_REC_ONE,
+                                 hv_colour_order((w0 >> 24) | ((w1 & 0xffffu) << 8), P.bgr) | HV_REC_ONE,
+                                 hv_colour_order((w1 >> 16) | ((w2 & 0xffu) << 16), P.bgr) | HV_REC_ONE,
+                                 hv_colour_order(w2 >> 8, P.bgr) | HV_REC_ONE};
+        const uint4 r0 = make_uint4(__float_as_uint(d[0]), col[0], __float_as_uint(m.x), __float_as_uint(d[1]));
+        const uint4 r1 = make_uint4(col[1], __float_as_uint(m.y), __float_as_uint(d[2]), col[2]);
+        const uint4 r2 = make_uint4(__float_as_uint(m.z), __float_as_uint(d[3]), col[3], __float_as_uint(m.w));
+        uint4 *dst12 = (uint4 *)((uint32_t *)frame_px + ((int64_t)(f0 + k) * npx + i0) * 3);
+        if (STAGE) {
+            const int lane = hv_lane_id();
+            stage[lane * 3 + 0] = r0; stage[lane * 3 + 1] = r1; stage[lane * 3 + 2] = r2;
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint4 a = stage[lane], b = stage[HV_WAVE + lane], c = stage[2 * HV_WAVE + lane];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier(); // (the next frame's records overwrite the stage)
+            uint4 *base = dst12 - lane * 3; // lane 0's records: the wave's 192 uint4 follow each other
+            base[lane] = a; base[HV_WAVE + lane] = b; base[2 * HV_WAVE + lane] = c;
+        } else {
+            dst12[0] = r0; dst12[1] = r1; dst12[2] = r2;
+        }
+    }
+}
+
 // ---- host side (hv_tsdf.hip), shared with hv_deintegrate.hip ----
 static constexpr int HV_BATCH_MAX = 64; // frames per sweep (one bit per frame in a unit's mask)
 int make_frame_params(hv_volume *v, int H, int W, const double *intr, const double *T_cw, double depth_scale, double depth_trunc,
