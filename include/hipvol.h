@@ -300,6 +300,64 @@ int hv_mvs_sgm(hv_volume *v, const uint8_t *ref, const uint8_t *sources, int32_t
                int16_t *index_out /* may be NULL */, float *depth_out /* may be NULL */,
                hv_speckle_stats *stats /* may be NULL, host */, int32_t loc);
 
+/* ---- cross-view consistency check and fusion of posed depth maps ----------------------------------------
+ * hv_depth_consistency: a float32 depth map and the depth maps of 1..4 posed neighbours of the same shape -> the depth map with
+ * the pixels removed that the neighbours do not confirm (0 = none), the confirmed ones optionally averaged with the neighbours'
+ * depths, and per pixel the number of views that agree, are occluded, are violated and see the pixel at all.  The geometric
+ * consistency check of multi-view stereo, for the depth of hv_mvs_sgm (which has no left-right check of its own) and for any other
+ * posed depth stream: stereo depth of consecutive keyframes, a network's or a sensor's depth before fusion.  The algorithm is
+ * fixed by the rules below, restated in numpy in tests/depth_consistency_reference.py, and the library is held to that restatement
+ * bit for bit.  N = n_sources.  Every arithmetic line is ONE IEEE float32 operation per written operator, in the written order (no
+ * fused multiply-add, no fast reciprocal or divide); every comparison is a float comparison, so a NaN fails it.
+ *   C1 valid input   z = depth[y,x] is valid iff z > 0 and z < inf.  Otherwise the output depth is 0 and all four counts are 0.
+ *                    w = 1.0f / z
+ *   C2 forward       rule M3 with views[s] and w gives q, ur, vr and the seen test (q_2 > 0, 0 <= ur <= W-1, 0 <= vr <= H-1).  A
+ *                    view that does not see the pixel contributes nothing.  Otherwise seen += 1, the predicted source depth is
+ *                    zs = z * q_2 and d = source_depths[s][vr,ur] (ur, vr from here on: the integer pixel as floats, +0.0 for 0).
+ *                    If not (d > 0 and d < inf) the view contributes nothing more
+ *   C3 backward      with back_views[s] = [A' | b'], in this order:
+ *                      ws = 1.0f / d
+ *                      a'_i = (A'_i0 * ur + A'_i1 * vr) + A'_i2                  q'_i = a'_i + ws * b'_i
+ *                      xb = q'_0 / q'_2, yb = q'_1 / q'_2, zb = d * q'_2
+ *                      ex = xb - float(x), ey = yb - float(y), e2 = ex * ex + ey * ey
+ *                      wb = 1.0f / zb
+ *   C4 agreement     view s AGREES iff q'_2 > 0 and e2 <= max_reproj_error * max_reproj_error (the product formed once in float32
+ *                    on the host) and fabsf(wb - w) <= inv_depth_tol + rel_depth_tol * w.  inv_depth_tol is an absolute tolerance
+ *                    in inverse metres (the unit of a plane sweep: one plane step is (1 / min_depth - 1 / max_depth) / (D - 1)),
+ *                    rel_depth_tol a relative depth difference; either may be 0, not both
+ *   C5 otherwise     a view that has a depth and does not agree is OCCLUDED if d < zs (the source sees something nearer), else
+ *                    VIOLATED (the source sees through the point; d == zs and a NaN zs count here)
+ *   C6 keep          a valid pixel is kept iff agree >= min_consistent and violated <= max_violations
+ *   C7 output        depth_out: 0 if not kept; z if kept and fuse == 0; else acc / float(agree + 1) with acc = z and then
+ *                    acc = acc + zb for the agreeing views in ascending s.  counts_out (agree, occluded, violated, seen) is written
+ *                    for every pixel, kept or not
+ * depth: float32 [height,width]; source_depths: n_sources such images behind each other; depth_out: float32 [height,width];
+ * counts_out: uint8 [height,width,4], 4-byte aligned (one 32-bit store per pixel); all at `loc` (as in hv_mvs_sgm, staged by the
+ * library for HV_HOST).  Either output may be NULL, not both.  views, back_views: float[n_sources][12], HOST memory for either loc:
+ * 3x4 matrices [A | b] in the convention of rule M3, views[s] from a reference pixel to source s, back_views[s] from a pixel of
+ * source s to the reference.  stats (may be NULL, host memory): the pixels valid on input (C1), the pixels kept (C6) and the sum of
+ * the agree counts over all pixels, all exact; when given, the call waits for the stream.  A device call is otherwise queued on
+ * the volume's stream and returns.  Works on a volume of any mode and reads nothing of it.  No scratch beyond the staging of host
+ * arguments (with stats 8 KB more of it, for the counters).
+ * HV_ERR_INVALID before anything is launched or written: a NULL image, matrix set or params; both outputs NULL; n_sources
+ * outside 1..4; the image-size limits of hv_mvs_sgm; a matrix entry that is not finite; max_reproj_error, inv_depth_tol or
+ * rel_depth_tol negative or not finite; both tolerances 0; min_consistent or max_violations outside 0..n_sources. */
+typedef struct hv_consistency_params {
+    float max_reproj_error;  /* 1.0, pixels */
+    float inv_depth_tol;     /* 0.0, 1 / metres */
+    float rel_depth_tol;     /* 0.01 */
+    int32_t min_consistent;  /* 1 */
+    int32_t max_violations;  /* 0 */
+    int32_t fuse;            /* 1 */
+} hv_consistency_params;
+typedef struct hv_consistency_stats {
+    int64_t valid_pixels, kept_pixels, agree_sum;
+} hv_consistency_stats;
+int hv_depth_consistency(hv_volume *v, const float *depth, const float *source_depths, int32_t n_sources, int32_t height, int32_t width,
+                         const float *views /* float[n_sources][12], host */, const float *back_views /* float[n_sources][12], host */,
+                         const hv_consistency_params *params, float *depth_out /* may be NULL */, uint8_t *counts_out /* may be NULL */,
+                         hv_consistency_stats *stats /* may be NULL, host */, int32_t loc);
+
 /* get_voxels(min_count, min_confidence) (voxel_block_grid.hpp:717-819): rows = sum / count.
  * Pass points == NULL to query *n only.  At most `cap` rows are written; *n is the full count. */
 int hv_get_voxels(hv_volume *v, int32_t min_count, float min_confidence, float *points,

@@ -252,6 +252,15 @@ class HvMvsParams(_c.Structure):
                 ("min_depth", _f64), ("max_depth", _f64), ("speckle_window_size", _i32), ("speckle_range", _i32)]
 
 
+class HvConsistencyParams(_c.Structure):
+    _fields_ = [("max_reproj_error", _f32), ("inv_depth_tol", _f32), ("rel_depth_tol", _f32), ("min_consistent", _i32), ("max_violations", _i32),
+                ("fuse", _i32)]
+
+
+class HvConsistencyStats(_c.Structure):
+    _fields_ = [("valid_pixels", _i64), ("kept_pixels", _i64), ("agree_sum", _i64)]
+
+
 HV_SPECKLE_I16, HV_SPECKLE_F32 = 0, 1
 
 
@@ -288,6 +297,8 @@ SIGNATURES = {
     "hv_stereo_sgm_speckle": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _c.POINTER(HvStereoParams), _i32, _i32, _vp, _vp,
                                      _c.POINTER(HvSpeckleStats), _i32]),
     "hv_mvs_sgm": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _c.POINTER(HvMvsParams), _vp, _vp, _c.POINTER(HvSpeckleStats), _i32]),
+    "hv_depth_consistency": (_i32, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvConsistencyParams), _vp, _vp,
+                                    _c.POINTER(HvConsistencyStats), _i32]),
     "hv_get_voxels": (_i32, [_vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_bb": (_i32, [_vp, _vp, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),
     "hv_get_voxels_in_frustum": (_i32, [_vp, _vp, _i32, _i32, _vp, _f32, _f32, _i32, _f32, _vp, _vp, _i64, _pi64, _i32]),

@@ -53,6 +53,13 @@ class Parameters:
     kVolumetricIntegrationMvsMaxBaseline = 0.5
     kVolumetricIntegrationMvsSpeckleWindowSize = 0
     kVolumetricIntegrationMvsSpeckleRange = 1
+    # the cross-view check of the matched depth against the raw depths of the keyframes it was matched with (hv_depth_consistency):
+    # the views that must agree (0: no check), the inverse-depth tolerance in plane steps, the reprojection tolerance in pixels and
+    # the views that may see through a point
+    kVolumetricIntegrationMvsConsistencyMinViews = 0
+    kVolumetricIntegrationMvsConsistencyInvDepthSteps = 1.0
+    kVolumetricIntegrationMvsConsistencyMaxReproj = 1.0
+    kVolumetricIntegrationMvsConsistencyMaxViolations = 0
     # semantic integration, config_parameters.py:364-380
     kVolumetricSemanticProbabilisticIntegrationUseDepth = True
     kVolumetricSemanticProbabilisticIntegrationDepthThresholdIndoor = 5.0

@@ -697,7 +697,10 @@ class VolumetricIntegratorBase:
                         self.volume, self.camera, min_depth=float(P("MinDepth", 0.5)), max_depth=float(P("MaxDepth", np.inf)),
                         max_sources=int(P("MaxSources", 2)), min_baseline=float(P("MinBaseline", 0.05)), max_baseline=float(P("MaxBaseline", 0.5)),
                         num_planes=int(P("NumPlanes", 128)), speckle_window_size=int(P("SpeckleWindowSize", 0)),
-                        speckle_range=int(P("SpeckleRange", 1)))
+                        speckle_range=int(P("SpeckleRange", 1)), consistency_min_views=int(P("ConsistencyMinViews", 0)),
+                        consistency_inv_depth_steps=float(P("ConsistencyInvDepthSteps", 1.0)),
+                        consistency_max_reproj=float(P("ConsistencyMaxReproj", 1.0)),
+                        consistency_max_violations=int(P("ConsistencyMaxViolations", 0)))
                 elif window > 0:
                     self.depth_estimator = DepthEstimatorSgm(self.volume, self.camera, speckle_window_size=window,
                                                              speckle_range=int(getattr(Parameters, "kVolumetricIntegrationSgmSpeckleRange", 1)))

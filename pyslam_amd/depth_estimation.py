@@ -101,10 +101,21 @@ class DepthEstimatorMvs:
     than min_views (an mvs_param, 1 by default) qualify it returns (None, None): the front skips such a keyframe.  depth is z-depth
     in metres, a float32 CUDA tensor with keep_on_device and a numpy array otherwise, 0 = none; index_map is the int16 plane index
     in sixteenths (-16 = invalid) in the same place, sources_used the ring positions of the chosen keyframes (0 = the last one).
-    mvs_params: num_planes, p1, p2, uniqueness_ratio, min_views, paths, speckle_window_size, speckle_range."""
+    mvs_params: num_planes, p1, p2, uniqueness_ratio, min_views, paths, speckle_window_size, speckle_range.
+
+    consistency_min_views > 0 adds the cross-view check (_Volume.filter_depth_consistency, hv_depth_consistency): the ring also keeps
+    each keyframe's RAW depth - the matcher's output before any check, None for a keyframe that produced none, so that one
+    keyframe's verdict does not cascade into the next - and the freshly matched depth is checked against those chosen sources that
+    carry one, fused with the agreeing ones.  A pixel needs consistency_min_views agreeing views and at most
+    consistency_max_violations violated ones (capped at the number of sources checked against); the inverse-depth tolerance is
+    consistency_inv_depth_steps plane steps of this estimator's own sweep, the reprojection tolerance consistency_max_reproj
+    pixels.  While fewer than consistency_min_views of the chosen sources carry a depth the keyframe returns (None, None) like
+    one without sources; it enters the ring with its raw depth all the same.  counts_map is the uint8 [H,W,4] of the check (agree,
+    occluded, violated, seen), None without one; index_map stays the matcher's own.  The default 0 runs no check."""
 
     def __init__(self, volume, camera, keep_on_device=True, *, min_depth, max_depth=np.inf, max_sources=2, min_baseline,
-                 max_baseline=np.inf, ring_size=8, **mvs_params):
+                 max_baseline=np.inf, ring_size=8, consistency_min_views=0, consistency_inv_depth_steps=1.0, consistency_max_reproj=1.0,
+                 consistency_max_violations=0, **mvs_params):
         if not 1 <= int(max_sources) <= 4:
             raise ValueError(f"DepthEstimatorMvs: max_sources must be in 1..4, got {max_sources}")
         if not 0.0 <= float(min_baseline) <= float(max_baseline):
@@ -117,9 +128,19 @@ class DepthEstimatorMvs:
         self.min_depth, self.max_depth = float(min_depth), float(max_depth)
         self.max_sources, self.ring_size = int(max_sources), int(ring_size)
         self.min_baseline, self.max_baseline = float(min_baseline), float(max_baseline)
+        if int(consistency_min_views) != consistency_min_views or not 0 <= int(consistency_min_views) <= int(max_sources):
+            raise ValueError(f"DepthEstimatorMvs: consistency_min_views must be in 0..max_sources, got {consistency_min_views}")
+        if int(consistency_max_violations) != consistency_max_violations or int(consistency_max_violations) < 0:
+            raise ValueError(f"DepthEstimatorMvs: consistency_max_violations must be an integer >= 0, got {consistency_max_violations}")
+        if not (0.0 < float(consistency_inv_depth_steps) < np.inf and 0.0 <= float(consistency_max_reproj) < np.inf):
+            raise ValueError("DepthEstimatorMvs: need consistency_inv_depth_steps > 0 and consistency_max_reproj >= 0, both finite, got "
+                             f"{consistency_inv_depth_steps} and {consistency_max_reproj}")
         self.mvs_params = dict(mvs_params)
-        self.ring = []  # [(image, T_cw, camera centre)], the last keyframe first
+        self.consistency_min_views, self.consistency_max_violations = int(consistency_min_views), int(consistency_max_violations)
+        self.consistency_inv_depth_steps, self.consistency_max_reproj = float(consistency_inv_depth_steps), float(consistency_max_reproj)
+        self.ring = []  # [(image, T_cw, camera centre, raw depth or None)], the last keyframe first
         self.index_map = None
+        self.counts_map = None
         self.sources_used = ()
 
     def infer(self, image, image_right=None):
@@ -135,20 +156,37 @@ class DepthEstimatorMvs:
 
             ref = torch.from_numpy(ref).to(self.volume._device())
         chosen = []
-        for k, (_, _, c) in enumerate(self.ring):
+        for k, (_, _, c, _) in enumerate(self.ring):
             if len(chosen) < self.max_sources and self.min_baseline <= float(np.linalg.norm(c - centre)) <= self.max_baseline:
                 chosen.append(k)
-        sources = [self.ring[k][0] for k in chosen]
-        poses = [self.ring[k][1] for k in chosen]
-        self.ring = ([(ref, T, centre)] + self.ring)[:self.ring_size]
+        earlier = [self.ring[k] for k in chosen]
         self.sources_used = tuple(chosen)
-        if len(chosen) < max(int(self.mvs_params.get("min_views", 1)), 1):
-            self.index_map = None
-            return None, None
+        self.index_map = self.counts_map = None
+        index = raw = None
         K = tuple(float(getattr(self.camera, a)) for a in ("fx", "fy", "cx", "cy"))
-        self.index_map, depth = self.volume.multiview_sgm(ref, sources, intrinsic=K, T_ref=T, T_sources=np.stack(poses), min_depth=self.min_depth,
-                                                          max_depth=self.max_depth, **self.mvs_params)
+        if len(chosen) >= max(int(self.mvs_params.get("min_views", 1)), 1):
+            index, raw = self.volume.multiview_sgm(ref, [e[0] for e in earlier], intrinsic=K, T_ref=T, T_sources=np.stack([e[1] for e in earlier]),
+                                                   min_depth=self.min_depth, max_depth=self.max_depth, **self.mvs_params)
+        self.ring = ([(ref, T, centre, raw)] + self.ring)[:self.ring_size]
+        if raw is None:
+            return None, None
+        if self.consistency_min_views == 0:
+            self.index_map = index
+            return raw, None
+        checked = [e for e in earlier if e[3] is not None]
+        if len(checked) < self.consistency_min_views:
+            return None, None
+        self.index_map = index
+        depth, self.counts_map = self.volume.filter_depth_consistency(
+            raw, [e[3] for e in checked], intrinsic=K, T_ref=T, T_sources=np.stack([e[1] for e in checked]),
+            max_reproj_error=self.consistency_max_reproj, inv_depth_tol=self.consistency_inv_depth_steps * self.plane_step(), rel_depth_tol=0.0,
+            min_consistent=self.consistency_min_views, max_violations=min(self.consistency_max_violations, len(checked)), fuse=True, counts=True)
         return depth, None
+
+    def plane_step(self):
+        """One plane step of this estimator's sweep in inverse metres: (1 / min_depth - 1 / max_depth) / (num_planes - 1)"""
+        far = 0.0 if np.isinf(self.max_depth) else 1.0 / self.max_depth
+        return (1.0 / self.min_depth - far) / (int(self.mvs_params.get("num_planes", 128)) - 1)
 
 
 def make_stub_stereo_net(seed=0):

@@ -127,6 +127,20 @@ def plane_sweep_views(K_ref, T_ref_cw, K_src, T_src_cw):
     return np.ascontiguousarray(out.astype(np.float32))
 
 
+def consistency_views(K_ref, T_ref_cw, K_src, T_src_cw):
+    """Both directions of plane_sweep_views, as filter_depth_consistency takes them (include/hipvol.h rules C2 and C3): views[s] takes
+    a reference pixel and an inverse depth to source s, back_views[s] a pixel of source s and its inverse depth to the reference.
+    Arguments as plane_sweep_views.  -> (views, back_views), float32 [N,3,4] each"""
+    T_src = np.asarray(T_src_cw, dtype=np.float64).reshape(-1, 4, 4)
+    if isinstance(K_src, (list, tuple)) and len(K_src) == len(T_src) and not np.isscalar(K_src[0]):
+        Ks = list(K_src)
+    else:
+        Ks = [K_src] * len(T_src)
+    views = plane_sweep_views(K_ref, T_ref_cw, K_src, T_src)
+    back = np.concatenate([plane_sweep_views(K, T, K_ref, T_ref_cw) for K, T in zip(Ks, T_src)]) if len(T_src) else views.copy()
+    return views, np.ascontiguousarray(back)
+
+
 class RectifyMaps:
     """A pair of maps fixed for a camera's lifetime, for volume.remap: host arrays for host images, and for a CUDA image a device
     copy made once per device (remap itself keeps nothing between calls).  The host arrays are this object's own read-only copies,

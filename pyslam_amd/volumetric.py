@@ -378,6 +378,13 @@ class SpeckleStats(_Stats):
     __slots__ = ("valid_pixels", "components", "largest", "removed_components", "removed_pixels")
 
 
+class ConsistencyStats(_Stats):
+    """What one filter_depth_consistency found (hv_consistency_stats): valid_pixels = pixels with a depth on input, kept_pixels =
+    pixels the check kept, agree_sum = the sum over all pixels of the views that agree."""
+
+    __slots__ = ("valid_pixels", "kept_pixels", "agree_sum")
+
+
 class SpeckleResult:
     """What filter_speckles returns when more than the image is asked for: image (the filtered image), depth (the companion depth
     with 0 where a pixel was removed, or None), labels (int32 [H,W]: the smallest row-major index of the pixel's region, -1 for an
@@ -1028,6 +1035,94 @@ class _Volume:
             L.check(self._lib.hv_mvs_sgm(self._h, L.ptr(a), L.ptr(b), N, H, W, channels, L.ptr(m), ctypes.byref(prm), L.ptr(out["index"]),
                                          L.ptr(out["depth"]), None, L.location(a)))
         return out["index"], out["depth"]
+
+    def filter_depth_consistency(self, depth, source_depths, views=None, back_views=None, *, intrinsic=None, T_ref=None, T_sources=None,
+                                 max_reproj_error=1.0, inv_depth_tol=0.0, rel_depth_tol=0.01, min_consistent=1, max_violations=0, fuse=True,
+                                 counts=False, stats=False):
+        """The cross-view consistency check of a float32 depth map [H,W] against the depth maps of 1..4 posed neighbours of the same
+        shape (hv_depth_consistency, the rules C1 - C7 in include/hipvol.h): a pixel is projected with its depth into each
+        neighbour, the neighbour's depth is read there and projected back; the view agrees when the pixel lands within
+        max_reproj_error pixels of where it started and its inverse depth within inv_depth_tol + rel_depth_tol / depth of what it
+        started with.  A view that has a depth there and does not agree is occluded (it sees something nearer) or violated (it sees
+        through the point).  A pixel is kept iff at least min_consistent views agree and at most max_violations are violated.
+        -> (depth float32 [H,W]: 0 where a pixel went, the mean of its own and the agreeing views' depths with fuse, its own
+        depth without; counts uint8 [H,W,4]: agree, occluded, violated, seen - or None without counts=True) and, with stats=True,
+        a ConsistencyStats as a third item (the call then waits for the stream).  source_depths: a list of images or one [N,H,W]
+        array.  Pass views and back_views, [N,3,4] float32 each (reference pixel -> source s, pixel of source s -> reference, in
+        the convention of multiview_sgm), or intrinsic with the world-to-camera poses T_ref [4,4] and T_sources [N,4,4], which
+        prep.consistency_views turns into both.  inv_depth_tol is absolute, in 1 / metres: one plane step for the depth of a
+        plane sweep; rel_depth_tol is relative: for metric sensors; one of them must be positive.  numpy arrays in, numpy arrays
+        out; torch CUDA tensors on the volume's GPU in, tensors out, queued on the volume's stream.  Works on a volume of any
+        mode and reads nothing of it."""
+        on_gpu = L.location(depth) == L.HV_DEVICE
+        is_list = isinstance(source_depths, (list, tuple))
+        src_list = list(source_depths) if is_list else [source_depths]
+        if not src_list or any((L.location(s) == L.HV_DEVICE) != on_gpu for s in src_list):
+            raise ValueError("filter_depth_consistency: depth and source_depths must live in the same place")
+        if on_gpu:
+            import torch
+
+            if depth.dtype != torch.float32 or any(s.dtype != torch.float32 for s in src_list):
+                raise ValueError("filter_depth_consistency: the depth maps must be float32")
+            if any(t.device != self._device() for t in [depth] + src_list):
+                raise ValueError(f"filter_depth_consistency: the depth maps must live on the volume's GPU {self._device()}")
+            a, stack = depth.contiguous(), torch.stack
+        else:
+            a = depth.cpu().numpy() if _is_torch(depth) else np.asarray(depth)
+            src_list = [s.cpu().numpy() if _is_torch(s) else np.asarray(s) for s in src_list]
+            if a.dtype != np.float32 or any(s.dtype != np.float32 for s in src_list):
+                raise ValueError("filter_depth_consistency: the depth maps must be float32")
+            a, stack = np.ascontiguousarray(a), np.stack
+        # a list of maps of the reference's shape becomes one block; an array or tensor must be [N] + that shape already
+        want = tuple(a.shape) if is_list else (int(src_list[0].shape[0]),) + tuple(a.shape) if src_list[0].ndim else None
+        if a.ndim != 2 or any(tuple(s.shape) != want for s in src_list):
+            raise ValueError(f"filter_depth_consistency: the sources must be 1..4 depth maps of the reference's shape {tuple(a.shape)}")
+        b = stack(src_list) if is_list else src_list[0].contiguous() if on_gpu else np.ascontiguousarray(src_list[0])
+        N, H, W = int(b.shape[0]), int(a.shape[0]), int(a.shape[1])
+        # what hv_depth_consistency answers with HV_ERR_INVALID, refused here before anything is allocated
+        if H < 1 or W < 1 or H > 32768 or W > 32768 or H * W >= 1 << 30:
+            raise ValueError(f"filter_depth_consistency: bad image size {tuple(a.shape)}")
+        if not 1 <= N <= 4:
+            raise ValueError(f"filter_depth_consistency: need 1..4 source views, got {N}")
+        f32_max = float(np.finfo(np.float32).max)  # (the library reads float32)
+        if not 0.0 <= float(max_reproj_error) <= f32_max:
+            raise ValueError(f"filter_depth_consistency: max_reproj_error must be finite and not negative, got {max_reproj_error}")
+        if not (0.0 <= float(inv_depth_tol) <= f32_max and 0.0 <= float(rel_depth_tol) <= f32_max):
+            raise ValueError(f"filter_depth_consistency: the depth tolerances must be finite and not negative, got {inv_depth_tol} and {rel_depth_tol}")
+        if not (np.float32(inv_depth_tol) > 0 or np.float32(rel_depth_tol) > 0):
+            raise ValueError("filter_depth_consistency: one of inv_depth_tol and rel_depth_tol must be positive")
+        if int(min_consistent) != min_consistent or not 0 <= int(min_consistent) <= N:
+            raise ValueError(f"filter_depth_consistency: min_consistent must be in 0..{N}, got {min_consistent}")
+        if int(max_violations) != max_violations or not 0 <= int(max_violations) <= N:
+            raise ValueError(f"filter_depth_consistency: max_violations must be in 0..{N}, got {max_violations}")
+        if (views is None) != (back_views is None) or (views is None) == (intrinsic is None):
+            raise ValueError("filter_depth_consistency: pass either views and back_views or intrinsic with T_ref and T_sources")
+        if views is None:
+            if T_ref is None or T_sources is None:
+                raise ValueError("filter_depth_consistency: intrinsic needs the poses T_ref and T_sources")
+            from .prep import consistency_views
+
+            m, mb = consistency_views(intrinsic, T_ref, intrinsic, T_sources)
+        else:
+            if T_ref is not None or T_sources is not None:
+                raise ValueError("filter_depth_consistency: pass either views and back_views or intrinsic with T_ref and T_sources")
+            m, mb = (np.ascontiguousarray(x.cpu().numpy() if _is_torch(x) else x, dtype=np.float32) for x in (views, back_views))
+        for name, x in (("views", m), ("back_views", mb)):
+            if x.size != 12 * N or tuple(x.shape[-2:]) != (3, 4):
+                raise ValueError(f"filter_depth_consistency: {name} must be [{N}, 3, 4], got {tuple(x.shape)}")
+            if not np.isfinite(x).all():
+                raise ValueError("filter_depth_consistency: a view matrix entry is not finite")
+        prm = L.HvConsistencyParams(float(max_reproj_error), float(inv_depth_tol), float(rel_depth_tol), int(min_consistent), int(max_violations),
+                                    1 if fuse else 0)
+        out = self._results({"depth": ((H, W), np.float32), "counts": ((H, W, 4), np.uint8) if counts else None}, on_gpu, pinned=False,
+                            synchronize=False)
+        st = L.HvConsistencyStats() if stats else None
+        with self._ordered(a, b, out["depth"], out["counts"]):
+            L.check(self._lib.hv_depth_consistency(self._h, L.ptr(a), L.ptr(b), N, H, W, L.ptr(m), L.ptr(mb), ctypes.byref(prm), L.ptr(out["depth"]),
+                                                   L.ptr(out["counts"]), ctypes.byref(st) if stats else None, L.location(a)))
+        if stats:
+            return out["depth"], out["counts"], _stats(ConsistencyStats, st)
+        return out["depth"], out["counts"]
 
     def remap(self, img, map_x, map_y, linear=False):
         """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU; the maps are [H, W] like the image.
