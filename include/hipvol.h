@@ -844,6 +844,71 @@ int hv_tsdf_track_color(hv_volume *v, const void *depth, int32_t depth_dtype, co
                         const double *intr, const double *T_cw_init, const hv_track_color_params *params, hv_track_color_result *result,
                         double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc);
 
+/* Frame-to-frame RGB-D odometry (the place of Open3D's rgbd_odometry_multi_scale, methods PointToPlane and Hybrid): how did the
+ * camera move between two RGB-D frames - the first keyframes of a session, when the map is still empty; a relative-pose check of a
+ * loop-closure candidate; a start pose for hv_tsdf_track after a fast motion.  It is hv_tsdf_track / hv_tsdf_track_color with the
+ * model built from a second frame instead of a cast of the map.  This project's own contract.  The volume is context only (stream,
+ * scratch, staging; any mode): nothing of the map is read or changed.  Both colours NULL: the depth-only call (hv_tsdf_track's 30
+ * sums, trace rows of HV_TRACK_TRACE_STRIDE); both given: hybrid (hv_tsdf_track_color's 32 sums, HV_TRACK_COLOR_TRACE_STRIDE);
+ * exactly one NULL: HV_ERR_INVALID.  EVERYTHING not listed here stays as hv_tsdf_track / hv_tsdf_track_color state it - level
+ * intrinsics, source pyramid (depth and intensity, of the SOURCE frame), association, inlier test, residual, Jacobian, Huber weights,
+ * the photometric expansion, the sums and their order, the solve, the degenerate and stopping rules, the trace row layout and the
+ * outputs of the last level-0 linearisation:
+ *   frames    ANCHOR = the target camera.  transformation = T_target_source maps a point in source-camera coordinates into
+ *             target-camera coordinates; with world poses T_cw(target) inverse(T_cw(source)).  The state A starts at T_init (NULL:
+ *             the identity; else finite with bottom row 0 0 0 1), A := exp(xi) A, and transformation is A itself.
+ *   target    the source pyramid's rules applied to the target frame: depth z (float32, 0 = invalid) and, hybrid, intensity I_t of
+ *             every level.
+ *   model     per level with iterations[l] > 0, per target pixel (u, v), with P(u, v) = z ((u - cx) / fx, (v - cy) / fy, 1) in double
+ *             at the level's intrinsics: mask = 1 iff 1 <= u <= W-2 and 1 <= v <= H-2, z > 0 at the pixel and its four neighbours,
+ *             |z(neighbour) - z(u, v)| <= depth_outlier_trunc for each (the float32 depths subtracted and compared in double), and
+ *             c = dy x dx, dx = P(u+1, v) - P(u-1, v), dy = P(u, v+1) - P(u, v-1), has a finite length sqrt((c_x c_x + c_y c_y) + c_z c_z)
+ *             > 0.  normal = c / |c|, negated when (n_x P_x + n_y P_y) + n_z P_z > 0 at (u, v) (it faces the camera), each component
+ *             rounded to float32; 0 where mask = 0.  The model depth is z, the vertex q = P.  The normals are in the anchor frame
+ *             already: the linearisation's R0 is the identity.
+ *   record    hybrid, per target pixel: I_m = I_t(u, v); where mask = 1, g_x = 0.5f (I_t(u+1, v) - I_t(u-1, v)), g_y = 0.5f
+ *             (I_t(u, v+1) - I_t(u, v-1)) and has-gradient = 1, elsewhere g = 0 and has-gradient = 0: every inlier carries a
+ *             photometric term, photometric_inliers == inliers.  A level narrower or lower than 3 pixels has an empty mask and ends
+ *             degenerate (fewer than HV_TRACK_MIN_INLIERS inliers).
+ *   result    as hv_tsdf_track; photometric_inliers and intensity_rmse are 0 in the depth-only call.  When the FIRST level-0
+ *             linearisation is degenerate (empty frames are not an error), success = 0 and transformation = T_init.
+ * intensity_weight and intensity_huber_delta are read (and checked) by the hybrid call only; with intensity_weight = 0 it gives the
+ * depth-only call's transformation, information, fitness, inlier_rmse, counts, iterations and flags bit for bit.  Depths and colours
+ * are all at loc; colour channel order as hv_tsdf_set_color_order.  Errors as hv_tsdf_track (sizes against n_levels, depth range,
+ * scale, thresholds, iterations), checked before any launch.  All launches are queued at once on the volume's stream, one host
+ * wait, no float atomics, bitwise reproducible.
+ * hv_rgbd_odometry_model: what the call builds from its target frame, for tests and for users who want the maps - the pyramid of
+ * one frame down to `level` (0 .. HV_TRACK_MAX_LEVELS - 1, H >> level >= 1), then the model of that level: depth [h,w] float32,
+ * normal [h,w,3] float32, mask [h,w] uint8, record [h,w,4] float32 {I_m, g_x, g_y, has-gradient}, at loc; any may be NULL; a record
+ * needs a colour.  Of params it reads depth_scale, depth_min, depth_max and depth_outlier_trunc. */
+typedef struct hv_odometry_params {
+    double depth_scale, depth_min, depth_max;
+    double depth_outlier_trunc;   /* Open3D default 0.07 m */
+    double depth_huber_delta;     /* Open3D default 0.05 m */
+    double intensity_weight;      /* hybrid: lambda >= 0 */
+    double intensity_huber_delta; /* hybrid: > 0, image range [0, 1] */
+    int32_t n_levels;
+    int32_t iterations[HV_TRACK_MAX_LEVELS]; /* per level, level 0 first */
+} hv_odometry_params;
+typedef struct hv_odometry_result {
+    double transformation[16]; /* T_target_source, row-major */
+    double information[36];
+    double fitness, inlier_rmse;
+    int64_t inliers, valid;
+    int32_t iterations[HV_TRACK_MAX_LEVELS];
+    int32_t degenerate;
+    int32_t success;
+    int64_t photometric_inliers;
+    double intensity_rmse;
+} hv_odometry_result;
+int hv_rgbd_odometry(hv_volume *v, const void *source_depth, const void *target_depth, int32_t depth_dtype,
+                     const uint8_t *source_color, const uint8_t *target_color, int32_t height, int32_t width, const double *intr,
+                     const double *T_init, const hv_odometry_params *params, hv_odometry_result *result, double *trace,
+                     int64_t trace_cap, int64_t *trace_rows, int32_t loc);
+int hv_rgbd_odometry_model(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height, int32_t width,
+                           const double *intr, const hv_odometry_params *params, int32_t level, float *out_depth, float *out_normal,
+                           uint8_t *out_mask, float *out_record, int32_t loc);
+
 /* Pruning: give units back to the pool.  Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
  * sampled depth point, whether or not a voxel of it is then updated, and de-integration leaves the units it emptied allocated - so
  * a long session holds units that carry nothing, and units far from where the camera now is.  This project's own contract (Open3D's

@@ -82,6 +82,36 @@ class HvTrackColorResult(_c.Structure):
     _fields_ = [("base", HvTrackResult), ("photometric_inliers", _i64), ("intensity_rmse", _f64)]
 
 
+class HvOdometryParams(_c.Structure):
+    _fields_ = [
+        ("depth_scale", _f64),
+        ("depth_min", _f64),
+        ("depth_max", _f64),
+        ("depth_outlier_trunc", _f64),
+        ("depth_huber_delta", _f64),
+        ("intensity_weight", _f64),
+        ("intensity_huber_delta", _f64),
+        ("n_levels", _i32),
+        ("iterations", _i32 * HV_TRACK_MAX_LEVELS),
+    ]
+
+
+class HvOdometryResult(_c.Structure):
+    _fields_ = [
+        ("transformation", _f64 * 16),
+        ("information", _f64 * 36),
+        ("fitness", _f64),
+        ("inlier_rmse", _f64),
+        ("inliers", _i64),
+        ("valid", _i64),
+        ("iterations", _i32 * HV_TRACK_MAX_LEVELS),
+        ("degenerate", _i32),
+        ("success", _i32),
+        ("photometric_inliers", _i64),
+        ("intensity_rmse", _f64),
+    ]
+
+
 HV_TSDF_DEINTEGRATE_MAX_FRAMES = 64
 
 
@@ -367,6 +397,8 @@ SIGNATURES = {
     "hv_tsdf_register_volume": (_i32, [_vp, _vp, _vp, _c.POINTER(HvRegisterParams), _c.POINTER(HvRegisterResult), _vp, _i64, _pi64]),
     "hv_tsdf_track": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    "hv_rgbd_odometry": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
+    "hv_rgbd_odometry_model": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
     "hv_lookup_points": (_i32, [_vp, _vp, _i32, _i64, _c.POINTER(HvLookupParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(HvLookupStats), _i32]),

@@ -573,7 +573,7 @@ struct hv_volume {
     size_t out_a_bytes = 0, out_b_bytes = 0, out_c_bytes = 0;
     void *dist_buf = nullptr;    // hv_tsdf_distance_field: counters, the intermediate grid, classes and HV_HOST outputs (hv_distance.hip)
     size_t dist_buf_bytes = 0;
-    void *track_buf = nullptr;   // hv_tsdf_track: source pyramid, model casts, reduction slab, state and trace (device)
+    void *track_buf = nullptr;   // hv_tsdf_track / hv_rgbd_odometry: source pyramid, model maps, reduction slab, state and trace (device)
     size_t track_buf_bytes = 0;
     // histograms + state of hv_filter_shadow_points_on_stream (a caller's stream, beside the volume's: scratch of its own, four sets in turn)
     void *shadow_ring = nullptr;

@@ -1,6 +1,7 @@
 // libpyslam_hipvol.so — frame-to-model tracking against the fused TSDF map on gfx950: point-to-plane (hv_tsdf_track) and hybrid,
-// point-to-plane plus a photometric term on the map's colour (hv_tsdf_track_color).  The contracts (pyramid, model, association,
-// linearisation, solve, stopping, outputs) are written once in include/hipvol.h; tests/track_reference.py and
+// point-to-plane plus a photometric term on the map's colour (hv_tsdf_track_color); and the same schedule against a second RGB-D
+// frame instead of the map, frame-to-frame odometry (hv_rgbd_odometry, last paragraph).  The contracts (pyramid, model,
+// association, linearisation, solve, stopping, outputs) are written once in include/hipvol.h; tests/track_reference.py and
 // tests/track_color_reference.py restate them in numpy.
 //
 // Per call, all on the volume's stream and queued up front: one launch per source pyramid level, one ray cast per level (the
@@ -16,6 +17,11 @@
 // k_track_linearise<32> adds the photometric rank-1 update and two more sums (32 instead of 30).  The geometric body, workgroup
 // size, grid rule and reduction are one text for both instantiations - so with intensity_weight = 0 every float64 sum associates
 // as in the depth-only call and the two agree bit for bit.
+//
+// Frame-to-frame odometry is tk_run with another model provider: where the tracker queues a ray cast (and k_track_model_prep) per
+// level, TkFrameModel queues the target frame's pyramid (the source pyramid's two kernels) and one k_odometry_model launch per level,
+// which turns the level's depth (and intensity) into normal, mask (and record); the state starts at T_init, the normals need no
+// rotation (R0 = identity), and the result pose is the state A itself.  tests/odometry_reference.py restates it.
 #include <cmath>
 
 #include "hv_common.h"
@@ -44,15 +50,15 @@ using TkStateColor = TkStateT<TK_NACC_COLOR>;
 
 struct TkLevel {
     const float *src;        // source depth of the level, metres, 0 = invalid
-    const float *mdepth;     // model (cast) depth
-    const float *mnormal;    // model normal, world frame [H,W,3]
-    const uint8_t *mmask;    // model hit mask
+    const float *mdepth;     // model depth (the map cast at T_cw_init, or the target frame)
+    const float *mnormal;    // model normal [H,W,3]: world frame (cast) or anchor frame already (target frame, R0 = identity)
+    const uint8_t *mmask;    // model mask
     int32_t height, width;
     double fx, fy, cx, cy;
 };
 
 struct TkParams {
-    double R0[9];  // R_cw_init: world normal -> anchor frame
+    double R0[9];  // model normal -> anchor frame: R_cw_init for the cast's world normals, the identity for a target frame's
     double trunc, delta;
 };
 
@@ -149,6 +155,78 @@ __global__ __launch_bounds__(256) void k_track_model_prep(const float *__restric
         }
     }
     rec[i] = o;
+}
+
+// frame-to-frame: the state of k_track_init with A = A0 (T_init) instead of the identity
+struct TkPose {
+    double m[16];
+};
+template <int NACC>
+__global__ __launch_bounds__(64) void k_track_init_at(TkStateT<NACC> *st, TkPose A0) {
+    const int t = threadIdx.x;
+    if (t < 16) st->A[t] = A0.m[t];
+    if (t < NACC) st->last[t] = 0.0;
+    if (t < HV_TRACK_MAX_LEVELS) {
+        st->done[t] = 0;
+        st->iters[t] = 0;
+    }
+    if (t == 0) st->rows = 0;
+}
+
+// frame-to-frame, per level: the target frame's depth z (and intensity it) of the level -> the model the linearisation reads: normal
+// and mask, HYBRID also the record {I_t, g_x, g_y, has-gradient}.  One thread per target pixel, a 5-point stencil on plain loads
+// (a row's neighbours are the same cache lines, the rows above and below were just read by the neighbouring workgroups).
+// mask = 1 iff the pixel is off the border, z > 0 at it and its four neighbours, no neighbour's depth is further than trunc from its
+// own (double), and c = dy x dx of the back-projected central differences has a finite length > 0; normal = c / |c|, turned to face
+// the camera, rounded to float32; 0 where mask = 0.  All geometry in double, one IEEE operation per step (tests/odometry_reference.py
+// restates it bit for bit).
+template <bool HYBRID>
+__global__ __launch_bounds__(256) void k_odometry_model(const float *__restrict__ z, const float *__restrict__ it, int32_t height, int32_t width,
+                                                        double fx, double fy, double cx, double cy, double trunc, float *__restrict__ normal,
+                                                        uint8_t *__restrict__ mask, float4 *__restrict__ rec) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)height * width) return;
+    const int u = (int)(i % width), v = (int)(i / width);
+    float n[3] = {0.0f, 0.0f, 0.0f};
+    bool ok = false;
+    const bool inner = u >= 1 && v >= 1 && u + 1 < width && v + 1 < height;
+    const int64_t nb[4] = {i + 1, i - 1, i + width, i - width}; // (read only when inner)
+    if (inner) {
+        const float zc = z[i];
+        const float zn[4] = {z[nb[0]], z[nb[1]], z[nb[2]], z[nb[3]]};
+        ok = zc > 0.0f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ok = ok && zn[k] > 0.0f && fabs((double)zn[k] - (double)zc) <= trunc;
+        if (ok) {
+            const double xm = ((double)(u - 1) - cx) / fx, x0 = ((double)u - cx) / fx, xp = ((double)(u + 1) - cx) / fx;
+            const double ym = ((double)(v - 1) - cy) / fy, y0 = ((double)v - cy) / fy, yp = ((double)(v + 1) - cy) / fy;
+            const double zr = (double)zn[0], zl = (double)zn[1], zd = (double)zn[2], zu = (double)zn[3], zz = (double)zc;
+            const double dx[3] = {zr * xp - zl * xm, zr * y0 - zl * y0, zr - zl};
+            const double dy[3] = {zd * x0 - zu * x0, zd * yp - zu * ym, zd - zu};
+            const double c[3] = {dy[1] * dx[2] - dy[2] * dx[1], dy[2] * dx[0] - dy[0] * dx[2], dy[0] * dx[1] - dy[1] * dx[0]};
+            const double len = sqrt((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+            ok = isfinite(len) && len > 0.0;
+            if (ok) {
+                double m[3] = {c[0] / len, c[1] / len, c[2] / len};
+                const bool away = (m[0] * (zz * x0) + m[1] * (zz * y0)) + m[2] * zz > 0.0;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) n[k] = (float)(away ? -m[k] : m[k]);
+            }
+        }
+    }
+    normal[3 * i] = n[0];
+    normal[3 * i + 1] = n[1];
+    normal[3 * i + 2] = n[2];
+    mask[i] = ok ? 1 : 0;
+    if constexpr (HYBRID) {
+        float4 o = make_float4(it[i], 0.0f, 0.0f, 0.0f);
+        if (ok) {
+            o.y = 0.5f * (it[nb[0]] - it[nb[1]]);
+            o.z = 0.5f * (it[nb[2]] - it[nb[3]]);
+            o.w = 1.0f;
+        }
+        rec[i] = o;
+    }
 }
 
 
@@ -272,55 +350,222 @@ __global__ __launch_bounds__(TK_SUM_THREADS) void k_track_solve(TkStateT<NACC> *
     if (status != 0) st->done[level] = status;
 }
 
-// Both entry points: HYBRID = false is hv_tsdf_track (color, cprm and cres unused), true is hv_tsdf_track_color.  The depth-only
-// call queues exactly the launches it always did, with null colour / intensity operands.
-template <bool HYBRID>
-int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height, int32_t width,
-           const double *intr, const double *T_cw_init, const hv_track_params *prm, const hv_track_color_params *cprm,
-           hv_track_result *res, hv_track_color_result *cres, double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc) {
+// ---- the schedule, once (tk_run), and the two things a kind of call supplies to it ------------------------------------------------
+// What every call shares: the schedule's numbers, checked by tk_run before any launch.
+struct TkSchedule {
+    double depth_scale, depth_min, depth_max, trunc, delta;
+    double lambda, idelta;  // hybrid only
+    int32_t n_levels;
+    const int32_t *iterations;
+};
+
+// One level's model maps in the call's scratch, as tk_run hands them to the provider that fills them.
+struct TkModelMaps {
+    float *depth, *normal;
+    uint8_t *mask;
+    float *aux;   // hybrid: the provider's own plane of AUX_BYTES per pixel (cast colour / target intensity)
+    float4 *rec;  // hybrid: {I_m, g_x, g_y, has-gradient}
+    int32_t height, width;
+    double K[4];
+};
+
+// What tk_run leaves behind: the final state and the outputs of the last level-0 linearisation.  The caller forms its pose from A.
+struct TkOutcome {
+    double A[16];
+    double information[36];
+    double fitness, inlier_rmse, intensity_rmse;
+    int64_t inliers, valid, photometric_inliers;
+    int32_t iterations[HV_TRACK_MAX_LEVELS];
+    int32_t degenerate, success;
+    bool level0_started;  // a level-0 linearisation left the level running (false: A holds coarser levels' steps at most)
+};
+
+template <class Result>
+void tk_copy_result(const TkOutcome &o, Result *res) {
+    for (int i = 0; i < 36; ++i) res->information[i] = o.information[i];
+    res->fitness = o.fitness;
+    res->inlier_rmse = o.inlier_rmse;
+    res->inliers = o.inliers;
+    res->valid = o.valid;
+    for (int l = 0; l < HV_TRACK_MAX_LEVELS; ++l) res->iterations[l] = o.iterations[l];
+    res->degenerate = o.degenerate;
+    res->success = o.success;
+}
+
+// A model provider says where the per-level model comes from.  tk_run calls, in this order: check() (before any launch), stage()
+// (the call's frames -> device pointers of the SOURCE frame), start() (queues the state's initialisation), after the source pyramid
+// prepare() (what the levels' models need first) and per level with iterations level() (queues the model of that level into its
+// maps); R0() is the rotation the linearisation applies to the model's normals.
+
+// Frame-to-model: the map cast at T_cw_init, hybrid also k_track_model_prep on the cast's colour (hv_tsdf_track[_color]).
+struct TkMapModel {
+    static constexpr size_t AUX_BYTES = 12;  // the cast's colour
+    hv_volume *v;
+    const char *fn;
+    const void *depth;
+    int32_t depth_dtype;
+    const uint8_t *color;
+    const double *T0;
+    double depth_min, depth_max, weight_threshold, trunc;
+
+    int check() const {
+        HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", fn);
+        HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: tracking needs the whole volume (owner-sharded: merge or gather first)", fn);
+        HV_REQUIRE(std::isfinite(weight_threshold), HV_ERR_INVALID, "%s: bad intrinsics / threshold / scale", fn);
+        for (int r = 0; r < 4; ++r)
+            for (int c = 0; c < 4; ++c) HV_REQUIRE(std::isfinite(T0[r * 4 + c]), HV_ERR_INVALID, "%s: T_cw_init is not finite", fn);
+        return HV_OK;
+    }
+    int stage(size_t npx, int32_t loc, const void **d_depth, const uint8_t **d_color) {
+        return hv_stage_frame(v, depth, depth_dtype, color, npx, loc, d_depth, d_color);
+    }
+    template <int NACC>
+    void start(TkStateT<NACC> *st) const {
+        hipLaunchKernelGGL(k_track_init<NACC>, dim3(1), dim3(64), 0, v->stream, st);
+    }
+    template <bool HYBRID>
+    int prepare(const TkModelMaps *, int) const {
+        return HV_OK;
+    }
+    template <bool HYBRID>
+    int level(const TkModelMaps &m) const {
+        const int rc = hv_ray_cast_launch(v, m.height, m.width, m.K, T0, depth_min, depth_max, weight_threshold, 1.0, m.depth, nullptr, m.normal,
+                                          HYBRID ? m.aux : (float *)nullptr, m.mask);
+        if (rc != HV_OK) return rc;
+        if (HYBRID) {
+            const size_t n = (size_t)m.height * (size_t)m.width;
+            hv_profile_begin(v);
+            hipLaunchKernelGGL(k_track_model_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, (const float *)m.aux,
+                               (const float *)m.depth, (const uint8_t *)m.mask, m.height, m.width, trunc, m.rec);
+            hv_profile_end(v, 0);
+        }
+        return HV_OK;
+    }
+    void R0(double *R) const {
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) R[r * 3 + c] = T0[r * 4 + c];
+    }
+};
+
+// Frame-to-frame: the model is a second RGB-D frame (hv_rgbd_odometry): its pyramid through the source's two kernels straight into
+// the levels' model depth (and, hybrid, the aux plane = target intensity), then k_odometry_model per level.
+struct TkFrameModel {
+    static constexpr size_t AUX_BYTES = 4;  // the target intensity of the level
+    hv_volume *v;
+    const char *fn;
+    const void *source_depth, *target_depth;
+    int32_t depth_dtype;
+    const uint8_t *source_color, *target_color;
+    double T0[16];
+    double depth_scale, depth_min, depth_max, trunc;
+    const void *d_target_depth = nullptr;
+    const uint8_t *d_target_color = nullptr;
+
+    int check() const {
+        for (int i = 0; i < 16; ++i) HV_REQUIRE(std::isfinite(T0[i]), HV_ERR_INVALID, "%s: T_init is not finite", fn);
+        HV_REQUIRE(T0[12] == 0.0 && T0[13] == 0.0 && T0[14] == 0.0 && T0[15] == 1.0, HV_ERR_INVALID, "%s: T_init's bottom row must be 0 0 0 1", fn);
+        return HV_OK;
+    }
+    int stage(size_t npx, int32_t loc, const void **d_depth, const uint8_t **d_color) {
+        HvStage st(v, loc);
+        const size_t depth_bytes = npx * (depth_dtype == HV_DEPTH_U16 ? 2 : 4);
+        const int i_sd = st.in(source_depth, depth_bytes), i_td = st.in(target_depth, depth_bytes);
+        const int i_sc = st.in(source_color, npx * 3), i_tc = st.in(target_color, npx * 3);
+        const int rc = st.commit(&v->stage, &v->stage_bytes);
+        *d_depth = st.dev<const void>(i_sd);
+        *d_color = st.dev<const uint8_t>(i_sc);
+        d_target_depth = st.dev<const void>(i_td);
+        d_target_color = st.dev<const uint8_t>(i_tc);
+        return rc;
+    }
+    template <int NACC>
+    void start(TkStateT<NACC> *st) const {
+        TkPose A0;
+        for (int i = 0; i < 16; ++i) A0.m[i] = T0[i];
+        hipLaunchKernelGGL(k_track_init_at<NACC>, dim3(1), dim3(64), 0, v->stream, st, A0);
+    }
+    // the target pyramid, levels 0 .. nl - 1 (maps[l].depth, hybrid maps[l].aux)
+    template <bool HYBRID>
+    int prepare(const TkModelMaps *maps, int nl) const {
+        const size_t npx0 = (size_t)maps[0].height * (size_t)maps[0].width;
+        hv_profile_begin(v);
+        hipLaunchKernelGGL(k_track_source<HYBRID>, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_target_depth,
+                           depth_dtype == HV_DEPTH_U16 ? 1 : 0, d_target_color, v->color_bgr, (int64_t)npx0, (float)depth_scale, depth_min,
+                           depth_max, maps[0].depth, HYBRID ? maps[0].aux : (float *)nullptr);
+        hv_profile_end(v, 0);
+        for (int l = 1; l < nl; ++l) {
+            const size_t n = (size_t)maps[l].height * (size_t)maps[l].width;
+            hv_profile_begin(v);
+            hipLaunchKernelGGL(k_track_down<HYBRID>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, (const float *)maps[l - 1].depth,
+                               HYBRID ? (const float *)maps[l - 1].aux : (const float *)nullptr, maps[l - 1].width, maps[l].depth,
+                               HYBRID ? maps[l].aux : (float *)nullptr, maps[l].height, maps[l].width, trunc);
+            hv_profile_end(v, 0);
+        }
+        HV_HIP(hipGetLastError());
+        return HV_OK;
+    }
+    template <bool HYBRID>
+    int level(const TkModelMaps &m) const {
+        const size_t n = (size_t)m.height * (size_t)m.width;
+        hv_profile_begin(v);
+        hipLaunchKernelGGL(k_odometry_model<HYBRID>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream, (const float *)m.depth,
+                           HYBRID ? (const float *)m.aux : (const float *)nullptr, m.height, m.width, m.K[0], m.K[1], m.K[2], m.K[3], trunc,
+                           m.normal, m.mask, HYBRID ? m.rec : (float4 *)nullptr);
+        hv_profile_end(v, (int64_t)n);
+        return HV_OK;
+    }
+    void R0(double *R) const {
+        for (int i = 0; i < 9; ++i) R[i] = (i % 4 == 0) ? 1.0 : 0.0;
+    }
+};
+
+// What hv_tsdf_track states for sizes, depth range, intrinsics, scale, thresholds and iterations, for every kind of call
+int tk_check_schedule(const char *fn, const TkSchedule &S, bool hybrid, int32_t height, int32_t width, const double *intr, int64_t *steps) {
+    const int nl = S.n_levels;
+    HV_REQUIRE(nl >= 1 && nl <= HV_TRACK_MAX_LEVELS, HV_ERR_INVALID, "%s: need 1 to %d pyramid levels, got %d", fn, HV_TRACK_MAX_LEVELS, nl);
+    HV_REQUIRE(height > 0 && width > 0 && height <= 65535 && width <= 65535 && (height >> (nl - 1)) >= 1 && (width >> (nl - 1)) >= 1,
+               HV_ERR_INVALID, "%s: bad image size %d x %d for %d levels", fn, (int)height, (int)width, nl);
+    HV_REQUIRE(std::isfinite(S.depth_min) && std::isfinite(S.depth_max) && S.depth_min >= 0.0 && S.depth_min < S.depth_max, HV_ERR_INVALID,
+               "%s: bad depth range [%g, %g)", fn, S.depth_min, S.depth_max);
+    HV_REQUIRE(std::isfinite(intr[0]) && std::isfinite(intr[1]) && std::isfinite(intr[2]) && std::isfinite(intr[3]) && intr[0] != 0.0 &&
+                   intr[1] != 0.0 && std::isfinite(S.depth_scale) && S.depth_scale != 0.0,
+               HV_ERR_INVALID, "%s: bad intrinsics / threshold / scale", fn);
+    HV_REQUIRE(std::isfinite(S.trunc) && S.trunc > 0.0 && std::isfinite(S.delta) && S.delta > 0.0, HV_ERR_INVALID,
+               "%s: depth_outlier_trunc and depth_huber_delta must be positive", fn);
+    if (hybrid) {
+        HV_REQUIRE(std::isfinite(S.lambda) && S.lambda >= 0.0, HV_ERR_INVALID, "%s: intensity_weight must be finite and >= 0", fn);
+        HV_REQUIRE(std::isfinite(S.idelta) && S.idelta > 0.0, HV_ERR_INVALID, "%s: intensity_huber_delta must be positive", fn);
+    }
+    *steps = 0;
+    for (int l = 0; l < nl; ++l) {
+        HV_REQUIRE(S.iterations[l] >= 0 && S.iterations[l] <= 10000, HV_ERR_INVALID, "%s: bad iteration count %d at level %d", fn,
+                   (int)S.iterations[l], l);
+        *steps += S.iterations[l];
+    }
+    HV_REQUIRE(S.iterations[0] >= 1, HV_ERR_INVALID, "%s: level 0 needs at least one iteration", fn);
+    return HV_OK;
+}
+
+// Every entry point: state init, source pyramid, per-level model (the provider's), the linearise / solve steps, fetch, outcome.
+// HYBRID = false is the depth-only call (30 sums; colour operands null and not read), true the hybrid one (32 sums).  With
+// TkMapModel it queues exactly the launches hv_tsdf_track / hv_tsdf_track_color always queued.
+template <bool HYBRID, class Model>
+int tk_run(const char *fn, hv_volume *v, Model &model, const TkSchedule &S, int32_t depth_dtype, int32_t height, int32_t width,
+           const double *intr, TkOutcome *out, double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc) {
     constexpr int NACC = HYBRID ? TK_NACC_COLOR : TK_NACC;
     constexpr int STRIDE = HYBRID ? HV_TRACK_COLOR_TRACE_STRIDE : HV_TRACK_TRACE_STRIDE;
     using State = TkStateT<NACC>;
-    HV_REQUIRE(v != nullptr && depth != nullptr && intr != nullptr && T_cw_init != nullptr && prm != nullptr && res != nullptr &&
-                   (!HYBRID || color != nullptr),
-               HV_ERR_INVALID, "%s: null argument", fn);
-    HV_REQUIRE(v->cfg.mode == HV_MODE_TSDF, HV_ERR_MODE, "%s: volume is not in TSDF mode", fn);
-    HV_REQUIRE(v->owner_world <= 1, HV_ERR_MODE, "%s: tracking needs the whole volume (owner-sharded: merge or gather first)", fn);
-    HV_REQUIRE(depth_dtype == HV_DEPTH_F32 || depth_dtype == HV_DEPTH_U16, HV_ERR_INVALID, "%s: bad depth dtype %d", fn,
-               (int)depth_dtype);
+    HV_REQUIRE(depth_dtype == HV_DEPTH_F32 || depth_dtype == HV_DEPTH_U16, HV_ERR_INVALID, "%s: bad depth dtype %d", fn, (int)depth_dtype);
     HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "%s: bad loc %d", fn, (int)loc);
-    const int nl = prm->n_levels;
-    HV_REQUIRE(nl >= 1 && nl <= HV_TRACK_MAX_LEVELS, HV_ERR_INVALID, "%s: need 1 to %d pyramid levels, got %d", fn,
-               HV_TRACK_MAX_LEVELS, nl);
-    HV_REQUIRE(height > 0 && width > 0 && height <= 65535 && width <= 65535 && (height >> (nl - 1)) >= 1 && (width >> (nl - 1)) >= 1,
-               HV_ERR_INVALID, "%s: bad image size %d x %d for %d levels", fn, (int)height, (int)width, nl);
-    HV_REQUIRE(std::isfinite(prm->depth_min) && std::isfinite(prm->depth_max) && prm->depth_min >= 0.0 && prm->depth_min < prm->depth_max,
-               HV_ERR_INVALID, "%s: bad depth range [%g, %g)", fn, prm->depth_min, prm->depth_max);
-    HV_REQUIRE(std::isfinite(intr[0]) && std::isfinite(intr[1]) && std::isfinite(intr[2]) && std::isfinite(intr[3]) && intr[0] != 0.0 &&
-                   intr[1] != 0.0 && std::isfinite(prm->weight_threshold) && std::isfinite(prm->depth_scale) && prm->depth_scale != 0.0,
-               HV_ERR_INVALID, "%s: bad intrinsics / threshold / scale", fn);
-    HV_REQUIRE(std::isfinite(prm->depth_outlier_trunc) && prm->depth_outlier_trunc > 0.0 && std::isfinite(prm->depth_huber_delta) &&
-                   prm->depth_huber_delta > 0.0,
-               HV_ERR_INVALID, "%s: depth_outlier_trunc and depth_huber_delta must be positive", fn);
-    if (HYBRID) {
-        HV_REQUIRE(std::isfinite(cprm->intensity_weight) && cprm->intensity_weight >= 0.0, HV_ERR_INVALID,
-                   "%s: intensity_weight must be finite and >= 0", fn);
-        HV_REQUIRE(std::isfinite(cprm->intensity_huber_delta) && cprm->intensity_huber_delta > 0.0, HV_ERR_INVALID,
-                   "%s: intensity_huber_delta must be positive", fn);
-    }
+    int rc = model.check();
+    if (rc != HV_OK) return rc;
     int64_t steps = 0;
-    for (int l = 0; l < nl; ++l) {
-        HV_REQUIRE(prm->iterations[l] >= 0 && prm->iterations[l] <= 10000, HV_ERR_INVALID, "%s: bad iteration count %d at level %d", fn,
-                   (int)prm->iterations[l], l);
-        steps += prm->iterations[l];
-    }
-    HV_REQUIRE(prm->iterations[0] >= 1, HV_ERR_INVALID, "%s: level 0 needs at least one iteration", fn);
-    for (int r = 0; r < 4; ++r)
-        for (int c = 0; c < 4; ++c)
-            HV_REQUIRE(std::isfinite(T_cw_init[r * 4 + c]), HV_ERR_INVALID, "%s: T_cw_init is not finite", fn);
+    rc = tk_check_schedule(fn, S, HYBRID, height, width, intr, &steps);
+    if (rc != HV_OK) return rc;
+    const int nl = S.n_levels;
     HV_HIP(hipSetDevice(v->device));
 
-    // scratch: [state][slab][trace][per level: source, model depth, model normal, model mask; hybrid: model colour, model
+    // scratch: [state][slab][trace][per level: source, model depth, model normal, model mask; hybrid: the provider's plane, model
     // record, source intensity]
     size_t off = 0;
     auto take = [&off](size_t bytes) { // -> the offset of the next bytes, every piece 256-byte aligned
@@ -332,7 +577,7 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
     const size_t o_slab = take(sizeof(double) * NACC * TK_MAX_BLOCKS);
     const size_t o_trace = take(sizeof(double) * STRIDE * (size_t)steps);
     size_t o_src[HV_TRACK_MAX_LEVELS], o_md[HV_TRACK_MAX_LEVELS], o_mn[HV_TRACK_MAX_LEVELS], o_mm[HV_TRACK_MAX_LEVELS];
-    size_t o_mc[HV_TRACK_MAX_LEVELS] = {}, o_rec[HV_TRACK_MAX_LEVELS] = {}, o_int[HV_TRACK_MAX_LEVELS] = {};
+    size_t o_aux[HV_TRACK_MAX_LEVELS] = {}, o_rec[HV_TRACK_MAX_LEVELS] = {}, o_int[HV_TRACK_MAX_LEVELS] = {};
     for (int l = 0; l < nl; ++l) {
         const size_t n = (size_t)(height >> l) * (size_t)(width >> l);
         o_src[l] = take(4 * n);
@@ -340,12 +585,12 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
         o_mn[l] = take(12 * n);
         o_mm[l] = take(n);
         if (HYBRID) {
-            o_mc[l] = take(12 * n);
+            o_aux[l] = take(Model::AUX_BYTES * n);
             o_rec[l] = take(16 * n);
             o_int[l] = take(4 * n);
         }
     }
-    int rc = hv_ensure_buffer(v, &v->track_buf, &v->track_buf_bytes, off);
+    rc = hv_ensure_buffer(v, &v->track_buf, &v->track_buf_bytes, off);
     if (rc != HV_OK) return rc;
     char *base = (char *)v->track_buf;
     // the source intensity of a level; null in the depth-only call, whose kernels do not read it
@@ -357,59 +602,55 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
     const void *d_depth = nullptr;
     const uint8_t *d_color = nullptr;
     const size_t npx0 = (size_t)height * (size_t)width;
-    rc = hv_stage_frame(v, depth, depth_dtype, HYBRID ? color : nullptr, npx0, loc, &d_depth, &d_color);
+    rc = model.stage(npx0, loc, &d_depth, &d_color);
     if (rc != HV_OK) return rc;
     // reads only, as hv_tsdf_ray_cast: the next batch starts a fresh touch + pack chain behind this call
     v->pipe_armed = false;
 
-    hipLaunchKernelGGL(k_track_init<NACC>, dim3(1), dim3(64), 0, v->stream, st);
+    model.template start<NACC>(st);
     hv_profile_begin(v);
     hipLaunchKernelGGL(k_track_source<HYBRID>, dim3((unsigned)((npx0 + 255) / 256)), dim3(256), 0, v->stream, d_depth,
-                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, d_color, v->color_bgr, (int64_t)npx0, (float)prm->depth_scale,
-                       prm->depth_min, prm->depth_max, (float *)(base + o_src[0]), intensity(0));
+                       depth_dtype == HV_DEPTH_U16 ? 1 : 0, d_color, v->color_bgr, (int64_t)npx0, (float)S.depth_scale, S.depth_min,
+                       S.depth_max, (float *)(base + o_src[0]), intensity(0));
     hv_profile_end(v, 0);
     for (int l = 1; l < nl; ++l) {
         const int ho = height >> l, wo = width >> l;
         hv_profile_begin(v);
         hipLaunchKernelGGL(k_track_down<HYBRID>, dim3((unsigned)(((size_t)ho * wo + 255) / 256)), dim3(256), 0, v->stream,
                            (const float *)(base + o_src[l - 1]), (const float *)intensity(l - 1), width >> (l - 1),
-                           (float *)(base + o_src[l]), intensity(l), ho, wo, prm->depth_outlier_trunc);
+                           (float *)(base + o_src[l]), intensity(l), ho, wo, S.trunc);
         hv_profile_end(v, 0);
     }
     HV_HIP(hipGetLastError());
 
     TkLevel lv[HV_TRACK_MAX_LEVELS];
+    TkModelMaps maps[HV_TRACK_MAX_LEVELS];
     for (int l = 0; l < nl; ++l) {
         const double s = (double)(1 << l);
-        const double li[4] = {intr[0] / s, intr[1] / s, (intr[2] + 0.5) / s - 0.5, (intr[3] + 0.5) / s - 0.5};
-        lv[l] = TkLevel{(const float *)(base + o_src[l]), (const float *)(base + o_md[l]), (const float *)(base + o_mn[l]),
-                        (const uint8_t *)(base + o_mm[l]), height >> l, width >> l, li[0], li[1], li[2], li[3]};
-        if (prm->iterations[l] == 0) continue;
-        rc = hv_ray_cast_launch(v, height >> l, width >> l, li, T_cw_init, prm->depth_min, prm->depth_max, prm->weight_threshold, 1.0,
-                                (float *)(base + o_md[l]), nullptr, (float *)(base + o_mn[l]),
-                                HYBRID ? (float *)(base + o_mc[l]) : (float *)nullptr, (uint8_t *)(base + o_mm[l]));
+        maps[l] = TkModelMaps{(float *)(base + o_md[l]), (float *)(base + o_mn[l]), (uint8_t *)(base + o_mm[l]),
+                              HYBRID ? (float *)(base + o_aux[l]) : (float *)nullptr, HYBRID ? (float4 *)(base + o_rec[l]) : (float4 *)nullptr,
+                              height >> l, width >> l, {intr[0] / s, intr[1] / s, (intr[2] + 0.5) / s - 0.5, (intr[3] + 0.5) / s - 0.5}};
+        lv[l] = TkLevel{(const float *)(base + o_src[l]), maps[l].depth, maps[l].normal, maps[l].mask, height >> l, width >> l,
+                        maps[l].K[0], maps[l].K[1], maps[l].K[2], maps[l].K[3]};
+    }
+    rc = model.template prepare<HYBRID>(maps, nl);
+    if (rc != HV_OK) return rc;
+    for (int l = 0; l < nl; ++l) {
+        if (S.iterations[l] == 0) continue;
+        rc = model.template level<HYBRID>(maps[l]);
         if (rc != HV_OK) return rc;
-        if (HYBRID) {
-            const size_t n = (size_t)lv[l].height * (size_t)lv[l].width;
-            hv_profile_begin(v);
-            hipLaunchKernelGGL(k_track_model_prep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, v->stream,
-                               (const float *)(base + o_mc[l]), (const float *)(base + o_md[l]), (const uint8_t *)(base + o_mm[l]),
-                               lv[l].height, lv[l].width, prm->depth_outlier_trunc, (float4 *)(base + o_rec[l]));
-            hv_profile_end(v, 0);
-        }
     }
 
     TkParams P{};
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) P.R0[r * 3 + c] = T_cw_init[r * 4 + c];
-    P.trunc = prm->depth_outlier_trunc;
-    P.delta = prm->depth_huber_delta;
+    model.R0(P.R0);
+    P.trunc = S.trunc;
+    P.delta = S.delta;
     for (int l = nl - 1; l >= 0; --l) {
         const int64_t npx = (int64_t)lv[l].height * lv[l].width;
         const int blocks = (int)std::min<int64_t>((npx + TK_BLOCK - 1) / TK_BLOCK, TK_MAX_BLOCKS);
         TkColor C{}; // depth only: zero, and not read
-        if constexpr (HYBRID) C = TkColor{(const float4 *)(base + o_rec[l]), intensity(l), cprm->intensity_weight, cprm->intensity_huber_delta};
-        for (int it = 0; it < prm->iterations[l]; ++it) {
+        if constexpr (HYBRID) C = TkColor{(const float4 *)maps[l].rec, intensity(l), S.lambda, S.idelta};
+        for (int it = 0; it < S.iterations[l]; ++it) {
             hv_profile_begin(v);
             hipLaunchKernelGGL(k_track_linearise<NACC>, dim3((unsigned)blocks), dim3(TK_BLOCK), 0, v->stream, lv[l], P, C,
                                (const State *)st, l, slab);
@@ -433,41 +674,77 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
         *trace_rows = 0;
     }
 
+    for (int i = 0; i < 16; ++i) out->A[i] = h.A[i];
+    {
+        int q = 0;
+        for (int a = 0; a < 6; ++a)
+            for (int b = a; b < 6; ++b) {
+                out->information[a * 6 + b] = out->information[b * 6 + a] = h.last[q++];
+            }
+    }
+    const double e = h.last[27], inl = h.last[28], val = h.last[29];
+    out->inliers = (int64_t)inl;
+    out->valid = (int64_t)val;
+    out->fitness = val > 0.0 ? inl / val : 0.0;
+    out->inlier_rmse = inl > 0.0 ? std::sqrt(e / inl) : 0.0;
+    out->degenerate = 0;
+    for (int l = 0; l < HV_TRACK_MAX_LEVELS; ++l) {
+        out->iterations[l] = l < nl ? h.iters[l] : 0;
+        if (l < nl && h.done[l] == 2) out->degenerate |= 1 << l;
+    }
+    out->success = (h.done[0] != 2 && inl >= (double)HV_TRACK_MIN_INLIERS) ? 1 : 0;
+    out->level0_started = !(h.done[0] == 2 && h.iters[0] <= 1);
+    out->photometric_inliers = 0;
+    out->intensity_rmse = 0.0;
+    if constexpr (HYBRID) {
+        const double pin = h.last[30], pe = h.last[31];
+        out->photometric_inliers = (int64_t)pin;
+        out->intensity_rmse = pin > 0.0 ? std::sqrt(pe / pin) : 0.0;
+    }
+    return HV_OK;
+}
+
+// hv_tsdf_track / hv_tsdf_track_color: the map as the model, T_cw = inverse(A) T_cw_init
+template <bool HYBRID>
+int tk_track(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height, int32_t width,
+             const double *intr, const double *T_cw_init, const hv_track_params *prm, const hv_track_color_params *cprm,
+             hv_track_result *res, hv_track_color_result *cres, double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc) {
+    HV_REQUIRE(v != nullptr && depth != nullptr && intr != nullptr && T_cw_init != nullptr && prm != nullptr && res != nullptr &&
+                   (!HYBRID || color != nullptr),
+               HV_ERR_INVALID, "%s: null argument", fn);
+    TkMapModel model{v, fn, depth, depth_dtype, HYBRID ? color : nullptr, T_cw_init, prm->depth_min, prm->depth_max, prm->weight_threshold,
+                     prm->depth_outlier_trunc};
+    const TkSchedule S{prm->depth_scale, prm->depth_min, prm->depth_max, prm->depth_outlier_trunc, prm->depth_huber_delta,
+                       HYBRID ? cprm->intensity_weight : 0.0, HYBRID ? cprm->intensity_huber_delta : 0.0, prm->n_levels, prm->iterations};
+    TkOutcome o{};
+    const int rc = tk_run<HYBRID>(fn, v, model, S, depth_dtype, height, width, intr, &o, trace, trace_cap, trace_rows, loc);
+    if (rc != HV_OK) return rc;
     // T_cw = inverse(A) T_cw_init, A rigid: inverse(A) = [R^T, -R^T t]
     double Ai[16] = {};
     for (int r = 0; r < 3; ++r) {
-        for (int c = 0; c < 3; ++c) Ai[r * 4 + c] = h.A[c * 4 + r];
-        Ai[r * 4 + 3] = -(h.A[r] * h.A[3] + h.A[4 + r] * h.A[7] + h.A[8 + r] * h.A[11]);
+        for (int c = 0; c < 3; ++c) Ai[r * 4 + c] = o.A[c * 4 + r];
+        Ai[r * 4 + 3] = -(o.A[r] * o.A[3] + o.A[4 + r] * o.A[7] + o.A[8 + r] * o.A[11]);
     }
     Ai[15] = 1.0;
     for (int r = 0; r < 4; ++r)
         for (int c = 0; c < 4; ++c)
             res->T_cw[r * 4 + c] = Ai[r * 4] * T_cw_init[c] + Ai[r * 4 + 1] * T_cw_init[4 + c] + Ai[r * 4 + 2] * T_cw_init[8 + c] +
                                    Ai[r * 4 + 3] * T_cw_init[12 + c];
-    {
-        int q = 0;
-        for (int a = 0; a < 6; ++a)
-            for (int b = a; b < 6; ++b) {
-                res->information[a * 6 + b] = res->information[b * 6 + a] = h.last[q++];
-            }
-    }
-    const double e = h.last[27], inl = h.last[28], val = h.last[29];
-    res->inliers = (int64_t)inl;
-    res->valid = (int64_t)val;
-    res->fitness = val > 0.0 ? inl / val : 0.0;
-    res->inlier_rmse = inl > 0.0 ? std::sqrt(e / inl) : 0.0;
-    res->degenerate = 0;
-    for (int l = 0; l < HV_TRACK_MAX_LEVELS; ++l) {
-        res->iterations[l] = l < nl ? h.iters[l] : 0;
-        if (l < nl && h.done[l] == 2) res->degenerate |= 1 << l;
-    }
-    res->success = (h.done[0] != 2 && inl >= (double)HV_TRACK_MIN_INLIERS) ? 1 : 0;
+    tk_copy_result(o, res);
     if constexpr (HYBRID) {
-        const double pin = h.last[30], pe = h.last[31];
-        cres->photometric_inliers = (int64_t)pin;
-        cres->intensity_rmse = pin > 0.0 ? std::sqrt(pe / pin) : 0.0;
+        cres->photometric_inliers = o.photometric_inliers;
+        cres->intensity_rmse = o.intensity_rmse;
     }
     return HV_OK;
+}
+
+// the provider of the two odometry entry points (T_init null: the identity)
+TkFrameModel od_frame_model(const char *fn, hv_volume *v, const void *source_depth, const void *target_depth, int32_t depth_dtype,
+                            const uint8_t *source_color, const uint8_t *target_color, const double *T_init, const hv_odometry_params *prm) {
+    TkFrameModel model{v, fn, source_depth, target_depth, depth_dtype, source_color, target_color, {}, prm->depth_scale, prm->depth_min,
+                       prm->depth_max, prm->depth_outlier_trunc};
+    for (int i = 0; i < 16; ++i) model.T0[i] = T_init != nullptr ? T_init[i] : ((i % 5 == 0) ? 1.0 : 0.0);
+    return model;
 }
 
 } // namespace
@@ -475,14 +752,110 @@ int tk_run(const char *fn, hv_volume *v, const void *depth, int32_t depth_dtype,
 extern "C" int hv_tsdf_track(hv_volume *v, const void *depth, int32_t depth_dtype, int32_t height, int32_t width, const double *intr,
                              const double *T_cw_init, const hv_track_params *prm, hv_track_result *res, double *trace, int64_t trace_cap,
                              int64_t *trace_rows, int32_t loc) {
-    return tk_run<false>("hv_tsdf_track", v, depth, depth_dtype, nullptr, height, width, intr, T_cw_init, prm, nullptr, res, nullptr, trace,
-                         trace_cap, trace_rows, loc);
+    return tk_track<false>("hv_tsdf_track", v, depth, depth_dtype, nullptr, height, width, intr, T_cw_init, prm, nullptr, res, nullptr, trace,
+                           trace_cap, trace_rows, loc);
 }
 
 extern "C" int hv_tsdf_track_color(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height,
                                    int32_t width, const double *intr, const double *T_cw_init, const hv_track_color_params *prm,
                                    hv_track_color_result *res, double *trace, int64_t trace_cap, int64_t *trace_rows, int32_t loc) {
     HV_REQUIRE(prm != nullptr && res != nullptr, HV_ERR_INVALID, "hv_tsdf_track_color: null argument");
-    return tk_run<true>("hv_tsdf_track_color", v, depth, depth_dtype, color, height, width, intr, T_cw_init, &prm->base, prm, &res->base,
-                        res, trace, trace_cap, trace_rows, loc);
+    return tk_track<true>("hv_tsdf_track_color", v, depth, depth_dtype, color, height, width, intr, T_cw_init, &prm->base, prm, &res->base,
+                          res, trace, trace_cap, trace_rows, loc);
 }
+
+extern "C" int hv_rgbd_odometry(hv_volume *v, const void *source_depth, const void *target_depth, int32_t depth_dtype,
+                                const uint8_t *source_color, const uint8_t *target_color, int32_t height, int32_t width, const double *intr,
+                                const double *T_init, const hv_odometry_params *prm, hv_odometry_result *res, double *trace,
+                                int64_t trace_cap, int64_t *trace_rows, int32_t loc) {
+    const char *fn = "hv_rgbd_odometry";
+    HV_REQUIRE(v != nullptr && source_depth != nullptr && target_depth != nullptr && intr != nullptr && prm != nullptr && res != nullptr,
+               HV_ERR_INVALID, "%s: null argument", fn);
+    HV_REQUIRE((source_color == nullptr) == (target_color == nullptr), HV_ERR_INVALID,
+               "%s: give both colour images (hybrid) or neither (depth only)", fn);
+    const bool hybrid = source_color != nullptr;
+    TkFrameModel model = od_frame_model(fn, v, source_depth, target_depth, depth_dtype, source_color, target_color, T_init, prm);
+    const TkSchedule S{prm->depth_scale, prm->depth_min, prm->depth_max, prm->depth_outlier_trunc, prm->depth_huber_delta,
+                       prm->intensity_weight, prm->intensity_huber_delta, prm->n_levels, prm->iterations};
+    TkOutcome o{};
+    const int rc = hybrid ? tk_run<true>(fn, v, model, S, depth_dtype, height, width, intr, &o, trace, trace_cap, trace_rows, loc)
+                          : tk_run<false>(fn, v, model, S, depth_dtype, height, width, intr, &o, trace, trace_cap, trace_rows, loc);
+    if (rc != HV_OK) return rc;
+    // transformation = A itself; T_init when level 0 never got going (A then holds the steps of coarser levels at most)
+    for (int i = 0; i < 16; ++i) res->transformation[i] = o.level0_started ? o.A[i] : model.T0[i];
+    tk_copy_result(o, res);
+    res->photometric_inliers = o.photometric_inliers;
+    res->intensity_rmse = o.intensity_rmse;
+    return HV_OK;
+}
+
+extern "C" int hv_rgbd_odometry_model(hv_volume *v, const void *depth, int32_t depth_dtype, const uint8_t *color, int32_t height,
+                                      int32_t width, const double *intr, const hv_odometry_params *prm, int32_t level, float *out_depth,
+                                      float *out_normal, uint8_t *out_mask, float *out_record, int32_t loc) {
+    const char *fn = "hv_rgbd_odometry_model";
+    HV_REQUIRE(v != nullptr && depth != nullptr && intr != nullptr && prm != nullptr, HV_ERR_INVALID, "%s: null argument", fn);
+    HV_REQUIRE(depth_dtype == HV_DEPTH_F32 || depth_dtype == HV_DEPTH_U16, HV_ERR_INVALID, "%s: bad depth dtype %d", fn, (int)depth_dtype);
+    HV_REQUIRE(loc == HV_HOST || loc == HV_DEVICE, HV_ERR_INVALID, "%s: bad loc %d", fn, (int)loc);
+    HV_REQUIRE(level >= 0 && level < HV_TRACK_MAX_LEVELS, HV_ERR_INVALID, "%s: level must be in 0..%d", fn, HV_TRACK_MAX_LEVELS - 1);
+    HV_REQUIRE(out_record == nullptr || color != nullptr, HV_ERR_INVALID, "%s: the record needs a colour image", fn);
+    // the schedule's checks at n_levels = level + 1, one linearisation at level 0 (nothing is linearised here)
+    const int32_t one[HV_TRACK_MAX_LEVELS] = {1, 0, 0, 0, 0, 0, 0, 0};
+    const int nl = level + 1;
+    const TkSchedule S{prm->depth_scale, prm->depth_min, prm->depth_max, prm->depth_outlier_trunc, 1.0, 0.0, 1.0, nl, one};
+    int64_t steps = 0;
+    int rc = tk_check_schedule(fn, S, false, height, width, intr, &steps);
+    if (rc != HV_OK) return rc;
+    const bool hybrid = color != nullptr;
+    TkFrameModel model = od_frame_model(fn, v, depth, depth, depth_dtype, color, color, nullptr, prm);
+    HV_HIP(hipSetDevice(v->device));
+
+    // scratch: per level the depth (hybrid: and intensity) of the pyramid; for `level` also normal, mask and, hybrid, the record
+    size_t off = 0;
+    auto take = [&off](size_t bytes) {
+        const size_t at = off;
+        off += (bytes + 255) & ~(size_t)255;
+        return at;
+    };
+    size_t o_d[HV_TRACK_MAX_LEVELS], o_i[HV_TRACK_MAX_LEVELS] = {};
+    for (int l = 0; l < nl; ++l) {
+        const size_t n = (size_t)(height >> l) * (size_t)(width >> l);
+        o_d[l] = take(4 * n);
+        if (hybrid) o_i[l] = take(4 * n);
+    }
+    const size_t n = (size_t)(height >> level) * (size_t)(width >> level);
+    const size_t o_n = take(12 * n), o_m = take(n), o_r = hybrid ? take(16 * n) : 0;
+    rc = hv_ensure_buffer(v, &v->track_buf, &v->track_buf_bytes, off);
+    if (rc != HV_OK) return rc;
+    char *base = (char *)v->track_buf;
+    TkModelMaps maps[HV_TRACK_MAX_LEVELS];
+    for (int l = 0; l < nl; ++l) {
+        const double s = (double)(1 << l);
+        maps[l] = TkModelMaps{(float *)(base + o_d[l]), nullptr, nullptr, hybrid ? (float *)(base + o_i[l]) : (float *)nullptr, nullptr,
+                              height >> l, width >> l, {intr[0] / s, intr[1] / s, (intr[2] + 0.5) / s - 0.5, (intr[3] + 0.5) / s - 0.5}};
+    }
+    maps[level].normal = (float *)(base + o_n);
+    maps[level].mask = (uint8_t *)(base + o_m);
+    maps[level].rec = hybrid ? (float4 *)(base + o_r) : (float4 *)nullptr;
+
+    // the one frame is the provider's target: staged once (its source slots are the same pointers)
+    const void *d_depth = nullptr;
+    const uint8_t *d_color = nullptr;
+    rc = hv_stage_frame(v, depth, depth_dtype, color, (size_t)height * (size_t)width, loc, &d_depth, &d_color);
+    if (rc != HV_OK) return rc;
+    model.d_target_depth = d_depth;
+    model.d_target_color = d_color;
+    v->pipe_armed = false;
+    rc = hybrid ? model.prepare<true>(maps, nl) : model.prepare<false>(maps, nl);
+    if (rc != HV_OK) return rc;
+    rc = hybrid ? model.level<true>(maps[level]) : model.level<false>(maps[level]);
+    if (rc != HV_OK) return rc;
+    HV_HIP(hipGetLastError());
+    const hipMemcpyKind kind = loc == HV_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (out_depth) HV_HIP(hipMemcpyAsync(out_depth, maps[level].depth, 4 * n, kind, v->stream));
+    if (out_normal) HV_HIP(hipMemcpyAsync(out_normal, maps[level].normal, 12 * n, kind, v->stream));
+    if (out_mask) HV_HIP(hipMemcpyAsync(out_mask, maps[level].mask, n, kind, v->stream));
+    if (out_record) HV_HIP(hipMemcpyAsync(out_record, maps[level].rec, 16 * n, kind, v->stream));
+    HV_HIP(hipStreamSynchronize(v->stream));
+    return HV_OK;
+}
+

@@ -171,8 +171,9 @@ def _tsdf_operands(depth, color, intrinsic, frames=None, depth_only=False):
 
 
 class OdometryResult:
-    """What ScalableTSDFVolume.track_frame_to_model returns (the fields of Open3D's tensor odometry result, plus the rest of
-    hv_track_result):  transformation 4x4 float64 T_cw; fitness = inliers / valid source pixels and inlier_rmse (metres) of the
+    """What ScalableTSDFVolume.track_frame_to_model and rgbd_odometry return (the fields of Open3D's tensor odometry result, plus the
+    rest of hv_track_result / hv_odometry_result):  transformation 4x4 float64, T_cw after tracking, T_target_source after
+    rgbd_odometry; fitness = inliers / valid source pixels and inlier_rmse (metres) of the
     last full-resolution linearisation; information 6x6 float64 (its Gauss-Newton matrix H, anchor frame, order (omega, t));
     success; iterations run per pyramid level (level 0 first); degenerate = bit l set when level l ended on a degenerate step;
     inliers / valid counts; trace = None, or one dict per linearisation (level, iteration, status, inliers, valid, sq_error,
@@ -1123,6 +1124,98 @@ class _Volume:
         if stats:
             return out["depth"], out["counts"], _stats(ConsistencyStats, st)
         return out["depth"], out["counts"]
+
+    @staticmethod
+    def _odometry_params(depth_scale, depth_min, depth_max, iterations, depth_outlier_trunc, depth_huber_delta, intensity_weight=0.0,
+                         intensity_huber_delta=1.0):
+        """-> (hv_odometry_params, the iteration counts as ints)"""
+        iters = [int(i) for i in iterations]
+        prm = L.HvOdometryParams()
+        prm.depth_scale, prm.depth_min, prm.depth_max = float(depth_scale), float(depth_min), float(depth_max)
+        prm.depth_outlier_trunc, prm.depth_huber_delta = float(depth_outlier_trunc), float(depth_huber_delta)
+        prm.intensity_weight, prm.intensity_huber_delta = float(intensity_weight), float(intensity_huber_delta)
+        prm.n_levels = len(iters)
+        for i, n in enumerate(iters[:L.HV_TRACK_MAX_LEVELS]):
+            prm.iterations[i] = n
+        return prm, iters
+
+    def rgbd_odometry(self, source_depth, target_depth, intrinsic, init=None, source_color=None, target_color=None, depth_scale=1.0,
+                      depth_min=0.1, depth_max=3.0, iterations=(10, 5, 4), depth_outlier_trunc=0.07, depth_huber_delta=0.05,
+                      intensity_weight=0.01, intensity_huber_delta=0.1, trace=False):
+        """How the camera moved between two RGB-D frames (hv_rgbd_odometry; the place of Open3D's rgbd_odometry_multi_scale): ->
+        OdometryResult whose transformation is T_target_source - it maps a point in source-camera coordinates into target-camera
+        coordinates; with world poses T_cw(target) @ inv(T_cw(source)).  The volume is context only (its stream and scratch, any
+        mode): the map is neither read nor changed.  It is track_frame_to_model's alignment with the model built from the target
+        frame instead of the map; parameters and result fields mean what they mean there.
+        source_depth, target_depth [H,W]: numpy or torch (either device), uint16 or any real dtype (as float32), divided by
+        depth_scale; H, W = intrinsic.height, intrinsic.width.  Both frames must share place, dtype and shape.  init: the 4x4 start
+        of T_target_source (None: identity).  source_color and target_color [H,W,3] uint8, both or neither: hybrid (point-to-plane
+        plus a photometric term weighted by intensity_weight; 0 is the depth-only result bit for bit) or depth only.  When the
+        frames cannot be aligned (empty, or geometry that leaves a motion free and no colour) success is False and transformation
+        is init.  CUDA tensors are read after the work queued on torch's current stream.  trace=True: the per-linearisation record."""
+        who = "rgbd_odometry"
+        if (source_color is None) != (target_color is None):
+            raise ValueError(f"{who}: give both source_color and target_color (hybrid) or neither (depth only)")
+        hybrid = source_color is not None
+        shapes = [tuple(int(s) for s in np.shape(a)) for a in (source_depth, target_depth)]
+        if shapes[0] != shapes[1]:
+            raise ValueError(f"{who}: source_depth is {shapes[0]}, target_depth is {shapes[1]}: the two frames must have the same shape")
+        sd, sc, skind, _ = _tsdf_operands(source_depth, source_color, intrinsic, depth_only=not hybrid)
+        td, tc, tkind, _ = _tsdf_operands(target_depth, target_color, intrinsic, depth_only=not hybrid)
+        if skind != tkind:
+            raise ValueError(f"{who}: source_depth is {sd.dtype}, target_depth is {td.dtype}: the two frames must have the same dtype")
+        places = [str(a.device) if L.location(a) == L.HV_DEVICE else "the host" for a in (sd, td)]
+        if places[0] != places[1]:
+            raise ValueError(f"{who}: source_depth lives on {places[0]}, target_depth on {places[1]}: the two frames must live in the same place")
+        T0 = None
+        if init is not None:
+            T0 = _as_f64_4x4(init)
+            if not np.isfinite(T0).all() or not np.array_equal(T0[3], (0.0, 0.0, 0.0, 1.0)):
+                raise ValueError(f"{who}: init must be a finite rigid 4x4 with bottom row 0 0 0 1")
+        H, W = int(sd.shape[0]), int(sd.shape[1])
+        prm, iters = self._odometry_params(depth_scale, depth_min, depth_max, iterations, depth_outlier_trunc, depth_huber_delta,
+                                           intensity_weight, intensity_huber_delta)
+        res = L.HvOdometryResult()
+        intr = intrinsic.as_array()
+        steps = max(sum(iters), 1)
+        rows = np.zeros((steps, L.HV_TRACK_COLOR_TRACE_STRIDE if hybrid else L.HV_TRACK_TRACE_STRIDE), np.float64) if trace else None
+        n_rows = ctypes.c_int64()
+        with self._ordered(sd, td, sc, tc):
+            L.check(self._lib.hv_rgbd_odometry(self._h, L.ptr(sd), L.ptr(td), skind, L.ptr(sc), L.ptr(tc), H, W, L.ptr(intr), L.ptr(T0),
+                                               ctypes.byref(prm), ctypes.byref(res), L.ptr(rows), steps if trace else 0, ctypes.byref(n_rows),
+                                               L.location(sd)))
+        n_levels = min(len(iters), L.HV_TRACK_MAX_LEVELS)
+        return OdometryResult(np.array(res.transformation, np.float64).reshape(4, 4), float(res.fitness), float(res.inlier_rmse),
+                              np.array(res.information, np.float64).reshape(6, 6), bool(res.success),
+                              tuple(int(res.iterations[i]) for i in range(n_levels)), int(res.degenerate), int(res.inliers),
+                              int(res.valid), _trace_rows(rows[:n_rows.value]) if trace else None,
+                              int(res.photometric_inliers) if hybrid else None, float(res.intensity_rmse) if hybrid else None)
+
+    def rgbd_odometry_model(self, depth, intrinsic, color=None, level=0, depth_scale=1.0, depth_min=0.1, depth_max=3.0,
+                            depth_outlier_trunc=0.07, device=False):
+        """The model rgbd_odometry builds from its target frame at pyramid `level` (hv_rgbd_odometry_model): a dict with depth [h,w]
+        float32 (metres, 0 = invalid), normal [h,w,3] float32 (camera frame, facing the camera, 0 where the mask is not set), mask
+        [h,w] bool and record [h,w,4] float32 {intensity, g_x, g_y, has-gradient} (None without color); h, w = H >> level, W >> level.
+        depth and color as rgbd_odometry takes a frame.  device=False: numpy arrays; True: torch CUDA tensors on the volume's GPU,
+        ordered before later work on torch's current stream; the operands are moved to that side first."""
+        d, c, dkind, _ = _tsdf_operands(depth, color, intrinsic, depth_only=color is None)
+        H, W = int(d.shape[0]), int(d.shape[1])
+        level = int(level)
+        if not 0 <= level < L.HV_TRACK_MAX_LEVELS or min(H >> level, W >> level) < 1:
+            raise ValueError(f"rgbd_odometry_model: a {H}x{W} frame has no pyramid level {level}")
+        d, dev = self._query_place(d, bool(device))
+        if c is not None:
+            c, _ = self._query_place(c, bool(device))
+        prm, _ = self._odometry_params(depth_scale, depth_min, depth_max, (1,), depth_outlier_trunc, 1.0)
+        h, w = H >> level, W >> level
+        out = self._results({"depth": ((h, w), np.float32), "normal": ((h, w, 3), np.float32), "mask": ((h, w), np.bool_),
+                             "record": None if c is None else ((h, w, 4), np.float32)}, bool(device), pinned=False)
+        intr = intrinsic.as_array()
+        with self._ordered(d, c):
+            L.check(self._lib.hv_rgbd_odometry_model(self._h, L.ptr(d), dkind, L.ptr(c), H, W, L.ptr(intr), ctypes.byref(prm), level,
+                                                     L.ptr(out["depth"]), L.ptr(out["normal"]), L.ptr(out["mask"]), L.ptr(out["record"]),
+                                                     L.HV_DEVICE if device else L.HV_HOST))
+        return out
 
     def remap(self, img, map_x, map_y, linear=False):
         """cv2.remap(img, map_x, map_y, INTER_LINEAR if linear else INTER_NEAREST) on the GPU; the maps are [H, W] like the image.
