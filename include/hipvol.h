@@ -909,7 +909,112 @@ int hv_rgbd_odometry_model(hv_volume *v, const void *depth, int32_t depth_dtype,
                            const double *intr, const hv_odometry_params *params, int32_t level, float *out_depth, float *out_normal,
                            uint8_t *out_mask, float *out_record, int32_t loc);
 
-/* Pruning: give units back to the pool.  Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
+/* Pose-graph optimisation (the place of Open3D's pipelines::registration::GlobalOptimization with the Levenberg-Marquardt method and
+ * its line process): given node poses, relative poses between pairs of them with their information matrices, and which of those are
+ * trusted (odometry) and which are not (loop closures), the node poses that fit them best, with the weight of every untrusted edge.
+ * This project's own contract.  The volume is context only, as for hv_rgbd_odometry (stream, scratch, staging; any mode): nothing of
+ * the map is read or changed.
+ *   operands  all at loc (HV_HOST arrays are staged by the library and the results copied back before the call returns).
+ *             poses [N,16] float64 row-major T_wc (camera-to-world), in and out; edge_nodes [E,2] int32 {source, target}; edge_T
+ *             [E,16] float64 Z = T_target_source - exactly hv_rgbd_odometry's transformation for that pair and
+ *             hv_tsdf_register_volume's T_self_source; edge_info [E,36] float64, the 6 x 6 information in the order (omega, t) that
+ *             xi has everywhere in this project; edge_uncertain [E] uint8 (non-zero = uncertain) or NULL = all certain;
+ *             params->fixed: the node that does not move.  Rotation blocks are taken as orthonormal: every inverse is [R^T, -R^T t].
+ *             Duplicate edges and edges with source > target are legal.
+ *   exp, Log  exp(xi) = [Rodrigues(omega), t], hv_gauss_newton.h's: R = I + a K + b K K, K = [omega]x, th = |omega|, a = sin th / th,
+ *             b = (1 - cos th) / th^2 (a = 1, b = 1/2 for th < 1e-8); the translation part is t itself.  Log(T) = (Log R, t) inverts it:
+ *             v = (R21 - R12, R02 - R20, R10 - R01) / 2, s = |v|, c = (trace R - 1) / 2, th = atan2(s, c);
+ *               c >= -0.99, s >= 1e-8   omega = v th / s
+ *               c >= -0.99, s <  1e-8   omega = v                               (small angle)
+ *               c <  -0.99              near pi, where v vanishes: A = ((R + R^T) / 2 - c I) / (1 - c) = a a^T for the axis a; k = the
+ *                                       first largest diagonal entry of A, a = A[k, :] / sqrt(A[k, k]), normalised, negated when
+ *                                       a . v < 0; omega = th a.
+ *   residual  per edge X = inv(T_t) T_s inv(Z), r = Log(X) = (omega, t).  edge_info is used as the odometry returns it: its
+ *             information is about a left perturbation exp(xi) T_target_source, and Log(P inv(Z)) is that xi.
+ *   update    T_i := exp(d_i) T_i.  With it J_t = -J_s and J_s = Jl^-1(r) Ad(inv(T_t)), where for inv(T_t) = [Ra, ta]
+ *               Ad = [[Ra, 0], [[ta]x Ra, Ra]]                              ((omega, t) order; first order of A exp(d) inv(A))
+ *               Jl^-1(r) = [[Jw(omega), 0], [-[t]x, I]]                     (closed form: the left Jacobian of THIS exp, rotation and
+ *                                                                            translation uncoupled except through exp(d) acting on t)
+ *               Jw = I - K / 2 + c2 K K, c2 = 1 / th^2 - cos(th / 2) / (2 th sin(th / 2)), finite up to th = pi; for th < 0.05 its
+ *                    series 1/12 + th^2 / 720 + th^4 / 30240 (the closed form cancels there; the series' next term is below 2e-17)
+ *             so J_s = [[Jw Ra, 0], [[ta - t]x Ra, Ra]].
+ *   edge      M_e = l_e J_s^T Omega_e J_s goes to the blocks (s,s) and (t,t) and -M_e to (s,t) and (t,s); g_e = l_e J_s^T Omega_e r
+ *             goes to s and -g_e to t.  The optimiser keeps M_e (its upper triangle) and g_e per edge and nothing else.
+ *   objective F = sum_e l_e chi2_e + sum_uncertain mu (sqrt(l_e) - 1)^2, chi2_e = r^T Omega_e r; l_e = 1 for a certain edge, l_e =
+ *             (mu / (mu + chi2_e))^2 for an uncertain one, recomputed from the state at EVERY evaluation (linearisation and trial).
+ *             mu = line_process_weight, default 1.  An uncertain edge is switched off (l < 1/4) when chi2_e > mu, so mu is the chi2
+ *             of the worst loop edge the caller still wants to keep: about (the largest acceptable residual)^2 times the typical
+ *             diagonal of the loop edges' information (Open3D derives it from preference_loop_closure and the mean information; this
+ *             call takes the number).  edge_weight_out [E] at loc (may be NULL): the final l_e; kept = l_e >= edge_prune_threshold
+ *             (default 0.25); the call marks edges and never removes one.
+ *   outer     Levenberg-Marquardt on (H + lambda I) d = -b, b = the sum of +-g_e, lambda_0 = lambda_scale max diag H (default 1e-5,
+ *             Open3D's tau) over the free nodes.  Gain ratio rho = (F - F_trial) / (d . (lambda d - b)), which is the model's decrease
+ *             for every CG iterate started at 0; rho is 0 when the denominator is not positive or F_trial is not a number.  Accepted
+ *             iff rho > 0: lambda *= max(1/3, 1 - (2 rho - 1)^3), nu = 2; else lambda *= nu, nu *= 2 (Nielsen).  An iteration stops
+ *             the call, rules tested in this order: F <= residual_tolerance (HV_POSE_GRAPH_RESIDUAL, no step taken); max |b| <=
+ *             gradient_tolerance (HV_POSE_GRAPH_GRADIENT, no step taken); |d|_2 <= step_tolerance (HV_POSE_GRAPH_STEP, the step taken
+ *             if accepted); accepted and F - F_trial <= decrease_tolerance F (HV_POSE_GRAPH_DECREASE); max_iterations reached
+ *             (converged = 0).  Defaults 1e-6 each and 100 iterations, Open3D's GlobalOptimizationConvergenceCriteria.
+ *   inner     block-Jacobi preconditioned conjugate gradients from x = 0 over the free nodes (the fixed node's rows and columns are
+ *             dropped); the preconditioner is the Cholesky factor of each node's 6 x 6 block D_i + lambda I.  It ends when
+ *             sqrt(r.z / r0.z0) <= cg_tolerance (default 1e-8) or after cg_max_iterations (default 100): a truncated solve is still a
+ *             descent step with the rho above.  The matrix is never formed: a product is one pass over the edges, u_e = M_e (x_s -
+ *             x_t), and one over the nodes, which add +u_e / -u_e in the order of their incidence list (a CSR built once per call on
+ *             the host, sorted by edge index).  Dot products, F and the norms are two-stage sums in a fixed order; no float atomics;
+ *             bitwise reproducible run to run.  alpha, beta and the "done" flag live on the device: a finished CG turns the rest of
+ *             its queued launches into no-ops, and there is no host wait inside the CG loop.  An outer iteration queues 7 + 4
+ *             cg_max_iterations launches and costs ONE host wait (the read of its decision).  The call adds one wait for its start,
+ *             one for its results and, with loc = HV_DEVICE, one to fetch the operands for the checks below.
+ *   result    chi2_initial / chi2_final: F at the first linearisation / at the final state; lambda: the last; iterations: outer
+ *             iterations run; cg_iterations_total; edges_kept: edges with l_e >= edge_prune_threshold (certain ones included);
+ *             converged: the rule that stopped the call (HV_POSE_GRAPH_*, 0 = max_iterations); success = converged != 0, every
+ *             block factorisation had positive pivots and chi2_final is finite.
+ *   trace     (host memory for either loc, may be NULL) one row of HV_POSE_GRAPH_TRACE_STRIDE doubles per outer iteration, at most
+ *             trace_cap: {iteration, lambda, F before, F of the trial, rho, accepted, CG iterations, CG residual sqrt(r.z / r0.z0),
+ *             |d|_2, max |b|, the new lambda, the rule that fired or 0}.  With params->trace_state, trace_poses [trace_cap, N, 16]
+ *             (host) receives the poses each iteration STARTED from, so that a restatement can be fed the same state.
+ *   errors    HV_ERR_INVALID, all checked on the host before any launch, poses untouched: N < 1; fixed outside 0..N-1; a node index
+ *             outside 0..N-1; a self edge; a pose or Z that is not finite or whose bottom row is not 0 0 0 1; an information matrix
+ *             that is not finite or not symmetric BITWISE (Omega[a][b] == Omega[b][a]); a node that is not connected to `fixed`
+ *             through CERTAIN edges (union-find on the host; the message says so) - the line process could cut it loose; parameters
+ *             out of range.  E == 0 with N == 1 is a no-op with success = 1.
+ * hv_pose_graph_linearise: what one linearisation of the call computes at the given poses, for tests: per edge r [E,6], chi2 [E],
+ * l [E], M_e [E,36] (full, symmetric), g_e [E,6] and the gradient b [N,6] (no node fixed), outputs in HOST memory for either loc, any
+ * may be NULL; the same kernels, the same checks except connectivity. */
+#define HV_POSE_GRAPH_TRACE_STRIDE 12
+#define HV_POSE_GRAPH_GRADIENT 1
+#define HV_POSE_GRAPH_STEP 2
+#define HV_POSE_GRAPH_DECREASE 3
+#define HV_POSE_GRAPH_RESIDUAL 4
+typedef struct hv_pose_graph_params {
+    double line_process_weight;  /* mu > 0, default 1 */
+    double edge_prune_threshold; /* default 0.25 */
+    double lambda_scale;         /* default 1e-5 */
+    double gradient_tolerance;   /* max |b|, default 1e-6 (Open3D min_right_term) */
+    double step_tolerance;       /* |d|_2, default 1e-6 (Open3D min_relative_increment, here absolute) */
+    double decrease_tolerance;   /* (F - F_trial) / F, default 1e-6 (Open3D min_relative_residual_increment) */
+    double residual_tolerance;   /* F, default 1e-6 (Open3D min_residual) */
+    double cg_tolerance;         /* default 1e-8 */
+    int32_t max_iterations;      /* default 100 (Open3D max_iteration) */
+    int32_t cg_max_iterations;   /* default 100 */
+    int32_t fixed;               /* default 0 */
+    int32_t trace_state;
+} hv_pose_graph_params;
+typedef struct hv_pose_graph_result {
+    double chi2_initial, chi2_final, lambda;
+    int32_t iterations, cg_iterations_total, edges_kept, converged, success;
+} hv_pose_graph_result;
+void hv_pose_graph_default_params(hv_pose_graph_params *params);
+int hv_pose_graph_optimize(hv_volume *v, double *poses, int64_t n_nodes, const int32_t *edge_nodes, const double *edge_T,
+                           const double *edge_info, const uint8_t *edge_uncertain, int64_t n_edges, const hv_pose_graph_params *params,
+                           double *edge_weight_out, hv_pose_graph_result *result, double *trace, double *trace_poses, int64_t trace_cap,
+                           int64_t *trace_rows, int32_t loc);
+int hv_pose_graph_linearise(hv_volume *v, const double *poses, int64_t n_nodes, const int32_t *edge_nodes, const double *edge_T,
+                            const double *edge_info, const uint8_t *edge_uncertain, int64_t n_edges, double line_process_weight,
+                            double *r_out, double *chi2_out, double *l_out, double *M_out, double *g_out, double *gradient_out,
+                            int32_t loc);
+
+/* Pruning: give units back to the pool. Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
  * sampled depth point, whether or not a voxel of it is then updated, and de-integration leaves the units it emptied allocated - so
  * a long session holds units that carry nothing, and units far from where the camera now is.  This project's own contract (Open3D's
  * ScalableTSDFVolume never frees a unit):

@@ -82,6 +82,40 @@ class HvTrackColorResult(_c.Structure):
     _fields_ = [("base", HvTrackResult), ("photometric_inliers", _i64), ("intensity_rmse", _f64)]
 
 
+HV_POSE_GRAPH_TRACE_STRIDE = 12
+HV_POSE_GRAPH_RULES = {0: "max_iterations", 1: "gradient", 2: "step", 3: "decrease", 4: "residual"}
+
+
+class HvPoseGraphParams(_c.Structure):
+    _fields_ = [
+        ("line_process_weight", _f64),
+        ("edge_prune_threshold", _f64),
+        ("lambda_scale", _f64),
+        ("gradient_tolerance", _f64),
+        ("step_tolerance", _f64),
+        ("decrease_tolerance", _f64),
+        ("residual_tolerance", _f64),
+        ("cg_tolerance", _f64),
+        ("max_iterations", _i32),
+        ("cg_max_iterations", _i32),
+        ("fixed", _i32),
+        ("trace_state", _i32),
+    ]
+
+
+class HvPoseGraphResult(_c.Structure):
+    _fields_ = [
+        ("chi2_initial", _f64),
+        ("chi2_final", _f64),
+        ("lambda_", _f64),
+        ("iterations", _i32),
+        ("cg_iterations_total", _i32),
+        ("edges_kept", _i32),
+        ("converged", _i32),
+        ("success", _i32),
+    ]
+
+
 class HvOdometryParams(_c.Structure):
     _fields_ = [
         ("depth_scale", _f64),
@@ -399,6 +433,10 @@ SIGNATURES = {
     "hv_tsdf_track_color": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_rgbd_odometry": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _pi64, _i32]),
     "hv_rgbd_odometry_model": (_i32, [_vp, _vp, _i32, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _i32]),
+    "hv_pose_graph_default_params": (None, [_c.POINTER(HvPoseGraphParams)]),
+    "hv_pose_graph_optimize": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _c.POINTER(HvPoseGraphParams), _vp, _c.POINTER(HvPoseGraphResult),
+                                      _vp, _vp, _i64, _pi64, _i32]),
+    "hv_pose_graph_linearise": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
     "hv_lookup_points": (_i32, [_vp, _vp, _i32, _i64, _c.POINTER(HvLookupParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(HvLookupStats), _i32]),

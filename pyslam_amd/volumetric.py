@@ -170,6 +170,27 @@ def _tsdf_operands(depth, color, intrinsic, frames=None, depth_only=False):
     return d, c, dkind, converted
 
 
+class PoseGraphResult:
+    """What optimize_pose_graph returns (hv_pose_graph_result and the call's arrays): poses [N,4,4] float64 T_wc after the
+    optimisation; line_process [E] float64, the final weight l_e of every edge (1 for a certain one); kept [E] bool = l_e >=
+    edge_prune_threshold; chi2_initial / chi2_final, the objective at the first linearisation and at the final state; lambda_, the
+    last damping; iterations (outer), cg_iterations_total, edges_kept; converged: the rule that stopped the call ("gradient",
+    "step", "decrease", "residual" or "max_iterations"); success; trace = None, or one dict per outer iteration (iteration, lambda_,
+    chi2, chi2_trial, gain_ratio, accepted, cg_iterations, cg_residual, step_norm, gradient_norm, lambda_new, converged, and poses
+    [N,4,4] - the state the iteration started from)."""
+    __slots__ = ("poses", "line_process", "kept", "chi2_initial", "chi2_final", "lambda_", "iterations", "cg_iterations_total", "edges_kept",
+                 "converged", "success", "trace")
+
+    def __init__(self, *values):
+        for name, value in zip(self.__slots__, values):
+            setattr(self, name, value)
+
+
+_POSE_GRAPH_TRACE = (("iteration", int), ("lambda_", float), ("chi2", float), ("chi2_trial", float), ("gain_ratio", float), ("accepted", bool),
+                     ("cg_iterations", int), ("cg_residual", float), ("step_norm", float), ("gradient_norm", float), ("lambda_new", float),
+                     ("converged", int))
+
+
 class OdometryResult:
     """What ScalableTSDFVolume.track_frame_to_model and rgbd_odometry return (the fields of Open3D's tensor odometry result, plus the
     rest of hv_track_result / hv_odometry_result):  transformation 4x4 float64, T_cw after tracking, T_target_source after
@@ -1215,6 +1236,110 @@ class _Volume:
             L.check(self._lib.hv_rgbd_odometry_model(self._h, L.ptr(d), dkind, L.ptr(c), H, W, L.ptr(intr), ctypes.byref(prm), level,
                                                      L.ptr(out["depth"]), L.ptr(out["normal"]), L.ptr(out["mask"]), L.ptr(out["record"]),
                                                      L.HV_DEVICE if device else L.HV_HOST))
+        return out
+
+    def _pose_graph_operands(self, who, poses, edges, transformations, informations, uncertain):
+        """The graph's arrays where the call reads them: all on the volume's GPU when `poses` is a CUDA tensor, else all on the host;
+        float64 / int32 / uint8, C-contiguous.  -> (poses [N,4,4], edges [E,2], Z [E,4,4], info [E,6,6], uncertain [E] or None, on_gpu, N, E)"""
+        on_gpu = L.location(poses) == L.HV_DEVICE
+        if on_gpu:
+            import torch
+
+            dev = self._device()
+            if poses.device != dev:
+                raise ValueError(f"{who}: poses live on {poses.device}, the volume on {dev}")
+
+            def place(a, dtype):
+                t = a if _is_torch(a) else torch.as_tensor(np.asarray(a))
+                return t.to(device=dev, dtype=getattr(torch, dtype)).contiguous()
+        else:
+            def place(a, dtype):
+                return np.ascontiguousarray(a.cpu().numpy() if _is_torch(a) else np.asarray(a), dtype=dtype)
+
+        P = place(poses, "float64")
+        if P.ndim != 3 or tuple(P.shape[1:]) != (4, 4) or P.shape[0] < 1:
+            raise ValueError(f"{who}: poses must be [N,4,4] with N >= 1, got {tuple(P.shape)}")
+        N = int(P.shape[0])
+        Ed = place(edges, "int32").reshape(-1, 2)
+        E = int(Ed.shape[0])
+        Z, Om = place(transformations, "float64"), place(informations, "float64")
+        if int(np.prod(Z.shape)) != 16 * E or (E > 0 and tuple(Z.shape[-2:]) != (4, 4)):
+            raise ValueError(f"{who}: transformations must be [{E},4,4] for {E} edges, got {tuple(Z.shape)}")
+        if int(np.prod(Om.shape)) != 36 * E or (E > 0 and tuple(Om.shape[-2:]) != (6, 6)):
+            raise ValueError(f"{who}: informations must be [{E},6,6] for {E} edges, got {tuple(Om.shape)}")
+        Z, Om = Z.reshape(E, 4, 4), Om.reshape(E, 6, 6)
+        U = None
+        if uncertain is not None:
+            U = place(uncertain, "bool")
+            U = U.to(torch.uint8) if on_gpu else U.astype(np.uint8)
+            if tuple(U.shape) != (E,):
+                raise ValueError(f"{who}: uncertain must be [{E}], got {tuple(U.shape)}")
+        return P, Ed, Z, Om, U, on_gpu, N, E
+
+    def optimize_pose_graph(self, poses, edges, transformations, informations, uncertain=None, fixed=0, line_process_weight=1.0,
+                            edge_prune_threshold=0.25, max_iterations=100, lambda_scale=1e-5, gradient_tolerance=1e-6, step_tolerance=1e-6,
+                            decrease_tolerance=1e-6, residual_tolerance=1e-6, cg_max_iterations=100, cg_tolerance=1e-8, trace=False):
+        """Pose-graph optimisation on the GPU (hv_pose_graph_optimize; the place of Open3D's global_optimization with
+        Levenberg-Marquardt and the line process): -> PoseGraphResult.  poses [N,4,4] T_wc (camera-to-world) of the nodes; edges
+        [E,2] {source, target}; transformations [E,4,4] T_target_source of each edge - what rgbd_odometry returns for (source,
+        target) and register_volume returns as T_self_source; informations [E,6,6], as those calls return them, order (omega, t);
+        uncertain [E] bool: loop closures, which the line process may switch off (None: all certain); fixed: the node that does
+        not move.  Every node must reach `fixed` through certain edges.  line_process_weight is the chi2 above which an uncertain
+        edge is switched off: about (the largest residual still accepted)^2 times the information's diagonal.  The operands are
+        not changed.  numpy or torch on either device: with `poses` a CUDA tensor on the volume's GPU everything is read there and
+        poses, line_process and kept come back as tensors ordered on torch's current stream; else numpy arrays.  The volume is
+        context only (its stream and scratch, any mode): the map is neither read nor changed.  trace=True: one dict per outer
+        iteration with the poses it started from."""
+        who = "optimize_pose_graph"
+        P, Ed, Z, Om, U, on_gpu, N, E = self._pose_graph_operands(who, poses, edges, transformations, informations, uncertain)
+        if int(fixed) != fixed or not 0 <= int(fixed) < N:
+            raise ValueError(f"{who}: fixed must be a node index in 0..{N - 1}, got {fixed}")
+        if not (np.isfinite(line_process_weight) and line_process_weight > 0):
+            raise ValueError(f"{who}: line_process_weight must be positive and finite, got {line_process_weight}")
+        if not 0.0 <= edge_prune_threshold <= 1.0:
+            raise ValueError(f"{who}: edge_prune_threshold must be in 0..1, got {edge_prune_threshold}")
+        if not (1 <= int(max_iterations) <= 10000 and 1 <= int(cg_max_iterations) <= 10000):
+            raise ValueError(f"{who}: max_iterations and cg_max_iterations must be in 1..10000")
+        prm = L.HvPoseGraphParams(float(line_process_weight), float(edge_prune_threshold), float(lambda_scale), float(gradient_tolerance),
+                                  float(step_tolerance), float(decrease_tolerance), float(residual_tolerance), float(cg_tolerance),
+                                  int(max_iterations), int(cg_max_iterations), int(fixed), 1 if trace else 0)
+        out = self._results({"poses": ((N, 4, 4), np.float64), "line_process": ((E,), np.float64)}, on_gpu, pinned=False, synchronize=False)
+        if on_gpu:
+            out["poses"].copy_(P)
+        else:
+            out["poses"][...] = P
+        cap = int(max_iterations) if trace else 0
+        rows = np.zeros((cap, L.HV_POSE_GRAPH_TRACE_STRIDE), np.float64) if trace else None
+        states = np.zeros((cap, N, 4, 4), np.float64) if trace else None
+        n_rows = ctypes.c_int64()
+        res = L.HvPoseGraphResult()
+        with self._ordered(P, Ed, Z, Om, U, out["poses"], out["line_process"]):
+            L.check(self._lib.hv_pose_graph_optimize(self._h, L.ptr(out["poses"]), N, L.ptr(Ed), L.ptr(Z), L.ptr(Om), L.ptr(U), E, ctypes.byref(prm),
+                                                     L.ptr(out["line_process"]), ctypes.byref(res), L.ptr(rows), L.ptr(states), cap,
+                                                     ctypes.byref(n_rows), L.location(P)))
+        lp = out["line_process"]
+        if E == 0:
+            lp = lp[:0]
+        tr = None
+        if trace:
+            tr = [dict({name: kind(r[i]) for i, (name, kind) in enumerate(_POSE_GRAPH_TRACE)}, poses=states[k].copy())
+                  for k, r in enumerate(rows[:n_rows.value])]
+        return PoseGraphResult(out["poses"], lp, lp >= float(edge_prune_threshold), float(res.chi2_initial), float(res.chi2_final),
+                               float(res.lambda_), int(res.iterations), int(res.cg_iterations_total), int(res.edges_kept),
+                               L.HV_POSE_GRAPH_RULES.get(int(res.converged), str(int(res.converged))), bool(res.success), tr)
+
+    def pose_graph_linearise(self, poses, edges, transformations, informations, uncertain=None, line_process_weight=1.0):
+        """One linearisation of optimize_pose_graph at `poses`, for tests (hv_pose_graph_linearise): a dict of numpy arrays r [E,6],
+        chi2 [E], l [E], M [E,6,6], g [E,6] per edge and the gradient b [N,6] with no node fixed.  Operands as optimize_pose_graph."""
+        who = "pose_graph_linearise"
+        P, Ed, Z, Om, U, on_gpu, N, E = self._pose_graph_operands(who, poses, edges, transformations, informations, uncertain)
+        if E < 1:
+            raise ValueError(f"{who}: the graph has no edge")
+        out = {"r": np.zeros((E, 6)), "chi2": np.zeros(E), "l": np.zeros(E), "M": np.zeros((E, 6, 6)), "g": np.zeros((E, 6)), "b": np.zeros((N, 6))}
+        with self._ordered(P, Ed, Z, Om, U):
+            L.check(self._lib.hv_pose_graph_linearise(self._h, L.ptr(P), N, L.ptr(Ed), L.ptr(Z), L.ptr(Om), L.ptr(U), E, float(line_process_weight),
+                                                      L.ptr(out["r"]), L.ptr(out["chi2"]), L.ptr(out["l"]), L.ptr(out["M"]), L.ptr(out["g"]),
+                                                      L.ptr(out["b"]), L.location(P)))
         return out
 
     def remap(self, img, map_x, map_y, linear=False):
