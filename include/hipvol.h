@@ -1014,6 +1014,82 @@ int hv_pose_graph_linearise(hv_volume *v, const double *poses, int64_t n_nodes, 
                             double *r_out, double *chi2_out, double *l_out, double *M_out, double *g_out, double *gradient_out,
                             int32_t loc);
 
+/* ---- oriented binary keypoints and Hamming matching ---------------------------------------------------------
+ * hv_orb_detect: a uint8 image -> keypoints of a FAST-9 segment test on a factor-2 pyramid, each with an orientation bin and a
+ * 256-bit binary descriptor steered to that bin; hv_match_descriptors: brute-force Hamming matching of such descriptors against one
+ * or many sets.  Together with pyslam_amd/features.py they are what the reference's loop closing does by appearance
+ * (pyslam/local_features/feature_matcher.py:76-136,371-396, cpp/hamming/, pyslam/loop_closing/loop_closing.py:266-365).  OpenCV is
+ * not a dependency; compatibility with cv2.ORB descriptors or a DBoW vocabulary is not claimed, and the descriptor pattern is not
+ * the learned ORB pattern: it is generated (F10).  The algorithm is fixed by the rules below, restated in numpy in
+ * tests/orb_reference.py, and the library is held to that restatement bit for bit.  Integer arithmetic only.
+ *   F1 grey         stereo rule 1
+ *   F2 pyramid      level 0 is the grey image [H_0,W_0]; level l+1 is [H_l / 2, W_l / 2] (integer division), each pixel
+ *                   (a + b + c + d + 2) >> 2 of its 2x2 block.  A level with H_l < 33 or W_l < 33 yields nothing, and neither does
+ *                   any level after it
+ *   F3 segment test the 16 ring offsets (dx,dy) start at (0,-3) and go clockwise: (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3)
+ *                   (0,3) (-1,3) (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).  With c the centre and t = threshold, a ring pixel r is
+ *                   brighter iff r - c > t, darker iff c - r > t.  A pixel is a corner iff at least 9 circularly contiguous ring
+ *                   pixels are brighter, or at least 9 are darker.  Candidates only at 16 <= x < W_l - 16, 16 <= y < H_l - 16
+ *   F4 score        V = max(sum over the brighter ring pixels of r - c - t, sum over the darker ones of c - r - t), over all 16 ring
+ *                   pixels; 0 for a non-corner
+ *   F5 suppression  a corner survives iff for each of its 8 neighbours n: V > V_n, or V == V_n and n comes later in row-major order;
+ *                   pixels outside the candidate region count as 0
+ *   F6 selection    cells are 32x32, aligned to the level's origin; each keeps its per_cell survivors of largest V, ties to the smaller
+ *                   row-major index
+ *   F7 order        level ascending, then cell in row-major order, then rank in the cell (V descending, index ascending)
+ *   F8 orientation  over the disc dx^2 + dy^2 <= 225 on the level's grey g: m10 = sum dx g, m01 = sum dy g.  The bin is the SMALLEST
+ *                   b in 0..31 that maximises m10 CX[b] + m01 CY[b] in int64; CX[b] = round(1024 cos(2 pi b / 32)),
+ *                   CY[b] = round(1024 sin(2 pi b / 32)), literal tables (m10 = m01 = 0 takes bin 0)
+ *   F9 smoothing    s(y,x) = the 5x5 box sum of the level's grey centred on the pixel (the border keeps every read inside the image)
+ *   F10 pattern     256 point pairs (A[k], B[k]) with integer coordinates in the disc of radius 13, drawn by this generator:
+ *                   x <- (1103515245 x + 12345) mod 2^31 starting from x = 1 (HV_ORB_PATTERN_SEED); one draw is ((x >> 16) mod 27) - 13;
+ *                   a point is two draws (px, py), both redrawn while px^2 + py^2 > 169; pair k is a point A, then a point B redrawn
+ *                   while B == A, k = 0..255 in the order drawn.  For bin b, with c = cos(2 pi b / 32), s = sin(2 pi b / 32) in
+ *                   float64: A_b[k] = (floor(c ax - s ay + 0.5), floor(s ax + c ay + 0.5)), B_b[k] alike.  tools/gen_orb_pattern.py
+ *                   writes the pattern, its 32 rotations and CX / CY into pyslam_amd/csrc/orb_pattern.h as literal arrays
+ *   F11 bit k       s(p + A_b[k]) < s(p + B_b[k]), stored in byte k >> 3, bit k & 7
+ * image: [height,width] (channels 1) or [height,width,3] uint8.  keypoints_out: int32 [capacity,5] = x, y (at the keypoint's level),
+ * level, score V, orientation bin; the level-0 position of a keypoint is ((x + 0.5) 2^level - 0.5, (y + 0.5) 2^level - 0.5).
+ * descriptors_out: uint8 [capacity,32].  Rows 0 .. *count_out - 1 are written, in the F7 order; capacity (rows of both arrays) must
+ * be at least the bound: per_cell times the 32x32 cells (partial ones included) of every level that yields - the library never
+ * truncates.  count_out is HOST memory.  `loc` as in hv_stereo_sgm for the image and the two arrays; the call waits for the stream
+ * for either loc, because it returns the count.  Works on a volume of any mode and reads nothing of it; scratch (the grey pyramid,
+ * a uint16 score map of the same layout, 8 bytes per cell and 12 per cell and rank) is owned by the handle.
+ * HV_ERR_INVALID before anything is launched or written: a NULL pointer, channels not 1 or 3, height or width < 1 or > 32768,
+ * levels outside 1..8, threshold outside 1..254, per_cell outside 1..16, capacity below the bound. */
+typedef struct hv_feature_params {
+    int32_t levels;    /* 3 */
+    int32_t threshold; /* 20 */
+    int32_t per_cell;  /* 8 */
+} hv_feature_params;
+int hv_orb_detect(hv_volume *v, const uint8_t *image, int32_t height, int32_t width, int32_t channels, const hv_feature_params *params,
+                  int32_t *keypoints_out, uint8_t *descriptors_out, int64_t capacity, int32_t *count_out /* host */, int32_t loc);
+/* hv_match_descriptors: query uint8 [n_query,32] against train uint8 [n_train,32], which segment_offsets (int32 [n_segments + 1],
+ * HOST memory for either loc: non-decreasing, first 0, last n_train) cuts into segments - one keyframe's descriptors each;
+ * n_segments = 1 is plain two-set matching.  Per segment s and query i:
+ *   M1 distance     popcount of the 256-bit xor
+ *   M2 best, second j1 = the smallest train index in the segment attaining the minimum distance d1; d2 = the minimum over the segment
+ *                   without j1 (65535 when the segment has one descriptor); d1 = 65535 and j1 = -1 when the segment is empty
+ *   M3 acceptance   d1 <= max_distance and 100 d1 < ratio_percent d2; ratio_percent 0 skips the second half
+ *   M4 cross-check  (cross_check 1) among all n_query queries, the smallest query index attaining the minimum distance to train j1 is i
+ *   M5 outputs      index int32 [n_segments,n_query]: the global train index j1 of an accepted match, else -1; distance and second
+ *                   uint16 [n_segments,n_query]: d1 and d2, accepted or not; counts int32 [n_segments]: the number accepted.  Any
+ *                   output but index may be NULL
+ * Every result is independent of the order of execution.  `loc` as in hv_stereo_sgm (device descriptors 4-byte aligned).  Scratch
+ * (4 bytes per train descriptor, 4 per segment and query) is owned by the handle.
+ * HV_ERR_INVALID before anything is launched or written: a NULL query, offsets, params or index (train may be NULL when n_train is 0);
+ * n_query outside 1..65536; n_train outside 0..2^24 - 1; n_segments < 1 or n_segments n_query >= 2^27; max_distance outside 0..256;
+ * ratio_percent outside 0..100; cross_check not 0 or 1; offsets that decrease, do not start at 0 or do not end at n_train. */
+typedef struct hv_match_params {
+    int32_t max_distance;  /* 64 */
+    int32_t ratio_percent; /* 80; 0 disables the ratio half of M3 */
+    int32_t cross_check;   /* 1 */
+} hv_match_params;
+int hv_match_descriptors(hv_volume *v, const uint8_t *query, int32_t n_query, const uint8_t *train, int32_t n_train,
+                         const int32_t *segment_offsets /* host */, int32_t n_segments, const hv_match_params *params, int32_t *index_out,
+                         uint16_t *distance_out /* may be NULL */, uint16_t *second_out /* may be NULL */,
+                         int32_t *counts_out /* may be NULL */, int32_t loc);
+
 /* Pruning: give units back to the pool. Fusion only ever claims units - the touch pass claims every unit within sdf_trunc of a
  * sampled depth point, whether or not a voxel of it is then updated, and de-integration leaves the units it emptied allocated - so
  * a long session holds units that carry nothing, and units far from where the camera now is.  This project's own contract (Open3D's

@@ -325,6 +325,14 @@ class HvConsistencyStats(_c.Structure):
     _fields_ = [("valid_pixels", _i64), ("kept_pixels", _i64), ("agree_sum", _i64)]
 
 
+class HvFeatureParams(_c.Structure):
+    _fields_ = [("levels", _i32), ("threshold", _i32), ("per_cell", _i32)]
+
+
+class HvMatchParams(_c.Structure):
+    _fields_ = [("max_distance", _i32), ("ratio_percent", _i32), ("cross_check", _i32)]
+
+
 HV_SPECKLE_I16, HV_SPECKLE_F32 = 0, 1
 
 
@@ -437,6 +445,8 @@ SIGNATURES = {
     "hv_pose_graph_optimize": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _c.POINTER(HvPoseGraphParams), _vp, _c.POINTER(HvPoseGraphResult),
                                       _vp, _vp, _i64, _pi64, _i32]),
     "hv_pose_graph_linearise": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "hv_orb_detect": (_i32, [_vp, _vp, _i32, _i32, _i32, _c.POINTER(HvFeatureParams), _vp, _vp, _i64, _pi32, _i32]),
+    "hv_match_descriptors": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _c.POINTER(HvMatchParams), _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_check_frame": (_i32, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _c.POINTER(HvCheckParams), _vp, _vp, _c.POINTER(HvCheckStats), _i32]),
     "hv_lookup_points": (_i32, [_vp, _vp, _i32, _i64, _c.POINTER(HvLookupParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _c.POINTER(HvLookupStats), _i32]),

@@ -579,6 +579,7 @@ struct hv_volume {
     void *shadow_ring = nullptr;
     int shadow_ring_next = 0;
     // hv_stereo_sgm: [S npx D u16][census left npx u64][census right npx u64][d_left npx i16][right keys npx u32] (hv_stereo.hip)
+    // (also the scratch of hv_orb_detect and hv_match_descriptors, each with its own layout: hv_features.hip)
     void *stereo_buf = nullptr;
     size_t stereo_buf_bytes = 0;
     // hv_filter_speckles: [parent npx i32][size npx i32] (hv_speckle.hip)

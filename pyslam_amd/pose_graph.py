@@ -18,6 +18,16 @@ def _rigid_inverse(T):
     return out
 
 
+def _host(a):
+    return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+
+
+def _torch_cat(parts):
+    import torch
+
+    return torch.cat(parts)
+
+
 class PoseGraph:
     """Nodes and edges as plain arrays: poses [N,4,4] float64, edges [E,2] int32, transformations [E,4,4], informations [E,6,6],
     uncertain [E] bool (properties; the lists behind them grow by add_node / add_edge)."""
@@ -93,11 +103,21 @@ class KeyframeGraphRgbd:
     rgbd_odometry(source j, target i, init=D); a success with fitness >= min_fitness becomes an UNCERTAIN edge (j, i).  -> the new
     edges' indices.
 
+    features: a dict of detect_features parameters ({} for the defaults).  add_frame then also detects and keeps each keyframe's
+    Features - it needs `color` for that, for the depth-only method too - and close_loops_by_appearance(min_gap, min_inliers,
+    inlier_threshold, max_candidates, min_fitness, **match_params) finds loops the pose estimates cannot: for each keyframe j, ONE
+    segmented match_features call against the descriptors of all keyframes i <= j - min_gap; the up to max_candidates keyframes with
+    the most accepted matches (at least 3; ties to the earlier one) are verified with features.backproject and
+    features.rigid_from_matches(threshold = inlier_threshold metres); with min_inliers inliers or more, rgbd_odometry(source j, target
+    i, init = the RANSAC pose), and a success with fitness >= min_fitness becomes an UNCERTAIN edge (j, i), as in close_loops.  Pairs
+    that already share an edge are skipped.  -> the new edges' indices; appearance_log lists every verified pair
+    (j, i, matches, inliers, T_ransac, edge index or None).
+
     The keyframes' images are kept where VisualOdometryRgbd keeps its previous frame: on the volume's GPU with keep_on_device,
     else as host arrays.  volume: context only.  odometry_params: what rgbd_odometry takes."""
 
     def __init__(self, volume, camera, method="hybrid", keyframe_every=1, keep_on_device=True, T_wc0=None, lost_information=1.0,
-                 **odometry_params):
+                 features=None, **odometry_params):
         if method not in METHODS:
             raise ValueError(f"KeyframeGraphRgbd: method must be one of {METHODS}, got {method!r}")
         if int(keyframe_every) < 1:
@@ -115,6 +135,9 @@ class KeyframeGraphRgbd:
         self.T_wc0 = np.eye(4) if T_wc0 is None else np.array(T_wc0, dtype=np.float64).reshape(4, 4)
         self.graph = PoseGraph()
         self.keyframes = []  # (depth, color or None) per node, where rgbd_odometry reads them
+        self.feature_params = None if features is None else dict(features)
+        self.features = []  # Features per node (with feature_params), where match_features reads them
+        self.appearance_log = []
         self.lost_nodes = []
         self.last_result = None
         self.lost = False
@@ -136,10 +159,14 @@ class KeyframeGraphRgbd:
         hybrid = self.method == "hybrid"
         if hybrid and color is None:
             raise ValueError("KeyframeGraphRgbd: the hybrid method needs the colour image")
+        if self.feature_params is not None and color is None:
+            raise ValueError("KeyframeGraphRgbd: features need the colour image")
         self.frames += 1
         if (self.frames - 1) % self.keyframe_every != 0:
             return None
         frame = (self._place(depth), self._place(color) if hybrid else None)
+        if self.feature_params is not None:
+            self.features.append(self.volume.detect_features(frame[1] if hybrid else self._place(color), **self.feature_params))
         if not self.keyframes:
             self.keyframes.append(frame)
             self.lost = False
@@ -179,6 +206,52 @@ class KeyframeGraphRgbd:
             res = self._align(self.keyframes[j], self.keyframes[i], init=D)
             if res.success and res.fitness >= min_fitness:
                 added.append(self.graph.add_edge(j, i, res.transformation, res.information, uncertain=True))
+        return added
+
+    def close_loops_by_appearance(self, min_gap=10, min_inliers=8, inlier_threshold=0.05, max_candidates=3, min_fitness=0.0, **match_params):
+        from .features import backproject, rigid_from_matches
+
+        if self.feature_params is None:
+            raise ValueError("KeyframeGraphRgbd.close_loops_by_appearance: the graph was made without features")
+        if int(min_gap) < 1:
+            raise ValueError(f"KeyframeGraphRgbd.close_loops_by_appearance: min_gap must be at least 1, got {min_gap}")
+        host = _host
+        depth_scale = float(self.odometry_params.get("depth_scale", 1.0))
+        joined = {frozenset(e) for e in self.graph._edges}
+        sizes = [int(f.descriptors.shape[0]) for f in self.features]
+        added = []
+        for j in range(len(self.features)):
+            last = j - int(min_gap)
+            if last < 0 or sizes[j] == 0:
+                continue
+            offsets = np.concatenate([[0], np.cumsum(sizes[:last + 1])]).astype(np.int32)
+            if offsets[-1] == 0:
+                continue
+            parts = [self.features[i].descriptors for i in range(last + 1)]
+            train = np.concatenate(parts) if isinstance(parts[0], np.ndarray) else _torch_cat(parts)
+            res = self.volume.match_features(self.features[j].descriptors, train, segments=offsets, **match_params)
+            counts, index = host(res.counts), host(res.index)
+            ranked = [int(i) for i in np.argsort(-counts, kind="stable")[:int(max_candidates)] if counts[i] >= 3]
+            xy_j, depth_j = host(self.features[j].xy), None
+            for i in ranked:
+                if frozenset((j, i)) in joined:
+                    continue
+                if depth_j is None:
+                    depth_j = host(self.keyframes[j][0])
+                hit = index[i] >= 0
+                P, ok_p = backproject(xy_j[hit], depth_j, self.intrinsic, depth_scale)
+                Q, ok_q = backproject(host(self.features[i].xy)[index[i][hit] - offsets[i]], host(self.keyframes[i][0]), self.intrinsic, depth_scale)
+                ok = ok_p & ok_q
+                T, inliers = rigid_from_matches(P[ok], Q[ok], inlier_threshold)
+                entry = [j, i, int(hit.sum()), int(inliers.sum()), T, None]
+                self.appearance_log.append(entry)
+                if T is None or inliers.sum() < min_inliers:
+                    continue
+                out = self._align(self.keyframes[j], self.keyframes[i], init=T)
+                if out.success and out.fitness >= min_fitness:
+                    entry[5] = self.graph.add_edge(j, i, out.transformation, out.information, uncertain=True)
+                    joined.add(frozenset((j, i)))
+                    added.append(entry[5])
         return added
 
     def optimize(self, **params):

@@ -422,6 +422,38 @@ class SpeckleResult:
         return f"SpeckleResult(shape={tuple(self.image.shape)}, depth={self.depth is not None}, labels={self.labels is not None}, stats={self.stats})"
 
 
+class Features(typing.NamedTuple):
+    """What detect_features returns: keypoints int32 [N,5] = x, y (at the keypoint's level), level, score, orientation bin, in the
+    order of rule F7; xy float32 [N,2], the level-0 position ((x + 0.5) 2^level - 0.5, (y + 0.5) 2^level - 0.5); descriptors uint8
+    [N,32]."""
+
+    keypoints: typing.Any
+    xy: typing.Any
+    descriptors: typing.Any
+
+
+class MatchResult(typing.NamedTuple):
+    """What match_features returns: index int32 [S,Nq], the global train index of each accepted match or -1; distance / second
+    uint16 [S,Nq], the best and second-best Hamming distance in the segment, accepted or not; counts int32 [S], the accepted matches
+    per segment."""
+
+    index: typing.Any
+    distance: typing.Any
+    second: typing.Any
+    counts: typing.Any
+
+
+def feature_capacity(height, width, levels, per_cell):
+    """The rows hv_orb_detect wants its outputs to have: per_cell times the 32x32 cells of every pyramid level that yields."""
+    n = 0
+    for _ in range(int(levels)):
+        if height < 33 or width < 33:
+            break
+        n += ((height + 31) // 32) * ((width + 31) // 32) * int(per_cell)
+        height, width = height // 2, width // 2
+    return n
+
+
 # hv_tsdf_distance_field's cell classes (include/hipvol.h): DIST_SITE is OR-ed onto DIST_FREE or DIST_INSIDE
 DIST_UNKNOWN, DIST_FREE, DIST_INSIDE, DIST_SITE = L.HV_DIST_UNKNOWN, L.HV_DIST_FREE, L.HV_DIST_INSIDE, L.HV_DIST_SITE
 
@@ -962,6 +994,115 @@ class _Volume:
                 L.check(self._lib.hv_stereo_sgm_speckle(self._h, L.ptr(a), L.ptr(b), H, W, channels, ctypes.byref(prm), int(speckle_window_size),
                                                         int(speckle_range), L.ptr(out["disparity"]), L.ptr(out["depth"]), None, L.location(a)))
         return out["disparity"], out["depth"]
+
+    def detect_features(self, image, levels=3, threshold=20, per_cell=8):
+        """Oriented binary keypoints of a uint8 image, [H,W] or [H,W,3] (hv_orb_detect, the rules F1 - F11 in include/hipvol.h):
+        FAST-9 corners on a factor-2 pyramid, non-maximum suppression, the per_cell strongest of every 32x32 cell, an orientation
+        bin and a steered 256-bit descriptor each.  -> Features(keypoints, xy, descriptors).  A numpy array in, numpy arrays out;
+        a torch CUDA tensor on the volume's GPU in, tensors out.  The call waits for the GPU (it returns the count).  Works on a
+        volume of any mode and reads nothing of it."""
+        on_gpu = L.location(image) == L.HV_DEVICE
+        if on_gpu:
+            import torch
+
+            if image.dtype != torch.uint8:
+                raise ValueError("detect_features: the image must be uint8")
+            if image.device != self._device():
+                raise ValueError(f"detect_features: the image lives on {image.device}, the volume on {self._device()}")
+            a = image.contiguous()
+        else:
+            a = image.cpu().numpy() if _is_torch(image) else np.asarray(image)
+            if a.dtype != np.uint8:
+                raise ValueError("detect_features: the image must be uint8")
+            a = np.ascontiguousarray(a)
+        if a.ndim not in (2, 3):
+            raise ValueError(f"detect_features: the image must be [H,W] or [H,W,3], got {tuple(a.shape)}")
+        H, W = int(a.shape[0]), int(a.shape[1])
+        channels = 1 if a.ndim == 2 else int(a.shape[2])
+        # what hv_orb_detect answers with HV_ERR_INVALID, refused here before anything is allocated
+        if channels not in (1, 3):
+            raise ValueError(f"detect_features: images must have 1 or 3 channels, got {channels}")
+        if H < 1 or W < 1 or H > 32768 or W > 32768:
+            raise ValueError(f"detect_features: height and width must be in 1..32768, got {tuple(a.shape)}")
+        for name, value, lo, hi in (("levels", levels, 1, 8), ("threshold", threshold, 1, 254), ("per_cell", per_cell, 1, 16)):
+            if int(value) != value or not lo <= int(value) <= hi:
+                raise ValueError(f"detect_features: {name} must be an integer in {lo}..{hi}, got {value}")
+        bound = feature_capacity(H, W, levels, per_cell)
+        cap = max(bound, 1)
+        prm = L.HvFeatureParams(int(levels), int(threshold), int(per_cell))
+        out = self._results({"keypoints": ((cap, 5), np.int32), "descriptors": ((cap, 32), np.uint8)}, on_gpu, pinned=False, synchronize=False)
+        count = ctypes.c_int32(0)
+        with self._ordered(a, out["keypoints"], out["descriptors"]):
+            L.check(self._lib.hv_orb_detect(self._h, L.ptr(a), H, W, channels, ctypes.byref(prm), L.ptr(out["keypoints"]), L.ptr(out["descriptors"]),
+                                            cap, ctypes.byref(count), L.location(a)))
+        n = int(count.value)
+        kp, desc = out["keypoints"][:n], out["descriptors"][:n]
+        if on_gpu:
+            import torch
+
+            scale = torch.pow(2.0, kp[:, 2:3].clamp(0, 7).to(torch.float32))
+            xy = (kp[:, 0:2].to(torch.float32) + 0.5) * scale - 0.5
+        else:
+            scale = (1 << np.clip(kp[:, 2:3], 0, 7)).astype(np.float32)
+            xy = ((kp[:, 0:2].astype(np.float32) + np.float32(0.5)) * scale - np.float32(0.5)).astype(np.float32)
+        return Features(kp, xy, desc)
+
+    def match_features(self, query, train, segments=None, max_distance=64, ratio=0.8, cross_check=True):
+        """Brute-force Hamming matching of 256-bit descriptors, query uint8 [Nq,32] against train uint8 [Nt,32]
+        (hv_match_descriptors, the rules M1 - M5 in include/hipvol.h).  segments: int32 [S+1] offsets into train (non-decreasing, first
+        0, last Nt), one segment per keyframe - None: one segment, all of train.  A match is accepted when its distance is at most
+        max_distance, 100 d1 < round(100 ratio) d2 (ratio=None: no ratio test) and, with cross_check, the query is the best one of its
+        train descriptor among all queries.  -> MatchResult(index [S,Nq], distance, second, counts [S]).  numpy arrays in, numpy
+        arrays out; torch CUDA tensors on the volume's GPU in, tensors out, queued on the volume's stream.  Works on a volume of any
+        mode and reads nothing of it."""
+        on_gpu = L.location(query) == L.HV_DEVICE
+        if on_gpu != (L.location(train) == L.HV_DEVICE):
+            raise ValueError("match_features: query and train must live in the same place")
+        if on_gpu:
+            import torch
+
+            if query.dtype != torch.uint8 or train.dtype != torch.uint8:
+                raise ValueError("match_features: the descriptors must be uint8")
+            if query.device != self._device() or train.device != self._device():
+                raise ValueError(f"match_features: the descriptors live on {query.device} / {train.device}, the volume on {self._device()}")
+            q, t = query.contiguous(), train.contiguous()
+        else:
+            q, t = (x.cpu().numpy() if _is_torch(x) else np.asarray(x) for x in (query, train))
+            if q.dtype != np.uint8 or t.dtype != np.uint8:
+                raise ValueError("match_features: the descriptors must be uint8")
+            q, t = np.ascontiguousarray(q), np.ascontiguousarray(t)
+        if q.ndim != 2 or t.ndim != 2 or q.shape[1] != 32 or t.shape[1] != 32:
+            raise ValueError(f"match_features: query {tuple(q.shape)} and train {tuple(t.shape)} must be [N,32]")
+        Nq, Nt = int(q.shape[0]), int(t.shape[0])
+        seg = np.array([0, Nt], np.int32) if segments is None else np.ascontiguousarray(
+            segments.cpu().numpy() if _is_torch(segments) else np.asarray(segments))
+        if seg.ndim != 1 or seg.shape[0] < 2 or not np.issubdtype(seg.dtype, np.integer):
+            raise ValueError("match_features: segments must be a 1-D integer array of at least two offsets")
+        seg = seg.astype(np.int64)
+        if seg[0] != 0 or seg[-1] != Nt or (np.diff(seg) < 0).any():
+            raise ValueError(f"match_features: segments must not decrease, start at 0 and end at {Nt}")
+        seg = np.ascontiguousarray(seg, dtype=np.int32)
+        S = int(seg.shape[0]) - 1
+        # what hv_match_descriptors answers with HV_ERR_INVALID, refused here before anything is allocated
+        if not 1 <= Nq <= 65536:
+            raise ValueError(f"match_features: need 1..65536 query descriptors, got {Nq}")
+        if Nt >= 1 << 24:
+            raise ValueError(f"match_features: at most 2^24 - 1 train descriptors, got {Nt}")
+        if S * Nq >= 1 << 27:
+            raise ValueError(f"match_features: segments times queries must stay below 2^27, got {S} x {Nq}")
+        if int(max_distance) != max_distance or not 0 <= int(max_distance) <= 256:
+            raise ValueError(f"match_features: max_distance must be an integer in 0..256, got {max_distance}")
+        ratio_percent = 0 if ratio is None else int(round(100.0 * float(ratio)))
+        if ratio is not None and not 0 <= ratio_percent <= 100:
+            raise ValueError(f"match_features: ratio must be in 0..1 or None, got {ratio}")
+        prm = L.HvMatchParams(int(max_distance), ratio_percent, 1 if cross_check else 0)
+        out = self._results({"index": ((S, Nq), np.int32), "distance": ((S, Nq), np.uint16), "second": ((S, Nq), np.uint16),
+                             "counts": ((S,), np.int32)}, on_gpu, pinned=False, synchronize=False)
+        with self._ordered(q, t, out["index"], out["distance"], out["second"], out["counts"]):
+            L.check(self._lib.hv_match_descriptors(self._h, L.ptr(q), Nq, L.ptr(t) if Nt else None, Nt, L.ptr(seg), S, ctypes.byref(prm),
+                                                   L.ptr(out["index"]), L.ptr(out["distance"]), L.ptr(out["second"]), L.ptr(out["counts"]),
+                                                   L.location(q)))
+        return MatchResult(out["index"], out["distance"], out["second"], out["counts"])
 
     def multiview_sgm(self, ref, sources, views=None, *, intrinsic=None, T_ref=None, T_sources=None, min_depth, max_depth=np.inf,
                       num_planes=128, p1=10, p2=120, uniqueness_ratio=15, min_views=1, paths=8, speckle_window_size=0, speckle_range=1,
