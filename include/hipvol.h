@@ -1014,6 +1014,89 @@ int hv_pose_graph_linearise(hv_volume *v, const double *poses, int64_t n_nodes, 
                             double *r_out, double *chi2_out, double *l_out, double *M_out, double *g_out, double *gradient_out,
                             int32_t loc);
 
+/* ---- bundle adjustment ---------------------------------------------------------------------------------------
+ * hv_bundle_adjust: Levenberg-Marquardt over camera poses AND points against pixel measurements, with the Schur complement on the
+ * points as the inner system.  It takes the place of the reference's bundle_adjustment / global_bundle_adjustment /
+ * local_bundle_adjustment / pose_optimization (pyslam/slam/optimizer_g2o.py, g2o's EdgeSE3ProjectXYZ and EdgeStereoSE3ProjectXYZ with
+ * a Huber kernel); g2o's solver is not reproduced - the algorithm is fixed by the rules below, restated in numpy in
+ * tests/bundle_reference.py.  The volume is context only, as for hv_pose_graph_optimize (stream, scratch, staging; any mode).
+ *   B1 state     cameras [N,16] float64 row-major T_cw (world to camera: the reference's Tcw, this project's extrinsics), in and
+ *                out; points [M,3] float64 in the world, in and out; camera_fixed [N] uint8 (non-zero = does not move) or NULL = none;
+ *                params->fixed_points: no point moves (pose-only, the reference's pose_optimization); one pinhole per call, params->
+ *                fx, fy, cx, cy, bf (bf = baseline times fx; it must be positive even when no observation is stereo).
+ *   B2 observation  obs_index [O,2] int32 {camera, point}; obs_meas [O,4] float64 {u, v, u_r, inv_sigma2}; obs_active [O] uint8 or
+ *                NULL = all.  With q = R p + t, pi(q) = (fx q_x / q_z + cx, fy q_y / q_z + cy): u_r not finite = monocular, r = (u, v)
+ *                - pi(q); else stereo / RGB-D, r = (u, v, u_r) - (pi(q), pi_u(q) - bf / q_z).  Information inv_sigma2 I, so chi2 =
+ *                inv_sigma2 r.r.  Duplicate (camera, point) pairs are legal: each observation is a term of its own.
+ *   B3 kernel    params->huber: rho = chi2 when chi2 <= delta2, else 2 delta sqrt(chi2) - delta2; the weight w = rho' = 1, else
+ *                delta / sqrt(chi2); delta2 = huber_delta2_mono (5.991) / huber_delta2_stereo (7.815).  Without it rho = chi2, w = 1.
+ *                F = sum of rho over the active observations.  The normal equations take w as a constant (g2o's robustified
+ *                information): with J = d r / d q, A_o = w inv_sigma2 J^T J and g_o = w inv_sigma2 J^T r.
+ *   B4 depth     an active observation with q_z <= min_depth (default 1e-6) at the call's FIRST linearisation is switched off for
+ *                the whole call and reported in behind_out [O] uint8.  A trial state in which a still-active observation has q_z <=
+ *                min_depth has F_trial = not-a-number: rho_gain = 0 and the step is rejected.  So every accepted state keeps every
+ *                active observation in front of its camera and F is continuous along the call.
+ *   B5 update    camera T := exp(d) T, exp as in the pose-graph section, (omega, t) order, translation uncoupled: d q / d d =
+ *                W(q) = [-[q]x, I].  Point p := p + d: d q / d d = R.  So an observation adds W^T A W to its camera's block B_i, R^T A R
+ *                to its point's block C_j, E_o = W^T A R between them, W^T g to the camera's gradient and R^T g to the point's.
+ *   B6 outer     the pose graph's Levenberg-Marquardt to the letter: (H + lambda I) d = -b with lambda I on camera and point blocks,
+ *                lambda_0 = lambda_scale max diag H over the free variables; gain ratio (F - F_trial) / (d . (lambda d - b)); Nielsen's
+ *                update; the four stopping rules in the pose graph's order with its codes (HV_POSE_GRAPH_*); its trace row layout.
+ *   B7 inner     H = [[B, E], [E^T, C]], C block-diagonal.  Preconditioned CG from x = 0 on S x = -(b_c - E (C + lambda I)^-1 b_p),
+ *                S = (B + lambda I) - E (C + lambda I)^-1 E^T over the free cameras, never formed: a product is one pass cameras ->
+ *                observations -> points, y_j = (C_j + lambda I)^-1 sum_o E_o^T x, and one pass back, (B_i + lambda I) x_i - sum_o E_o
+ *                y_j.  Then d_j = -(C_j + lambda I)^-1 (b_j + sum_o E_o^T x).  (C_j + lambda I)^-1 is formed once per linearisation
+ *                through its Cholesky factor.  Preconditioner: the Cholesky factor of (B_i + lambda I) - sum_o E_o (C_j + lambda I)^-1
+ *                E_o^T, the sum over the camera's observations one by one.  Stopping as in the pose graph (cg_tolerance,
+ *                cg_max_iterations).  With fixed_points E and the points' gradient are taken as zero in the same code: S is block-
+ *                diagonal and the CG ends after one iteration.  A fixed camera has x = 0 and the unit factor.
+ *   B8 sums      no float atomics.  Two incidence lists are built once per call on the host (the observations of a camera, of a
+ *                point), each sorted by observation index and holding inactive observations too (they add zeros).  A point's sums run
+ *                down its list in order.  A camera's sums: lane l of 64 adds the list's entries l, l + 64, ... in order, the 64 lanes
+ *                are added by xor butterfly (offsets 32, 16, ..., 1).  Sums over observations, cameras and points for F, the dot
+ *                products and the norms: 256 consecutive items by butterfly per 64 and the four sixty-fours in order, then the groups
+ *                in order.  Bitwise reproducible run to run.
+ *   result       as hv_pose_graph_result; chi2_out [O] float64 at loc (may be NULL): chi2 at the final state, 0 for an observation that
+ *                is inactive or behind; behind_out [O] uint8 at loc (may be NULL).  trace as for the pose graph; with params->
+ *                trace_state, trace_cameras [trace_cap,N,16] and trace_points [trace_cap,M,3] (host) receive the state each iteration
+ *                STARTED from.
+ *   errors       HV_ERR_INVALID, all checked on the host before any launch, operands untouched: N or M < 1 with observations
+ *                present; an index out of range; a camera, point, u or v that is not finite; a bottom row not 0 0 0 1; inv_sigma2 not
+ *                positive and finite; no fixed camera while the points are free; fx, fy or bf not positive; parameters out of range.
+ *                Not errors: no observation, or none active (a no-op with success = 1, converged = HV_POSE_GRAPH_RESIDUAL); every camera fixed
+ *                with the points free (points only).
+ * hv_bundle_linearise: one linearisation at the given state, for tests: per observation r [O,3] (third entry 0 for a monocular one),
+ * chi2 [O], w [O], behind [O]; per camera B [N,36] and b [N,6] (no camera fixed); per point C [M,9] and b [M,3]; F.  Outputs in HOST
+ * memory for either loc, any may be NULL; the same kernels, the same checks except the fixed camera. */
+typedef struct hv_bundle_params {
+    double fx, fy, cx, cy, bf;
+    double huber_delta2_mono;   /* default 5.991 */
+    double huber_delta2_stereo; /* default 7.815 */
+    double min_depth;           /* default 1e-6 */
+    double lambda_scale;        /* default 1e-5 */
+    double gradient_tolerance, step_tolerance, decrease_tolerance, residual_tolerance; /* default 1e-6 each */
+    double cg_tolerance;        /* default 1e-8 */
+    int32_t max_iterations;     /* default 100 */
+    int32_t cg_max_iterations;  /* default 100 */
+    int32_t huber;              /* default 1 */
+    int32_t fixed_points;       /* default 0 */
+    int32_t trace_state;
+    int32_t reserved;
+} hv_bundle_params;
+typedef struct hv_bundle_result {
+    double chi2_initial, chi2_final, lambda;
+    int32_t iterations, cg_iterations_total, converged, success;
+} hv_bundle_result;
+void hv_bundle_default_params(hv_bundle_params *params);
+int hv_bundle_adjust(hv_volume *v, double *cameras, int64_t n_cameras, double *points, int64_t n_points, const uint8_t *camera_fixed,
+                     const int32_t *obs_index, const double *obs_meas, const uint8_t *obs_active, int64_t n_obs,
+                     const hv_bundle_params *params, double *chi2_out, uint8_t *behind_out, hv_bundle_result *result, double *trace,
+                     double *trace_cameras, double *trace_points, int64_t trace_cap, int64_t *trace_rows, int32_t loc);
+int hv_bundle_linearise(hv_volume *v, const double *cameras, int64_t n_cameras, const double *points, int64_t n_points,
+                        const int32_t *obs_index, const double *obs_meas, const uint8_t *obs_active, int64_t n_obs,
+                        const hv_bundle_params *params, double *r_out, double *chi2_out, double *w_out, uint8_t *behind_out, double *B_out,
+                        double *bc_out, double *C_out, double *bp_out, double *F_out, int32_t loc);
+
 /* ---- oriented binary keypoints and Hamming matching ---------------------------------------------------------
  * hv_orb_detect: a uint8 image -> keypoints of a FAST-9 segment test on a factor-2 pyramid, each with an orientation bin and a
  * 256-bit binary descriptor steered to that bin; hv_match_descriptors: brute-force Hamming matching of such descriptors against one

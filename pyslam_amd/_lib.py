@@ -116,6 +116,43 @@ class HvPoseGraphResult(_c.Structure):
     ]
 
 
+class HvBundleParams(_c.Structure):
+    _fields_ = [
+        ("fx", _f64),
+        ("fy", _f64),
+        ("cx", _f64),
+        ("cy", _f64),
+        ("bf", _f64),
+        ("huber_delta2_mono", _f64),
+        ("huber_delta2_stereo", _f64),
+        ("min_depth", _f64),
+        ("lambda_scale", _f64),
+        ("gradient_tolerance", _f64),
+        ("step_tolerance", _f64),
+        ("decrease_tolerance", _f64),
+        ("residual_tolerance", _f64),
+        ("cg_tolerance", _f64),
+        ("max_iterations", _i32),
+        ("cg_max_iterations", _i32),
+        ("huber", _i32),
+        ("fixed_points", _i32),
+        ("trace_state", _i32),
+        ("reserved", _i32),
+    ]
+
+
+class HvBundleResult(_c.Structure):
+    _fields_ = [
+        ("chi2_initial", _f64),
+        ("chi2_final", _f64),
+        ("lambda_", _f64),
+        ("iterations", _i32),
+        ("cg_iterations_total", _i32),
+        ("converged", _i32),
+        ("success", _i32),
+    ]
+
+
 class HvOdometryParams(_c.Structure):
     _fields_ = [
         ("depth_scale", _f64),
@@ -445,6 +482,11 @@ SIGNATURES = {
     "hv_pose_graph_optimize": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _c.POINTER(HvPoseGraphParams), _vp, _c.POINTER(HvPoseGraphResult),
                                       _vp, _vp, _i64, _pi64, _i32]),
     "hv_pose_graph_linearise": (_i32, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "hv_bundle_default_params": (None, [_c.POINTER(HvBundleParams)]),
+    "hv_bundle_adjust": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _c.POINTER(HvBundleParams), _vp, _vp, _c.POINTER(HvBundleResult),
+                                _vp, _vp, _vp, _i64, _pi64, _i32]),
+    "hv_bundle_linearise": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _c.POINTER(HvBundleParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                   _vp, _i32]),
     "hv_orb_detect": (_i32, [_vp, _vp, _i32, _i32, _i32, _c.POINTER(HvFeatureParams), _vp, _vp, _i64, _pi32, _i32]),
     "hv_match_descriptors": (_i32, [_vp, _vp, _i32, _vp, _i32, _vp, _i32, _c.POINTER(HvMatchParams), _vp, _vp, _vp, _vp, _i32]),
     "hv_tsdf_sample_points": (_i32, [_vp, _vp, _i32, _i64, _f64, _vp, _vp, _vp, _vp, _vp, _i32]),

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libpyslam_hipvol.so")
-SOURCES = ["hv_core.hip", "hv_stage.hip", "hv_tsdf.hip", "hv_voxel_grid.hip", "hv_semantic.hip", "hv_semantic_ops.hip", "hv_extract.hip", "hv_prep.hip", "hv_halo.hip", "hv_raycast.hip", "hv_track.hip", "hv_deintegrate.hip", "hv_prune.hip", "hv_merge.hip", "hv_register.hip", "hv_pack.hip", "hv_grid_pack.hip", "hv_sample.hip", "hv_distance.hip", "hv_components.hip", "hv_lookup.hip", "hv_stereo.hip", "hv_speckle.hip", "hv_mvs.hip", "hv_depth_consistency.hip", "hv_pose_graph.hip", "hv_features.hip"]
+SOURCES = ["hv_core.hip", "hv_stage.hip", "hv_tsdf.hip", "hv_voxel_grid.hip", "hv_semantic.hip", "hv_semantic_ops.hip", "hv_extract.hip", "hv_prep.hip", "hv_halo.hip", "hv_raycast.hip", "hv_track.hip", "hv_deintegrate.hip", "hv_prune.hip", "hv_merge.hip", "hv_register.hip", "hv_pack.hip", "hv_grid_pack.hip", "hv_sample.hip", "hv_distance.hip", "hv_components.hip", "hv_lookup.hip", "hv_stereo.hip", "hv_speckle.hip", "hv_mvs.hip", "hv_depth_consistency.hip", "hv_pose_graph.hip", "hv_features.hip", "hv_bundle.hip"]
 INCLUDE = os.path.join(ROOT, "include")
 
 

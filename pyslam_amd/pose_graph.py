@@ -257,5 +257,52 @@ class KeyframeGraphRgbd:
     def optimize(self, **params):
         return self.graph.optimize(self.volume, **params)
 
+    def feature_matches(self, **match_params):
+        """The accepted matches of every keyframe against its predecessors along the graph's edges: for each keyframe j ONE segmented
+        match_features call against the descriptors of the keyframes i < j it shares an edge with.  -> [(i, j, matches [K,2] of
+        (keypoint in i, keypoint in j))] in the order (j, i)."""
+        if self.feature_params is None:
+            raise ValueError("KeyframeGraphRgbd.feature_matches: the graph was made without features")
+        sizes = [int(f.descriptors.shape[0]) for f in self.features]
+        before = [sorted({min(e) for e in self.graph._edges if max(e) == j}) for j in range(len(self.features))]
+        pairs = []
+        for j, prev in enumerate(before):
+            prev = [i for i in prev if sizes[i] > 0]
+            if not prev or sizes[j] == 0:
+                continue
+            offsets = np.concatenate([[0], np.cumsum([sizes[i] for i in prev])]).astype(np.int32)
+            parts = [self.features[i].descriptors for i in prev]
+            train = np.concatenate(parts) if isinstance(parts[0], np.ndarray) else _torch_cat(parts)
+            index = _host(self.volume.match_features(self.features[j].descriptors, train, segments=offsets, **match_params).index)
+            for s, i in enumerate(prev):
+                hit = np.flatnonzero(index[s] >= 0)
+                pairs.append((i, j, np.stack([index[s][hit] - offsets[s], hit], -1).astype(np.int64)))
+        return pairs
+
+    def bundle_adjust(self, bf, min_length=2, rounds=10, match_params=None, **params):
+        """Bundle adjustment of the keyframe poses and the points their features saw (bundle.bundle_adjust_two_phase over
+        _Volume.bundle_adjust, node 0 fixed): feature_matches(**match_params), bundle.build_tracks(min_length), bundle.initial_points
+        from the keyframes' depth, then the two phases of `rounds` outer iterations.  bf = baseline x fx of the depth the RGB-D
+        observations are turned into (the reference's Camera.bf).  On success the poses go back into the graph, so that extrinsics()
+        feeds reintegrate_batch unchanged.  -> (BundleResult, mean chi2 over the observations of the second phase); bundle_log keeps
+        the tracks, the observation arrays and the active flags."""
+        from . import bundle
+
+        pairs = self.feature_matches(**(match_params or {}))
+        tracks = bundle.build_tracks(pairs, min_length)
+        depth_scale = float(self.odometry_params.get("depth_scale", 1.0))
+        cameras = self.graph.extrinsics()
+        points, index, meas, s2, keep = bundle.initial_points(tracks, self.features, [k[0] for k in self.keyframes], cameras, self.intrinsic, bf,
+                                                              depth_scale)
+        fixed = np.zeros(len(cameras), bool)
+        fixed[0] = True
+        result, active, mean = bundle.bundle_adjust_two_phase(self.volume, cameras, points, index, meas, self.intrinsic, bf, inv_sigma2=s2,
+                                                              camera_fixed=fixed, rounds=rounds, **params)
+        self.bundle_log = dict(tracks=[t for t, k in zip(tracks, keep) if k], points=points, index=index, measurements=meas, inv_sigma2=s2,
+                               active=_host(active), cameras=cameras)
+        if result.success:
+            self.graph._poses = [np.array(T, np.float64) for T in _rigid_inverse(_host(result.cameras))]
+        return result, mean
+
     def extrinsics(self):
         return self.graph.extrinsics()

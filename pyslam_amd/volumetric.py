@@ -191,6 +191,22 @@ _POSE_GRAPH_TRACE = (("iteration", int), ("lambda_", float), ("chi2", float), ("
                      ("converged", int))
 
 
+class BundleResult:
+    """What bundle_adjust returns (hv_bundle_result and the call's arrays): cameras [N,4,4] float64 T_cw and points [M,3] float64 after
+    the adjustment; chi2 [O] float64, every observation's chi2 at the final state (0 where inactive or behind); behind [O] bool, the
+    observations switched off at the first linearisation because their point lay behind the camera; inlier [O] bool = active, not
+    behind and chi2 <= the gate (huber_delta2_mono / huber_delta2_stereo by the kind of the observation); chi2_initial / chi2_final,
+    the objective at the first linearisation and at the final state; lambda_; iterations (outer), cg_iterations_total; converged
+    ("gradient", "step", "decrease", "residual" or "max_iterations"); success; trace = None, or one dict per outer iteration (the
+    fields of a pose-graph trace row, and cameras [N,4,4] / points [M,3] - the state the iteration started from)."""
+    __slots__ = ("cameras", "points", "chi2", "behind", "inlier", "chi2_initial", "chi2_final", "lambda_", "iterations", "cg_iterations_total",
+                 "converged", "success", "trace")
+
+    def __init__(self, *values):
+        for name, value in zip(self.__slots__, values):
+            setattr(self, name, value)
+
+
 class OdometryResult:
     """What ScalableTSDFVolume.track_frame_to_model and rgbd_odometry return (the fields of Open3D's tensor odometry result, plus the
     rest of hv_track_result / hv_odometry_result):  transformation 4x4 float64, T_cw after tracking, T_target_source after
@@ -1481,6 +1497,146 @@ class _Volume:
             L.check(self._lib.hv_pose_graph_linearise(self._h, L.ptr(P), N, L.ptr(Ed), L.ptr(Z), L.ptr(Om), L.ptr(U), E, float(line_process_weight),
                                                       L.ptr(out["r"]), L.ptr(out["chi2"]), L.ptr(out["l"]), L.ptr(out["M"]), L.ptr(out["g"]),
                                                       L.ptr(out["b"]), L.location(P)))
+        return out
+
+    def _bundle_operands(self, who, cameras, points, observations, measurements, inv_sigma2, active, camera_fixed):
+        """The problem's arrays where the call reads them: all on the volume's GPU when `cameras` is a CUDA tensor, else all on the
+        host; float64 / int32 / uint8, C-contiguous.  -> (cameras [N,4,4], points [M,3], index [O,2], meas [O,4], active [O] or None,
+        fixed [N] or None, on_gpu, N, M, O)"""
+        on_gpu = L.location(cameras) == L.HV_DEVICE
+        if on_gpu:
+            import torch
+
+            dev = self._device()
+            if cameras.device != dev:
+                raise ValueError(f"{who}: cameras live on {cameras.device}, the volume on {dev}")
+
+            def place(a, dtype):
+                t = a if _is_torch(a) else torch.as_tensor(np.asarray(a))
+                return t.to(device=dev, dtype=getattr(torch, dtype)).contiguous()
+        else:
+            def place(a, dtype):
+                return np.ascontiguousarray(a.cpu().numpy() if _is_torch(a) else np.asarray(a), dtype=dtype)
+
+        T = place(cameras, "float64")
+        if T.ndim != 3 or tuple(T.shape[1:]) != (4, 4):
+            raise ValueError(f"{who}: cameras must be [N,4,4], got {tuple(T.shape)}")
+        X = place(points, "float64")
+        if X.ndim != 2 or X.shape[1] != 3:
+            raise ValueError(f"{who}: points must be [M,3], got {tuple(X.shape)}")
+        N, M = int(T.shape[0]), int(X.shape[0])
+        idx = place(observations, "int32").reshape(-1, 2)
+        O = int(idx.shape[0])
+        Z = place(measurements, "float64")
+        if Z.ndim != 2 or int(Z.shape[0]) != O or int(Z.shape[1]) not in (2, 3):
+            raise ValueError(f"{who}: measurements must be [{O},2] (u, v) or [{O},3] (u, v, u_r) for {O} observations, got {tuple(Z.shape)}")
+        if np.ndim(inv_sigma2) == 0:
+            inv_sigma2 = np.full(O, float(inv_sigma2))
+        s2 = place(inv_sigma2, "float64")
+        if tuple(s2.shape) != (O,):
+            raise ValueError(f"{who}: inv_sigma2 must be a number or [{O}], got {tuple(s2.shape)}")
+        if on_gpu:
+            meas = torch.full((O, 4), float("nan"), dtype=torch.float64, device=dev)
+        else:
+            meas = np.full((O, 4), np.nan)
+        meas[:, :int(Z.shape[1])] = Z
+        meas[:, 3] = s2
+
+        def flags(a, n, name):
+            if a is None:
+                return None
+            f = place(a, "bool")
+            f = f.to(torch.uint8) if on_gpu else f.astype(np.uint8)
+            if tuple(f.shape) != (n,):
+                raise ValueError(f"{who}: {name} must be [{n}], got {tuple(f.shape)}")
+            return f
+
+        return T, X, idx, meas, flags(active, O, "active"), flags(camera_fixed, N, "camera_fixed"), on_gpu, N, M, O
+
+    @staticmethod
+    def _bundle_params(who, intrinsic, bf, huber, fixed_points, trace, kw):
+        prm = L.HvBundleParams()
+        names = [n for n, _ in L.HvBundleParams._fields_[5:16]]
+        bad = sorted(set(kw) - set(names))
+        if bad:
+            raise TypeError(f"{who}: unknown parameter {bad[0]} (known: {', '.join(names)})")
+        values = dict(huber_delta2_mono=5.991, huber_delta2_stereo=7.815, min_depth=1e-6, lambda_scale=1e-5, gradient_tolerance=1e-6,
+                      step_tolerance=1e-6, decrease_tolerance=1e-6, residual_tolerance=1e-6, cg_tolerance=1e-8, max_iterations=100,
+                      cg_max_iterations=100)
+        values.update(kw)
+        if not (1 <= int(values["max_iterations"]) <= 10000 and 1 <= int(values["cg_max_iterations"]) <= 10000):
+            raise ValueError(f"{who}: max_iterations and cg_max_iterations must be in 1..10000")
+        if not (np.isfinite(bf) and bf > 0):
+            raise ValueError(f"{who}: bf must be positive and finite, got {bf}")
+        prm.fx, prm.fy, prm.cx, prm.cy, prm.bf = float(intrinsic.fx), float(intrinsic.fy), float(intrinsic.cx), float(intrinsic.cy), float(bf)
+        for name, value in values.items():
+            setattr(prm, name, int(value) if name.endswith("iterations") else float(value))
+        prm.huber, prm.fixed_points, prm.trace_state = int(bool(huber)), int(bool(fixed_points)), int(bool(trace))
+        return prm
+
+    def bundle_adjust(self, cameras, points, observations, measurements, intrinsic, bf=1.0, inv_sigma2=1.0, active=None, camera_fixed=None,
+                      fixed_points=False, huber=True, trace=False, **params):
+        """Bundle adjustment on the GPU (hv_bundle_adjust; the place of the reference's bundle_adjustment, local_bundle_adjustment
+        and, with fixed_points, pose_optimization): -> BundleResult.  cameras [N,4,4] T_cw (world to camera, this project's
+        extrinsics); points [M,3] in the world; observations [O,2] {camera, point}; measurements [O,2] (u, v) or [O,3] (u, v, u_r),
+        a u_r that is not finite marking a monocular observation; intrinsic: fx, fy, cx, cy of the one pinhole; bf = baseline x
+        fx; inv_sigma2: a number or [O], 4^-level for a keypoint of this project's pyramid; active [O] bool (None: all);
+        camera_fixed [N] bool (None: none; with free points one camera must be fixed); huber: the robust kernel.  **params: the
+        remaining fields of hv_bundle_params (max_iterations, cg_tolerance, huber_delta2_mono, ...).  The operands are not changed.
+        numpy or torch on either device: with `cameras` a CUDA tensor on the volume's GPU everything is read there and the arrays
+        come back as tensors ordered on torch's current stream; else numpy arrays.  The volume is context only (any mode): the map
+        is neither read nor changed.  trace=True: one dict per outer iteration with the state it started from."""
+        who = "bundle_adjust"
+        T, X, idx, meas, act, fix, on_gpu, N, M, O = self._bundle_operands(who, cameras, points, observations, measurements, inv_sigma2, active,
+                                                                           camera_fixed)
+        prm = self._bundle_params(who, intrinsic, bf, huber, fixed_points, trace, params)
+        out = self._results({"cameras": ((N, 4, 4), np.float64), "points": ((M, 3), np.float64), "chi2": ((O,), np.float64),
+                             "behind": ((O,), np.uint8)}, on_gpu, pinned=False, synchronize=False)
+        if on_gpu:
+            out["cameras"].copy_(T), out["points"].copy_(X), out["chi2"].zero_(), out["behind"].zero_()
+        else:
+            out["cameras"][...], out["points"][...], out["chi2"][...], out["behind"][...] = T, X, 0.0, 0
+        cap = int(prm.max_iterations) if trace else 0
+        rows = np.zeros((cap, L.HV_POSE_GRAPH_TRACE_STRIDE), np.float64) if trace else None
+        tc, tp = (np.zeros((cap, N, 4, 4), np.float64), np.zeros((cap, M, 3), np.float64)) if trace else (None, None)
+        n_rows = ctypes.c_int64()
+        res = L.HvBundleResult()
+        with self._ordered(T, X, idx, meas, act, fix, out["cameras"], out["points"], out["chi2"], out["behind"]):
+            L.check(self._lib.hv_bundle_adjust(self._h, L.ptr(out["cameras"]), N, L.ptr(out["points"]), M, L.ptr(fix), L.ptr(idx), L.ptr(meas),
+                                               L.ptr(act), O, ctypes.byref(prm), L.ptr(out["chi2"]), L.ptr(out["behind"]), ctypes.byref(res),
+                                               L.ptr(rows), L.ptr(tc), L.ptr(tp), cap, ctypes.byref(n_rows), L.location(T)))
+        chi2, behind = out["chi2"], out["behind"] != 0
+        stereo = meas[:, 2] == meas[:, 2]
+        stereo = stereo & (abs(meas[:, 2]) != float("inf"))
+        gate = stereo * float(prm.huber_delta2_stereo) + ~stereo * float(prm.huber_delta2_mono)
+        inlier = (chi2 <= gate) & ~behind
+        if act is not None:
+            inlier = inlier & (act != 0)
+        tr = None
+        if trace:
+            tr = [dict({name: kind(r[i]) for i, (name, kind) in enumerate(_POSE_GRAPH_TRACE)}, cameras=tc[k].copy(), points=tp[k].copy())
+                  for k, r in enumerate(rows[:n_rows.value])]
+        return BundleResult(out["cameras"], out["points"], chi2, behind, inlier, float(res.chi2_initial), float(res.chi2_final), float(res.lambda_),
+                            int(res.iterations), int(res.cg_iterations_total), L.HV_POSE_GRAPH_RULES.get(int(res.converged), str(int(res.converged))),
+                            bool(res.success), tr)
+
+    def bundle_linearise(self, cameras, points, observations, measurements, intrinsic, bf=1.0, inv_sigma2=1.0, active=None, huber=True, **params):
+        """One linearisation of bundle_adjust at the given state, for tests (hv_bundle_linearise): a dict of numpy arrays r [O,3],
+        chi2 [O], w [O], behind [O] bool per observation, B [N,6,6] and bc [N,6] per camera (none fixed), C [M,3,3] and bp [M,3] per
+        point, and F.  Operands as bundle_adjust."""
+        who = "bundle_linearise"
+        T, X, idx, meas, act, _, on_gpu, N, M, O = self._bundle_operands(who, cameras, points, observations, measurements, inv_sigma2, active, None)
+        if min(N, M, O) < 1:
+            raise ValueError(f"{who}: needs a camera, a point and an observation, got {N}, {M}, {O}")
+        prm = self._bundle_params(who, intrinsic, bf, huber, False, False, params)
+        out = {"r": np.zeros((O, 3)), "chi2": np.zeros(O), "w": np.zeros(O), "behind": np.zeros(O, np.uint8), "B": np.zeros((N, 6, 6)),
+               "bc": np.zeros((N, 6)), "C": np.zeros((M, 3, 3)), "bp": np.zeros((M, 3)), "F": np.zeros(1)}
+        with self._ordered(T, X, idx, meas, act):
+            L.check(self._lib.hv_bundle_linearise(self._h, L.ptr(T), N, L.ptr(X), M, L.ptr(idx), L.ptr(meas), L.ptr(act), O, ctypes.byref(prm),
+                                                  L.ptr(out["r"]), L.ptr(out["chi2"]), L.ptr(out["w"]), L.ptr(out["behind"]), L.ptr(out["B"]),
+                                                  L.ptr(out["bc"]), L.ptr(out["C"]), L.ptr(out["bp"]), L.ptr(out["F"]), L.location(T)))
+        out["behind"] = out["behind"] != 0
+        out["F"] = float(out["F"][0])
         return out
 
     def remap(self, img, map_x, map_y, linear=False):
